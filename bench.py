@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the dtsim hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (what a caller of the
+timed path reads back) as DIR/<name>.npy, float32 / float64, at most DUMP_LIMIT bytes in all.  The inputs are fixed
+by the arguments (seeded actions and spawn pool), so two builds can be compared output for output.
 
 Workload (config.workload): BASELINE.json configs[2] -- Duckietown-small_loop-v0, 4096
 batched envs PER GPU, 640x480 RGB raster + fisheye distortion, domain_rand off, random
@@ -34,6 +38,36 @@ import numpy as np  # noqa: E402
 PEAK_HBM = 8.0e12          # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
 W, H = 640, 480
 FRAME_BYTES = W * H * 3    # algorithmic bytes per env-step: the frame, written once
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes written in all
+DUMP_FRAMES = 8            # --dump-outputs: envs whose whole frame is written (a fixed, seeded sample)
+DUMP_ENVS = 65536          # --dump-outputs: per-env arrays of larger batches are a fixed, seeded sample of this many envs
+
+
+def _dump_rows(n: int, k: int) -> np.ndarray:
+    """Fixed, seeded sample of k of n rows (all of them when n <= k), sorted."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+
+
+def _write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <path>/<name>.npy (float64 stays float64, everything else becomes float32)."""
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT} byte budget")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def _sim_outputs(sim, rows) -> dict:
+    """The per-env results a caller reads back after a step (pose, reward, done, episode bookkeeping), rows `rows`."""
+    from dtsim import _ffi
+    fields = {"pos": _ffi.FIELD_POS, "angle": _ffi.FIELD_ANGLE, "reward": _ffi.FIELD_REWARD, "done": _ffi.FIELD_DONE,
+              "done_code": _ffi.FIELD_DONE_CODE, "step_count": _ffi.FIELD_STEP_COUNT, "episode": _ffi.FIELD_EPISODE,
+              "speed": _ffi.FIELD_SPEED, "lane": _ffi.FIELD_LANE, "in_lane": _ffi.FIELD_IN_LANE, "tile": _ffi.FIELD_TILE}
+    return {k: sim.read(f)[rows] for k, f in fields.items()}
 
 
 def _oracle_env_steps(job):
@@ -207,6 +241,9 @@ def main_c2(args):
     sim.sync()
     dt = time.perf_counter() - t0
     n_s, ms_s = sim.profile_read(_ffi.KERNEL_STEP)
+    if args.dump_outputs:
+        rows = _dump_rows(N, DUMP_ENVS)
+        _write_outputs(args.dump_outputs, dict(_sim_outputs(sim, rows), envs=rows.astype(np.float64)))
     # state actually touched per env-step on a map without dynamic objects: 31 f64 arrays (pose, SE(2) state,
     # velocities, 2x5 delay ring, gains, wheel_dist, timestamp, speed, reward, lane[4], prox, wheels[2]),
     # 4 int32 (ring head, step count, tile i/j), 3 uint8 (done, code, in_lane); read + written once per step,
@@ -246,11 +283,13 @@ def main_c1(args):
             env.reset()
     t0 = time.perf_counter()
     for _ in range(K):
-        obs, _, d, _ = env.step(rng.uniform(-1, 1, 2))
+        obs, r, d, _ = env.step(rng.uniform(-1, 1, 2))
         if d:
             env.reset()
     dt = time.perf_counter() - t0
     assert obs.shape == (84, 84, 3)
+    if args.dump_outputs and K > 0:
+        _write_outputs(args.dump_outputs, {"obs": obs, "reward": np.float64(r), "done": np.float32(d)})
     cpu = None
     if args.cpu_steps > 0:
         from dtsim import assets
@@ -293,7 +332,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--cpu-steps", type=int, default=32, help="oracle env-steps for cpu_baseline (about 15 s on one host core)")
-    ap.add_argument("--windows", type=int, default=5, help="timed regions of --steps steps each; value = the median one")
+    ap.add_argument("--windows", type=int, default=1, help="the --steps timed steps are split into this many consecutive regions; "
+                                                           "value = the median one's time per step (each region pays one queue fill and drain)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL frame all-gather measurement")
     ap.add_argument("--gather-timeout", type=float, default=120.0, help="give up on the frame exchange after this many seconds")
     ap.add_argument("--config", default="c3", choices=["c3", "c1", "c2", "c4", "c5", "c3dr"],
@@ -359,7 +401,7 @@ def main():
 
     dev = torch.device("cuda", local_rank)
     # SURVEY 8(d) input protocol: np.random.default_rng(1234).uniform(-1, 1, (T, N_total, 2)) as float32, uploaded once; a rank takes
-    # the columns of ITS global env range (the slice ShardedSimulator.local_actions makes); T = warm-up + K, cycled over the windows
+    # the columns of ITS global env range (the slice ShardedSimulator.local_actions makes); T = warm-up + K, one row per step
     acts_all = np.random.default_rng(1234).uniform(-1.0, 1.0, (K + Wm, world * N, 2)).astype(np.float32)
     acts = torch.from_numpy(np.ascontiguousarray(acts_all[:, rank * N:(rank + 1) * N, :])).to(dev)   # resident in HBM
     del acts_all
@@ -380,15 +422,20 @@ def main():
     sync_all()
     sim.profile_read(_ffi.KERNEL_RENDER)
     sim.profile_read(_ffi.KERNEL_STEP)
-    # The timed region: EXACTLY K steps between two (barrier + synchronize) brackets, MAX over ranks.  It is repeated
-    # args.windows times (each window is such a region of K steps; the box-to-box and run-to-run spread of a 40 ms region is
-    # the size of most deltas this repo reports) and `value` comes from the MEDIAN window; all of them are in `windows_ms`.
+    # The timed steps: EXACTLY K, each with its own action row (Wm .. Wm + K - 1), split into up to args.windows consecutive
+    # regions between two (barrier + synchronize) brackets, MAX over ranks (the box-to-box and run-to-run spread of one region
+    # is the size of most deltas this repo reports): `value` and `ms_per_step` come from the region with the MEDIAN time per
+    # step; all of them are in `windows_ms`.
+    n_win = max(1, min(args.windows, K))
+    sizes = [K // n_win + (1 if i < K % n_win else 0) for i in range(n_win)]
     win = []
-    for wi in range(max(1, args.windows)):
+    start = Wm
+    for size in sizes:
         sync_all()
         t0 = time.perf_counter()
-        for t in range(Wm, Wm + K):
+        for t in range(start, start + size):
             one_step(t)
+        start += size
         sim.sync()
         torch.cuda.synchronize()
         tw = torch.tensor([time.perf_counter() - t0], device="cpu" if one_gpu else dev, dtype=torch.float64)
@@ -398,8 +445,19 @@ def main():
         win.append(float(tw.item()))
     n_r, ms_r = sim.profile_read(_ffi.KERNEL_RENDER)
     n_s, ms_s = sim.profile_read(_ffi.KERNEL_STEP)
-    win_sorted = sorted(win)
-    t_local = win_sorted[len(win_sorted) // 2]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for a caller: the frames of a fixed sample of envs, a checksum of every env's frame
+        # (sum of its bytes), and the per-env results of the step
+        frames = torch.as_tensor(sim.frames_device(), device=dev)
+        rows = _dump_rows(N, DUMP_FRAMES)
+        fsum = torch.cat([frames[e:e + 256].sum(dim=(1, 2, 3), dtype=torch.int64) for e in range(0, N, 256)])
+        outs = {"frames": frames[torch.from_numpy(rows).to(dev)].cpu().numpy(), "frames_envs": rows.astype(np.float64),
+                "frame_sum": fsum.cpu().numpy().astype(np.float64)}
+        del frames
+        env_rows = _dump_rows(N, DUMP_ENVS)
+        _write_outputs(args.dump_outputs, dict(outs, envs=env_rows.astype(np.float64), **_sim_outputs(sim, env_rows)))
+    per_step = sorted(w / s for w, s in zip(win, sizes))
+    t_local = K * per_step[len(per_step) // 2]      # K steps at the median region's time per step
     # run-to-run spread of the render pass: a separate short series AFTER the timed region, one HIP-event reading per launch
     per_launch = []
     for t in range(min(K, 16)):
@@ -479,9 +537,11 @@ def main():
             "steps": K,
             "warmup": Wm,
             "ms_per_step": 1e3 * t_max / K,
-            "windows_ms": {"min": 1e3 * win_sorted[0], "median": 1e3 * t_max, "max": 1e3 * win_sorted[-1], "n": len(win), "all": [1e3 * w for w in win],
-                           "note": f"{len(win)} timed regions of exactly {K} steps each (barrier + synchronize on both sides, max over ranks); "
-                                   "value and ms_per_step are those of the median region"},
+            "windows_ms": {"min": 1e3 * per_step[0], "median": 1e3 * per_step[len(per_step) // 2], "max": 1e3 * per_step[-1], "n": len(win),
+                           "steps": sizes, "all": [1e3 * w for w in win],
+                           "note": f"the {K} timed steps as {len(win)} consecutive regions (barrier + synchronize on both sides, max over ranks); "
+                                   "min / median / max are ms per step of a region, `all` the ms of each region; value and ms_per_step are "
+                                   "those of the median region"},
             "actions": "np.random.default_rng(1234).uniform(-1, 1, (warmup + steps, n_gpus * envs, 2)).astype(float32), uploaded once; rank r takes columns [r*envs, (r+1)*envs)",
             "higher_is_better": True,
             "scaling": "weak",

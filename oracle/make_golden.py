@@ -16,6 +16,8 @@ travel to the GPU box where /root/reference does not exist:
   ref_kat.json           SURVEY Appendix A known-answer vectors, re-derived from the reference
   ref_distortion.npz     Distortion._invert_map/_fill_holes (reference code) applied to the
                          restated OpenCV rectify maps: rounded source pixel per output pixel
+  ref_pins.npz           the reference's answers to the queries of tests/test_oracle_vs_reference.py
+                         (with their inputs); alone: python -m oracle.make_golden pins
 Inputs (maps, stand-in mesh extents) come from gym-duckietown_amd/dtsim/assets.py.
 """
 from __future__ import annotations
@@ -221,8 +223,169 @@ def main():
             om[f"{tag}_{k}"] = r[k]
         om[f"{tag}_textures"] = np.array(["" if t is None else os.path.basename(t) for t in r["textures"]])
     np.savez_compressed(os.path.join(OUT, "ref_objmesh.npz"), **om)
+    pins()
     print("golden fixtures written to", OUT)
 
 
+# the paths and object names tests/test_oracle_vs_reference.py::test_segmentation_rules_equal_the_reference asks about
+SEGMENT_PATHS = ["tiles-processed/photos/straight/texture.jpg", "tiles-processed/photos/curve_left/texture.jpg",
+                 "tiles-processed/photos/curve_right/texture.jpg", "tiles-processed/photos/3way_left/texture.jpg",
+                 "tiles-processed/photos/4way/texture.jpg", "tiles-processed/photos/asphalt/texture.jpg",
+                 "tiles-processed/photos/grass/texture.jpg", "tiles-processed/photos/floor/texture.jpg",
+                 "tiles-processed/synthetic/calibration/texture.png", "sign_left_T_intersect.png", "sign_4_way_intersect.png",
+                 "trafficlight_card0.jpg", "duckie.png", "black_tile.png", "/data/highway/left.png", "bus.png", "/home/asphalt/straight.png"]
+SEGMENT_NAMES = ["duckie", "duckiebot", "sign_generic", "trafficlight", "tree", "house", "bus", "cone", "truck", "barrier",
+                 "building", "object"]
+# (vel, steer) -> wheels: the DuckietownEnv parameter sets of test_duckietown_env_kinematics_equal_the_reference
+ENV_KW = (dict(gain=1.0, trim=0.0, radius=0.0318, k=27.0, limit=1.0), dict(gain=1.4, trim=-0.05, radius=0.03, k=24.0, limit=0.7))
+MOVING = {"loop_pedestrians": (250, 300), "loop_dyn_duckiebots": (60, 240)}
+
+
+def _query(r, ns, out, key, pos, a):
+    """Pose queries of the reference (geometry of simulator.py) into out[key_*] lists; lane pose NaN where NotInLane."""
+    out.setdefault(key + "_pos", []).append(pos)
+    out.setdefault(key + "_angle", []).append(a)
+    out.setdefault(key + "_valid", []).append(r._valid_pose(pos, a))
+    out.setdefault(key + "_collision", []).append(r._collision(ns.simulator.get_agent_corners(pos, a)))
+    out.setdefault(key + "_prox", []).append(r.proximity_penalty2(pos, a))
+    try:
+        lp = [float(v) for v in r.get_lane_pos2(pos, a)]
+    except ns.simulator.NotInLane:
+        lp = [np.nan] * 4
+    out.setdefault(key + "_lane", []).append(lp)
+
+
+def pins():
+    """tests/golden/ref_pins.npz: what the reference's own code answers to the queries of tests/test_oracle_vs_reference.py, so that
+    those tests pin oracle/sim.py without the reference tree.  Every query is stored with its input (pose, seed, action)."""
+    import tempfile
+    from oracle import distortion as odist
+    from oracle.fixtures import junction_map, start_tile_cases
+    out = {}
+    # random poses around the collidable objects: valid pose, collision, proximity, lane pose
+    for m in ("small_loop_only_duckies", "loop_only_duckies"):
+        r, ns = ref_sim(m)
+        rng = np.random.default_rng(99)
+        for _ in range(800):
+            c = r.collidable_centers[rng.integers(len(r.collidable_centers))]
+            _query(r, ns, out, f"fresh_{m}", c + np.array([rng.uniform(-0.4, 0.4), 0, rng.uniform(-0.4, 0.4)]), rng.uniform(-7, 7))
+    # reset() streams: three resets per seed
+    for dr in (False, True):
+        for seed in (11, 12, 13):
+            r, _ = ref_sim("loop_only_duckies", dr, seed)
+            for _ in range(3):
+                r.reset()
+                out.setdefault(f"resets_dr{int(dr)}_pos", []).append(np.array(r.cur_pos, dtype=np.float64))
+                out.setdefault(f"resets_dr{int(dr)}_angle", []).append(float(r.cur_angle))
+                out.setdefault(f"resets_dr{int(dr)}_ground", []).append(np.array(r.ground_color, dtype=np.float64))
+    # Distortion._invert_map / _fill_holes on the restated rectify maps (unrounded: the float32 maps themselves)
+    _, ns = ref_sim("small_loop")
+    Dm = ns.distortion.Distortion.__new__(ns.distortion.Distortion)
+    mapx, mapy = odist.rectify_maps(160, 120)
+    out["fill_rx"], out["fill_ry"] = Dm._invert_map(mapx.copy(), mapy.copy())
+    # should_segment_out and the segmentation colour ObjMesh hands to load_texture for an untextured chunk
+    out["segment_out"] = [bool(ns.graphics.should_segment_out(p)) for p in SEGMENT_PATHS]
+    with tempfile.TemporaryDirectory() as d:
+        for name in SEGMENT_NAMES:
+            f = os.path.join(d, f"{name}.obj")
+            with open(f, "w") as fh:
+                fh.write("v 0 0 0\nv 1 0 0\nv 0 1 0\nvt 0 0\nvn 0 0 1\nf 1/1/1 2/1/1 3/1/1\n")
+            open(os.path.join(d, "black_tile.png"), "wb").close()
+            res = {"black_tile.png": os.path.join(d, "black_tile.png")}
+            (path, seg, col), = refstub.ref_objmesh(f, name, lambda bn, _r=res: _r.get(bn), segment=True)["textures"]
+            out.setdefault("segment_flag", []).append(bool(seg))
+            out.setdefault("segment_texture", []).append(os.path.basename(path))
+            out.setdefault("segment_color", []).append([float(v) for v in col])
+    # every tile kind in every orientation: the tile table, then random poses incl. drivable / closest curve point
+    md = junction_map()
+    r, ns = ref_sim("junctions", md=copy.deepcopy(md))
+    for j in range(r.grid_height):
+        for i in range(r.grid_width):
+            t = r._get_tile(i, j)
+            out.setdefault("tiles_present", []).append(t is not None)
+            out.setdefault("tiles_kind", []).append("" if t is None else t["kind"])
+            out.setdefault("tiles_angle", []).append(-1 if t is None else t["angle"])
+            out.setdefault("tiles_drivable", []).append(t is not None and bool(t["drivable"]))
+            if t is not None and t["drivable"]:
+                out.setdefault("tiles_curves", []).append(np.asarray(t["curves"], dtype=np.float64))
+            out.setdefault("tiles_n_curves", []).append(len(t["curves"]) if t is not None and t["drivable"] else 0)
+    out["tiles_curves"] = np.concatenate(out["tiles_curves"])
+    rng = np.random.default_rng(5)
+    for _ in range(3000):
+        pos = np.array([rng.uniform(-0.3, r.grid_width * 0.585 + 0.3), 0, rng.uniform(-0.3, r.grid_height * 0.585 + 0.3)])
+        a = rng.uniform(-7, 7)
+        _query(r, ns, out, "junctions", pos, a)
+        out.setdefault("junctions_drivable", []).append(r._drivable_pos(pos))
+        cp, ct = r.closest_curve_point(pos, a)
+        out.setdefault("junctions_has_cp", []).append(cp is not None)
+        out.setdefault("junctions_cp", []).append(np.full(6, np.nan) if cp is None else np.concatenate([cp, ct]).astype(np.float64))
+    # DuckietownEnv.step: (vel, steer) -> the [left, right] duty handed to Simulator.step, and the info block's keys
+    DE = ns.duckietown_env.DuckietownEnv
+    seen = {}
+
+    def fake_step(self, vels):
+        seen["vels"] = np.array(vels, dtype=np.float64)
+        return None, 0.0, False, {}
+
+    orig = ns.simulator.Simulator.step
+    ns.simulator.Simulator.step = fake_step
+    try:
+        rng = np.random.default_rng(8)
+        for kw in ENV_KW:
+            env = DE.__new__(DE)
+            for k, v in kw.items():
+                setattr(env, k, v)
+            env.wheel_dist = 0.102 * 1.04
+            env.unwrapped = env
+            for _ in range(300):
+                act = rng.uniform(-1.6, 1.6, 2)
+                _, _, _, info = env.step(act)
+                out.setdefault("env_action", []).append(act)
+                out.setdefault("env_vels", []).append(seen["vels"])
+        out["env_info_keys"] = sorted(info["DuckietownEnv"])
+    finally:
+        ns.simulator.Simulator.step = orig
+    # reset()'s tile / pose selection branches and the optional objects' visibility draw
+    for dr in (False, True):
+        for c, (cmd, kw) in enumerate(start_tile_cases(assets.get_map("loop_only_duckies"), junction_map())):
+            r, _ = ref_sim("case", dr, 3, md=copy.deepcopy(cmd))
+            r.user_tile_start = kw.get("user_tile_start")
+            for _ in range(3):
+                r.reset()
+                out.setdefault(f"start_dr{int(dr)}_{c}_pos", []).append(np.array(r.cur_pos, dtype=np.float64))
+                out.setdefault(f"start_dr{int(dr)}_{c}_angle", []).append(float(r.cur_angle))
+                out.setdefault(f"start_dr{int(dr)}_{c}_visible", []).append([bool(ob.visible) for ob in r.objects])
+    # collision / proximity / _inconvenient_spawn against objects mid-walk / mid-drive
+    for m, steps in MOVING.items():
+        r, ns = ref_sim(m, md=copy.deepcopy(assets.get_map(m)))
+        if m == "loop_pedestrians":
+            for ob in r.objects:
+                ob.wiggle = np.pi / 15                       # the reference draws it from the global RNG (objects.py:362)
+        rng = np.random.default_rng(17)
+        t = 0
+        for t_end in steps:
+            while t < t_end:
+                for ob in r.objects:
+                    if ob.kind == "duckiebot" and not ob.static:
+                        ob.step_duckiebot(1 / 30, r.closest_curve_point, r.objects)
+                    elif not ob.static:
+                        ob.step(1 / 30)
+                t += 1
+            out[f"moving_{m}_{t_end}_obj_pos"] = np.array([np.asarray(ob.pos, float) for ob in r.objects])
+            out[f"moving_{m}_{t_end}_obj_static"] = np.array([bool(ob.static) for ob in r.objects])
+            key = f"moving_{m}_{t_end}"
+            for _ in range(600):
+                c = np.asarray(r.objects[rng.integers(len(r.objects))].pos, float)
+                pos = np.array([c[0] + rng.uniform(-0.35, 0.35), 0, c[2] + rng.uniform(-0.35, 0.35)])
+                _query(r, ns, out, key, pos, rng.uniform(-7, 7))
+                out.setdefault(key + "_inconvenient", []).append(bool(r._inconvenient_spawn(pos)))
+    out = {k: np.asarray(v) for k, v in out.items()}
+    np.savez_compressed(os.path.join(OUT, "ref_pins.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["pins"]:
+        assert refstub.available(), "run in the build container (needs /root/reference)"
+        pins()
+    else:
+        main()
