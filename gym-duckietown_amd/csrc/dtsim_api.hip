@@ -80,6 +80,7 @@ struct dtsim {
   float* d_lines = nullptr;       // dtsim_draw_lines: device copy of the caller's segments
   int lines_cap = 0;
   int render_tables = 0;          // dt_launch_render: which env-invariant tables are valid (camera LUT + maps unchanged)
+  int render_pipe = 0;            // DTSIM_PIPE_* of the last render pass (DTSIM_FIELD_RENDER_PIPE)
   RenderOverlap overlap{};        // render parts (DTSIM_RENDER_PARTS > 1): second stream + ordering events
   int q_cap = 0;
   // render
@@ -274,7 +275,7 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(frames %zu B): %s", h->frames_bytes, hipGetErrorString(e)); }
     h->frames = h->frames_own;
     e = hipMalloc(&h->d_lut, sizeof(float) * 4 * (size_t)cfg->cam_height * cfg->cam_width);
-    if (e == hipSuccess) e = hipMalloc(&h->d_envcam, (size_t)h->N * (128 + 64 + 64 + 4) + 64 + ((size_t)h->N + 1) * 64 + (size_t)h->N * 320);   // EnvCam[N], EnvFast[N], EnvQ[N], render order [N], (aligned) EnvV[N + 1], EnvD[N]
+    if (e == hipSuccess) e = hipMalloc(&h->d_envcam, (size_t)h->N * (128 + 64 + 64 + 4) + 64 + ((size_t)h->N + 1) * 64 + (size_t)h->N * 320 + ((size_t)h->N + 1) * 16);   // EnvCam[N], EnvFast[N], EnvQ[N], render order [N], (aligned) EnvV[N + 1], EnvD[N], EnvL[N + 1]
     if (e == hipSuccess) e = hipMalloc(&h->d_pixtab, (size_t)cfg->cam_height * cfg->cam_width * 64 + 2048);   // PixTab + SampTab + 1 KB store dump + debug counters
     {  // MSAA edge queue: one worst-case region per raster wavefront (render.hip QREGION)
       const size_t n_wg = dt_raster_tiles(cfg->cam_width, cfg->cam_height) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK);
@@ -897,7 +898,7 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
   R.blockbox = reinterpret_cast<float*>(h->d_objmask);
   R.objrange = h->d_objmask ? reinterpret_cast<uint2*>(reinterpret_cast<char*>(h->d_objmask) + dt_raster_tiles(R.W, R.H) * 4 * 16) : nullptr;
   R.objmask = h->d_objmask ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(R.objrange) + (size_t)DTSIM_MAX_MAPS * DTSIM_MAX_OBJECTS * 8) : nullptr;
-  R.pad4_ = 0;
+  R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
   R.queue = h->d_queue; R.qcount = h->d_qcount;
   R.dbg = nullptr;
   const size_t n_wg_ = dt_raster_tiles(R.W, R.H) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK);
@@ -926,7 +927,8 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
 #endif
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
-    h->render_tables = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr);
+    const int t = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr);
+    h->render_tables = t & 0xFF; h->render_pipe = t >> 8;
   }
   HIPCHK(hipGetLastError());
   h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true;
@@ -1335,6 +1337,7 @@ size_t public_bytes(const dtsim* h, int field) {
     case DTSIM_FIELD_OBJ_EXTRA: return N * DTSIM_MAX_DYNAMIC * 5 * 8;
     case DTSIM_FIELD_STATE_BLOB: return h->slab_bytes;
     case DTSIM_FIELD_RENDER_POS: return N * 4;
+    case DTSIM_FIELD_RENDER_PIPE: return N * 4;
     default: {
       FieldDesc d;
       if (!field_desc(const_cast<dtsim*>(h), field, d)) return 0;
@@ -1395,6 +1398,12 @@ int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
       hipError_t e = to_host ? hipMemcpy(host, h->slab, need, hipMemcpyDeviceToHost)
                              : hipMemcpy(h->slab, host, need, hipMemcpyHostToDevice);
       if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy blob: %s", hipGetErrorString(e));
+      return DTSIM_OK;
+    }
+    case DTSIM_FIELD_RENDER_PIPE: {                   // read-only
+      if (!to_host) return fail(DTSIM_E_INVALID, "DTSIM_FIELD_RENDER_PIPE is read-only");
+      int32_t* out = static_cast<int32_t*>(host);
+      for (size_t i = 0; i < N; ++i) out[i] = (int32_t)h->render_pipe;
       return DTSIM_OK;
     }
     case DTSIM_FIELD_RENDER_POS: {                    // read-only; the identity until a render pass ran in k_env_sort's order

@@ -233,7 +233,7 @@ struct RenderParams {
   void* envv;                   // [N + 1] EnvV (render.hip): k_raster_v3's per-env constants in render order
   void* envd;                   // [N] EnvD (render_v3dr.inc, 320 B, render order): k_raster_v3dr's per-env constants (domain randomisation)
   int32_t q3_rows;              // k_raster_v3 (render_v3.inc): rows of its LDS tile table (largest padded grid height); 0: k_raster_q is used
-  int32_t pad4_;
+  int32_t light;                // DTSIM_F_LIGHT_CAPTURE with the shared camera: every env lit by its own eye-space light (k_cam_setup, the LIGHT kernels)
   unsigned long long* spans;    // DT_WAVE_SPANS build variant only (else null): [2][2048 workgroups][4 wavefronts]{start, end, items, longest / first item, start of the first, sum, last item} in 100 MHz ticks
 };
 // tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an

@@ -151,6 +151,15 @@ struct alignas(16) EnvV {
   uint32_t tab3, hor_rgb, reach, env, pad[2];
 };
 static_assert(sizeof(EnvV) == 64, "EnvV is 64 bytes");
+// Per-env light of the shared camera (DTSIM_F_LIGHT_CAPTURE without DTSIM_F_DOMAIN_RAND), in render order, [N + 1] entries: the env's
+// eye-space light rotated into the yaw-local frame (right, up, forward) of the shared camera, where the pixel-centre hit on the tile plane is
+// (lr, -Cy, lf) and the plane normal (0, 1, 0).  lit / 256 = min(base / 256 + kd8 * rsq((Lr - lr)^2 + (Lf - lf)^2 + h2), 1 / 256)  (env_lit8):
+//   position:  Lr, Lf as rotated, h2 = h^2 with h = Lu + Cy (= N.(L - P), the same for every pixel), kd8 = dif * max(h, 0) / 256 (a light
+//              at or below the plane: h2 = 1, kd8 = 0 -- unlit, and no 0 * inf where a pixel lies under it);
+//   direction: Lr = Lf = 0, h2 = 2^120 -- the pixel's own terms vanish beside it, so the root is 2^-60 for every pixel (a wave-uniform
+//              constant) -- and kd8 = dif * max(N.L, 0) * 2^60 / 256.
+struct alignas(16) EnvL { float Lr, Lf, h2, kd8; };
+static_assert(sizeof(EnvL) == 16, "EnvL is 16 bytes");
 
 // coverage-only part of a ScreenTri kept in LDS by k_resolve_obj; the winner's colours are fetched
 // from global memory.
@@ -239,9 +248,11 @@ __global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapD
   for (int e = tid + KEEP * 1024; e < A.N; e += 1024) pos[e] = atomicAdd(&s_hist[bin_of(e)], 1);
 }
 
+// light: DTSIM_F_LIGHT_CAPTURE with the shared camera -- the env's own eye-space light (colors[12..15]) instead of default_cam()'s, also as the
+// rotated per-position constants of the quad kernels' LIGHT instantiations (envl, [N + 1], when given).
 __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float aspect, EnvCam* out, EnvFast* fast,
                             const RenderMapDev* __restrict__ maps, EnvQ* envq, int qlog2, const int32_t* __restrict__ pos, EnvV* envv,
-                            EnvD* envd, int W, int H) {
+                            EnvD* envd, int W, int H, int light, EnvL* envl) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const size_t N = A.N;
   if (e >= A.N) return;
@@ -264,7 +275,7 @@ __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float asp
     const CamShared s = default_cam(aspect);
     c.sth = s.sth; c.cth = s.cth; c.tx = s.tx; c.ty = s.ty; c.Cy = s.Cy;
     for (int k = 0; k < 3; ++k) { base[k] = s.base; dif[k] = s.dif; }
-    for (int k = 0; k < 4; ++k) L[k] = s.L[k];
+    for (int k = 0; k < 4; ++k) L[k] = light ? A.colors[(12 + k) * N + e] : s.L[k];
   }
   // glTranslatef(0,0,CAMERA_FORWARD_DIST) before gluLookAt (simulator.py:1784,1803): the
   // camera centre sits 6.6 cm ahead of the axle along dir = (cos a, 0, -sin a).
@@ -285,6 +296,18 @@ __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float asp
     L[0] *= inv; L[1] *= inv; L[2] *= inv;
   }
   for (int k = 0; k < 4; ++k) c.L[k] = L[k];
+  if (envl) {                // (shared camera: c.sth, c.cth, c.Cy and dif are default_cam()'s)
+    EnvL l;
+    const float Lu = L[1] * c.cth + L[2] * c.sth;
+    if (L[3] == 0.f) {
+      l.Lr = l.Lf = 0.f; l.h2 = 0x1p120f; l.kd8 = dif[0] * fmaxf(Lu, 0.f) * (0x1p60f / 256.f);   // (/ 256: Q8_LIT)
+    } else {
+      const float h = Lu + c.Cy;
+      l.Lr = L[0]; l.Lf = L[1] * c.sth - L[2] * c.cth; l.h2 = h > 0.f ? h * h : 1.f; l.kd8 = dif[0] * fmaxf(h, 0.f) * (1.f / 256.f);
+    }
+    envl[pos ? pos[e] : e] = l;
+    if (e == A.N - 1) envl[A.N] = l;                 // the entry past the end (prefetched, never used)
+  }
   // ground quad corners: per-vertex lighting (Gouraud over the 100 m quad)
   for (int k = 0; k < 4; ++k) {
     const float X = (k & 1) ? GROUND_HALF : -GROUND_HALF, Z = (k & 2) ? GROUND_HALF : -GROUND_HALF;
@@ -1608,6 +1631,23 @@ __device__ inline uint32_t quad_weights8(float a8, float b8, float l) {
   W = __builtin_amdgcn_cvt_pk_u8_f32(w01, 2, W);
   return __builtin_amdgcn_cvt_pk_u8_f32(w11, 3, W);
 }
+// The tile plane's lit factor / 256 of one pixel (yaw-local centre hit lr, lf) under an env's own light (EnvL): the raster's env loops and the
+// exact paths all go through these operations, so that a one-ray pixel gets the same bytes from either (the packed form in the env loops is
+// these operations, two pixels each).  base8 = the shared ambient term / 256; the clamp at 1 / 256 is exact (a power of two).
+__device__ inline float env_lit8(const EnvL& l, float lr, float lf, float base8) {
+#pragma clang fp contract(off)
+  const float dx = l.Lr - lr, dz = l.Lf - lf;
+  return fminf(fmaf(l.kd8, frsq(fmaf(dx, dx, fmaf(dz, dz, l.h2))), base8), Q8_LIT);
+}
+__device__ inline float env_base8() { return default_cam(1.f).base * Q8_LIT; }
+__device__ inline f2_t env_lit8_2(const EnvL& l, const f2_t lr, const f2_t lf) {   // env_lit8 of two pixels
+#pragma clang fp contract(off)
+  const f2_t dx = f2_t{l.Lr, l.Lr} - lr, dz = f2_t{l.Lf, l.Lf} - lf;
+  const f2_t d2 = fma2(dx, dx, fma2(dz, dz, f2_t{l.h2, l.h2}));
+  const float b8 = env_base8();
+  const f2_t t = fma2(f2_t{l.kd8, l.kd8}, f2_t{frsq(d2.x), frsq(d2.y)}, f2_t{b8, b8});
+  return f2_t{fminf(t.x, Q8_LIT), fminf(t.y, Q8_LIT)};
+}
 // one-ray colour 0x00BBGGRR of a record (a8, b8 as above; I = lit factor, 0..1)
 __device__ inline uint32_t quad_filter(const uint4& q, float a8, float b8, float I) {
   const uint32_t W = quad_weights8(a8, b8, I * Q8_LIT);
@@ -1632,13 +1672,14 @@ __device__ inline void quad_filter3(const uint4& q, float a8, float b8, float I,
 // [i0, i0 + n) of the concatenation, (p1, p2, p3) = where regions 1..3 start in it.  Per wavefront the regions hold anything
 // from nothing (sky blocks) to several hundred entries (a seam along the block): pooled, the 64-entry batches run full and
 // no wavefront of a workgroup idles while another drains its seam.
-template <bool S256, bool V3 = false, bool POOL = false>
+// LIGHT: the shared camera with per-env lights (EnvL in render order, envl): the lit factor of the tile plane is env_lit8's, per entry.
+template <bool S256, bool V3 = false, bool POOL = false, bool LIGHT = false>
 __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __restrict__ cams, const EnvQ* __restrict__ envq,
                                       const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab,
                                       const uint8_t* __restrict__ qtex, const uint32_t* s_qt, uint32_t* w_list,
                                       const uint16_t* w_queue, const int n, const int e0, const int tile_x0, const int wave_y0,
                                       const int lane, const int i0 = 0, const int p1 = 0, const int p2 = 0, const int p3 = 0,
-                                      const uint4* s_envq = nullptr) {
+                                      const uint4* s_envq = nullptr, const EnvL* __restrict__ envl = nullptr) {
   // s_envq (V3): the EnvQ records of the chunk's 64 positions, staged in LDS by the workgroup -- an entry's constants are three
   // ds_read_b128 instead of three 16-byte gathers through the texture unit (in both phases).
   const int npix = R.W * R.H;
@@ -1749,6 +1790,7 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
         }
         if (V3) qb[u].z = qd.z;
         env[u] = (int)qd.y;
+        if constexpr (LIGHT) { const EnvL l = envl[min(e0 + el[u], R.N - 1)]; pt[u].lit = pt[u].lit > 0.f ? 256.f * env_lit8(l, pt[u].lr, pt[u].lf, env_base8()) : pt[u].lit; }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1864,8 +1906,9 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
         const float goff = (float)DT_QRING * Sf + 0.5f, ghalf = GROUND_HALF * qpm;   // world 0 and 50 m in padded quad coordinates
         const float Xu = fmaf(pt.lf, B, fmaf(pt.lr, A, Cx)), Zu = fmaf(pt.lf, -A, fmaf(pt.lr, B, Cz));
         const uint32_t xic = q8_bits(Xu), zic = q8_bits(Zu);              // the centre's snapped coordinates: q8_rec256 works on these bits
-        const float lit = pt.lit > 0.f ? pt.lit : 0.55f;
-        const uint32_t W8 = quad_weights8(q8_frac(xic), q8_frac(zic), lit * Q8_LIT);
+        float lit8 = (pt.lit > 0.f ? pt.lit : 0.55f) * Q8_LIT;
+        if constexpr (LIGHT) { if (pt.lit > 0.f) lit8 = env_lit8(envl[min(e0 + el, R.N - 1)], pt.lr, pt.lf, env_base8()); }
+        const uint32_t W8 = quad_weights8(q8_frac(xic), q8_frac(zic), lit8);
         uint32_t aS[3] = {0u, 0u, 0u};                 // sum over the samples of the byte-weight filter of each sample's record
         int n_sky = 0, n_gnd = 0;
         float gX = 0.f, gZ = 0.f;                      // ground hit (quad coordinates) of the lowest-index ground sample
@@ -1934,7 +1977,8 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
       const float Xu = fmaf(pt.lf, B, fmaf(pt.lr, A, Cx)), Zu = fmaf(pt.lf, -A, fmaf(pt.lr, B, Cz));
       const uint32_t xub = q8_bits(Xu), zub = q8_bits(Zu);
       const float ax = q8_frac(xub), az = q8_frac(zub);
-      const float lit = pt.lit > 0.f ? pt.lit : 0.55f;
+      float lit = pt.lit > 0.f ? pt.lit : 0.55f;
+      if constexpr (LIGHT) { if (pt.lit > 0.f) lit = 256.f * env_lit8(envl[min(e0 + el, R.N - 1)], pt.lr, pt.lf, env_base8()); }
       // coverage: per sample tile (tile plane hit within [near, far] on a present tile), else ground quad, else clear colour
       uint32_t key[4];                                 // 0 sky, 1 ground, else 2 + table address of the tile
       uint2 te[4];
@@ -2037,12 +2081,13 @@ __host__ __device__ inline int dt_q_tile_group(int n_tiles) {
 #ifndef DT_Q_PRIO
 #define DT_Q_PRIO 3                                  // s_setprio level while a wavefront issues its quad loads (0: off)
 #endif
-template <bool OBJ, bool S256>
+// LIGHT: per-env lights (EnvL in render order), as k_raster_v3<OBJ, true> (render_v3.inc)
+template <bool OBJ, bool S256, bool LIGHT = false>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_WAVES - 1 : DT_Q_WAVES, OBJ ? DT_Q_WAVES - 1 : DT_Q_WAVES))) void k_raster_q(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast* __restrict__ fasts,
                                                  const EnvQ* __restrict__ envq, uint8_t* __restrict__ frames,
                                                  const uint8_t* __restrict__ qtex, const float4* __restrict__ lut, const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab,
                                                  const uint32_t* __restrict__ qtiles, uint16_t* __restrict__ queue,
-                                                 int32_t* __restrict__ qcount) {
+                                                 int32_t* __restrict__ qcount, const EnvL* __restrict__ envl) {
   extern __shared__ uint32_t s_mem[];
   uint32_t* s_qt = s_mem;                                                                   // [n_qtiles]
   const int tid = threadIdx.x;
@@ -2300,7 +2345,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
       f2 w00, w10, w01, w11;
       {
 #pragma clang fp contract(off)
-        const f2 I2 = lit2[j] * Q8_LIT, c256 = f2{256.f, 256.f};
+        f2 I2 = lit2[j] * Q8_LIT;
+        if constexpr (LIGHT) I2 = env_lit8_2(envl[e], lr2[j], lf2[j]);
+        const f2 c256 = f2{256.f, 256.f};
         const f2 u = ax2[j] * I2, v = fma2(I2, c256, -u);
         w11 = u * az2[j]; w01 = v * az2[j];
         w10 = fma2(u, c256, -w11); w00 = fma2(v, c256, -w01);
@@ -2422,7 +2469,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     // exact path for this wavefront's own edge pixels, right here (the frame stores of the env loop are ordered
     // before the byte patches: same wavefront, same addresses)
     __builtin_amdgcn_s_waitcnt(0);                 // queue stores have left the wavefront
-    resolve_region<S256>(R, cams, envq, pixtab, samptab, qtex, s_qt, s_px, w_queue, qn, e0, tile_x0, wave_y0, lane);
+    resolve_region<S256, false, false, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, s_px, w_queue, qn, e0, tile_x0, wave_y0, lane, 0, 0, 0, 0, nullptr, envl);
   }
   }
   if (OBJ) {   // mesh objects: k_resolve_obj drains the object-box entries (back of the regions) -- work items for it
@@ -3025,7 +3072,7 @@ template <class K> static size_t resident_blocks(K kernel, size_t lds) {
 // One range of chunks through its raster (stream s) and exact-path kernels (stream s_res, after event ev when it is
 // another stream): the whole batch, or one of dt_launch_render's render parts (every array already moved to the range).
 static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t ev, const RenderParams& R, EnvCam* cams, EnvFast* fasts, EnvQ* envq,
-                                  EnvV* envv, EnvD* envd, uint8_t* frames_raster, bool quad, bool v3, bool v3dr, bool obj, bool has_pos) {
+                                  EnvV* envv, EnvD* envd, EnvL* envl, uint8_t* frames_raster, bool quad, bool v3, bool v3dr, bool obj, bool has_pos) {
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
   const size_t lds = (size_t)R.n_tile_recs * sizeof(TileLds);
   const size_t lds1 = lds + (size_t)RB * PPT * sizeof(uint32_t);          // + store transpose
@@ -3041,14 +3088,18 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
     const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
     PixTab* pixtab = reinterpret_cast<PixTab*>(R.pixtab);
     SampTab* samptab = reinterpret_cast<SampTab*>(pixtab + (size_t)R.W * R.H);
-#define LAUNCH_Q(OBJ_, S256_) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, R.qtex, \
-                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount)
+#define LAUNCH_Q(OBJ_, S256_) do { if (R.light) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, true>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, \
+                                           R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
+                                else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, R.qtex, \
+                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
     const bool s256 = R.qlog2 == 8 && R.qmax_tiles < 256;
     // k_raster_v3 (render_v3.inc): S = 256 textures, padded grids up to 32 x 24 tiles, up to 4 maps (else k_raster_q)
     if (v3) {
       const size_t lds3 = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // tile table, per-wavefront buffers, the chunk's EnvQ records
-#define LAUNCH_V3(OBJ_) hipLaunchKernelGGL((k_raster_v3<OBJ_>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, R.qtex, \
-                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount)
+#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, \
+                                           R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
+                                else hipLaunchKernelGGL((k_raster_v3<OBJ_>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, R.qtex, \
+                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
       if (obj) LAUNCH_V3(true); else
       LAUNCH_V3(false);
 #undef LAUNCH_V3
@@ -3059,7 +3110,7 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
     const size_t ldsd = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * RQ_LIST * 4;
     if (obj) hipLaunchKernelGGL((k_raster_v3dr<true>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
     else hipLaunchKernelGGL((k_raster_v3dr<false>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-  } else if (R.domain_rand || R.segment) { if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); }   // per-env EnvCam path
+  } else if (R.domain_rand || R.segment || R.light) { if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); }   // per-env EnvCam path (light: the shared camera's EnvCam with the env's light)
   else { if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false); }
 #undef LAUNCH_RASTER
   // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region); generic raster:
@@ -3093,6 +3144,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   EnvQ* envq = reinterpret_cast<EnvQ*>(fasts + A.N);
   EnvV* envv = reinterpret_cast<EnvV*>(R.envv);
   EnvD* envd = reinterpret_cast<EnvD*>(R.envd);
+  EnvL* envl = reinterpret_cast<EnvL*>(envd + A.N);   // [N + 1] behind the EnvD records (dtsim_api.hip allocates them)
   // domain randomisation on the quad records (k_raster_v3dr): same table / texture conditions as k_raster_v3
   const bool v3dr = R.qtex && R.envd && R.domain_rand && !R.segment && !R.no_msaa && (R.W & 3) == 0 && R.qlog2 == 8 && R.q3_rows > 0 &&
                     R.q3_rows <= 24 && R.n_maps * 32 <= 128;
@@ -3107,7 +3159,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   if (pos) { hipLaunchKernelGGL(k_env_sort, dim3(1), dim3(1024), 0, s, A, R.maps, pos); tables |= 4; }
   hipLaunchKernelGGL(k_cam_setup, dim3((A.N + 63) / 64), dim3(64), 0, s, A, R.domain_rand, R.segment,
                      (float)R.W / (float)R.H, cams, fasts, R.maps, (quad || v3dr) ? envq : nullptr, R.qlog2, pos, quad ? envv : nullptr,
-                     v3dr ? envd : nullptr, R.W, R.H);
+                     v3dr ? envd : nullptr, R.W, R.H, R.light, (quad && R.light) ? envl : nullptr);
   (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * sizeof(int32_t), s);            // work-item counts + cursors of k_resolve / k_resolve_obj
   if (R.max_tris > 0) {
     if (!(tables & 2)) hipLaunchKernelGGL(k_blk_setup, dim3((unsigned)dt_raster_tiles(R.W, R.H)), dim3(RB), 0, s, R, reinterpret_cast<const float4*>(R.lut), reinterpret_cast<float4*>(R.blockbox));
@@ -3130,7 +3182,11 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   // kernels are the same; only the quad-record paths in the sorted render order are split (k_raster_v3, k_raster_v3dr).
   int parts = 1;
   if (ov && ov->parts > 1 && !R.no_msaa && (v3 || v3dr) && pos && (obj || !quad)) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
-  if (parts <= 1) { launch_raster_resolve(s, s, nullptr, R, cams, fasts, envq, envv, envd, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
+  // which raster ran (DTSIM_FIELD_RENDER_PIPE): bits 8.. of the result
+  tables |= (quad ? (v3 ? DTSIM_PIPE_V3 : DTSIM_PIPE_Q) : v3dr ? DTSIM_PIPE_V3DR : (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV
+             : DTSIM_PIPE_GENERIC) << 8;
+  if (R.light) tables |= DTSIM_PIPE_ENV_LIGHT << 8;
+  if (parts <= 1) { launch_raster_resolve(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
   static const bool parts_serial = [] { const char* v = getenv("DTSIM_RENDER_PARTS_SERIAL"); return v && v[0] == '1'; }();   // experiment: the split without the overlap
   const size_t n_tiles = dt_raster_tiles(R.W, R.H), n_blk = n_tiles * 4;
   (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * parts * sizeof(int32_t), s);
@@ -3149,7 +3205,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     // per-POSITION arrays move to the range (EnvQ / EnvV / EnvD in render order, masks, queues, items above); per-ENV arrays (EnvCam, frames,
     // screen triangles, object boxes) stay whole: the kernels reach them through the env id of the position's record
     EnvQ* envq_p = envq + e0; EnvV* envv_p = envv ? envv + e0 : nullptr; EnvD* envd_p = envd ? envd + e0 : nullptr;
-    launch_raster_resolve(s, parts_serial ? s : ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, R.frames, quad, v3, v3dr, obj, true);
+    launch_raster_resolve(s, parts_serial ? s : ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
   }
   (void)hipEventRecord(ov->ev[DT_MAX_RENDER_PARTS], ov->s2);
   (void)hipStreamWaitEvent(s, ov->ev[DT_MAX_RENDER_PARTS], 0);

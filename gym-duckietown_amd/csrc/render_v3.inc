@@ -89,12 +89,15 @@ __device__ inline C3 c3_of_rgb(const uint32_t rgb) { return C3{rgb, rgb}; }   //
 
 struct GndK { float Cx, Cz, sa, ca, kg, gnd[3], base[3], dif[3], gndl[4], pad[2]; };   // ground-quad constants of one env
 
-template <bool OBJ>
+// LIGHT (DTSIM_F_LIGHT_CAPTURE): every env lit by its own light (envl: EnvL in render order, [N + 1]) -- the lit factor of a (pixel, env) is
+// env_lit8's, two pixels per packed operation, in place of the PixTab's shared one; the PixTab's lit keeps its class role (< 0 outside the
+// image, 0 sky, > 0 candidate).  Without LIGHT envl is not read.
+template <bool OBJ, bool LIGHT = false>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_V3_WAVES_OBJ : DT_V3_WAVES, OBJ ? DT_V3_WAVES_OBJ : DT_V3_WAVES)))
 void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast* __restrict__ fasts, const EnvQ* __restrict__ envq,
                  const EnvV* __restrict__ envv, uint8_t* __restrict__ frames, const uint8_t* __restrict__ qtex, const float4* __restrict__ lut,
                  const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab, const uint32_t* __restrict__ qtiles,
-                 uint16_t* __restrict__ queue, int32_t* __restrict__ qcount) {
+                 uint16_t* __restrict__ queue, int32_t* __restrict__ qcount, const EnvL* __restrict__ envl) {
   extern __shared__ uint32_t s_mem[];
   uint32_t* s_qt = s_mem;                             // [q3_rows][V3_TAB_PITCH] block byte offsets
   const int tid = threadIdx.x;
@@ -428,7 +431,9 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
         f2 w00, w10, w01, w11;
         {
 #pragma clang fp contract(off)
-          const f2 I2 = lit2[j], c256 = f2{256.f, 256.f};
+          f2 I2 = lit2[j];
+          if constexpr (LIGHT) I2 = env_lit8_2(envl[e], lr2[j], lf2[j]);
+          const f2 c256 = f2{256.f, 256.f};
           const f2 u = st.ax2[j] * I2, v = fma2(I2, c256, -u);
           w11 = u * st.az2[j]; w01 = v * st.az2[j];
           w10 = fma2(u, c256, -w11); w00 = fma2(v, c256, -w01);
@@ -533,7 +538,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
     if (qn > 0) {
 #endif
       __builtin_amdgcn_s_waitcnt(0);                   // queue stores have left the wavefront
-      resolve_region<true, true>(R, cams, envq, pixtab, samptab, qtex, s_qt, w_lds, w_queue, qn, e0, bx0, by0, lane, 0, 0, 0, 0, s_envq);
+      resolve_region<true, true, false, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, w_lds, w_queue, qn, e0, bx0, by0, lane, 0, 0, 0, 0, s_envq, envl);
     }
   }
 #ifdef DT_WAVE_SPANS

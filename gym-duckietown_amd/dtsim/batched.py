@@ -88,10 +88,9 @@ class BatchedSimulator:
         flags |= _ffi.F_DOMAIN_RAND if (domain_rand or per_env_camera) else 0
         flags |= _ffi.F_AUTO_RESET if auto_reset else 0
         # light_capture (DTSIM_F_LIGHT_CAPTURE): device-side resets take the new episode's light through the camera of the pose the previous
-        # episode ended at, as GL does with reset()'s glLightfv (simulator.py:565-584).  Only the per-env render path has a per-env light.
+        # episode ended at, as GL does with reset()'s glLightfv (simulator.py:565-584).  With domain_rand=False the shared-camera render then
+        # lights each env with its own light (ABI v12: the LIGHT instantiations of the quad rasters).
         self.light_capture = bool(light_capture)
-        if self.light_capture and not domain_rand:
-            raise ValueError("light_capture needs domain_rand=True: the shared-camera render path lights every env alike (DESIGN.md section 5)")
         flags |= _ffi.F_LIGHT_CAPTURE if self.light_capture else 0
         flags |= _ffi.F_ACTIONS_F64 if actions_f64 else 0
         flags |= _ffi.F_PROFILE if profile else 0
@@ -427,6 +426,20 @@ class BatchedSimulator:
             self._install_segment_assets()
         _ffi.check(self._lib, self._lib.dtsim_render_ex(self._h, _ffi.RENDER_SEGMENT | flags))
 
+    _PIPE_NAMES = {_ffi.PIPE_GENERIC: "k_raster", _ffi.PIPE_GENERIC_ENV: "k_raster_env", _ffi.PIPE_Q: "k_raster_q",
+                   _ffi.PIPE_V3: "k_raster_v3", _ffi.PIPE_V3DR: "k_raster_v3dr"}
+
+    @property
+    def render_pipeline(self) -> Optional[str]:
+        """The raster of the last render() (DTSIM_FIELD_RENDER_PIPE): "k_raster_v3", "k_raster_q", "k_raster" (the shared camera),
+        "k_raster_env" (the generic raster through each env's camera record), "k_raster_v3dr" (domain randomisation); "+light" is appended when
+        the shared camera lit each env with its own light (light_capture).  None before the first pass."""
+        code = int(self.read(_ffi.FIELD_RENDER_PIPE)[0])
+        if not code:
+            return None
+        name = self._PIPE_NAMES[code & (_ffi.PIPE_ENV_LIGHT - 1)]
+        return name + ("+light" if code & _ffi.PIPE_ENV_LIGHT else "")
+
     def segment_assets(self):
         """(segmented textures mirroring self.textures, per-mesh flat colours [n_meshes,3]) -- host prep of the
         segmentation render: tile textures through load_texture(segment=True) (graphics.py:70-126, into black),
@@ -606,7 +619,7 @@ class BatchedSimulator:
         _ffi.FIELD_OBJ_VISIBLE: ("u1", (_ffi.MAX_OBJECTS,)), _ffi.FIELD_EPISODE: ("i4", ()),
         _ffi.FIELD_OBJ_LIGHT: ("u1", (_ffi.MAX_OBJECTS,)), _ffi.FIELD_OBJ_Y: ("f8", (_ffi.MAX_DYNAMIC,)),
         _ffi.FIELD_OBJ_EXTRA: ("f8", (_ffi.MAX_DYNAMIC, 5)), _ffi.FIELD_CAMERA: ("f4", (6,)), _ffi.FIELD_COLORS: ("f4", (16,)),
-        _ffi.FIELD_WHEEL_DIST: ("f8", ()), _ffi.FIELD_RENDER_POS: ("i4", ()),
+        _ffi.FIELD_WHEEL_DIST: ("f8", ()), _ffi.FIELD_RENDER_POS: ("i4", ()), _ffi.FIELD_RENDER_PIPE: ("i4", ()),
     }
 
     def read(self, field: int) -> np.ndarray:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DTSIM_ABI_VERSION 11
+#define DTSIM_ABI_VERSION 12
 
 /* error codes */
 #define DTSIM_OK 0
@@ -63,7 +63,10 @@ extern "C" {
                                   * second episode on the light given in the init state is taken through the camera of the pose the previous episode ended at
                                   * (a direction is rotated, a position also translated) before it becomes the env's eye-space light.  Honoured by the per-env
                                   * render path (DTSIM_F_DOMAIN_RAND); dtsim_reset(states) takes the light as given (the caller's business, as the gym facade
-                                  * does it on the host). */
+                                  * does it on the host).
+                                  * (ABI v12) With DTSIM_F_DOMAIN_RAND off as well, the shared-camera render lights each env with its own eye-space light
+                                  * (colors[12..15] of DTSIM_FIELD_COLORS, whether dtsim_reset(states) set it or a device-side reset captured it); ambient and
+                                  * diffuse stay the shared values.  Without this flag the shared camera lights every env with the first episode's light. */
 
 /* dtsim_config.action_mode */
 #define DTSIM_ACTION_WHEELS 0    /* Simulator.step: [left, right] duty, clipped to [-1,1] (simulator.py:1669-1672) */
@@ -249,8 +252,20 @@ enum {
   DTSIM_FIELD_RENDER_POS = 27,/* int32  [N]     read-only: position of each env in the render order of the last dtsim_render (k_env_sort:
                                * envs standing on the same tile and facing the same way are neighbours; 32 consecutive positions share a
                                * raster workgroup, XCD x owns the x-th eighth of the order); the identity when the pass ran in index order */
-  DTSIM_FIELD__COUNT = 28
+  DTSIM_FIELD_RENDER_PIPE = 28,/* int32 [N]     read-only (ABI v12): the raster of the last dtsim_render, the same value for every env: DTSIM_PIPE_* below,
+                               * | DTSIM_PIPE_ENV_LIGHT when the shared camera lit each env with its own light (DTSIM_F_LIGHT_CAPTURE); 0 before any pass.
+                               * One value for the whole pass, repeated per env so that the field reads like every other.  The flag
+                               * describes the configuration: a segmentation pass is unlit whatever it says. */
+  DTSIM_FIELD__COUNT = 29
 };
+
+/* DTSIM_FIELD_RENDER_PIPE values */
+#define DTSIM_PIPE_GENERIC 1      /* generic raster, shared camera */
+#define DTSIM_PIPE_GENERIC_ENV 2  /* generic raster through each env's camera record (domain randomisation, segmentation, per-env light) */
+#define DTSIM_PIPE_Q 3            /* quad-record raster, shared camera (tile textures other than 256 x 256, larger grids) */
+#define DTSIM_PIPE_V3 4           /* quad-record raster, shared camera, 256 x 256 tile textures */
+#define DTSIM_PIPE_V3DR 5         /* quad-record raster, per-env camera (domain randomisation) */
+#define DTSIM_PIPE_ENV_LIGHT 16   /* flag: each env lit by its own light on the shared camera */
 
 /* kernels for dtsim_profile_read */
 enum { DTSIM_KERNEL_STEP = 0, DTSIM_KERNEL_RENDER = 1, DTSIM_KERNEL_RESET = 2, DTSIM_KERNEL_QUERY = 3, DTSIM_KERNEL_OBSERVE = 4, DTSIM_KERNEL__COUNT = 5 };
