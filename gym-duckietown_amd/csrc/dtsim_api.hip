@@ -122,10 +122,11 @@ struct dtsim {
   int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
   int32_t* d_obsc_tab = nullptr;  // dtsim_observe_cubic tables (device copy of obsc_tab)
   std::vector<int32_t> obsc_tab;
-  int32_t* d_obs_tab = nullptr;   // dtsim_observe resampling tables (cached per output size)
+  int32_t* d_obs_tab = nullptr;   // dtsim_observe resampling tables (device copy of obs_tab)
+  std::vector<int32_t> obs_tab;   // the cache key: output size, tap counts and the caller's tables
   int obs_h = 0, obs_w = 0, obs_kx = 0, obs_ky = 0, obs_rpb = 0, obs_rows_in = 0;
   size_t obs_off_by = 0;
-  ObserveParams obs_fast{};       // the power-of-two fast-path fields of the cached output size (hfast .. vw)
+  ObserveParams obs_fast{};       // the power-of-two fast-path fields of the cached tables (hfast .. vw)
   int max_tris = 0;
   int n_tilerecs = 0, tex_w = 1, tex_h = 1;
   ObjInstDev* d_robjs = nullptr;
@@ -1119,15 +1120,18 @@ int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
   if ((out_w != W && (!bounds_x || !taps_x || ksize_x <= 0)) || (out_h != H && (!bounds_y || !taps_y || ksize_y <= 0)))
     return fail(DTSIM_E_INVALID, "resampling tables missing for a resized axis");
   HIPCHK(hipSetDevice(h->cfg.device));
-  // tables: cached per (out_h, out_w); [bx | kkx | by | kky] in one device buffer
-  if (h->obs_h != out_h || h->obs_w != out_w || !h->d_obs_tab) {
-    std::vector<int32_t> tab;
-    std::vector<int32_t> by(2 * (size_t)out_h);
-    if (out_w != W) { tab.insert(tab.end(), bounds_x, bounds_x + 2 * (size_t)out_w); tab.insert(tab.end(), taps_x, taps_x + (size_t)out_w * ksize_x); }
-    else ksize_x = 0;
-    h->obs_off_by = tab.size();
-    if (out_h != H) for (int i = 0; i < 2 * out_h; ++i) by[i] = bounds_y[i];
-    else { for (int i = 0; i < out_h; ++i) { by[2 * i] = i; by[2 * i + 1] = 1; } ksize_y = 0; }
+  // tables: [bx | kkx | by | kky] in one device buffer, re-sent (and the fast paths re-derived) when they differ from the
+  // cached ones -- the same output size may come with other tables
+  std::vector<int32_t> tab;
+  std::vector<int32_t> by(2 * (size_t)out_h);
+  if (out_w != W) { tab.insert(tab.end(), bounds_x, bounds_x + 2 * (size_t)out_w); tab.insert(tab.end(), taps_x, taps_x + (size_t)out_w * ksize_x); }
+  else ksize_x = 0;
+  const size_t off_by = tab.size();
+  if (out_h != H) for (int i = 0; i < 2 * out_h; ++i) by[i] = bounds_y[i];
+  else { for (int i = 0; i < out_h; ++i) { by[2 * i] = i; by[2 * i + 1] = 1; } ksize_y = 0; }
+  tab.insert(tab.end(), by.begin(), by.end());
+  if (out_h != H) tab.insert(tab.end(), taps_y, taps_y + (size_t)out_h * ksize_y);
+  if (h->obs_h != out_h || h->obs_w != out_w || h->obs_kx != ksize_x || h->obs_ky != ksize_y || tab != h->obs_tab || !h->d_obs_tab) {
     for (int i = 0; i < out_h; ++i)
       if (by[2 * i] < 0 || by[2 * i + 1] <= 0 || by[2 * i] + by[2 * i + 1] > H || (i && by[2 * i] < by[2 * i - 2]))
         return fail(DTSIM_E_INVALID, "bounds_y[%d] = (%d, %d) out of range / not monotone", i, by[2 * i], by[2 * i + 1]);
@@ -1135,11 +1139,8 @@ int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
       for (int i = 0; i < out_w; ++i)
         if (bounds_x[2 * i] < 0 || bounds_x[2 * i + 1] <= 0 || bounds_x[2 * i + 1] > ksize_x || bounds_x[2 * i] + bounds_x[2 * i + 1] > W)
           return fail(DTSIM_E_INVALID, "bounds_x[%d] = (%d, %d) out of range", i, bounds_x[2 * i], bounds_x[2 * i + 1]);
-    tab.insert(tab.end(), by.begin(), by.end());
-    if (out_h != H) {
+    if (out_h != H)
       for (int i = 0; i < out_h; ++i) if (by[2 * i + 1] > ksize_y) return fail(DTSIM_E_INVALID, "bounds_y[%d] count > ksize_y", i);
-      tab.insert(tab.end(), taps_y, taps_y + (size_t)out_h * ksize_y);
-    }
     // rows per workgroup: as many output rows as keep the uint8 intermediate (+ staging) within 48 KB of LDS
     const size_t stage = DT_OBS_STAGE_ROWS * (((size_t)W * 3 + 3) / 4) * 4 + 32, tabs = (out_w != W && ksize_x <= 9) ? (size_t)out_w * 11 * 4 : 0;
     const size_t budget = DT_OBS_LDS_KB * 1024 - stage - tabs - 32;
@@ -1160,6 +1161,7 @@ int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
     if (h->d_obs_tab) { (void)hipFree(h->d_obs_tab); h->d_obs_tab = nullptr; }
     HIPCHK(hipMalloc(&h->d_obs_tab, tab.size() * sizeof(int32_t)));
     HIPCHK(hipMemcpy(h->d_obs_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->obs_tab = tab; h->obs_off_by = off_by;
     h->obs_h = out_h; h->obs_w = out_w; h->obs_kx = ksize_x; h->obs_ky = ksize_y; h->obs_rpb = rpb; h->obs_rows_in = need;
     // power-of-two down-scaling: interior columns / rows with identical small-integer taps (k_observe's dot4 / two-lane paths)
     h->obs_fast = ObserveParams{};

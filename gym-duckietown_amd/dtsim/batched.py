@@ -561,7 +561,8 @@ class BatchedSimulator:
         (learning/utils/wrappers.py ResizeWrapper) or, with interpolation="cv_cubic", the cv2 INTER_CUBIC resize of the
         reference's own ResizeWrapper (src/gym_duckietown/wrappers.py:129-138); optional HWC->CHW (ImgWrapper) and /255
         float32 (NormalizeWrapper).  Returns a device array ([N,h,w,3] or [N,3,h,w]); `out` may be any object with
-        __cuda_array_interface__ of that shape/dtype (e.g. the send buffer of the frame all-gather)."""
+        __cuda_array_interface__ of that shape/dtype, C-contiguous (e.g. the send buffer of the frame all-gather); any other `out` raises
+        ValueError before anything is launched."""
         import torch
         from . import resample
         if interpolation not in ("pil_bilinear", "cv_cubic"):
@@ -575,7 +576,17 @@ class BatchedSimulator:
                                             device=f"cuda:{self.device_index}")
                 self._obs_key = key
             out = self._obs_buf
-        ptr = out.__cuda_array_interface__["data"][0]
+        ai = out.__cuda_array_interface__
+        typestr = "<f4" if normalize else "|u1"
+        item = 4 if normalize else 1
+        c_strides = tuple(int(np.prod(shape[i + 1:])) * item for i in range(len(shape)))
+        strides = ai.get("strides")
+        if tuple(ai["shape"]) != shape or ai["typestr"] != typestr or not (
+                strides is None or all(s == c for s, c, n in zip(strides, c_strides, shape) if n > 1)):
+            # the kernel writes exactly this layout from the data pointer: anything else would be misread or overrun
+            raise ValueError(f"out: need a C-contiguous {typestr} array of shape {shape}, got shape {tuple(ai['shape'])}, "
+                             f"typestr {ai['typestr']!r}, strides {strides}")
+        ptr = ai["data"][0]
         ip = C.POINTER(C.c_int32)
         flags = (_ffi.OBS_CHW if chw else 0) | (_ffi.OBS_F32 if normalize else 0)
         if interpolation == "cv_cubic":

@@ -409,7 +409,9 @@ int dtsim_allgather_frames(dtsim_t* h, void* nccl_comm, void* recv, const void* 
  * :57-69).  `taps_*` are Pillow's per-output-coordinate tables (first tap, tap count / fixed-point taps)
  * as built by dtsim/resample.py; pass NULL tables for an axis whose size does not change.
  * out: device pointer to [num_envs][out_h][out_w][3] (DTSIM_OBS_HWC) or [num_envs][3][out_h][out_w]
- * (DTSIM_OBS_CHW), uint8 or float32 (DTSIM_OBS_F32).  Asynchronous, stream-ordered after dtsim_render. */
+ * (DTSIM_OBS_CHW), uint8 or float32 (DTSIM_OBS_F32).  Asynchronous, stream-ordered after dtsim_render.
+ * The handle keeps one device copy of the tables, keyed on their contents (and the output size): a call whose
+ * tables differ from the cached ones re-validates and re-uploads them, whatever the output size. */
 enum { DTSIM_OBS_HWC = 0, DTSIM_OBS_CHW = 1, DTSIM_OBS_F32 = 2 };
 int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                   const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,

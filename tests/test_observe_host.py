@@ -70,3 +70,29 @@ def test_power_of_two_scales_have_uniform_small_integer_taps(n_in, n_out, S):
         assert bounds[o, 0] == S * o - S // 2 and bounds[o, 1] == 2 * S
         assert kk[o, :2 * S].tolist() == [w << shift for w in tri]
     assert bounds[0, 0] == 0 and bounds[0, 1] < 2 * S and bounds[-1, 0] + bounds[-1, 1] == n_in
+
+
+def test_taps_past_each_count_are_zero_on_random_sizes():
+    """k_observe's 9-tap window multiplies ALL nine taps of a column over the bytes after its window (real pixels of the row, or
+    whatever follows it): only zero-filled taps past each coordinate's count keep that exact.  Fuzz against Pillow: the horizontal
+    pass computed the kernel's way -- nine taps over a row padded with 255 -- equals Image.resize along x."""
+    from PIL import Image
+    rng = np.random.default_rng(321)
+    for _ in range(60):
+        W, ow = int(rng.integers(1, 400)), int(rng.integers(1, 200))
+        bounds, kk = resample.coeffs(W, ow)
+        for o in range(ow):
+            assert np.all(kk[o, bounds[o, 1]:] == 0), (W, ow, o)
+        assert np.all(bounds[:, 1] <= kk.shape[1]) and np.all(bounds[:, 0] + bounds[:, 1] <= W)
+        if kk.shape[1] > 9:
+            continue
+        H = int(rng.integers(1, 5))
+        img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        row = np.concatenate([img, np.full((H, 9, 3), 255, np.uint8)], axis=1).astype(np.int64)
+        k9 = np.zeros((ow, 9), np.int64)
+        k9[:, :kk.shape[1]] = kk
+        idx = bounds[:, :1].astype(np.int64) + np.arange(9)[None, :]
+        acc = np.einsum("ot,hotc->hoc", k9, row[:, idx]) + (1 << (resample.PRECISION_BITS - 1))
+        got = np.clip(acc >> resample.PRECISION_BITS, 0, 255).astype(np.uint8)
+        want = np.asarray(Image.fromarray(img).resize((ow, H), Image.BILINEAR))
+        assert np.array_equal(got, want), (W, ow)
