@@ -885,11 +885,6 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
   R.distortion = (h->cfg.flags & DTSIM_F_DISTORTION) ? 1 : 0;
   R.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
   R.n_maps = h->M.n_maps;
-#ifdef DT_RASTER_NO_MSAA   // profiling ablation, tools/build_variant.sh only: never in the product build
-  R.no_msaa = 1;
-#else
-  R.no_msaa = 0;
-#endif
   R.frames = h->frames; R.lut = h->d_lut; R.texels = segment ? h->d_texels_seg : h->d_texels; R.tex = h->d_tex;
   R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg;
   R.maps = h->d_rmaps; R.tiles = h->d_rtiles; R.objs = h->d_robjs; R.meshes = h->d_meshes; R.tris = h->d_tris;
@@ -941,30 +936,10 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
     if (FILE* f = fopen(getenv("DTSIM_WAVE_SPANS"), "wb")) { fwrite(sp.data(), 8, sp.size(), f); fclose(f); }
   }
 #endif
-  if (getenv("DTSIM_DEBUG_QUEUE") || getenv("DTSIM_DEBUG_TIMERS")) {   // profiling aid: how many pixels took the exact MSAA path (DEBUG_TIMERS: without the in-kernel counters)
+  if (getenv("DTSIM_DEBUG_QUEUE")) {   // profiling aid: how many pixels took the exact MSAA path
     HIPCHK(hipStreamSynchronize(h->stream));
-    {  // phase timers of the DT_Q_TIMING build variant (zero otherwise)
-      unsigned long long tc[4];
+    {
       char* dbgp = (char*)h->d_pixtab + (size_t)R.W * R.H * 64 + 1024;
-      HIPCHK(hipMemcpy(tc, dbgp, sizeof tc, hipMemcpyDeviceToHost));
-      if (tc[3]) fprintf(stderr, "[dtsim] k_raster_q phase cycles per wavefront iteration: issue %.0f, wait for quads %.0f, filter+slow+transpose %.0f  (%llu iterations)\n",
-                         (double)tc[0] / tc[3], (double)tc[1] / tc[3], (double)tc[2] / tc[3], tc[3]);
-      HIPCHK(hipMemset(dbgp, 0, sizeof tc));
-      unsigned long long t3[8];                      // DT_V3_TIMING build variant: k_raster_v3 phase cycles (second KB of the scratch)
-      HIPCHK(hipMemcpy(t3, dbgp + 512, sizeof t3, hipMemcpyDeviceToHost));
-      if (t3[7]) fprintf(stderr, "[dtsim] k_raster_v3 cycles per wavefront iteration (wall clock of the wavefront): issue %.0f, store+prefetch %.0f, "
-                         "wait for the records %.0f, weights+filter %.0f, transpose %.0f, slow+append %.0f; whole iteration %.0f  (%llu iterations)\n",
-                         (double)t3[0] / t3[7], (double)t3[1] / t3[7], (double)t3[2] / t3[7], (double)t3[3] / t3[7], (double)t3[4] / t3[7],
-                         (double)t3[5] / t3[7], (double)t3[6] / t3[7], t3[7]);
-      HIPCHK(hipMemset(dbgp + 512, 0, sizeof t3));
-      unsigned long long tr[13];                     // DT_RES_TIMING build variant: k_resolve phase cycles
-      HIPCHK(hipMemcpy(tr, dbgp + 64, sizeof tr, hipMemcpyDeviceToHost));
-      if (tr[8]) fprintf(stderr, "[dtsim] k_resolve cycles per wavefront: total %.0f = item setup %.0f + entry load %.0f + mesh stream %.0f + z-buffer %.0f + shade %.0f; "
-                         "%.1f items, %.1f batches per wavefront (%llu wavefronts)\n", (double)tr[7] / tr[8], (double)tr[0] / tr[8], (double)tr[1] / tr[8], (double)tr[2] / tr[8],
-                         (double)tr[3] / tr[8], (double)tr[4] / tr[8], (double)tr[6] / tr[8], (double)tr[5] / tr[8], tr[8]);
-      if (tr[8]) fprintf(stderr, "[dtsim] k_resolve: longest wavefront %llu, longest batch %llu cycles; %llu (batch, env) pairs with objects in %llu batches, at most %llu in one batch\n",
-                         tr[9], tr[10], tr[11], tr[5], tr[12]);
-      HIPCHK(hipMemset(dbgp + 64, 0, sizeof tr));
       int32_t ro[12];                                // DT_RO_STATS build variant: k_resolve_obj's z-buffer
       HIPCHK(hipMemcpy(ro, dbgp + 768, sizeof ro, hipMemcpyDeviceToHost));
       unsigned long long rp; memcpy(&rp, ro + 6, 8);

@@ -192,7 +192,7 @@ static inline size_t dt_raster_tiles(int W, int H) {
 
 struct RenderParams {
   int32_t N, W, H, distortion;
-  int32_t domain_rand, n_maps, n_tile_recs, no_msaa;   // no_msaa: profiling ablation only (-DDT_RASTER_NO_MSAA build variant)
+  int32_t domain_rand, n_maps, n_tile_recs;
   int32_t tex_w, tex_h;           // all tile textures share one (power-of-two) size
   const TileLds* tile_recs;       // [n_tile_recs], maps concatenated (RenderMapDev.tile_off)
   uint8_t* frames;

@@ -31,7 +31,7 @@
 //                 texture index, traffic-light card by pattern, segmentation colour), reduces per-object screen boxes
 //                 and writes, per (env, block), the mask of the objects whose box meets the block.
 //   k_raster_q<OBJ,S256> (shared camera, square power-of-two tile textures): quad-record one-ray path +
-//                 the exact path of plane-edge pixels inside the same wavefronts (resolve_region).
+//                 the exact path of plane-edge pixels inside the same wavefronts (resolve_region_q).
 //   k_raster_v3<OBJ> (render_v3.inc; 256 x 256 tile textures, the BASELINE configurations): k_raster_q on an instruction diet -- the
 //                 headline kernel; k_raster_v3dr<OBJ> (render_v3dr.inc): domain randomisation on the same records (per-env homography).
 //   k_env_sort:   render order of the envs for the quad-record paths (tile under the camera, heading quadrant): an XCD's L2 serves one
@@ -1164,7 +1164,7 @@ __device__ inline PixInv pix_inv_dr(float nx, float ny, bool valid, const DrCam&
 // stored for it is not final: k_resolve_obj leaves a pixel alone when no mesh triangle covers any of its samples and the
 // bit is clear (the raster's one-ray colour is the pixel).  k_raster_v3 / k_raster_v3dr tell; the other rasters always set it.
 #define QE_PLANE_EDGE 0x8000u
-#define QE_ALWAYS_EDGE 0x4000u    // plane-edge entries of k_raster_v3 (front of the region): never a one-ray pixel (resolve_region skips its interior test)
+#define QE_ALWAYS_EDGE 0x4000u    // front-of-region entry that is never a one-ray pixel (resolve_region_q skips its interior test); no raster sets it at present
 static_assert(ENVS_PER_BLOCK <= 64, "the env position of a queue entry has six bits");
 #define ITEM_B DT_ITEM_B   // 64-entry batches per k_resolve work item
 #define ITEMS_PER_WG DT_ITEMS_PER_WG
@@ -1469,7 +1469,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
 #pragma unroll
     for (int k = 0; k < PPT; ++k) { any_oedge |= oedge[k]; edge[k] &= !oedge[k]; any_edge |= edge[k]; }
     const uint32_t etag = (uint32_t)(e - e0) << 8;
-    if (OBJ && !R.no_msaa && __ballot(any_oedge)) {    // wave-uniform: object-box pixels fill the region from its far end
+    if (OBJ && __ballot(any_oedge)) {    // wave-uniform: object-box pixels fill the region from its far end
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {
         const bool ek = oedge[k];
@@ -1481,7 +1481,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
         qo += __popcll(mk);
       }
     }
-    if (!R.no_msaa && __ballot(any_edge)) {    // wave-uniform
+    if (__ballot(any_edge)) {    // wave-uniform
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {                // per pixel slot: ballot -> rank -> masked store
         const bool ek = edge[k];
@@ -1503,7 +1503,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
   __shared__ int s_nb[RB / 64], s_no[RB / 64];
   if (lane == 0) { s_nb[wave] = (qn + 63) >> 6; s_no[wave] = qo; }
   __syncthreads();
-  if (tid == 0 && !R.no_msaa) {
+  if (tid == 0) {
     int nb = 0, no = 0;
 #pragma unroll
     for (int r = 0; r < RB / 64; ++r) { nb += s_nb[r]; no += s_no[r]; }
@@ -1577,7 +1577,7 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
 
 __device__ inline float med3f(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
 
-// ---- resolve_region: exact path of the quad-layout pipeline (shared camera, no mesh objects) ----------------------
+// ---- resolve_region_q: exact path of k_raster_q (shared camera, no mesh objects) ------------------------------------
 // Called by every wavefront of k_raster_q at the end of its env loop on ITS OWN queue region (the entries it appended):
 // no second launch, no work list, no atomics -- and the gather-bound resolve of one wavefront overlaps the VALU-bound
 // env loops of the other wavefronts on the CU.  Per entry (one pixel of one env):
@@ -1591,6 +1591,7 @@ __device__ inline float med3f(float x, float lo, float hi) { return __builtin_am
 //      +-50 m; else the clear colour), shading once per distinct primitive at the pixel centre (GL semantics:
 //      simulator.py:1932-1934, graphics.py:172-251): a tile is shaded with ITS texture at the centre hit -- outside the
 //      tile the coordinate wraps (GL_REPEAT), which the quad records encode -- times the centre's lit factor.
+// k_raster_v3 drains its regions with its own exact path, resolve_region_v3 (render_v3.inc): no interior test, no list.
 // ---- the quad-record filter ("dtsim8") -------------------------------------------------------------------
 // GL's own filter (llvmpipe: gl_linear_rgb above) works with 8-bit weights and 8-bit intermediates, so nothing is gained by filtering
 // finer than that; the quad pipeline filters in ONE v_dot4_u32_u8 per channel: the four bilinear weights, times the lit factor
@@ -1664,30 +1665,28 @@ __device__ inline void quad_filter3(const uint4& q, float a8, float b8, float I,
 }
 
 #define RQ_LIST 256                                  // MSAA entries compacted per round (the wavefront's 1 KB of LDS)
-// V3: the LDS tile table layout of k_raster_v3 (render_v3.inc: block offset at (tz << 10 | tx << 2) + the map's column
-// offset EnvQ.pad[0], the record-offset mask 512 bytes behind it) and its wavefront block shape; (tile_x0, wave_y0) is the
-// origin of the wavefront's block either way.
-// POOL (k_raster_v3, round 3): the four queue regions of a workgroup are drained as ONE list, an equal share per wavefront.
-// w_queue = region 0 of the workgroup, (tile_x0, wave_y0) = origin of the workgroup tile, the wavefront's share = entries
-// [i0, i0 + n) of the concatenation, (p1, p2, p3) = where regions 1..3 start in it.  Per wavefront the regions hold anything
-// from nothing (sky blocks) to several hundred entries (a seam along the block): pooled, the 64-entry batches run full and
-// no wavefront of a workgroup idles while another drains its seam.
+// one pixel's colour 0x00BBGGRR into frame e of the exact paths' byte patches: two stores, a 2-byte aligned half + one byte,
+// whichever way the pixel's 3 bytes fall
+__device__ inline void store_rgb(uint8_t* frames, const int npix, const int e, const int pix, const uint32_t rgb) {
+  uint8_t* dst = frames + ((size_t)e * npix + pix) * 3;
+  const bool odd = (reinterpret_cast<uintptr_t>(dst) & 1u) != 0u;
+  uint8_t* p8 = odd ? dst : dst + 2;
+  uint16_t* p16 = reinterpret_cast<uint16_t*>(odd ? dst + 1 : dst);
+  *p8 = (uint8_t)(odd ? rgb : rgb >> 16);
+  *p16 = (uint16_t)(odd ? rgb >> 8 : rgb);
+}
 // LIGHT: the shared camera with per-env lights (EnvL in render order, envl): the lit factor of the tile plane is env_lit8's, per entry.
-template <bool S256, bool V3 = false, bool POOL = false, bool LIGHT = false>
-__device__ inline void resolve_region(const RenderParams& R, const EnvCam* __restrict__ cams, const EnvQ* __restrict__ envq,
-                                      const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab,
-                                      const uint8_t* __restrict__ qtex, const uint32_t* s_qt, uint32_t* w_list,
-                                      const uint16_t* w_queue, const int n, const int e0, const int tile_x0, const int wave_y0,
-                                      const int lane, const int i0 = 0, const int p1 = 0, const int p2 = 0, const int p3 = 0,
-                                      const uint4* s_envq = nullptr, const EnvL* __restrict__ envl = nullptr) {
-  // s_envq (V3): the EnvQ records of the chunk's 64 positions, staged in LDS by the workgroup -- an entry's constants are three
-  // ds_read_b128 instead of three 16-byte gathers through the texture unit (in both phases).
+template <bool S256, bool LIGHT = false>
+__device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __restrict__ cams, const EnvQ* __restrict__ envq,
+                                        const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab,
+                                        const uint8_t* __restrict__ qtex, const uint32_t* s_qt, uint32_t* w_list,
+                                        const uint16_t* w_queue, const int n, const int e0, const int tile_x0, const int wave_y0,
+                                        const int lane, const EnvL* __restrict__ envl) {
   const int npix = R.W * R.H;
   const int LS = R.qlog2;
   const uint32_t SM = (1u << LS) - 1u;
   const float Sf = (float)(1 << LS), lo = 0.5f * Sf;
   const char* qtb = reinterpret_cast<const char*>(s_qt);
-  constexpr int WWc = V3 ? DT_V3_WW : WAVE_W;          // pixel columns of the wavefront block the entries index
   const uint32_t tex_min = 32u;                        // block offsets from here on are textured tiles
 
   // Table entry (block byte offset, record-offset mask) of the tile that OWNS padded quad coordinates (X, Z): tile
@@ -1698,10 +1697,6 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
     const float Xc = med3f(X - 0.5f, lo, Xhi), Zc = med3f(Z - 0.5f, lo, Zhi);
     const uint32_t ti = (uint32_t)flr_i32(Xc) >> LS, tj = (uint32_t)flr_i32(Zc) >> LS;
     ox = (float)(ti << LS) + 0.5f; oz = (float)(tj << LS) + 0.5f;
-    if (V3) {
-      ta = (tj << 10) + (ti << 2) + tab_b;
-      return make_uint2(*reinterpret_cast<const uint32_t*>(qtb + ta), *reinterpret_cast<const uint32_t*>(qtb + ta + 512));
-    }
     ta = (ti << 3) + __umul24(tj, pitch4) + tab_b;
     return *reinterpret_cast<const uint2*>(qtb + ta);
   };
@@ -1710,18 +1705,6 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
     if (S256) return *reinterpret_cast<const uint4*>(qtex + (te.x | q8_rec256(xb, zb, te.y)));
     const uint32_t local = (((q8_cell(zb) & SM) << LS) | (q8_cell(xb) & SM)) & te.y;
     return *reinterpret_cast<const uint4*>(qtex + (te.x + (local << 4)));
-  };
-  auto store_rgb = [&](int e, int pix, uint32_t rgb) {
-    uint8_t* dst = R.frames + ((size_t)e * npix + pix) * 3;
-#ifdef DT_Q_ABL_NOPATCH
-    if (rgb != 0x12345678u) return;                  // ablation: what the byte patches cost (traffic, time)
-#endif
-    // two stores: a 2-byte aligned half + one byte, whichever way the pixel's 3 bytes fall
-    const bool odd = (reinterpret_cast<uintptr_t>(dst) & 1u) != 0u;
-    uint8_t* p8 = odd ? dst : dst + 2;
-    uint16_t* p16 = reinterpret_cast<uint16_t*>(odd ? dst + 1 : dst);
-    *p8 = (uint8_t)(odd ? rgb : rgb >> 16);
-    *p16 = (uint16_t)(odd ? rgb >> 8 : rgb);
   };
 
   // ---- phase 1: per entry, the exact interior test; interior entries get the one-ray colour, the others are
@@ -1733,243 +1716,90 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
     constexpr int U = decltype(utag)::value;
     int n_list = 0;                                  // wave-uniform
     bool have[U], interior[U], tagged[U], skip[U];
-      int pix[U], el[U], env[U];
-      PixTab pt[U];
-      float Xu[U], Zu[U];
-      uint2 te_c[U];
+    int pix[U], el[U], env[U];
+    PixTab pt[U];
+    float Xu[U], Zu[U];
+    uint2 te_c[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        have[u] = r0 + u * 64 + lane < n;
-        int qoff = r0 + u * 64 + lane, rx = 0, ry = 0;
-        if (POOL) {                                    // entry of the pooled list -> (region, offset in it)
-          constexpr int wx = DT_TILE_W / WWc, rows = WAVE_PIX / WWc;
-          const int gi = i0 + qoff;
-          const int r = (gi >= p1) + (gi >= p2) + (gi >= p3);
-          qoff = r * QREGION + gi - (r == 0 ? 0 : r == 1 ? p1 : r == 2 ? p2 : p3);
-          rx = (r % wx) * WWc; ry = (r / wx) * rows;
-        }
-        // the entries were written by this wavefront (workgroup) a moment ago: bypass the (possibly stale) L1 line
-        const uint32_t ent = have[u] ? (uint32_t)__builtin_nontemporal_load(w_queue + qoff) : 0u;
-        el[u] = (int)((ent >> 8) & 63u);
-        // QE_ALWAYS_EDGE (k_raster_v3, round 4): the pixel can never be a one-ray pixel (horizon band, near / far limits): it goes to
-        // the list without the interior test -- and without its loads when the whole batch is such (these entries come in runs)
-        tagged[u] = (ent & QE_ALWAYS_EDGE) != 0u;
-#ifndef DT_Q_V3_PHASE1                                // (A/B aid: -DDT_Q_V3_PHASE1 restores the interior test for k_raster_v3's entries)
-        // k_raster_v3 (round 6): NO interior test -- every entry takes the four samples.  The test resolved 30 % of the entries with one record but cost
-        // as much as the four-sample phase (a table gather, a record gather and two patches per entry, latency-bound): without it the exact path is
-        // 0.10 ms shorter (profiles/r06_variants_ab.txt block E); an interior pixel's four samples give the one-ray colour anyway.
-        if (V3) tagged[u] = true;
-#endif
-        skip[u] = !__ballot(have[u] && !tagged[u]);    // wave-uniform
-        const int lp = (int)(ent & 255u);
-        pix[u] = (wave_y0 + ry + lp / WWc) * R.W + tile_x0 + rx + lp % WWc;
+    for (int u = 0; u < U; ++u) {
+      have[u] = r0 + u * 64 + lane < n;
+      const int qoff = r0 + u * 64 + lane;
+      // the entries were written by this wavefront (workgroup) a moment ago: bypass the (possibly stale) L1 line
+      const uint32_t ent = have[u] ? (uint32_t)__builtin_nontemporal_load(w_queue + qoff) : 0u;
+      el[u] = (int)((ent >> 8) & 63u);
+      // QE_ALWAYS_EDGE: the pixel can never be a one-ray pixel (horizon band, near / far limits): it goes to the list without
+      // the interior test -- and without its loads when the whole batch is such (these entries come in runs)
+      tagged[u] = (ent & QE_ALWAYS_EDGE) != 0u;
+      skip[u] = !__ballot(have[u] && !tagged[u]);    // wave-uniform
+      const int lp = (int)(ent & 255u);
+      pix[u] = (wave_y0 + lp / WAVE_W) * R.W + tile_x0 + lp % WAVE_W;
+    }
+    float4 qa[U];
+    uint4 qb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      qa[u] = make_float4(0.f, 0.f, 0.f, 0.f); qb[u] = make_uint4(0u, 0u, 0u, 0u); env[u] = 0;
+      pt[u] = PixTab{0.f, 0.f, 0.f, 0xFFFFu};
+      if (skip[u]) continue;                         // wave-uniform
+      pt[u] = pixtab[pix[u]];
+      const EnvQ* fq = envq + min(e0 + el[u], R.N - 1);   // position in the render order -> constants, frame index
+      qa[u] = *reinterpret_cast<const float4*>(&fq->A);     // A, B, Cx, Cz
+      qb[u] = *reinterpret_cast<const uint4*>(&fq->Xhi);    // Xhi, Zhi, tab_b, pitch4
+      const uint4 qd = *reinterpret_cast<const uint4*>(&fq->reach);   // reach, env, pad[0], pad[1] (one 16-byte piece: the path is bound by its vector-memory instruction count)
+      env[u] = (int)qd.y;
+      if constexpr (LIGHT) { const EnvL l = envl[min(e0 + el[u], R.N - 1)]; pt[u].lit = pt[u].lit > 0.f ? 256.f * env_lit8(l, pt[u].lr, pt[u].lf, env_base8()) : pt[u].lit; }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      interior[u] = false; Xu[u] = Zu[u] = 0.f; te_c[u] = make_uint2(0u, 0u);
+      if (skip[u]) continue;                         // wave-uniform
+      const float A = qa[u].x, B = qa[u].y, Cx = qa[u].z, Cz = qa[u].w;
+      const float Xhi = __uint_as_float(qb[u].x), Zhi = __uint_as_float(qb[u].y);
+      Xu[u] = fmaf(pt[u].lf, B, fmaf(pt[u].lr, A, Cx)); Zu[u] = fmaf(pt[u].lf, -A, fmaf(pt[u].lr, B, Cz));
+      uint32_t ta_c;
+      float ox, oz;
+      te_c[u] = tile_entry(Xu[u], Zu[u], Xhi, Zhi, qb[u].z, qb[u].w, ta_c, ox, oz);
+      // distance of the hit to the boundary of the tile that owns it, in cells, against the MSAA reach
+      const float mrg = __half2float(__ushort_as_half((unsigned short)(pt[u].mi >> 16)));   // metres, rounded up
+      const float ux = Xu[u] - ox, uz = Zu[u] - oz;        // in [0, S) inside the owner tile
+      const float d = fminf(fminf(ux, Sf - ux), fminf(uz, Sf - uz));
+      const bool in_range = Xu[u] - 0.5f >= lo && Xu[u] - 0.5f <= Xhi && Zu[u] - 0.5f >= lo && Zu[u] - 0.5f <= Zhi;
+      interior[u] = have[u] && !tagged[u] && in_range && te_c[u].x >= tex_min && pt[u].lit > 0.f && (pt[u].mi & 0xFFFFu) < 0xFFF0u && d > mrg * R.q_per_m;
+    }
+    uint4 qc[U];
+#pragma unroll
+    // only the INTERIOR entries (~ 30 %) use the record: the gather runs under their lanes -- its cost on the texture path is per distinct line
+    for (int u = 0; u < U; ++u) { qc[u] = make_uint4(0u, 0u, 0u, 0u); if (!skip[u] && interior[u]) qc[u] = tile_quad(te_c[u], q8_bits(Xu[u]), q8_bits(Zu[u])); }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (!skip[u]) {                                // wave-uniform
+        const uint32_t rgb = quad_filter(qc[u], q8_frac(q8_bits(Xu[u])), q8_frac(q8_bits(Zu[u])), pt[u].lit);
+        if (interior[u]) store_rgb(R.frames, npix, env[u], pix[u], rgb);
       }
-      float4 qa[U];
-      uint4 qb[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        qa[u] = make_float4(0.f, 0.f, 0.f, 0.f); qb[u] = make_uint4(0u, 0u, 0u, 0u); env[u] = 0;
-        pt[u] = PixTab{0.f, 0.f, 0.f, 0xFFFFu};
-        if (skip[u]) continue;                       // wave-uniform
-#ifdef DT_ABL_P1_NOPIXTAB                              // ablation (wrong frames): what phase 1's per-entry table gather costs
-        pt[u] = PixTab{0.3f + 1e-3f * (float)lane, 0.4f, 0.7f, 0x3c000001u};
-#else
-        pt[u] = pixtab[pix[u]];
-#endif
-        uint4 qd;
-        if (V3 && s_envq) {
-          const uint4* fl = s_envq + el[u] * 4;
-          const uint4 a4 = fl[0];
-          qa[u] = make_float4(__uint_as_float(a4.x), __uint_as_float(a4.y), __uint_as_float(a4.z), __uint_as_float(a4.w));
-          qb[u] = fl[1]; qd = fl[3];
-        } else {
-          const EnvQ* fq = envq + min(e0 + el[u], R.N - 1);   // position in the render order -> constants, frame index
-          qa[u] = *reinterpret_cast<const float4*>(&fq->A);     // A, B, Cx, Cz
-          qb[u] = *reinterpret_cast<const uint4*>(&fq->Xhi);    // Xhi, Zhi, tab_b, pitch4
-          qd = *reinterpret_cast<const uint4*>(&fq->reach);   // reach, env, pad[0], pad[1] (one 16-byte piece: the path is bound by its vector-memory instruction count)
-        }
-        if (V3) qb[u].z = qd.z;
-        env[u] = (int)qd.y;
-        if constexpr (LIGHT) { const EnvL l = envl[min(e0 + el[u], R.N - 1)]; pt[u].lit = pt[u].lit > 0.f ? 256.f * env_lit8(l, pt[u].lr, pt[u].lf, env_base8()) : pt[u].lit; }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        interior[u] = false; Xu[u] = Zu[u] = 0.f; te_c[u] = make_uint2(0u, 0u);
-        if (skip[u]) continue;                       // wave-uniform
-        const float A = qa[u].x, B = qa[u].y, Cx = qa[u].z, Cz = qa[u].w;
-        const float Xhi = __uint_as_float(qb[u].x), Zhi = __uint_as_float(qb[u].y);
-        Xu[u] = fmaf(pt[u].lf, B, fmaf(pt[u].lr, A, Cx)); Zu[u] = fmaf(pt[u].lf, -A, fmaf(pt[u].lr, B, Cz));
-        uint32_t ta_c;
-        float ox, oz;
-        te_c[u] = tile_entry(Xu[u], Zu[u], Xhi, Zhi, qb[u].z, qb[u].w, ta_c, ox, oz);
-        // distance of the hit to the boundary of the tile that owns it, in cells, against the MSAA reach
-        const float mrg = __half2float(__ushort_as_half((unsigned short)(pt[u].mi >> 16)));   // metres, rounded up
-        const float ux = Xu[u] - ox, uz = Zu[u] - oz;        // in [0, S) inside the owner tile
-        const float d = fminf(fminf(ux, Sf - ux), fminf(uz, Sf - uz));
-        const bool in_range = Xu[u] - 0.5f >= lo && Xu[u] - 0.5f <= Xhi && Zu[u] - 0.5f >= lo && Zu[u] - 0.5f <= Zhi;
-        interior[u] = have[u] && !tagged[u] && in_range && te_c[u].x >= tex_min && pt[u].lit > 0.f && (pt[u].mi & 0xFFFFu) < 0xFFF0u && d > mrg * R.q_per_m;
-      }
-      uint4 qc[U];
-#pragma unroll
-#ifdef DT_Q_P1_LOAD_ALL                                // A/B aid (round 5 behaviour): every lane gathers its record, interior or not
-      for (int u = 0; u < U; ++u) { qc[u] = make_uint4(0u, 0u, 0u, 0u); if (!skip[u]) qc[u] = tile_quad(te_c[u], q8_bits(Xu[u]), q8_bits(Zu[u])); }   // always in bounds (record 0 / 1 for non-tiles)
-#else
-      // only the INTERIOR entries (~ 30 %) use the record: the gather runs under their lanes -- its cost on the texture path is per distinct line
-      for (int u = 0; u < U; ++u) { qc[u] = make_uint4(0u, 0u, 0u, 0u); if (!skip[u] && interior[u]) qc[u] = tile_quad(te_c[u], q8_bits(Xu[u]), q8_bits(Zu[u])); }
-#endif
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (!skip[u]) {                                // wave-uniform
-          const uint32_t rgb = quad_filter(qc[u], q8_frac(q8_bits(Xu[u])), q8_frac(q8_bits(Zu[u])), pt[u].lit);
-#ifdef DT_ABL_P1_NOSTORE
-          if (interior[u] && rgb == 0x12345678u) store_rgb(env[u], pix[u], rgb);
-#else
-          if (interior[u]) store_rgb(env[u], pix[u], rgb);
-#endif
-        }
-        const bool msaa = have[u] && !interior[u];
-        const unsigned long long mm = __ballot(msaa);
-        if (msaa) w_list[n_list + __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u))] = (uint32_t)pix[u] | ((uint32_t)el[u] << 24);
-        n_list += __popcll(mm);
-      }
+      const bool msaa = have[u] && !interior[u];
+      const unsigned long long mm = __ballot(msaa);
+      if (msaa) w_list[n_list + __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u))] = (uint32_t)pix[u] | ((uint32_t)el[u] << 24);
+      n_list += __popcll(mm);
+    }
     return n_list;
   };
-#ifdef DT_Q_V3_PHASE1
-  constexpr bool DIRECT = false;
-#else
-  constexpr bool DIRECT = V3 && !POOL;                 // k_raster_v3 (round 6): the queue entries ARE the list -- no interior test, no compaction, no LDS round trip
-#endif
   for (int r0 = 0; r0 < n; r0 += RQ_LIST) {          // wave-uniform: rounds of up to RQ_LIST entries
     const int rem = n - r0;
-    int n_list;
-    if constexpr (DIRECT) n_list = min(rem, RQ_LIST);
-    else {
-      n_list = rem > 128 ? phase1(std::integral_constant<int, 4>{}, r0)
-             : rem > 64 ? phase1(std::integral_constant<int, 2>{}, r0) : phase1(std::integral_constant<int, 1>{}, r0);
-      // ---- phase 2: the four samples of the listed pixels, on dense lanes
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-#ifdef DT_Q_ABL_NOPHASE2
-    for (int l0 = 0; l0 < 0; l0 += 64) {
-#else
+    const int n_list = rem > 128 ? phase1(std::integral_constant<int, 4>{}, r0)
+                     : rem > 64 ? phase1(std::integral_constant<int, 2>{}, r0) : phase1(std::integral_constant<int, 1>{}, r0);
+    // ---- phase 2: the four samples of the listed pixels, on dense lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int l0 = 0; l0 < n_list; l0 += 64) {          // wave-uniform
-#endif
       const bool have = l0 + lane < n_list;
-      int pix, el;
-      if constexpr (DIRECT) {
-        // the entries were written by this wavefront a moment ago: bypass the (possibly stale) L1 line
-        const uint32_t ent = have ? (uint32_t)__builtin_nontemporal_load(w_queue + r0 + l0 + lane) : 0u;
-        const int lp = (int)(ent & 255u);
-        el = (int)((ent >> 8) & 63u);
-        pix = have ? (wave_y0 + lp / WWc) * R.W + tile_x0 + lp % WWc : 0;
-      } else {
-        const uint32_t le = have ? w_list[l0 + lane] : 0u;
-        pix = (int)(le & 0xFFFFFFu); el = (int)(le >> 24);
-      }
-#ifdef DT_ABL_P2_NOSAMPTAB                             // ablation (wrong frames): what phase 2's per-entry table gathers cost
-      SampTab sp = samptab[lane];
-#else
+      const uint32_t le = have ? w_list[l0 + lane] : 0u;
+      const int pix = (int)(le & 0xFFFFFFu), el = (int)(le >> 24);
       const SampTab sp = samptab[pix];
-#endif
-      PixTab pt;
-      if constexpr (V3) { pt.lr = __uint_as_float(sp.pad[0]); pt.lf = __uint_as_float(sp.pad[1]); pt.lit = __uint_as_float(sp.pad[2]); pt.mi = 0u; }   // (one table, two 16-byte loads)
-      else pt = pixtab[pix];
+      const PixTab pt = pixtab[pix];
       const EnvQ* fq = envq + min(e0 + el, R.N - 1);
-      if constexpr (V3) {
-        // k_raster_v3's version (round 3): no list of distinct primitives.  The colour of a pixel is the sum over its four
-        // samples of the shade of the sample's primitive AT THE PIXEL CENTRE (GL: graphics.py:172-251), so every tile
-        // sample adds the integer filter of ITS tile's record at the centre cell (same cell index and weights for every
-        // tile: the blocks share one cell grid; a sample that is not on a tile reads the all-zero record 0) to one
-        // accumulator per channel -- 6 v_dot4 per sample, exact -- and sky / ground samples add their colour once per
-        // count.  Tile look-ups go by v_perm like the env loop's; the +-50 m ground-quad test is made in quad coordinates.
-        // the env's constants as three 16-byte pieces (round 5: the exact path is bound by the NUMBER of vector-memory instructions it issues)
-        float4 qa;
-        uint4 qb, qd;
-        if (s_envq) {
-          const uint4* fl = s_envq + el * 4;
-          const uint4 a4 = fl[0];
-          qa = make_float4(__uint_as_float(a4.x), __uint_as_float(a4.y), __uint_as_float(a4.z), __uint_as_float(a4.w));
-          qb = fl[1]; qd = fl[3];
-        } else {
-          qa = *reinterpret_cast<const float4*>(&fq->A);
-          qb = *reinterpret_cast<const uint4*>(&fq->Xhi); qd = *reinterpret_cast<const uint4*>(&fq->reach);
-        }
-        const float A = qa.x, B = qa.y, Cx = qa.z, Cz = qa.w, Xhi = __uint_as_float(qb.x), Zhi = __uint_as_float(qb.y);
-        const uint32_t tab = qd.z;
-        const int e = (int)qd.y;
-        const float4* c4 = reinterpret_cast<const float4*>(cams + e);   // EnvCam as 16-byte pieces: [2] = {ty, hor[3]}, [3] = {gnd[3], base0}, [4] = {base1, base2, dif0, dif1}, [5] = {dif2, L..}, [6] = {L3, gndl[0..2]}, [7] = {gndl3, ..}
-        const float wCy = default_cam((float)R.W / (float)R.H).Cy;      // shared camera: the same height for every env (what k_cam_setup wrote)
-        const float kg = (wCy - GROUND_Y) / wCy;
-        const float qpm = __uint_as_float(qd.w);                           // quad cells per metre of the env's map
-        const float goff = (float)DT_QRING * Sf + 0.5f, ghalf = GROUND_HALF * qpm;   // world 0 and 50 m in padded quad coordinates
-        const float Xu = fmaf(pt.lf, B, fmaf(pt.lr, A, Cx)), Zu = fmaf(pt.lf, -A, fmaf(pt.lr, B, Cz));
-        const uint32_t xic = q8_bits(Xu), zic = q8_bits(Zu);              // the centre's snapped coordinates: q8_rec256 works on these bits
-        float lit8 = (pt.lit > 0.f ? pt.lit : 0.55f) * Q8_LIT;
-        if constexpr (LIGHT) { if (pt.lit > 0.f) lit8 = env_lit8(envl[min(e0 + el, R.N - 1)], pt.lr, pt.lf, env_base8()); }
-        const uint32_t W8 = quad_weights8(q8_frac(xic), q8_frac(zic), lit8);
-        uint32_t aS[3] = {0u, 0u, 0u};                 // sum over the samples of the byte-weight filter of each sample's record
-        int n_sky = 0, n_gnd = 0;
-        float gX = 0.f, gZ = 0.f;                      // ground hit (quad coordinates) of the lowest-index ground sample
-        uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t raddr_prev = 0u;
-#pragma unroll
-        for (int s = 3; s >= 0; --s) {
-          const uint32_t hr = sp.dlr[s >> 1], hf = sp.dlf[s >> 1];
-          const float slr = pt.lr + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hr >> 16 : hr)));
-          const float slf = pt.lf + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hf >> 16 : hf)));
-          const float Xs = fmaf(slf, B, fmaf(slr, A, Cx)), Zs = fmaf(slf, -A, fmaf(slr, B, Cz));
-          // the tile that OWNS the sample (ownership on (X - 0.5, Z - 0.5), clamped into the padded grid)
-          const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
-          const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
-          const bool s_in = (Xc == Xo) & (Zc == Zo);
-          const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
-          const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
-          const uint32_t tb = tp[0], sel = tp[128];
-          const bool is_tile = have & (((sp.flags >> s) & 1u) != 0u) & s_in & (tb != 0u);
-          // ground-quad hit of the sample: camera + kg * (tile-plane hit - camera), inside +-50 m
-          const float Xg = fmaf(kg, Xs - Cx, Cx), Zg = fmaf(kg, Zs - Cz, Cz);
-          const bool is_gnd = have & !is_tile & (((sp.flags >> (4 + s)) & 1u) != 0u) & (fabsf(Xg - goff) <= ghalf) & (fabsf(Zg - goff) <= ghalf);
-          n_gnd += is_gnd; n_sky += !(is_tile | is_gnd);
-          if (is_gnd) { gX = Xg; gZ = Zg; }
-          // one record per DISTINCT tile among the pixel's samples (round 4: the path is texture-unit heavy, its gathers fully divergent;
-          // the samples of most edge pixels share a tile, or are not on a tile at all): a lane loads only when its address changes
-          const uint32_t raddr = is_tile ? (tb | q8_rec256(xic, zic, sel)) : 0u;
-          if (s == 3 || raddr != raddr_prev) rec = *reinterpret_cast<const uint4*>(qtex + raddr);
-          raddr_prev = raddr;
-          aS[0] = __builtin_amdgcn_udot4(rec.x, W8, aS[0], false);
-          aS[1] = __builtin_amdgcn_udot4(rec.y, W8, aS[1], false);
-          aS[2] = __builtin_amdgcn_udot4(rec.z, W8, aS[2], false);
-        }
-        float acc[3];
-        float4 hc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (__ballot(n_sky > 0)) hc = c4[2];           // wave-uniform: the horizon colour only where some sample sees the sky
-        acc[0] = fmaf((float)n_sky, hc.y, (float)aS[0] * (1.f / 256.f));
-        acc[1] = fmaf((float)n_sky, hc.z, (float)aS[1] * (1.f / 256.f));
-        acc[2] = fmaf((float)n_sky, hc.w, (float)aS[2] * (1.f / 256.f));
-        if (__ballot(n_gnd > 0)) {                     // wave-uniform: shade the ground quad (lit at its corners, bilinear)
-          if (pt.lit > 0.f && (pt.lr != 0.f || pt.lf != 0.f)) { gX = fmaf(kg, Xu - Cx, Cx); gZ = fmaf(kg, Zu - Cz, Cz); }   // the centre ray hits the planes
-          const float hs = 0.5f / ghalf;
-          const float a_ = fminf(fmaxf(fmaf(gX - goff, hs, 0.5f), 0.f), 1.f), b_ = fminf(fmaxf(fmaf(gZ - goff, hs, 0.5f), 0.f), 1.f);
-          const float4 q3 = c4[3], q4 = c4[4], q5 = c4[5], q6 = c4[6], q7 = c4[7];
-          const float n0 = q6.y + a_ * (q6.z - q6.y), n1 = q6.w + a_ * (q7.x - q6.w);
-          const float ndl = n0 + b_ * (n1 - n0);
-          const float ng = (float)n_gnd;
-          acc[0] += ng * (q3.x * fminf(q3.w + q4.z * ndl, 1.f));
-          acc[1] += ng * (q3.y * fminf(q4.x + q4.w * ndl, 1.f));
-          acc[2] += ng * (q3.z * fminf(q4.y + q5.x * ndl, 1.f));
-        }
-        const float o[3] = {0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2]};
-#ifdef DT_ABL_P2_NOSTORE
-        if (have && o[0] < -1.f) store_rgb(e, pix, pack_rgb(o));
-#else
-        if (have) store_rgb(e, pix, pack_rgb(o));
-#endif
-        continue;
-      }
       const float A = fq->A, B = fq->B, Cx = fq->Cx, Cz = fq->Cz, Xhi = fq->Xhi, Zhi = fq->Zhi;
-      const uint32_t tab_b = V3 ? fq->pad[0] : fq->tab_b, pitch4 = fq->pitch4;
+      const uint32_t tab_b = fq->tab_b, pitch4 = fq->pitch4;
       const int e = (int)fq->env;
       const EnvCam* c = cams + e;
       const float wCx = c->Cx, wCy = c->Cy, wCz = c->Cz, sa = c->sa, ca = c->ca;
@@ -2035,7 +1865,7 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
         for (int k = 0; k < 3; ++k) acc[k] += (float)cnt * col[k];
       }
       const float o[3] = {0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2]};
-      if (have) store_rgb(e, pix, pack_rgb(o));
+      if (have) store_rgb(R.frames, npix, e, pix, pack_rgb(o));
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -2057,7 +1887,7 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
 //     each axis straddles the seam (half of it belongs to the neighbour tile) and is always an edge;
 //   * all-sky wavefront blocks (env-invariant with the shared camera) take a three-store loop.
 // Anything that is not a fast tile pixel falls into a wave-uniform slow branch that decides ground-fast vs edge and
-// appends edge pixels to the wavefront's queue region; the exact path (resolve_region) drains it at the end of the env loop.
+// appends edge pixels to the wavefront's queue region; the exact path (resolve_region_q) drains it at the end of the env loop.
 // With mesh objects (OBJ) the pixels inside object screen boxes are appended from the far end of the region instead and
 // left to k_resolve_obj.
 
@@ -2067,17 +1897,11 @@ __device__ inline void resolve_region(const RenderParams& R, const EnvCam* __res
 // Frame tiles per group of the launch order: an XCD takes the tiles of a group for one chunk of its slice, then for the next chunk, ..., then the next
 // group.  Round 6: HALF the frame per group (150 tiles at 640 x 480; 10 before) -- with 64 envs per workgroup the tiles of ONE chunk fill an XCD, and the
 // envs of a chunk look at one region of the map (k_env_sort): one L2 serves one region.  C3 - 4.6 %, C5 - 1.8 %; the whole frame as one group is + 5 ... 12 %
-// (profiles/r06_variants_ab.txt block P).  -DDT_Q_TILE_GROUP=n fixes the group size instead (A/B aid).
+// (profiles/r06_variants_ab.txt block P).
 #ifndef DT_Q_TILE_SPLIT
 #define DT_Q_TILE_SPLIT 2
 #endif
-__host__ __device__ inline int dt_q_tile_group(int n_tiles) {
-#ifdef DT_Q_TILE_GROUP
-  return DT_Q_TILE_GROUP;
-#else
-  return (n_tiles + DT_Q_TILE_SPLIT - 1) / DT_Q_TILE_SPLIT;
-#endif
-}
+__host__ __device__ inline int dt_q_tile_group(int n_tiles) { return (n_tiles + DT_Q_TILE_SPLIT - 1) / DT_Q_TILE_SPLIT; }
 #ifndef DT_Q_PRIO
 #define DT_Q_PRIO 3                                  // s_setprio level while a wavefront issues its quad loads (0: off)
 #endif
@@ -2265,7 +2089,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     for (int j = 0; j < PPT / 2; ++j) {
       // two pixels per packed op: X = Cx + lr*A + lf*B, Z = Cz + lr*B - lf*A
       // (+ Q8_SNAP as a third, separate add: ONE rounding to 256ths of a texel; the sum's bits are the fixed-point coordinate, see quad_weights8)
-      const f2 X2 = fma2(lf2[j], vB, fma2(lr2[j], vA, vCx)) + vK;       // (explicit fused multiply-adds in resolve_region's order: the snap makes the last bit visible)
+      const f2 X2 = fma2(lf2[j], vB, fma2(lr2[j], vA, vCx)) + vK;       // (explicit fused multiply-adds in resolve_region_q's order: the snap makes the last bit visible)
       const f2 Z2 = fma2(lf2[j], -vA, fma2(lr2[j], vB, vCz)) + vK;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -2289,13 +2113,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
         const uint32_t tb = te.x;
         if (S256) local = q8_rec256(xb, zb, te.y) >> 4;                        // te.y: mask of the record's byte offset (4 x 2 cells per line), or 0
         else local = (((q8_cell(zb) & SM) << LS) | (q8_cell(xb) & SM)) & te.y; // te.y: cell mask
-#ifdef DT_Q_NO_LOAD
-        st.q[k] = make_uint4(tb + local, tb ^ local, local, 0x00000080u);
-#elif 0
-        st.q[k] = *reinterpret_cast<const uint4*>(qtex + (tb + ((local & 0x3FFu) << 4)));   // ablation: L1-resident taps
-#else
         st.q[k] = *reinterpret_cast<const uint4*>(qtex + (tb + (local << 4)));
-#endif
       }
     }
   };
@@ -2306,14 +2124,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   const uint32_t st_stride = st_ok ? (uint32_t)npix * 3u : 0u;
   auto store = [&](const uint32_t env, const U3& o) __attribute__((always_inline)) {   // env: frame index
     uint32_t* d = reinterpret_cast<uint32_t*>(st_base + (size_t)env * st_stride);
-#if defined(DT_Q_NO_STORE)
-    if (o.a == 0x12345678u) *d = 1u;
-#elif 0
-    *reinterpret_cast<U3*>(d) = o;
-#else
     // non-temporal: the frame is written once and not read back by this pass; keep the taps in L2
     __builtin_nontemporal_store(o.a, d); __builtin_nontemporal_store(o.b, d + 1); __builtin_nontemporal_store(o.c, d + 2);
-#endif
   };
   // Clamping the coordinates into the padded grid (two v_med3 per pixel) is only needed when a hit of this block can
   // leave it: the block's farthest hit (cells, env-invariant) against the camera's distance to the border (per env).
@@ -2370,9 +2182,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
         asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(px[k]) : "v"(hor_v), "v"(rgb), "s"(fm));   // not a one-ray tile pixel: clear colour
       }
     }
-#ifdef DT_Q_ABL_NOSLOW
-    slow = 0ull;
-#endif
     if (slow) {                                      // wave-uniform: some pixel is not a certain tile interior
       // Per pixel slot, and only for the slots that have such lanes (scalar tests on lane masks):
       //   off-grid cell: ground quad, if every sample stays off the grid and inside the quad;
@@ -2461,15 +2270,11 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     store(env, held);
   }
   if (lane == 0) qcount[rwg * (RB / 64) + wave] = OBJ ? qo : qn;
-#ifdef DT_Q_ABL_NORESOLVE
-  if (qn < 0) {
-#else
   if (qn > 0) {
-#endif
     // exact path for this wavefront's own edge pixels, right here (the frame stores of the env loop are ordered
     // before the byte patches: same wavefront, same addresses)
     __builtin_amdgcn_s_waitcnt(0);                 // queue stores have left the wavefront
-    resolve_region<S256, false, false, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, s_px, w_queue, qn, e0, tile_x0, wave_y0, lane, 0, 0, 0, 0, nullptr, envl);
+    resolve_region_q<S256, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, s_px, w_queue, qn, e0, tile_x0, wave_y0, lane, envl);
   }
   }
   if (OBJ) {   // mesh objects: k_resolve_obj drains the object-box entries (back of the regions) -- work items for it
@@ -2720,9 +2525,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
             for (int q = 0; q < 4; ++q) { zbest[j][q] = 0.f; tbest[j][q] = -1; }   // w = 1 / depth: 0 = nothing yet
           }
           unsigned long long hm = hm0;
-#ifdef DT_RO_NOSTREAM
-          hm = 0ull;
-#endif
           if (hm) {
             // ---- mesh pass: stream the triangles of the objects whose screen box meets the tile, 64 at a time (one per
             // lane, coverage half only), keep those whose box meets the bounding box of the unit's pixels, compact them
@@ -2769,16 +2571,12 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                   if (j > 0 && g0 + j * 64 >= n_p) break;            // wave-uniform
-#ifdef DT_RO_NOZ
-                  if (fill == 12345) zbest[j][0] = 0.f;
-#else
                   zbuffer_chunk(w_tris, w_scr, fill, have[j], lane, (nxv[j] + 1.f) * 0.5f * (float)R.W, (1.f - nyv[j]) * 0.5f * (float)R.H,
                                 zbest[j], tbest[j],
 #ifdef DT_RO_STATS
                                 reinterpret_cast<int32_t*>(reinterpret_cast<char*>(R.pixtab) + (size_t)R.W * R.H * 64 + 1024 + 768));
 #else
                                 nullptr);
-#endif
 #endif
                 }
                 fill = 0;
@@ -2793,11 +2591,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
             have[j] = have[j] && (pedge[j] || (tbest[j][0] & tbest[j][1] & tbest[j][2] & tbest[j][3]) >= 0);   // all four < 0  <=>  the AND is negative
             if (!__ballot(have[j])) continue;                        // wave-uniform: nothing of this batch needs shading
             if (have[j]) {
-#ifdef DT_RO_NOSHADE
-              const uint32_t v = (uint32_t)tbest[j][0] ^ (uint32_t)tbest[j][1] ^ (uint32_t)tbest[j][2] ^ (uint32_t)tbest[j][3];
-#else
               const uint32_t v = shade_msaa<true>(c, m, R, s_tiles, nxv[j], nyv[j], base, zbest[j], tbest[j]);
-#endif
               uint8_t* dst = R.frames + ((size_t)env_p * npix + pix[j]) * 3;
               dst[0] = (uint8_t)v; dst[1] = (uint8_t)(v >> 8); dst[2] = (uint8_t)(v >> 16);
             }
@@ -3113,26 +2907,24 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
   } else if (R.domain_rand || R.segment || R.light) { if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); }   // per-env EnvCam path (light: the shared camera's EnvCam with the env's light)
   else { if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false); }
 #undef LAUNCH_RASTER
-  // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region); generic raster:
+  // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region_q); generic raster:
   // k_resolve drains them (front of the queue regions).  Pixels inside mesh-object screen boxes (far end of the regions)
   // are k_resolve_obj's, after either raster.
-  if (!R.no_msaa) {
-    if (s_res != s && (obj || !quad)) { (void)hipEventRecord(ev, s); (void)hipStreamWaitEvent(s_res, ev, 0); }
-    // persistent wavefronts pulling work items: enough workgroups to fill every CU at the kernel's occupancy
-    // (round 4: EXACTLY the resident workgroups -- every wavefront's first grab is static, a workgroup that waits for a slot would sit on its items)
-    if (v3dr) {                                        // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
-      const size_t ldsr = (size_t)R.q3_rows * V3_TAB_PITCH * 4;
-      const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, ldsr)));
-      hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), ldsr, s_res, R, cams, envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-    } else if (!quad) {
-      const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve, lds2)));
-      hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s_res, R, cams, R.queue, R.qcount);
-    }
-    if (obj) {
-      const size_t lds4 = lds + (size_t)(RB / 64) * TRI_CAP * sizeof(TriCov) + (size_t)(RB / 64) * RO_SCR_BYTES;
-      const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_obj<DT_RES_NB>, lds4)));
-      hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s_res, R, cams, R.queue, 1, has_pos ? envq : (const EnvQ*)nullptr);
-    }
+  if (s_res != s && (obj || !quad)) { (void)hipEventRecord(ev, s); (void)hipStreamWaitEvent(s_res, ev, 0); }
+  // persistent wavefronts pulling work items: enough workgroups to fill every CU at the kernel's occupancy
+  // (round 4: EXACTLY the resident workgroups -- every wavefront's first grab is static, a workgroup that waits for a slot would sit on its items)
+  if (v3dr) {                                        // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
+    const size_t ldsr = (size_t)R.q3_rows * V3_TAB_PITCH * 4;
+    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, ldsr)));
+    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), ldsr, s_res, R, cams, envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+  } else if (!quad) {
+    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve, lds2)));
+    hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s_res, R, cams, R.queue, R.qcount);
+  }
+  if (obj) {
+    const size_t lds4 = lds + (size_t)(RB / 64) * TRI_CAP * sizeof(TriCov) + (size_t)(RB / 64) * RO_SCR_BYTES;
+    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_obj<DT_RES_NB>, lds4)));
+    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s_res, R, cams, R.queue, 1, has_pos ? envq : (const EnvQ*)nullptr);
   }
 }
 
@@ -3146,11 +2938,11 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   EnvD* envd = reinterpret_cast<EnvD*>(R.envd);
   EnvL* envl = reinterpret_cast<EnvL*>(envd + A.N);   // [N + 1] behind the EnvD records (dtsim_api.hip allocates them)
   // domain randomisation on the quad records (k_raster_v3dr): same table / texture conditions as k_raster_v3
-  const bool v3dr = R.qtex && R.envd && R.domain_rand && !R.segment && !R.no_msaa && (R.W & 3) == 0 && R.qlog2 == 8 && R.q3_rows > 0 &&
+  const bool v3dr = R.qtex && R.envd && R.domain_rand && !R.segment && (R.W & 3) == 0 && R.qlog2 == 8 && R.q3_rows > 0 &&
                     R.q3_rows <= 24 && R.n_maps * 32 <= 128;
   // quad-layout fast path: shared camera, square power-of-two tile textures (else the generic k_raster)
   // (S = 256 tables carry the record-offset mask of the S256 kernels -- q8_rec256 --, which need a padded grid under 128 tiles: Q8_SNAP)
-  const bool quad = R.qtex && !R.domain_rand && !R.segment && !R.no_msaa && (size_t)R.n_qtiles * 8 <= 32768 && (R.W & 3) == 0 &&
+  const bool quad = R.qtex && !R.domain_rand && !R.segment && (size_t)R.n_qtiles * 8 <= 32768 && (R.W & 3) == 0 &&
                     !(R.qlog2 == 8 && R.qmax_tiles >= 256);
   const bool obj = R.max_tris > 0;
   // render order (k_env_sort): the quad pipeline indexes by position (EnvQ, object masks, queue entries); env ids come
@@ -3168,8 +2960,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   }
 
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-  const bool v3 = quad && R.qlog2 == 8 && R.q3_rows > 0 && R.q3_rows <= V3_MAX_ROWS && R.n_maps * V3_MAP_COLS <= V3_TAB_PITCH / 2 &&
-                  true;
+  const bool v3 = quad && R.qlog2 == 8 && R.q3_rows > 0 && R.q3_rows <= V3_MAX_ROWS && R.n_maps * V3_MAP_COLS <= V3_TAB_PITCH / 2;
   if (quad && !(tables & 1)) {
     PixTab* pixtab = reinterpret_cast<PixTab*>(R.pixtab);
     SampTab* samptab = reinterpret_cast<SampTab*>(pixtab + (size_t)R.W * R.H);
@@ -3181,13 +2972,12 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   // the vector ALU and the L1).  Every per-position array is addressed relative to the range's first chunk, so the
   // kernels are the same; only the quad-record paths in the sorted render order are split (k_raster_v3, k_raster_v3dr).
   int parts = 1;
-  if (ov && ov->parts > 1 && !R.no_msaa && (v3 || v3dr) && pos && (obj || !quad)) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
+  if (ov && ov->parts > 1 && (v3 || v3dr) && pos && (obj || !quad)) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
   // which raster ran (DTSIM_FIELD_RENDER_PIPE): bits 8.. of the result
   tables |= (quad ? (v3 ? DTSIM_PIPE_V3 : DTSIM_PIPE_Q) : v3dr ? DTSIM_PIPE_V3DR : (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV
              : DTSIM_PIPE_GENERIC) << 8;
   if (R.light) tables |= DTSIM_PIPE_ENV_LIGHT << 8;
   if (parts <= 1) { launch_raster_resolve(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
-  static const bool parts_serial = [] { const char* v = getenv("DTSIM_RENDER_PARTS_SERIAL"); return v && v[0] == '1'; }();   // experiment: the split without the overlap
   const size_t n_tiles = dt_raster_tiles(R.W, R.H), n_blk = n_tiles * 4;
   (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * parts * sizeof(int32_t), s);
   for (int p = 0; p < parts; ++p) {
@@ -3205,7 +2995,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     // per-POSITION arrays move to the range (EnvQ / EnvV / EnvD in render order, masks, queues, items above); per-ENV arrays (EnvCam, frames,
     // screen triangles, object boxes) stay whole: the kernels reach them through the env id of the position's record
     EnvQ* envq_p = envq + e0; EnvV* envv_p = envv ? envv + e0 : nullptr; EnvD* envd_p = envd ? envd + e0 : nullptr;
-    launch_raster_resolve(s, parts_serial ? s : ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
+    launch_raster_resolve(s, ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
   }
   (void)hipEventRecord(ov->ev[DT_MAX_RENDER_PARTS], ov->s2);
   (void)hipStreamWaitEvent(s, ov->ev[DT_MAX_RENDER_PARTS], 0);

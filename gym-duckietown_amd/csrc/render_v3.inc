@@ -1,5 +1,5 @@
 // render_v3.inc -- k_raster_v3: the quad-record one-ray path of k_raster_q on an instruction diet (included by render.hip
-// inside its anonymous namespace; shares EnvCam / EnvFast / EnvQ / PixTab / SampTab, the queue protocol and resolve_region).
+// inside its anonymous namespace; shares EnvCam / EnvFast / EnvQ / PixTab / SampTab and the queue protocol with k_raster_q).
 //
 // Replaces the same reference code as k_raster_q: simulator.py:1853-1884 (tile quads, GL_LINEAR / GL_REPEAT),
 // simulator.py:1806-1812 (ground quad), graphics.py:172-251 (4x MSAA resolve), distortion.py:85-125 (remap, folded in).
@@ -33,29 +33,22 @@
 #ifndef DT_V3_WAVES_OBJ
 #define DT_V3_WAVES_OBJ (DT_V3_WAVES - 1)   // the mesh-object instantiation: 111 VGPRs; one more wavefront spills 76 B and is 1.7 % slower
 #endif
-#ifndef DT_V3_SW
 #define DT_V3_SW (DT_V3_WW / 4)                       // pixel columns of a slot's sub-block (four slots side by side)
-#endif
 #define V3_ROWS (WAVE_PIX / DT_V3_WW)                 // rows of a wavefront block
 #define V3_WX (DT_TILE_W / DT_V3_WW)                  // wavefront blocks side by side in the workgroup tile
-#ifdef DT_V3_SHAPE_EXPERIMENT                        // (A/B aid: another block shape for k_raster_v3<false> alone -- the object / per-env paths decode queue entries by WAVE_W)
-static_assert(PPT == 4 && DT_TILE_W % DT_V3_WW == 0 && (RB / 64) % V3_WX == 0 &&
-#else
 static_assert(PPT == 4 && DT_V3_WW == 128 && DT_V3_WW == WAVE_W && DT_TILE_W % DT_V3_WW == 0 && (RB / 64) % V3_WX == 0 &&
-#endif
               V3_ROWS * ((RB / 64) / V3_WX) == DT_TILE_H, "k_raster_v3 / k_raster_v3dr: 128 x 2 wavefront blocks tiling the 128 x 8 workgroup tile "
               "(the generic k_resolve / k_resolve_obj decode the queue entries as row-major pixel numbers of such a block)");
 #define V3_TAB_PITCH 256                              // table entries per LDS row: the tile byte of Z selects the row
 #define V3_MAP_COLS 32                                // columns of one map inside a half row (padded grid width <= 32, up to 4 maps)
 #define V3_MAX_ROWS 24                                // padded grid height <= 24 (24 KB of LDS)
 #define V3_SEL_TILE 0x0c0c0602u                       // v_perm: (byte 2 of Z) << 8 | byte 2 of X -- the tile bytes of the snapped coordinates (Q8_SNAP)
-#define V3_WAVE_LDS RQ_LIST                           // dwords of LDS per wavefront: transpose buffer / resolve list
+#define V3_WAVE_LDS RQ_LIST                           // dwords of LDS per wavefront: the transpose buffer
 // pixel number (row-major in the wavefront block) of slot k of lane l; V3_XO*: byte distance of slot k from slot 0 in the transpose buffer
 static_assert(DT_V3_WW == 4 * DT_V3_SW && 64 % DT_V3_SW == 0, "four slots side by side");
 #define V3_PIX(k, l) (((l) / DT_V3_SW) * DT_V3_WW + (k) * DT_V3_SW + ((l) % DT_V3_SW))
 #define V3_XP_LANE(l) (((l) / DT_V3_SW) * DT_V3_WW + ((l) % DT_V3_SW))
-#if DT_V3_SW == 32
-#define V3_XO1 "96"
+#define V3_XO1 "96"                                   // 3 * DT_V3_SW bytes per slot (DT_V3_WW = 128)
 #define V3_XO1G "97"
 #define V3_XO1B "98"
 #define V3_XO2 "192"
@@ -64,17 +57,6 @@ static_assert(DT_V3_WW == 4 * DT_V3_SW && 64 % DT_V3_SW == 0, "four slots side b
 #define V3_XO3 "288"
 #define V3_XO3G "289"
 #define V3_XO3B "290"
-#elif DT_V3_SW == 16
-#define V3_XO1 "48"
-#define V3_XO1G "49"
-#define V3_XO1B "50"
-#define V3_XO2 "96"
-#define V3_XO2G "97"
-#define V3_XO2B "98"
-#define V3_XO3 "144"
-#define V3_XO3G "145"
-#define V3_XO3B "146"
-#endif
 #define V3_ROW16 (DT_V3_WW * 3 / 16)                  // 16-byte pieces of a block row
 
 struct alignas(4) U3 { uint32_t a, b, c; };           // 4 pixels x RGB
@@ -88,6 +70,119 @@ struct C3 { uint32_t rb, g; };
 __device__ inline C3 c3_of_rgb(const uint32_t rgb) { return C3{rgb, rgb}; }   // rgb = 0x00BBGGRR
 
 struct GndK { float Cx, Cz, sa, ca, kg, gnd[3], base[3], dif[3], gndl[4], pad[2]; };   // ground-quad constants of one env
+
+// ---- resolve_region_v3: exact path of k_raster_v3 -----------------------------------------------------------------------------
+// Called by every wavefront of k_raster_v3 at the end of its env loop on ITS OWN queue region, as resolve_region_q (render.hip) is by
+// k_raster_q, with two differences:
+//   * no interior test (round 6): every entry takes the four samples, and the queue entries ARE the list -- no compaction, no LDS round
+//     trip.  The test resolved 30 % of the entries with one record but cost as much as the four-sample phase (a table gather, a record
+//     gather and two patches per entry, latency-bound): without it the exact path is 0.10 ms shorter (profiles/r06_variants_ab.txt
+//     block E); an interior pixel's four samples give the one-ray colour anyway;
+//   * no list of distinct primitives (round 3).  The colour of a pixel is the sum over its four samples of the shade of the sample's
+//     primitive AT THE PIXEL CENTRE (GL: graphics.py:172-251), so every tile sample adds the integer filter of ITS tile's record at the
+//     centre cell (same cell index and weights for every tile: the blocks share one cell grid; a sample that is not on a tile reads the
+//     all-zero record 0) to one accumulator per channel -- 6 v_dot4 per sample, exact -- and sky / ground samples add their colour once
+//     per count.  Tile look-ups go by v_perm like the env loop's; the +-50 m ground-quad test is made in quad coordinates.
+// s_qt: k_raster_v3's LDS tile table (block offset at (tz << 10 | tx << 2) + the map's column offset EnvQ.pad[0], the record-offset
+// mask 512 bytes behind it); s_envq: the EnvQ records of the chunk's 64 positions, staged in LDS by the workgroup -- an entry's constants
+// are three ds_read_b128 instead of three 16-byte gathers through the texture unit; (bx0, by0): the origin of the wavefront's block.
+// LIGHT: per-env lights (EnvL in render order, envl): the lit factor of the tile plane is env_lit8's, per entry.
+template <bool LIGHT>
+__device__ inline void resolve_region_v3(const RenderParams& R, const EnvCam* __restrict__ cams, const SampTab* __restrict__ samptab,
+                                         const uint8_t* __restrict__ qtex, const uint32_t* s_qt, const uint16_t* w_queue, const int n,
+                                         const int e0, const int bx0, const int by0, const int lane, const uint4* s_envq,
+                                         const EnvL* __restrict__ envl) {
+  const int npix = R.W * R.H;
+  const float Sf = (float)(1 << R.qlog2), lo = 0.5f * Sf;
+  const char* qtb = reinterpret_cast<const char*>(s_qt);
+  for (int r0 = 0; r0 < n; r0 += RQ_LIST) {          // wave-uniform: rounds of up to RQ_LIST entries
+    const int n_list = min(n - r0, RQ_LIST);
+    for (int l0 = 0; l0 < n_list; l0 += 64) {          // wave-uniform
+      const bool have = l0 + lane < n_list;
+      // the entries were written by this wavefront a moment ago: bypass the (possibly stale) L1 line
+      const uint32_t ent = have ? (uint32_t)__builtin_nontemporal_load(w_queue + r0 + l0 + lane) : 0u;
+      const int lp = (int)(ent & 255u);
+      const int el = (int)((ent >> 8) & 63u);
+      const int pix = have ? (by0 + lp / DT_V3_WW) * R.W + bx0 + lp % DT_V3_WW : 0;
+      const SampTab sp = samptab[pix];
+      PixTab pt;                                       // the PixTab's hit and lit factor, from the SampTab (one table, two 16-byte loads)
+      pt.lr = __uint_as_float(sp.pad[0]); pt.lf = __uint_as_float(sp.pad[1]); pt.lit = __uint_as_float(sp.pad[2]); pt.mi = 0u;
+      // the env's constants as three 16-byte pieces (round 5: the exact path is bound by the NUMBER of vector-memory instructions it issues)
+      const uint4* fl = s_envq + el * 4;
+      const uint4 a4 = fl[0];
+      const float4 qa = make_float4(__uint_as_float(a4.x), __uint_as_float(a4.y), __uint_as_float(a4.z), __uint_as_float(a4.w));
+      const uint4 qb = fl[1], qd = fl[3];
+      const float A = qa.x, B = qa.y, Cx = qa.z, Cz = qa.w, Xhi = __uint_as_float(qb.x), Zhi = __uint_as_float(qb.y);
+      const uint32_t tab = qd.z;
+      const int e = (int)qd.y;
+      const float4* c4 = reinterpret_cast<const float4*>(cams + e);   // EnvCam as 16-byte pieces: [2] = {ty, hor[3]}, [3] = {gnd[3], base0}, [4] = {base1, base2, dif0, dif1}, [5] = {dif2, L..}, [6] = {L3, gndl[0..2]}, [7] = {gndl3, ..}
+      const float wCy = default_cam((float)R.W / (float)R.H).Cy;      // shared camera: the same height for every env (what k_cam_setup wrote)
+      const float kg = (wCy - GROUND_Y) / wCy;
+      const float qpm = __uint_as_float(qd.w);                           // quad cells per metre of the env's map
+      const float goff = (float)DT_QRING * Sf + 0.5f, ghalf = GROUND_HALF * qpm;   // world 0 and 50 m in padded quad coordinates
+      const float Xu = fmaf(pt.lf, B, fmaf(pt.lr, A, Cx)), Zu = fmaf(pt.lf, -A, fmaf(pt.lr, B, Cz));
+      const uint32_t xic = q8_bits(Xu), zic = q8_bits(Zu);              // the centre's snapped coordinates: q8_rec256 works on these bits
+      float lit8 = (pt.lit > 0.f ? pt.lit : 0.55f) * Q8_LIT;
+      if constexpr (LIGHT) { if (pt.lit > 0.f) lit8 = env_lit8(envl[min(e0 + el, R.N - 1)], pt.lr, pt.lf, env_base8()); }
+      const uint32_t W8 = quad_weights8(q8_frac(xic), q8_frac(zic), lit8);
+      uint32_t aS[3] = {0u, 0u, 0u};                   // sum over the samples of the byte-weight filter of each sample's record
+      int n_sky = 0, n_gnd = 0;
+      float gX = 0.f, gZ = 0.f;                        // ground hit (quad coordinates) of the lowest-index ground sample
+      uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+      uint32_t raddr_prev = 0u;
+#pragma unroll
+      for (int s = 3; s >= 0; --s) {
+        const uint32_t hr = sp.dlr[s >> 1], hf = sp.dlf[s >> 1];
+        const float slr = pt.lr + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hr >> 16 : hr)));
+        const float slf = pt.lf + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hf >> 16 : hf)));
+        const float Xs = fmaf(slf, B, fmaf(slr, A, Cx)), Zs = fmaf(slf, -A, fmaf(slr, B, Cz));
+        // the tile that OWNS the sample (ownership on (X - 0.5, Z - 0.5), clamped into the padded grid)
+        const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
+        const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
+        const bool s_in = (Xc == Xo) & (Zc == Zo);
+        const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
+        const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
+        const uint32_t tb = tp[0], sel = tp[128];
+        const bool is_tile = have & (((sp.flags >> s) & 1u) != 0u) & s_in & (tb != 0u);
+        // ground-quad hit of the sample: camera + kg * (tile-plane hit - camera), inside +-50 m
+        const float Xg = fmaf(kg, Xs - Cx, Cx), Zg = fmaf(kg, Zs - Cz, Cz);
+        const bool is_gnd = have & !is_tile & (((sp.flags >> (4 + s)) & 1u) != 0u) & (fabsf(Xg - goff) <= ghalf) & (fabsf(Zg - goff) <= ghalf);
+        n_gnd += is_gnd; n_sky += !(is_tile | is_gnd);
+        if (is_gnd) { gX = Xg; gZ = Zg; }
+        // one record per DISTINCT tile among the pixel's samples (round 4: the path is texture-unit heavy, its gathers fully divergent;
+        // the samples of most edge pixels share a tile, or are not on a tile at all): a lane loads only when its address changes
+        const uint32_t raddr = is_tile ? (tb | q8_rec256(xic, zic, sel)) : 0u;
+        if (s == 3 || raddr != raddr_prev) rec = *reinterpret_cast<const uint4*>(qtex + raddr);
+        raddr_prev = raddr;
+        aS[0] = __builtin_amdgcn_udot4(rec.x, W8, aS[0], false);
+        aS[1] = __builtin_amdgcn_udot4(rec.y, W8, aS[1], false);
+        aS[2] = __builtin_amdgcn_udot4(rec.z, W8, aS[2], false);
+      }
+      float acc[3];
+      float4 hc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (__ballot(n_sky > 0)) hc = c4[2];             // wave-uniform: the horizon colour only where some sample sees the sky
+      acc[0] = fmaf((float)n_sky, hc.y, (float)aS[0] * (1.f / 256.f));
+      acc[1] = fmaf((float)n_sky, hc.z, (float)aS[1] * (1.f / 256.f));
+      acc[2] = fmaf((float)n_sky, hc.w, (float)aS[2] * (1.f / 256.f));
+      if (__ballot(n_gnd > 0)) {                       // wave-uniform: shade the ground quad (lit at its corners, bilinear)
+        if (pt.lit > 0.f && (pt.lr != 0.f || pt.lf != 0.f)) { gX = fmaf(kg, Xu - Cx, Cx); gZ = fmaf(kg, Zu - Cz, Cz); }   // the centre ray hits the planes
+        const float hs = 0.5f / ghalf;
+        const float a_ = fminf(fmaxf(fmaf(gX - goff, hs, 0.5f), 0.f), 1.f), b_ = fminf(fmaxf(fmaf(gZ - goff, hs, 0.5f), 0.f), 1.f);
+        const float4 q3 = c4[3], q4 = c4[4], q5 = c4[5], q6 = c4[6], q7 = c4[7];
+        const float n0 = q6.y + a_ * (q6.z - q6.y), n1 = q6.w + a_ * (q7.x - q6.w);
+        const float ndl = n0 + b_ * (n1 - n0);
+        const float ng = (float)n_gnd;
+        acc[0] += ng * (q3.x * fminf(q3.w + q4.z * ndl, 1.f));
+        acc[1] += ng * (q3.y * fminf(q4.x + q4.w * ndl, 1.f));
+        acc[2] += ng * (q3.z * fminf(q4.y + q5.x * ndl, 1.f));
+      }
+      const float o[3] = {0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2]};
+      if (have) store_rgb(R.frames, npix, e, pix, pack_rgb(o));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
 
 // LIGHT (DTSIM_F_LIGHT_CAPTURE): every env lit by its own light (envl: EnvL in render order, [N + 1]) -- the lit factor of a (pixel, env) is
 // env_lit8's, two pixels per packed operation, in place of the PixTab's shared one; the PixTab's lit keeps its class role (< 0 outside the
@@ -135,7 +230,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
       s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
     }
   }
-  // the EnvQ records of the chunk's positions (the exact path reads them per entry: resolve_region), 16 bytes per thread
+  // the EnvQ records of the chunk's positions (the exact path reads them per entry: resolve_region_v3), 16 bytes per thread
   uint4* s_envq = reinterpret_cast<uint4*>(s_mem + R.q3_rows * V3_TAB_PITCH + (RB / 64) * V3_WAVE_LDS);
   static_assert(ENVS_PER_BLOCK * 4 <= RB, "one 16-byte piece per thread");
   if (tid < ENVS_PER_BLOCK * 4) s_envq[tid] = reinterpret_cast<const uint4*>(envq + min(e0 + tid / 4, R.N - 1))[tid & 3];
@@ -176,7 +271,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   uint16_t* w_queue = queue + ((size_t)rwg * (RB / 64) + wave) * QREGION;
   int qn = 0, qo = 0;                                  // plane-edge entries (front of the region), object-box entries (back)
   int qend_v = 0;
-  uint32_t* w_lds = s_mem + R.q3_rows * V3_TAB_PITCH + wave * V3_WAVE_LDS;   // transpose buffer, later resolve_region's list
+  uint32_t* w_lds = s_mem + R.q3_rows * V3_TAB_PITCH + wave * V3_WAVE_LDS;   // transpose buffer
   // the lane STORES pixels 4 * lane .. 4 * lane + 3 of the block (12 bytes), whatever the compute map
   const int st_x = bx0 + (lane * 4) % DT_V3_WW, st_y = by0 + (lane * 4) / DT_V3_WW;
   const bool st_ok = st_x < R.W && st_y < R.H;       // W % 4 == 0 (launch precondition): all four pixels or none
@@ -244,13 +339,9 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const bool wide = __builtin_amdgcn_readfirstlane((int)(R.W % DT_V3_WW == 0 && R.H % V3_ROWS == 0)) != 0;   // wave-uniform: every block lies inside the image
   const uint32_t st_voff16 = lane < 48 ? (uint32_t)(((size_t)(by0 + lane / V3_ROW16) * R.W + bx0) * 3u) + (uint32_t)(lane % V3_ROW16) * 16u : 0x80000000u;
   auto store = [&](const uint32_t env, const U4& o) __attribute__((always_inline)) {
-#ifdef DT_Q_NO_STORE   // ablation: the pass without its frame stores (the values stay live)
-    if (o.a == 0x12345678u) frames[(size_t)env * frame_bytes] = 1u;
-#else
     const v3_i32x4 fr = v3_rsrc(frames + (size_t)env * frame_bytes, frame_bytes);
     if (wide) v3_buf_store_v4i32(v3_u32x4{o.a, o.b, o.c, o.d}, fr, (int)st_voff16, 0, 2);   // wave-uniform; aux 2 = nt
     else v3_buf_store_v3i32(v3_u32x3{o.a, o.b, o.c}, fr, (int)st_voff, 0, 2);
-#endif
   };
   // ---- pixel colours (byte 2 of three dwords each) of the four slots -> the lane's 12 bytes of the frame row
   // (LDS byte addresses for the inline DS instructions: the low half of a flat LDS pointer is the LDS offset)
@@ -348,7 +439,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
         // + Q8_SNAP (one more packed add, after the two fused ones: ONE rounding): the sum's bit pattern IS the fixed-point coordinate --
         // byte 0 the fraction in 256ths of a texel (GL's own precision: llvmpipe rounds its coordinates to 8 fractional bits), byte 1
         // the cell, byte 2 the tile -- no v_cvt_flr, no v_fract
-        // (explicit fused multiply-adds in the exact path's order -- resolve_region's Xu, Zu: since the snap makes the last bit of these sums
+        // (explicit fused multiply-adds in the exact path's order -- resolve_region_v3's Xu, Zu: since the snap makes the last bit of these sums
         // visible, every copy of the loop and the exact path must round them the same way; -ffp-contract=fast alone leaves that to the compiler)
         const f2 X2 = fma2(lf2[j], vB, fma2(lr2[j], vA, vCx)) + vK;
         const f2 Z2 = fma2(lf2[j], -vA, fma2(lr2[j], vB, vCz)) + vK;
@@ -365,15 +456,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
           const uint32_t* tp = reinterpret_cast<const uint32_t*>(s_qtb + ta);
           const uint32_t tb = tp[0], sel = tp[V3_TAB_PITCH / 2];      // one ds_read2_b32: block offset, record-offset mask
           const uint32_t cell = q8_rec256(xi, zi, sel);                 // byte offset of the cell's record in its block (4 x 2 cells per line)
-#if defined(DT_Q_NO_LOAD)
-          st.q[k] = make_uint4(tb + cell, tb ^ cell, cell, 0x00000080u);
-#elif 0
-          st.q[k] = *reinterpret_cast<const uint4*>(qtex + (32u + (cell << 4)) + (tb & 16u));   // ablation: every tile samples block 0 (1 MB: L2-resident)
-#elif 0
-          st.q[k] = *reinterpret_cast<const uint4*>(qtex + (32u + ((cell & 0x3FFu) << 4)) + (tb & 16u));   // ablation: L1-resident taps (round 6: NOT a lower bound -- 4.1 ms against 1.6: every lane of the chip in one 16 KB window)
-#else
           st.q[k] = *reinterpret_cast<const uint4*>(qtex + (tb | cell));
-#endif
         }
       }
     };
@@ -411,7 +494,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
         if (!mk) continue;                             // wave-uniform
         if (__builtin_amdgcn_inverse_ballot_w64(mk)) {
           const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-          w_queue[qn + rank] = (uint16_t)(etag | (uint32_t)V3_PIX(k, lane));   // (QE_ALWAYS_EDGE is not set any more: resolve_region<V3> runs no interior test)
+          w_queue[qn + rank] = (uint16_t)(etag | (uint32_t)V3_PIX(k, lane));   // (no QE_ALWAYS_EDGE: resolve_region_v3 runs no interior test)
         }
         qn += __popcll(mk);
       }
@@ -461,9 +544,6 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
           c[k].rb = cand[k] ? c[k].rb : valid[k] ? hc.rb : 0u; c[k].g = cand[k] ? c[k].g : valid[k] ? hc.g : 0u;
         }
       }
-#ifdef DT_Q_ABL_NOSLOW
-      slow = 0ull;
-#endif
       if (!slow && !(OBJ && om)) return transpose(c);  // wave-uniform: every candidate pixel of the block is a certain tile interior
       unsigned long long em[PPT] = {0ull, 0ull, 0ull, 0ull}, oem[PPT] = {0ull, 0ull, 0ull, 0ull};   // edge / object-box lanes per slot (scalar)
       if (slow) {                                      // wave-uniform: some candidate pixel is not a certain tile interior
@@ -532,13 +612,9 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
     span_t2 = wall_clock64();
 #endif
     if (lane == 0) qcount[rwg * (RB / 64) + wave] = OBJ ? qo : qn;
-#ifdef DT_Q_ABL_NORESOLVE
-    if (qn < 0) {
-#else
     if (qn > 0) {
-#endif
       __builtin_amdgcn_s_waitcnt(0);                   // queue stores have left the wavefront
-      resolve_region<true, true, false, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, w_lds, w_queue, qn, e0, bx0, by0, lane, 0, 0, 0, 0, s_envq, envl);
+      resolve_region_v3<LIGHT>(R, cams, samptab, qtex, s_qt, w_queue, qn, e0, bx0, by0, lane, s_envq, envl);
     }
   }
 #ifdef DT_WAVE_SPANS

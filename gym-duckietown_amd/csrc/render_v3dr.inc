@@ -444,7 +444,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
 
 // ---- k_resolve_dr: the exact path of the plane-edge pixels k_raster_v3dr queues (round 5) -----------------------------
 // Replaces the generic k_resolve behind k_raster_v3dr: same work items (one per 8 queue batches of a raster workgroup, persistent
-// wavefronts, static first grab), but a pixel is resolved the way resolve_region<.., V3> resolves one for the shared camera --
+// wavefronts, static first grab), but a pixel is resolved the way resolve_region_v3 (render_v3.inc) resolves one for the shared camera --
 // on the quad records and the LDS tile table, with the env's HOMOGRAPHY in place of the per-pixel sample table:
 //   * the four MSAA samples (graphics.py:172-251: coverage and depth per sample) go from their rectilinear NDC straight to padded quad
 //     coordinates (EnvDG), one reciprocal each; the tile that OWNS a sample is looked up with one v_perm + one ds_read2;

@@ -11,7 +11,7 @@ Candidates:
   axis_blk  the same with the half-extents maximised over the 32 x 2 pixel slot (a scalar per (slot, env))
   fake      shipped test, but boundaries between tiles that share one quad block (same texture, same angle) do not count
   fake+axis both
-  exact     sub-cell circular test (what phase 1 of resolve_region decides)
+  exact     sub-cell circular test (what phase 1 of resolve_region_q decides)
 
 An analysis aid (uses the test oracle's map / camera model), not part of the product path.   python tools/edge_test_model.py [n_poses]
 """

@@ -28,5 +28,5 @@ for _ in range(K):
 sim.sync()
 dt = (time.time() - t) / K
 n, ms = sim.profile_read(_ffi.KERNEL_RENDER)
-print(f"N={N} dist={dist} dr={dr} light={light} per_env_camera={pec} ({sim.render_pipeline}) msaa_off={os.environ.get('DTSIM_RASTER_NO_MSAA','0')}: wall {dt*1e3:.3f} ms, event {ms/n:.3f} ms "
+print(f"N={N} dist={dist} dr={dr} light={light} per_env_camera={pec} ({sim.render_pipeline}): wall {dt*1e3:.3f} ms, event {ms/n:.3f} ms "
       f"-> {N/(ms/n*1e-3)/1e6:.3f} M env-steps/s, {N*640*480*3/(ms/n*1e-3)/1e12:.3f} TB/s ({N*640*480*3/(ms/n*1e-3)/8e12*100:.1f}% of 8 TB/s)")
