@@ -72,6 +72,7 @@ struct dtsim {
   dtsim_probe* d_qout = nullptr;
   dtsim_agent_info* d_agent = nullptr;
   bool rendered = false;          // a render pass has written the per-env cameras (dtsim_draw_lines needs them)
+  bool masked = false;            // the last pass was dtsim_render_masked: the post-passes need a full one
   RenderParams last_R{};          // the parameters of that pass (dtsim_draw_leds: projected triangles, tables); last_segment: it was the segment view
   bool last_segment = false;
   bool leds_ok = false;           // last_R still names live buffers (cleared by dtsim_set_assets / dtsim_set_maps / dtsim_set_distortion_lut, which re-allocate)
@@ -871,7 +872,15 @@ int dtsim_step_ex(dtsim_t* h, const void* actions, int n_steps, int actions_on_d
 
 int dtsim_render(dtsim_t* h) { return dtsim_render_ex(h, 0u); }
 
-int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
+static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask);
+int dtsim_render_ex(dtsim_t* h, uint32_t flags) { return render_pass(h, flags, nullptr); }
+int dtsim_render_masked(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
+  if (!mask) return fail(DTSIM_E_INVALID, "dtsim_render_masked: null mask");
+  return render_pass(h, flags, mask);
+}
+
+// mask: dtsim_render_masked's device mask, or null for the full pass
+static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
   if (flags & ~(uint32_t)(DTSIM_RENDER_SEGMENT | DTSIM_RENDER_GL_FILTER)) return fail(DTSIM_E_INVALID, "unknown render flags 0x%x", flags);
   const bool segment = (flags & DTSIM_RENDER_SEGMENT) != 0;
@@ -923,11 +932,11 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags) {
 #endif
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
-    const int t = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr);
+    const int t = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
     h->render_tables = t & 0xFF; h->render_pipe = t >> 8;
   }
   HIPCHK(hipGetLastError());
-  h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true;
+  h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true; h->masked = mask != nullptr;
 #ifdef DT_WAVE_SPANS
   if (R.spans) {   // the spans of the last render -> the file DTSIM_WAVE_SPANS names (tools/wave_spans.py reads it)
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -972,6 +981,7 @@ int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int
   if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if (!h->have_maps || !h->have_reset || !h->have_lut || !h->rendered) return fail(DTSIM_E_STATE, "dtsim_draw_lines before the first dtsim_render (the pass writes the cameras the lines go through)");
+  if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_lines after dtsim_render_masked: the post-passes need a full dtsim_render");
   if (n == 0) return DTSIM_OK;
   for (int i = 0; i < n; ++i) {
     const int e = env_idx ? env_idx[i] : 0;
@@ -1005,6 +1015,7 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
   if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if (!h->rendered || !h->leds_ok || h->last_segment) return fail(DTSIM_E_STATE, "dtsim_draw_leds needs a preceding dtsim_render (colour view): it tests the spheres against that pass's scene");
+  if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_leds after dtsim_render_masked: the post-passes need a full dtsim_render");
   if (n == 0) return DTSIM_OK;
   for (int i = 0; i < n; ++i) {
     const int e = env_idx ? env_idx[i] : 0;
@@ -1085,9 +1096,25 @@ int dtsim_allgather_frames(dtsim_t* h, void* nccl_comm, void* recv, const void* 
   return DTSIM_OK;
 }
 
+static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                        const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
+                        const int32_t* bounds_y, const int32_t* taps_y, int ksize_y);
 int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                   const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
                   const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
+  return observe_pass(h, out, out_h, out_w, flags, nullptr, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
+}
+int dtsim_observe_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                         const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
+                         const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
+  if (!mask) return fail(DTSIM_E_INVALID, "dtsim_observe_masked: null mask");
+  return observe_pass(h, out, out_h, out_w, flags, mask, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
+}
+
+// mask: dtsim_observe_masked's device mask, or null for every env
+static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                        const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
+                        const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
   if (!h || !out) return fail(DTSIM_E_INVALID, "bad argument");
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
@@ -1195,14 +1222,26 @@ int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
   memcpy(P.hw, h->obs_fast.hw, sizeof P.hw); memcpy(P.vw, h->obs_fast.vw, sizeof P.vw);
   {
     ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
-    dt_launch_observe(h->stream, P);
+    dt_launch_observe(h->stream, P, mask);
   }
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }
 
+static int observe_cubic_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                              const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y);
 int dtsim_observe_cubic(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                         const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
+  return observe_cubic_pass(h, out, out_h, out_w, flags, nullptr, first_x, taps_x, first_y, taps_y);
+}
+int dtsim_observe_cubic_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                               const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
+  if (!mask) return fail(DTSIM_E_INVALID, "dtsim_observe_cubic_masked: null mask");
+  return observe_cubic_pass(h, out, out_h, out_w, flags, mask, first_x, taps_x, first_y, taps_y);
+}
+
+static int observe_cubic_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                              const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
   if (!h || !out || !first_x || !taps_x || !first_y || !taps_y) return fail(DTSIM_E_INVALID, "bad argument");
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
@@ -1233,8 +1272,17 @@ int dtsim_observe_cubic(dtsim_t* h, void* out, int out_h, int out_w, int flags,
   P.bx = h->d_obsc_tab; P.kkx = P.bx + out_w; P.by = P.kkx + 4 * (size_t)out_w; P.kky = P.by + out_h;
   {
     ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
-    dt_launch_observe_cubic(h->stream, P);
+    dt_launch_observe_cubic(h->stream, P, mask);
   }
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_copy_rows(dtsim_t* h, void* dst, const void* src, size_t row_bytes, const uint8_t* mask) {
+  if (!h || !dst || !src || !mask) return fail(DTSIM_E_INVALID, "dtsim_copy_rows: null argument");
+  if (row_bytes == 0) return DTSIM_OK;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_copy_rows(h->stream, h->N, dst, src, row_bytes, mask);
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }

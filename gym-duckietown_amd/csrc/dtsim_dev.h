@@ -243,8 +243,12 @@ struct RenderParams {
 // next range; ev[p] orders range p across the two streams, ev[DT_MAX_RENDER_PARTS] joins s2 back into the caller's stream.
 #define DT_MAX_RENDER_PARTS 8
 #define DT_WORK_INTS 8           // RenderParams.work: ints per render part
+#define DT_WORK_LIVE 7           // RenderParams.work[DT_WORK_LIVE]: envs of a masked pass (k_env_sort_masked), read by the SUB rasters
 struct RenderOverlap { int parts; hipStream_t s2; hipEvent_t ev[DT_MAX_RENDER_PARTS + 1]; };
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int tables, const RenderOverlap* ov = nullptr);
+// mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
+// only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int tables, const RenderOverlap* ov = nullptr,
+                     const uint8_t* mask = nullptr);
 // GL_LINE overlays (draw_curve / draw_bbox) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);
@@ -285,6 +289,9 @@ struct ObserveParams {
   uint32_t vw[16];
 };
 size_t dt_observe_lds_bytes(const ObserveParams& P);
-void dt_launch_observe(hipStream_t s, const ObserveParams& P);
+// mask (device, [N] bytes, nonzero = selected; null = every env): dtsim_observe_masked -- the rows of other envs are not written
+void dt_launch_observe(hipStream_t s, const ObserveParams& P, const uint8_t* mask = nullptr);
 // OpenCV INTER_CUBIC: bx / by = first of the four taps per output column / row (borders replicate), kkx / kky = [..][4] 11-bit taps
-void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P);
+void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P, const uint8_t* mask = nullptr);
+// row e of src -> row e of dst (row_bytes each) for every e < N with mask[e] != 0 (device pointers; dtsim_copy_rows)
+void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);

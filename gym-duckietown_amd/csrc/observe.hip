@@ -10,6 +10,7 @@
 // `Image.resize`.  HBM-read bound: every frame byte is read once (plus the row overlap between
 // neighbouring row blocks), the output is 16x smaller at 640x480 -> 160x120.
 #include "dtsim_dev.h"
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -94,11 +95,15 @@ __device__ inline void observe_vertical(const ObserveParams& P, const uint8_t* s
   else observe_vertical_t<1>(P, s_tmp, e, oy0, oy1, y_first, tid);
 }
 
-__global__ __launch_bounds__(OB) void k_observe(ObserveParams P) {
+// MASKED (dtsim_observe_masked): the workgroups / threads of envs with mask[e] == 0 leave at once (the grid stays sized for N); the
+// unmasked instantiations do not read `mask`.
+template <bool MASKED = false>
+__global__ __launch_bounds__(OB) void k_observe(ObserveParams P, const uint8_t* __restrict__ mask) {
   extern __shared__ uint32_t s_mem[];
   const int tid = threadIdx.x;
   const int n_blocks = (P.oh + P.rows_per_block - 1) / P.rows_per_block;
   const int e = blockIdx.x / n_blocks, blk = blockIdx.x % n_blocks;
+  if (MASKED && !mask[e]) return;                    // (the whole workgroup: one env)
   const int oy0 = blk * P.rows_per_block, oy1 = min(oy0 + P.rows_per_block, P.oh);
   const int y_first = P.by[2 * oy0], y_last = P.by[2 * (oy1 - 1)] + P.by[2 * (oy1 - 1) + 1];
   const int rows_in = y_last - y_first;
@@ -251,14 +256,15 @@ __global__ __launch_bounds__(OB) void k_observe(ObserveParams P) {
 // neighbouring windows, the rows are shared through L1 / L2), rounds to the uint8 intermediate Pillow keeps, and adds it to
 // the one or two outputs the row belongs to.  The frame is read from HBM once; nothing is synchronised.  Border rows /
 // columns (clipped, renormalised taps) are k_observe_border's.
-template <int HN, int SY>
-__global__ __launch_bounds__(OB) void k_observe_pow2(ObserveParams P) {
+template <int HN, int SY, bool MASKED = false>
+__global__ __launch_bounds__(OB) void k_observe_pow2(ObserveParams P, const uint8_t* __restrict__ mask) {
   constexpr int R = 4;
   const int wi = P.ow - 2, G = (P.oh - 2 + R - 1) / R;
   const int per_env = G * wi;
   const int idx = blockIdx.x * OB + threadIdx.x;
   const int e = idx / per_env, rem = idx - e * per_env;
   if (e >= P.N) return;
+  if (MASKED && !mask[e]) return;
   const int g = rem / wi, ox = 1 + (rem - g * wi);
   const int oy0 = 1 + g * R;
   const int SX = P.hfast;
@@ -305,11 +311,13 @@ __global__ __launch_bounds__(OB) void k_observe_pow2(ObserveParams P) {
 }
 
 // the border pixels of the same output (first / last row and column): Pillow's two passes per pixel from the tables
-__global__ __launch_bounds__(OB) void k_observe_border(ObserveParams P) {
+template <bool MASKED = false>
+__global__ __launch_bounds__(OB) void k_observe_border(ObserveParams P, const uint8_t* __restrict__ mask) {
   const int nb = 2 * P.ow + 2 * (P.oh - 2);
   const int idx = blockIdx.x * OB + threadIdx.x;
   const int e = idx / nb, b = idx - e * nb;
   if (e >= P.N) return;
+  if (MASKED && !mask[e]) return;
   int oy, ox;
   if (b < P.ow) { oy = 0; ox = b; }
   else if (b < 2 * P.ow) { oy = P.oh - 1; ox = b - P.ow; }
@@ -347,11 +355,13 @@ __global__ __launch_bounds__(OB) void k_observe_border(ObserveParams P) {
 // four of them per channel with the column's taps.  OpenCV filters rows first and columns second, keeping int32 rows
 // without rounding: both orders are the same exact integer sum (|sum| < 2^31 for 8-bit pixels), and the single rounding
 // is saturate_cast<uchar>((v + 2^21) >> 22).
-__global__ __launch_bounds__(OB) void k_observe_cubic(ObserveParams P) {
+template <bool MASKED = false>
+__global__ __launch_bounds__(OB) void k_observe_cubic(ObserveParams P, const uint8_t* __restrict__ mask) {
   extern __shared__ uint32_t s_mem[];
   int32_t* s_v = reinterpret_cast<int32_t*>(s_mem);          // [W * 3] vertical sums
   const int tid = threadIdx.x;
   const int e = blockIdx.x / P.oh, oy = blockIdx.x % P.oh;
+  if (MASKED && !mask[e]) return;                    // (the whole workgroup: one env)
   const int in_row_bytes = P.W * 3;
   const uint8_t* frame = P.frames + (size_t)e * P.H * in_row_bytes;
   const int y0 = P.by[oy];                               // first of the four rows (may be < 0)
@@ -397,11 +407,40 @@ __global__ __launch_bounds__(OB) void k_observe_cubic(ObserveParams P) {
   }
 }
 
+// Row e of src -> row e of dst for every env with mask[e] != 0 (final observations / frames).  Grid: N x blocks_per_row workgroups; chunk c
+// of a row = bytes [16 c, 16 c + 16), the row's workgroups stride over its chunks -- 16-byte loads and stores when both bases and the row
+// size are 16-byte aligned (vec), else the chunk's bytes one by one.  Unselected rows leave at once.
+__global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, size_t row_bytes, int blocks_per_row,
+                                                   const uint8_t* __restrict__ mask, int vec) {
+  const int e = blockIdx.x / blocks_per_row;
+  if (!mask[e]) return;
+  uint8_t* d = dst + (size_t)e * row_bytes;
+  const uint8_t* p = src + (size_t)e * row_bytes;
+  const size_t stride = (size_t)blocks_per_row * 256 * 16;
+  for (size_t off = ((size_t)(blockIdx.x % blocks_per_row) * 256 + threadIdx.x) * 16; off < row_bytes; off += stride) {
+    if (vec) { *reinterpret_cast<uint4*>(d + off) = *reinterpret_cast<const uint4*>(p + off); continue; }
+    const size_t n = row_bytes - off < 16 ? row_bytes - off : 16;
+    for (size_t i = 0; i < n; ++i) d[off + i] = p[off + i];
+  }
+}
+
 }  // namespace
 
-void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P) {
-  hipLaunchKernelGGL(k_observe_cubic, dim3((unsigned)((size_t)P.N * P.oh)), dim3(OB), (size_t)P.W * 3 * sizeof(int32_t) + 16, s, P);
+void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P, const uint8_t* mask) {
+  const dim3 grid((unsigned)((size_t)P.N * P.oh));
+  const size_t lds = (size_t)P.W * 3 * sizeof(int32_t) + 16;
+  if (mask) hipLaunchKernelGGL(k_observe_cubic<true>, grid, dim3(OB), lds, s, P, mask);
+  else hipLaunchKernelGGL(k_observe_cubic<false>, grid, dim3(OB), lds, s, P, nullptr);
 }
+
+void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask) {
+  const size_t chunks = (row_bytes + 15) / 16;
+  const int per_row = (int)std::min<size_t>((chunks + 255) / 256, 16);   // (a selected row: up to 16 workgroups; the grid stays small when few are)
+  const int vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | row_bytes) & 15) == 0;
+  hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((size_t)N * per_row)), dim3(256), 0, s, static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src),
+                     row_bytes, per_row, mask, vec);
+}
+
 
 size_t dt_observe_lds_bytes(const ObserveParams& P) {
   const size_t in_row_words = ((size_t)P.W * 3 + 3) >> 2;
@@ -409,19 +448,26 @@ size_t dt_observe_lds_bytes(const ObserveParams& P) {
   return OBS_STAGE_ROWS * in_row_words * 4 + 32 + (((size_t)P.max_rows_in * P.ow * 3 + 3) & ~(size_t)3) + tabs + 16;
 }
 
-void dt_launch_observe(hipStream_t s, const ObserveParams& P) {
+void dt_launch_observe(hipStream_t s, const ObserveParams& P, const uint8_t* mask) {
   if (P.hfast && P.vfast && P.ow >= 3 && P.oh >= 3 && !getenv("DTSIM_OBSERVE_STAGED")) {   // power-of-two scale on both axes
     const int G = (P.oh - 2 + 3) / 4;
     const size_t n_in = (size_t)P.N * G * (P.ow - 2), n_b = (size_t)P.N * (2 * P.ow + 2 * (P.oh - 2));
     const dim3 grid((unsigned)((n_in + OB - 1) / OB)), gridb((unsigned)((n_b + OB - 1) / OB));
     bool done = true;
-#define DT_POW2(HN_, SY_) hipLaunchKernelGGL((k_observe_pow2<HN_, SY_>), grid, dim3(OB), 0, s, P)
+#define DT_POW2(HN_, SY_) do { if (mask) hipLaunchKernelGGL((k_observe_pow2<HN_, SY_, true>), grid, dim3(OB), 0, s, P, mask); \
+                               else hipLaunchKernelGGL((k_observe_pow2<HN_, SY_, false>), grid, dim3(OB), 0, s, P, nullptr); } while (0)
     if (P.hn == 7 && P.vfast == 2) DT_POW2(7, 2); else if (P.hn == 7 && P.vfast == 4) DT_POW2(7, 4); else if (P.hn == 7 && P.vfast == 8) DT_POW2(7, 8);
     else if (P.hn == 12 && P.vfast == 2) DT_POW2(12, 2); else if (P.hn == 12 && P.vfast == 4) DT_POW2(12, 4); else if (P.hn == 12 && P.vfast == 8) DT_POW2(12, 8);
     else done = false;
 #undef DT_POW2
-    if (done) { hipLaunchKernelGGL(k_observe_border, gridb, dim3(OB), 0, s, P); return; }
+    if (done) {
+      if (mask) hipLaunchKernelGGL(k_observe_border<true>, gridb, dim3(OB), 0, s, P, mask);
+      else hipLaunchKernelGGL(k_observe_border<false>, gridb, dim3(OB), 0, s, P, nullptr);
+      return;
+    }
   }
   const int n_blocks = (P.oh + P.rows_per_block - 1) / P.rows_per_block;
-  hipLaunchKernelGGL(k_observe, dim3((unsigned)((size_t)P.N * n_blocks)), dim3(OB), dt_observe_lds_bytes(P), s, P);
+  const dim3 grid((unsigned)((size_t)P.N * n_blocks));
+  if (mask) hipLaunchKernelGGL(k_observe<true>, grid, dim3(OB), dt_observe_lds_bytes(P), s, P, mask);
+  else hipLaunchKernelGGL(k_observe<false>, grid, dim3(OB), dt_observe_lds_bytes(P), s, P, nullptr);
 }

@@ -190,8 +190,12 @@ __device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const E
 // k_raster_q, all the envs one XCD's L2 serves -- look at the same few texture blocks.  A counting sort by
 // (tile under the camera, heading quadrant) in one workgroup; the order inside a bin is arbitrary (frames are
 // independent, so the order never changes a result).  pos[e] = position of env e.
+// MASKED (dtsim_render_masked): only the envs with mask[e] != 0 are binned; they take positions [0, live), the others pos = -1, and the
+// live count goes to *live (the SUB rasters read it at entry).
 #define SORT_BINS 4096
-__global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapDev* __restrict__ maps, int32_t* __restrict__ pos) {
+template <bool MASKED = false>
+__global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapDev* __restrict__ maps, int32_t* __restrict__ pos,
+                                                   const uint8_t* __restrict__ mask, int32_t* __restrict__ live) {
   __shared__ int s_hist[SORT_BINS];
   __shared__ int s_part[1024];
   const int tid = threadIdx.x;
@@ -216,10 +220,10 @@ __global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapD
 #pragma unroll
   for (int k = 0; k < KEEP; ++k) {
     const int e = tid + k * 1024;
-    bins[k] = e < A.N ? bin_of(e) : -1;
+    bins[k] = e < A.N && (!MASKED || mask[e]) ? bin_of(e) : -1;
     if (bins[k] >= 0) atomicAdd(&s_hist[bins[k]], 1);
   }
-  for (int e = tid + KEEP * 1024; e < A.N; e += 1024) atomicAdd(&s_hist[bin_of(e)], 1);
+  for (int e = tid + KEEP * 1024; e < A.N; e += 1024) if (!MASKED || mask[e]) atomicAdd(&s_hist[bin_of(e)], 1);
   __syncthreads();
   // exclusive scan of the bins: each thread owns SORT_BINS / 1024 consecutive bins
   int loc[SORT_BINS / 1024], sum = 0;
@@ -236,6 +240,7 @@ __global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapD
 #pragma unroll
     for (int d = 1; d < 16; d <<= 1) { const int v = __shfl_up(w, d, 16); if (tid >= d) w += v; }
     s_part[16 + tid] = w;                             // inclusive over the wavefronts
+    if (MASKED && tid == 15) *live = w;               // selected envs in all
   }
   __syncthreads();
   const int base = incl - sum + ((tid >> 6) ? s_part[16 + (tid >> 6) - 1] : 0);
@@ -245,17 +250,21 @@ __global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapD
 #pragma unroll
   for (int k = 0; k < KEEP; ++k)
     if (bins[k] >= 0) pos[tid + k * 1024] = atomicAdd(&s_hist[bins[k]], 1);
-  for (int e = tid + KEEP * 1024; e < A.N; e += 1024) pos[e] = atomicAdd(&s_hist[bin_of(e)], 1);
+    else if (MASKED && tid + k * 1024 < A.N) pos[tid + k * 1024] = -1;
+  for (int e = tid + KEEP * 1024; e < A.N; e += 1024) pos[e] = !MASKED || mask[e] ? atomicAdd(&s_hist[bin_of(e)], 1) : -1;
 }
 
 // light: DTSIM_F_LIGHT_CAPTURE with the shared camera -- the env's own eye-space light (colors[12..15]) instead of default_cam()'s, also as the
 // rotated per-position constants of the quad kernels' LIGHT instantiations (envl, [N + 1], when given).
+// MASKED: the masked pass (k_env_sort<true>'s order) -- envs at position -1 are not rendered and get no records.
+template <bool MASKED = false>
 __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float aspect, EnvCam* out, EnvFast* fast,
                             const RenderMapDev* __restrict__ maps, EnvQ* envq, int qlog2, const int32_t* __restrict__ pos, EnvV* envv,
                             EnvD* envd, int W, int H, int light, EnvL* envl) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const size_t N = A.N;
   if (e >= A.N) return;
+  if (MASKED && pos[e] < 0) return;
   EnvCam c;
   const double ang = A.angle[e];
   const double sa = sin(ang), ca = cos(ang);
@@ -522,8 +531,10 @@ __device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {
 #ifndef DT_OBJSETUP_T
 #define DT_OBJSETUP_T 256           // threads of a k_obj_setup workgroup (one workgroup per env)
 #endif
+template <bool MASKED = false>   // MASKED: the masked pass -- envs at position -1 (not rendered) are skipped
 __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, RenderParams R, const EnvCam* __restrict__ cams, const int32_t* __restrict__ pos) {
   const int e = blockIdx.x;
+  if (MASKED && pos[e] < 0) return;
   const int tid = threadIdx.x;
   const size_t N = A.N;
   const EnvCam c = cams[e];
@@ -1175,6 +1186,8 @@ static_assert(ENVS_PER_BLOCK <= 64, "the env position of a queue entry has six b
 #define RES_ENVS DT_RES_ENVS  // env positions of a chunk per k_resolve_obj work item
 static_assert(ENVS_PER_BLOCK % RES_ENVS == 0 && ENVS_PER_BLOCK / RES_ENVS <= ITEMS_PER_WG, "octet items");
 
+// The live count of a masked pass (positions [0, live) of the render order), written by k_env_sort<true> after the pass's work-list clear.
+__device__ inline int dt_sub_live(const RenderParams& R) { return __builtin_amdgcn_readfirstlane(R.work[DT_WORK_LIVE]); }
 // Work items of k_resolve_obj (its own list: R.work[2] = count, [3] = cursor; second part of R.items): one per RES_ENVS
 // env positions of a raster workgroup that queued object-box pixels.
 // groups: bit g = env group g of the chunk (RES_ENVS positions) has object-box entries in some region of the workgroup; the
@@ -1906,7 +1919,9 @@ __host__ __device__ inline int dt_q_tile_group(int n_tiles) { return (n_tiles + 
 #define DT_Q_PRIO 3                                  // s_setprio level while a wavefront issues its quad loads (0: off)
 #endif
 // LIGHT: per-env lights (EnvL in render order), as k_raster_v3<OBJ, true> (render_v3.inc)
-template <bool OBJ, bool S256, bool LIGHT = false>
+// SUB: the masked pass -- positions [0, live) of k_env_sort<true>'s order, live = R.work[DT_WORK_LIVE] (dt_sub_live); the grid is sized for
+// R.N and the workgroups past the live chunks leave at once.
+template <bool OBJ, bool S256, bool LIGHT = false, bool SUB = false>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_WAVES - 1 : DT_Q_WAVES, OBJ ? DT_Q_WAVES - 1 : DT_Q_WAVES))) void k_raster_q(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast* __restrict__ fasts,
                                                  const EnvQ* __restrict__ envq, uint8_t* __restrict__ frames,
                                                  const uint8_t* __restrict__ qtex, const float4* __restrict__ lut, const PixTab* __restrict__ pixtab, const SampTab* __restrict__ samptab,
@@ -1920,7 +1935,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   // XCD-affine workgroup map: workgroup b runs on XCD b % 8 (round-robin dispatch), and XCD x is given the x-th
   // eighth of the env chunks (all frame tiles of each): with the envs in k_env_sort order, one L2 serves the envs of one
   // region of the map for the whole launch.  The mapping only matters for speed.
-  const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
+  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
+  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
   // Within an XCD: groups of dt_q_tile_group() frame tiles, all chunks of the slice for one group before the next group,
   // so that a tile's PixTab slice (16 KB) is read from HBM once per XCD instead of once per chunk, while the workgroups
   // in flight still belong to few chunks.
@@ -1929,12 +1945,13 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   const int per_group = q_tg * cpx;
   const int grp = bi / per_group, gi = bi % per_group;
   const int g_tiles = min(q_tg, n_tiles - grp * q_tg);        // the last group may be short
-  const int tile = grp * q_tg + gi % g_tiles;
-  const int chunk = xcd * cpx + gi / g_tiles;
-  if (gi >= g_tiles * cpx || chunk >= n_chunks) return;   // padding workgroups (whole workgroup)
+  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
+  const int tile = SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles;
+  const int chunk = SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles;
+  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
   const int rwg = chunk * n_tiles + tile;            // logical workgroup index: queue regions, counts, work items
   const int e0 = chunk * ENVS_PER_BLOCK;             // positions in the render order
-  const int e1 = min(e0 + ENVS_PER_BLOCK, R.N);
+  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
   for (int i = tid; i < R.n_qtiles * 2; i += RB) s_qt[i] = qtiles[i];
   __syncthreads();
 
@@ -2865,6 +2882,8 @@ template <class K> static size_t resident_blocks(K kernel, size_t lds) {
 
 // One range of chunks through its raster (stream s) and exact-path kernels (stream s_res, after event ev when it is
 // another stream): the whole batch, or one of dt_launch_render's render parts (every array already moved to the range).
+// SUB: the masked pass -- the quad-record rasters' SUB instantiations over positions [0, live) (never the generic raster).
+template <bool SUB>
 static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t ev, const RenderParams& R, EnvCam* cams, EnvFast* fasts, EnvQ* envq,
                                   EnvV* envv, EnvD* envd, EnvL* envl, uint8_t* frames_raster, bool quad, bool v3, bool v3dr, bool obj, bool has_pos) {
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
@@ -2882,17 +2901,17 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
     const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
     PixTab* pixtab = reinterpret_cast<PixTab*>(R.pixtab);
     SampTab* samptab = reinterpret_cast<SampTab*>(pixtab + (size_t)R.W * R.H);
-#define LAUNCH_Q(OBJ_, S256_) do { if (R.light) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, true>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, \
+#define LAUNCH_Q(OBJ_, S256_) do { if (R.light) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, true, SUB>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, \
                                            R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
-                                else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, R.qtex, \
+                                else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, false, SUB>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, R.qtex, \
                                            reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
     const bool s256 = R.qlog2 == 8 && R.qmax_tiles < 256;
     // k_raster_v3 (render_v3.inc): S = 256 textures, padded grids up to 32 x 24 tiles, up to 4 maps (else k_raster_q)
     if (v3) {
       const size_t lds3 = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // tile table, per-wavefront buffers, the chunk's EnvQ records
-#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, \
+#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, \
                                            R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
-                                else hipLaunchKernelGGL((k_raster_v3<OBJ_>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, R.qtex, \
+                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, R.qtex, \
                                            reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
       if (obj) LAUNCH_V3(true); else
       LAUNCH_V3(false);
@@ -2902,8 +2921,8 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
 #undef LAUNCH_Q
   } else if (v3dr) {
     const size_t ldsd = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * RQ_LIST * 4;
-    if (obj) hipLaunchKernelGGL((k_raster_v3dr<true>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-    else hipLaunchKernelGGL((k_raster_v3dr<false>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+    if (obj) hipLaunchKernelGGL((k_raster_v3dr<true, SUB>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+    else hipLaunchKernelGGL((k_raster_v3dr<false, SUB>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
   } else if (R.domain_rand || R.segment || R.light) { if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); }   // per-env EnvCam path (light: the shared camera's EnvCam with the env's light)
   else { if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false); }
 #undef LAUNCH_RASTER
@@ -2928,7 +2947,7 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
   }
 }
 
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int tables, const RenderOverlap* ov) {
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int tables, const RenderOverlap* ov, const uint8_t* mask) {
   RenderParams R = R_in;
   tables &= 3;                                         // bit 2 (returned): this pass ran in k_env_sort's order (DTSIM_FIELD_RENDER_POS)
   EnvCam* cams = reinterpret_cast<EnvCam*>(R.envcam);
@@ -2948,15 +2967,26 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   // render order (k_env_sort): the quad pipeline indexes by position (EnvQ, object masks, queue entries); env ids come
   // from EnvQ.env
   int32_t* pos = ((quad || v3dr) && R.envpos && A.N > ENVS_PER_BLOCK) ? R.envpos : nullptr;   // one chunk: the order does not matter
-  if (pos) { hipLaunchKernelGGL(k_env_sort, dim3(1), dim3(1024), 0, s, A, R.maps, pos); tables |= 4; }
-  hipLaunchKernelGGL(k_cam_setup, dim3((A.N + 63) / 64), dim3(64), 0, s, A, R.domain_rand, R.segment,
-                     (float)R.W / (float)R.H, cams, fasts, R.maps, (quad || v3dr) ? envq : nullptr, R.qlog2, pos, quad ? envv : nullptr,
-                     v3dr ? envd : nullptr, R.W, R.H, R.light, (quad && R.light) ? envl : nullptr);
-  (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * sizeof(int32_t), s);            // work-item counts + cursors of k_resolve / k_resolve_obj
+  // masked pass (dtsim_render_masked): the selected envs take positions [0, live) -- always sorted, whatever N --, the others -1; every setup
+  // kernel skips them and the SUB rasters stop at live.  The generic rasters render every env instead (same state, same bytes).
+  const bool sub = mask && (quad || v3dr) && R.envpos;
+  if (sub) {
+    pos = R.envpos;
+    (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * sizeof(int32_t), s);          // (before the sort: it writes the live count there)
+    hipLaunchKernelGGL(k_env_sort<true>, dim3(1), dim3(1024), 0, s, A, R.maps, pos, mask, R.work + DT_WORK_LIVE);
+    tables |= 4;
+  } else if (pos) { hipLaunchKernelGGL(k_env_sort<false>, dim3(1), dim3(1024), 0, s, A, R.maps, pos, nullptr, nullptr); tables |= 4; }
+#define LAUNCH_CAM(M_) hipLaunchKernelGGL(k_cam_setup<M_>, dim3((A.N + 63) / 64), dim3(64), 0, s, A, R.domain_rand, R.segment,                  \
+                     (float)R.W / (float)R.H, cams, fasts, R.maps, (quad || v3dr) ? envq : nullptr, R.qlog2, pos, quad ? envv : nullptr,  \
+                     v3dr ? envd : nullptr, R.W, R.H, R.light, (quad && R.light) ? envl : nullptr)
+  if (sub) LAUNCH_CAM(true); else LAUNCH_CAM(false);
+#undef LAUNCH_CAM
+  if (!sub) (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * sizeof(int32_t), s);   // work-item counts + cursors of k_resolve / k_resolve_obj
   if (R.max_tris > 0) {
     if (!(tables & 2)) hipLaunchKernelGGL(k_blk_setup, dim3((unsigned)dt_raster_tiles(R.W, R.H)), dim3(RB), 0, s, R, reinterpret_cast<const float4*>(R.lut), reinterpret_cast<float4*>(R.blockbox));
     tables |= 2;
-    hipLaunchKernelGGL(k_obj_setup, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, cams, pos);
+    if (sub) hipLaunchKernelGGL(k_obj_setup<true>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, cams, pos);
+    else hipLaunchKernelGGL(k_obj_setup<false>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, cams, pos);
   }
 
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
@@ -2972,12 +3002,13 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   // the vector ALU and the L1).  Every per-position array is addressed relative to the range's first chunk, so the
   // kernels are the same; only the quad-record paths in the sorted render order are split (k_raster_v3, k_raster_v3dr).
   int parts = 1;
-  if (ov && ov->parts > 1 && (v3 || v3dr) && pos && (obj || !quad)) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
+  if (ov && ov->parts > 1 && (v3 || v3dr) && pos && (obj || !quad) && !sub) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
   // which raster ran (DTSIM_FIELD_RENDER_PIPE): bits 8.. of the result
   tables |= (quad ? (v3 ? DTSIM_PIPE_V3 : DTSIM_PIPE_Q) : v3dr ? DTSIM_PIPE_V3DR : (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV
              : DTSIM_PIPE_GENERIC) << 8;
   if (R.light) tables |= DTSIM_PIPE_ENV_LIGHT << 8;
-  if (parts <= 1) { launch_raster_resolve(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
+  if (sub) { launch_raster_resolve<true>(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, true); return tables; }
+  if (parts <= 1) { launch_raster_resolve<false>(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
   const size_t n_tiles = dt_raster_tiles(R.W, R.H), n_blk = n_tiles * 4;
   (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * parts * sizeof(int32_t), s);
   for (int p = 0; p < parts; ++p) {
@@ -2995,7 +3026,7 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     // per-POSITION arrays move to the range (EnvQ / EnvV / EnvD in render order, masks, queues, items above); per-ENV arrays (EnvCam, frames,
     // screen triangles, object boxes) stay whole: the kernels reach them through the env id of the position's record
     EnvQ* envq_p = envq + e0; EnvV* envv_p = envv ? envv + e0 : nullptr; EnvD* envd_p = envd ? envd + e0 : nullptr;
-    launch_raster_resolve(s, ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
+    launch_raster_resolve<false>(s, ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
   }
   (void)hipEventRecord(ov->ev[DT_MAX_RENDER_PARTS], ov->s2);
   (void)hipStreamWaitEvent(s, ov->ev[DT_MAX_RENDER_PARTS], 0);

@@ -186,8 +186,8 @@ __device__ inline void resolve_region_v3(const RenderParams& R, const EnvCam* __
 
 // LIGHT (DTSIM_F_LIGHT_CAPTURE): every env lit by its own light (envl: EnvL in render order, [N + 1]) -- the lit factor of a (pixel, env) is
 // env_lit8's, two pixels per packed operation, in place of the PixTab's shared one; the PixTab's lit keeps its class role (< 0 outside the
-// image, 0 sky, > 0 candidate).  Without LIGHT envl is not read.
-template <bool OBJ, bool LIGHT = false>
+// image, 0 sky, > 0 candidate).  Without LIGHT envl is not read.  SUB: the masked pass, as k_raster_q<.., SUB>.
+template <bool OBJ, bool LIGHT = false, bool SUB = false>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_V3_WAVES_OBJ : DT_V3_WAVES, OBJ ? DT_V3_WAVES_OBJ : DT_V3_WAVES)))
 void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast* __restrict__ fasts, const EnvQ* __restrict__ envq,
                  const EnvV* __restrict__ envv, uint8_t* __restrict__ frames, const uint8_t* __restrict__ qtex, const float4* __restrict__ lut,
@@ -199,7 +199,8 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
   // XCD-affine workgroup map, as k_raster_q
-  const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
+  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
+  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
   const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
   const int q_tg = dt_q_tile_group(n_tiles);
   const int per_group = q_tg * cpx;
@@ -207,16 +208,17 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const int g_tiles = min(q_tg, n_tiles - grp * q_tg);
   // (the divisions run on the vector ALU: bring the wave-uniform results back to scalar registers, or the env loop's
   // counter and the EnvQ address arithmetic stay vector instructions)
-  const int tile = __builtin_amdgcn_readfirstlane(grp * q_tg + gi % g_tiles);
-  const int chunk = __builtin_amdgcn_readfirstlane(xcd * cpx + gi / g_tiles);
-  if (gi >= g_tiles * cpx || chunk >= n_chunks) return;   // padding workgroups (whole workgroup)
+  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
+  const int tile = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles);
+  const int chunk = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles);
+  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
   const int rwg = chunk * n_tiles + tile;
   const int e0 = chunk * ENVS_PER_BLOCK;
 #ifdef DT_WAVE_SPANS   // experiment: wall-clock stamps of every wavefront (start, tables ready + XCC_ID, env loop done, end), tools/raster_spans.py
   const unsigned long long span_t0 = wall_clock64();
   unsigned long long span_t1 = 0, span_t2 = 0;
 #endif
-  const int e1 = min(e0 + ENVS_PER_BLOCK, R.N);
+  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
   // the tile tables of all maps -> LDS rows: block offsets in the first half of a row, record-offset masks in the second
   // (defaults of the unused columns: record 0 = off the grid, mask 0)
   for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
@@ -233,7 +235,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   // the EnvQ records of the chunk's positions (the exact path reads them per entry: resolve_region_v3), 16 bytes per thread
   uint4* s_envq = reinterpret_cast<uint4*>(s_mem + R.q3_rows * V3_TAB_PITCH + (RB / 64) * V3_WAVE_LDS);
   static_assert(ENVS_PER_BLOCK * 4 <= RB, "one 16-byte piece per thread");
-  if (tid < ENVS_PER_BLOCK * 4) s_envq[tid] = reinterpret_cast<const uint4*>(envq + min(e0 + tid / 4, R.N - 1))[tid & 3];
+  if (tid < ENVS_PER_BLOCK * 4) s_envq[tid] = reinterpret_cast<const uint4*>(envq + min(e0 + tid / 4, NL - 1))[tid & 3];
   __syncthreads();
 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // wave index in a scalar register: block origin, queue region, LDS slices

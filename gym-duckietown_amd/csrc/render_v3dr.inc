@@ -108,7 +108,7 @@ __device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const E
   arr[idx] = d;
 }
 
-template <bool OBJ>
+template <bool OBJ, bool SUB = false>   // SUB: the masked pass, as k_raster_q<.., SUB>
 #ifndef DT_V3DR_WAVES_MIN
 #define DT_V3DR_WAVES_MIN 6              // round 3: (5, 6) -> (6, 6): C4 pass 4.24 - 4.31 -> 4.08 - 4.13 ms on one box (4 / 5 / 7 wavefronts: 4.34 / 4.30 / 4.29)
 #define DT_V3DR_WAVES_MAX 6
@@ -125,18 +125,20 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
   // XCD-affine workgroup map, as k_raster_v3 (round 5): workgroup b runs on XCD b % 8, XCD x owns the x-th eighth of the chunks of the
   // render order (envs standing on one region of the map: one L2 serves them), the frame tiles dt_q_tile_group() at a time.
   // rwg = chunk * n_tiles + tile names the workgroup's queue regions / work items, as everywhere.
-  const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
+  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
+  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
   const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
   const int q_tg = dt_q_tile_group(n_tiles);
   const int per_group = q_tg * cpx;
   const int grp = bi / per_group, gi = bi % per_group;
   const int g_tiles = min(q_tg, n_tiles - grp * q_tg);
-  const int tile = __builtin_amdgcn_readfirstlane(grp * q_tg + gi % g_tiles);
-  const int chunk = __builtin_amdgcn_readfirstlane(xcd * cpx + gi / g_tiles);
-  if (gi >= g_tiles * cpx || chunk >= n_chunks) return;   // padding workgroups (whole workgroup)
+  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
+  const int tile = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles);
+  const int chunk = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles);
+  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
   const int rwg = chunk * n_tiles + tile;
   const int e0 = chunk * ENVS_PER_BLOCK;
-  const int e1 = min(e0 + ENVS_PER_BLOCK, R.N);
+  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
   for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
   __syncthreads();
   for (int mi = 0; mi < R.n_maps; ++mi) {

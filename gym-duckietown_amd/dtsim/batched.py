@@ -413,18 +413,33 @@ class BatchedSimulator:
             raise ValueError(f"actions has {a.size} elements, expected {n_steps}*{self.num_envs}*2")
         _ffi.check(self._lib, self._lib.dtsim_step_ex(self._h, a.ctypes.data_as(C.c_void_p), int(n_steps), 0, int(flags)))
 
-    def render(self, segment: bool = False, gl_filter: bool = False):
+    def _mask_ptr(self, mask) -> int:
+        """Device pointer of a per-env mask: a CUDA uint8 / bool tensor of shape [N] on the handle's device (contiguous), else ValueError."""
+        import torch
+        if not isinstance(mask, torch.Tensor) or mask.device.type != "cuda" or mask.device.index != self.device_index:
+            raise ValueError(f"mask: need a CUDA tensor on cuda:{self.device_index}, got {type(mask).__name__}"
+                             f"{' on ' + str(mask.device) if isinstance(mask, torch.Tensor) else ''}")
+        if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (self.num_envs,) or (self.num_envs > 1 and mask.stride(0) != 1):
+            raise ValueError(f"mask: need a contiguous uint8 / bool tensor of shape ({self.num_envs},), got {mask.dtype} of shape {tuple(mask.shape)}")
+        return mask.data_ptr()
+
+    def render(self, segment: bool = False, gl_filter: bool = False, mask=None):
         """render_obs() of every env into the frame batch; `segment=True` is the reference's segmentation render
         (simulator.py:1730-1737,1753,1808,1879).  `gl_filter=True` (DTSIM_RENDER_GL_FILTER): tile textures filtered with the arithmetic of the
         reference's renderer (Mesa llvmpipe's 8-bit GL_LINEAR) by the generic raster -- frames bit-identical to the reference's on 99.2 - 99.96 % of
-        the pixels, 2 - 4 x slower than the quad-record kernels: for validation, not for throughput."""
+        the pixels, 2 - 4 x slower than the quad-record kernels: for validation, not for throughput.
+        `mask` (CUDA uint8 / bool tensor [N] on the handle's device; anything else raises ValueError before a launch): dtsim_render_masked --
+        only the selected envs are rendered, the other frames keep their bytes (the generic pipelines re-render them unchanged)."""
         flags = _ffi.RENDER_GL_FILTER if gl_filter else 0
-        if not segment:
+        mp = None if mask is None else self._mask_ptr(mask)
+        if segment:
+            if not self._have_segment_assets:
+                self._install_segment_assets()
+            flags |= _ffi.RENDER_SEGMENT
+        if mp is None:
             _ffi.check(self._lib, self._lib.dtsim_render_ex(self._h, flags))
-            return
-        if not self._have_segment_assets:
-            self._install_segment_assets()
-        _ffi.check(self._lib, self._lib.dtsim_render_ex(self._h, _ffi.RENDER_SEGMENT | flags))
+        else:
+            _ffi.check(self._lib, self._lib.dtsim_render_masked(self._h, flags, C.c_void_p(mp)))
 
     _PIPE_NAMES = {_ffi.PIPE_GENERIC: "k_raster", _ffi.PIPE_GENERIC_ENV: "k_raster_env", _ffi.PIPE_Q: "k_raster_q",
                    _ffi.PIPE_V3: "k_raster_v3", _ffi.PIPE_V3DR: "k_raster_v3dr"}
@@ -556,17 +571,20 @@ class BatchedSimulator:
             sb = int(np.prod(ai["shape"])) * np.dtype(ai["typestr"]).itemsize
         _ffi.check(self._lib, self._lib.dtsim_allgather_frames(self._h, C.c_void_p(nccl_comm), C.c_void_p(rp), C.c_void_p(sp), C.c_size_t(sb)))
 
-    def observe(self, height: int, width: int, chw: bool = False, normalize: bool = False, out=None, interpolation: str = "pil_bilinear"):
+    def observe(self, height: int, width: int, chw: bool = False, normalize: bool = False, out=None, interpolation: str = "pil_bilinear",
+                mask=None):
         """Learner-side observation of the last rendered batch, on the device: PIL-exact bilinear resize
         (learning/utils/wrappers.py ResizeWrapper) or, with interpolation="cv_cubic", the cv2 INTER_CUBIC resize of the
         reference's own ResizeWrapper (src/gym_duckietown/wrappers.py:129-138); optional HWC->CHW (ImgWrapper) and /255
         float32 (NormalizeWrapper).  Returns a device array ([N,h,w,3] or [N,3,h,w]); `out` may be any object with
         __cuda_array_interface__ of that shape/dtype, C-contiguous (e.g. the send buffer of the frame all-gather); any other `out` raises
-        ValueError before anything is launched."""
+        ValueError before anything is launched.  `mask` (as render's): only the rows of the selected envs are written, the others keep
+        their content."""
         import torch
         from . import resample
         if interpolation not in ("pil_bilinear", "cv_cubic"):
             raise ValueError(f"interpolation {interpolation!r}: 'pil_bilinear' or 'cv_cubic'")
+        mp = None if mask is None else C.c_void_p(self._mask_ptr(mask))
         h, w = int(height), int(width)
         shape = (self.num_envs, 3, h, w) if chw else (self.num_envs, h, w, 3)
         if out is None:
@@ -593,8 +611,11 @@ class BatchedSimulator:
             fx, tx = resample.cubic_coeffs(self.camera_width, w)
             fy, ty = resample.cubic_coeffs(self.camera_height, h)
             fx, tx, fy, ty = (np.ascontiguousarray(a, dtype=np.int32) for a in (fx, tx, fy, ty))
-            _ffi.check(self._lib, self._lib.dtsim_observe_cubic(self._h, C.c_void_p(ptr), h, w, flags, fx.ctypes.data_as(ip), tx.ctypes.data_as(ip),
-                                                                fy.ctypes.data_as(ip), ty.ctypes.data_as(ip)))
+            tabs = (fx.ctypes.data_as(ip), tx.ctypes.data_as(ip), fy.ctypes.data_as(ip), ty.ctypes.data_as(ip))
+            if mp is None:
+                _ffi.check(self._lib, self._lib.dtsim_observe_cubic(self._h, C.c_void_p(ptr), h, w, flags, *tabs))
+            else:
+                _ffi.check(self._lib, self._lib.dtsim_observe_cubic_masked(self._h, C.c_void_p(ptr), h, w, flags, mp, *tabs))
             return out
         bx = kx = by = ky = None
         nkx = nky = 0
@@ -604,8 +625,25 @@ class BatchedSimulator:
         if h != self.camera_height:
             b, k = resample.coeffs(self.camera_height, h)
             by, ky, nky = b.ctypes.data_as(ip), k.ctypes.data_as(ip), k.shape[1]
-        _ffi.check(self._lib, self._lib.dtsim_observe(self._h, C.c_void_p(ptr), h, w, flags, bx, kx, nkx, by, ky, nky))
+        if mp is None:
+            _ffi.check(self._lib, self._lib.dtsim_observe(self._h, C.c_void_p(ptr), h, w, flags, bx, kx, nkx, by, ky, nky))
+        else:
+            _ffi.check(self._lib, self._lib.dtsim_observe_masked(self._h, C.c_void_p(ptr), h, w, flags, mp, bx, kx, nkx, by, ky, nky))
         return out
+
+    def copy_rows(self, dst, src, mask):
+        """dst[e] = src[e] for every env selected by `mask` (as render's), on the device, stream-ordered; the other rows of dst keep their
+        content.  dst / src: CUDA tensors on the handle's device, C-contiguous, same shape and dtype, leading dimension N."""
+        import torch
+        mp = self._mask_ptr(mask)
+        for name, t in (("dst", dst), ("src", src)):
+            if not isinstance(t, torch.Tensor) or t.device != mask.device or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != self.num_envs:
+                raise ValueError(f"copy_rows: {name} must be a contiguous CUDA tensor on {mask.device} with leading dimension {self.num_envs}")
+        if dst.shape != src.shape or dst.dtype != src.dtype:
+            raise ValueError(f"copy_rows: dst {tuple(dst.shape)} {dst.dtype} and src {tuple(src.shape)} {src.dtype} differ")
+        row = src[0].numel() * src.element_size() if self.num_envs else 0
+        _ffi.check(self._lib, self._lib.dtsim_copy_rows(self._h, C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(row), C.c_void_p(mp)))
+        return dst
 
     def frames_host(self) -> np.ndarray:
         """Synchronous copy of the frame batch to the host (tests / N=1 facade)."""

@@ -11,6 +11,14 @@ distributions and spawn test) -> `dtsim_render` -> `dtsim_observe` (the learners
 ImgWrapper / NormalizeWrapper, bit-identical to PIL).  So, as with gym's vector envs, the observation returned
 with `done[e] = True` is already the first observation of env e's next episode.  Everything is launched on one
 HIP stream shared with torch and ordered against the caller's stream on the GPU: no host synchronisation in the loop.
+
+Final observations (`final_obs=True`; gymnasium's `final_observation`, SB3's `terminal_observation`): the step renders and observes the
+whole batch BEFORE the reset -- the frames the reference's step() returns --, keeps the rows of the finished envs in
+`info["final_obs"]` (`dtsim_copy_rows`), restarts them and renders / observes only them again (`dtsim_render_masked`,
+`dtsim_observe_masked`).  `info["final_obs"]` is one persistent device tensor shaped like `obs` (raw frames with obs_shape=None);
+its rows where `info["final_obs_mask"]` (= done) is set hold the final observations, the other rows are unspecified.
+Always: `info["truncated"]` = done with done_code DTSIM_DONE_MAX_STEPS (the time limit: bootstrap on V(final obs)),
+`info["terminated"]` = the other finished envs (invalid pose).
 """
 from __future__ import annotations
 
@@ -25,7 +33,7 @@ from .batched import BatchedSimulator
 class DuckietownVecEnv:
     def __init__(self, map_name="small_loop", num_envs: int = 1024, obs_shape: Optional[Tuple[int, int]] = (120, 160),
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
-                 seed: Optional[int] = 0, **sim_kwargs):
+                 seed: Optional[int] = 0, final_obs: bool = False, **sim_kwargs):
         import torch
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -36,6 +44,8 @@ class DuckietownVecEnv:
                                     **sim_kwargs)
         self.num_envs = num_envs
         self.obs_shape, self.chw, self.normalize = obs_shape, chw, normalize
+        self.final_obs = bool(final_obs)
+        self._final = None                                          # info["final_obs"], allocated at the first step
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -45,12 +55,12 @@ class DuckietownVecEnv:
         self.action_shape = (num_envs, 2)
 
     # ------------------------------------------------------------------------------------------------
-    def _observe(self):
-        self.sim.render()
+    def _observe(self, mask=None):
+        self.sim.render(mask=mask)
         if self.obs_shape is None:
             return self._frames                                     # [N, H, W, 3] uint8, the raw camera frames
         return self.torch.as_tensor(self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=self.chw,
-                                                     normalize=self.normalize), device=self.device)
+                                                     normalize=self.normalize, mask=mask), device=self.device)
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -78,9 +88,21 @@ class DuckietownVecEnv:
                 self.sim.step(a)
             reward = self._reward.to(t.float32)                     # copies: the reset below clears the fields
             done = self._done.to(t.bool)
-            info = {"done_code": self._code.clone(), "episode_steps": self._steps.clone()}
-            self.sim.reset_done()
-            obs = self._observe()
+            code = self._code.clone()
+            # (dtsim_step sets done_code nonzero exactly when done: one comparison each)
+            info = {"done_code": code, "episode_steps": self._steps.clone(), "truncated": code == _ffi.DONE_MAX_STEPS,
+                    "terminated": code == _ffi.DONE_INVALID_POSE}
+            if self.final_obs:
+                obs = self._observe()                               # what the reference's step() returns, every env
+                if self._final is None:
+                    self._final = t.empty_like(obs)
+                self.sim.copy_rows(self._final, obs, done)          # kept for the finished envs
+                self.sim.reset_done()
+                obs = self._observe(mask=done)                      # their first frames, only theirs
+                info["final_obs"], info["final_obs_mask"] = self._final, done
+            else:
+                self.sim.reset_done()
+                obs = self._observe()
         self._leave()
         return obs, reward, done, info
 

@@ -251,7 +251,8 @@ enum {
   DTSIM_FIELD_WHEEL_DIST = 26,/* double [N]     wheel_dist (:597) */
   DTSIM_FIELD_RENDER_POS = 27,/* int32  [N]     read-only: position of each env in the render order of the last dtsim_render (k_env_sort:
                                * envs standing on the same tile and facing the same way are neighbours; 32 consecutive positions share a
-                               * raster workgroup, XCD x owns the x-th eighth of the order); the identity when the pass ran in index order */
+                               * raster workgroup, XCD x owns the x-th eighth of the order); the identity when the pass ran in index order; -1 for the envs a
+                               * masked pass (dtsim_render_masked) did not render */
   DTSIM_FIELD_RENDER_PIPE = 28,/* int32 [N]     read-only (ABI v12): the raster of the last dtsim_render, the same value for every env: DTSIM_PIPE_* below,
                                * | DTSIM_PIPE_ENV_LIGHT when the shared camera lit each env with its own light (DTSIM_F_LIGHT_CAPTURE); 0 before any pass.
                                * One value for the whole pass, repeated per env so that the field reads like every other.  The flag
@@ -364,6 +365,18 @@ enum { DTSIM_RENDER_SEGMENT = 1u, DTSIM_RENDER_GL_FILTER = 2u };
  * filter: the generic raster runs, 2 - 4 x slower, and the frames are bit-identical to the reference's on 99.2 - 99.96 % of the pixels instead of
  * within +-1/255 on all but 0.25 % (tests/test_gpu_gl_golden.py).  For validation against reference frames, not for throughput. */
 int dtsim_render_ex(dtsim_t* h, uint32_t flags);
+/* Masked render: dtsim_render_ex(h, flags) for the envs with mask[e] != 0 only.  `mask` is a DEVICE pointer to num_envs bytes (nonzero =
+ * selected), read on the handle's stream; the call is asynchronous and never waits for the host, so the count of selected envs is never
+ * needed there.  Frames of unselected envs are not written.  The quad-record pipelines (DTSIM_PIPE_V3, DTSIM_PIPE_Q, DTSIM_PIPE_V3DR) sort the
+ * selected envs into positions [0, live) of the render order (whatever N), their setup kernels skip the others and their rasters stop at the
+ * live count, so the pass costs about the selected fraction of a full one plus a fixed part (the sort, the setup launches, the workgroups
+ * past the live chunks leaving at once); it never splits into render parts (DTSIM_RENDER_PARTS).  Afterwards DTSIM_FIELD_RENDER_POS reads
+ * -1 for the envs that were not rendered, and dtsim_draw_lines / dtsim_draw_leds fail with DTSIM_E_STATE until a full dtsim_render.
+ * Fallback: the generic pipelines -- segmentation, DTSIM_RENDER_GL_FILTER, the per-env camera without the quad records, tile textures or
+ * tables outside the quad-record limits -- render EVERY env, as dtsim_render_ex would: an unselected env's unchanged state renders to the
+ * same bytes, so its frame keeps its content; only the cost differs.  Typical use: after dtsim_step, a full pass renders the frames step()
+ * returns, dtsim_copy_rows keeps those of the finished envs, dtsim_reset_done restarts them, and this call renders just their first frames. */
+int dtsim_render_masked(dtsim_t* h, uint32_t flags, const uint8_t* mask);
 /* GL_LINE overlays of the reference -- draw_curve (simulator.py:1886-1904, graphics.py:336-349) and draw_bbox (simulator.py:1907-1918,
  * objects.py:131-146) -- as a post-pass on the frames the last dtsim_render made: `lines` = [n][9] floats, world-space segment
  * (ax, ay, az, bx, by, bz) + colour (r, g, b in 0..1, the glColor3f of the line); env_idx[i] = the env segment i is drawn into (NULL: all
@@ -425,6 +438,18 @@ int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
  * cubic_coeffs (host pointers).  out / flags as dtsim_observe.  Asynchronous, stream-ordered after dtsim_render. */
 int dtsim_observe_cubic(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                         const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y);
+/* dtsim_observe / dtsim_observe_cubic for the envs with mask[e] != 0 only (`mask`: DEVICE pointer to num_envs bytes, nonzero = selected):
+ * the rows of selected envs are written exactly as the unmasked call writes them, the rows of the others are left untouched.  The launch
+ * is sized for num_envs; the workgroups of unselected envs leave at once.  Asynchronous, stream-ordered. */
+int dtsim_observe_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                         const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
+                         const int32_t* bounds_y, const int32_t* taps_y, int ksize_y);
+int dtsim_observe_cubic_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                               const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y);
+/* Row e of `src` -> row e of `dst` (row_bytes each, device pointers, num_envs rows) for every env with mask[e] != 0 (DEVICE pointer to
+ * num_envs bytes); other rows of dst are left untouched.  16-byte accesses when both pointers and row_bytes are 16-byte aligned.  For the
+ * final observations (or frames) of the envs that finished a step, before dtsim_reset_done.  Asynchronous, stream-ordered. */
+int dtsim_copy_rows(dtsim_t* h, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,
