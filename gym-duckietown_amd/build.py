@@ -4,8 +4,9 @@
 
 hipcc cross-compiles without a GPU.  Output: gym-duckietown_amd/lib/libdtsim.so
 (git-ignored, travels to the GPU box with the gpurun snapshot).
-physics.hip is compiled with -ffp-contract=off (separately rounded f64 ops, in the
-reference's operation order); render.hip with contraction allowed (speed, f32).
+physics.hip and remap.hip (the camera_rand table builder, pinned to numpy) are compiled with
+-ffp-contract=off (separately rounded ops, in the reference's operation order); render.hip with
+contraction allowed (speed, f32).
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ UNITS = [
     ("render.hip", ["-ffp-contract=fast"]),
     ("observe.hip", []),
     ("dtsim_api.hip", []),
+    ("remap.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical",
           "-I" + os.path.join(HERE, "..", "include")]

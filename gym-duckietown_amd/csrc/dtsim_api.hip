@@ -90,6 +90,13 @@ struct dtsim {
   size_t frames_bytes = 0;
   float* d_lut = nullptr;
   bool have_lut = false;
+  // camera_rand (dtsim_set_distortion_luts): per-env remap tables; while n_cal > 0 the raster writes the rectilinear frames into
+  // d_scratch (d_lut is the identity) and k_remap_cal gathers them into `frames`
+  int n_cal = 0;
+  bool camera_rand = false;       // DTSIM_LUTS_CAMERA_RAND: the device reset sampler scales the camera
+  int32_t* d_cal_src = nullptr;   // [n_cal][H*W]
+  int32_t* d_env_cal = nullptr;   // [N]
+  uint8_t* d_scratch = nullptr;   // [N][H][W][3]
   uint32_t* d_texels = nullptr;
   uint32_t* d_texels_seg = nullptr;   // segmented versions, same layout as d_texels (dtsim_set_segment_assets)
   uint8_t* d_mesh_seg = nullptr;      // [n_meshes][4] flat segmentation colour per mesh
@@ -193,6 +200,7 @@ StepParams step_params(const dtsim* h, int n_steps) {
   P.lanes = h->step_lanes;
   P.light_capture = (h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) ? 1 : 0;
   P.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
+  P.camera_rand = h->camera_rand ? 1 : 0;
   return P;
 }
 
@@ -318,7 +326,7 @@ void dtsim_destroy(dtsim_t* h) {
   }
   void* ptrs[] = {h->slab, h->d_blobs, h->d_dyn, h->d_states, h->d_mask, h->d_pool, h->d_actions, h->d_qenv,
                   h->d_qpose, h->d_qout, h->d_agent, h->frames_own, h->d_lut, h->d_texels, h->d_tex, h->d_meshes, h->d_tris,
-                  h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_envcam, h->d_tilerecs, h->d_stris, h->d_objbox, h->d_objmask, h->d_queue, h->d_qcount, h->d_items, h->d_qend, h->d_obs_tab, h->d_obsc_tab, h->d_sampler, h->d_texels_seg, h->d_mesh_seg, h->d_qtex, h->d_qtiles, h->d_pixtab, h->d_lines, h->d_leds};
+                  h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_envcam, h->d_tilerecs, h->d_stris, h->d_objbox, h->d_objmask, h->d_queue, h->d_qcount, h->d_items, h->d_qend, h->d_obs_tab, h->d_obsc_tab, h->d_sampler, h->d_texels_seg, h->d_mesh_seg, h->d_qtex, h->d_qtiles, h->d_pixtab, h->d_lines, h->d_leds, h->d_cal_src, h->d_env_cal, h->d_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->overlap.s2) { (void)hipStreamSynchronize(h->overlap.s2); (void)hipStreamDestroy(h->overlap.s2); }
   for (hipEvent_t ev : h->overlap.ev) if (ev) (void)hipEventDestroy(ev);
@@ -709,6 +717,8 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   return DTSIM_OK;
 }
 
+static int drop_luts(dtsim_t* h);
+
 int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
   h->leds_ok = false;
@@ -716,6 +726,7 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
   if (!h->d_lut) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if ((rmapx == nullptr) != (rmapy == nullptr)) return fail(DTSIM_E_INVALID, "rmapx/rmapy must both be given");
   if (rmapx && !(h->cfg.flags & DTSIM_F_DISTORTION)) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_DISTORTION");
+  if (h->n_cal) { int rc = drop_luts(h); if (rc) return rc; }   // one table for every env again
   HIPCHK(hipSetDevice(h->cfg.device));
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
   std::vector<float> lut((size_t)W * H * 4);
@@ -739,6 +750,80 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(h->d_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
   h->have_lut = true;
+  return DTSIM_OK;
+}
+
+static int drop_luts(dtsim_t* h) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (void* p : {(void*)h->d_cal_src, (void*)h->d_env_cal, (void*)h->d_scratch}) if (p) (void)hipFree(p);
+  h->d_cal_src = nullptr; h->d_env_cal = nullptr; h->d_scratch = nullptr;
+  h->n_cal = 0;                                       // (the sampler switch stays: it is dtsim_set_distortion_luts' to set)
+  return DTSIM_OK;
+}
+
+int dtsim_set_distortion_luts(dtsim_t* h, int n_cal, const int32_t* src_index, const int32_t* env_cal, uint32_t flags) {
+  if (!h) return fail(DTSIM_E_INVALID, "null handle");
+  if (flags & ~(uint32_t)DTSIM_LUTS_CAMERA_RAND) return fail(DTSIM_E_INVALID, "unknown flags 0x%x", flags);
+  if (!h->d_lut) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  if (n_cal == 0) {                                   // uninstall: the caller installs a single table with dtsim_set_distortion_lut
+    if (src_index || env_cal) return fail(DTSIM_E_INVALID, "n_cal = 0 takes no tables");
+    if ((flags & DTSIM_LUTS_CAMERA_RAND) && (h->cfg.flags & DTSIM_F_LIGHT_CAPTURE))
+      return fail(DTSIM_E_STATE, "DTSIM_LUTS_CAMERA_RAND with DTSIM_F_LIGHT_CAPTURE is not supported");
+    if (int rc = drop_luts(h)) return rc;
+    h->camera_rand = (flags & DTSIM_LUTS_CAMERA_RAND) != 0;
+    return DTSIM_OK;
+  }
+  if (n_cal < 0 || !src_index || !env_cal) return fail(DTSIM_E_INVALID, "n_cal %d, src_index %p, env_cal %p", n_cal, (const void*)src_index, (const void*)env_cal);
+  if (!(h->cfg.flags & DTSIM_F_DISTORTION)) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_DISTORTION");
+  if (h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) return fail(DTSIM_E_STATE, "per-env distortion tables with DTSIM_F_LIGHT_CAPTURE are not supported");
+  const int W = h->cfg.cam_width, H = h->cfg.cam_height;
+  const size_t hw = (size_t)W * H;
+  for (int e = 0; e < h->N; ++e)
+    if (env_cal[e] < 0 || env_cal[e] >= n_cal) return fail(DTSIM_E_INVALID, "env_cal[%d] = %d outside [0, %d)", e, env_cal[e], n_cal);
+  for (size_t i = 0; i < (size_t)n_cal * hw; ++i)     // every gather of k_remap_cal stays inside the env's scratch frame
+    if (src_index[i] < -1 || src_index[i] >= (int64_t)hw) return fail(DTSIM_E_INVALID, "src_index[%zu] = %d outside [-1, %zu)", i, src_index[i], hw);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // the new buffers first: on any failure the handle keeps the tables it had (single or per env), never a half-installed state
+  int32_t *d_src = nullptr, *d_cal = nullptr;
+  uint8_t* d_scr = nullptr;
+  hipError_t e = hipMalloc(&d_src, sizeof(int32_t) * hw * n_cal);
+  if (e == hipSuccess) e = hipMalloc(&d_cal, sizeof(int32_t) * (size_t)h->N);
+  if (e == hipSuccess) e = hipMalloc(&d_scr, h->frames_bytes);
+  if (e == hipSuccess) e = hipMemcpy(d_src, src_index, sizeof(int32_t) * hw * n_cal, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_cal, env_cal, sizeof(int32_t) * (size_t)h->N, hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? DTSIM_OK : fail(DTSIM_E_HIP, "dtsim_set_distortion_luts: %s", hipGetErrorString(e));
+  // the raster renders rectilinear frames while the tables are installed (this also drops the previous per-env tables)
+  if (rc == DTSIM_OK) rc = dtsim_set_distortion_lut(h, nullptr, nullptr);
+  if (rc != DTSIM_OK) {
+    for (void* p : {(void*)d_src, (void*)d_cal, (void*)d_scr}) if (p) (void)hipFree(p);
+    return rc;
+  }
+  h->d_cal_src = d_src; h->d_env_cal = d_cal; h->d_scratch = d_scr;
+  h->n_cal = n_cal;
+  h->camera_rand = (flags & DTSIM_LUTS_CAMERA_RAND) != 0;
+  return DTSIM_OK;
+}
+
+int dtsim_build_remap_maps(int width, int height, int n_cal, const double* K, const double* D, const double* inv_new_K, float* rmapx, float* rmapy) {
+  if (width < 5 || height < 5 || n_cal < 0 || (n_cal && (!K || !D || !inv_new_K || !rmapx || !rmapy)))
+    return fail(DTSIM_E_INVALID, "dtsim_build_remap_maps: %d x %d, n_cal %d, null tables", width, height, n_cal);
+  dt_build_remap_maps(width, height, n_cal, K, D, inv_new_K, rmapx, rmapy);
+  return DTSIM_OK;
+}
+
+int dtsim_fill_pack_remap(int width, int height, int n_cal, float* rmapx, float* rmapy, const int32_t* hole_order, const int64_t* hole_off,
+                          int32_t* src_index) {
+  if (width <= 0 || height <= 0 || n_cal < 0 || (n_cal && (!rmapx || !rmapy || !hole_off)))
+    return fail(DTSIM_E_INVALID, "dtsim_fill_pack_remap: %d x %d, n_cal %d, null tables", width, height, n_cal);
+  const int64_t hw = (int64_t)width * height;
+  for (int i = 0; i < n_cal; ++i) {
+    if (hole_off[i] < 0 || hole_off[i + 1] < hole_off[i] || (hole_off[i + 1] > hole_off[i] && !hole_order))
+      return fail(DTSIM_E_INVALID, "hole_off[%d..%d] = %lld, %lld", i, i + 1, (long long)hole_off[i], (long long)hole_off[i + 1]);
+    for (int64_t k = hole_off[i]; k < hole_off[i + 1]; ++k)
+      if (hole_order[k] < 0 || hole_order[k] >= hw) return fail(DTSIM_E_INVALID, "hole_order[%lld] = %d outside the image", (long long)k, hole_order[k]);
+  }
+  dt_fill_pack_remap(width, height, n_cal, rmapx, rmapy, hole_order, hole_off, src_index);
   return DTSIM_OK;
 }
 
@@ -894,7 +979,8 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   R.distortion = (h->cfg.flags & DTSIM_F_DISTORTION) ? 1 : 0;
   R.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
   R.n_maps = h->M.n_maps;
-  R.frames = h->frames; R.lut = h->d_lut; R.texels = segment ? h->d_texels_seg : h->d_texels; R.tex = h->d_tex;
+  R.frames = h->n_cal ? h->d_scratch : h->frames;   // camera_rand: the rectilinear frames, gathered into `frames` below
+  R.lut = h->d_lut; R.texels = segment ? h->d_texels_seg : h->d_texels; R.tex = h->d_tex;
   R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg;
   R.maps = h->d_rmaps; R.tiles = h->d_rtiles; R.objs = h->d_robjs; R.meshes = h->d_meshes; R.tris = h->d_tris;
   R.envcam = h->d_envcam;
@@ -934,6 +1020,7 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
     const int t = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
     h->render_tables = t & 0xFF; h->render_pipe = t >> 8;
+    if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch, h->frames, h->d_cal_src, h->d_env_cal, mask, h->N, R.W, R.H);
   }
   HIPCHK(hipGetLastError());
   h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true; h->masked = mask != nullptr;
@@ -982,6 +1069,7 @@ int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if (!h->have_maps || !h->have_reset || !h->have_lut || !h->rendered) return fail(DTSIM_E_STATE, "dtsim_draw_lines before the first dtsim_render (the pass writes the cameras the lines go through)");
   if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_lines after dtsim_render_masked: the post-passes need a full dtsim_render");
+  if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_lines with per-env distortion tables installed (the overlays read the single table)");
   if (n == 0) return DTSIM_OK;
   for (int i = 0; i < n; ++i) {
     const int e = env_idx ? env_idx[i] : 0;
@@ -1016,6 +1104,7 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if (!h->rendered || !h->leds_ok || h->last_segment) return fail(DTSIM_E_STATE, "dtsim_draw_leds needs a preceding dtsim_render (colour view): it tests the spheres against that pass's scene");
   if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_leds after dtsim_render_masked: the post-passes need a full dtsim_render");
+  if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_leds with per-env distortion tables installed (the overlays read the single table)");
   if (n == 0) return DTSIM_OK;
   for (int i = 0; i < n; ++i) {
     const int e = env_idx ? env_idx[i] : 0;

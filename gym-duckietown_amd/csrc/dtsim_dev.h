@@ -90,6 +90,7 @@ struct StepParams {
   uint32_t step_flags;                  // DTSIM_STEP_*
   int32_t light_capture, domain_rand;   // DTSIM_F_LIGHT_CAPTURE (device-side resets take the new light through the last frame's camera); DTSIM_F_DOMAIN_RAND (that camera carries its noise)
   int32_t lanes;                        // lanes of a wavefront that share one env in k_step (1, 2, 4, 8; physics.hip Coop)
+  int32_t camera_rand;                  // DTSIM_LUTS_CAMERA_RAND: device-side resets scale camera height / angle / fov_y (simulator.py:611-614)
   const dtsim_reset_sampler* sampler;   // device copy, or null: device-side reset sampling (N2)
   double delta_time, robot_speed;
   double gain, trim, radius, k, limit;
@@ -254,6 +255,12 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, i
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);
 // the LED spheres of enable_leds (render.hip k_overlay_leds): [count] spheres of env `env` from d_spheres[first..], world space, R = the last render pass's parameters
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env);
+// camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
+// envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
+void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,
+                         const uint8_t* mask, int N, int W, int H);
+void dt_build_remap_maps(int W, int H, int n_cal, const double* K, const double* D, const double* ir, float* rx, float* ry);
+void dt_fill_pack_remap(int W, int H, int n_cal, float* rx, float* ry, const int32_t* order, const int64_t* order_off, int32_t* src_index);
 
 #ifndef DT_OBS_STAGE_ROWS
 #define DT_OBS_STAGE_ROWS 8

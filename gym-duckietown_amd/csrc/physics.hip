@@ -650,7 +650,7 @@ __device__ inline void perturb3(Philox& g, bool on, const double v[3], double sc
 // What Simulator.reset() decides for one env (simulator.py:546-738), drawn on the device: the same
 // distributions and acceptance test as dtsim/reset.py + the host spawn loop, from the Philox stream.
 __device__ inline dtsim_init_state sample_init(const SimArrays& A, const MapSet& M, const uint64_t* blobs,
-                                               const dtsim_reset_sampler& rs, int e, int episode, int map_id) {
+                                               const dtsim_reset_sampler& rs, int e, int episode, int map_id, bool camera_rand) {
   const int N = A.N;
   Philox g = philox_init(rs.seed, (uint32_t)e, (uint32_t)episode);
   dtsim_init_state st;
@@ -680,9 +680,13 @@ __device__ inline dtsim_init_state sample_init(const SimArrays& A, const MapSet&
   perturb3(g, dr, dif, 0.99, st.light_diffuse);
   perturb3(g, dr, gnd, 0.3, st.ground_color);
   st.wheel_dist = dr ? 0.102 * rng_uniform(g, 0.9, 1.1) : 0.102;
-  st.cam_height = 0.108 * (dr ? cam_height_f : 1.0);
-  st.cam_angle_deg = 19.15 * (dr ? cam_angle_f : 1.0);
-  st.cam_fov_y_deg = 75.0 * (dr ? cam_fov_f : 1.0);
+  // camera_rand scales the camera even without domain randomisation (simulator.py:611-614); its noise stays a domain_rand effect
+  // (:1768-1769): zeroed here, as the host reset does, because the per-env render path applies whatever the state holds
+  const bool cam = dr || camera_rand;
+  st.cam_height = 0.108 * (cam ? cam_height_f : 1.0);
+  st.cam_angle_deg = 19.15 * (cam ? cam_angle_f : 1.0);
+  st.cam_fov_y_deg = 75.0 * (cam ? cam_fov_f : 1.0);
+  if (camera_rand && !dr) for (int k = 0; k < 3; ++k) st.camera_noise[k] = 0.0;
   st.dynamics_trim_on = rs.dynamics_rand ? 1 : 0;
   st.dynamics_trim = trim;
   const MapView m = map_view(blobs + M.blob_off[map_id]);
@@ -790,7 +794,7 @@ __global__ __launch_bounds__(STEP_BLOCK) void k_step(SimArrays A, MapSet M, Step
         const bool reload = P.sampler->map_cycle == 2;
         // the objects of the new (or reloaded) map must exist before the spawn test looks at them
         if (cur != nm || reload) { dtsim_init_state z{}; z.map_id = nm | (reload ? DTSIM_MAP_RELOAD : 0); z.wheel_dist = 0.102; apply_init(A, M, e, z, P.delay_steps, P.sampler); }
-        const dtsim_init_state st = sample_init(A, M, blobs, *P.sampler, e, ep, nm);
+        const dtsim_init_state st = sample_init(A, M, blobs, *P.sampler, e, ep, nm, P.camera_rand != 0);
         apply_init(A, M, e, st, P.delay_steps, P.sampler);
       } else {
         const long long slot = ((long long)e + (long long)ep * N) % P.n_pool;
@@ -910,7 +914,7 @@ __global__ __launch_bounds__(STEP_BLOCK) void k_reset(SimArrays A, MapSet M, Ste
                           : ((A.map_id[e] >= 0 && P.sampler->map_cycle) ? (cur + 1) % M.n_maps : cur);
     // objects of a fresh env must exist before the spawn test looks at them
     if (A.map_id[e] != nm || reload) { dtsim_init_state z{}; z.map_id = nm | (reload ? DTSIM_MAP_RELOAD : 0); z.wheel_dist = 0.102; apply_init(A, M, e, z, P.delay_steps, P.sampler); }
-    const dtsim_init_state st = sample_init(A, M, blobs, *P.sampler, e, ep, nm);
+    const dtsim_init_state st = sample_init(A, M, blobs, *P.sampler, e, ep, nm, P.camera_rand != 0);
     apply_init(A, M, e, st, P.delay_steps, P.sampler);
     if (P.light_capture && had_frame) light_through(A, e, mv);
   } else

@@ -696,6 +696,11 @@ __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, Render
     // raster reads one 8-byte mask per (env, block) instead of walking the env's object boxes
     const int n_blk = ((R.W + DT_TILE_W - 1) / DT_TILE_W) * ((R.H + DT_TILE_H - 1) / DT_TILE_H) * 4;
     const float4* bbx = reinterpret_cast<const float4*>(R.blockbox);
+    // The mask must hold every object the rasters' per-pixel test can select: that test takes the pixel centres as fp16 (half an ulp:
+    // up to 1 px below 4096) against the box widened by obj_mrg (up to 0.95 px), so the block boxes are widened by 2 px here.  Without
+    // the pad a pixel just outside an object's box was queued or not depending on which other pixels share its block -- i.e. on the
+    // distortion table, not on the pixel's own ray.
+    const float pad = 2.f;
     unsigned long long livem = 0ull;                 // objects with a live screen box (usually one or none)
     for (int o = 0; o < m.n_obj; ++o) livem |= s_oboxf[o][0] <= s_oboxf[o][1] ? 1ull << o : 0ull;
     for (int b = tid; b < n_blk; b += DT_OBJSETUP_T) {
@@ -703,7 +708,7 @@ __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, Render
       unsigned long long mk = 0ull;
       for (unsigned long long lm = livem; lm; lm &= lm - 1ull) {
         const int o = __builtin_ctzll(lm);
-        if (!(bb.y < s_oboxf[o][0] || bb.x > s_oboxf[o][1] || bb.w < s_oboxf[o][2] || bb.z > s_oboxf[o][3])) mk |= 1ull << o;
+        if (!(bb.y + pad < s_oboxf[o][0] || bb.x - pad > s_oboxf[o][1] || bb.w + pad < s_oboxf[o][2] || bb.z - pad > s_oboxf[o][3])) mk |= 1ull << o;
       }
       R.objmask[(size_t)(pos ? pos[e] : e) * n_blk + b] = mk;   // indexed by position in the render order
     }

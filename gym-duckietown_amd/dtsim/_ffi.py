@@ -38,6 +38,7 @@ OBS_HWC, OBS_CHW, OBS_F32 = 0, 1, 2
 RENDER_SEGMENT, RENDER_GL_FILTER = 1, 2
 STEP_ONE_UPDATE, STEP_POSE_ONLY = 1, 2        # dtsim_step_ex flags
 MAP_RELOAD = 0x40000000
+LUTS_CAMERA_RAND = 1                          # dtsim_set_distortion_luts flag
 
 EXPORTS = [
     "dtsim_abi_version", "dtsim_last_error", "dtsim_device_count", "dtsim_create", "dtsim_destroy",
@@ -45,6 +46,7 @@ EXPORTS = [
     "dtsim_set_spawn_pool", "dtsim_step", "dtsim_step_ex", "dtsim_render", "dtsim_render_ex", "dtsim_set_segment_assets", "dtsim_frames_devptr", "dtsim_frames_bytes",
     "dtsim_bind_frames", "dtsim_draw_lines", "dtsim_draw_leds", "dtsim_allgather_frames", "dtsim_observe", "dtsim_observe_cubic", "dtsim_render_masked", "dtsim_observe_masked", "dtsim_observe_cubic_masked", "dtsim_copy_rows", "dtsim_set_reset_sampler", "dtsim_reset_done", "dtsim_query", "dtsim_read_agent", "dtsim_read", "dtsim_write", "dtsim_field_devptr",
     "dtsim_field_bytes", "dtsim_state_bytes", "dtsim_sync", "dtsim_stream", "dtsim_profile_read",
+    "dtsim_set_distortion_luts", "dtsim_build_remap_maps", "dtsim_fill_pack_remap",
 ]
 
 
@@ -173,6 +175,11 @@ def load(path: str | None = None):
         "dtsim_set_assets": (ci, [vp, C.POINTER(Texture), ci, C.POINTER(Mesh), ci]),
         "dtsim_set_maps": (ci, [vp, C.POINTER(Map), ci]),
         "dtsim_set_distortion_lut": (ci, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "dtsim_set_distortion_luts": (ci, [vp, ci, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32]),
+        "dtsim_build_remap_maps": (ci, [ci, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "dtsim_fill_pack_remap": (ci, [ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
         "dtsim_reset": (ci, [vp, C.POINTER(C.c_uint8), C.POINTER(InitState)]),
         "dtsim_set_spawn_pool": (ci, [vp, C.POINTER(InitState), ci]),
         "dtsim_step": (ci, [vp, vp, ci, ci]),

@@ -43,7 +43,7 @@ class BatchedSimulator:
                  map_data: Optional[dict] = None,
                  asset_root: Optional[str] = None, style: str = "photos", device_reset: bool = False,
                  undistort: bool = False, per_env_camera: bool = False, light_capture: bool = False,
-                 do_reset: bool = True):
+                 camera_rand_pool: Optional[int] = None, do_reset: bool = True):
         self._lib = _ffi.load()
         self._h = C.c_void_p()
         self._device = int(device)
@@ -85,7 +85,13 @@ class BatchedSimulator:
             # domain_rand off the frames after a device-side reset would be jittered while the reference's are not
             raise ValueError("per_env_camera with domain_rand=False needs host-side resets (device_reset / auto_reset draw a camera noise "
                              "that this render path would apply)")
-        flags |= _ffi.F_DOMAIN_RAND if (domain_rand or per_env_camera) else 0
+        # camera_rand with the fisheye (simulator.py:352-358): a calibration per env -- the frames are gathered through per-env remap
+        # tables (dtsim_set_distortion_luts) -- and reset() scales camera height / angle / fov_y even without domain_rand (:611-614),
+        # so the frames go through the per-env camera path.  Without distortion camera_rand keeps its reset-only effect.
+        self.camera_rand_on = bool(camera_rand and distortion and render)
+        if self.camera_rand_on and light_capture:
+            raise ValueError("camera_rand with light_capture is not supported (the per-env fisheye renders through the per-env camera path)")
+        flags |= _ffi.F_DOMAIN_RAND if (domain_rand or per_env_camera or self.camera_rand_on) else 0
         flags |= _ffi.F_AUTO_RESET if auto_reset else 0
         # light_capture (DTSIM_F_LIGHT_CAPTURE): device-side resets take the new episode's light through the camera of the pose the previous
         # episode ended at, as GL does with reset()'s glLightfv (simulator.py:565-584).  With domain_rand=False the shared-camera render then
@@ -172,7 +178,14 @@ class BatchedSimulator:
         _ffi.check(self._lib, self._lib.dtsim_set_maps(self._h, farr, len(self.maps)))
         self.undistort = bool(undistort and distortion)
         self._skip_distort = False
-        if render and distortion:
+        self._cal = None
+        if self.camera_rand_on and not self.undistort:
+            P = min(self.num_envs, 64) if camera_rand_pool is None else int(camera_rand_pool)
+            if not 1 <= P <= self.num_envs:
+                raise ValueError(f"camera_rand_pool {camera_rand_pool}: need 1 <= pool <= num_envs ({self.num_envs})")
+            K, D = dist_mod.sample_calibrations(P, seed)
+            self.set_camera_calibrations(K, D, np.arange(self.num_envs) % P)
+        elif render and distortion:
             # undistort=True: UndistortWrapper(env) -- the simulator's fisheye is skipped (env.undistort, simulator.py:1969)
             # and the wrapper's rectify map is the per-pixel source map instead (wrappers.py:209-227)
             rmx, rmy = (dist_mod.undistort_wrapper_maps if self.undistort else dist_mod.distortion_maps)(
@@ -180,6 +193,10 @@ class BatchedSimulator:
             self.rmapx, self.rmapy = rmx, rmy
             _ffi.check(self._lib, self._lib.dtsim_set_distortion_lut(
                 self._h, rmx.ctypes.data_as(C.POINTER(C.c_float)), rmy.ctypes.data_as(C.POINTER(C.c_float))))
+            if self.camera_rand_on:
+                # undistort=True with camera_rand: no per-env tables (the wrapper skips the simulator's fisheye), but the device reset
+                # sampler still scales the camera and zeroes its noise (the per-env camera path would apply a drawn one)
+                _ffi.check(self._lib, self._lib.dtsim_set_distortion_luts(self._h, 0, None, None, _ffi.LUTS_CAMERA_RAND))
 
         # ---- per-env host reset state (RNG order lives on the host; reset.py)
         self.env_state = [R.EnvResetState(None if seed is None else seed + e) for e in range(self.num_envs)]
@@ -246,7 +263,7 @@ class BatchedSimulator:
                 dynamics_rand=self.dynamics_rand, color_sky=self.color_sky, color_ground=self.color_ground,
                 num_tris_distractors=self.num_tris_distractors, n_visible_draw=(), user_tile_start=self.user_tile_start)
             st.map_id = mi | (_ffi.MAP_RELOAD if self.map_random else 0)
-            if self.per_env_camera and not self.domain_rand:
+            if (self.per_env_camera or self.camera_rand_on) and not self.domain_rand:
                 st.camera_noise[:] = [0.0, 0.0, 0.0]             # drawn, but only applied under domain_rand (simulator.py:1768-1769)
             self.init_states[e] = st
             self.env_state[e].spawn_attempts = 0
@@ -392,10 +409,48 @@ class BatchedSimulator:
             return
         self._skip_distort = flag
         fp = C.POINTER(C.c_float)
-        if flag:
+        if self._cal is not None and not flag:
+            self._install_calibrations()
+        elif flag:
             _ffi.check(self._lib, self._lib.dtsim_set_distortion_lut(self._h, fp(), fp()))
         else:
             _ffi.check(self._lib, self._lib.dtsim_set_distortion_lut(self._h, self.rmapx.ctypes.data_as(fp), self.rmapy.ctypes.data_as(fp)))
+
+    def set_camera_calibrations(self, K, D, env_cal):
+        """Install calibrations for the fisheye (camera_rand): K [P,3,3], D [P,5] (plumb-bob k1, k2, p1, p2, k3 -- e.g. a real
+        Duckiebot's measured calibration) and env_cal [N] in [0, P), the calibration of every env.  The remap tables
+        (dtsim.distortion.build_src_index, bit-identical to the reference's construction) are built on the host, and every render
+        then gathers each env's frame through its own table.  Needs distortion=True; not with undistort=True (the wrapper skips
+        the simulator's fisheye), light_capture, or the overlays (draw_lines / draw_leds)."""
+        if not (self.distortion and self.render_enabled):
+            raise ValueError("set_camera_calibrations needs distortion=True (and render=True)")
+        if self.undistort:
+            raise ValueError("set_camera_calibrations with undistort=True: UndistortWrapper skips the simulator's fisheye")
+        if self.light_capture:
+            raise ValueError("set_camera_calibrations with light_capture is not supported")
+        K = np.ascontiguousarray(np.asarray(K, np.float64))
+        D = np.ascontiguousarray(np.asarray(D, np.float64))
+        if K.ndim != 3 or K.shape[1:] != (3, 3) or D.shape != (K.shape[0], 5) or K.shape[0] < 1:
+            raise ValueError(f"K [P,3,3] and D [P,5]: got {K.shape} and {D.shape}")
+        env_cal = np.ascontiguousarray(np.asarray(env_cal), np.int32)
+        if env_cal.shape != (self.num_envs,) or env_cal.min() < 0 or env_cal.max() >= K.shape[0]:
+            raise ValueError(f"env_cal: need [{self.num_envs}] indices in [0, {K.shape[0]})")
+        src = dist_mod.build_src_index(K, D, self.camera_width, self.camera_height)
+        new_K = np.stack([dist_mod.optimal_new_camera_matrix(K[i], D[i]) for i in range(K.shape[0])])
+        self._cal = (K, D, new_K, env_cal, src)
+        if not self._skip_distort:
+            self._install_calibrations()
+
+    def _install_calibrations(self):
+        _, _, _, env_cal, src = self._cal
+        ip = C.POINTER(C.c_int32)
+        _ffi.check(self._lib, self._lib.dtsim_set_distortion_luts(self._h, int(src.shape[0]), src.ctypes.data_as(ip), env_cal.ctypes.data_as(ip),
+                                                                  _ffi.LUTS_CAMERA_RAND if self.camera_rand_on else 0))
+
+    @property
+    def camera_calibrations(self):
+        """(K [P,3,3], D [P,5], new_K [P,3,3], env_cal [N]) of the installed calibrations, or None."""
+        return None if self._cal is None else tuple(a.copy() for a in self._cal[:4])
 
     # ------------------------------------------------------------------- step --
     def step(self, actions, n_steps: int = 1, flags: int = 0):
@@ -497,6 +552,8 @@ class BatchedSimulator:
         """GL_LINE overlays (the reference's draw_curve / draw_bbox) as a post-pass on the frames of the last render():
         lines [n, 9] = world-space segment (ax, ay, az, bx, by, bz) + colour (r, g, b in 0..1); env_idx [n] (non-decreasing) or None =
         env 0.  dtsim_draw_lines (include/dtsim.h)."""
+        if self._cal is not None and not self._skip_distort:
+            raise ValueError("draw_lines with per-env camera calibrations (camera_rand) is not supported")
         a = np.ascontiguousarray(np.asarray(lines, dtype=np.float32).reshape(-1, 9))
         n = a.shape[0]
         if n == 0:
@@ -544,6 +601,8 @@ class BatchedSimulator:
         """The LED spheres of the reference's enable_leds (objects.py:68-121) as a post-pass on the frames of the last render(): spheres [n, 8] =
         world-space centre (x, y, z), radius, colour (r, g, b in 0..1), alpha, in draw order; env_idx [n] (non-decreasing) or None = env 0.
         dtsim_draw_leds (include/dtsim.h)."""
+        if self._cal is not None and not self._skip_distort:
+            raise ValueError("draw_leds with per-env camera calibrations (camera_rand) is not supported")
         a = np.ascontiguousarray(np.asarray(spheres, dtype=np.float32).reshape(-1, 8))
         n = a.shape[0]
         if n == 0:

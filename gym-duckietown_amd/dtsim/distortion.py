@@ -7,6 +7,12 @@ Here the tables are built once (vectorised numpy) and handed to the library with
 dtsim_set_distortion_lut; the per-frame remap disappears into the raster's ray set-up.
 
 _fill_holes visits holes in the iteration order of a Python set (see fill_holes): kept.
+
+camera_rand (distortion.py:58-83): the reference draws each Simulator's K and D with carnivalmirror's ParameterSampler
+(absent here) within +-5 % of the nominal values; sample_calibrations restates that distribution from the ranges alone
+(uniform per parameter, in the reference's key order) -- PARITY UNPINNED, like the OpenCV calls.  The per-calibration
+tables come from calibration_maps (the numpy statement) or, bit-identical and fast, from build_src_index (host C++ of
+libdtsim, csrc/remap.hip).
 """
 from __future__ import annotations
 
@@ -151,15 +157,92 @@ def fill_holes(rx, ry):
     return rx, ry
 
 
+def calibration_maps(K, D, width: int, height: int):
+    """(rmapx, rmapy) float32 [height,width] of a Distortion with camera matrix K and coefficients D: new_K for the
+    640x480 calibration size (distortion.py:51-56), the rectify map at the observation size, _invert_map, _fill_holes."""
+    K, D = np.asarray(K, np.float64), np.asarray(D, np.float64).reshape(-1)
+    newK = optimal_new_camera_matrix(K, D)
+    mapx, mapy = rectify_maps(K, D, newK, (width, height))
+    rx, ry = invert_map(mapx, mapy)
+    rx, ry = fill_holes(rx, ry)
+    return np.ascontiguousarray(rx, np.float32), np.ascontiguousarray(ry, np.float32)
+
+
 @functools.lru_cache(maxsize=8)
 def distortion_maps(width: int, height: int):
     """(rmapx, rmapy) float32 [height,width]: Distortion().distort's cached tables for an
     observation of this size.  new_K is always computed for 640x480 (distortion.py:13-14,51)."""
-    newK = optimal_new_camera_matrix()
-    mapx, mapy = rectify_maps(CAMERA_MATRIX, DIST_COEFS, newK, (width, height))
-    rx, ry = invert_map(mapx, mapy)
-    rx, ry = fill_holes(rx, ry)
-    return np.ascontiguousarray(rx, np.float32), np.ascontiguousarray(ry, np.float32)
+    return calibration_maps(CAMERA_MATRIX, DIST_COEFS, width, height)
+
+
+# ---- camera_rand -------------------------------------------------------------------------------------------------------
+CAMERA_RAND_KEYS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+_CAMERA_RAND_TAG = int.from_bytes(b"camera_rand", "little")    # keys the sampler's stream apart from every env's np_random
+
+
+def camera_rand_ranges(K=CAMERA_MATRIX, D=DIST_COEFS):
+    """Distortion.randomize_camera's ranges (distortion.py:63-73): (0.95 v, 1.05 v) per parameter -- (high, low) for the
+    negative k1 and p2, (0, 0) for k3."""
+    D = np.asarray(D, np.float64).reshape(-1)
+    vals = (K[0, 0], K[1, 1], K[0, 2], K[1, 2], D[0], D[1], D[2], D[3], D[4])
+    return {k: (0.95 * v, 1.05 * v) for k, v in zip(CAMERA_RAND_KEYS, vals)}
+
+
+def sample_calibrations(n: int, seed=None):
+    """n calibrations (K [n,3,3], D [n,5] float64) drawn as Distortion(camera_rand=True) does, once per Simulator: each
+    parameter uniform between its two bounds, in the reference's key order.  The generator is keyed by (seed,
+    "camera_rand") and touches no env's np_random (carnivalmirror has its own RNG).  PARITY UNPINNED: carnivalmirror's
+    ParameterSampler is restated from the ranges, not pinned against it."""
+    rng = np.random.default_rng(None if seed is None else [int(seed) & 0xFFFFFFFFFFFFFFFF, _CAMERA_RAND_TAG])
+    ranges = camera_rand_ranges()
+    K = np.repeat(CAMERA_MATRIX[None], n, axis=0).copy()
+    D = np.zeros((n, 5), np.float64)
+    for i in range(n):
+        v = {k: float(rng.uniform(min(ranges[k]), max(ranges[k]))) for k in CAMERA_RAND_KEYS}   # (high, low) pairs: between them anyway
+        K[i, 0, 0], K[i, 1, 1], K[i, 0, 2], K[i, 1, 2] = v["fx"], v["fy"], v["cx"], v["cy"]
+        D[i] = (v["k1"], v["k2"], v["p1"], v["p2"], v["k3"])
+    return K, D
+
+
+def hole_order(rx) -> np.ndarray:
+    """The order fill_holes visits the NaN entries of rx in (row * W + col): the iteration order of the Python set it
+    builds, taken from Python itself."""
+    ii, jj = np.nonzero(np.isnan(rx))                  # row-major, like fill_holes' argwhere
+    holes = set(zip(ii.tolist(), jj.tolist()))          # the same insert sequence as fill_holes' add loop: the same table
+    if not holes:
+        return np.zeros(0, np.int32)
+    order = np.array(list(holes), np.int32)
+    return order[:, 0] * np.int32(rx.shape[1]) + order[:, 1]
+
+
+def build_src_index(K, D, width: int, height: int, return_maps: bool = False):
+    """Remap tables of calibrations K [P,3,3] / D [P,5], bit-identical to calibration_maps, built by libdtsim's host
+    C++ (dtsim_build_remap_maps / dtsim_fill_pack_remap, at most 16 threads; the hole visiting order from hole_order).
+    Returns src_index int32 [P,height,width] (the cvRound source pixel row * width + col, -1 outside the image: what
+    dtsim_set_distortion_luts takes), and with return_maps also the float maps (rmapx, rmapy) [P,height,width]."""
+    import ctypes as C
+    from . import _ffi
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(-1, 3, 3))
+    D = np.ascontiguousarray(np.asarray(D, np.float64).reshape(K.shape[0], 5))
+    P, W, H = K.shape[0], int(width), int(height)
+    if P > 256 and not return_maps:                    # the float maps of a chunk at a time (8 bytes a pixel each)
+        return np.concatenate([build_src_index(K[i:i + 256], D[i:i + 256], W, H) for i in range(0, P, 256)])
+    ir = np.ascontiguousarray(np.stack([np.linalg.inv(optimal_new_camera_matrix(K[i], D[i])) for i in range(P)]).reshape(P, 9))
+    rx = np.empty((P, H, W), np.float32)
+    ry = np.empty((P, H, W), np.float32)
+    lib = _ffi.load()
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    _ffi.check(lib, lib.dtsim_build_remap_maps(W, H, P, K.ctypes.data_as(dp), D.ctypes.data_as(dp), ir.ctypes.data_as(dp),
+                                               rx.ctypes.data_as(fp), ry.ctypes.data_as(fp)))
+    orders = [hole_order(rx[i]) for i in range(P)]
+    off = np.zeros(P + 1, np.int64)
+    off[1:] = np.cumsum([len(o) for o in orders])
+    order = np.ascontiguousarray(np.concatenate(orders) if off[-1] else np.zeros(1, np.int32), np.int32)
+    src = np.empty((P, H, W), np.int32)
+    _ffi.check(lib, lib.dtsim_fill_pack_remap(W, H, P, rx.ctypes.data_as(fp), ry.ctypes.data_as(fp),
+                                              order.ctypes.data_as(C.POINTER(C.c_int32)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              src.ctypes.data_as(C.POINTER(C.c_int32))))
+    return (src, rx, ry) if return_maps else src
 
 
 # UndistortWrapper (src/gym_duckietown/wrappers.py:145-227): the wrapper turns the simulator's own fisheye off

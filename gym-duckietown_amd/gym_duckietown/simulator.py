@@ -14,7 +14,7 @@ handle that copies the state; `segment=True` is the segmentation render.
 
 `draw_curve` / `draw_bbox` (round 5): the GL_LINE overlays as a post-pass on the resolved frame (`dtsim_draw_lines`; draw_bbox also switches
 to the reference's debugging camera 0.8 m above the robot).  Not provided (out of scope): the pyglet window itself (nothing
-is displayed), `camera_rand`'s carnivalmirror calibration sampling.  `enable_leds` blends the duckiebots' LED spheres
+is displayed), carnivalmirror itself (`camera_rand` samples from its ranges: dtsim.distortion.sample_calibrations).  `enable_leds` blends the duckiebots' LED spheres
 into the frame as a post-pass (`dtsim_draw_leds`: analytic spheres, front surfaces, after all opaque objects).
 """
 from __future__ import annotations
@@ -93,6 +93,23 @@ _DONE_MSG = {
 }
 
 
+class _CameraModel:
+    """Simulator.camera_model (simulator.py:352-358: a Distortion): the calibration the fisheye uses -- drawn once from the
+    seed with camera_rand (dtsim.distortion.sample_calibrations), else the nominal one."""
+
+    def __init__(self, sim):
+        from dtsim import distortion as dist_mod
+        cal = sim.camera_calibrations
+        if cal is not None:
+            K, D, new_K, env_cal = cal
+            c = int(env_cal[0])
+            self.camera_matrix, self.distortion_coefs, self.new_camera_matrix = K[c], D[c].reshape(1, 5), new_K[c]
+        else:
+            self.camera_matrix = dist_mod.CAMERA_MATRIX.copy()
+            self.distortion_coefs = dist_mod.DIST_COEFS.reshape(1, 5).copy()
+            self.new_camera_matrix = dist_mod.optimal_new_camera_matrix()
+
+
 class Simulator(_EnvBase):
     metadata = {"render.modes": ["human", "rgb_array", "app"], "video.frames_per_second": 30}
     _ACTION_MODE = "wheels"
@@ -107,7 +124,12 @@ class Simulator(_EnvBase):
                  color_ground: Sequence[float] = (0.15, 0.15, 0.15), color_sky: Sequence[float] = BLUE_SKY,
                  style: str = "photos", enable_leds: bool = False, device: int = 0, **env_kwargs):
         if camera_rand:
-            raise NotImplementedError("camera_rand (carnivalmirror calibration sampling) is outside the path this backend implements")
+            # simulator.py:352-356: camera_rand only takes effect with the fisheye on
+            if not distortion:
+                raise NotImplementedError("camera_rand needs distortion=True (the calibration it samples is the fisheye's)")
+            if enable_leds or draw_curve or draw_bbox:
+                raise ValueError("camera_rand with enable_leds / draw_curve / draw_bbox is not supported (the overlays read the single "
+                                 "fisheye table)")
         self.enable_leds = bool(enable_leds)
         self.gl_filter = bool(env_kwargs.pop("gl_filter", False))          # render with the reference renderer's GL_LINEAR arithmetic (DTSIM_RENDER_GL_FILTER: bit-faithful frames, slower)
         self.gl_light_capture = bool(env_kwargs.pop("gl_light_capture", True))   # reset()'s light through the last frame's model-view, as GL does (False: as given)
@@ -129,7 +151,7 @@ class Simulator(_EnvBase):
         self.window = None
         self.accept_start_angle_deg = accept_start_angle_deg
         self.distortion = distortion and not draw_bbox
-        self.camera_rand = False
+        self.camera_rand = bool(camera_rand)
         self._undistort = False
         self.dynamics_rand = dynamics_rand
         self.user_tile_start = user_tile_start
@@ -149,7 +171,8 @@ class Simulator(_EnvBase):
                 accept_start_angle_deg=accept_start_angle_deg, user_tile_start=user_tile_start, seed=seed,
                 distortion=self.distortion, dynamics_rand=dynamics_rand, num_tris_distractors=num_tris_distractors,
                 color_ground=color_ground, color_sky=color_sky, action_mode=self._ACTION_MODE, actions_f64=True,
-                device=device, style=style, do_reset=False, per_env_camera=self.gl_light_capture, **env_kwargs)
+                device=device, style=style, do_reset=False, per_env_camera=self.gl_light_capture, camera_rand=self.camera_rand,
+                **env_kwargs)
         except KeyError as e:
             raise InvalidMapException("Cannot load map data", map_name=map_name) from e
         except Exception as e:
@@ -161,6 +184,7 @@ class Simulator(_EnvBase):
                                  "pass map_name=[...] with the maps to draw from") from e
             raise
         self._bind_map(0)
+        self.camera_model = _CameraModel(self._sim)
         self.cam_offset = np.array([0, 0, 0])
         self.reset()
         self.last_action = np.array([0, 0])

@@ -289,6 +289,32 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps);
  * The per-frame cv2.remap(INTER_NEAREST) (distortion.py:118) is folded into the raster. */
 int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy);
 
+/* camera_rand (simulator.py:352-358, 611-614, 1968-1970; distortion.py:11-83): every Simulator samples its own K and D
+ * once, and its frames are cv2.remap(INTER_NEAREST)-ed through the tables built from them.  Installs n_cal tables
+ * src_index[n_cal][cam_height][cam_width] -- per output pixel the rectilinear source pixel (row * cam_width + col, the
+ * cvRound of the float maps) or -1 (outside the image: black, BORDER_CONSTANT) -- and the table of each env,
+ * env_cal[num_envs] in [0, n_cal).  Needs DTSIM_F_DISTORTION; not with DTSIM_F_LIGHT_CAPTURE.  While installed, the render
+ * pass rasterises rectilinear frames into a scratch batch and gathers every (masked) env's frame through its table;
+ * dtsim_draw_lines / dtsim_draw_leds refuse.  n_cal = 0 (tables NULL) uninstalls, and so does dtsim_set_distortion_lut,
+ * which installs one table for every env again.  Both copy the tables: the caller's buffers are free on return.
+ * DTSIM_LUTS_CAMERA_RAND: device-side resets also scale camera height, angle and fov_y by the randomizer's draws without
+ * domain randomisation, and zero the camera noise then (simulator.py:611-614, 1768-1769).  Every call sets this switch from
+ * its flags, n_cal = 0 included (camera_rand with one table for every env, e.g. UndistortWrapper's); dtsim_set_distortion_lut
+ * leaves it alone.  On failure the handle keeps the tables it had. */
+#define DTSIM_LUTS_CAMERA_RAND 1u
+int dtsim_set_distortion_luts(dtsim_t* h, int n_cal, const int32_t* src_index, const int32_t* env_cal, uint32_t flags);
+/* Host-only builders of those tables (no handle, no GPU), bit-identical to dtsim/distortion.py's numpy statement for any
+ * K and D, spread over at most 16 threads.  dtsim_build_remap_maps: per calibration K[9] and D[5] (the plumb-bob model)
+ * and inv_new_K[9] (np.linalg.inv of the new camera matrix, row-major), the rectify map and its inversion
+ * (Distortion._invert_map, distortion.py:138-216): rmapx / rmapy [n_cal][height][width] float, NaN for holes.
+ * dtsim_fill_pack_remap: Distortion._fill_holes (distortion.py:218-265) in place, visiting the holes of table i in the
+ * order hole_order[hole_off[i] .. hole_off[i + 1]) (row * width + col: the iteration order of the reference's Python set),
+ * then, unless src_index is NULL, the packed source index of dtsim_set_distortion_luts. */
+int dtsim_build_remap_maps(int width, int height, int n_cal, const double* K, const double* D, const double* inv_new_K,
+                           float* rmapx, float* rmapy);
+int dtsim_fill_pack_remap(int width, int height, int n_cal, float* rmapx, float* rmapy, const int32_t* hole_order,
+                          const int64_t* hole_off, int32_t* src_index);
+
 /* Simulator.reset() for the envs with mask[e] != 0 (mask NULL = all): state taken from
  * states[e] (array of num_envs entries). */
 int dtsim_reset(dtsim_t* h, const uint8_t* mask, const dtsim_init_state* states);   /* states == NULL: device sampler */
