@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the dtsim hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print
+the line.  --full adds everything else the benchmark measures, each outside the timed steps: `cpu_baseline` (c3 at N = 1, c1),
+the per-launch series of the render pass (`roofline.kernel_ms_per_launch`), the recorded timings of the reference's functions
+(`reference_functions`) and, on N > 1 ranks, the frame exchange (`gather`).  In a plain run these keys are null.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (what a caller of the
 timed path reads back) as DIR/<name>.npy, float32 / float64, at most DUMP_LIMIT bytes in all.  The inputs are fixed
@@ -17,9 +22,9 @@ Envs are independent, so GPUs shard them with NO data-path collective: `value` i
 sim throughput, scaling "weak".  The north star's RCCL all-gather of the uint8 frame batch
 is measured separately (`gather`, xGMI-link bound) and never part of `value`.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline`
-(dominant kernel = the raster; achieved = algorithmic bytes / HIP-event kernel time) and
-`cpu_baseline` (the oracle on 1 host core, plus `all_cores`: one env per process; bounded samples; N=1 only).
+Output: ONE JSON line on rank 0 with `roofline` (dominant kernel = the raster; achieved = algorithmic bytes / HIP-event
+kernel time) and, with --full, `cpu_baseline` (the reference's CPU path on 1 host core, plus `all_cores`: one env per process;
+bounded samples; N=1 only).
 """
 from __future__ import annotations
 
@@ -291,7 +296,7 @@ def main_c1(args):
     if args.dump_outputs and K > 0:
         _write_outputs(args.dump_outputs, {"obs": obs, "reward": np.float64(r), "done": np.float32(d)})
     cpu = None
-    if args.cpu_steps > 0:
+    if args.full and args.cpu_steps > 0:
         from dtsim import assets
         from oracle import raster, sim as osim
         ext = assets.mesh_extents(("duckie",))
@@ -331,12 +336,15 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
-    ap.add_argument("--cpu-steps", type=int, default=32, help="oracle env-steps for cpu_baseline (about 15 s on one host core)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, the per-launch kernel series, the recorded "
+                         "reference function timings and, on N > 1 ranks, the frame exchange (all outside the timed steps)")
+    ap.add_argument("--cpu-steps", type=int, default=32, help="--full: oracle env-steps for cpu_baseline (about 15 s on one host core)")
     ap.add_argument("--windows", type=int, default=1, help="the --steps timed steps are split into this many consecutive regions; "
                                                            "value = the median one's time per step (each region pays one queue fill and drain)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
-    ap.add_argument("--no-gather", action="store_true", help="skip the RCCL frame all-gather measurement")
+    ap.add_argument("--no-gather", action="store_true", help="--full: skip the RCCL frame all-gather measurement")
     ap.add_argument("--gather-timeout", type=float, default=120.0, help="give up on the frame exchange after this many seconds")
     ap.add_argument("--config", default="c3", choices=["c3", "c1", "c2", "c4", "c5", "c3dr"],
                     help="c3 (default, the headline): raster + fisheye; c1: ONE env through the gym facade, 84x84 observations, "
@@ -458,16 +466,17 @@ def main():
         _write_outputs(args.dump_outputs, dict(outs, envs=env_rows.astype(np.float64), **_sim_outputs(sim, env_rows)))
     per_step = sorted(w / s for w, s in zip(win, sizes))
     t_local = K * per_step[len(per_step) // 2]      # K steps at the median region's time per step
-    # run-to-run spread of the render pass: a separate short series AFTER the timed region, one HIP-event reading per launch
+    # --full: run-to-run spread of the render pass: a separate short series AFTER the timed region, one HIP-event reading per launch
     per_launch = []
-    for t in range(min(K, 16)):
-        one_step(Wm + (t % K))
-        sim.sync()
-        n1, ms1 = sim.profile_read(_ffi.KERNEL_RENDER)
-        if n1 == 1:
-            per_launch.append(ms1)
-    sim.profile_read(_ffi.KERNEL_STEP)
-    per_launch.sort()
+    if args.full:
+        for t in range(min(K, 16)):
+            one_step(Wm + (t % K))
+            sim.sync()
+            n1, ms1 = sim.profile_read(_ffi.KERNEL_RENDER)
+            if n1 == 1:
+                per_launch.append(ms1)
+        sim.profile_read(_ffi.KERNEL_STEP)
+        per_launch.sort()
     t_max = t_local                            # already the max over ranks, per window
 
     guard = {"marker": None}
@@ -516,9 +525,9 @@ def main():
                 pass
         # the reference's own lane / collision / reward functions per call.  They need /root/reference,
         # which the bench box does not have: the numbers recorded in the build container are reported, labelled as such.
-        ref_fn = {"status": "not runnable on the bench box (no /root/reference)"}
+        ref_fn = {"status": "not runnable on the bench box (the reference itself is not there)"} if args.full else None
         rj = os.path.join(ROOT, "profiles", "reference_function_timings.json")
-        if os.path.exists(rj):
+        if args.full and os.path.exists(rj):
             try:
                 rd = json.load(open(rj))
                 ref_fn = {"status": "recorded, not measured in this run", "us_per_call": rd.get("us_per_call"), "where": rd.get("where"),
@@ -566,6 +575,7 @@ def main():
             "gather": gather_,
             "episodes_per_env": done_frac,
             "setup_s": t_setup,
+            "full": bool(args.full),
         }
         try:                                   # RCCL's version banner sits in the C stdio buffer until exit: push it out
             import ctypes                      # first, so that the JSON line is the last line of stdout
@@ -581,12 +591,12 @@ def main():
                 pass
         print(json.dumps(line), flush=True)
 
-    # ---- optional: frame all-gather over RCCL/xGMI (north star; link-bound, not in `value`)
+    # ---- --full: frame all-gather over RCCL/xGMI (north star; link-bound, not in `value`)
     gather = None
     force_gather = os.environ.get("DTSIM_BENCH_FORCE_GATHER") == "1" and dist.is_initialized()
-    done_frac = float(sim.read(_ffi.FIELD_EPISODE).mean())
+    done_frac = float(sim.read(_ffi.FIELD_EPISODE).mean())   # (with --full, the per-launch series' steps are counted too)
     watchdog = None
-    if (world > 1 or force_gather) and not args.no_gather:
+    if args.full and (world > 1 or force_gather) and not args.no_gather:
         # The exchange is reported beside `value`, never inside it: if a collective stalls (a hung link would
         # block inside RCCL, where no exception can be caught) the already-measured line is still printed.
         import threading
@@ -716,7 +726,7 @@ def main():
         watchdog.cancel()
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_steps > 0 and args.config == "c3":
+    if args.full and rank == 0 and world == 1 and args.cpu_steps > 0 and args.config == "c3":
         cpu = cpu_baseline(args.cpu_steps)
 
     if rank == 0:

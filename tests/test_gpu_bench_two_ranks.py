@@ -1,10 +1,10 @@
 """`-m gpu`: bench.py's multi-rank code path with its exchange legs EXECUTED, on a one-GPU box.
 
 The driver launches `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` on an 8-GPU node; this test runs
-the same launch with N = 2 and DTSIM_BENCH_ONE_GPU=1 (both ranks on device 0, gloo for the collectives: the frame / observation
-exchange is staged through pinned host memory instead of RCCL over xGMI) at a small batch, and checks the JSON line: whole-job
-value over both ranks, and every `gather` leg present, finite and checksum-clean.  What it cannot cover is the RCCL transport itself
-(one GPU): that stays "unmeasured on hardware" in DESIGN.md 6.
+the same launch with --full (which runs the exchange legs), N = 2 and DTSIM_BENCH_ONE_GPU=1 (both ranks on device 0, gloo for the
+collectives: the frame / observation exchange is staged through pinned host memory instead of RCCL over xGMI) at a small batch, and
+checks the JSON line: whole-job value over both ranks, and every `gather` leg present, finite and checksum-clean.  What it cannot
+cover is the RCCL transport itself (one GPU): that stays "unmeasured on hardware" in DESIGN.md 6.
 """
 import json
 import os
@@ -23,7 +23,7 @@ def _launch(extra_env):
     env = dict(os.environ, DTSIM_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--envs", "64", "--steps", "3", "--warmup", "1",
-           "--windows", "1", "--cpu-steps", "0", "--gather-timeout", "240"]
+           "--windows", "1", "--full", "--cpu-steps", "0", "--gather-timeout", "240"]
     return subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
 
 

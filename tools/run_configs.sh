@@ -5,13 +5,13 @@ export TAG=${1:-r02}
 OUT=gpurun_out/${TAG}_configs.json
 mkdir -p gpurun_out
 : > $OUT
-python bench.py --config c1 --steps 200 --warmup 20 --cpu-steps 8 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c2 --steps 20 --warmup 3 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c2 --envs 1048576 --fuse 1 --steps 20 --warmup 3 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c3 --steps 30 --warmup 5 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c4 --steps 20 --warmup 3 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c5 --steps 20 --warmup 3 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
-python bench.py --config c3dr --steps 20 --warmup 3 --cpu-steps 0 --no-gather 2>/dev/null | tail -1 >> $OUT   # the gym.make defaults (domain_rand on, no fisheye): context, not a BASELINE config
+python bench.py --full --config c1 --steps 200 --warmup 20 --cpu-steps 8 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c2 --steps 20 --warmup 3 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c2 --envs 1048576 --fuse 1 --steps 20 --warmup 3 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c3 --steps 30 --warmup 5 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c4 --steps 20 --warmup 3 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c5 --steps 20 --warmup 3 --cpu-steps 0 2>/dev/null | tail -1 >> $OUT
+python bench.py --full --config c3dr --steps 20 --warmup 3 --cpu-steps 0 --no-gather 2>/dev/null | tail -1 >> $OUT   # the gym.make defaults (domain_rand on, no fisheye): context, not a BASELINE config
 python - <<'PY'
 import json, sys, os
 tag = os.environ.get("TAG", "r02")
