@@ -110,22 +110,14 @@ struct dtsim {
   RenderMapDev* d_rmaps = nullptr;
   uint32_t* d_rtiles = nullptr;
   TileLds* d_tilerecs = nullptr;
-  ScreenTri* d_stris = nullptr;
-  ObjBox* d_objbox = nullptr;
-  void* d_objmask = nullptr;    // block boxes [tiles*4][4] floats, then object masks [N][tiles*4] u64
+  void* d_render[DT_SLABS] = {};  // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND at dtsim_create, the object slabs at dtsim_set_maps
   std::vector<uint32_t> h_pool;       // host copy of the RGBA8 pool (quad blocks are built from it at dtsim_set_maps)
-  void* d_pixtab = nullptr;           // per-pixel tables of the shared camera (k_pix_setup)
   uint8_t* d_qtex = nullptr;          // quad-layout blocks for k_raster_q
   uint32_t* d_qtiles = nullptr;
   int n_qtiles = 0, qlog2 = 0;
-  int q3_rows = 0;                    // k_raster_v3: LDS table rows (largest padded grid height), 0 = its layout limits are exceeded
-  bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: keep k_raster_q (A/B timing only)
+  bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop); DTSIM_STEP_LANES = 1 / 2 / 4 / 8
   float q_per_m = 0.f;
-  uint16_t* d_queue = nullptr;
-  int32_t* d_qcount = nullptr;
-  uint32_t* d_items = nullptr;
-  uint16_t* d_qend = nullptr;
   dtsim_reset_sampler* d_sampler = nullptr;   // device copy when a reset sampler is installed
   int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
   int32_t* d_obsc_tab = nullptr;  // dtsim_observe_cubic tables (device copy of obsc_tab)
@@ -138,7 +130,6 @@ struct dtsim {
   int max_tris = 0;
   int n_tilerecs = 0, tex_w = 1, tex_h = 1;
   ObjInstDev* d_robjs = nullptr;
-  void* d_envcam = nullptr;
   ProfSlot prof[DTSIM_KERNEL__COUNT];
 };
 
@@ -285,16 +276,11 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(frames %zu B): %s", h->frames_bytes, hipGetErrorString(e)); }
     h->frames = h->frames_own;
     e = hipMalloc(&h->d_lut, sizeof(float) * 4 * (size_t)cfg->cam_height * cfg->cam_width);
-    if (e == hipSuccess) e = hipMalloc(&h->d_envcam, (size_t)h->N * (128 + 64 + 64 + 4) + 64 + ((size_t)h->N + 1) * 64 + (size_t)h->N * 320 + ((size_t)h->N + 1) * 16);   // EnvCam[N], EnvFast[N], EnvQ[N], render order [N], (aligned) EnvV[N + 1], EnvD[N], EnvL[N + 1]
-    if (e == hipSuccess) e = hipMalloc(&h->d_pixtab, (size_t)cfg->cam_height * cfg->cam_width * 64 + 2048);   // PixTab + SampTab + 1 KB store dump + debug counters
-    {  // MSAA edge queue: one worst-case region per raster wavefront (render.hip QREGION)
-      const size_t n_wg = dt_raster_tiles(cfg->cam_width, cfg->cam_height) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK);
-      if (e == hipSuccess) e = hipMalloc(&h->d_queue, n_wg * 4 * (64 * DT_PPT) * DT_ENVS_PER_BLOCK * sizeof(uint16_t));
-      if (e == hipSuccess) e = hipMalloc(&h->d_qcount, (n_wg * 4 + 8 + DT_WORK_INTS * DT_MAX_RENDER_PARTS) * sizeof(int32_t));   // counts, debug counters, work-list header (of each render part)
-      if (e == hipSuccess) e = hipMalloc(&h->d_items, n_wg * (DT_ITEMS_PER_WG + DT_ENVS_PER_BLOCK) * sizeof(uint32_t));   // k_resolve's list + k_resolve_obj's (at most one per env of a workgroup)
-      if (e == hipSuccess) e = hipMalloc(&h->d_qend, n_wg * 4 * DT_ENVS_PER_BLOCK * sizeof(uint16_t));
-    }
-    if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(lut): %s", hipGetErrorString(e)); }
+    size_t bytes[DT_SLABS]; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, bytes);
+    for (int i = DT_SLAB_ENV; i <= DT_SLAB_QEND && e == hipSuccess; ++i) e = hipMalloc(&h->d_render[i], bytes[i]);
+    RenderParams R{}; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, nullptr, h->d_render, &R);
+    if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));   // (the DT_RO_STATS counters start at 0)
+    if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(render scratch): %s", hipGetErrorString(e)); }
     {  // render parts: off (1) unless asked for
       const char* rp = getenv("DTSIM_RENDER_PARTS");
       const int parts = rp ? std::min(std::max(atoi(rp), 1), DT_MAX_RENDER_PARTS) : 1;
@@ -305,7 +291,6 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
         h->overlap.parts = parts;
       }
     }
-    (void)hipMemset((char*)h->d_pixtab + (size_t)cfg->cam_height * cfg->cam_width * 64, 0, 2048);
     if (!(cfg->flags & DTSIM_F_DISTORTION)) {
       // identity LUT: output pixel == rectilinear pixel
       int rc = dtsim_set_distortion_lut(h, nullptr, nullptr);
@@ -326,8 +311,9 @@ void dtsim_destroy(dtsim_t* h) {
   }
   void* ptrs[] = {h->slab, h->d_blobs, h->d_dyn, h->d_states, h->d_mask, h->d_pool, h->d_actions, h->d_qenv,
                   h->d_qpose, h->d_qout, h->d_agent, h->frames_own, h->d_lut, h->d_texels, h->d_tex, h->d_meshes, h->d_tris,
-                  h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_envcam, h->d_tilerecs, h->d_stris, h->d_objbox, h->d_objmask, h->d_queue, h->d_qcount, h->d_items, h->d_qend, h->d_obs_tab, h->d_obsc_tab, h->d_sampler, h->d_texels_seg, h->d_mesh_seg, h->d_qtex, h->d_qtiles, h->d_pixtab, h->d_lines, h->d_leds, h->d_cal_src, h->d_env_cal, h->d_scratch};
+                  h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_tilerecs, h->d_obs_tab, h->d_obsc_tab, h->d_sampler, h->d_texels_seg, h->d_mesh_seg, h->d_qtex, h->d_qtiles, h->d_lines, h->d_leds, h->d_cal_src, h->d_env_cal, h->d_scratch};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (void* p : h->d_render) if (p) (void)hipFree(p);
   if (h->overlap.s2) { (void)hipStreamSynchronize(h->overlap.s2); (void)hipStreamDestroy(h->overlap.s2); }
   for (hipEvent_t ev : h->overlap.ev) if (ev) (void)hipEventDestroy(ev);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -371,7 +357,7 @@ int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, 
   // (which reads d_texels) is used until the next dtsim_set_maps rebuilds them -- never a frame mixing both pools
   if (h->d_qtex) { (void)hipFree(h->d_qtex); h->d_qtex = nullptr; }
   if (h->d_qtiles) { (void)hipFree(h->d_qtiles); h->d_qtiles = nullptr; }
-  h->n_qtiles = 0; h->qlog2 = 0; h->q3_rows = 0;
+  h->n_qtiles = 0; h->qlog2 = 0;
   if (h->d_texels_seg) { (void)hipFree(h->d_texels_seg); h->d_texels_seg = nullptr; }   // mirrors the old list
   if (h->d_texels) { (void)hipFree(h->d_texels); h->d_texels = nullptr; }
   if (h->d_tex) { (void)hipFree(h->d_tex); h->d_tex = nullptr; }
@@ -669,32 +655,22 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   for (void* p : olds) if (p) (void)hipFree(p);
   h->d_blobs = nullptr; h->d_dyn = nullptr; h->d_rmaps = nullptr; h->d_rtiles = nullptr; h->d_robjs = nullptr;
   h->d_tilerecs = nullptr; h->d_qtex = nullptr; h->d_qtiles = nullptr;
-  h->n_qtiles = 0; h->qlog2 = 0; h->q_per_m = 0.f; h->q3_rows = 0;
+  h->n_qtiles = 0; h->qlog2 = 0; h->q_per_m = 0.f;
   if (qlog2 > 0 && !qtiles.empty()) {
     HIPCHK(hipMalloc(&h->d_qtex, qblocks.size() * 4));
     HIPCHK(hipMemcpy(h->d_qtex, qblocks.data(), qblocks.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&h->d_qtiles, qtiles.size() * 4));
     HIPCHK(hipMemcpy(h->d_qtiles, qtiles.data(), qtiles.size() * 4, hipMemcpyHostToDevice));
     h->n_qtiles = (int)qtiles.size() / 2; h->qlog2 = qlog2; h->q_per_m = q_per_m;
-    // ---- k_raster_v3 (render_v3.inc) reads the same pool and table through its own LDS layout: S = 256, padded grids up
-    // to 32 x 24 tiles, up to 4 maps
-    int rows = 0, cols = 0;
-    for (int mi = 0; mi < n_maps; ++mi) { rows = std::max(rows, maps[mi].grid_h + 2 * DT_QRING); cols = std::max(cols, maps[mi].grid_w + 2 * DT_QRING); }
-    if (qlog2 == 8 && rows <= 24 && cols <= 32 && n_maps * 32 <= 128 && !h->raster_old) h->q3_rows = rows;
   }
   HIPCHK(hipMalloc(&h->d_tilerecs, std::max<size_t>(trecs.size(), 1) * sizeof(TileLds)));
   if (!trecs.empty()) HIPCHK(hipMemcpy(h->d_tilerecs, trecs.data(), trecs.size() * sizeof(TileLds), hipMemcpyHostToDevice));
-  if (h->d_stris) { (void)hipFree(h->d_stris); h->d_stris = nullptr; }
-  if (h->d_objbox) { (void)hipFree(h->d_objbox); h->d_objbox = nullptr; }
-  if (h->d_objmask) { (void)hipFree(h->d_objmask); h->d_objmask = nullptr; }
+  for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i) { (void)hipFree(h->d_render[i]); h->d_render[i] = nullptr; }
   h->max_tris = 0;
   for (auto& rm : rmaps) h->max_tris = std::max(h->max_tris, rm.n_tris);
-  if (h->max_tris > 0 && (h->cfg.flags & DTSIM_F_RENDER)) {
-    HIPCHK(hipMalloc(&h->d_stris, (sizeof(ScreenTri) + 16) * (size_t)h->max_tris * h->N));   // + the 16-byte screen boxes behind the triangles
-    HIPCHK(hipMalloc(&h->d_objbox, sizeof(ObjBox) * (size_t)h->N * DTSIM_MAX_OBJECTS));
-    const size_t n_blk = dt_raster_tiles(h->cfg.cam_width, h->cfg.cam_height) * 4;
-    HIPCHK(hipMalloc(&h->d_objmask, n_blk * 16 + (size_t)DTSIM_MAX_MAPS * DTSIM_MAX_OBJECTS * 8 + (size_t)h->N * n_blk * 8));
-  }
+  size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, h->max_tris, bytes);
+  for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i)     // the object slabs: only with mesh objects
+    if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(hipMalloc(&h->d_render[i], bytes[i]));
   h->n_tilerecs = (int)trecs.size();
   h->tex_w = tex_w ? tex_w : 1; h->tex_h = tex_h ? tex_h : 1;
   HIPCHK(hipMalloc(&h->d_blobs, blobs.size() * 8));
@@ -983,43 +959,28 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   R.lut = h->d_lut; R.texels = segment ? h->d_texels_seg : h->d_texels; R.tex = h->d_tex;
   R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg;
   R.maps = h->d_rmaps; R.tiles = h->d_rtiles; R.objs = h->d_robjs; R.meshes = h->d_meshes; R.tris = h->d_tris;
-  R.envcam = h->d_envcam;
-  R.max_tris = h->d_stris ? h->max_tris : 0; R.stris = h->d_stris; R.objbox = h->d_objbox;
-  R.tribox = h->d_stris ? reinterpret_cast<float4*>(h->d_stris + (size_t)h->max_tris * h->N) : nullptr;
-  R.blockbox = reinterpret_cast<float*>(h->d_objmask);
-  R.objrange = h->d_objmask ? reinterpret_cast<uint2*>(reinterpret_cast<char*>(h->d_objmask) + dt_raster_tiles(R.W, R.H) * 4 * 16) : nullptr;
-  R.objmask = h->d_objmask ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(R.objrange) + (size_t)DTSIM_MAX_MAPS * DTSIM_MAX_OBJECTS * 8) : nullptr;
+  R.max_tris = h->d_render[DT_SLAB_STRIS] ? h->max_tris : 0;
+  dt_render_layout(R.N, R.W, R.H, R.max_tris, nullptr, h->d_render, &R);
   R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
-  R.queue = h->d_queue; R.qcount = h->d_qcount;
-  R.dbg = nullptr;
-  const size_t n_wg_ = dt_raster_tiles(R.W, R.H) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK);
-  R.work = h->d_qcount + n_wg_ * 4 + 8; R.items = h->d_items; R.items2 = h->d_items + n_wg_ * DT_ITEMS_PER_WG; R.qend = h->d_qend;
-  if (getenv("DTSIM_DEBUG_QUEUE")) {
-    R.dbg = h->d_qcount + n_wg_ * 4;
-    HIPCHK(hipMemsetAsync(R.dbg, 0, 8 * sizeof(int32_t), h->stream));
-  }
+  if (getenv("DTSIM_DEBUG_QUEUE")) HIPCHK(hipMemsetAsync(R.dbg, 0, DT_DEBUG_INTS * sizeof(int32_t), h->stream)); else R.dbg = nullptr;
   R.tile_recs = h->d_tilerecs; R.n_tile_recs = h->n_tilerecs; R.tex_w = h->tex_w; R.tex_h = h->tex_h;
   R.qtex = (flags & DTSIM_RENDER_GL_FILTER) ? nullptr : h->d_qtex;   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
   R.qtiles = h->d_qtiles; R.n_qtiles = h->n_qtiles; R.qlog2 = h->qlog2; R.q_per_m = h->q_per_m;
-  R.pixtab = h->d_pixtab;
-  R.q3_rows = h->q3_rows;
-  R.envpos = reinterpret_cast<int32_t*>((char*)h->d_envcam + (size_t)h->N * (128 + 64 + 64));
-  R.envv = (char*)h->d_envcam + (((size_t)h->N * (128 + 64 + 64 + 4) + 63) / 64) * 64;
-  R.envd = (char*)R.envv + ((size_t)h->N + 1) * 64;
-  R.dump = (char*)h->d_pixtab + (size_t)R.W * R.H * 64;
-  R.qmax_tiles = 0;
-  for (int mi = 0; mi < h->M.n_maps; ++mi) R.qmax_tiles = std::max(R.qmax_tiles, std::max(h->map_w[mi], h->map_h[mi]) + 2 * DT_QRING);
+  int grid_rows = 0, grid_cols = 0;                  // the largest padded tile grid of the maps
+  for (int mi = 0; mi < h->M.n_maps; ++mi) { grid_rows = std::max(grid_rows, h->map_h[mi] + 2 * DT_QRING); grid_cols = std::max(grid_cols, h->map_w[mi] + 2 * DT_QRING); }
+  R.qmax_tiles = std::max(grid_rows, grid_cols);
+  const int pipe = dt_raster_pipe(R, grid_rows, grid_cols, h->raster_old);
 #ifdef DT_WAVE_SPANS   // experiment: [2][2048][4][8] spans of the exact-path kernels, then [raster workgroups][4 wavefronts][4] stamps of k_raster_v3
   static unsigned long long* d_spans = nullptr;
-  const size_t n_spans = (size_t)2 * 2048 * 4 * 8 + dt_raster_tiles(R.W, R.H) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK) * 4 * 4;
+  const size_t n_spans = (size_t)2 * 2048 * 4 * 8 + dt_raster_groups(R.N, R.W, R.H) * 4 * 4;
   if (getenv("DTSIM_WAVE_SPANS") && !d_spans) HIPCHK(hipMalloc(&d_spans, n_spans * 8));
   R.spans = getenv("DTSIM_WAVE_SPANS") ? d_spans : nullptr;
   if (R.spans) HIPCHK(hipMemsetAsync(R.spans, 0, n_spans * 8, h->stream));
 #endif
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
-    const int t = dt_launch_render(h->stream, h->A, R, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
-    h->render_tables = t & 0xFF; h->render_pipe = t >> 8;
+    h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
+    h->render_pipe = pipe | (R.light ? DTSIM_PIPE_ENV_LIGHT : 0);
     if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch, h->frames, h->d_cal_src, h->d_env_cal, mask, h->N, R.W, R.H);
   }
   HIPCHK(hipGetLastError());
@@ -1034,26 +995,21 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
 #endif
   if (getenv("DTSIM_DEBUG_QUEUE")) {   // profiling aid: how many pixels took the exact MSAA path
     HIPCHK(hipStreamSynchronize(h->stream));
-    {
-      char* dbgp = (char*)h->d_pixtab + (size_t)R.W * R.H * 64 + 1024;
-      int32_t ro[12];                                // DT_RO_STATS build variant: k_resolve_obj's z-buffer
-      HIPCHK(hipMemcpy(ro, dbgp + 768, sizeof ro, hipMemcpyDeviceToHost));
-      unsigned long long rp; memcpy(&rp, ro + 6, 8);
-      if (ro[4]) fprintf(stderr, "[dtsim] k_resolve_obj z-buffer: %d calls (%d triangle-parallel), %.1f staged triangles and %.1f pixels per call, "
-                         "%.2f box candidates per pixel, %.2f passes per call (max over lanes), %.2f if the pairs were spread evenly\n",
-                         ro[4], ro[5], (double)ro[2] / ro[4], (double)ro[3] / ro[4], ro[3] ? (double)ro[8] / ro[3] : 0.0, (double)ro[9] / ro[4], (double)ro[10] / ro[4]);
-      HIPCHK(hipMemset(dbgp + 768, 0, sizeof ro));
-    }
+    int32_t* ro_stats = reinterpret_cast<RenderDump*>(R.dump)->ro_stats, ro[12];   // DT_RO_STATS build variant: k_resolve_obj's z-buffer
+    HIPCHK(hipMemcpy(ro, ro_stats, sizeof ro, hipMemcpyDeviceToHost));
+    if (ro[4]) fprintf(stderr, "[dtsim] k_resolve_obj z-buffer: %d calls (%d triangle-parallel), %.1f staged triangles and %.1f pixels per call, "
+                       "%.2f box candidates per pixel, %.2f passes per call (max over lanes), %.2f if the pairs were spread evenly\n",
+                       ro[4], ro[5], (double)ro[2] / ro[4], (double)ro[3] / ro[4], ro[3] ? (double)ro[8] / ro[3] : 0.0, (double)ro[9] / ro[4], (double)ro[10] / ro[4]);
+    HIPCHK(hipMemset(ro_stats, 0, sizeof ro));
     const size_t npix = (size_t)R.W * R.H;
-    const size_t n_wg = dt_raster_tiles(h->cfg.cam_width, h->cfg.cam_height) * (((size_t)h->N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK);
-    std::vector<int32_t> qc(n_wg * 4);
-    HIPCHK(hipMemcpy(qc.data(), h->d_qcount, qc.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> qc(dt_raster_groups(R.N, R.W, R.H) * 4);   // one count per raster wavefront
+    HIPCHK(hipMemcpy(qc.data(), R.qcount, qc.size() * 4, hipMemcpyDeviceToHost));
     long long tot = 0, mx = 0, iters = 0, nonempty = 0;
     for (int32_t v : qc) { tot += v; mx = std::max<long long>(mx, v); iters += (v + 63) / 64; nonempty += v > 0; }
     fprintf(stderr, "[dtsim] resolve: %lld of %zu wavefront regions non-empty, %lld 64-lane iterations, lane utilisation %.1f%%\n",
             nonempty, qc.size(), iters, iters ? 100.0 * tot / (64.0 * iters) : 0.0);
-    int32_t dbg[8];
-    HIPCHK(hipMemcpy(dbg, h->d_qcount + n_wg * 4, sizeof dbg, hipMemcpyDeviceToHost));
+    int32_t dbg[DT_DEBUG_INTS];
+    HIPCHK(hipMemcpy(dbg, R.dbg, sizeof dbg, hipMemcpyDeviceToHost));
     unsigned long long pairs; memcpy(&pairs, dbg + 6, 8);
     fprintf(stderr, "[dtsim] resolve mesh pass: %d (batch,env) pairs, %d objects streamed, %d z-buffer calls (%d triangle-parallel), "
                     "%d triangles staged, %d pixels, %llu pixel x triangle tests\n", dbg[0], dbg[1], dbg[4], dbg[5], dbg[2], dbg[3], pairs);
@@ -1084,7 +1040,8 @@ int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int
   }
   HIPCHK(hipMemcpyAsync(h->d_lines, lines, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   RenderParams R{};
-  R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height; R.frames = h->frames; R.lut = h->d_lut; R.envcam = h->d_envcam;
+  R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height; R.frames = h->frames; R.lut = h->d_lut;
+  dt_render_layout(R.N, R.W, R.H, 0, nullptr, h->d_render, &R);   // (the overlays read the EnvCam records the pass wrote)
   int i0 = 0;
   while (i0 < n) {                                    // one launch per env that has segments
     const int e = env_idx ? env_idx[i0] : 0;
@@ -1524,8 +1481,8 @@ int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
       if (!to_host) return fail(DTSIM_E_INVALID, "DTSIM_FIELD_RENDER_POS is read-only");
       int32_t* out = static_cast<int32_t*>(host);
       if (h->render_tables & 4) {
-        const int32_t* envpos = reinterpret_cast<const int32_t*>((const char*)h->d_envcam + N * (128 + 64 + 64));
-        hipError_t e = hipMemcpy(out, envpos, N * 4, hipMemcpyDeviceToHost);
+        RenderParams R{}; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, 0, nullptr, h->d_render, &R);
+        hipError_t e = hipMemcpy(out, R.envpos, N * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy render order: %s", hipGetErrorString(e));
       } else {
         for (size_t i = 0; i < N; ++i) out[i] = (int32_t)i;

@@ -190,6 +190,7 @@ struct ObjBox { float bx0, bx1, by0, by1; int32_t first, count, pad[2]; };      
 static inline size_t dt_raster_tiles(int W, int H) {
   return (size_t)((W + DT_TILE_W - 1) / DT_TILE_W) * (size_t)((H + DT_TILE_H - 1) / DT_TILE_H);
 }
+static inline size_t dt_raster_groups(int N, int W, int H) { return dt_raster_tiles(W, H) * (((size_t)N + DT_ENVS_PER_BLOCK - 1) / DT_ENVS_PER_BLOCK); }
 
 struct RenderParams {
   int32_t N, W, H, distortion;
@@ -205,7 +206,7 @@ struct RenderParams {
   const ObjInstDev* objs;
   const MeshDev* meshes;
   const TriDev* tris;
-  void* envcam;                 // [N] EnvCam scratch written by the setup kernel
+  void* envcam;                 // [N] EnvCam written by the setup kernel (the render scratch: dt_render_layout)
   // mesh objects: per-env screen-space triangles written by the object setup kernel
   int32_t max_tris, segment;    // triangle slots per env (max over maps), 0 = no objects anywhere; segment: DTSIM_RENDER_SEGMENT
   ScreenTri* stris;             // [N][max_tris]
@@ -217,8 +218,8 @@ struct RenderParams {
   uint16_t* queue;              // MSAA edge-pixel queue regions, [workgroups][4][256*16]
   int32_t* qcount;              // [workgroups][4]
   uint16_t* qend;               // [workgroups][4][DT_ENVS_PER_BLOCK] queue fill of each region after each env of the chunk (mesh-object renders)
-  int32_t* dbg;                 // optional debug counters (DTSIM_DEBUG_QUEUE), else null
-  int32_t* work;                // [0] number of work items (raster appends), [1] resolve cursor, [2], [3] the same for k_resolve_obj ([2] = its heavy items, front of the list; [6] = the others, back); zeroed per render (DT_WORK_INTS per render part)
+  int32_t* dbg;                 // [DT_DEBUG_INTS] debug counters (DTSIM_DEBUG_QUEUE), else null
+  int32_t* work;                // [0] number of work items (raster appends), [1] resolve cursor, [2], [3] the same for k_resolve_obj ([2] = its heavy items, front of the list; [6] = the others, back); zeroed per render ([DT_MAX_RENDER_PARTS][DT_WORK_INTS])
   uint32_t* items;              // [workgroups * DT_ITEMS_PER_WG] work items: raster workgroup * DT_ITEMS_PER_WG + part
   uint32_t* items2;             // [workgroups * DT_ENVS_PER_BLOCK] work items of k_resolve_obj: raster workgroup * DT_ITEMS_PER_WG + env group
   const uint8_t* mesh_seg;      // [n_meshes][4] flat segmentation colour per mesh (segment renders only)
@@ -229,26 +230,39 @@ struct RenderParams {
   float q_per_m;                // quad cells per metre (S / tile_size), max over maps: scales the MSAA margin
   int32_t qmax_tiles;           // largest padded grid extent over the maps (tiles)
   int32_t* envpos;              // [N] position of each env in the render order (k_env_sort)
-  void* dump;                   // 1 KB scratch: masked lanes of the unconditional frame store write here
-  void* pixtab;                 // [H*W] PixTab (16 B) then [H*W] SampTab (48 B): per-pixel tables of the shared camera
+  void* dump;                   // RenderDump: masked lanes of the unconditional frame store write here
+  void* pixtab;                 // [H*W] PixTab (16 B), then [H*W] SampTab (32 B) (render.hip): per-pixel tables of the shared camera
   void* envv;                   // [N + 1] EnvV (render.hip): k_raster_v3's per-env constants in render order
   void* envd;                   // [N] EnvD (render_v3dr.inc, 320 B, render order): k_raster_v3dr's per-env constants (domain randomisation)
-  int32_t q3_rows;              // k_raster_v3 (render_v3.inc): rows of its LDS tile table (largest padded grid height); 0: k_raster_q is used
+  int32_t q3_rows;              // k_raster_v3 / k_raster_v3dr: rows of their LDS tile table (largest padded grid height); 0: they cannot run (dt_raster_pipe)
   int32_t light;                // DTSIM_F_LIGHT_CAPTURE with the shared camera: every env lit by its own eye-space light (k_cam_setup, the LIGHT kernels)
   unsigned long long* spans;    // DT_WAVE_SPANS build variant only (else null): [2][2048 workgroups][4 wavefronts]{start, end, items, longest / first item, start of the first, sum, last item} in 100 MHz ticks
 };
-// tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an
+#define DT_MAX_RENDER_PARTS 8
+#define DT_WORK_INTS 8           // RenderParams.work: ints per render part
+#define DT_WORK_LIVE 7           // RenderParams.work[DT_WORK_LIVE]: envs of a masked pass (k_env_sort_masked), read by the SUB rasters
+#define DT_DEBUG_INTS 8          // RenderParams.dbg
+// RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane); `ro_stats`, the DT_RO_STATS build
+// variant's k_resolve_obj z-buffer counters (DTSIM_DEBUG_QUEUE prints them)
+struct RenderDump { uint8_t store[64 * 16]; int32_t ro_stats[12]; };
+// The render scratch (render.hip dt_render_layout): the allocations RenderParams points into, each a run of arrays -- ENV: per env EnvCam, EnvFast,
+// EnvQ, envpos, EnvV [N + 1], EnvD, EnvL [N + 1]; PIX: PixTab, SampTab, RenderDump; QCOUNT: qcount, dbg, work; ITEMS: items, items2; STRIS: stris, tribox.
+enum RenderSlab { DT_SLAB_ENV, DT_SLAB_PIX, DT_SLAB_QUEUE, DT_SLAB_QCOUNT, DT_SLAB_ITEMS, DT_SLAB_QEND, DT_SLAB_STRIS, DT_SLAB_OBJBOX, DT_SLAB_OBJMASK, DT_SLABS };
+// With bytes: bytes[s] = the size of slab s for N envs, W x H frames and max_tris triangle slots per env (0: no such slab).  With R: points
+// R's scratch fields (envcam .. objmask, dbg included; the object arrays only with max_tris > 0) into base[DT_SLABS] (null bases: null arrays).
+void dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base = nullptr, RenderParams* R = nullptr);
+// The raster of a pass (DTSIM_PIPE_*) from R, the largest padded tile grid of the maps (grid_rows x grid_cols, DT_QRING ring included) and
+// DTSIM_RASTER_OLD (raster_old: k_raster_q / the generic raster instead of k_raster_v3 / k_raster_v3dr); sets R.q3_rows.
+int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_old);
+// pipe: dt_raster_pipe's choice for R.  tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an
 // earlier launch (they depend on the camera LUT and the maps only); returns the bits that are valid after this launch,
 // plus bit 2 when the pass ran in k_env_sort's render order (RenderParams.envpos holds it: DTSIM_FIELD_RENDER_POS).
 // Render parts (round 4): with parts > 1 the exact-path kernels of one range of chunks run on s2 beside the raster of the
 // next range; ev[p] orders range p across the two streams, ev[DT_MAX_RENDER_PARTS] joins s2 back into the caller's stream.
-#define DT_MAX_RENDER_PARTS 8
-#define DT_WORK_INTS 8           // RenderParams.work: ints per render part
-#define DT_WORK_LIVE 7           // RenderParams.work[DT_WORK_LIVE]: envs of a masked pass (k_env_sort_masked), read by the SUB rasters
 struct RenderOverlap { int parts; hipStream_t s2; hipEvent_t ev[DT_MAX_RENDER_PARTS + 1]; };
 // mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
 // only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int tables, const RenderOverlap* ov = nullptr,
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int pipe, int tables, const RenderOverlap* ov = nullptr,
                      const uint8_t* mask = nullptr);
 // GL_LINE overlays (draw_curve / draw_bbox) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.

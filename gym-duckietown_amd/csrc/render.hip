@@ -45,6 +45,7 @@
 //                 1/depth space, then the same shading.
 //   Segmentation render (dtsim_render_ex): same kernels on the segmented texel pool, k_cam_setup forces the unlit
 //                 state and the magenta clear / ground colour, k_obj_setup folds the mesh's flat colour into Kd.
+//   Host side: dt_render_layout lays out the render scratch (per-env records, per-pixel tables, queues, work lists); dt_raster_pipe picks the raster.
 //
 // Roofline: algorithmic bytes per env-step = W*H*3 (921 600 B at 640x480), written once (+ the ~1.3 % edge
 // pixels a second time); LUT / textures / tables are shared by all envs and stay in registers / LDS / L2.
@@ -2596,7 +2597,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
                   zbuffer_chunk(w_tris, w_scr, fill, have[j], lane, (nxv[j] + 1.f) * 0.5f * (float)R.W, (1.f - nyv[j]) * 0.5f * (float)R.H,
                                 zbest[j], tbest[j],
 #ifdef DT_RO_STATS
-                                reinterpret_cast<int32_t*>(reinterpret_cast<char*>(R.pixtab) + (size_t)R.W * R.H * 64 + 1024 + 768));
+                                reinterpret_cast<RenderDump*>(R.dump)->ro_stats);
 #else
                                 nullptr);
 #endif
@@ -2885,12 +2886,61 @@ template <class K> static size_t resident_blocks(K kernel, size_t lds) {
   return cache[key] = (size_t)per_cu * (size_t)n_cu;
 }
 
-// One range of chunks through its raster (stream s) and exact-path kernels (stream s_res, after event ev when it is
+// ---- the render scratch: every array of the slabs (dtsim_dev.h RenderSlab), each from a 64-byte boundary ----------------------------------
+#define DT_SCRATCH_ALIGN 64
+static_assert(DT_SCRATCH_ALIGN % 64 == 0 && DT_SCRATCH_ALIGN % alignof(EnvD) == 0 && DT_SCRATCH_ALIGN % alignof(float4) == 0,
+              "EnvQ, EnvV and EnvD records are 64-byte aligned (one scalar load each), tribox 16-byte aligned (float4)");
+struct Slab {                                         // the arrays of one allocation, one after the other (base null: sizes only)
+  char* base; size_t bytes = 0;
+  template <class T> T* take(size_t n) {
+    const size_t off = (bytes + DT_SCRATCH_ALIGN - 1) / DT_SCRATCH_ALIGN * DT_SCRATCH_ALIGN;
+    bytes = off + n * sizeof(T); return base ? reinterpret_cast<T*>(base + off) : nullptr;
+  }
+};
+// the arrays dt_launch_render reaches beside RenderParams; the per-position ones (EnvQ, EnvV, EnvD, EnvL: render order) move with a render part
+struct EnvRecs { EnvCam* cams; EnvFast* fasts; EnvQ* envq; EnvV* envv; EnvD* envd; EnvL* envl; PixTab* pixtab; SampTab* samptab; };
+static EnvRecs render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams& R) {
+  const size_t n = (size_t)N, n_pix = (size_t)W * H, n_tiles = dt_raster_tiles(W, H), n_wg = dt_raster_groups(N, W, H);
+  Slab sl[DT_SLABS];                                  // (null bases: sizes only)
+  for (int i = 0; i < DT_SLABS; ++i) sl[i].base = base ? static_cast<char*>(base[i]) : nullptr;
+  Slab &env = sl[DT_SLAB_ENV], &pix = sl[DT_SLAB_PIX], &qc = sl[DT_SLAB_QCOUNT], &it = sl[DT_SLAB_ITEMS], &ob = sl[DT_SLAB_OBJMASK];
+  EnvRecs x;                                          // EnvV and EnvL: one record more (the env loops prefetch one past their chunk)
+  R.envcam = x.cams = env.take<EnvCam>(n); x.fasts = env.take<EnvFast>(n); x.envq = env.take<EnvQ>(n); R.envpos = env.take<int32_t>(n);
+  R.envv = x.envv = env.take<EnvV>(n + 1); R.envd = x.envd = env.take<EnvD>(n); x.envl = env.take<EnvL>(n + 1);
+  R.pixtab = x.pixtab = pix.take<PixTab>(n_pix); x.samptab = pix.take<SampTab>(n_pix); R.dump = pix.take<RenderDump>(1);
+  R.queue = sl[DT_SLAB_QUEUE].take<uint16_t>(n_wg * (RB / 64) * QREGION);
+  R.qcount = qc.take<int32_t>(n_wg * (RB / 64)); R.dbg = qc.take<int32_t>(DT_DEBUG_INTS); R.work = qc.take<int32_t>((size_t)DT_WORK_INTS * DT_MAX_RENDER_PARTS);
+  R.items = it.take<uint32_t>(n_wg * ITEMS_PER_WG); R.items2 = it.take<uint32_t>(n_wg * ENVS_PER_BLOCK);   // items2: k_resolve_obj's, at most one per env of a workgroup
+  R.qend = sl[DT_SLAB_QEND].take<uint16_t>(n_wg * (RB / 64) * ENVS_PER_BLOCK);
+  if (max_tris > 0) {
+    R.stris = sl[DT_SLAB_STRIS].take<ScreenTri>(n * max_tris); R.tribox = sl[DT_SLAB_STRIS].take<float4>(n * max_tris);
+    R.objbox = sl[DT_SLAB_OBJBOX].take<ObjBox>(n * DTSIM_MAX_OBJECTS);
+    R.blockbox = reinterpret_cast<float*>(ob.take<float4>(n_tiles * 4)); R.objrange = ob.take<uint2>((size_t)DTSIM_MAX_MAPS * DTSIM_MAX_OBJECTS);
+    R.objmask = ob.take<unsigned long long>(n * n_tiles * 4);
+  }
+  if (bytes) for (int i = 0; i < DT_SLABS; ++i) bytes[i] = sl[i].bytes;
+  return x;
+}
+void dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams* R) { RenderParams tmp{}; render_layout(N, W, H, max_tris, bytes, base, R ? *R : tmp); }
+
+int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_old) {
+  // k_raster_v3 / k_raster_v3dr: 256 x 256 tile textures; the maps' padded grids side by side in one LDS tile table
+  const bool v3 = R.qlog2 == 8 && grid_rows <= V3_MAX_ROWS && grid_cols <= V3_MAP_COLS && R.n_maps * V3_MAP_COLS <= V3_TAB_PITCH / 2 && !raster_old;
+  R.q3_rows = v3 ? grid_rows : 0;
+  const bool records = R.qtex && !R.segment && (R.W & 3) == 0;   // the quad records (none with gl_filter)
+  // shared camera: square power-of-two tile textures (S = 256 tables carry the record-offset mask of the S256 kernels -- q8_rec256 --,
+  // which need a padded grid under 128 tiles: Q8_SNAP)
+  if (records && !R.domain_rand && (size_t)R.n_qtiles * 8 <= 32768 && !(R.qlog2 == 8 && R.qmax_tiles >= 256)) return v3 ? DTSIM_PIPE_V3 : DTSIM_PIPE_Q;
+  if (records && R.domain_rand && v3) return DTSIM_PIPE_V3DR;   // domain randomisation on the quad records
+  return (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV : DTSIM_PIPE_GENERIC;   // the generic k_raster
+}
+
+// One range of chunks through raster `pipe` (stream s) and the exact-path kernels (stream s_res, after event ev when it is
 // another stream): the whole batch, or one of dt_launch_render's render parts (every array already moved to the range).
 // SUB: the masked pass -- the quad-record rasters' SUB instantiations over positions [0, live) (never the generic raster).
 template <bool SUB>
-static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t ev, const RenderParams& R, EnvCam* cams, EnvFast* fasts, EnvQ* envq,
-                                  EnvV* envv, EnvD* envd, EnvL* envl, uint8_t* frames_raster, bool quad, bool v3, bool v3dr, bool obj, bool has_pos) {
+static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t ev, const RenderParams& R, const EnvRecs& x, int pipe, bool has_pos) {
+  const bool obj = R.max_tris > 0, quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q;
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
   const size_t lds = (size_t)R.n_tile_recs * sizeof(TileLds);
   const size_t lds1 = lds + (size_t)RB * PPT * sizeof(uint32_t);          // + store transpose
@@ -2899,37 +2949,34 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
   // XCD-affine map: 8 slices of ceil(n_chunks / 8) chunks, frame tiles in groups of dt_q_tile_group() (the last group padded)
   const int q_tg = dt_q_tile_group((int)dt_raster_tiles(R.W, R.H));
   const dim3 gridq((unsigned)(((dt_raster_tiles(R.W, R.H) + q_tg - 1) / q_tg) * q_tg * ((n_chunks + 7) / 8) * 8));
+  const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
+  const size_t lds_tab = (size_t)R.q3_rows * V3_TAB_PITCH * 4;   // the v3 kernels' LDS tile table
+  const size_t lds3 = lds_tab + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // + per-wavefront buffers, the chunk's EnvQ records
+  const size_t ldsd = lds_tab + (size_t)(RB / 64) * RQ_LIST * 4;
+  const bool s256 = R.qlog2 == 8 && R.qmax_tiles < 256;
 #define LAUNCH_RASTER(DR_, OBJ_)                                                                              \
-  hipLaunchKernelGGL((k_raster<DR_, OBJ_>), grid, dim3(RB), lds1, s, R, cams, fasts, frames_raster, R.texels,               \
+  hipLaunchKernelGGL((k_raster<DR_, OBJ_>), grid, dim3(RB), lds1, s, R, x.cams, x.fasts, R.frames, R.texels,                  \
                      reinterpret_cast<const float4*>(R.lut), R.maps, R.tile_recs, R.queue, R.qcount)
-  if (quad) {
-    const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
-    PixTab* pixtab = reinterpret_cast<PixTab*>(R.pixtab);
-    SampTab* samptab = reinterpret_cast<SampTab*>(pixtab + (size_t)R.W * R.H);
-#define LAUNCH_Q(OBJ_, S256_) do { if (R.light) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, true, SUB>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, \
-                                           R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
-                                else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, false, SUB>), gridq, dim3(RB), ldsq, s, R, cams, fasts, envq, frames_raster, R.qtex, \
-                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
-    const bool s256 = R.qlog2 == 8 && R.qmax_tiles < 256;
-    // k_raster_v3 (render_v3.inc): S = 256 textures, padded grids up to 32 x 24 tiles, up to 4 maps (else k_raster_q)
-    if (v3) {
-      const size_t lds3 = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // tile table, per-wavefront buffers, the chunk's EnvQ records
-#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, \
-                                           R.qtex, reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, envl); \
-                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridq, dim3(RB), lds3, s, R, cams, fasts, envq, envv, frames_raster, R.qtex, \
-                                           reinterpret_cast<const float4*>(R.lut), pixtab, samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
-      if (obj) LAUNCH_V3(true); else
-      LAUNCH_V3(false);
+#define LAUNCH_Q(OBJ_, S256_) do { if (R.light) hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, true, SUB>), gridq, dim3(RB), ldsq, s, R, x.cams, x.fasts, x.envq, R.frames, \
+                                           R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
+                                else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, false, SUB>), gridq, dim3(RB), ldsq, s, R, x.cams, x.fasts, x.envq, R.frames, R.qtex, \
+                                           reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
+#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridq, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, \
+                                           R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
+                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridq, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, R.qtex, \
+                                           reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
+  switch (pipe) {
+    case DTSIM_PIPE_V3: if (obj) LAUNCH_V3(true); else LAUNCH_V3(false); break;
+    case DTSIM_PIPE_Q: if (obj) { if (s256) LAUNCH_Q(true, true); else LAUNCH_Q(true, false); } else if (s256) LAUNCH_Q(false, true); else LAUNCH_Q(false, false); break;
+    case DTSIM_PIPE_V3DR:
+      if (obj) hipLaunchKernelGGL((k_raster_v3dr<true, SUB>), gridq, dim3(RB), ldsd, s, R, x.cams, x.envd, R.frames, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+      else hipLaunchKernelGGL((k_raster_v3dr<false, SUB>), gridq, dim3(RB), ldsd, s, R, x.cams, x.envd, R.frames, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+      break;
+    case DTSIM_PIPE_GENERIC_ENV: if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); break;   // per-env EnvCam (light: the shared camera's, with the env's light)
+    default: if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false);
+  }
 #undef LAUNCH_V3
-    } else if (obj) { if (s256) LAUNCH_Q(true, true); else LAUNCH_Q(true, false); }
-    else { if (s256) LAUNCH_Q(false, true); else LAUNCH_Q(false, false); }
 #undef LAUNCH_Q
-  } else if (v3dr) {
-    const size_t ldsd = (size_t)R.q3_rows * V3_TAB_PITCH * 4 + (size_t)(RB / 64) * RQ_LIST * 4;
-    if (obj) hipLaunchKernelGGL((k_raster_v3dr<true, SUB>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-    else hipLaunchKernelGGL((k_raster_v3dr<false, SUB>), gridq, dim3(RB), ldsd, s, R, cams, envd, frames_raster, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-  } else if (R.domain_rand || R.segment || R.light) { if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); }   // per-env EnvCam path (light: the shared camera's EnvCam with the env's light)
-  else { if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false); }
 #undef LAUNCH_RASTER
   // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region_q); generic raster:
   // k_resolve drains them (front of the queue regions).  Pixels inside mesh-object screen boxes (far end of the regions)
@@ -2937,38 +2984,26 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
   if (s_res != s && (obj || !quad)) { (void)hipEventRecord(ev, s); (void)hipStreamWaitEvent(s_res, ev, 0); }
   // persistent wavefronts pulling work items: enough workgroups to fill every CU at the kernel's occupancy
   // (round 4: EXACTLY the resident workgroups -- every wavefront's first grab is static, a workgroup that waits for a slot would sit on its items)
-  if (v3dr) {                                        // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
-    const size_t ldsr = (size_t)R.q3_rows * V3_TAB_PITCH * 4;
-    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, ldsr)));
-    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), ldsr, s_res, R, cams, envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+  if (pipe == DTSIM_PIPE_V3DR) {                     // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
+    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, lds_tab)));
+    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), lds_tab, s_res, R, x.cams, x.envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
   } else if (!quad) {
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve, lds2)));
-    hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s_res, R, cams, R.queue, R.qcount);
+    hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s_res, R, x.cams, R.queue, R.qcount);
   }
   if (obj) {
     const size_t lds4 = lds + (size_t)(RB / 64) * TRI_CAP * sizeof(TriCov) + (size_t)(RB / 64) * RO_SCR_BYTES;
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_obj<DT_RES_NB>, lds4)));
-    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s_res, R, cams, R.queue, 1, has_pos ? envq : (const EnvQ*)nullptr);
+    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s_res, R, x.cams, R.queue, 1, has_pos ? x.envq : (const EnvQ*)nullptr);
   }
 }
 
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int tables, const RenderOverlap* ov, const uint8_t* mask) {
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int pipe, int tables, const RenderOverlap* ov, const uint8_t* mask) {
   RenderParams R = R_in;
   tables &= 3;                                         // bit 2 (returned): this pass ran in k_env_sort's order (DTSIM_FIELD_RENDER_POS)
-  EnvCam* cams = reinterpret_cast<EnvCam*>(R.envcam);
-  EnvFast* fasts = reinterpret_cast<EnvFast*>(cams + A.N);
-  EnvQ* envq = reinterpret_cast<EnvQ*>(fasts + A.N);
-  EnvV* envv = reinterpret_cast<EnvV*>(R.envv);
-  EnvD* envd = reinterpret_cast<EnvD*>(R.envd);
-  EnvL* envl = reinterpret_cast<EnvL*>(envd + A.N);   // [N + 1] behind the EnvD records (dtsim_api.hip allocates them)
-  // domain randomisation on the quad records (k_raster_v3dr): same table / texture conditions as k_raster_v3
-  const bool v3dr = R.qtex && R.envd && R.domain_rand && !R.segment && (R.W & 3) == 0 && R.qlog2 == 8 && R.q3_rows > 0 &&
-                    R.q3_rows <= 24 && R.n_maps * 32 <= 128;
-  // quad-layout fast path: shared camera, square power-of-two tile textures (else the generic k_raster)
-  // (S = 256 tables carry the record-offset mask of the S256 kernels -- q8_rec256 --, which need a padded grid under 128 tiles: Q8_SNAP)
-  const bool quad = R.qtex && !R.domain_rand && !R.segment && (size_t)R.n_qtiles * 8 <= 32768 && (R.W & 3) == 0 &&
-                    !(R.qlog2 == 8 && R.qmax_tiles >= 256);
-  const bool obj = R.max_tris > 0;
+  void* base[DT_SLABS] = {R.envcam, R.pixtab}; RenderParams carved{};   // each slab's first array; R keeps its own pointers (render_pass set R.dbg)
+  const EnvRecs x = render_layout(A.N, R.W, R.H, 0, nullptr, base, carved);
+  const bool quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q, v3 = pipe == DTSIM_PIPE_V3, v3dr = pipe == DTSIM_PIPE_V3DR, obj = R.max_tris > 0;
   // render order (k_env_sort): the quad pipeline indexes by position (EnvQ, object masks, queue entries); env ids come
   // from EnvQ.env
   int32_t* pos = ((quad || v3dr) && R.envpos && A.N > ENVS_PER_BLOCK) ? R.envpos : nullptr;   // one chunk: the order does not matter
@@ -2982,24 +3017,21 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     tables |= 4;
   } else if (pos) { hipLaunchKernelGGL(k_env_sort<false>, dim3(1), dim3(1024), 0, s, A, R.maps, pos, nullptr, nullptr); tables |= 4; }
 #define LAUNCH_CAM(M_) hipLaunchKernelGGL(k_cam_setup<M_>, dim3((A.N + 63) / 64), dim3(64), 0, s, A, R.domain_rand, R.segment,                  \
-                     (float)R.W / (float)R.H, cams, fasts, R.maps, (quad || v3dr) ? envq : nullptr, R.qlog2, pos, quad ? envv : nullptr,  \
-                     v3dr ? envd : nullptr, R.W, R.H, R.light, (quad && R.light) ? envl : nullptr)
+                     (float)R.W / (float)R.H, x.cams, x.fasts, R.maps, (quad || v3dr) ? x.envq : nullptr, R.qlog2, pos, quad ? x.envv : nullptr,  \
+                     v3dr ? x.envd : nullptr, R.W, R.H, R.light, (quad && R.light) ? x.envl : nullptr)
   if (sub) LAUNCH_CAM(true); else LAUNCH_CAM(false);
 #undef LAUNCH_CAM
   if (!sub) (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * sizeof(int32_t), s);   // work-item counts + cursors of k_resolve / k_resolve_obj
   if (R.max_tris > 0) {
     if (!(tables & 2)) hipLaunchKernelGGL(k_blk_setup, dim3((unsigned)dt_raster_tiles(R.W, R.H)), dim3(RB), 0, s, R, reinterpret_cast<const float4*>(R.lut), reinterpret_cast<float4*>(R.blockbox));
     tables |= 2;
-    if (sub) hipLaunchKernelGGL(k_obj_setup<true>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, cams, pos);
-    else hipLaunchKernelGGL(k_obj_setup<false>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, cams, pos);
+    if (sub) hipLaunchKernelGGL(k_obj_setup<true>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, x.cams, pos);
+    else hipLaunchKernelGGL(k_obj_setup<false>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, x.cams, pos);
   }
 
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-  const bool v3 = quad && R.qlog2 == 8 && R.q3_rows > 0 && R.q3_rows <= V3_MAX_ROWS && R.n_maps * V3_MAP_COLS <= V3_TAB_PITCH / 2;
   if (quad && !(tables & 1)) {
-    PixTab* pixtab = reinterpret_cast<PixTab*>(R.pixtab);
-    SampTab* samptab = reinterpret_cast<SampTab*>(pixtab + (size_t)R.W * R.H);
-    hipLaunchKernelGGL(k_pix_setup, dim3((R.W * R.H + 255) / 256), dim3(256), 0, s, R, reinterpret_cast<const float4*>(R.lut), pixtab, samptab);
+    hipLaunchKernelGGL(k_pix_setup, dim3((R.W * R.H + 255) / 256), dim3(256), 0, s, R, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab);
     tables |= 1;
   }
   // Render parts (DTSIM_RENDER_PARTS = P > 1): the chunks of the batch in P ranges; the raster of range p + 1 on the
@@ -3008,12 +3040,8 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
   // kernels are the same; only the quad-record paths in the sorted render order are split (k_raster_v3, k_raster_v3dr).
   int parts = 1;
   if (ov && ov->parts > 1 && (v3 || v3dr) && pos && (obj || !quad) && !sub) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
-  // which raster ran (DTSIM_FIELD_RENDER_PIPE): bits 8.. of the result
-  tables |= (quad ? (v3 ? DTSIM_PIPE_V3 : DTSIM_PIPE_Q) : v3dr ? DTSIM_PIPE_V3DR : (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV
-             : DTSIM_PIPE_GENERIC) << 8;
-  if (R.light) tables |= DTSIM_PIPE_ENV_LIGHT << 8;
-  if (sub) { launch_raster_resolve<true>(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, true); return tables; }
-  if (parts <= 1) { launch_raster_resolve<false>(s, s, nullptr, R, cams, fasts, envq, envv, envd, envl, R.frames, quad, v3, v3dr, obj, pos != nullptr); return tables; }
+  if (sub) { launch_raster_resolve<true>(s, s, nullptr, R, x, pipe, true); return tables; }
+  if (parts <= 1) { launch_raster_resolve<false>(s, s, nullptr, R, x, pipe, pos != nullptr); return tables; }
   const size_t n_tiles = dt_raster_tiles(R.W, R.H), n_blk = n_tiles * 4;
   (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * parts * sizeof(int32_t), s);
   for (int p = 0; p < parts; ++p) {
@@ -3025,13 +3053,13 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     if (R.objmask) Rp.objmask = R.objmask + e0 * n_blk;
     Rp.queue = R.queue + wg0 * (RB / 64) * QREGION;
     Rp.qcount = R.qcount + wg0 * (RB / 64);
-    if (R.qend) Rp.qend = R.qend + wg0 * (RB / 64) * ENVS_PER_BLOCK;
+    Rp.qend = R.qend + wg0 * (RB / 64) * ENVS_PER_BLOCK;
     Rp.items = R.items + wg0 * ITEMS_PER_WG;
     Rp.items2 = R.items2 + wg0 * ENVS_PER_BLOCK;
     // per-POSITION arrays move to the range (EnvQ / EnvV / EnvD in render order, masks, queues, items above); per-ENV arrays (EnvCam, frames,
     // screen triangles, object boxes) stay whole: the kernels reach them through the env id of the position's record
-    EnvQ* envq_p = envq + e0; EnvV* envv_p = envv ? envv + e0 : nullptr; EnvD* envd_p = envd ? envd + e0 : nullptr;
-    launch_raster_resolve<false>(s, ov->s2, ov->ev[p], Rp, cams, fasts, envq_p, envv_p, envd_p, envl + e0, R.frames, quad, v3, v3dr, obj, true);
+    EnvRecs xp = x; xp.envq += e0; xp.envv += e0; xp.envd += e0; xp.envl += e0;
+    launch_raster_resolve<false>(s, ov->s2, ov->ev[p], Rp, xp, pipe, true);
   }
   (void)hipEventRecord(ov->ev[DT_MAX_RENDER_PARTS], ov->s2);
   (void)hipStreamWaitEvent(s, ov->ev[DT_MAX_RENDER_PARTS], 0);

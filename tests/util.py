@@ -52,7 +52,7 @@ from oracle.fixtures import junction_map  # noqa: E402,F401  (every tile kind x 
 
 def oracle_mode(sim, segment=False):
     """`lighting` argument of oracle.raster.render_obs that restates what the product's pipeline for THIS simulator does (the dispatch of
-    csrc/render.hip dt_launch_render): the quad-record kernels filter tile textures with byte weights -- the lit factor folded into them on
+    csrc/render.hip dt_raster_pipe): the quad-record kernels filter tile textures with byte weights -- the lit factor folded into them on
     the shared-camera path ("pixel": k_raster_v3 / k_raster_q), applied per channel afterwards on the per-env path ("pixel-dr":
     k_raster_v3dr, domain randomisation or per_env_camera) -- and the generic raster (segment view, widths that are not a multiple of 4,
     per-env cameras over tile textures that are not 256 x 256) with llvmpipe's own arithmetic ("pixel-gl")."""
