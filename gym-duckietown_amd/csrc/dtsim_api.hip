@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,43 @@ struct ProfSlot {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> free_;
 };
 
+// One device allocation of the handle: freed when its owner is replaced or the handle deleted.  The caller synchronises
+// h->stream first whenever the stream may still read the old buffer.
+struct HipFree {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
+template <typename T>
+using DevPtr = std::unique_ptr<T, HipFree>;
+
+// n elements of T into `out`, which keeps what it had on failure
+template <typename T>
+hipError_t dev_alloc(DevPtr<T>& out, size_t n) {
+  T* p = nullptr;
+  hipError_t e = hipMalloc(&p, sizeof(T) * n);
+  if (e == hipSuccess) out.reset(p);
+  return e;
+}
+
+// src[0, n) in a new buffer of max(n, min_n) elements (null for none), moved into `out` only on success
+template <typename T>
+hipError_t dev_upload(DevPtr<T>& out, const T* src, size_t n, size_t min_n = 0) {
+  DevPtr<T> p;
+  hipError_t e = dev_alloc(p, std::max(n, min_n));
+  if (e == hipSuccess && n) e = hipMemcpy(p.get(), src, sizeof(T) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) out = std::move(p);
+  return e;
+}
+
+// a staging buffer of n elements in place of `buf`, whose old buffer is released once stream `s` no longer reads it
+template <typename T>
+hipError_t dev_grow(DevPtr<T>& buf, size_t n, hipStream_t s) {
+  DevPtr<T> p;
+  hipError_t e = dev_alloc(p, n);
+  if (e == hipSuccess && buf) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) buf = std::move(p);
+  return e;
+}
+
 }  // namespace
 
 struct dtsim {
@@ -49,87 +87,86 @@ struct dtsim {
   bool own_stream = false;
   int N = 0;
   // SoA slab
-  void* slab = nullptr;
+  DevPtr<char> slab;
   size_t slab_bytes = 0;
   SimArrays A{};
   // maps
   bool have_maps = false, have_reset = false;
   MapSet M{};
-  uint64_t* d_blobs = nullptr;
-  DynInit* d_dyn = nullptr;
-  std::vector<int> map_n_dyn, map_n_obj;
+  DevPtr<uint64_t> d_blobs;
+  DevPtr<DynInit> d_dyn;
   // reset / pool staging
-  dtsim_init_state* d_states = nullptr;
-  uint8_t* d_mask = nullptr;
-  dtsim_init_state* d_pool = nullptr;
+  DevPtr<dtsim_init_state> d_states;
+  DevPtr<uint8_t> d_mask;
+  DevPtr<dtsim_init_state> d_pool;
   int n_pool = 0;
   // actions staging
-  void* d_actions = nullptr;
+  DevPtr<char> d_actions;
   size_t actions_cap = 0;
   // query staging
-  int32_t* d_qenv = nullptr;
-  double* d_qpose = nullptr;
-  dtsim_probe* d_qout = nullptr;
-  dtsim_agent_info* d_agent = nullptr;
+  DevPtr<int32_t> d_qenv;
+  DevPtr<double> d_qpose;
+  DevPtr<dtsim_probe> d_qout;
+  DevPtr<dtsim_agent_info> d_agent;
   bool rendered = false;          // a render pass has written the per-env cameras (dtsim_draw_lines needs them)
   bool masked = false;            // the last pass was dtsim_render_masked: the post-passes need a full one
   RenderParams last_R{};          // the parameters of that pass (dtsim_draw_leds: projected triangles, tables); last_segment: it was the segment view
   bool last_segment = false;
   bool leds_ok = false;           // last_R still names live buffers (cleared by dtsim_set_assets / dtsim_set_maps / dtsim_set_distortion_lut, which re-allocate)
-  float* d_leds = nullptr;        // dtsim_draw_leds: device copy of the caller's spheres
+  DevPtr<float> d_leds;          // dtsim_draw_leds: device copy of the caller's spheres
   int leds_cap = 0;
-  float* d_lines = nullptr;       // dtsim_draw_lines: device copy of the caller's segments
+  DevPtr<float> d_lines;          // dtsim_draw_lines: device copy of the caller's segments
   int lines_cap = 0;
   int render_tables = 0;          // dt_launch_render: which env-invariant tables are valid (camera LUT + maps unchanged)
   int render_pipe = 0;            // DTSIM_PIPE_* of the last render pass (DTSIM_FIELD_RENDER_PIPE)
   RenderOverlap overlap{};        // render parts (DTSIM_RENDER_PARTS > 1): second stream + ordering events
   int q_cap = 0;
   // render
-  uint8_t* frames_own = nullptr;
-  uint8_t* frames = nullptr;
+  DevPtr<uint8_t> frames_own;
+  uint8_t* frames = nullptr;      // frames_own, or the caller's memory (dtsim_bind_frames)
   size_t frames_bytes = 0;
-  float* d_lut = nullptr;
+  DevPtr<float> d_lut;
   bool have_lut = false;
   // camera_rand (dtsim_set_distortion_luts): per-env remap tables; while n_cal > 0 the raster writes the rectilinear frames into
   // d_scratch (d_lut is the identity) and k_remap_cal gathers them into `frames`
   int n_cal = 0;
   bool camera_rand = false;       // DTSIM_LUTS_CAMERA_RAND: the device reset sampler scales the camera
-  int32_t* d_cal_src = nullptr;   // [n_cal][H*W]
-  int32_t* d_env_cal = nullptr;   // [N]
-  uint8_t* d_scratch = nullptr;   // [N][H][W][3]
-  uint32_t* d_texels = nullptr;
-  uint32_t* d_texels_seg = nullptr;   // segmented versions, same layout as d_texels (dtsim_set_segment_assets)
-  uint8_t* d_mesh_seg = nullptr;      // [n_meshes][4] flat segmentation colour per mesh
-  TexDev* d_tex = nullptr;
+  DevPtr<int32_t> d_cal_src;      // [n_cal][H*W]
+  DevPtr<int32_t> d_env_cal;      // [N]
+  DevPtr<uint8_t> d_scratch;      // [N][H][W][3]
+  DevPtr<uint32_t> d_texels;
+  DevPtr<uint32_t> d_texels_seg;      // segmented versions, same layout as d_texels (dtsim_set_segment_assets)
+  DevPtr<uint8_t> d_mesh_seg;         // [n_meshes][4] flat segmentation colour per mesh
+  DevPtr<TexDev> d_tex;
   int n_tex = 0;
   std::vector<TexDev> h_tex;
-  MeshDev* d_meshes = nullptr;
-  TriDev* d_tris = nullptr;
+  DevPtr<MeshDev> d_meshes;
+  DevPtr<TriDev> d_tris;
   int n_meshes = 0;
   std::vector<MeshDev> h_meshes;
-  RenderMapDev* d_rmaps = nullptr;
-  uint32_t* d_rtiles = nullptr;
-  TileLds* d_tilerecs = nullptr;
-  void* d_render[DT_SLABS] = {};  // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND at dtsim_create, the object slabs at dtsim_set_maps
+  DevPtr<RenderMapDev> d_rmaps;
+  DevPtr<uint32_t> d_rtiles;
+  DevPtr<TileLds> d_tilerecs;
+  DevPtr<char> d_render[DT_SLABS];    // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND at dtsim_create, the object slabs at dtsim_set_maps
   std::vector<uint32_t> h_pool;       // host copy of the RGBA8 pool (quad blocks are built from it at dtsim_set_maps)
-  uint8_t* d_qtex = nullptr;          // quad-layout blocks for k_raster_q
-  uint32_t* d_qtiles = nullptr;
+  DevPtr<uint8_t> d_qtex;             // quad-layout blocks for k_raster_q
+  DevPtr<uint32_t> d_qtiles;
   int n_qtiles = 0, qlog2 = 0;
   bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop); DTSIM_STEP_LANES = 1 / 2 / 4 / 8
   float q_per_m = 0.f;
-  dtsim_reset_sampler* d_sampler = nullptr;   // device copy when a reset sampler is installed
+  DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
   int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
-  int32_t* d_obsc_tab = nullptr;  // dtsim_observe_cubic tables (device copy of obsc_tab)
+  DevPtr<int32_t> d_obsc_tab;     // dtsim_observe_cubic tables (device copy of obsc_tab)
   std::vector<int32_t> obsc_tab;
-  int32_t* d_obs_tab = nullptr;   // dtsim_observe resampling tables (device copy of obs_tab)
+  DevPtr<int32_t> d_obs_tab;      // dtsim_observe resampling tables (device copy of obs_tab)
   std::vector<int32_t> obs_tab;   // the cache key: output size, tap counts and the caller's tables
   int obs_h = 0, obs_w = 0, obs_kx = 0, obs_ky = 0, obs_rpb = 0, obs_rows_in = 0;
   size_t obs_off_by = 0;
   ObserveParams obs_fast{};       // the power-of-two fast-path fields of the cached tables (hfast .. vw)
   int max_tris = 0;
   int n_tilerecs = 0, tex_w = 1, tex_h = 1;
-  ObjInstDev* d_robjs = nullptr;
+  DevPtr<ObjInstDev> d_robjs;
   ProfSlot prof[DTSIM_KERNEL__COUNT];
 };
 
@@ -184,7 +221,7 @@ StepParams step_params(const dtsim* h, int n_steps) {
   P.actions_f64 = (h->cfg.flags & DTSIM_F_ACTIONS_F64) ? 1 : 0;
   P.auto_reset = ((h->cfg.flags & DTSIM_F_AUTO_RESET) && (h->n_pool > 0 || h->d_sampler)) ? 1 : 0;
   P.n_pool = h->n_pool;
-  P.sampler = h->d_sampler;
+  P.sampler = h->d_sampler.get();
   P.delta_time = h->cfg.delta_time;
   P.robot_speed = h->cfg.robot_speed;
   P.gain = h->cfg.gain; P.trim = h->cfg.trim; P.radius = h->cfg.radius; P.k = h->cfg.k; P.limit = h->cfg.limit;
@@ -193,6 +230,13 @@ StepParams step_params(const dtsim* h, int n_steps) {
   P.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
   P.camera_rand = h->camera_rand ? 1 : 0;
   return P;
+}
+
+// points R's scratch fields into the handle's render slabs (dt_render_layout)
+void render_scratch(const dtsim* h, int max_tris, RenderParams* R) {
+  void* base[DT_SLABS];
+  for (int i = 0; i < DT_SLABS; ++i) base[i] = h->d_render[i].get();
+  dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, nullptr, base, R);
 }
 
 struct ProfScope {
@@ -261,24 +305,24 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
   }
   SimArrays tmp{};
   h->slab_bytes = layout_arrays(tmp, h->N, reinterpret_cast<char*>(4096));
-  hipError_t e = hipMalloc(&h->slab, h->slab_bytes);
+  hipError_t e = dev_alloc(h->slab, h->slab_bytes);
   if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(state %zu B): %s", h->slab_bytes, hipGetErrorString(e)); }
-  (void)hipMemsetAsync(h->slab, 0, h->slab_bytes, h->stream);
-  layout_arrays(h->A, h->N, (char*)h->slab);
+  (void)hipMemsetAsync(h->slab.get(), 0, h->slab_bytes, h->stream);
+  layout_arrays(h->A, h->N, h->slab.get());
   // map_id = -1 everywhere so the first reset creates the world objects
   (void)hipMemsetAsync(h->A.map_id, 0xFF, sizeof(int32_t) * (size_t)h->N, h->stream);
-  e = hipMalloc(&h->d_states, sizeof(dtsim_init_state) * (size_t)h->N);
-  if (e == hipSuccess) e = hipMalloc(&h->d_mask, (size_t)h->N);
+  e = dev_alloc(h->d_states, (size_t)h->N);
+  if (e == hipSuccess) e = dev_alloc(h->d_mask, (size_t)h->N);
   if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(reset staging): %s", hipGetErrorString(e)); }
   if (cfg->flags & DTSIM_F_RENDER) {
     h->frames_bytes = (size_t)h->N * cfg->cam_height * cfg->cam_width * 3;
-    e = hipMalloc(&h->frames_own, h->frames_bytes);
+    e = dev_alloc(h->frames_own, h->frames_bytes);
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(frames %zu B): %s", h->frames_bytes, hipGetErrorString(e)); }
-    h->frames = h->frames_own;
-    e = hipMalloc(&h->d_lut, sizeof(float) * 4 * (size_t)cfg->cam_height * cfg->cam_width);
+    h->frames = h->frames_own.get();
+    e = dev_alloc(h->d_lut, 4 * (size_t)cfg->cam_height * cfg->cam_width);
     size_t bytes[DT_SLABS]; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, bytes);
-    for (int i = DT_SLAB_ENV; i <= DT_SLAB_QEND && e == hipSuccess; ++i) e = hipMalloc(&h->d_render[i], bytes[i]);
-    RenderParams R{}; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, nullptr, h->d_render, &R);
+    for (int i = DT_SLAB_ENV; i <= DT_SLAB_QEND && e == hipSuccess; ++i) e = dev_alloc(h->d_render[i], bytes[i]);
+    RenderParams R{}; render_scratch(h, 0, &R);
     if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));   // (the DT_RO_STATS counters start at 0)
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(render scratch): %s", hipGetErrorString(e)); }
     {  // render parts: off (1) unless asked for
@@ -309,15 +353,10 @@ void dtsim_destroy(dtsim_t* h) {
     for (auto& p : s.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto& p : s.free_) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   }
-  void* ptrs[] = {h->slab, h->d_blobs, h->d_dyn, h->d_states, h->d_mask, h->d_pool, h->d_actions, h->d_qenv,
-                  h->d_qpose, h->d_qout, h->d_agent, h->frames_own, h->d_lut, h->d_texels, h->d_tex, h->d_meshes, h->d_tris,
-                  h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_tilerecs, h->d_obs_tab, h->d_obsc_tab, h->d_sampler, h->d_texels_seg, h->d_mesh_seg, h->d_qtex, h->d_qtiles, h->d_lines, h->d_leds, h->d_cal_src, h->d_env_cal, h->d_scratch};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (void* p : h->d_render) if (p) (void)hipFree(p);
   if (h->overlap.s2) { (void)hipStreamSynchronize(h->overlap.s2); (void)hipStreamDestroy(h->overlap.s2); }
   for (hipEvent_t ev : h->overlap.ev) if (ev) (void)hipEventDestroy(ev);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // frees every device buffer the handle owns
 }
 
 // textures -> one RGBA8 pool: padded (h+1) x (w+1) storage so that GL_REPEAT bilinear fetches never wrap
@@ -350,26 +389,10 @@ int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, 
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   std::vector<uint32_t> pool;
-  h->h_tex.clear();
-  if (int rc = build_texel_pool(textures, n_textures, pool, &h->h_tex)) return rc;
-  h->h_pool = pool;
-  // the quad-layout blocks were built from the OLD texel pool (dtsim_set_maps): drop them, so that the generic raster
-  // (which reads d_texels) is used until the next dtsim_set_maps rebuilds them -- never a frame mixing both pools
-  if (h->d_qtex) { (void)hipFree(h->d_qtex); h->d_qtex = nullptr; }
-  if (h->d_qtiles) { (void)hipFree(h->d_qtiles); h->d_qtiles = nullptr; }
-  h->n_qtiles = 0; h->qlog2 = 0;
-  if (h->d_texels_seg) { (void)hipFree(h->d_texels_seg); h->d_texels_seg = nullptr; }   // mirrors the old list
-  if (h->d_texels) { (void)hipFree(h->d_texels); h->d_texels = nullptr; }
-  if (h->d_tex) { (void)hipFree(h->d_tex); h->d_tex = nullptr; }
-  h->n_tex = n_textures;
-  if (n_textures > 0) {
-    HIPCHK(hipMalloc(&h->d_texels, pool.size() * 4));
-    HIPCHK(hipMemcpy(h->d_texels, pool.data(), pool.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_tex, sizeof(TexDev) * n_textures));
-    HIPCHK(hipMemcpy(h->d_tex, h->h_tex.data(), sizeof(TexDev) * n_textures, hipMemcpyHostToDevice));
-  }
+  std::vector<TexDev> tex;
+  if (int rc = build_texel_pool(textures, n_textures, pool, &tex)) return rc;
+  std::vector<MeshDev> mesh_descs;
   std::vector<TriDev> tris;
-  h->h_meshes.clear();
   for (int m = 0; m < n_meshes; ++m) {
     const dtsim_mesh& ms = meshes[m];
     if (ms.n_tris < 0 || (ms.n_tris > 0 && (!ms.verts || !ms.normals || !ms.colors)))
@@ -390,19 +413,25 @@ int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, 
       if (td.tex < 0) td.tex = -1;
       tris.push_back(td);
     }
-    h->h_meshes.push_back(d);
+    mesh_descs.push_back(d);
   }
-  if (h->d_meshes) { (void)hipFree(h->d_meshes); h->d_meshes = nullptr; }
-  if (h->d_tris) { (void)hipFree(h->d_tris); h->d_tris = nullptr; }
+  DevPtr<uint32_t> d_texels;
+  DevPtr<TexDev> d_tex;
+  DevPtr<MeshDev> d_meshes;
+  DevPtr<TriDev> d_tris;
+  HIPCHK(dev_upload(d_texels, pool.data(), pool.size()));
+  HIPCHK(dev_upload(d_tex, tex.data(), tex.size()));
+  HIPCHK(dev_upload(d_meshes, mesh_descs.data(), mesh_descs.size()));
+  HIPCHK(dev_upload(d_tris, tris.data(), tris.size()));
+  h->d_texels = std::move(d_texels); h->d_tex = std::move(d_tex); h->h_tex = std::move(tex); h->h_pool = std::move(pool);
+  h->n_tex = n_textures;
+  h->d_meshes = std::move(d_meshes); h->d_tris = std::move(d_tris); h->h_meshes = std::move(mesh_descs);
   h->n_meshes = n_meshes;
-  if (n_meshes > 0) {
-    HIPCHK(hipMalloc(&h->d_meshes, sizeof(MeshDev) * n_meshes));
-    HIPCHK(hipMemcpy(h->d_meshes, h->h_meshes.data(), sizeof(MeshDev) * n_meshes, hipMemcpyHostToDevice));
-    if (!tris.empty()) {
-      HIPCHK(hipMalloc(&h->d_tris, sizeof(TriDev) * tris.size()));
-      HIPCHK(hipMemcpy(h->d_tris, tris.data(), sizeof(TriDev) * tris.size(), hipMemcpyHostToDevice));
-    }
-  }
+  // the quad-layout blocks were built from the OLD texel pool (dtsim_set_maps): drop them, so that the generic raster
+  // (which reads d_texels) is used until the next dtsim_set_maps rebuilds them -- never a frame mixing both pools
+  h->d_qtex.reset(); h->d_qtiles.reset();
+  h->n_qtiles = 0; h->qlog2 = 0;
+  h->d_texels_seg.reset();        // mirrors the old list
   return DTSIM_OK;
 }
 
@@ -420,14 +449,12 @@ int dtsim_set_segment_assets(dtsim_t* h, const dtsim_texture* textures, int n_te
   HIPCHK(hipStreamSynchronize(h->stream));
   std::vector<uint32_t> pool;
   if (int rc = build_texel_pool(textures, n_textures, pool, nullptr)) return rc;
-  if (h->d_texels_seg) { (void)hipFree(h->d_texels_seg); h->d_texels_seg = nullptr; }
-  if (h->d_mesh_seg) { (void)hipFree(h->d_mesh_seg); h->d_mesh_seg = nullptr; }
-  HIPCHK(hipMalloc(&h->d_texels_seg, std::max<size_t>(pool.size(), 1) * 4));
-  if (!pool.empty()) HIPCHK(hipMemcpy(h->d_texels_seg, pool.data(), pool.size() * 4, hipMemcpyHostToDevice));
   std::vector<uint8_t> rgbx((size_t)std::max(n_meshes, 1) * 4, 0);
   for (int m = 0; m < n_meshes; ++m) { rgbx[m * 4] = mesh_rgb[m * 3]; rgbx[m * 4 + 1] = mesh_rgb[m * 3 + 1]; rgbx[m * 4 + 2] = mesh_rgb[m * 3 + 2]; }
-  HIPCHK(hipMalloc(&h->d_mesh_seg, rgbx.size()));
-  HIPCHK(hipMemcpy(h->d_mesh_seg, rgbx.data(), rgbx.size(), hipMemcpyHostToDevice));
+  DevPtr<uint32_t> d_texels_seg;
+  HIPCHK(dev_upload(d_texels_seg, pool.data(), pool.size(), 1));
+  HIPCHK(dev_upload(h->d_mesh_seg, rgbx.data(), rgbx.size()));
+  h->d_texels_seg = std::move(d_texels_seg);
   return DTSIM_OK;
 }
 
@@ -481,8 +508,6 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   std::vector<ObjInstDev> robjs;
   MapSet M{};
   M.n_maps = n_maps;
-  h->map_n_dyn.assign(n_maps, 0);
-  h->map_n_obj.assign(n_maps, 0);
   for (int mi = 0; mi < n_maps; ++mi) {
     const dtsim_map& mp = maps[mi];
     const int nt = mp.grid_w * mp.grid_h;
@@ -501,7 +526,6 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
     if (n_static > DTSIM_MAX_STATIC) return fail(DTSIM_E_LIMIT, "map %d: %d static collidables > %d", mi, n_static, DTSIM_MAX_STATIC);
     if (n_dyn > DTSIM_MAX_DYNAMIC) return fail(DTSIM_E_LIMIT, "map %d: %d dynamic objects > %d", mi, n_dyn, DTSIM_MAX_DYNAMIC);
     MapHdr hd{};
-    h->map_w[mi] = mp.grid_w; h->map_h[mi] = mp.grid_h;
     hd.grid_w = mp.grid_w; hd.grid_h = mp.grid_h; hd.n_curves = mp.n_curves; hd.n_static = n_static;
     hd.n_lights = 0;
     for (int o = 0; o < mp.n_objects; ++o) hd.n_lights += mp.objects[o].light_freq > 0 ? 1 : 0;
@@ -599,7 +623,6 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
         return fail(DTSIM_E_INVALID, "map %d object %d: light texture not loaded", mi, o);
       robjs.push_back(oi);
     }
-    h->map_n_dyn[mi] = n_dyn; h->map_n_obj[mi] = mp.n_objects;
   }
   // ---- quad-layout fast path tables: possible when every tile texture is one square power-of-two size
   std::vector<uint32_t> qblocks, qtiles;
@@ -651,49 +674,53 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
     return fail(DTSIM_E_LIMIT, "map tables %zu B exceed the 60 KB LDS staging budget", (size_t)M.total_words * 8);
   if (trecs.size() > DTSIM_LDS_TILES)
     return fail(DTSIM_E_LIMIT, "%zu tiles over all maps exceed the %d LDS raster records", trecs.size(), DTSIM_LDS_TILES);
-  void* olds[] = {h->d_blobs, h->d_dyn, h->d_rmaps, h->d_rtiles, h->d_robjs, h->d_tilerecs, h->d_qtex, h->d_qtiles};
-  for (void* p : olds) if (p) (void)hipFree(p);
-  h->d_blobs = nullptr; h->d_dyn = nullptr; h->d_rmaps = nullptr; h->d_rtiles = nullptr; h->d_robjs = nullptr;
-  h->d_tilerecs = nullptr; h->d_qtex = nullptr; h->d_qtiles = nullptr;
-  h->n_qtiles = 0; h->qlog2 = 0; h->q_per_m = 0.f;
-  if (qlog2 > 0 && !qtiles.empty()) {
-    HIPCHK(hipMalloc(&h->d_qtex, qblocks.size() * 4));
-    HIPCHK(hipMemcpy(h->d_qtex, qblocks.data(), qblocks.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_qtiles, qtiles.size() * 4));
-    HIPCHK(hipMemcpy(h->d_qtiles, qtiles.data(), qtiles.size() * 4, hipMemcpyHostToDevice));
-    h->n_qtiles = (int)qtiles.size() / 2; h->qlog2 = qlog2; h->q_per_m = q_per_m;
-  }
-  HIPCHK(hipMalloc(&h->d_tilerecs, std::max<size_t>(trecs.size(), 1) * sizeof(TileLds)));
-  if (!trecs.empty()) HIPCHK(hipMemcpy(h->d_tilerecs, trecs.data(), trecs.size() * sizeof(TileLds), hipMemcpyHostToDevice));
-  for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i) { (void)hipFree(h->d_render[i]); h->d_render[i] = nullptr; }
-  h->max_tris = 0;
-  for (auto& rm : rmaps) h->max_tris = std::max(h->max_tris, rm.n_tris);
-  size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, h->max_tris, bytes);
+  int max_tris = 0;
+  for (auto& rm : rmaps) max_tris = std::max(max_tris, rm.n_tris);
+  DevPtr<uint64_t> d_blobs;
+  DevPtr<DynInit> d_dyn;
+  DevPtr<RenderMapDev> d_rmaps;
+  DevPtr<uint32_t> d_rtiles, d_qtiles;
+  DevPtr<ObjInstDev> d_robjs;
+  DevPtr<TileLds> d_tilerecs;
+  DevPtr<uint8_t> d_qtex;
+  DevPtr<char> obj_slabs[DT_SLABS];
+  HIPCHK(dev_upload(d_blobs, blobs.data(), blobs.size()));
+  HIPCHK(dev_upload(d_dyn, dyn.data(), dyn.size()));
+  HIPCHK(dev_upload(d_rmaps, rmaps.data(), rmaps.size()));
+  HIPCHK(dev_upload(d_rtiles, rtiles.data(), rtiles.size(), 1));
+  HIPCHK(dev_upload(d_robjs, robjs.data(), robjs.size(), 1));
+  HIPCHK(dev_upload(d_tilerecs, trecs.data(), trecs.size(), 1));
+  if (qlog2 <= 0 || qtiles.empty()) { qblocks.clear(); qtiles.clear(); qlog2 = 0; q_per_m = 0.f; }   // no quad records: the generic raster
+  HIPCHK(dev_upload(d_qtex, reinterpret_cast<const uint8_t*>(qblocks.data()), qblocks.size() * 4));
+  HIPCHK(dev_upload(d_qtiles, qtiles.data(), qtiles.size()));
+  size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, bytes);
   for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i)     // the object slabs: only with mesh objects
-    if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(hipMalloc(&h->d_render[i], bytes[i]));
-  h->n_tilerecs = (int)trecs.size();
-  h->tex_w = tex_w ? tex_w : 1; h->tex_h = tex_h ? tex_h : 1;
-  HIPCHK(hipMalloc(&h->d_blobs, blobs.size() * 8));
-  HIPCHK(hipMemcpy(h->d_blobs, blobs.data(), blobs.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->d_dyn, dyn.size() * sizeof(DynInit)));
-  HIPCHK(hipMemcpy(h->d_dyn, dyn.data(), dyn.size() * sizeof(DynInit), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->d_rmaps, rmaps.size() * sizeof(RenderMapDev)));
-  HIPCHK(hipMemcpy(h->d_rmaps, rmaps.data(), rmaps.size() * sizeof(RenderMapDev), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->d_rtiles, std::max<size_t>(rtiles.size(), 1) * 4));
-  if (!rtiles.empty()) HIPCHK(hipMemcpy(h->d_rtiles, rtiles.data(), rtiles.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->d_robjs, std::max<size_t>(robjs.size(), 1) * sizeof(ObjInstDev)));
-  if (!robjs.empty()) HIPCHK(hipMemcpy(h->d_robjs, robjs.data(), robjs.size() * sizeof(ObjInstDev), hipMemcpyHostToDevice));
-  M.blobs = h->d_blobs;
-  M.dyn = h->d_dyn;
-  h->M = M;
-  h->have_maps = true;
+    if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(dev_alloc(obj_slabs[i], bytes[i]));
   // worlds must be re-created against the new maps
   HIPCHK(hipMemsetAsync(h->A.map_id, 0xFF, sizeof(int32_t) * (size_t)h->N, h->stream));
+  h->d_blobs = std::move(d_blobs); h->d_dyn = std::move(d_dyn);
+  M.blobs = h->d_blobs.get();
+  M.dyn = h->d_dyn.get();
+  h->M = M;
+  for (int mi = 0; mi < n_maps; ++mi) { h->map_w[mi] = maps[mi].grid_w; h->map_h[mi] = maps[mi].grid_h; }
+  h->d_rmaps = std::move(d_rmaps); h->d_rtiles = std::move(d_rtiles); h->d_robjs = std::move(d_robjs);
+  h->d_tilerecs = std::move(d_tilerecs);
+  h->n_tilerecs = (int)trecs.size();
+  h->tex_w = tex_w ? tex_w : 1; h->tex_h = tex_h ? tex_h : 1;
+  h->d_qtex = std::move(d_qtex); h->d_qtiles = std::move(d_qtiles);
+  h->n_qtiles = (int)qtiles.size() / 2; h->qlog2 = qlog2; h->q_per_m = q_per_m;
+  for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i) h->d_render[i] = std::move(obj_slabs[i]);
+  h->max_tris = max_tris;
+  h->have_maps = true;
   h->have_reset = false;
   return DTSIM_OK;
 }
 
-static int drop_luts(dtsim_t* h);
+// one distortion table for every env again (the sampler switch stays: it is dtsim_set_distortion_luts' to set)
+static void drop_luts(dtsim_t* h) {
+  h->d_cal_src.reset(); h->d_env_cal.reset(); h->d_scratch.reset();
+  h->n_cal = 0;
+}
 
 int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
@@ -702,7 +729,6 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
   if (!h->d_lut) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if ((rmapx == nullptr) != (rmapy == nullptr)) return fail(DTSIM_E_INVALID, "rmapx/rmapy must both be given");
   if (rmapx && !(h->cfg.flags & DTSIM_F_DISTORTION)) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_DISTORTION");
-  if (h->n_cal) { int rc = drop_luts(h); if (rc) return rc; }   // one table for every env again
   HIPCHK(hipSetDevice(h->cfg.device));
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
   std::vector<float> lut((size_t)W * H * 4);
@@ -724,17 +750,9 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
       o[3] = 0.f;
     }
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(h->d_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(dev_upload(h->d_lut, lut.data(), lut.size()));
+  drop_luts(h);
   h->have_lut = true;
-  return DTSIM_OK;
-}
-
-static int drop_luts(dtsim_t* h) {
-  HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (void* p : {(void*)h->d_cal_src, (void*)h->d_env_cal, (void*)h->d_scratch}) if (p) (void)hipFree(p);
-  h->d_cal_src = nullptr; h->d_env_cal = nullptr; h->d_scratch = nullptr;
-  h->n_cal = 0;                                       // (the sampler switch stays: it is dtsim_set_distortion_luts' to set)
   return DTSIM_OK;
 }
 
@@ -746,7 +764,9 @@ int dtsim_set_distortion_luts(dtsim_t* h, int n_cal, const int32_t* src_index, c
     if (src_index || env_cal) return fail(DTSIM_E_INVALID, "n_cal = 0 takes no tables");
     if ((flags & DTSIM_LUTS_CAMERA_RAND) && (h->cfg.flags & DTSIM_F_LIGHT_CAPTURE))
       return fail(DTSIM_E_STATE, "DTSIM_LUTS_CAMERA_RAND with DTSIM_F_LIGHT_CAPTURE is not supported");
-    if (int rc = drop_luts(h)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    drop_luts(h);
     h->camera_rand = (flags & DTSIM_LUTS_CAMERA_RAND) != 0;
     return DTSIM_OK;
   }
@@ -760,22 +780,14 @@ int dtsim_set_distortion_luts(dtsim_t* h, int n_cal, const int32_t* src_index, c
   for (size_t i = 0; i < (size_t)n_cal * hw; ++i)     // every gather of k_remap_cal stays inside the env's scratch frame
     if (src_index[i] < -1 || src_index[i] >= (int64_t)hw) return fail(DTSIM_E_INVALID, "src_index[%zu] = %d outside [-1, %zu)", i, src_index[i], hw);
   HIPCHK(hipSetDevice(h->cfg.device));
-  // the new buffers first: on any failure the handle keeps the tables it had (single or per env), never a half-installed state
-  int32_t *d_src = nullptr, *d_cal = nullptr;
-  uint8_t* d_scr = nullptr;
-  hipError_t e = hipMalloc(&d_src, sizeof(int32_t) * hw * n_cal);
-  if (e == hipSuccess) e = hipMalloc(&d_cal, sizeof(int32_t) * (size_t)h->N);
-  if (e == hipSuccess) e = hipMalloc(&d_scr, h->frames_bytes);
-  if (e == hipSuccess) e = hipMemcpy(d_src, src_index, sizeof(int32_t) * hw * n_cal, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_cal, env_cal, sizeof(int32_t) * (size_t)h->N, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? DTSIM_OK : fail(DTSIM_E_HIP, "dtsim_set_distortion_luts: %s", hipGetErrorString(e));
+  DevPtr<int32_t> d_src, d_cal;
+  DevPtr<uint8_t> d_scr;
+  HIPCHK(dev_upload(d_src, src_index, hw * n_cal));
+  HIPCHK(dev_upload(d_cal, env_cal, (size_t)h->N));
+  HIPCHK(dev_alloc(d_scr, h->frames_bytes));
   // the raster renders rectilinear frames while the tables are installed (this also drops the previous per-env tables)
-  if (rc == DTSIM_OK) rc = dtsim_set_distortion_lut(h, nullptr, nullptr);
-  if (rc != DTSIM_OK) {
-    for (void* p : {(void*)d_src, (void*)d_cal, (void*)d_scr}) if (p) (void)hipFree(p);
-    return rc;
-  }
-  h->d_cal_src = d_src; h->d_env_cal = d_cal; h->d_scratch = d_scr;
+  if (int rc = dtsim_set_distortion_lut(h, nullptr, nullptr)) return rc;
+  h->d_cal_src = std::move(d_src); h->d_env_cal = std::move(d_cal); h->d_scratch = std::move(d_scr);
   h->n_cal = n_cal;
   h->camera_rand = (flags & DTSIM_LUTS_CAMERA_RAND) != 0;
   return DTSIM_OK;
@@ -817,7 +829,7 @@ int dtsim_set_reset_sampler(dtsim_t* h, const dtsim_reset_sampler* sampler) {
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (!sampler) {
-    if (h->d_sampler) { (void)hipFree(h->d_sampler); h->d_sampler = nullptr; }
+    h->d_sampler.reset();
     return DTSIM_OK;
   }
   if (!h->have_maps) return fail(DTSIM_E_STATE, "dtsim_set_reset_sampler before dtsim_set_maps");
@@ -828,8 +840,7 @@ int dtsim_set_reset_sampler(dtsim_t* h, const dtsim_reset_sampler* sampler) {
     if (i < 0) continue;
     if (i >= h->map_w[m] || j < 0 || j >= h->map_h[m]) return fail(DTSIM_E_INVALID, "sampler: start tile (%d,%d) outside map %d", i, j, m);
   }
-  if (!h->d_sampler) HIPCHK(hipMalloc(&h->d_sampler, sizeof(dtsim_reset_sampler)));
-  HIPCHK(hipMemcpy(h->d_sampler, sampler, sizeof(dtsim_reset_sampler), hipMemcpyHostToDevice));
+  HIPCHK(dev_upload(h->d_sampler, sampler, 1));
   return DTSIM_OK;
 }
 
@@ -854,10 +865,10 @@ int dtsim_reset(dtsim_t* h, const uint8_t* mask, const dtsim_init_state* states)
   if (!states) {                                     // device-side sampling
     if (!h->d_sampler) return fail(DTSIM_E_STATE, "dtsim_reset(states = NULL) needs dtsim_set_reset_sampler");
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (mask) HIPCHK(hipMemcpyAsync(h->d_mask, mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.get(), mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
     {
       ProfScope ps(h, DTSIM_KERNEL_RESET);
-      dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask : nullptr, nullptr);
+      dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, nullptr);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -867,11 +878,11 @@ int dtsim_reset(dtsim_t* h, const uint8_t* mask, const dtsim_init_state* states)
   int rc = check_states(h, states, h->N, mask);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
-  HIPCHK(hipMemcpyAsync(h->d_states, states, sizeof(dtsim_init_state) * (size_t)h->N, hipMemcpyHostToDevice, h->stream));
-  if (mask) HIPCHK(hipMemcpyAsync(h->d_mask, mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_states.get(), states, sizeof(dtsim_init_state) * (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+  if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.get(), mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
   {
     ProfScope ps(h, DTSIM_KERNEL_RESET);
-    dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask : nullptr, h->d_states);
+    dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, h->d_states.get());
   }
   HIPCHK(hipGetLastError());
   // the host buffers may be reused by the caller as soon as we return
@@ -888,9 +899,7 @@ int dtsim_set_spawn_pool(dtsim_t* h, const dtsim_init_state* pool, int n_pool) {
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->d_pool) { (void)hipFree(h->d_pool); h->d_pool = nullptr; }
-  HIPCHK(hipMalloc(&h->d_pool, sizeof(dtsim_init_state) * (size_t)n_pool));
-  HIPCHK(hipMemcpy(h->d_pool, pool, sizeof(dtsim_init_state) * (size_t)n_pool, hipMemcpyHostToDevice));
+  HIPCHK(dev_upload(h->d_pool, pool, (size_t)n_pool));
   h->n_pool = n_pool;
   return DTSIM_OK;
 }
@@ -910,22 +919,19 @@ int dtsim_step_ex(dtsim_t* h, const void* actions, int n_steps, int actions_on_d
   const void* dptr = actions;
   if (!actions_on_device) {
     if (bytes > h->actions_cap) {
-      HIPCHK(hipStreamSynchronize(h->stream));
-      if (h->d_actions) (void)hipFree(h->d_actions);
-      h->d_actions = nullptr; h->actions_cap = 0;
-      HIPCHK(hipMalloc(&h->d_actions, bytes));
+      HIPCHK(dev_grow(h->d_actions, bytes, h->stream));
       h->actions_cap = bytes;
     }
     // pageable host memory: hipMemcpyAsync stages synchronously, so the caller may
     // reuse `actions` on return
-    HIPCHK(hipMemcpyAsync(h->d_actions, actions, bytes, hipMemcpyHostToDevice, h->stream));
-    dptr = h->d_actions;
+    HIPCHK(hipMemcpyAsync(h->d_actions.get(), actions, bytes, hipMemcpyHostToDevice, h->stream));
+    dptr = h->d_actions.get();
   }
   {
     ProfScope ps(h, DTSIM_KERNEL_STEP);
     StepParams sp = step_params(h, n_steps);
     sp.step_flags = flags;
-    dt_launch_step(h->stream, h->A, h->M, sp, dptr, h->d_pool);
+    dt_launch_step(h->stream, h->A, h->M, sp, dptr, h->d_pool.get());
   }
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
@@ -955,17 +961,17 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   R.distortion = (h->cfg.flags & DTSIM_F_DISTORTION) ? 1 : 0;
   R.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
   R.n_maps = h->M.n_maps;
-  R.frames = h->n_cal ? h->d_scratch : h->frames;   // camera_rand: the rectilinear frames, gathered into `frames` below
-  R.lut = h->d_lut; R.texels = segment ? h->d_texels_seg : h->d_texels; R.tex = h->d_tex;
-  R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg;
-  R.maps = h->d_rmaps; R.tiles = h->d_rtiles; R.objs = h->d_robjs; R.meshes = h->d_meshes; R.tris = h->d_tris;
+  R.frames = h->n_cal ? h->d_scratch.get() : h->frames;   // camera_rand: the rectilinear frames, gathered into `frames` below
+  R.lut = h->d_lut.get(); R.texels = segment ? h->d_texels_seg.get() : h->d_texels.get(); R.tex = h->d_tex.get();
+  R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg.get();
+  R.maps = h->d_rmaps.get(); R.tiles = h->d_rtiles.get(); R.objs = h->d_robjs.get(); R.meshes = h->d_meshes.get(); R.tris = h->d_tris.get();
   R.max_tris = h->d_render[DT_SLAB_STRIS] ? h->max_tris : 0;
-  dt_render_layout(R.N, R.W, R.H, R.max_tris, nullptr, h->d_render, &R);
+  render_scratch(h, R.max_tris, &R);
   R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
   if (getenv("DTSIM_DEBUG_QUEUE")) HIPCHK(hipMemsetAsync(R.dbg, 0, DT_DEBUG_INTS * sizeof(int32_t), h->stream)); else R.dbg = nullptr;
-  R.tile_recs = h->d_tilerecs; R.n_tile_recs = h->n_tilerecs; R.tex_w = h->tex_w; R.tex_h = h->tex_h;
-  R.qtex = (flags & DTSIM_RENDER_GL_FILTER) ? nullptr : h->d_qtex;   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
-  R.qtiles = h->d_qtiles; R.n_qtiles = h->n_qtiles; R.qlog2 = h->qlog2; R.q_per_m = h->q_per_m;
+  R.tile_recs = h->d_tilerecs.get(); R.n_tile_recs = h->n_tilerecs; R.tex_w = h->tex_w; R.tex_h = h->tex_h;
+  R.qtex = (flags & DTSIM_RENDER_GL_FILTER) ? nullptr : h->d_qtex.get();   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
+  R.qtiles = h->d_qtiles.get(); R.n_qtiles = h->n_qtiles; R.qlog2 = h->qlog2; R.q_per_m = h->q_per_m;
   int grid_rows = 0, grid_cols = 0;                  // the largest padded tile grid of the maps
   for (int mi = 0; mi < h->M.n_maps; ++mi) { grid_rows = std::max(grid_rows, h->map_h[mi] + 2 * DT_QRING); grid_cols = std::max(grid_cols, h->map_w[mi] + 2 * DT_QRING); }
   R.qmax_tiles = std::max(grid_rows, grid_cols);
@@ -981,7 +987,7 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
     h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
     h->render_pipe = pipe | (R.light ? DTSIM_PIPE_ENV_LIGHT : 0);
-    if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch, h->frames, h->d_cal_src, h->d_env_cal, mask, h->N, R.W, R.H);
+    if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch.get(), h->frames, h->d_cal_src.get(), h->d_env_cal.get(), mask, h->N, R.W, R.H);
   }
   HIPCHK(hipGetLastError());
   h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true; h->masked = mask != nullptr;
@@ -1034,20 +1040,20 @@ int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->lines_cap < n) {
-    if (h->d_lines) { HIPCHK(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_lines); h->d_lines = nullptr; }
-    h->lines_cap = std::max(n, 1024);
-    HIPCHK(hipMalloc(&h->d_lines, sizeof(float) * 9 * (size_t)h->lines_cap));
+    const int cap = std::max(n, 1024);
+    HIPCHK(dev_grow(h->d_lines, 9 * (size_t)cap, h->stream));
+    h->lines_cap = cap;
   }
-  HIPCHK(hipMemcpyAsync(h->d_lines, lines, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_lines.get(), lines, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   RenderParams R{};
-  R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height; R.frames = h->frames; R.lut = h->d_lut;
-  dt_render_layout(R.N, R.W, R.H, 0, nullptr, h->d_render, &R);   // (the overlays read the EnvCam records the pass wrote)
+  R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height; R.frames = h->frames; R.lut = h->d_lut.get();
+  render_scratch(h, 0, &R);   // (the overlays read the EnvCam records the pass wrote)
   int i0 = 0;
   while (i0 < n) {                                    // one launch per env that has segments
     const int e = env_idx ? env_idx[i0] : 0;
     int i1 = i0;
     while (i1 < n && (env_idx ? env_idx[i1] : 0) == e) ++i1;
-    dt_launch_overlay_lines(h->stream, R, h->d_lines, i0, i1 - i0, e);
+    dt_launch_overlay_lines(h->stream, R, h->d_lines.get(), i0, i1 - i0, e);
     i0 = i1;
   }
   HIPCHK(hipGetLastError());
@@ -1070,11 +1076,11 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   if (h->leds_cap < n) {
-    if (h->d_leds) { HIPCHK(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_leds); h->d_leds = nullptr; }
-    h->leds_cap = std::max(n, 256);
-    HIPCHK(hipMalloc(&h->d_leds, sizeof(float) * 8 * (size_t)h->leds_cap));
+    const int cap = std::max(n, 256);
+    HIPCHK(dev_grow(h->d_leds, 8 * (size_t)cap, h->stream));
+    h->leds_cap = cap;
   }
-  HIPCHK(hipMemcpyAsync(h->d_leds, spheres, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_leds.get(), spheres, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   RenderParams R = h->last_R;
   R.frames = h->frames;                               // (dtsim_bind_frames may have moved the output since the pass)
   int i0 = 0;
@@ -1082,7 +1088,7 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
     const int e = env_idx ? env_idx[i0] : 0;
     int i1 = i0;
     while (i1 < n && (env_idx ? env_idx[i1] : 0) == e) ++i1;
-    dt_launch_overlay_leds(h->stream, R, h->d_leds, i0, i1 - i0, e);
+    dt_launch_overlay_leds(h->stream, R, h->d_leds.get(), i0, i1 - i0, e);
     i0 = i1;
   }
   HIPCHK(hipGetLastError());
@@ -1096,7 +1102,7 @@ size_t dtsim_frames_bytes(const dtsim_t* h) { return h ? h->frames_bytes : 0; }
 int dtsim_bind_frames(dtsim_t* h, void* devptr) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
   if (!h->frames_own) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
-  h->frames = devptr ? (uint8_t*)devptr : h->frames_own;
+  h->frames = devptr ? (uint8_t*)devptr : h->frames_own.get();
   return DTSIM_OK;
 }
 
@@ -1206,9 +1212,7 @@ static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, 
     }
     if (rpb == 0) return fail(DTSIM_E_LIMIT, "observation %dx%d: one output row needs more input rows than fit in LDS", out_w, out_h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_obs_tab) { (void)hipFree(h->d_obs_tab); h->d_obs_tab = nullptr; }
-    HIPCHK(hipMalloc(&h->d_obs_tab, tab.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(h->d_obs_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(dev_upload(h->d_obs_tab, tab.data(), tab.size()));
     h->obs_tab = tab; h->obs_off_by = off_by;
     h->obs_h = out_h; h->obs_w = out_w; h->obs_kx = ksize_x; h->obs_ky = ksize_y; h->obs_rpb = rpb; h->obs_rows_in = need;
     // power-of-two down-scaling: interior columns / rows with identical small-integer taps (k_observe's dot4 / two-lane paths)
@@ -1261,8 +1265,8 @@ static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, 
   P.rows_per_block = h->obs_rpb; P.max_rows_in = h->obs_rows_in;
   P.chw = (flags & DTSIM_OBS_CHW) ? 1 : 0; P.f32 = (flags & DTSIM_OBS_F32) ? 1 : 0;
   P.frames = h->frames; P.out = out;
-  P.bx = h->d_obs_tab; P.kkx = h->d_obs_tab + (out_w != W ? 2 * (size_t)out_w : 0);
-  P.by = h->d_obs_tab + h->obs_off_by; P.kky = P.by + 2 * (size_t)out_h;
+  P.bx = h->d_obs_tab.get(); P.kkx = P.bx + (out_w != W ? 2 * (size_t)out_w : 0);
+  P.by = P.bx + h->obs_off_by; P.kky = P.by + 2 * (size_t)out_h;
   P.hfast = h->obs_fast.hfast; P.hn = h->obs_fast.hn; P.hoff = h->obs_fast.hoff; P.hsh = h->obs_fast.hsh;
   P.vfast = h->obs_fast.vfast; P.vsh = h->obs_fast.vsh;
   memcpy(P.hw, h->obs_fast.hw, sizeof P.hw); memcpy(P.vw, h->obs_fast.vw, sizeof P.vw);
@@ -1306,16 +1310,14 @@ static int observe_cubic_pass(dtsim_t* h, void* out, int out_h, int out_w, int f
   tab.insert(tab.end(), first_y, first_y + out_h); tab.insert(tab.end(), taps_y, taps_y + 4 * (size_t)out_h);
   if (tab != h->obsc_tab || !h->d_obsc_tab) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_obsc_tab) { (void)hipFree(h->d_obsc_tab); h->d_obsc_tab = nullptr; }
-    HIPCHK(hipMalloc(&h->d_obsc_tab, tab.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(h->d_obsc_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(dev_upload(h->d_obsc_tab, tab.data(), tab.size()));
     h->obsc_tab = tab;
   }
   ObserveParams P{};
   P.N = h->N; P.H = H; P.W = W; P.oh = out_h; P.ow = out_w; P.kx = 4; P.ky = 4;
   P.chw = (flags & DTSIM_OBS_CHW) ? 1 : 0; P.f32 = (flags & DTSIM_OBS_F32) ? 1 : 0;
   P.frames = h->frames; P.out = out;
-  P.bx = h->d_obsc_tab; P.kkx = P.bx + out_w; P.by = P.kkx + 4 * (size_t)out_w; P.kky = P.by + out_h;
+  P.bx = h->d_obsc_tab.get(); P.kkx = P.bx + out_w; P.by = P.kkx + 4 * (size_t)out_w; P.kky = P.by + out_h;
   {
     ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
     dt_launch_observe_cubic(h->stream, P, mask);
@@ -1341,25 +1343,20 @@ int dtsim_query(dtsim_t* h, int n, const int32_t* env_idx, const double* poses, 
     if (env_idx[i] < 0 || env_idx[i] >= h->N) return fail(DTSIM_E_INVALID, "env_idx[%d]=%d out of range", i, env_idx[i]);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (n > h->q_cap) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_qenv) (void)hipFree(h->d_qenv);
-    if (h->d_qpose) (void)hipFree(h->d_qpose);
-    if (h->d_qout) (void)hipFree(h->d_qout);
-    h->d_qenv = nullptr; h->d_qpose = nullptr; h->d_qout = nullptr; h->q_cap = 0;
     const int cap = n < 256 ? 256 : n;
-    HIPCHK(hipMalloc(&h->d_qenv, sizeof(int32_t) * cap));
-    HIPCHK(hipMalloc(&h->d_qpose, sizeof(double) * 3 * cap));
-    HIPCHK(hipMalloc(&h->d_qout, sizeof(dtsim_probe) * cap));
+    HIPCHK(dev_grow(h->d_qenv, cap, h->stream));
+    HIPCHK(dev_grow(h->d_qpose, 3 * (size_t)cap, h->stream));
+    HIPCHK(dev_grow(h->d_qout, cap, h->stream));
     h->q_cap = cap;
   }
-  HIPCHK(hipMemcpyAsync(h->d_qenv, env_idx, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->d_qpose, poses, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_qenv.get(), env_idx, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_qpose.get(), poses, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
   {
     ProfScope ps(h, DTSIM_KERNEL_QUERY);
-    dt_launch_query(h->stream, h->A, h->M, step_params(h, 0), n, h->d_qenv, h->d_qpose, safety_factor, h->d_qout);
+    dt_launch_query(h->stream, h->A, h->M, step_params(h, 0), n, h->d_qenv.get(), h->d_qpose.get(), safety_factor, h->d_qout.get());
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, h->d_qout, sizeof(dtsim_probe) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(out, h->d_qout.get(), sizeof(dtsim_probe) * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return DTSIM_OK;
 }
@@ -1466,8 +1463,8 @@ int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
   std::vector<void*> bases;
   switch (field) {
     case DTSIM_FIELD_STATE_BLOB: {
-      hipError_t e = to_host ? hipMemcpy(host, h->slab, need, hipMemcpyDeviceToHost)
-                             : hipMemcpy(h->slab, host, need, hipMemcpyHostToDevice);
+      hipError_t e = to_host ? hipMemcpy(host, h->slab.get(), need, hipMemcpyDeviceToHost)
+                             : hipMemcpy(h->slab.get(), host, need, hipMemcpyHostToDevice);
       if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy blob: %s", hipGetErrorString(e));
       return DTSIM_OK;
     }
@@ -1481,7 +1478,7 @@ int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
       if (!to_host) return fail(DTSIM_E_INVALID, "DTSIM_FIELD_RENDER_POS is read-only");
       int32_t* out = static_cast<int32_t*>(host);
       if (h->render_tables & 4) {
-        RenderParams R{}; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, 0, nullptr, h->d_render, &R);
+        RenderParams R{}; render_scratch(h, 0, &R);
         hipError_t e = hipMemcpy(out, R.envpos, N * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy render order: %s", hipGetErrorString(e));
       } else {
@@ -1515,10 +1512,10 @@ int dtsim_read_agent(dtsim_t* h, int env, dtsim_agent_info* out) {
   if (!h || !out) return fail(DTSIM_E_INVALID, "null argument");
   if (env < 0 || env >= h->N) return fail(DTSIM_E_INVALID, "env %d out of range [0, %d)", env, h->N);
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->d_agent) HIPCHK(hipMalloc(&h->d_agent, sizeof(dtsim_agent_info)));
-  hipLaunchKernelGGL(k_agent_info, dim3(1), dim3(1), 0, h->stream, h->A, env, h->d_agent);
+  if (!h->d_agent) HIPCHK(dev_alloc(h->d_agent, 1));
+  hipLaunchKernelGGL(k_agent_info, dim3(1), dim3(1), 0, h->stream, h->A, env, h->d_agent.get());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, h->d_agent, sizeof(dtsim_agent_info), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(out, h->d_agent.get(), sizeof(dtsim_agent_info), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return DTSIM_OK;
 }
@@ -1531,7 +1528,7 @@ int dtsim_write(dtsim_t* h, int field, const void* src, size_t bytes) {
 
 void* dtsim_field_devptr(dtsim_t* h, int field) {
   if (!h) return nullptr;
-  if (field == DTSIM_FIELD_STATE_BLOB) return h->slab;
+  if (field == DTSIM_FIELD_STATE_BLOB) return h->slab.get();
   if (field == DTSIM_FIELD_POS) return h->A.pos_x;  // planar: x plane; z plane = pos_z
   FieldDesc d;
   if (!field_desc(h, field, d)) return nullptr;

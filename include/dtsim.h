@@ -280,6 +280,10 @@ int dtsim_device_count(void);
 int dtsim_create(const dtsim_config* cfg, dtsim_t** out);
 void dtsim_destroy(dtsim_t* h);
 
+/* The setters -- dtsim_set_assets, dtsim_set_maps, dtsim_set_distortion_lut(s), dtsim_set_reset_sampler, dtsim_set_spawn_pool,
+ * dtsim_set_segment_assets -- and the table caches of dtsim_observe / dtsim_observe_cubic: on failure the handle keeps what it
+ * had.  Only what the last render pass left for the post-passes may be dropped: dtsim_draw_leds then waits for a dtsim_render. */
+
 /* Textures (graphics.py:69-169 load_texture) and meshes (objmesh.py:62-293). */
 int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures,
                      const dtsim_mesh* meshes, int n_meshes);
@@ -300,7 +304,7 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
  * DTSIM_LUTS_CAMERA_RAND: device-side resets also scale camera height, angle and fov_y by the randomizer's draws without
  * domain randomisation, and zero the camera noise then (simulator.py:611-614, 1768-1769).  Every call sets this switch from
  * its flags, n_cal = 0 included (camera_rand with one table for every env, e.g. UndistortWrapper's); dtsim_set_distortion_lut
- * leaves it alone.  On failure the handle keeps the tables it had. */
+ * leaves it alone. */
 #define DTSIM_LUTS_CAMERA_RAND 1u
 int dtsim_set_distortion_luts(dtsim_t* h, int n_cal, const int32_t* src_index, const int32_t* env_cal, uint32_t flags);
 /* Host-only builders of those tables (no handle, no GPU), bit-identical to dtsim/distortion.py's numpy statement for any
