@@ -119,7 +119,6 @@ struct dtsim {
   int lines_cap = 0;
   int render_tables = 0;          // dt_launch_render: which env-invariant tables are valid (camera LUT + maps unchanged)
   int render_pipe = 0;            // DTSIM_PIPE_* of the last render pass (DTSIM_FIELD_RENDER_PIPE)
-  RenderOverlap overlap{};        // render parts (DTSIM_RENDER_PARTS > 1): second stream + ordering events
   int q_cap = 0;
   // render
   DevPtr<uint8_t> frames_own;
@@ -153,7 +152,7 @@ struct dtsim {
   DevPtr<uint32_t> d_qtiles;
   int n_qtiles = 0, qlog2 = 0;
   bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
-  int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop); DTSIM_STEP_LANES = 1 / 2 / 4 / 8
+  int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop): 1, 2 or 4
   float q_per_m = 0.f;
   DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
   int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
@@ -287,14 +286,10 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
   HIPCHK(hipSetDevice(cfg->device));
   dtsim* h = new dtsim();
   { const char* ro = getenv("DTSIM_RASTER_OLD"); h->raster_old = ro && ro[0] == '1'; }   // A/B timing aid: k_raster_q instead of k_raster_v3
-  {  // lanes of a wavefront per env in k_step: as many (up to 4) as keep the launch within ~32 K threads -- a small batch is a
-     // latency problem (one f64 chain per env, 64 wavefronts on 1024 SIMDs at N = 4096), a large one a throughput problem,
-     // where the redundant lanes would cost (profiles/r03_c2_lanes_ab.txt).  DTSIM_STEP_LANES = 1 / 2 / 4 / 8 overrides.
-    const char* sl = getenv("DTSIM_STEP_LANES");
-    int v = sl ? atoi(sl) : 0;
-    if (!(v == 1 || v == 2 || v == 4 || v == 8)) v = cfg->num_envs * 4 <= 32768 ? 4 : cfg->num_envs * 2 <= 32768 ? 2 : 1;
-    h->step_lanes = v;
-  }
+  // lanes of a wavefront per env in k_step: as many (up to 4) as keep the launch within ~32 K threads -- a small batch is a
+  // latency problem (one f64 chain per env, 64 wavefronts on 1024 SIMDs at N = 4096), a large one a throughput problem,
+  // where the redundant lanes would cost (profiles/r03_c2_lanes_ab.txt)
+  h->step_lanes = cfg->num_envs * 4 <= 32768 ? 4 : cfg->num_envs * 2 <= 32768 ? 2 : 1;
   h->cfg = *cfg;
   h->N = cfg->num_envs;
   if (cfg->stream) { h->stream = (hipStream_t)cfg->stream; }
@@ -323,18 +318,8 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     size_t bytes[DT_SLABS]; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, bytes);
     for (int i = DT_SLAB_ENV; i <= DT_SLAB_QEND && e == hipSuccess; ++i) e = dev_alloc(h->d_render[i], bytes[i]);
     RenderParams R{}; render_scratch(h, 0, &R);
-    if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));   // (the DT_RO_STATS counters start at 0)
+    if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(render scratch): %s", hipGetErrorString(e)); }
-    {  // render parts: off (1) unless asked for
-      const char* rp = getenv("DTSIM_RENDER_PARTS");
-      const int parts = rp ? std::min(std::max(atoi(rp), 1), DT_MAX_RENDER_PARTS) : 1;
-      if (parts > 1) {
-        e = hipStreamCreateWithFlags(&h->overlap.s2, hipStreamNonBlocking);
-        for (int i = 0; i <= DT_MAX_RENDER_PARTS && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->overlap.ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "render parts (stream / events): %s", hipGetErrorString(e)); }
-        h->overlap.parts = parts;
-      }
-    }
     if (!(cfg->flags & DTSIM_F_DISTORTION)) {
       // identity LUT: output pixel == rectilinear pixel
       int rc = dtsim_set_distortion_lut(h, nullptr, nullptr);
@@ -353,8 +338,6 @@ void dtsim_destroy(dtsim_t* h) {
     for (auto& p : s.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto& p : s.free_) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   }
-  if (h->overlap.s2) { (void)hipStreamSynchronize(h->overlap.s2); (void)hipStreamDestroy(h->overlap.s2); }
-  for (hipEvent_t ev : h->overlap.ev) if (ev) (void)hipEventDestroy(ev);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;   // frees every device buffer the handle owns
 }
@@ -968,7 +951,6 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   R.max_tris = h->d_render[DT_SLAB_STRIS] ? h->max_tris : 0;
   render_scratch(h, R.max_tris, &R);
   R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
-  if (getenv("DTSIM_DEBUG_QUEUE")) HIPCHK(hipMemsetAsync(R.dbg, 0, DT_DEBUG_INTS * sizeof(int32_t), h->stream)); else R.dbg = nullptr;
   R.tile_recs = h->d_tilerecs.get(); R.n_tile_recs = h->n_tilerecs; R.tex_w = h->tex_w; R.tex_h = h->tex_h;
   R.qtex = (flags & DTSIM_RENDER_GL_FILTER) ? nullptr : h->d_qtex.get();   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
   R.qtiles = h->d_qtiles.get(); R.n_qtiles = h->n_qtiles; R.qlog2 = h->qlog2; R.q_per_m = h->q_per_m;
@@ -976,52 +958,14 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   for (int mi = 0; mi < h->M.n_maps; ++mi) { grid_rows = std::max(grid_rows, h->map_h[mi] + 2 * DT_QRING); grid_cols = std::max(grid_cols, h->map_w[mi] + 2 * DT_QRING); }
   R.qmax_tiles = std::max(grid_rows, grid_cols);
   const int pipe = dt_raster_pipe(R, grid_rows, grid_cols, h->raster_old);
-#ifdef DT_WAVE_SPANS   // experiment: [2][2048][4][8] spans of the exact-path kernels, then [raster workgroups][4 wavefronts][4] stamps of k_raster_v3
-  static unsigned long long* d_spans = nullptr;
-  const size_t n_spans = (size_t)2 * 2048 * 4 * 8 + dt_raster_groups(R.N, R.W, R.H) * 4 * 4;
-  if (getenv("DTSIM_WAVE_SPANS") && !d_spans) HIPCHK(hipMalloc(&d_spans, n_spans * 8));
-  R.spans = getenv("DTSIM_WAVE_SPANS") ? d_spans : nullptr;
-  if (R.spans) HIPCHK(hipMemsetAsync(R.spans, 0, n_spans * 8, h->stream));
-#endif
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
-    h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, h->overlap.parts > 1 ? &h->overlap : nullptr, mask);
+    h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, mask);
     h->render_pipe = pipe | (R.light ? DTSIM_PIPE_ENV_LIGHT : 0);
     if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch.get(), h->frames, h->d_cal_src.get(), h->d_env_cal.get(), mask, h->N, R.W, R.H);
   }
   HIPCHK(hipGetLastError());
   h->rendered = true; h->last_R = R; h->last_segment = segment; h->leds_ok = true; h->masked = mask != nullptr;
-#ifdef DT_WAVE_SPANS
-  if (R.spans) {   // the spans of the last render -> the file DTSIM_WAVE_SPANS names (tools/wave_spans.py reads it)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<unsigned long long> sp(n_spans);
-    HIPCHK(hipMemcpy(sp.data(), R.spans, sp.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(getenv("DTSIM_WAVE_SPANS"), "wb")) { fwrite(sp.data(), 8, sp.size(), f); fclose(f); }
-  }
-#endif
-  if (getenv("DTSIM_DEBUG_QUEUE")) {   // profiling aid: how many pixels took the exact MSAA path
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int32_t* ro_stats = reinterpret_cast<RenderDump*>(R.dump)->ro_stats, ro[12];   // DT_RO_STATS build variant: k_resolve_obj's z-buffer
-    HIPCHK(hipMemcpy(ro, ro_stats, sizeof ro, hipMemcpyDeviceToHost));
-    if (ro[4]) fprintf(stderr, "[dtsim] k_resolve_obj z-buffer: %d calls (%d triangle-parallel), %.1f staged triangles and %.1f pixels per call, "
-                       "%.2f box candidates per pixel, %.2f passes per call (max over lanes), %.2f if the pairs were spread evenly\n",
-                       ro[4], ro[5], (double)ro[2] / ro[4], (double)ro[3] / ro[4], ro[3] ? (double)ro[8] / ro[3] : 0.0, (double)ro[9] / ro[4], (double)ro[10] / ro[4]);
-    HIPCHK(hipMemset(ro_stats, 0, sizeof ro));
-    const size_t npix = (size_t)R.W * R.H;
-    std::vector<int32_t> qc(dt_raster_groups(R.N, R.W, R.H) * 4);   // one count per raster wavefront
-    HIPCHK(hipMemcpy(qc.data(), R.qcount, qc.size() * 4, hipMemcpyDeviceToHost));
-    long long tot = 0, mx = 0, iters = 0, nonempty = 0;
-    for (int32_t v : qc) { tot += v; mx = std::max<long long>(mx, v); iters += (v + 63) / 64; nonempty += v > 0; }
-    fprintf(stderr, "[dtsim] resolve: %lld of %zu wavefront regions non-empty, %lld 64-lane iterations, lane utilisation %.1f%%\n",
-            nonempty, qc.size(), iters, iters ? 100.0 * tot / (64.0 * iters) : 0.0);
-    int32_t dbg[DT_DEBUG_INTS];
-    HIPCHK(hipMemcpy(dbg, R.dbg, sizeof dbg, hipMemcpyDeviceToHost));
-    unsigned long long pairs; memcpy(&pairs, dbg + 6, 8);
-    fprintf(stderr, "[dtsim] resolve mesh pass: %d (batch,env) pairs, %d objects streamed, %d z-buffer calls (%d triangle-parallel), "
-                    "%d triangles staged, %d pixels, %llu pixel x triangle tests\n", dbg[0], dbg[1], dbg[4], dbg[5], dbg[2], dbg[3], pairs);
-    fprintf(stderr, "[dtsim] exact-path pixels: %lld of %zu (%.2f%%), max per wavefront region %lld\n", tot, npix * h->N,
-            100.0 * tot / (double)(npix * h->N), mx);
-  }
   return DTSIM_OK;
 }
 

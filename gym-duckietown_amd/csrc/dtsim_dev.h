@@ -89,7 +89,7 @@ struct StepParams {
   int32_t action_mode, actions_f64, auto_reset, n_pool;
   uint32_t step_flags;                  // DTSIM_STEP_*
   int32_t light_capture, domain_rand;   // DTSIM_F_LIGHT_CAPTURE (device-side resets take the new light through the last frame's camera); DTSIM_F_DOMAIN_RAND (that camera carries its noise)
-  int32_t lanes;                        // lanes of a wavefront that share one env in k_step (1, 2, 4, 8; physics.hip Coop)
+  int32_t lanes;                        // lanes of a wavefront that share one env in k_step (1, 2, 4; physics.hip Coop)
   int32_t camera_rand;                  // DTSIM_LUTS_CAMERA_RAND: device-side resets scale camera height / angle / fov_y (simulator.py:611-614)
   const dtsim_reset_sampler* sampler;   // device copy, or null: device-side reset sampling (N2)
   double delta_time, robot_speed;
@@ -218,8 +218,7 @@ struct RenderParams {
   uint16_t* queue;              // MSAA edge-pixel queue regions, [workgroups][4][256*16]
   int32_t* qcount;              // [workgroups][4]
   uint16_t* qend;               // [workgroups][4][DT_ENVS_PER_BLOCK] queue fill of each region after each env of the chunk (mesh-object renders)
-  int32_t* dbg;                 // [DT_DEBUG_INTS] debug counters (DTSIM_DEBUG_QUEUE), else null
-  int32_t* work;                // [0] number of work items (raster appends), [1] resolve cursor, [2], [3] the same for k_resolve_obj ([2] = its heavy items, front of the list; [6] = the others, back); zeroed per render ([DT_MAX_RENDER_PARTS][DT_WORK_INTS])
+  int32_t* work;                // [0] number of work items (raster appends), [1] resolve cursor, [2], [3] the same for k_resolve_obj ([2] = its heavy items, front of the list; [6] = the others, back); zeroed per render ([DT_WORK_INTS])
   uint32_t* items;              // [workgroups * DT_ITEMS_PER_WG] work items: raster workgroup * DT_ITEMS_PER_WG + part
   uint32_t* items2;             // [workgroups * DT_ENVS_PER_BLOCK] work items of k_resolve_obj: raster workgroup * DT_ITEMS_PER_WG + env group
   const uint8_t* mesh_seg;      // [n_meshes][4] flat segmentation colour per mesh (segment renders only)
@@ -236,20 +235,16 @@ struct RenderParams {
   void* envd;                   // [N] EnvD (render_v3dr.inc, 320 B, render order): k_raster_v3dr's per-env constants (domain randomisation)
   int32_t q3_rows;              // k_raster_v3 / k_raster_v3dr: rows of their LDS tile table (largest padded grid height); 0: they cannot run (dt_raster_pipe)
   int32_t light;                // DTSIM_F_LIGHT_CAPTURE with the shared camera: every env lit by its own eye-space light (k_cam_setup, the LIGHT kernels)
-  unsigned long long* spans;    // DT_WAVE_SPANS build variant only (else null): [2][2048 workgroups][4 wavefronts]{start, end, items, longest / first item, start of the first, sum, last item} in 100 MHz ticks
 };
-#define DT_MAX_RENDER_PARTS 8
-#define DT_WORK_INTS 8           // RenderParams.work: ints per render part
+#define DT_WORK_INTS 8           // RenderParams.work
 #define DT_WORK_LIVE 7           // RenderParams.work[DT_WORK_LIVE]: envs of a masked pass (k_env_sort_masked), read by the SUB rasters
-#define DT_DEBUG_INTS 8          // RenderParams.dbg
-// RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane); `ro_stats`, the DT_RO_STATS build
-// variant's k_resolve_obj z-buffer counters (DTSIM_DEBUG_QUEUE prints them)
-struct RenderDump { uint8_t store[64 * 16]; int32_t ro_stats[12]; };
+// RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane)
+struct RenderDump { uint8_t store[64 * 16]; };
 // The render scratch (render.hip dt_render_layout): the allocations RenderParams points into, each a run of arrays -- ENV: per env EnvCam, EnvFast,
-// EnvQ, envpos, EnvV [N + 1], EnvD, EnvL [N + 1]; PIX: PixTab, SampTab, RenderDump; QCOUNT: qcount, dbg, work; ITEMS: items, items2; STRIS: stris, tribox.
+// EnvQ, envpos, EnvV [N + 1], EnvD, EnvL [N + 1]; PIX: PixTab, SampTab, RenderDump; QCOUNT: qcount, work; ITEMS: items, items2; STRIS: stris, tribox.
 enum RenderSlab { DT_SLAB_ENV, DT_SLAB_PIX, DT_SLAB_QUEUE, DT_SLAB_QCOUNT, DT_SLAB_ITEMS, DT_SLAB_QEND, DT_SLAB_STRIS, DT_SLAB_OBJBOX, DT_SLAB_OBJMASK, DT_SLABS };
 // With bytes: bytes[s] = the size of slab s for N envs, W x H frames and max_tris triangle slots per env (0: no such slab).  With R: points
-// R's scratch fields (envcam .. objmask, dbg included; the object arrays only with max_tris > 0) into base[DT_SLABS] (null bases: null arrays).
+// R's scratch fields (envcam .. objmask; the object arrays only with max_tris > 0) into base[DT_SLABS] (null bases: null arrays).
 void dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base = nullptr, RenderParams* R = nullptr);
 // The raster of a pass (DTSIM_PIPE_*) from R, the largest padded tile grid of the maps (grid_rows x grid_cols, DT_QRING ring included) and
 // DTSIM_RASTER_OLD (raster_old: k_raster_q / the generic raster instead of k_raster_v3 / k_raster_v3dr); sets R.q3_rows.
@@ -257,13 +252,9 @@ int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_ol
 // pipe: dt_raster_pipe's choice for R.  tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an
 // earlier launch (they depend on the camera LUT and the maps only); returns the bits that are valid after this launch,
 // plus bit 2 when the pass ran in k_env_sort's render order (RenderParams.envpos holds it: DTSIM_FIELD_RENDER_POS).
-// Render parts (round 4): with parts > 1 the exact-path kernels of one range of chunks run on s2 beside the raster of the
-// next range; ev[p] orders range p across the two streams, ev[DT_MAX_RENDER_PARTS] joins s2 back into the caller's stream.
-struct RenderOverlap { int parts; hipStream_t s2; hipEvent_t ev[DT_MAX_RENDER_PARTS + 1]; };
 // mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
 // only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int pipe, int tables, const RenderOverlap* ov = nullptr,
-                     const uint8_t* mask = nullptr);
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int pipe, int tables, const uint8_t* mask = nullptr);
 // GL_LINE overlays (draw_curve / draw_bbox) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);

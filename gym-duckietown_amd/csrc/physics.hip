@@ -83,7 +83,7 @@ __device__ inline void proj4(double nx, double nz, const double* c, double& mn, 
 }
 
 // collision.py:129-186: SAT between the agent box (corners ac, axes an) and one OBB.
-// ---- lane co-operation inside one env (DTSIM_STEP_LANES, k_step<SAMPLER, L>) -----------------------------------------
+// ---- lane co-operation inside one env (k_step<SAMPLER, L>, L = 1, 2 or 4) ---------------------------------------------
 // With L > 1, L adjacent lanes of a wavefront work on ONE env: everything serial (dynamics, trigonometry, the Bezier
 // bisection) runs redundantly on all of them -- identical inputs, identical results, identical (duplicate) stores -- and
 // the loops over OBJECTS (collision.py:129-186 intersects / intersects_single_obj, simulator.py:1430-1459
@@ -961,13 +961,13 @@ __global__ __launch_bounds__(STEP_BLOCK) void k_query(SimArrays A, MapSet M, Ste
 
 void dt_launch_step(hipStream_t s, const SimArrays& A, const MapSet& M, const StepParams& P,
                     const void* actions, const dtsim_init_state* pool) {
-  // P.lanes adjacent lanes per env (1, 2, 4 or 8; Coop in this file): more wavefronts for the same envs, object loops split
-  const int L = (P.lanes == 2 || P.lanes == 4 || P.lanes == 8) ? P.lanes : 1;
+  // P.lanes adjacent lanes per env (1, 2 or 4; Coop in this file): more wavefronts for the same envs, object loops split
+  const int L = (P.lanes == 2 || P.lanes == 4) ? P.lanes : 1;
   const int grid = (int)(((long long)A.N * L + STEP_BLOCK - 1) / STEP_BLOCK);
   const size_t lds = (size_t)M.total_words * 8;
 #define LAUNCH_STEP(S_, L_) hipLaunchKernelGGL((k_step<S_, L_>), dim3(grid), dim3(STEP_BLOCK), lds, s, A, M, P, actions, pool)
-  if (P.sampler) { if (L == 8) LAUNCH_STEP(true, 8); else if (L == 4) LAUNCH_STEP(true, 4); else if (L == 2) LAUNCH_STEP(true, 2); else LAUNCH_STEP(true, 1); }
-  else { if (L == 8) LAUNCH_STEP(false, 8); else if (L == 4) LAUNCH_STEP(false, 4); else if (L == 2) LAUNCH_STEP(false, 2); else LAUNCH_STEP(false, 1); }
+  if (P.sampler) { if (L == 4) LAUNCH_STEP(true, 4); else if (L == 2) LAUNCH_STEP(true, 2); else LAUNCH_STEP(true, 1); }
+  else { if (L == 4) LAUNCH_STEP(false, 4); else if (L == 2) LAUNCH_STEP(false, 2); else LAUNCH_STEP(false, 1); }
 #undef LAUNCH_STEP
 }
 

@@ -839,7 +839,7 @@ __device__ inline void test_tri_inside(const Tri& st, float pcx, float pcy, floa
 #endif
 #define RO_SCR_BYTES (64 * 4 * 8 + RO_PAIR_CAP * 2)       // per wavefront: sample keys + the pair list
 __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int fill, bool mine, int lane, float pcx, float pcy,
-                                     float wbest[4], int tbest[4], int32_t* dbg) {
+                                     float wbest[4], int tbest[4]) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -847,10 +847,6 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
   const int n_mine = __popcll(mm);
   const int n_chunks = (fill + 63) >> 6;
   const bool tri_parallel = n_mine * (n_chunks * 110 + 110) < fill * 8 + 400;
-  if (dbg && lane == 0) {                            // DTSIM_DEBUG_QUEUE statistics
-    atomicAdd(dbg + 2, fill); atomicAdd(dbg + 3, n_mine); atomicAdd(dbg + 4, 1); atomicAdd(dbg + 5, tri_parallel ? 1 : 0);
-    atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 6), (unsigned long long)fill * (unsigned long long)n_mine);
-  }
   if (tri_parallel) {
     unsigned long long todo = mm;
     while (todo) {                                   // wave-uniform
@@ -892,9 +888,6 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
 #pragma unroll
     for (int q = 0; q < 4; ++q) zb[lane * 4 + q] = 0ull;
     int base = 0;
-#ifdef DT_RO_STATS
-    int n_pairs = 0, n_pass = 0;
-#endif
     auto drain = [&]() {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -904,9 +897,6 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
         const uint32_t pr = act ? plist[q0 + lane] : 0u;
         const int src = pr & 63;
         const float qx = __shfl(pcx, src), qy = __shfl(pcy, src);
-#ifdef DT_RO_STATS
-        ++n_pass;
-#endif
         if (act) {
           const TriCov& st = w_tris[pr >> 6];
           const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
@@ -944,9 +934,6 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
       if (__builtin_amdgcn_inverse_ballot_w64(m))
         plist[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)((j << 6) | lane);
       base += __popcll(m);
-#ifdef DT_RO_STATS
-      n_pairs += __popcll(m);
-#endif
       if (base > RO_PAIR_CAP - 64) { drain(); base = 0; }
     }
     if (base) drain();
@@ -959,9 +946,6 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
         if (k != 0ull && (w > wbest[q] || (w == wbest[q] && ix < tbest[q]))) { wbest[q] = w; tbest[q] = ix; }
       }
     }
-#ifdef DT_RO_STATS
-    if (dbg && lane == 0) { atomicAdd(dbg + 8, n_pairs); atomicAdd(dbg + 9, n_pass); atomicAdd(dbg + 10, (n_pairs + 63) >> 6); }
-#endif
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -991,17 +975,6 @@ __device__ inline uint32_t shade_msaa(const EnvCam& c, const MapU& m, const Rend
     else if (hs.cls == CLS_TILE) key[s] = 2u | ((uint32_t)hs.tj << 2) | ((uint32_t)hs.ti << 14);
     else { key[s] = (uint32_t)hs.cls; n_sky += hs.cls == CLS_SKY; n_gnd += hs.cls == CLS_GROUND; }
   }
-#ifdef DT_WAVE_SPANS   // experiment: how many exact-path pixels have all four samples on one primitive (counters behind the span slots)
-  if (!OBJ && R.spans) {
-    unsigned long long* cn = R.spans + 2 * 2048 * 4 * 8 - 8;
-    const bool uni = key[0] == key[1] && key[1] == key[2] && key[2] == key[3];
-    const unsigned long long all = __ballot(true), ut = __ballot(uni && (key[0] & 3u) == 2u), ug = __ballot(uni && key[0] == 1u), us = __ballot(uni && key[0] == 0u);
-    if ((int)(threadIdx.x & 63) == __builtin_ctzll(all)) {
-      atomicAdd(cn + 0, (unsigned long long)__popcll(all)); atomicAdd(cn + 1, (unsigned long long)__popcll(ut));
-      atomicAdd(cn + 2, (unsigned long long)__popcll(ug)); atomicAdd(cn + 3, (unsigned long long)__popcll(us));
-    }
-  }
-#endif
   // 2. shading: once per primitive, at the pixel centre, weighted by its sample count.  Sky and the
   //    ground quad are single primitives; tiles / triangles are walked as a list of distinct keys so
   //    that a wavefront runs max-over-lanes(distinct) passes of the expensive code, not one per sample.
@@ -2339,9 +2312,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
   uint32_t* s_wave = s_mem + R.n_tile_recs * (sizeof(TileLds) / 4);
   EnvCam* w_cams = reinterpret_cast<EnvCam*>(s_wave) + wave * ENVS_PER_BLOCK;                    // wavefront-local
   const int n_items = R.work[0];                     // written by the raster launch
-#ifdef DT_WAVE_SPANS   // experiment: wall-clock span of every persistent wavefront (100 MHz ticks), read back by dtsim_render
-  const unsigned long long span_t0 = wall_clock64(); unsigned long long span_long = 0, span_first = 0, span_first_at = 0, span_sum = 0, span_last = 0; int span_n = 0;
-#endif
   // One atomic buys `grab` items, taken with stride n_grabs through the list: same-address atomics are
   // serialised by the L2 (~0.2 ms per 100 k of them), and the stride keeps the consecutive items of one hot
   // raster workgroup on different wavefronts.  Granularity: ~4 grabs per resident wavefront, <= GRAB_MAX items.
@@ -2360,9 +2330,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
     first_grab = false;
     if (g >= n_grabs) break;
     for (int it = g; it < n_items; it += n_grabs) {  // wave-uniform
-#ifdef DT_WAVE_SPANS
-      const unsigned long long span_i0 = wall_clock64(); ++span_n;
-#endif
       const uint32_t item = R.items[it];
       const int rwg = (int)(item / ITEMS_PER_WG), part = (int)(item % ITEMS_PER_WG);
       const int tile = rwg % n_tiles, chunk = rwg / n_tiles;
@@ -2407,17 +2374,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
           dst[0] = (uint8_t)v; dst[1] = (uint8_t)(v >> 8); dst[2] = (uint8_t)(v >> 16);
         }
       }
-#ifdef DT_WAVE_SPANS
-      { const unsigned long long d = wall_clock64() - span_i0; span_long = d > span_long ? d : span_long; span_sum += d; span_last = d; if (span_n == 1) { span_first = d; span_first_at = span_i0 - span_t0; } }
-#endif
     }
   }
-#ifdef DT_WAVE_SPANS
-  if (R.spans && lane == 0) {
-    unsigned long long* o = R.spans + ((size_t)blockIdx.x * 4 + wave) * 8;
-    o[0] = span_t0; o[1] = wall_clock64(); o[2] = (unsigned long long)span_n; o[3] = span_long; o[4] = span_first; o[5] = span_first_at; o[6] = span_sum; o[7] = span_last;
-  }
-#endif
 }
 
 // Exact path of the pixels inside mesh-object screen boxes (and, after the generic raster, of every queued pixel).
@@ -2453,9 +2411,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
   const int n_front = R.work[2], n_items = n_front + R.work[6];   // written by the raster launch (push_obj_items): heavy items first
   const size_t items_cap = obj_items_cap(R);
   auto item_at = [&](int i) -> uint32_t { return R.items2[i < n_front ? (size_t)i : items_cap - 1 - (size_t)(i - n_front)]; };
-#ifdef DT_WAVE_SPANS
-  const unsigned long long span_t0 = wall_clock64(); unsigned long long span_long = 0, span_first = 0, span_first_at = 0, span_sum = 0, span_last = 0; int span_n = 0;
-#endif
   const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
   const int n_grabs = (n_items + grab - 1) / grab;
   const int n_waves = (int)gridDim.x * (RB / 64);     // first grab = the wavefront's own index, as in k_resolve
@@ -2500,9 +2455,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
       const int ne = min(ENVS_PER_BLOCK, R.N - e0);
       if (p0 >= ne) continue;
       const int tile_x0 = (tile % tiles_x) * DT_TILE_W, tile_y0 = (tile / tiles_x) * DT_TILE_H;
-#ifdef DT_WAVE_SPANS
-      const unsigned long long span_i0 = wall_clock64(); ++span_n;
-#endif
       {                                                // the (tile, env) unit
         const int p = p0;
         int c_[4], s_[4];
@@ -2595,12 +2547,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
                 for (int j = 0; j < NB; ++j) {
                   if (j > 0 && g0 + j * 64 >= n_p) break;            // wave-uniform
                   zbuffer_chunk(w_tris, w_scr, fill, have[j], lane, (nxv[j] + 1.f) * 0.5f * (float)R.W, (1.f - nyv[j]) * 0.5f * (float)R.H,
-                                zbest[j], tbest[j],
-#ifdef DT_RO_STATS
-                                reinterpret_cast<RenderDump*>(R.dump)->ro_stats);
-#else
-                                nullptr);
-#endif
+                                zbest[j], tbest[j]);
                 }
                 fill = 0;
               }
@@ -2621,17 +2568,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
           }
         }
       }
-#ifdef DT_WAVE_SPANS
-      { const unsigned long long d = wall_clock64() - span_i0; span_long = d > span_long ? d : span_long; span_sum += d; span_last = d; if (span_n == 1) { span_first = d; span_first_at = span_i0 - span_t0; } }
-#endif
     }
   }
-#ifdef DT_WAVE_SPANS
-  if (R.spans && lane == 0) {
-    unsigned long long* o = R.spans + ((size_t)(2048 + blockIdx.x) * 4 + wave) * 8;
-    o[0] = span_t0; o[1] = wall_clock64(); o[2] = (unsigned long long)span_n; o[3] = span_long; o[4] = span_first; o[5] = span_first_at; o[6] = span_sum; o[7] = span_last;
-  }
-#endif
 }
 
 
@@ -2882,7 +2820,6 @@ template <class K> static size_t resident_blocks(K kernel, size_t lds) {
   int per_cu = 0, n_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RB, lds) != hipSuccess || per_cu < 1) per_cu = 3;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-  if (getenv("DTSIM_DEBUG_RESIDENT")) fprintf(stderr, "[dtsim] resident_blocks: %d workgroups per CU x %d CUs (%zu B of dynamic LDS)\n", per_cu, n_cu, lds);
   return cache[key] = (size_t)per_cu * (size_t)n_cu;
 }
 
@@ -2897,7 +2834,7 @@ struct Slab {                                         // the arrays of one alloc
     bytes = off + n * sizeof(T); return base ? reinterpret_cast<T*>(base + off) : nullptr;
   }
 };
-// the arrays dt_launch_render reaches beside RenderParams; the per-position ones (EnvQ, EnvV, EnvD, EnvL: render order) move with a render part
+// the arrays dt_launch_render reaches beside RenderParams
 struct EnvRecs { EnvCam* cams; EnvFast* fasts; EnvQ* envq; EnvV* envv; EnvD* envd; EnvL* envl; PixTab* pixtab; SampTab* samptab; };
 static EnvRecs render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams& R) {
   const size_t n = (size_t)N, n_pix = (size_t)W * H, n_tiles = dt_raster_tiles(W, H), n_wg = dt_raster_groups(N, W, H);
@@ -2909,7 +2846,7 @@ static EnvRecs render_layout(int N, int W, int H, int max_tris, size_t* bytes, v
   R.envv = x.envv = env.take<EnvV>(n + 1); R.envd = x.envd = env.take<EnvD>(n); x.envl = env.take<EnvL>(n + 1);
   R.pixtab = x.pixtab = pix.take<PixTab>(n_pix); x.samptab = pix.take<SampTab>(n_pix); R.dump = pix.take<RenderDump>(1);
   R.queue = sl[DT_SLAB_QUEUE].take<uint16_t>(n_wg * (RB / 64) * QREGION);
-  R.qcount = qc.take<int32_t>(n_wg * (RB / 64)); R.dbg = qc.take<int32_t>(DT_DEBUG_INTS); R.work = qc.take<int32_t>((size_t)DT_WORK_INTS * DT_MAX_RENDER_PARTS);
+  R.qcount = qc.take<int32_t>(n_wg * (RB / 64)); R.work = qc.take<int32_t>(DT_WORK_INTS);
   R.items = it.take<uint32_t>(n_wg * ITEMS_PER_WG); R.items2 = it.take<uint32_t>(n_wg * ENVS_PER_BLOCK);   // items2: k_resolve_obj's, at most one per env of a workgroup
   R.qend = sl[DT_SLAB_QEND].take<uint16_t>(n_wg * (RB / 64) * ENVS_PER_BLOCK);
   if (max_tris > 0) {
@@ -2935,11 +2872,10 @@ int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_ol
   return (R.domain_rand || R.segment || R.light) ? DTSIM_PIPE_GENERIC_ENV : DTSIM_PIPE_GENERIC;   // the generic k_raster
 }
 
-// One range of chunks through raster `pipe` (stream s) and the exact-path kernels (stream s_res, after event ev when it is
-// another stream): the whole batch, or one of dt_launch_render's render parts (every array already moved to the range).
+// The batch through raster `pipe` and the exact-path kernels, all on stream s.
 // SUB: the masked pass -- the quad-record rasters' SUB instantiations over positions [0, live) (never the generic raster).
 template <bool SUB>
-static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t ev, const RenderParams& R, const EnvRecs& x, int pipe, bool has_pos) {
+static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const EnvRecs& x, int pipe, bool has_pos) {
   const bool obj = R.max_tris > 0, quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q;
   const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
   const size_t lds = (size_t)R.n_tile_recs * sizeof(TileLds);
@@ -2981,29 +2917,28 @@ static void launch_raster_resolve(hipStream_t s, hipStream_t s_res, hipEvent_t e
   // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region_q); generic raster:
   // k_resolve drains them (front of the queue regions).  Pixels inside mesh-object screen boxes (far end of the regions)
   // are k_resolve_obj's, after either raster.
-  if (s_res != s && (obj || !quad)) { (void)hipEventRecord(ev, s); (void)hipStreamWaitEvent(s_res, ev, 0); }
   // persistent wavefronts pulling work items: enough workgroups to fill every CU at the kernel's occupancy
   // (round 4: EXACTLY the resident workgroups -- every wavefront's first grab is static, a workgroup that waits for a slot would sit on its items)
   if (pipe == DTSIM_PIPE_V3DR) {                     // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, lds_tab)));
-    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), lds_tab, s_res, R, x.cams, x.envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
+    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), lds_tab, s, R, x.cams, x.envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
   } else if (!quad) {
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve, lds2)));
-    hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s_res, R, x.cams, R.queue, R.qcount);
+    hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s, R, x.cams, R.queue, R.qcount);
   }
   if (obj) {
     const size_t lds4 = lds + (size_t)(RB / 64) * TRI_CAP * sizeof(TriCov) + (size_t)(RB / 64) * RO_SCR_BYTES;
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_obj<DT_RES_NB>, lds4)));
-    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s_res, R, x.cams, R.queue, 1, has_pos ? x.envq : (const EnvQ*)nullptr);
+    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s, R, x.cams, R.queue, 1, has_pos ? x.envq : (const EnvQ*)nullptr);
   }
 }
 
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int pipe, int tables, const RenderOverlap* ov, const uint8_t* mask) {
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int pipe, int tables, const uint8_t* mask) {
   RenderParams R = R_in;
   tables &= 3;                                         // bit 2 (returned): this pass ran in k_env_sort's order (DTSIM_FIELD_RENDER_POS)
-  void* base[DT_SLABS] = {R.envcam, R.pixtab}; RenderParams carved{};   // each slab's first array; R keeps its own pointers (render_pass set R.dbg)
+  void* base[DT_SLABS] = {R.envcam, R.pixtab}; RenderParams carved{};   // each slab's first array; R keeps its own pointers
   const EnvRecs x = render_layout(A.N, R.W, R.H, 0, nullptr, base, carved);
-  const bool quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q, v3 = pipe == DTSIM_PIPE_V3, v3dr = pipe == DTSIM_PIPE_V3DR, obj = R.max_tris > 0;
+  const bool quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q, v3dr = pipe == DTSIM_PIPE_V3DR;
   // render order (k_env_sort): the quad pipeline indexes by position (EnvQ, object masks, queue entries); env ids come
   // from EnvQ.env
   int32_t* pos = ((quad || v3dr) && R.envpos && A.N > ENVS_PER_BLOCK) ? R.envpos : nullptr;   // one chunk: the order does not matter
@@ -3029,39 +2964,11 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in
     else hipLaunchKernelGGL(k_obj_setup<false>, dim3(A.N), dim3(DT_OBJSETUP_T), 0, s, A, R, x.cams, pos);
   }
 
-  const int n_chunks = (R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
   if (quad && !(tables & 1)) {
     hipLaunchKernelGGL(k_pix_setup, dim3((R.W * R.H + 255) / 256), dim3(256), 0, s, R, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab);
     tables |= 1;
   }
-  // Render parts (DTSIM_RENDER_PARTS = P > 1): the chunks of the batch in P ranges; the raster of range p + 1 on the
-  // caller's stream runs beside the exact-path kernels of range p on a second stream (they wait on memory, the raster on
-  // the vector ALU and the L1).  Every per-position array is addressed relative to the range's first chunk, so the
-  // kernels are the same; only the quad-record paths in the sorted render order are split (k_raster_v3, k_raster_v3dr).
-  int parts = 1;
-  if (ov && ov->parts > 1 && (v3 || v3dr) && pos && (obj || !quad) && !sub) parts = std::min(std::min(ov->parts, DT_MAX_RENDER_PARTS), n_chunks / 8);
-  if (sub) { launch_raster_resolve<true>(s, s, nullptr, R, x, pipe, true); return tables; }
-  if (parts <= 1) { launch_raster_resolve<false>(s, s, nullptr, R, x, pipe, pos != nullptr); return tables; }
-  const size_t n_tiles = dt_raster_tiles(R.W, R.H), n_blk = n_tiles * 4;
-  (void)hipMemsetAsync(R.work, 0, DT_WORK_INTS * parts * sizeof(int32_t), s);
-  for (int p = 0; p < parts; ++p) {
-    const int c0 = (int)((long long)n_chunks * p / parts), c1 = (int)((long long)n_chunks * (p + 1) / parts);
-    const size_t e0 = (size_t)c0 * ENVS_PER_BLOCK, wg0 = (size_t)c0 * n_tiles;
-    RenderParams Rp = R;
-    Rp.N = std::min(R.N, c1 * ENVS_PER_BLOCK) - (int)e0;
-    Rp.work = R.work + DT_WORK_INTS * p;
-    if (R.objmask) Rp.objmask = R.objmask + e0 * n_blk;
-    Rp.queue = R.queue + wg0 * (RB / 64) * QREGION;
-    Rp.qcount = R.qcount + wg0 * (RB / 64);
-    Rp.qend = R.qend + wg0 * (RB / 64) * ENVS_PER_BLOCK;
-    Rp.items = R.items + wg0 * ITEMS_PER_WG;
-    Rp.items2 = R.items2 + wg0 * ENVS_PER_BLOCK;
-    // per-POSITION arrays move to the range (EnvQ / EnvV / EnvD in render order, masks, queues, items above); per-ENV arrays (EnvCam, frames,
-    // screen triangles, object boxes) stay whole: the kernels reach them through the env id of the position's record
-    EnvRecs xp = x; xp.envq += e0; xp.envv += e0; xp.envd += e0; xp.envl += e0;
-    launch_raster_resolve<false>(s, ov->s2, ov->ev[p], Rp, xp, pipe, true);
-  }
-  (void)hipEventRecord(ov->ev[DT_MAX_RENDER_PARTS], ov->s2);
-  (void)hipStreamWaitEvent(s, ov->ev[DT_MAX_RENDER_PARTS], 0);
+  if (sub) launch_raster_resolve<true>(s, R, x, pipe, true);
+  else launch_raster_resolve<false>(s, R, x, pipe, pos != nullptr);
   return tables;
 }

@@ -214,10 +214,6 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
   const int rwg = chunk * n_tiles + tile;
   const int e0 = chunk * ENVS_PER_BLOCK;
-#ifdef DT_WAVE_SPANS   // experiment: wall-clock stamps of every wavefront (start, tables ready + XCC_ID, env loop done, end), tools/raster_spans.py
-  const unsigned long long span_t0 = wall_clock64();
-  unsigned long long span_t1 = 0, span_t2 = 0;
-#endif
   const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
   // the tile tables of all maps -> LDS rows: block offsets in the first half of a row, record-offset masks in the second
   // (defaults of the unused columns: record 0 = off the grid, mask 0)
@@ -239,9 +235,6 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   __syncthreads();
 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // wave index in a scalar register: block origin, queue region, LDS slices
-#ifdef DT_WAVE_SPANS
-  span_t1 = wall_clock64();                           // tile tables in LDS
-#endif
   const int bx0 = (tile % tiles_x) * DT_TILE_W + (wave % V3_WX) * DT_V3_WW;   // origin of the wavefront's block
   const int by0 = (tile / tiles_x) * DT_TILE_H + (wave / V3_WX) * V3_ROWS;
   const float lo = 0.5f * 256.f;
@@ -610,22 +603,12 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
       store(env, held);
     };
     if (mixed) run(std::true_type{}); else run(std::false_type{});
-#ifdef DT_WAVE_SPANS
-    span_t2 = wall_clock64();
-#endif
     if (lane == 0) qcount[rwg * (RB / 64) + wave] = OBJ ? qo : qn;
     if (qn > 0) {
       __builtin_amdgcn_s_waitcnt(0);                   // queue stores have left the wavefront
       resolve_region_v3<LIGHT>(R, cams, samptab, qtex, s_qt, w_queue, qn, e0, bx0, by0, lane, s_envq, envl);
     }
   }
-#ifdef DT_WAVE_SPANS
-  if (R.spans && lane == 0) {
-    unsigned long long* o = R.spans + 2 * 2048 * 4 * 8 + ((size_t)rwg * (RB / 64) + wave) * 4;
-    o[0] = span_t0; o[1] = (span_t1 - span_t0) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 32) | ((unsigned long long)(blockIdx.x & 7) << 40);
-    o[2] = span_t2; o[3] = wall_clock64();
-  }
-#endif
   if (OBJ) {
     if (lane < ENVS_PER_BLOCK) R.qend[((size_t)rwg * (RB / 64) + wave) * ENVS_PER_BLOCK + lane] = (uint16_t)qend_v;
     __shared__ envmask_t s_og[RB / 64], s_oh[RB / 64];

@@ -400,8 +400,8 @@ int dtsim_render_ex(dtsim_t* h, uint32_t flags);
  * needed there.  Frames of unselected envs are not written.  The quad-record pipelines (DTSIM_PIPE_V3, DTSIM_PIPE_Q, DTSIM_PIPE_V3DR) sort the
  * selected envs into positions [0, live) of the render order (whatever N), their setup kernels skip the others and their rasters stop at the
  * live count, so the pass costs about the selected fraction of a full one plus a fixed part (the sort, the setup launches, the workgroups
- * past the live chunks leaving at once); it never splits into render parts (DTSIM_RENDER_PARTS).  Afterwards DTSIM_FIELD_RENDER_POS reads
- * -1 for the envs that were not rendered, and dtsim_draw_lines / dtsim_draw_leds fail with DTSIM_E_STATE until a full dtsim_render.
+ * past the live chunks leaving at once).  Afterwards DTSIM_FIELD_RENDER_POS reads -1 for the envs that were not rendered, and
+ * dtsim_draw_lines / dtsim_draw_leds fail with DTSIM_E_STATE until a full dtsim_render.
  * Fallback: the generic pipelines -- segmentation, DTSIM_RENDER_GL_FILTER, the per-env camera without the quad records, tile textures or
  * tables outside the quad-record limits -- render EVERY env, as dtsim_render_ex would: an unselected env's unchanged state renders to the
  * same bytes, so its frame keeps its content; only the cost differs.  Typical use: after dtsim_step, a full pass renders the frames step()

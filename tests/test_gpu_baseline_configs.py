@@ -221,16 +221,15 @@ def test_c5_full_size_batch_matches_oracle_directly():
 
 
 @pytest.mark.parametrize("cfg", ["c5", "c4"])
-def test_render_parts_give_the_same_frames(cfg, monkeypatch):
-    """DTSIM_RENDER_PARTS (read at dtsim_create): the chunks of the batch in ranges, the exact-path kernels of one range on a second stream
-    beside the raster of the next -- every per-position array addressed relative to the range.  Same frames, bit for bit, as the one-part
-    launch: 1024 envs = 16 chunks = two parts of 8 (k_raster_v3<OBJ> in the sorted render order for C5, k_raster_v3dr for C4)."""
+def test_two_handles_render_one_state_to_the_same_bytes(cfg):
+    """Two fresh handles built from one seeded state render the same frames, bit for bit, on the mesh-object paths: 1024 envs =
+    16 chunks in the sorted render order, k_raster_v3<OBJ> + k_resolve_obj for C5, k_raster_v3dr<OBJ> + k_resolve_dr + k_resolve_obj
+    for C4 (the envs reach the raster and the persistent exact-path wavefronts in an order that differs from launch to launch)."""
     N = 1024
     kw = dict(c5=dict(maps=["loop_only_duckies", "small_loop_only_duckies"], dr=False, extra=dict(map_cycle=True)),
               c4=dict(maps="loop_pedestrians", dr=True, extra={}))[cfg]
     out = []
-    for parts in ("1", "2"):
-        monkeypatch.setenv("DTSIM_RENDER_PARTS", parts)
+    for _ in range(2):
         sim = BatchedSimulator(kw["maps"], N, camera_width=W, camera_height=H, distortion=True, domain_rand=kw["dr"], seed=5, max_steps=100000,
                                **kw["extra"])
         acts = np.random.default_rng(9).uniform(0.2, 0.9, (4, N, 2)).astype(np.float32)

@@ -1,5 +1,5 @@
-"""Time dtsim_step (physics only) for a given map / N / lanes per env (HIP events around the launches).
-    MAP=loop_pedestrians N=4096 F=32 K=20 DTSIM_STEP_LANES=4 python tools/time_step.py"""
+"""Time dtsim_step (physics only) for a given map / N (HIP events around the launches).
+    MAP=loop_pedestrians N=4096 F=32 K=20 python tools/time_step.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -25,5 +25,5 @@ for _ in range(K):
 sim.sync()
 n, ms = sim.profile_read(_ffi.KERNEL_STEP)
 us = 1e3 * ms / n / F
-print(f"map={mp} N={N} fused={F} lanes={os.environ.get('DTSIM_STEP_LANES', '1')}: {us:.2f} us per step, {N / us:.1f} M env-steps/s; "
+print(f"map={mp} N={N} fused={F}: {us:.2f} us per step, {N / us:.1f} M env-steps/s; "
       f"active duckies {int(sim.read(_ffi.FIELD_OBJ_ACTIVE).sum())}, done {int(sim.read(_ffi.FIELD_DONE).sum())}")
