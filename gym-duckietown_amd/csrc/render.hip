@@ -45,6 +45,8 @@
 //                 1/depth space, then the same shading.
 //   Segmentation render (dtsim_render_ex): same kernels on the segmented texel pool, k_cam_setup forces the unlit
 //                 state and the magenta clear / ground colour, k_obj_setup folds the mesh's flat colour into Kd.
+//   Scaffolding shared by the rasters (ahead of k_raster): the XCD-affine workgroup map and its launch size (raster_wg / raster_wg_grid), the v3 LDS
+//                 tile table fill, the chunk's object masks, the packed source-pixel centres (spxy).
 //   Host side: dt_render_layout lays out the render scratch (per-env records, per-pixel tables, queues, work lists); dt_raster_pipe picks the raster.
 //
 // Roofline: algorithmic bytes per env-step = W*H*3 (921 600 B at 640x480), written once (+ the ~1.3 % edge
@@ -1215,6 +1217,114 @@ __device__ inline envmask_t obj_groups_of(int qend_v, int lane, envmask_t* heavy
   return g;
 }
 
+// ==== scaffolding shared by the rasters ===================================================================================================
+// What every raster must agree on with the host and the exact-path kernels, stated once: the workgroup map and its launch size, the v3 LDS
+// tile table, the chunk's object masks and the packed source-pixel centres.  (The queue appends, push_obj, the four-pixel transposes and the
+// hand-over epilogues are still written out per kernel: as helpers they changed the code generated for the env loops.)  What a kernel does differently is an argument at its call site.
+
+// ---- XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr) and its launch size.
+// Workgroup b runs on XCD b % 8 (round-robin dispatch), and XCD x is given the x-th eighth of the env chunks (all frame tiles of each): with
+// the envs in k_env_sort order, one L2 serves the envs of one region of the map for the whole launch.  Within an XCD: groups of
+// dt_q_tile_group() frame tiles, all chunks of the slice for one group before the next group, so that a tile's PixTab slice (16 KB) is read
+// from HBM once per XCD instead of once per chunk, while the workgroups in flight still belong to few chunks.  The mapping only matters for speed.
+// Group size, round 6: HALF the frame (150 tiles at 640 x 480; 10 before) -- with 64 envs per workgroup the tiles of ONE chunk fill an XCD.
+// C3 - 4.6 %, C5 - 1.8 %; the whole frame as one group is + 5 ... 12 % (profiles/r06_variants_ab.txt block P).
+#ifndef DT_Q_TILE_SPLIT
+#define DT_Q_TILE_SPLIT 2
+#endif
+__host__ __device__ inline int dt_q_tile_group(int n_tiles) { return (n_tiles + DT_Q_TILE_SPLIT - 1) / DT_Q_TILE_SPLIT; }
+// launch size: 8 slices of ceil(n_chunks / 8) chunks, frame tiles in groups of dt_q_tile_group() (the last group padded); n_chunks: of all N envs, also
+// when the pass is masked (SUB: the workgroups past the live chunks leave at once)
+inline size_t raster_wg_grid(size_t n_tiles, int n_chunks) {
+  const int q_tg = dt_q_tile_group((int)n_tiles);
+  return ((n_tiles + q_tg - 1) / q_tg) * q_tg * ((n_chunks + 7) / 8) * 8;
+}
+// NL: envs of the pass; live: false for a workgroup of the grid's padding (the whole workgroup leaves, before anything else is derived);
+// rwg: the logical workgroup index (queue regions, counts, work items); [e0, e1): the chunk's positions in the render order.
+struct RasterWg {
+  int NL, tile, chunk; bool live;
+  __device__ int rwg(const int n_tiles) const { return chunk * n_tiles + tile; }
+  __device__ int e0() const { return chunk * ENVS_PER_BLOCK; }
+  __device__ int e1() const { return min(e0() + ENVS_PER_BLOCK, NL); }
+};
+// SUB: the masked pass -- positions [0, live) of k_env_sort<true>'s order, few live chunks: workgroup b takes tile b % n_tiles of chunk
+// b / n_tiles, so that every chunk's tiles spread over all eight XCDs.
+// SCALAR: tile and chunk through readfirstlane -- the divisions run on the vector ALU, and without it the env loop's counter and the per-env
+// address arithmetic of k_raster_v3 / k_raster_v3dr stay vector instructions; k_raster_q was tuned without it and keeps its form.
+template <bool SUB, bool SCALAR>
+__device__ inline RasterWg raster_wg(const RenderParams& R, const int n_tiles, const unsigned bx) {
+  RasterWg w;
+  w.NL = SUB ? dt_sub_live(R) : R.N;                 // (SUB: the live chunks)
+  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
+  const int xcd = bx & 7, bi = bx >> 3;
+  const int q_tg = dt_q_tile_group(n_tiles);
+  const int per_group = q_tg * cpx;
+  const int grp = bi / per_group, gi = bi % per_group;
+  const int g_tiles = min(q_tg, n_tiles - grp * q_tg);        // the last group may be short
+  const int tile = SUB ? (int)bx % n_tiles : grp * q_tg + gi % g_tiles;
+  w.tile = SCALAR ? __builtin_amdgcn_readfirstlane(tile) : tile;
+  const int chunk = SUB ? (int)bx / n_tiles : xcd * cpx + gi / g_tiles;
+  w.chunk = SCALAR ? __builtin_amdgcn_readfirstlane(chunk) : chunk;
+  w.live = SUB ? w.chunk < n_chunks : (gi < g_tiles * cpx && w.chunk < n_chunks);
+  return w;
+}
+
+// ---- LDS tile table of k_raster_v3 / k_raster_v3dr / k_resolve_dr: the tile tables of all maps in rows of V3_TAB_PITCH entries, block byte
+// offsets in the first half of a row, record-offset masks in the second (defaults of the unused columns: record 0 = off the grid, mask 0).
+// The caller's barrier follows.
+#define V3_TAB_PITCH 256                              // table entries per LDS row: the tile byte of Z selects the row
+#define V3_MAP_COLS 32                                // columns of one map inside a half row (padded grid width <= 32, up to 4 maps)
+__device__ inline void v3_fill_tile_table(const RenderParams& R, const uint32_t* __restrict__ qtiles, uint32_t* s_qt, const int tid) {
+  for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
+  __syncthreads();
+  for (int mi = 0; mi < R.n_maps; ++mi) {
+    const int pitch = R.maps[mi].qt_pitch, off = R.maps[mi].qt_off, n = pitch * (R.maps[mi].grid_h + 2 * DT_QRING);
+    for (int i = tid; i < n; i += RB) {
+      const int r = i / pitch, c = i - r * pitch;
+      const uint2 te = reinterpret_cast<const uint2*>(qtiles)[off + i];
+      s_qt[r * V3_TAB_PITCH + mi * V3_MAP_COLS + c] = te.x;
+      s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
+    }
+  }
+}
+
+// ---- object masks (k_obj_setup: bit o = object o's screen box meets the block) of the chunk's envs for one wavefront block.  One vector
+// load up front: lane l holds the mask of position e0 + l (a scalar load per env would sit in the same counter as the LDS reads of the env
+// loop and stall them: measured +0.4 ms); per env two v_readlane.
+template <bool OBJ>
+struct ChunkObjMasks {
+  static_assert(ENVS_PER_BLOCK <= 64, "one lane per env of the chunk");
+  uint32_t lo, hi;
+  int e0;
+  __device__ void load(const RenderParams& R, const int e0_, const int e1, const int n_blk, const int blk, const int lane) {
+    uint32_t om_lo = 0u, om_hi = 0u;
+    if (OBJ && lane < e1 - e0_) {
+      const unsigned long long v = R.objmask[(size_t)(e0_ + lane) * n_blk + blk];
+      om_lo = (uint32_t)v; om_hi = (uint32_t)(v >> 32);
+    }
+    lo = om_lo; hi = om_hi; e0 = e0_;
+  }
+  __device__ unsigned long long of(const int e) const {
+    if (!OBJ) return 0ull;
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, e - e0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lo, e - e0);
+  }
+};
+
+// ---- spxy: the source-pixel centre of a pixel (from its LUT entry) as two fp16 in one register (x | y << 16): 0.25 px rounding below
+// 1024, which the object-box margin covers.  The unpack sits behind a register barrier: it is redone per env, not hoisted ahead of the env
+// loop (8 registers).
+__device__ inline uint32_t spxy_pack(const float4& l, const int W, const int H) {
+  const float sx = (l.x + 1.f) * 0.5f * (float)W, sy = (1.f - l.y) * 0.5f * (float)H;
+  return (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
+}
+__device__ inline void spxy_unpack(uint32_t t, float& sx, float& sy) {
+  asm volatile("" : "+v"(t));
+  sx = __half2float(__ushort_as_half((unsigned short)(t & 0xFFFFu)));
+  sy = __half2float(__ushort_as_half((unsigned short)(t >> 16)));
+}
+
+struct alignas(4) U3 { uint32_t a, b, c; };           // 4 pixels x RGB: a lane's 12 bytes of a frame row
+
 template <bool DR, bool OBJ>
 __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __restrict__ cams,
                                                const EnvFast* __restrict__ fasts, uint8_t* __restrict__ frames, const uint32_t* __restrict__ texels,
@@ -1295,7 +1405,8 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
   const size_t st_off = ((size_t)st_y * R.W + st_x) * 3;
   const int tw1 = R.tex_w + 1, xmask = R.tex_w - 1, ymask = R.tex_h - 1;
 
-  // object masks of the chunk's envs for this block: one vector load, lane l <-> env e0 + l (see k_raster_q)
+  // object masks of the chunk's envs for this block: one vector load, lane l <-> env e0 + l.  (Written out, not ChunkObjMasks: with the struct
+  // the compiler assigns the registers of this kernel's env loop differently.)
   uint32_t om_lo = 0u, om_hi = 0u;
   if (OBJ && lane < e1 - e0) {
     const unsigned long long v = R.objmask[(size_t)(e0 + lane) * (n_tiles * 4) + blk];
@@ -1886,14 +1997,6 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
 #ifndef DT_Q_WAVES
 #define DT_Q_WAVES 5                                 // wavefronts per SIMD the register allocation is held to (96 VGPRs)
 #endif
-// Frame tiles per group of the launch order: an XCD takes the tiles of a group for one chunk of its slice, then for the next chunk, ..., then the next
-// group.  Round 6: HALF the frame per group (150 tiles at 640 x 480; 10 before) -- with 64 envs per workgroup the tiles of ONE chunk fill an XCD, and the
-// envs of a chunk look at one region of the map (k_env_sort): one L2 serves one region.  C3 - 4.6 %, C5 - 1.8 %; the whole frame as one group is + 5 ... 12 %
-// (profiles/r06_variants_ab.txt block P).
-#ifndef DT_Q_TILE_SPLIT
-#define DT_Q_TILE_SPLIT 2
-#endif
-__host__ __device__ inline int dt_q_tile_group(int n_tiles) { return (n_tiles + DT_Q_TILE_SPLIT - 1) / DT_Q_TILE_SPLIT; }
 #ifndef DT_Q_PRIO
 #define DT_Q_PRIO 3                                  // s_setprio level while a wavefront issues its quad loads (0: off)
 #endif
@@ -1911,26 +2014,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   const int tid = threadIdx.x;
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
-  // XCD-affine workgroup map: workgroup b runs on XCD b % 8 (round-robin dispatch), and XCD x is given the x-th
-  // eighth of the env chunks (all frame tiles of each): with the envs in k_env_sort order, one L2 serves the envs of one
-  // region of the map for the whole launch.  The mapping only matters for speed.
-  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
-  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
-  // Within an XCD: groups of dt_q_tile_group() frame tiles, all chunks of the slice for one group before the next group,
-  // so that a tile's PixTab slice (16 KB) is read from HBM once per XCD instead of once per chunk, while the workgroups
-  // in flight still belong to few chunks.
-  const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
-  const int q_tg = dt_q_tile_group(n_tiles);
-  const int per_group = q_tg * cpx;
-  const int grp = bi / per_group, gi = bi % per_group;
-  const int g_tiles = min(q_tg, n_tiles - grp * q_tg);        // the last group may be short
-  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
-  const int tile = SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles;
-  const int chunk = SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles;
-  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
-  const int rwg = chunk * n_tiles + tile;            // logical workgroup index: queue regions, counts, work items
-  const int e0 = chunk * ENVS_PER_BLOCK;             // positions in the render order
-  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
+  const RasterWg wg = raster_wg<SUB, /*SCALAR=*/false>(R, n_tiles, blockIdx.x);   // (tile and chunk stay as computed: this kernel was tuned so)
+  if (!wg.live) return;
+  const int tile = wg.tile, rwg = wg.rwg(n_tiles), e0 = wg.e0(), e1 = wg.e1();
   for (int i = tid; i < R.n_qtiles * 2; i += RB) s_qt[i] = qtiles[i];
   __syncthreads();
 
@@ -1957,11 +2043,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     valid[k] = t.lit >= 0.f; cand[k] = t.lit > 0.f; gok[k] = (t.mi & 0xFFFFu) != 0xFFFFu;
     any_cand |= cand[k];
     spxy[k] = 0u;
-    if (OBJ && inimg) {
-      const float4 l = lut[pix];
-      const float sx = (l.x + 1.f) * 0.5f * (float)R.W, sy = (1.f - l.y) * 0.5f * (float)R.H;
-      spxy[k] = (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
-    }
+    if (OBJ && inimg) spxy[k] = spxy_pack(lut[pix], R.W, R.H);
   }
 
   uint16_t* w_queue = queue + ((size_t)rwg * (RB / 64) + wave) * QREGION;
@@ -1974,19 +2056,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   const size_t st_off = ((size_t)st_y * R.W + st_x) * 3;
 
   // object masks (OBJ) are indexed by position in the render order (k_obj_setup)
-  const int n_blk = n_tiles * 4, blk = tile * 4 + __builtin_amdgcn_readfirstlane(wave);
-  // One vector load up front: lane l holds the mask of position e0 + l (a scalar load per env would sit in the same
-  // counter as the LDS reads of the env loop and stall them: measured +0.4 ms); per env two v_readlane.
-  static_assert(ENVS_PER_BLOCK <= 64, "one lane per env of the chunk");
-  uint32_t om_lo = 0u, om_hi = 0u;
-  if (OBJ && lane < e1 - e0) {
-    const unsigned long long v = R.objmask[(size_t)(e0 + lane) * n_blk + blk];
-    om_lo = (uint32_t)v; om_hi = (uint32_t)(v >> 32);
-  }
-  auto objmask_of = [&](int e) -> unsigned long long {
-    if (!OBJ) return 0ull;
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)om_hi, e - e0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)om_lo, e - e0);
-  };
+  ChunkObjMasks<OBJ> objmasks;
+  objmasks.load(R, e0, e1, n_tiles * 4, tile * 4 + __builtin_amdgcn_readfirstlane(wave), lane);
   // pixels of this block inside the screen boxes of the objects in `om` -> appended from the far end of the region
   auto push_obj = [&](const int e, const uint32_t env, unsigned long long om, bool oedge[PPT]) __attribute__((always_inline)) {
     const ObjBox* boxes = R.objbox + (size_t)env * DTSIM_MAX_OBJECTS;
@@ -1994,12 +2065,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     // box: a pixel just outside a box may take the exact path for nothing, one inside always does.
     float sx[PPT], sy[PPT];
 #pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      uint32_t t = spxy[k];
-      asm volatile("" : "+v"(t));                    // unpack here, not once ahead of the env loop (8 registers)
-      sx[k] = __half2float(__ushort_as_half((unsigned short)(t & 0xFFFFu)));
-      sy[k] = __half2float(__ushort_as_half((unsigned short)(t >> 16)));
-    }
+    for (int k = 0; k < PPT; ++k) spxy_unpack(spxy[k], sx[k], sy[k]);
     while (om) {                                     // wave-uniform
       const ObjBox ob = boxes[__builtin_ctzll(om)];
       om &= om - 1ull;
@@ -2034,7 +2100,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     const uint32_t m0 = (vm.x & 0x00FFFFFFu) | (vm.y << 24), m1 = ((vm.y >> 8) & 0xFFFFu) | (vm.z << 16), m2 = ((vm.z >> 16) & 0xFFu) | (vm.w << 8);
     for (int e = e0; e < e1; ++e) {
       const EnvQ f = envq[e];
-      const unsigned long long om = objmask_of(e);
+      const unsigned long long om = objmasks.of(e);
       if (st_ok) {
         uint32_t* d32 = reinterpret_cast<uint32_t*>(frames + (size_t)f.env * npix * 3 + st_off);
         d32[0] = f.sky[0] & m0; d32[1] = f.sky[1] & m1; d32[2] = f.sky[2] & m2;
@@ -2113,7 +2179,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
       }
     }
   };
-  struct alignas(4) U3 { uint32_t a, b, c; };
   // The lane's 12 bytes of frame e.  The store is unconditional (no branch around it, so that the wait counts the
   // compiler derives for the texel loads do not have to cover it): lanes without pixels write to a dump slot.
   uint8_t* const st_base = st_ok ? frames + st_off : reinterpret_cast<uint8_t*>(R.dump) + lane * 16;
@@ -2253,14 +2318,14 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     issue(f, sa);
     uint32_t hor = f.hor_rgb, env = f.env, env_prev;
     f = envq[min(e0 + 1, e1 - 1)];
-    U3 held = finish(e0, env, hor, sa, objmask_of(e0));
+    U3 held = finish(e0, env, hor, sa, objmasks.of(e0));
     if (OBJ) qend_v = qo;
     for (int e = e0 + 1; e < e1; ++e) {
       env_prev = env; hor = f.hor_rgb; env = f.env;
       issue(f, sa);
       store(env_prev, held);
       f = envq[min(e + 1, e1 - 1)];                  // next env's constants: the scalar load has the whole filter to land
-      held = finish(e, env, hor, sa, objmask_of(e));
+      held = finish(e, env, hor, sa, objmasks.of(e));
       if (OBJ) qend_v = lane >= e - e0 ? qo : qend_v;
     }
     store(env, held);
@@ -2273,7 +2338,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
     resolve_region_q<S256, LIGHT>(R, cams, envq, pixtab, samptab, qtex, s_qt, s_px, w_queue, qn, e0, tile_x0, wave_y0, lane, envl);
   }
   }
-  if (OBJ) {   // mesh objects: k_resolve_obj drains the object-box entries (back of the regions) -- work items for it
+  if (OBJ) {   // mesh objects: k_resolve_obj drains the object-box entries (back of the regions) -- work items for it, every env group
     if (lane < ENVS_PER_BLOCK) R.qend[((size_t)rwg * (RB / 64) + wave) * ENVS_PER_BLOCK + lane] = (uint16_t)qend_v;
     __shared__ int s_nb[RB / 64];
     if (lane == 0) s_nb[wave] = qo;
@@ -2882,9 +2947,7 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   const size_t lds1 = lds + (size_t)RB * PPT * sizeof(uint32_t);          // + store transpose
   const size_t lds2 = lds + (size_t)(RB / 64) * ENVS_PER_BLOCK * sizeof(EnvCam);
   const dim3 grid((unsigned)(dt_raster_tiles(R.W, R.H) * n_chunks));
-  // XCD-affine map: 8 slices of ceil(n_chunks / 8) chunks, frame tiles in groups of dt_q_tile_group() (the last group padded)
-  const int q_tg = dt_q_tile_group((int)dt_raster_tiles(R.W, R.H));
-  const dim3 gridq((unsigned)(((dt_raster_tiles(R.W, R.H) + q_tg - 1) / q_tg) * q_tg * ((n_chunks + 7) / 8) * 8));
+  const dim3 gridq((unsigned)raster_wg_grid(dt_raster_tiles(R.W, R.H), n_chunks));   // the quad-record rasters' XCD-affine map (raster_wg)
   const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
   const size_t lds_tab = (size_t)R.q3_rows * V3_TAB_PITCH * 4;   // the v3 kernels' LDS tile table
   const size_t lds3 = lds_tab + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // + per-wavefront buffers, the chunk's EnvQ records

@@ -1,5 +1,7 @@
 // render_v3.inc -- k_raster_v3: the quad-record one-ray path of k_raster_q on an instruction diet (included by render.hip
 // inside its anonymous namespace; shares EnvCam / EnvFast / EnvQ / PixTab / SampTab and the queue protocol with k_raster_q).
+// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"); the queue
+// appends, push_obj, the transpose and the hand-over epilogue are this kernel's own copies.
 //
 // Replaces the same reference code as k_raster_q: simulator.py:1853-1884 (tile quads, GL_LINEAR / GL_REPEAT),
 // simulator.py:1806-1812 (ground quad), graphics.py:172-251 (4x MSAA resolve), distortion.py:85-125 (remap, folded in).
@@ -39,8 +41,6 @@
 static_assert(PPT == 4 && DT_V3_WW == 128 && DT_V3_WW == WAVE_W && DT_TILE_W % DT_V3_WW == 0 && (RB / 64) % V3_WX == 0 &&
               V3_ROWS * ((RB / 64) / V3_WX) == DT_TILE_H, "k_raster_v3 / k_raster_v3dr: 128 x 2 wavefront blocks tiling the 128 x 8 workgroup tile "
               "(the generic k_resolve / k_resolve_obj decode the queue entries as row-major pixel numbers of such a block)");
-#define V3_TAB_PITCH 256                              // table entries per LDS row: the tile byte of Z selects the row
-#define V3_MAP_COLS 32                                // columns of one map inside a half row (padded grid width <= 32, up to 4 maps)
 #define V3_MAX_ROWS 24                                // padded grid height <= 24 (24 KB of LDS)
 #define V3_SEL_TILE 0x0c0c0602u                       // v_perm: (byte 2 of Z) << 8 | byte 2 of X -- the tile bytes of the snapped coordinates (Q8_SNAP)
 #define V3_WAVE_LDS RQ_LIST                           // dwords of LDS per wavefront: the transpose buffer
@@ -59,7 +59,6 @@ static_assert(DT_V3_WW == 4 * DT_V3_SW && 64 % DT_V3_SW == 0, "four slots side b
 #define V3_XO3B "290"
 #define V3_ROW16 (DT_V3_WW * 3 / 16)                  // 16-byte pieces of a block row
 
-struct alignas(4) U3 { uint32_t a, b, c; };           // 4 pixels x RGB
 struct U4 { uint32_t a, b, c, d; };                   // k_raster_v3's row fragment: 16 bytes on 48 lanes (12 bytes, d unused, when the image is not a whole number of blocks wide)
 #define V3_XPOSE_WAIT " s_waitcnt lgkmcnt(0)"
 
@@ -198,36 +197,10 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const int tid = threadIdx.x;
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
-  // XCD-affine workgroup map, as k_raster_q
-  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
-  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
-  const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
-  const int q_tg = dt_q_tile_group(n_tiles);
-  const int per_group = q_tg * cpx;
-  const int grp = bi / per_group, gi = bi % per_group;
-  const int g_tiles = min(q_tg, n_tiles - grp * q_tg);
-  // (the divisions run on the vector ALU: bring the wave-uniform results back to scalar registers, or the env loop's
-  // counter and the EnvQ address arithmetic stay vector instructions)
-  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
-  const int tile = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles);
-  const int chunk = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles);
-  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
-  const int rwg = chunk * n_tiles + tile;
-  const int e0 = chunk * ENVS_PER_BLOCK;
-  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
-  // the tile tables of all maps -> LDS rows: block offsets in the first half of a row, record-offset masks in the second
-  // (defaults of the unused columns: record 0 = off the grid, mask 0)
-  for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
-  __syncthreads();
-  for (int mi = 0; mi < R.n_maps; ++mi) {
-    const int pitch = R.maps[mi].qt_pitch, off = R.maps[mi].qt_off, n = pitch * (R.maps[mi].grid_h + 2 * DT_QRING);
-    for (int i = tid; i < n; i += RB) {
-      const int r = i / pitch, c = i - r * pitch;
-      const uint2 te = reinterpret_cast<const uint2*>(qtiles)[off + i];
-      s_qt[r * V3_TAB_PITCH + mi * V3_MAP_COLS + c] = te.x;
-      s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
-    }
-  }
+  const RasterWg wg = raster_wg<SUB, /*SCALAR=*/true>(R, n_tiles, blockIdx.x);   // (tile and chunk in scalar registers: the env loop's counter and the EnvQ addresses follow)
+  if (!wg.live) return;
+  const int NL = wg.NL, tile = wg.tile, rwg = wg.rwg(n_tiles), e0 = wg.e0(), e1 = wg.e1();
+  v3_fill_tile_table(R, qtiles, s_qt, tid);
   // the EnvQ records of the chunk's positions (the exact path reads them per entry: resolve_region_v3), 16 bytes per thread
   uint4* s_envq = reinterpret_cast<uint4*>(s_mem + R.q3_rows * V3_TAB_PITCH + (RB / 64) * V3_WAVE_LDS);
   static_assert(ENVS_PER_BLOCK * 4 <= RB, "one 16-byte piece per thread");
@@ -253,11 +226,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
     lr[k] = t.lr; lf[k] = t.lf; lit[k] = fmaxf(t.lit, 0.f) * Q8_LIT; Mi[k] = t.mi;   // lit / 256: the fractions below are bytes (quad_weights8)
     valid[k] = t.lit >= 0.f; cand[k] = t.lit > 0.f; gok[k] = (t.mi & 0xFFFFu) != 0xFFFFu;
     spxy[k] = 0u;
-    if (OBJ && inimg) {
-      const float4 l = lut[y * R.W + x];
-      const float sx = (l.x + 1.f) * 0.5f * (float)R.W, sy = (1.f - l.y) * 0.5f * (float)R.H;
-      spxy[k] = (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
-    }
+    if (OBJ && inimg) spxy[k] = spxy_pack(lut[y * R.W + x], R.W, R.H);
   }
   bool any_cand = false;
 #pragma unroll
@@ -272,17 +241,8 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const bool st_ok = st_x < R.W && st_y < R.H;       // W % 4 == 0 (launch precondition): all four pixels or none
   const size_t st_off = ((size_t)st_y * R.W + st_x) * 3;
 
-  const int n_blk = n_tiles * 4, blk = tile * 4 + wave;
-  static_assert(ENVS_PER_BLOCK <= 64, "one lane per env of the chunk");
-  uint32_t om_lo = 0u, om_hi = 0u;
-  if (OBJ && lane < e1 - e0) {
-    const unsigned long long v = R.objmask[(size_t)(e0 + lane) * n_blk + blk];
-    om_lo = (uint32_t)v; om_hi = (uint32_t)(v >> 32);
-  }
-  auto objmask_of = [&](int e) -> unsigned long long {
-    if (!OBJ) return 0ull;
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)om_hi, e - e0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)om_lo, e - e0);
-  };
+  ChunkObjMasks<OBJ> objmasks;
+  objmasks.load(R, e0, e1, n_tiles * 4, tile * 4 + wave, lane);
   // pixels of the block inside the screen boxes of the objects in `om` -> appended from the far end of the region; oem[k]: their lanes
   auto push_obj = [&](const int e, const uint32_t env, unsigned long long om, unsigned long long oem[PPT], const unsigned long long em[PPT]) __attribute__((always_inline)) {
     const ObjBox* boxes = R.objbox + (size_t)env * DTSIM_MAX_OBJECTS;
@@ -294,12 +254,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
     const float obj_mrg = (R.W > 2048 || R.H > 2048) ? 0.95f : (R.W > 1024 || R.H > 1024) ? 0.45f : 0.3f;
     float sx[PPT], sy[PPT];
 #pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      uint32_t t = spxy[k];
-      asm volatile("" : "+v"(t));
-      sx[k] = __half2float(__ushort_as_half((unsigned short)(t & 0xFFFFu)));
-      sy[k] = __half2float(__ushort_as_half((unsigned short)(t >> 16)));
-    }
+    for (int k = 0; k < PPT; ++k) spxy_unpack(spxy[k], sx[k], sy[k]);
     while (om) {                                     // wave-uniform
       const int o = __builtin_ctzll(om);
       const ObjBox ob = boxes[o];
@@ -387,7 +342,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
     }
     for (int e = e0; e < e1; ++e) {
       const EnvV f = envv[e];
-      const unsigned long long om = objmask_of(e);
+      const unsigned long long om = objmasks.of(e);
       const uint32_t s0 = __builtin_amdgcn_perm(f.hor_rgb, f.hor_rgb, hsel[0]), s1 = __builtin_amdgcn_perm(f.hor_rgb, f.hor_rgb, hsel[1]),
                      s2 = __builtin_amdgcn_perm(f.hor_rgb, f.hor_rgb, hsel[2]), s3 = __builtin_amdgcn_perm(f.hor_rgb, f.hor_rgb, hsel[3]);
       if (OBJ && om) {                                 // wave-uniform: objects in front of the sky only add queue entries (the sky pixel is final unless covered)
@@ -590,14 +545,14 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
       issue(f, sa);
       uint32_t hor = f.hor_rgb, env = f.env, env_prev;
       f = fp[1]; ++fp;
-      U4 held = finish(e0, env, hor, sa, objmask_of(e0), mixed_tag);
+      U4 held = finish(e0, env, hor, sa, objmasks.of(e0), mixed_tag);
       if (OBJ) qend_v = qo;
       for (int e = e0 + 1; e < e1; ++e) {
         env_prev = env; hor = f.hor_rgb; env = f.env;
         issue(f, sa);
         store(env_prev, held);
         f = fp[1]; ++fp;
-        held = finish(e, env, hor, sa, objmask_of(e), mixed_tag);
+        held = finish(e, env, hor, sa, objmasks.of(e), mixed_tag);
         if (OBJ) qend_v = lane >= e - e0 ? qo : qend_v;
       }
       store(env, held);

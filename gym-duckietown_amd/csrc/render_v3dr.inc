@@ -1,5 +1,7 @@
 // render_v3dr.inc -- k_raster_v3dr: domain randomisation (per-env camera, light, colours) on the quad records of
 // k_raster_v3 (included by render.hip inside its anonymous namespace, after render_v3.inc).
+// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"); the queue
+// appends, push_obj, the transpose and the hand-over epilogue are this kernel's own copies.
 //
 // Reference: simulator.py:565-614 (the per-reset camera / light / colour perturbations), :1761-1803 (projection and
 // model-view per env), :1853-1884 (tile quads, GL_LINEAR / GL_REPEAT), graphics.py:172-251 (4x MSAA).
@@ -122,34 +124,10 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
   const int tid = threadIdx.x;
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
-  // XCD-affine workgroup map, as k_raster_v3 (round 5): workgroup b runs on XCD b % 8, XCD x owns the x-th eighth of the chunks of the
-  // render order (envs standing on one region of the map: one L2 serves them), the frame tiles dt_q_tile_group() at a time.
-  // rwg = chunk * n_tiles + tile names the workgroup's queue regions / work items, as everywhere.
-  const int NL = SUB ? dt_sub_live(R) : R.N;         // (SUB: the live chunks)
-  const int n_chunks = (NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
-  const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
-  const int q_tg = dt_q_tile_group(n_tiles);
-  const int per_group = q_tg * cpx;
-  const int grp = bi / per_group, gi = bi % per_group;
-  const int g_tiles = min(q_tg, n_tiles - grp * q_tg);
-  // SUB: few live chunks -- workgroup b takes tile b % n_tiles of chunk b / n_tiles, so that every chunk's tiles spread over all eight XCDs
-  const int tile = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x % n_tiles : grp * q_tg + gi % g_tiles);
-  const int chunk = __builtin_amdgcn_readfirstlane(SUB ? (int)blockIdx.x / n_tiles : xcd * cpx + gi / g_tiles);
-  if (SUB ? chunk >= n_chunks : (gi >= g_tiles * cpx || chunk >= n_chunks)) return;   // padding workgroups (whole workgroup)
-  const int rwg = chunk * n_tiles + tile;
-  const int e0 = chunk * ENVS_PER_BLOCK;
-  const int e1 = min(e0 + ENVS_PER_BLOCK, NL);
-  for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
-  __syncthreads();
-  for (int mi = 0; mi < R.n_maps; ++mi) {
-    const int pitch = R.maps[mi].qt_pitch, off = R.maps[mi].qt_off, n = pitch * (R.maps[mi].grid_h + 2 * DT_QRING);
-    for (int i = tid; i < n; i += RB) {
-      const int r = i / pitch, c = i - r * pitch;
-      const uint2 te = reinterpret_cast<const uint2*>(qtiles)[off + i];
-      s_qt[r * V3_TAB_PITCH + mi * V3_MAP_COLS + c] = te.x;
-      s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
-    }
-  }
+  const RasterWg wg = raster_wg<SUB, /*SCALAR=*/true>(R, n_tiles, blockIdx.x);   // (tile and chunk in scalar registers: the env loop's counter and the EnvD addresses follow)
+  if (!wg.live) return;
+  const int tile = wg.tile, rwg = wg.rwg(n_tiles), e0 = wg.e0(), e1 = wg.e1();
+  v3_fill_tile_table(R, qtiles, s_qt, tid);
   __syncthreads();
 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -172,10 +150,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
     const bool ok = l.z != 0.f;
     nx[k] = ok ? l.x : __builtin_nanf(""); ny[k] = ok ? l.y : __builtin_nanf("");
     spxy[k] = 0x7E007E00u;
-    if (OBJ && ok) {
-      const float sx = (l.x + 1.f) * 0.5f * (float)R.W, sy = (1.f - l.y) * 0.5f * (float)R.H;
-      spxy[k] = (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
-    }
+    if (OBJ && ok) spxy[k] = spxy_pack(l, R.W, R.H);
   }
   f2 nx2[PPT / 2], ny2[PPT / 2];
 #pragma unroll
@@ -205,16 +180,8 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
     return U3{__builtin_amdgcn_perm(o.y, o.x, 0x04020100u), __builtin_amdgcn_perm(o.z, o.y, 0x05040201u), __builtin_amdgcn_perm(o.w, o.z, 0x06050402u)};
   };
 
-  const int n_blk = n_tiles * 4, blk = tile * 4 + wave;
-  uint32_t om_lo = 0u, om_hi = 0u;
-  if (OBJ && lane < e1 - e0) {
-    const unsigned long long v = R.objmask[(size_t)(e0 + lane) * n_blk + blk];
-    om_lo = (uint32_t)v; om_hi = (uint32_t)(v >> 32);
-  }
-  auto objmask_of = [&](int e) -> unsigned long long {
-    if (!OBJ) return 0ull;
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)om_hi, e - e0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)om_lo, e - e0);
-  };
+  ChunkObjMasks<OBJ> objmasks;
+  objmasks.load(R, e0, e1, n_tiles * 4, tile * 4 + wave, lane);
   auto push_obj = [&](const int e, const uint32_t env, unsigned long long om, unsigned long long oem[PPT], const unsigned long long em[PPT]) __attribute__((always_inline)) {
     const ObjBox* boxes = R.objbox + (size_t)env * DTSIM_MAX_OBJECTS;
     bool oedge[PPT];
@@ -224,10 +191,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       oedge[k] = false;
-      uint32_t t = spxy[k];
-      asm volatile("" : "+v"(t));
-      sx[k] = __half2float(__ushort_as_half((unsigned short)(t & 0xFFFFu)));
-      sy[k] = __half2float(__ushort_as_half((unsigned short)(t >> 16)));
+      spxy_unpack(spxy[k], sx[k], sy[k]);
     }
     while (om) {                                     // wave-uniform
       const int o = __builtin_ctzll(om);
@@ -256,7 +220,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
   U3 held{0u, 0u, 0u};
   uint32_t env_held = 0u;
   for (int e = e0; e < e1; ++e) {
-    const unsigned long long om = objmask_of(e);
+    const unsigned long long om = objmasks.of(e);
     uint4 q[PPT];
     f2 ax2[PPT / 2], az2[PPT / 2], inv2[PPT / 2], den2[PPT / 2], X2[PPT / 2], Z2[PPT / 2];
     const f2 vna1 = f2{g.na1, g.na1}, vsth = f2{g.sth, g.sth};
@@ -421,7 +385,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
     if (OBJ) qend_v = lane >= e - e0 ? qo : qend_v;
   }
   store(env_held, held);
-  // hand-over to k_resolve (plane-edge entries, front of the regions) and k_resolve_obj (object-box entries, back): as k_raster
+  // hand-over: the plane-edge entries (front of the regions) to k_resolve_dr, the object-box entries (back) to k_resolve_obj, by env group
   if (lane == 0) qcount[rwg * (RB / 64) + wave] = qn;
   if (OBJ && lane < ENVS_PER_BLOCK) R.qend[((size_t)rwg * (RB / 64) + wave) * ENVS_PER_BLOCK + lane] = (uint16_t)qend_v;
   __shared__ int s_nb[RB / 64];
@@ -471,17 +435,7 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
   const int wave = tid >> 6, lane = tid & 63;
-  for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
-  __syncthreads();
-  for (int mi = 0; mi < R.n_maps; ++mi) {
-    const int pitch = R.maps[mi].qt_pitch, off = R.maps[mi].qt_off, n = pitch * (R.maps[mi].grid_h + 2 * DT_QRING);
-    for (int i = tid; i < n; i += RB) {
-      const int r = i / pitch, c = i - r * pitch;
-      const uint2 te = reinterpret_cast<const uint2*>(qtiles)[off + i];
-      s_qt[r * V3_TAB_PITCH + mi * V3_MAP_COLS + c] = te.x;
-      s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
-    }
-  }
+  v3_fill_tile_table(R, qtiles, s_qt, tid);
   __syncthreads();
   const char* qtb = reinterpret_cast<const char*>(s_qt);
   const float lo = 0.5f * 256.f;

@@ -15,6 +15,7 @@ PIPELINES = {
     "v3_light": ("small_loop", dict(domain_rand=False, light_capture=True), {}, "k_raster_v3+light", None),
     "v3_obj": ("small_loop_only_duckies", dict(domain_rand=False), {}, "k_raster_v3", None),
     "q": ("small_loop", dict(domain_rand=False), {}, "k_raster_q", "1"),
+    "q_obj": ("small_loop_only_duckies", dict(domain_rand=False), {}, "k_raster_q", "1"),
     "v3dr": ("small_loop", dict(domain_rand=True), {}, "k_raster_v3dr", None),
     "v3dr_obj": ("small_loop_only_duckies", dict(domain_rand=True), {}, "k_raster_v3dr", None),
     "generic_segment": ("small_loop_only_duckies", dict(domain_rand=False), dict(segment=True), "k_raster_env", None),
