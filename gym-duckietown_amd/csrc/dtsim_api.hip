@@ -79,6 +79,12 @@ hipError_t dev_grow(DevPtr<T>& buf, size_t n, hipStream_t s) {
   return e;
 }
 
+// The plan of the last observation resize of one kind and the device copy of its tables, kept while the next call brings the same tables.
+struct ObserveSlot {
+  ObservePlan plan;
+  DevPtr<int32_t> d_tab;
+};
+
 }  // namespace
 
 struct dtsim {
@@ -156,13 +162,7 @@ struct dtsim {
   float q_per_m = 0.f;
   DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
   int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
-  DevPtr<int32_t> d_obsc_tab;     // dtsim_observe_cubic tables (device copy of obsc_tab)
-  std::vector<int32_t> obsc_tab;
-  DevPtr<int32_t> d_obs_tab;      // dtsim_observe resampling tables (device copy of obs_tab)
-  std::vector<int32_t> obs_tab;   // the cache key: output size, tap counts and the caller's tables
-  int obs_h = 0, obs_w = 0, obs_kx = 0, obs_ky = 0, obs_rpb = 0, obs_rows_in = 0;
-  size_t obs_off_by = 0;
-  ObserveParams obs_fast{};       // the power-of-two fast-path fields of the cached tables (hfast .. vw)
+  ObserveSlot obs, obsc;          // dtsim_observe / dtsim_observe_cubic (and their masked forms)
   int max_tris = 0;
   int n_tilerecs = 0, tex_w = 1, tex_h = 1;
   DevPtr<ObjInstDev> d_robjs;
@@ -1092,182 +1092,63 @@ int dtsim_allgather_frames(dtsim_t* h, void* nccl_comm, void* recv, const void* 
   return DTSIM_OK;
 }
 
-static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
-                        const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
-                        const int32_t* bounds_y, const int32_t* taps_y, int ksize_y);
+// The shared body of the four observation entry points.  cubic: dtsim_observe_cubic's tables (first_x / taps_x / first_y / taps_y, four taps)
+// into h->obsc, else dtsim_observe's into h->obs; mask: the masked forms' device mask, or null for every env.
+static int observe_run(dtsim_t* h, bool cubic, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
+                       const int32_t* bounds_x, const int32_t* taps_x, int ksize_x, const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
+  if (!h || !out) return fail(DTSIM_E_INVALID, "bad argument");
+  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  const int W = h->cfg.cam_width, H = h->cfg.cam_height;
+  ObserveSlot& slot = cubic ? h->obsc : h->obs;
+  ObservePlan next;
+  std::string err;
+  int rc = cubic ? dt_observe_pack_cubic(next, err, W, H, h->N, out_h, out_w, bounds_x, taps_x, bounds_y, taps_y)
+                 : dt_observe_pack(next, err, W, H, h->N, out_h, out_w, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
+  if (rc != DTSIM_OK) return fail(rc, "%s", err.c_str());
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!slot.d_tab || !next.same_tables(slot.plan)) {
+    // other tables than the slot's (the same output size may come with other tables): plan them -- the A/B switches are read here,
+    // once per plan -- and replace the slot only when all of it succeeded
+    rc = cubic ? dt_observe_plan_cubic(next, err)
+               : dt_observe_plan(next, err, getenv("DTSIM_OBSERVE_STAGED") != nullptr, getenv("DTSIM_OBSERVE_GENERIC") != nullptr);
+    if (rc != DTSIM_OK) return fail(rc, "%s", err.c_str());
+    HIPCHK(hipStreamSynchronize(h->stream));         // the stream may still read the old tables
+    HIPCHK(dev_upload(slot.d_tab, next.tab.data(), next.tab.size()));
+    slot.plan = std::move(next);
+  }
+  const ObservePlan& plan = slot.plan;
+  ObserveParams P = plan.P;
+  P.chw = (flags & DTSIM_OBS_CHW) ? 1 : 0; P.f32 = (flags & DTSIM_OBS_F32) ? 1 : 0;
+  P.frames = h->frames; P.out = out;
+  const int32_t* tab = slot.d_tab.get();
+  P.bx = tab + plan.off_bx; P.kkx = tab + plan.off_kkx; P.by = tab + plan.off_by; P.kky = tab + plan.off_kky;
+  {
+    ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
+    dt_launch_observe(h->stream, plan, P, mask);
+  }
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
 int dtsim_observe(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                   const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
                   const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
-  return observe_pass(h, out, out_h, out_w, flags, nullptr, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
+  return observe_run(h, false, out, out_h, out_w, flags, nullptr, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
 }
 int dtsim_observe_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
                          const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
                          const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
   if (!mask) return fail(DTSIM_E_INVALID, "dtsim_observe_masked: null mask");
-  return observe_pass(h, out, out_h, out_w, flags, mask, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
+  return observe_run(h, false, out, out_h, out_w, flags, mask, bounds_x, taps_x, ksize_x, bounds_y, taps_y, ksize_y);
 }
-
-// mask: dtsim_observe_masked's device mask, or null for every env
-static int observe_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
-                        const int32_t* bounds_x, const int32_t* taps_x, int ksize_x,
-                        const int32_t* bounds_y, const int32_t* taps_y, int ksize_y) {
-  if (!h || !out) return fail(DTSIM_E_INVALID, "bad argument");
-  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
-  const int W = h->cfg.cam_width, H = h->cfg.cam_height;
-  if (out_h <= 0 || out_w <= 0) return fail(DTSIM_E_INVALID, "output size %dx%d", out_w, out_h);
-  if ((out_w != W && (!bounds_x || !taps_x || ksize_x <= 0)) || (out_h != H && (!bounds_y || !taps_y || ksize_y <= 0)))
-    return fail(DTSIM_E_INVALID, "resampling tables missing for a resized axis");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // tables: [bx | kkx | by | kky] in one device buffer, re-sent (and the fast paths re-derived) when they differ from the
-  // cached ones -- the same output size may come with other tables
-  std::vector<int32_t> tab;
-  std::vector<int32_t> by(2 * (size_t)out_h);
-  if (out_w != W) { tab.insert(tab.end(), bounds_x, bounds_x + 2 * (size_t)out_w); tab.insert(tab.end(), taps_x, taps_x + (size_t)out_w * ksize_x); }
-  else ksize_x = 0;
-  const size_t off_by = tab.size();
-  if (out_h != H) for (int i = 0; i < 2 * out_h; ++i) by[i] = bounds_y[i];
-  else { for (int i = 0; i < out_h; ++i) { by[2 * i] = i; by[2 * i + 1] = 1; } ksize_y = 0; }
-  tab.insert(tab.end(), by.begin(), by.end());
-  if (out_h != H) tab.insert(tab.end(), taps_y, taps_y + (size_t)out_h * ksize_y);
-  if (h->obs_h != out_h || h->obs_w != out_w || h->obs_kx != ksize_x || h->obs_ky != ksize_y || tab != h->obs_tab || !h->d_obs_tab) {
-    for (int i = 0; i < out_h; ++i)
-      if (by[2 * i] < 0 || by[2 * i + 1] <= 0 || by[2 * i] + by[2 * i + 1] > H || (i && by[2 * i] < by[2 * i - 2]))
-        return fail(DTSIM_E_INVALID, "bounds_y[%d] = (%d, %d) out of range / not monotone", i, by[2 * i], by[2 * i + 1]);
-    if (out_w != W)
-      for (int i = 0; i < out_w; ++i)
-        if (bounds_x[2 * i] < 0 || bounds_x[2 * i + 1] <= 0 || bounds_x[2 * i + 1] > ksize_x || bounds_x[2 * i] + bounds_x[2 * i + 1] > W)
-          return fail(DTSIM_E_INVALID, "bounds_x[%d] = (%d, %d) out of range", i, bounds_x[2 * i], bounds_x[2 * i + 1]);
-    if (out_h != H)
-      for (int i = 0; i < out_h; ++i) if (by[2 * i + 1] > ksize_y) return fail(DTSIM_E_INVALID, "bounds_y[%d] count > ksize_y", i);
-    // rows per workgroup: as many output rows as keep the uint8 intermediate (+ staging) within 48 KB of LDS
-    const size_t stage = DT_OBS_STAGE_ROWS * (((size_t)W * 3 + 3) / 4) * 4 + 32, tabs = (out_w != W && ksize_x <= 9) ? (size_t)out_w * 11 * 4 : 0;
-    const size_t budget = DT_OBS_LDS_KB * 1024 - stage - tabs - 32;
-    const int max_rows = (int)std::min<size_t>((size_t)H, budget / ((size_t)out_w * 3));
-    int rpb = 0, need = 0;
-    for (int cand = 1; cand <= out_h; ++cand) {
-      int worst = 0;
-      for (int o0 = 0; o0 < out_h; o0 += cand) {
-        const int o1 = std::min(o0 + cand, out_h) - 1;
-        worst = std::max(worst, by[2 * o1] + by[2 * o1 + 1] - by[2 * o0]);
-      }
-      if (worst > max_rows) break;
-      rpb = cand; need = worst;
-      if (cand >= DT_OBS_MAX_RPB) break;            // enough rows per workgroup; keep the grid large
-    }
-    if (rpb == 0) return fail(DTSIM_E_LIMIT, "observation %dx%d: one output row needs more input rows than fit in LDS", out_w, out_h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(dev_upload(h->d_obs_tab, tab.data(), tab.size()));
-    h->obs_tab = tab; h->obs_off_by = off_by;
-    h->obs_h = out_h; h->obs_w = out_w; h->obs_kx = ksize_x; h->obs_ky = ksize_y; h->obs_rpb = rpb; h->obs_rows_in = need;
-    // power-of-two down-scaling: interior columns / rows with identical small-integer taps (k_observe's dot4 / two-lane paths)
-    h->obs_fast = ObserveParams{};
-    auto uniform = [&](const int32_t* bounds, const int32_t* taps, int ksize, int n_in, int n_out, int S, uint32_t* w, int* sh) -> bool {
-      if (n_out < 3 || n_out * S != n_in || 2 * S > ksize || 2 * S > 16) return false;
-      const int32_t* k1 = taps + (size_t)1 * ksize;
-      int common = 22;                                  // trailing zero bits shared by the taps of column 1
-      for (int t = 0; t < 2 * S; ++t) { if (k1[t] <= 0) return false; common = std::min(common, __builtin_ctz((unsigned)k1[t])); }
-      long long sum = 0;
-      for (int t = 0; t < 2 * S; ++t) { const int q = k1[t] >> common; if (q > 255) return false; w[t] = (uint32_t)q; sum += q; }
-      if (sum != (1ll << (22 - common)) || 22 - common < 1 || 22 - common > 7) return false;   // two-lane sums must stay below 2^16
-      for (int o = 1; o < n_out - 1; ++o) {
-        if (bounds[2 * o] != S * o - S / 2 || bounds[2 * o + 1] != 2 * S) return false;
-        for (int t = 0; t < 2 * S; ++t) if (taps[(size_t)o * ksize + t] != k1[t]) return false;
-      }
-      *sh = 22 - common;
-      return true;
-    };
-    if (out_w != W && ((size_t)W * 3) % 4 == 0) {
-      for (int S : {4, 8}) {
-        uint32_t w[16]; int sh = 0;
-        if (!uniform(bounds_x, taps_x, ksize_x, W, out_w, S, w, &sh)) continue;
-        ObserveParams& F = h->obs_fast;
-        F.hfast = S; F.hsh = sh;
-        const int start = -3 * S / 2;                  // first byte of a column's window relative to 3 S ox
-        F.hoff = start & ~3;                           // (two's complement: rounds towards minus infinity)
-        F.hn = (3 * 2 * S + (start - F.hoff) + 3) / 4;
-        if (F.hn != 7 && F.hn != 12) { F.hfast = 0; continue; }
-        for (int b = 0; b < 3 * 2 * S; ++b) {
-          const int p = b + (start - F.hoff);
-          F.hw[b % 3][p / 4] |= w[b / 3] << (8 * (p % 4));
-        }
-        break;
-      }
-    }
-    if (out_h != H && ((size_t)out_w * 3) % 4 == 0) {
-      for (int S : {2, 4, 8}) {
-        uint32_t w[16]; int sh = 0;
-        if (!uniform(by.data(), taps_y, ksize_y, H, out_h, S, w, &sh)) continue;
-        h->obs_fast.vfast = S; h->obs_fast.vsh = sh;
-        for (int t = 0; t < 2 * S; ++t) h->obs_fast.vw[t] = w[t];
-        break;
-      }
-    }
-    if (getenv("DTSIM_OBSERVE_GENERIC")) h->obs_fast = ObserveParams{};   // A/B switch: the table-driven paths only
-  }
-  ObserveParams P{};
-  P.N = h->N; P.H = H; P.W = W; P.oh = out_h; P.ow = out_w; P.kx = h->obs_kx; P.ky = h->obs_ky;
-  P.rows_per_block = h->obs_rpb; P.max_rows_in = h->obs_rows_in;
-  P.chw = (flags & DTSIM_OBS_CHW) ? 1 : 0; P.f32 = (flags & DTSIM_OBS_F32) ? 1 : 0;
-  P.frames = h->frames; P.out = out;
-  P.bx = h->d_obs_tab.get(); P.kkx = P.bx + (out_w != W ? 2 * (size_t)out_w : 0);
-  P.by = P.bx + h->obs_off_by; P.kky = P.by + 2 * (size_t)out_h;
-  P.hfast = h->obs_fast.hfast; P.hn = h->obs_fast.hn; P.hoff = h->obs_fast.hoff; P.hsh = h->obs_fast.hsh;
-  P.vfast = h->obs_fast.vfast; P.vsh = h->obs_fast.vsh;
-  memcpy(P.hw, h->obs_fast.hw, sizeof P.hw); memcpy(P.vw, h->obs_fast.vw, sizeof P.vw);
-  {
-    ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
-    dt_launch_observe(h->stream, P, mask);
-  }
-  HIPCHK(hipGetLastError());
-  return DTSIM_OK;
-}
-
-static int observe_cubic_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
-                              const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y);
 int dtsim_observe_cubic(dtsim_t* h, void* out, int out_h, int out_w, int flags,
                         const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
-  return observe_cubic_pass(h, out, out_h, out_w, flags, nullptr, first_x, taps_x, first_y, taps_y);
+  return observe_run(h, true, out, out_h, out_w, flags, nullptr, first_x, taps_x, 4, first_y, taps_y, 4);
 }
 int dtsim_observe_cubic_masked(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
                                const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
   if (!mask) return fail(DTSIM_E_INVALID, "dtsim_observe_cubic_masked: null mask");
-  return observe_cubic_pass(h, out, out_h, out_w, flags, mask, first_x, taps_x, first_y, taps_y);
-}
-
-static int observe_cubic_pass(dtsim_t* h, void* out, int out_h, int out_w, int flags, const uint8_t* mask,
-                              const int32_t* first_x, const int32_t* taps_x, const int32_t* first_y, const int32_t* taps_y) {
-  if (!h || !out || !first_x || !taps_x || !first_y || !taps_y) return fail(DTSIM_E_INVALID, "bad argument");
-  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
-  const int W = h->cfg.cam_width, H = h->cfg.cam_height;
-  if (out_h <= 0 || out_w <= 0) return fail(DTSIM_E_INVALID, "output size %dx%d", out_w, out_h);
-  if ((size_t)W * 3 * sizeof(int32_t) + 16 > 64 * 1024) return fail(DTSIM_E_LIMIT, "frame rows of %d pixels do not fit the kernel's LDS row", W);
-  for (int i = 0; i < out_w; ++i)
-    if (first_x[i] < -3 || first_x[i] >= W) return fail(DTSIM_E_INVALID, "first_x[%d] = %d out of range", i, first_x[i]);
-  for (int i = 0; i < out_h; ++i)
-    if (first_y[i] < -3 || first_y[i] >= H) return fail(DTSIM_E_INVALID, "first_y[%d] = %d out of range", i, first_y[i]);
-  for (size_t i = 0; i < 4 * (size_t)out_w; ++i) if (taps_x[i] < -32768 || taps_x[i] > 32767) return fail(DTSIM_E_INVALID, "taps_x[%zu] is not a 16-bit tap", i);
-  for (size_t i = 0; i < 4 * (size_t)out_h; ++i) if (taps_y[i] < -32768 || taps_y[i] > 32767) return fail(DTSIM_E_INVALID, "taps_y[%zu] is not a 16-bit tap", i);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  // tables: [first_x | taps_x | first_y | taps_y] in one device buffer, re-sent when they differ from the cached ones
-  std::vector<int32_t> tab;
-  tab.insert(tab.end(), first_x, first_x + out_w); tab.insert(tab.end(), taps_x, taps_x + 4 * (size_t)out_w);
-  tab.insert(tab.end(), first_y, first_y + out_h); tab.insert(tab.end(), taps_y, taps_y + 4 * (size_t)out_h);
-  if (tab != h->obsc_tab || !h->d_obsc_tab) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(dev_upload(h->d_obsc_tab, tab.data(), tab.size()));
-    h->obsc_tab = tab;
-  }
-  ObserveParams P{};
-  P.N = h->N; P.H = H; P.W = W; P.oh = out_h; P.ow = out_w; P.kx = 4; P.ky = 4;
-  P.chw = (flags & DTSIM_OBS_CHW) ? 1 : 0; P.f32 = (flags & DTSIM_OBS_F32) ? 1 : 0;
-  P.frames = h->frames; P.out = out;
-  P.bx = h->d_obsc_tab.get(); P.kkx = P.bx + out_w; P.by = P.kkx + 4 * (size_t)out_w; P.kky = P.by + out_h;
-  {
-    ProfScope ps(h, DTSIM_KERNEL_OBSERVE);
-    dt_launch_observe_cubic(h->stream, P, mask);
-  }
-  HIPCHK(hipGetLastError());
-  return DTSIM_OK;
+  return observe_run(h, true, out, out_h, out_w, flags, mask, first_x, taps_x, 4, first_y, taps_y, 4);
 }
 
 int dtsim_copy_rows(dtsim_t* h, void* dst, const void* src, size_t row_bytes, const uint8_t* mask) {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dtsim.h"
+#include "observe_plan.h"
 
 // ---- constants of the reference (simulator.py:99-177), evaluated exactly as
 // Python evaluates them (IEEE double, same operation order) -------------------
@@ -267,43 +268,9 @@ void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames,
 void dt_build_remap_maps(int W, int H, int n_cal, const double* K, const double* D, const double* ir, float* rx, float* ry);
 void dt_fill_pack_remap(int W, int H, int n_cal, float* rx, float* ry, const int32_t* order, const int64_t* order_off, int32_t* src_index);
 
-#ifndef DT_OBS_STAGE_ROWS
-#define DT_OBS_STAGE_ROWS 8
-#endif
-#ifndef DT_OBS_LDS_KB
-#define DT_OBS_LDS_KB 48
-#endif
-#ifndef DT_OBS_MAX_RPB
-#define DT_OBS_MAX_RPB 8
-#endif
-// observation post-processing (observe.hip): Pillow-exact bilinear resize + layout + normalisation
-struct ObserveParams {
-  int32_t N, H, W, oh, ow;
-  int32_t kx, ky;               // taps per output column / row in the tables
-  int32_t rows_per_block;       // output rows per workgroup
-  int32_t max_rows_in;          // input rows any workgroup needs (sizes the LDS intermediate)
-  int32_t chw, f32;             // layout (0: [N,h,w,3], 1: [N,3,h,w]) and dtype (0: uint8, 1: float32 / 255)
-  const uint8_t* frames;        // [N,H,W,3]
-  void* out;
-  const int32_t* bx;            // [ow][2] first tap, tap count   (dtsim/resample.py coeffs)
-  const int32_t* kkx;           // [ow][kx] 22-bit fixed-point taps
-  const int32_t* by;            // [oh][2]
-  const int32_t* kky;           // [oh][ky]
-  // power-of-two down-scaling (640 -> 160 / 80, 480 -> 240 / 120 / 60): away from the borders every output column (row) has the
-  // SAME taps, and they are small integers times a power of two (the triangle filter of scale S normalises to (1, 3, .., 2S-1,
-  // 2S-1, .., 1) / 2S^2).  hfast: 0 off, else S: the 2S taps x 3 channels of a column sit in `hn` aligned dwords starting `hoff`
-  // bytes from 3 S ox; hw[c][d] holds channel c's tap weights at their byte positions of dword d (zeros elsewhere): three
-  // chains of v_dot4_u32_u8 filter a column.  vfast: 0 off, else S: vw[t] the 2S row weights, applied to four bytes at a time
-  // in two 16-bit lanes.  hsh / vsh: the fixed-point shift that is left (22 - log2 of the common factor).
-  int32_t hfast, hn, hoff, hsh;
-  int32_t vfast, vsh;
-  uint32_t hw[3][12];
-  uint32_t vw[16];
-};
-size_t dt_observe_lds_bytes(const ObserveParams& P);
-// mask (device, [N] bytes, nonzero = selected; null = every env): dtsim_observe_masked -- the rows of other envs are not written
-void dt_launch_observe(hipStream_t s, const ObserveParams& P, const uint8_t* mask = nullptr);
-// OpenCV INTER_CUBIC: bx / by = first of the four taps per output column / row (borders replicate), kkx / kky = [..][4] 11-bit taps
-void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P, const uint8_t* mask = nullptr);
+// observation post-processing (observe.hip).  plan: dt_observe_plan / dt_observe_plan_cubic's (observe_plan.h), P: its parameters with
+// the per-call fields and the table pointers set.  mask (device, [N] bytes, nonzero = selected; null = every env): dtsim_observe_masked --
+// the rows of other envs are not written
+void dt_launch_observe(hipStream_t s, const ObservePlan& plan, const ObserveParams& P, const uint8_t* mask = nullptr);
 // row e of src -> row e of dst (row_bytes each) for every e < N with mask[e] != 0 (device pointers; dtsim_copy_rows)
 void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);

@@ -11,7 +11,6 @@
 // neighbouring row blocks), the output is 16x smaller at 640x480 -> 160x120.
 #include "dtsim_dev.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
 
@@ -426,13 +425,6 @@ __global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ dst, co
 
 }  // namespace
 
-void dt_launch_observe_cubic(hipStream_t s, const ObserveParams& P, const uint8_t* mask) {
-  const dim3 grid((unsigned)((size_t)P.N * P.oh));
-  const size_t lds = (size_t)P.W * 3 * sizeof(int32_t) + 16;
-  if (mask) hipLaunchKernelGGL(k_observe_cubic<true>, grid, dim3(OB), lds, s, P, mask);
-  else hipLaunchKernelGGL(k_observe_cubic<false>, grid, dim3(OB), lds, s, P, nullptr);
-}
-
 void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask) {
   const size_t chunks = (row_bytes + 15) / 16;
   const int per_row = (int)std::min<size_t>((chunks + 255) / 256, 16);   // (a selected row: up to 16 workgroups; the grid stays small when few are)
@@ -441,33 +433,24 @@ void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_
                      row_bytes, per_row, mask, vec);
 }
 
-
-size_t dt_observe_lds_bytes(const ObserveParams& P) {
-  const size_t in_row_words = ((size_t)P.W * 3 + 3) >> 2;
-  const size_t tabs = (P.ow != P.W && P.kx <= 9) ? (size_t)P.ow * (2 + 9) * 4 : 0;
-  return OBS_STAGE_ROWS * in_row_words * 4 + 32 + (((size_t)P.max_rows_in * P.ow * 3 + 3) & ~(size_t)3) + tabs + 16;
-}
-
-void dt_launch_observe(hipStream_t s, const ObserveParams& P, const uint8_t* mask) {
-  if (P.hfast && P.vfast && P.ow >= 3 && P.oh >= 3 && !getenv("DTSIM_OBSERVE_STAGED")) {   // power-of-two scale on both axes
-    const int G = (P.oh - 2 + 3) / 4;
-    const size_t n_in = (size_t)P.N * G * (P.ow - 2), n_b = (size_t)P.N * (2 * P.ow + 2 * (P.oh - 2));
-    const dim3 grid((unsigned)((n_in + OB - 1) / OB)), gridb((unsigned)((n_b + OB - 1) / OB));
-    bool done = true;
-#define DT_POW2(HN_, SY_) do { if (mask) hipLaunchKernelGGL((k_observe_pow2<HN_, SY_, true>), grid, dim3(OB), 0, s, P, mask); \
-                               else hipLaunchKernelGGL((k_observe_pow2<HN_, SY_, false>), grid, dim3(OB), 0, s, P, nullptr); } while (0)
-    if (P.hn == 7 && P.vfast == 2) DT_POW2(7, 2); else if (P.hn == 7 && P.vfast == 4) DT_POW2(7, 4); else if (P.hn == 7 && P.vfast == 8) DT_POW2(7, 8);
-    else if (P.hn == 12 && P.vfast == 2) DT_POW2(12, 2); else if (P.hn == 12 && P.vfast == 4) DT_POW2(12, 4); else if (P.hn == 12 && P.vfast == 8) DT_POW2(12, 8);
-    else done = false;
-#undef DT_POW2
-    if (done) {
-      if (mask) hipLaunchKernelGGL(k_observe_border<true>, gridb, dim3(OB), 0, s, P, mask);
-      else hipLaunchKernelGGL(k_observe_border<false>, gridb, dim3(OB), 0, s, P, nullptr);
-      return;
+void dt_launch_observe(hipStream_t s, const ObservePlan& plan, const ObserveParams& P, const uint8_t* mask) {
+  using Kernel = void (*)(ObserveParams, const uint8_t*);
+  auto launch = [&](Kernel k, size_t blocks) { hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(OB), plan.lds, s, P, mask); };
+  switch (plan.kernel) {
+    case DT_OBS_CUBIC:
+      launch(mask ? k_observe_cubic<true> : k_observe_cubic<false>, (size_t)P.N * P.oh);
+      break;
+    case DT_OBS_POW2: {                                // interior pixels, four rows of a column per thread; then the border pixels
+      const size_t n_in = (size_t)P.N * ((P.oh - 2 + 3) / 4) * (P.ow - 2), n_b = (size_t)P.N * (2 * P.ow + 2 * (P.oh - 2));
+#define DT_OBS_LAUNCH(HN_, SY_) \
+      if (P.hn == HN_ && P.vfast == SY_) launch(mask ? k_observe_pow2<HN_, SY_, true> : k_observe_pow2<HN_, SY_, false>, (n_in + OB - 1) / OB);
+      DT_OBS_POW2_LIST(DT_OBS_LAUNCH)
+#undef DT_OBS_LAUNCH
+      launch(mask ? k_observe_border<true> : k_observe_border<false>, (n_b + OB - 1) / OB);
+      break;
     }
+    case DT_OBS_STAGED:
+      launch(mask ? k_observe<true> : k_observe<false>, (size_t)P.N * ((P.oh + P.rows_per_block - 1) / P.rows_per_block));
+      break;
   }
-  const int n_blocks = (P.oh + P.rows_per_block - 1) / P.rows_per_block;
-  const dim3 grid((unsigned)((size_t)P.N * n_blocks));
-  if (mask) hipLaunchKernelGGL(k_observe<true>, grid, dim3(OB), dt_observe_lds_bytes(P), s, P, mask);
-  else hipLaunchKernelGGL(k_observe<false>, grid, dim3(OB), dt_observe_lds_bytes(P), s, P, nullptr);
 }

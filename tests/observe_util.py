@@ -1,6 +1,6 @@
-"""Helpers of the observation-resize tests: which kernel path of dtsim_observe a shape reaches (a restatement of the selection in
-csrc/dtsim_api.hip dtsim_observe and csrc/observe.hip dt_launch_observe / k_observe, checked on the CPU), adversarial frame
-content, and injection of arbitrary frames into a handle's frame batch (GPU)."""
+"""Helpers of the observation-resize tests: which kernel path of dtsim_observe a shape reaches (a restatement of the planner,
+csrc/observe_plan.h dt_observe_plan, which tests/test_observe_paths_host.py holds it to, and of the branches inside csrc/observe.hip
+k_observe), adversarial frame content, and injection of arbitrary frames into a handle's frame batch (GPU)."""
 import zlib
 
 import numpy as np
@@ -8,12 +8,12 @@ import numpy as np
 from dtsim import resample
 
 PREC = resample.PRECISION_BITS
-STAGE_ROWS = 8                 # DT_OBS_STAGE_ROWS (csrc/dtsim_dev.h)
+STAGE_ROWS = 8                 # DT_OBS_STAGE_ROWS (csrc/observe_plan.h)
 PF_WORDS = 16 * 256            # k_observe's prefetch registers x threads per workgroup
 
 
 def _uniform(bounds, taps, n_in, n_out, S):
-    """dtsim_observe's `uniform` lambda: every interior output coordinate has the same 2S small-integer taps starting at S*o - S/2.
+    """dt_observe_uniform: every interior output coordinate has the same 2S small-integer taps starting at S*o - S/2.
     Returns the tap shift (22 - common trailing zeros) or None."""
     ksize = taps.shape[1]
     if n_out < 3 or n_out * S != n_in or 2 * S > ksize or 2 * S > 16:
@@ -31,9 +31,8 @@ def _uniform(bounds, taps, n_in, n_out, S):
     return 22 - common
 
 
-def observe_path(W, H, ow, oh, staged=False, generic=False):
-    """The kernel path dtsim_observe takes for camera W x H -> ow x oh (DTSIM_OBSERVE_STAGED / DTSIM_OBSERVE_GENERIC as flags).
-    "pow2<HN,SY>/tail<t>" for k_observe_pow2 (+ k_observe_border), else "k_observe/h=<..>/v=<..>/PER=<..>/load=<..>"."""
+def fast_taps(W, H, ow, oh, generic=False):
+    """(hfast, hn, vfast) of the plan: the power-of-two scales whose interior taps are uniform (0: none), and the dwords of a column window."""
     hfast = hn = vfast = 0
     if not generic:
         if ow != W and (W * 3) % 4 == 0:
@@ -53,6 +52,13 @@ def observe_path(W, H, ow, oh, staged=False, generic=False):
                 if _uniform(by, ky, H, oh, S) is not None:
                     vfast = S
                     break
+    return hfast, hn, vfast
+
+
+def observe_path(W, H, ow, oh, staged=False, generic=False):
+    """The kernel path dtsim_observe takes for camera W x H -> ow x oh (DTSIM_OBSERVE_STAGED / DTSIM_OBSERVE_GENERIC as flags).
+    "pow2<HN,SY>/tail<t>" for k_observe_pow2 (+ k_observe_border), else "k_observe/h=<..>/v=<..>/PER=<..>/load=<..>"."""
+    hfast, hn, vfast = fast_taps(W, H, ow, oh, generic)
     if hfast and vfast and ow >= 3 and oh >= 3 and not staged and hn in (7, 12) and vfast in (2, 4, 8):
         return f"pow2<{hn},{vfast}>/tail{(oh - 2) % 4}"
     kx_n = resample.coeffs(W, ow)[1].shape[1] if ow != W else 0

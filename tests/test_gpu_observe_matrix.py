@@ -1,13 +1,14 @@
 """GPU: every kernel path of dtsim_observe / dtsim_observe_cubic, bit-exact on injected adversarial frames (independent per-channel
 noise, 1-px 0/255 checkerboards, saturated constants, ramps), in all four output layouts.  Which path each shape reaches is
-tests/observe_util.py observe_path, checked on the CPU by tests/test_observe_paths_host.py."""
+tests/observe_util.py observe_path, which tests/test_observe_paths_host.py holds the planner (csrc/observe_plan.h) to on the CPU."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from dtsim import BatchedSimulator, _ffi, resample
-from observe_util import BILINEAR_CASES, CONSTANT_KINDS, CUBIC_CASES, content, cubic_headroom, inject, layouts, observe_host, pil_bilinear
+from observe_util import (BILINEAR_CASES, CONSTANT_KINDS, CUBIC_CASES, content, cubic_headroom, inject, layouts, observe_host, observe_path,
+                          pil_bilinear)
 
 pytestmark = pytest.mark.gpu
 pytest.importorskip("PIL.Image")
@@ -150,6 +151,41 @@ def test_table_cache_is_keyed_by_the_tables():
         assert np.array_equal(call(*nearest(ow), *nearest(oh)), frames[:, ::2, ::2])
         assert np.array_equal(call(*resample.coeffs(W, ow), *resample.coeffs(H, oh)), pil_bilinear(frames, oh, ow))
         assert np.array_equal(call(*nearest(ow), *nearest(oh)), frames[:, ::2, ::2])
+    finally:
+        sim.close()
+
+
+def test_plans_replace_each_other_on_one_handle():
+    """One handle through pow2 -> k_observe -> pow2 -> cubic -> masked pow2: every call rebuilds or reuses the plan of its slot and stays
+    exact; a call whose tables are rejected changes nothing, so the next call with the earlier tables is exact too."""
+    import torch
+    W, H, N = 32, 16, 4
+    assert observe_path(W, H, 4, 4).startswith("pow2") and observe_path(W, H, 7, 5).startswith("k_observe")
+    sim = _make(W, H, N)
+    try:
+        frames = content("noise", N, H, W, seed=11)
+        inject(sim, frames)
+        small = pil_bilinear(frames, 4, 4)
+        assert np.array_equal(observe_host(sim, 4, 4), small)
+        assert np.array_equal(observe_host(sim, 5, 7), pil_bilinear(frames, 5, 7))
+        assert np.array_equal(observe_host(sim, 4, 4), small)
+        assert np.array_equal(observe_host(sim, 5, 6, interpolation="cv_cubic"), np.stack([resample.resize_cubic(f, 5, 6) for f in frames]))
+        dev = f"cuda:{sim.device_index}"
+        out = torch.full((N, 4, 4, 3), 0xA5, dtype=torch.uint8, device=dev)
+        mask = torch.tensor([0, 1, 0, 1], dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(sim.device_index)             # (torch's fills, then the library's stream)
+        got = observe_host(sim, 4, 4, out=out, mask=mask)
+        assert np.array_equal(got[[1, 3]], small[[1, 3]]) and (got[[0, 2]] == 0xA5).all()
+        ip = C.POINTER(C.c_int32)
+        bx, kx = resample.coeffs(W, 4)
+        by, ky = resample.coeffs(H, 4)
+        by = by.copy()
+        by[2, 0] = by[1, 0] - 1                               # in range, but before the row above
+        tabs = [np.ascontiguousarray(a, dtype=np.int32) for a in (bx, kx, by, ky)]
+        rc = sim._lib.dtsim_observe(sim._h, C.c_void_p(out.data_ptr()), 4, 4, 0, tabs[0].ctypes.data_as(ip), tabs[1].ctypes.data_as(ip), tabs[1].shape[1],
+                                    tabs[2].ctypes.data_as(ip), tabs[3].ctypes.data_as(ip), tabs[3].shape[1])
+        assert rc == _ffi.E_INVALID and b"not monotone" in sim._lib.dtsim_last_error()
+        assert np.array_equal(observe_host(sim, 4, 4), small)
     finally:
         sim.close()
 
