@@ -85,6 +85,36 @@ struct ObserveSlot {
   DevPtr<int32_t> d_tab;
 };
 
+// The assets of the last dtsim_set_assets: the device copies, and on the host what dt_pack_maps and dt_pack_segment_texels need
+// later (T.tris is released after the upload).
+struct AssetSlot {
+  AssetTables T;
+  DevPtr<uint32_t> d_texels;
+  DevPtr<TexDev> d_tex;
+  DevPtr<MeshDev> d_meshes;
+  DevPtr<TriDev> d_tris;
+};
+
+// The maps of the last dtsim_set_maps: M (blobs, dyn) serves physics, reset, query and the sampler; the rest is the render side,
+// packed against the assets of that moment -- a later dtsim_set_assets releases it (renderable = false) until the next dtsim_set_maps.
+struct MapSlot : MapScalars {
+  DevPtr<uint64_t> d_blobs;
+  DevPtr<DynInit> d_dyn;
+  bool renderable = false;
+  DevPtr<RenderMapDev> d_rmaps;
+  DevPtr<uint32_t> d_rtiles;
+  DevPtr<TileLds> d_tilerecs;
+  DevPtr<ObjInstDev> d_robjs;
+  DevPtr<uint8_t> d_qtex;             // quad-layout blocks for k_raster_q
+  DevPtr<uint32_t> d_qtiles;
+  DevPtr<char> d_obj[DT_SLABS];       // DT_SLAB_STRIS .. DT_SLAB_OBJMASK of the render scratch (dt_render_layout): only with mesh objects
+  void release_render() {
+    renderable = false;
+    d_rmaps.reset(); d_rtiles.reset(); d_tilerecs.reset(); d_robjs.reset(); d_qtex.reset(); d_qtiles.reset();
+    for (auto& p : d_obj) p.reset();
+  }
+};
+
 }  // namespace
 
 struct dtsim {
@@ -98,9 +128,7 @@ struct dtsim {
   SimArrays A{};
   // maps
   bool have_maps = false, have_reset = false;
-  MapSet M{};
-  DevPtr<uint64_t> d_blobs;
-  DevPtr<DynInit> d_dyn;
+  MapSlot maps;
   // reset / pool staging
   DevPtr<dtsim_init_state> d_states;
   DevPtr<uint8_t> d_mask;
@@ -139,33 +167,14 @@ struct dtsim {
   DevPtr<int32_t> d_cal_src;      // [n_cal][H*W]
   DevPtr<int32_t> d_env_cal;      // [N]
   DevPtr<uint8_t> d_scratch;      // [N][H][W][3]
-  DevPtr<uint32_t> d_texels;
-  DevPtr<uint32_t> d_texels_seg;      // segmented versions, same layout as d_texels (dtsim_set_segment_assets)
+  AssetSlot assets;
+  DevPtr<uint32_t> d_texels_seg;      // segmented versions, same layout as assets.d_texels (dtsim_set_segment_assets)
   DevPtr<uint8_t> d_mesh_seg;         // [n_meshes][4] flat segmentation colour per mesh
-  DevPtr<TexDev> d_tex;
-  int n_tex = 0;
-  std::vector<TexDev> h_tex;
-  DevPtr<MeshDev> d_meshes;
-  DevPtr<TriDev> d_tris;
-  int n_meshes = 0;
-  std::vector<MeshDev> h_meshes;
-  DevPtr<RenderMapDev> d_rmaps;
-  DevPtr<uint32_t> d_rtiles;
-  DevPtr<TileLds> d_tilerecs;
-  DevPtr<char> d_render[DT_SLABS];    // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND at dtsim_create, the object slabs at dtsim_set_maps
-  std::vector<uint32_t> h_pool;       // host copy of the RGBA8 pool (quad blocks are built from it at dtsim_set_maps)
-  DevPtr<uint8_t> d_qtex;             // quad-layout blocks for k_raster_q
-  DevPtr<uint32_t> d_qtiles;
-  int n_qtiles = 0, qlog2 = 0;
+  DevPtr<char> d_render[DT_SLABS];    // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND, allocated at dtsim_create (the object slabs: maps.d_obj)
   bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop): 1, 2 or 4
-  float q_per_m = 0.f;
   DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
-  int map_w[DTSIM_MAX_MAPS] = {0}, map_h[DTSIM_MAX_MAPS] = {0};
   ObserveSlot obs, obsc;          // dtsim_observe / dtsim_observe_cubic (and their masked forms)
-  int max_tris = 0;
-  int n_tilerecs = 0, tex_w = 1, tex_h = 1;
-  DevPtr<ObjInstDev> d_robjs;
   ProfSlot prof[DTSIM_KERNEL__COUNT];
 };
 
@@ -234,8 +243,29 @@ StepParams step_params(const dtsim* h, int n_steps) {
 // points R's scratch fields into the handle's render slabs (dt_render_layout)
 void render_scratch(const dtsim* h, int max_tris, RenderParams* R) {
   void* base[DT_SLABS];
-  for (int i = 0; i < DT_SLABS; ++i) base[i] = h->d_render[i].get();
+  for (int i = 0; i < DT_SLABS; ++i) base[i] = i < DT_SLAB_STRIS ? h->d_render[i].get() : h->maps.d_obj[i].get();
   dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, nullptr, base, R);
+}
+
+// the scene of a pass: the assets (segment: their segmented texels) and the render side of the maps
+void render_scene(const dtsim* h, bool segment, RenderParams* R) {
+  const AssetSlot& a = h->assets;
+  const MapSlot& m = h->maps;
+  R->texels = segment ? h->d_texels_seg.get() : a.d_texels.get(); R->tex = a.d_tex.get();
+  R->meshes = a.d_meshes.get(); R->tris = a.d_tris.get();
+  R->n_maps = m.M.n_maps;
+  R->maps = m.d_rmaps.get(); R->tiles = m.d_rtiles.get(); R->objs = m.d_robjs.get();
+  R->max_tris = m.d_obj[DT_SLAB_STRIS] ? m.max_tris : 0;
+  R->tile_recs = m.d_tilerecs.get(); R->n_tile_recs = m.n_tilerecs; R->tex_w = m.tex_w; R->tex_h = m.tex_h;
+  R->qtex = m.d_qtex.get(); R->qtiles = m.d_qtiles.get(); R->n_qtiles = m.n_qtiles; R->qlog2 = m.qlog2; R->q_per_m = m.q_per_m;
+  R->qmax_tiles = std::max(m.grid_rows, m.grid_cols);
+}
+
+// the render entry points after a dtsim_set_assets that followed dtsim_set_maps: the maps' render tables indexed the old assets and are gone
+int check_renderable(const dtsim* h, const char* who) {
+  if (h->have_maps && !h->maps.renderable)
+    return fail(DTSIM_E_STATE, "%s: dtsim_set_assets replaced the assets the maps were packed against: call dtsim_set_maps again", who);
+  return DTSIM_OK;
 }
 
 struct ProfScope {
@@ -342,358 +372,71 @@ void dtsim_destroy(dtsim_t* h) {
   delete h;   // frees every device buffer the handle owns
 }
 
-// textures -> one RGBA8 pool: padded (h+1) x (w+1) storage so that GL_REPEAT bilinear fetches never wrap
-static int build_texel_pool(const dtsim_texture* textures, int n_textures, std::vector<uint32_t>& pool, std::vector<TexDev>* descs) {
-  for (int t = 0; t < n_textures; ++t) {
-    const dtsim_texture& tx = textures[t];
-    if (tx.width <= 0 || tx.height <= 0 || (tx.width & (tx.width - 1)) || (tx.height & (tx.height - 1)) || !tx.rgba)
-      return fail(DTSIM_E_INVALID, "texture %d: size must be a power of two", t);
-    TexDev d{tx.width, tx.height, (int32_t)pool.size(), 0};
-    const int pw = tx.width + 1;
-    pool.resize(pool.size() + (size_t)pw * (tx.height + 1));
-    uint32_t* dst = pool.data() + d.off;
-    for (int y = 0; y <= tx.height; ++y)
-      for (int x = 0; x <= tx.width; ++x) {
-        const uint8_t* s = tx.rgba + ((size_t)(y % tx.height) * tx.width + (x % tx.width)) * 4;
-        dst[(size_t)y * pw + x] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
-      }
-    if (descs) descs->push_back(d);
-  }
-  return DTSIM_OK;
-}
-
 int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, const dtsim_mesh* meshes,
                      int n_meshes) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
   h->leds_ok = false;
   h->render_tables = 0;           // the cached per-pixel / per-block render tables depend on this
-  if (n_textures < 0 || n_textures > DTSIM_MAX_TEXTURES) return fail(DTSIM_E_LIMIT, "n_textures %d > %d", n_textures, DTSIM_MAX_TEXTURES);
-  if (n_meshes < 0 || n_meshes > DTSIM_MAX_MESHES) return fail(DTSIM_E_LIMIT, "n_meshes %d > %d", n_meshes, DTSIM_MAX_MESHES);
+  AssetSlot next;
+  std::string err;
+  if (int rc = dt_pack_assets(next.T, err, textures, n_textures, meshes, n_meshes)) return fail(rc, "%s", err.c_str());
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  std::vector<uint32_t> pool;
-  std::vector<TexDev> tex;
-  if (int rc = build_texel_pool(textures, n_textures, pool, &tex)) return rc;
-  std::vector<MeshDev> mesh_descs;
-  std::vector<TriDev> tris;
-  for (int m = 0; m < n_meshes; ++m) {
-    const dtsim_mesh& ms = meshes[m];
-    if (ms.n_tris < 0 || (ms.n_tris > 0 && (!ms.verts || !ms.normals || !ms.colors)))
-      return fail(DTSIM_E_INVALID, "mesh %d: null arrays", m);
-    MeshDev d{};
-    d.n_tris = ms.n_tris; d.off = (int32_t)tris.size();
-    for (int k = 0; k < 3; ++k) { d.mn[k] = 1e30f; d.mx[k] = -1e30f; }
-    for (int t = 0; t < ms.n_tris * 3; ++t)
-      for (int k = 0; k < 3; ++k) { d.mn[k] = std::min(d.mn[k], ms.verts[t * 3 + k]); d.mx[k] = std::max(d.mx[k], ms.verts[t * 3 + k]); }
-    for (int t = 0; t < ms.n_tris; ++t) {
-      TriDev td;
-      memcpy(td.v, ms.verts + (size_t)t * 9, 36);
-      memcpy(td.n, ms.normals + (size_t)t * 9, 36);
-      memcpy(td.c, ms.colors + (size_t)t * 9, 36);
-      if (ms.uvs) memcpy(td.uv, ms.uvs + (size_t)t * 6, 24); else memset(td.uv, 0, 24);
-      td.tex = (ms.uvs && ms.tri_tex) ? ms.tri_tex[t] : -1; td.pad = 0;
-      if (td.tex >= n_textures) return fail(DTSIM_E_INVALID, "mesh %d triangle %d: texture %d not loaded", m, t, td.tex);
-      if (td.tex < 0) td.tex = -1;
-      tris.push_back(td);
-    }
-    mesh_descs.push_back(d);
-  }
-  DevPtr<uint32_t> d_texels;
-  DevPtr<TexDev> d_tex;
-  DevPtr<MeshDev> d_meshes;
-  DevPtr<TriDev> d_tris;
-  HIPCHK(dev_upload(d_texels, pool.data(), pool.size()));
-  HIPCHK(dev_upload(d_tex, tex.data(), tex.size()));
-  HIPCHK(dev_upload(d_meshes, mesh_descs.data(), mesh_descs.size()));
-  HIPCHK(dev_upload(d_tris, tris.data(), tris.size()));
-  h->d_texels = std::move(d_texels); h->d_tex = std::move(d_tex); h->h_tex = std::move(tex); h->h_pool = std::move(pool);
-  h->n_tex = n_textures;
-  h->d_meshes = std::move(d_meshes); h->d_tris = std::move(d_tris); h->h_meshes = std::move(mesh_descs);
-  h->n_meshes = n_meshes;
-  // the quad-layout blocks were built from the OLD texel pool (dtsim_set_maps): drop them, so that the generic raster
-  // (which reads d_texels) is used until the next dtsim_set_maps rebuilds them -- never a frame mixing both pools
-  h->d_qtex.reset(); h->d_qtiles.reset();
-  h->n_qtiles = 0; h->qlog2 = 0;
+  HIPCHK(dev_upload(next.d_texels, next.T.pool.data(), next.T.pool.size()));
+  HIPCHK(dev_upload(next.d_tex, next.T.tex.data(), next.T.tex.size()));
+  HIPCHK(dev_upload(next.d_meshes, next.T.meshes.data(), next.T.meshes.size()));
+  HIPCHK(dev_upload(next.d_tris, next.T.tris.data(), next.T.tris.size()));
+  next.T.tris = {};
+  h->assets = std::move(next);
+  h->maps.release_render();       // the installed maps' render tables index the old lists: the render entry points wait for dtsim_set_maps
   h->d_texels_seg.reset();        // mirrors the old list
   return DTSIM_OK;
 }
 
 int dtsim_set_segment_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, const uint8_t* mesh_rgb, int n_meshes) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
-  if (n_textures != h->n_tex || n_meshes != h->n_meshes)
-    return fail(DTSIM_E_INVALID, "segment assets must mirror dtsim_set_assets (%d textures, %d meshes), got %d / %d", h->n_tex,
-                h->n_meshes, n_textures, n_meshes);
-  if ((n_textures > 0 && !textures) || (n_meshes > 0 && !mesh_rgb)) return fail(DTSIM_E_INVALID, "null argument");
-  for (int t = 0; t < n_textures; ++t)
-    if (textures[t].width != h->h_tex[t].w || textures[t].height != h->h_tex[t].h)
-      return fail(DTSIM_E_INVALID, "segmented texture %d is %dx%d, the texture it replaces is %dx%d", t, textures[t].width,
-                  textures[t].height, h->h_tex[t].w, h->h_tex[t].h);
+  std::vector<uint32_t> pool;
+  std::vector<uint8_t> rgbx;
+  std::string err;
+  if (int rc = dt_pack_segment_texels(pool, rgbx, err, textures, n_textures, mesh_rgb, n_meshes, h->assets.T)) return fail(rc, "%s", err.c_str());
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  std::vector<uint32_t> pool;
-  if (int rc = build_texel_pool(textures, n_textures, pool, nullptr)) return rc;
-  std::vector<uint8_t> rgbx((size_t)std::max(n_meshes, 1) * 4, 0);
-  for (int m = 0; m < n_meshes; ++m) { rgbx[m * 4] = mesh_rgb[m * 3]; rgbx[m * 4 + 1] = mesh_rgb[m * 3 + 1]; rgbx[m * 4 + 2] = mesh_rgb[m * 3 + 2]; }
   DevPtr<uint32_t> d_texels_seg;
+  DevPtr<uint8_t> d_mesh_seg;
   HIPCHK(dev_upload(d_texels_seg, pool.data(), pool.size(), 1));
-  HIPCHK(dev_upload(h->d_mesh_seg, rgbx.data(), rgbx.size()));
-  h->d_texels_seg = std::move(d_texels_seg);
+  HIPCHK(dev_upload(d_mesh_seg, rgbx.data(), rgbx.size()));
+  h->d_texels_seg = std::move(d_texels_seg); h->d_mesh_seg = std::move(d_mesh_seg);
   return DTSIM_OK;
 }
 
-// One quad block (S x S records of 16 B) of a tile texture pre-rotated by the tile angle (render.hip k_raster_q).
-// Cell (x0, z0) covers the padded-quad coordinates [x0, x0+1) x [z0, z0+1) of the tile, i.e. the GL_LINEAR taps
-// P[z0-1][x0-1], P[z0-1][x0], P[z0][x0-1], P[z0][x0] (GL_REPEAT wrap) of the tile-frame image P with
-// P[zz][xx] = T[y][x], (x, y) the texel the tile-local point ((xx+.5)/S, (zz+.5)/S) maps to under glRotatef(angle*90+180)
-// and uv = (pu, 1-pv) (simulator.py:394-401,1872-1873): u = {1-fx, fz, fx, 1-fz}[angle], v = {fz, fx, 1-fz, 1-fx}[angle].
-// `pool` holds T padded to (S+1) x (S+1).  Meta dword: cells to the nearest tile boundary (DT_QMETA, dtsim_dev.h).
-static void build_quad_block(std::vector<uint32_t>& out, const uint32_t* pool, int S, int ang) {
-  const size_t base = out.size();
-  out.resize(base + (size_t)S * S * 4);
-  auto texel = [&](int xx, int zz) -> uint32_t {
-    xx &= S - 1; zz &= S - 1;
-    int x, y;
-    switch (ang & 3) {
-      case 0: x = S - 1 - xx; y = zz; break;
-      case 1: x = zz; y = xx; break;
-      case 2: x = xx; y = S - 1 - zz; break;
-      default: x = S - 1 - zz; y = S - 1 - xx; break;
-    }
-    return pool[(size_t)y * (S + 1) + x];
-  };
-  for (int z0 = 0; z0 < S; ++z0)
-    for (int x0 = 0; x0 < S; ++x0) {
-      const uint32_t t00 = texel(x0 - 1, z0 - 1), t10 = texel(x0, z0 - 1), t01 = texel(x0 - 1, z0), t11 = texel(x0, z0);
-      // S = 256: 4 x 2 cells per 128-byte line -- record number (x0 >> 2) << 10 | z0 << 2 | (x0 & 3) (render.hip, q8_rec256: a 32 x 2 pixel slot of the
-      // raster touches ~ 15 % fewer lines than with the rows of the texture laid end to end); other sizes: row-major
-      const size_t rec = (S == 256) ? ((size_t)(x0 >> 2) << 10) | ((size_t)z0 << 2) | (size_t)(x0 & 3) : (size_t)z0 * S + x0;
-      uint32_t* q = &out[base + rec * 4];
-      for (int c = 0; c < 3; ++c)
-        q[c] = ((t00 >> (8 * c)) & 255u) | (((t10 >> (8 * c)) & 255u) << 8) | (((t01 >> (8 * c)) & 255u) << 16) | (((t11 >> (8 * c)) & 255u) << 24);
-      q[3] = (uint32_t)std::min(std::min(std::min(x0, S - x0), std::min(z0, S - z0)), 0xFFFF);
-    }
-}
-
 int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
-  if (!h || !maps) return fail(DTSIM_E_INVALID, "null argument");
+  if (!h) return fail(DTSIM_E_INVALID, "null argument");
   h->leds_ok = false;
   h->render_tables = 0;           // the cached per-pixel / per-block render tables depend on this
-  if (n_maps <= 0 || n_maps > DTSIM_MAX_MAPS) return fail(DTSIM_E_LIMIT, "n_maps %d outside [1,%d]", n_maps, DTSIM_MAX_MAPS);
+  MapTables T;
+  std::string err;
+  if (int rc = dt_pack_maps(T, err, maps, n_maps, h->assets.T, (h->cfg.flags & DTSIM_F_RENDER) != 0)) return fail(rc, "%s", err.c_str());
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  std::vector<uint64_t> blobs;
-  std::vector<DynInit> dyn((size_t)n_maps * DTSIM_MAX_DYNAMIC);
-  memset(dyn.data(), 0, dyn.size() * sizeof(DynInit));
-  std::vector<RenderMapDev> rmaps(n_maps);
-  std::vector<uint32_t> rtiles;
-  std::vector<TileLds> trecs;
-  int tex_w = 0, tex_h = 0;
-  std::vector<ObjInstDev> robjs;
-  MapSet M{};
-  M.n_maps = n_maps;
-  for (int mi = 0; mi < n_maps; ++mi) {
-    const dtsim_map& mp = maps[mi];
-    const int nt = mp.grid_w * mp.grid_h;
-    if (mp.grid_w <= 0 || mp.grid_h <= 0 || nt > DTSIM_MAX_TILES) return fail(DTSIM_E_LIMIT, "map %d: %d tiles > %d", mi, nt, DTSIM_MAX_TILES);
-    if (mp.n_curves < 0 || mp.n_curves > DTSIM_MAX_CURVES) return fail(DTSIM_E_LIMIT, "map %d: n_curves %d", mi, mp.n_curves);
-    if (mp.n_objects < 0 || mp.n_objects > DTSIM_MAX_OBJECTS) return fail(DTSIM_E_LIMIT, "map %d: n_objects %d > %d", mi, mp.n_objects, DTSIM_MAX_OBJECTS);
-    if (!mp.tile_kind || !mp.tile_angle || !mp.tile_tex || !mp.tile_curve_off || !mp.tile_curve_cnt || !(mp.tile_size > 0))
-      return fail(DTSIM_E_INVALID, "map %d: null tile arrays / tile_size", mi);
-    if (mp.n_curves > 0 && (!mp.curves || !mp.curve_heads)) return fail(DTSIM_E_INVALID, "map %d: null curves", mi);
-    if (mp.n_objects > 0 && !mp.objects) return fail(DTSIM_E_INVALID, "map %d: null objects", mi);
-    int n_static = 0, n_dyn = 0;
-    for (int o = 0; o < mp.n_objects; ++o) {
-      if (mp.objects[o].dynamic) ++n_dyn;
-      else if (mp.objects[o].collidable) ++n_static;
-    }
-    if (n_static > DTSIM_MAX_STATIC) return fail(DTSIM_E_LIMIT, "map %d: %d static collidables > %d", mi, n_static, DTSIM_MAX_STATIC);
-    if (n_dyn > DTSIM_MAX_DYNAMIC) return fail(DTSIM_E_LIMIT, "map %d: %d dynamic objects > %d", mi, n_dyn, DTSIM_MAX_DYNAMIC);
-    MapHdr hd{};
-    hd.grid_w = mp.grid_w; hd.grid_h = mp.grid_h; hd.n_curves = mp.n_curves; hd.n_static = n_static;
-    hd.n_lights = 0;
-    for (int o = 0; o < mp.n_objects; ++o) hd.n_lights += mp.objects[o].light_freq > 0 ? 1 : 0;
-    hd.n_dyn = n_dyn; hd.n_obj = mp.n_objects; hd.tile_size = mp.tile_size;
-    int w = MAPHDR_WORDS;
-    hd.off_tiles = w; w += nt;
-    hd.off_curves = w; w += 8 * mp.n_curves;
-    hd.off_heads = w; w += 2 * mp.n_curves;
-    hd.off_static = w; w += STATIC_WORDS * n_static;
-    hd.off_objs = w; w += OBJ_WORDS * mp.n_objects;
-    hd.total_words = w;
-    const size_t base = blobs.size();
-    M.blob_off[mi] = (int32_t)base;
-    blobs.resize(base + w);
-    uint64_t* b = blobs.data() + base;
-    memcpy(b, &hd, sizeof hd);
-    for (int t = 0; t < nt; ++t) {
-      TileRec tr{};
-      tr.kind = mp.tile_kind[t]; tr.angle = mp.tile_angle[t];
-      tr.drivable = (tr.kind >= DTSIM_TILE_STRAIGHT && tr.kind <= DTSIM_TILE_4WAY) ? 1 : 0;
-      tr.curve_cnt = mp.tile_curve_cnt[t]; tr.curve_off = mp.tile_curve_off[t]; tr.tex = mp.tile_tex[t];
-      if (tr.drivable && (tr.curve_off < 0 || tr.curve_off + tr.curve_cnt > mp.n_curves || tr.curve_cnt == 0))
-        return fail(DTSIM_E_INVALID, "map %d tile %d: drivable tile without curves", mi, t);
-      if (tr.tex >= h->n_tex) return fail(DTSIM_E_INVALID, "map %d tile %d: texture %d not loaded", mi, t, tr.tex);
-      memcpy(&b[hd.off_tiles + t], &tr, 8);
-    }
-    if (mp.n_curves) {
-      memcpy(&b[hd.off_curves], mp.curves, sizeof(double) * 8 * mp.n_curves);
-      memcpy(&b[hd.off_heads], mp.curve_heads, sizeof(double) * 2 * mp.n_curves);
-    }
-    double* st = reinterpret_cast<double*>(&b[hd.off_static]);
-    double* ob = reinterpret_cast<double*>(&b[hd.off_objs]);
-    int si = 0, di = 0;
-    RenderMapDev& rm = rmaps[mi];
-    rm.grid_w = mp.grid_w; rm.grid_h = mp.grid_h; rm.n_obj = mp.n_objects; rm.n_tris = 0;
-    for (int o = 0; o < mp.n_objects; ++o)
-      if (mp.objects[o].mesh_id >= 0 && mp.objects[o].mesh_id < (int)h->h_meshes.size()) rm.n_tris += h->h_meshes[mp.objects[o].mesh_id].n_tris;
-    rm.tile_size = (float)mp.tile_size; rm.inv_tile_size = (float)(1.0 / mp.tile_size);
-    rm.tile_off = (int32_t)rtiles.size(); rm.obj_off = (int32_t)robjs.size();
-    for (int t = 0; t < nt; ++t) {
-      const bool present = mp.tile_kind[t] != DTSIM_TILE_EMPTY;
-      const int tex = mp.tile_tex[t] < 0 ? 0xFF : mp.tile_tex[t];
-      rtiles.push_back((uint32_t)tex | ((uint32_t)(mp.tile_angle[t] & 3) << 8) | ((present ? 1u : 0u) << 15) |
-                       ((mp.tile_tex[t] >= 0 ? 1u : 0u) << 14));
-      TileLds tr{};
-      tr.flags = present ? 1u : 0u;
-      if (present && mp.tile_tex[t] >= 0 && mp.tile_tex[t] < (int)h->h_tex.size()) {
-        const TexDev& td = h->h_tex[mp.tile_tex[t]];
-        if (tex_w == 0) { tex_w = td.w; tex_h = td.h; }
-        if (td.w != tex_w || td.h != tex_h)
-          return fail(DTSIM_E_LIMIT, "map %d tile %d: all tile textures must share one size (%dx%d vs %dx%d)", mi, t, td.w, td.h, tex_w, tex_h);
-        const int ang = mp.tile_angle[t] & 3;
-        const float TW = (float)td.w, TH = (float)td.h;
-        tr.tex_off = (uint32_t)td.off;
-        tr.flags |= 2u;
-        // u = {1-fx, fz, fx, 1-fz}[ang], v = {fz, fx, 1-fz, 1-fx}[ang]; x = u*TW - 0.5, y = v*TH - 0.5
-        const bool swp = (ang & 1) != 0, flip_u = (ang == 0 || ang == 3), flip_v = (ang == 2 || ang == 3);
-        const float mu = flip_u ? -TW : TW, mv = flip_v ? -TH : TH;
-        tr.mxx = swp ? 0.f : mu; tr.mxz = swp ? mu : 0.f; tr.ox = flip_u ? TW - 0.5f : -0.5f;
-        tr.myx = swp ? mv : 0.f; tr.myz = swp ? 0.f : mv; tr.oy = flip_v ? TH - 0.5f : -0.5f;
-      }
-      trecs.push_back(tr);
-    }
-    for (int o = 0; o < mp.n_objects; ++o) {
-      const dtsim_object& ob_ = mp.objects[o];
-      if (ob_.mesh_id >= h->n_meshes) return fail(DTSIM_E_INVALID, "map %d object %d: mesh %d not loaded", mi, o, ob_.mesh_id);
-      int slot = -1;
-      if (ob_.dynamic) {
-        slot = di++;
-        DynInit& d = dyn[(size_t)mi * DTSIM_MAX_DYNAMIC + slot];
-        d.cx = ob_.pos[0]; d.cz = ob_.pos[2];
-        memcpy(d.corners, ob_.corners, sizeof d.corners);
-        memcpy(d.norm, ob_.norm, sizeof d.norm);
-        d.heading_x = std::cos(ob_.angle); d.heading_z = -std::sin(ob_.angle);  // collision.py:223-230
-        d.angle = ob_.angle; d.safety_radius = ob_.safety_radius;
-        d.walk_distance = ob_.walk_distance; d.vel = ob_.vel; d.wait_time = ob_.wait_time; d.wiggle = ob_.wiggle;
-        d.obj_index = o; d.kind = ob_.dynamic;
-      } else if (ob_.collidable) {
-        double* r = st + STATIC_WORDS * si++;
-        memcpy(r, ob_.corners, 8 * sizeof(double));
-        memcpy(r + 8, ob_.norm, 4 * sizeof(double));
-        r[12] = ob_.pos[0]; r[13] = ob_.pos[2]; r[14] = ob_.safety_radius;
-      }
-      ob[o * OBJ_WORDS + 0] = ob_.pos[0]; ob[o * OBJ_WORDS + 1] = ob_.pos[2];
-      ob[o * OBJ_WORDS + 2] = ob_.spawn_clear;
-      ob[o * OBJ_WORDS + 3] = (double)(slot >= 0 ? slot : (ob_.optional ? -2 : -1));   // -2: optional static object
-      ob[o * OBJ_WORDS + 4] = (double)ob_.light_freq; ob[o * OBJ_WORDS + 5] = (double)(ob_.light_pattern & 1);
-      if (ob_.light_freq < 0) return fail(DTSIM_E_INVALID, "map %d object %d: light_freq %d", mi, o, ob_.light_freq);
-      ObjInstDev oi{};
-      oi.x = (float)ob_.pos[0]; oi.y = (float)ob_.pos[1]; oi.z = (float)ob_.pos[2];
-      oi.scale = (float)ob_.scale; oi.yrot_deg = (float)(ob_.angle * (180.0 / 3.141592653589793));
-      oi.mesh_id = ob_.mesh_id; oi.dyn_slot = slot;
-      oi.light_tris = ob_.light_freq > 0 ? ob_.light_tris : 0; oi.light_tex0 = ob_.light_tex[0]; oi.light_tex1 = ob_.light_tex[1];
-      if (oi.light_tris > 0 && (oi.light_tex0 >= h->n_tex || oi.light_tex1 >= h->n_tex))
-        return fail(DTSIM_E_INVALID, "map %d object %d: light texture not loaded", mi, o);
-      robjs.push_back(oi);
-    }
-  }
-  // ---- quad-layout fast path tables: possible when every tile texture is one square power-of-two size
-  std::vector<uint32_t> qblocks, qtiles;
-  int qlog2 = -1;
-  float q_per_m = 0.f;
-  if ((h->cfg.flags & DTSIM_F_RENDER) && tex_w == tex_h && tex_w >= 2) {
-    const int S = tex_w;
-    qlog2 = 0; while ((1 << qlog2) < S) ++qlog2;
-    std::vector<int> block_of((size_t)std::max(h->n_tex, 1) * 4, -1);
-    // the two one-record blocks: off-grid (meta high half 1) and untextured (meta 0); then the S x S blocks
-    const uint32_t special[8] = {0u, 0u, 0u, 1u << 16, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u};   // untextured: white vertex colour
-    qblocks.assign(special, special + 8);
-    const size_t block_bytes = (size_t)S * S * 16;
-    // second dword of a table entry: the mask of the record's byte offset inside its block (S = 256, q8_rec256) / of the cell number (other sizes): 0 for the
-    // two one-record blocks.  S = 256: the blocks start at multiples of 1 MB (the offset is OR-ed in), the first one holds the two special records only.
-    const uint32_t cell_sel = (qlog2 == 8) ? 0xFFFFFu : (uint32_t)(S * S - 1);
-    const uint32_t zero_sel = 0u;
-    if (qlog2 == 8) qblocks.resize(block_bytes / 4, 0u);
-    int n_blocks = 0;
-    for (int mi = 0; mi < n_maps; ++mi) {
-      const dtsim_map& mp = maps[mi];
-      RenderMapDev& rm = rmaps[mi];
-      rm.qt_off = (int32_t)(qtiles.size() / 2); rm.qt_pitch = mp.grid_w + 2 * DT_QRING;
-      q_per_m = std::max(q_per_m, (float)((double)S / mp.tile_size));
-      for (int j = -DT_QRING; j < mp.grid_h + DT_QRING; ++j)
-        for (int i = -DT_QRING; i < mp.grid_w + DT_QRING; ++i) {
-          uint32_t off = 0u, sel = zero_sel;        // record 0: off-grid
-          if (i >= 0 && j >= 0 && i < mp.grid_w && j < mp.grid_h) {
-            const int t = j * mp.grid_w + i;
-            if (mp.tile_kind[t] != DTSIM_TILE_EMPTY) {
-              const int tx = mp.tile_tex[t];
-              if (tx < 0 || tx >= (int)h->h_tex.size()) off = 16u;   // record 1: present but untextured
-              else {
-                int& b = block_of[(size_t)tx * 4 + (mp.tile_angle[t] & 3)];
-                if (b < 0) { b = n_blocks++; build_quad_block(qblocks, h->h_pool.data() + h->h_tex[tx].off, S, mp.tile_angle[t] & 3); }
-                off = (qlog2 == 8) ? (uint32_t)((size_t)(b + 1) << 20) : (uint32_t)(32 + (size_t)b * block_bytes); sel = cell_sel;
-              }
-            }
-          }
-          qtiles.push_back(off); qtiles.push_back(sel);
-        }
-    }
-    if (32 + (size_t)(n_blocks + 1) * block_bytes >= ((size_t)1 << 32)) qlog2 = -1;   // 32-bit block offsets
-    for (int mi = 0; mi < n_maps; ++mi)                                           // quad coordinates below 32768 (render.hip, Q8_SNAP): else the generic raster
-      if ((size_t)(std::max(maps[mi].grid_w, maps[mi].grid_h) + 2 * DT_QRING) * S >= 32768) qlog2 = -1;
-  }
-  M.total_words = (int32_t)blobs.size();
-  if ((size_t)M.total_words * 8 > 60000)
-    return fail(DTSIM_E_LIMIT, "map tables %zu B exceed the 60 KB LDS staging budget", (size_t)M.total_words * 8);
-  if (trecs.size() > DTSIM_LDS_TILES)
-    return fail(DTSIM_E_LIMIT, "%zu tiles over all maps exceed the %d LDS raster records", trecs.size(), DTSIM_LDS_TILES);
-  int max_tris = 0;
-  for (auto& rm : rmaps) max_tris = std::max(max_tris, rm.n_tris);
-  DevPtr<uint64_t> d_blobs;
-  DevPtr<DynInit> d_dyn;
-  DevPtr<RenderMapDev> d_rmaps;
-  DevPtr<uint32_t> d_rtiles, d_qtiles;
-  DevPtr<ObjInstDev> d_robjs;
-  DevPtr<TileLds> d_tilerecs;
-  DevPtr<uint8_t> d_qtex;
-  DevPtr<char> obj_slabs[DT_SLABS];
-  HIPCHK(dev_upload(d_blobs, blobs.data(), blobs.size()));
-  HIPCHK(dev_upload(d_dyn, dyn.data(), dyn.size()));
-  HIPCHK(dev_upload(d_rmaps, rmaps.data(), rmaps.size()));
-  HIPCHK(dev_upload(d_rtiles, rtiles.data(), rtiles.size(), 1));
-  HIPCHK(dev_upload(d_robjs, robjs.data(), robjs.size(), 1));
-  HIPCHK(dev_upload(d_tilerecs, trecs.data(), trecs.size(), 1));
-  if (qlog2 <= 0 || qtiles.empty()) { qblocks.clear(); qtiles.clear(); qlog2 = 0; q_per_m = 0.f; }   // no quad records: the generic raster
-  HIPCHK(dev_upload(d_qtex, reinterpret_cast<const uint8_t*>(qblocks.data()), qblocks.size() * 4));
-  HIPCHK(dev_upload(d_qtiles, qtiles.data(), qtiles.size()));
-  size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, bytes);
+  MapSlot next;
+  static_cast<MapScalars&>(next) = T;
+  HIPCHK(dev_upload(next.d_blobs, T.blobs.data(), T.blobs.size()));
+  HIPCHK(dev_upload(next.d_dyn, T.dyn.data(), T.dyn.size()));
+  HIPCHK(dev_upload(next.d_rmaps, T.rmaps.data(), T.rmaps.size()));
+  HIPCHK(dev_upload(next.d_rtiles, T.rtiles.data(), T.rtiles.size(), 1));
+  HIPCHK(dev_upload(next.d_robjs, T.robjs.data(), T.robjs.size(), 1));
+  HIPCHK(dev_upload(next.d_tilerecs, T.trecs.data(), T.trecs.size(), 1));
+  HIPCHK(dev_upload(next.d_qtex, reinterpret_cast<const uint8_t*>(T.qblocks.data()), T.qblocks.size() * 4));
+  HIPCHK(dev_upload(next.d_qtiles, T.qtiles.data(), T.qtiles.size()));
+  size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, T.max_tris, bytes);
   for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i)     // the object slabs: only with mesh objects
-    if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(dev_alloc(obj_slabs[i], bytes[i]));
+    if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(dev_alloc(next.d_obj[i], bytes[i]));
   // worlds must be re-created against the new maps
   HIPCHK(hipMemsetAsync(h->A.map_id, 0xFF, sizeof(int32_t) * (size_t)h->N, h->stream));
-  h->d_blobs = std::move(d_blobs); h->d_dyn = std::move(d_dyn);
-  M.blobs = h->d_blobs.get();
-  M.dyn = h->d_dyn.get();
-  h->M = M;
-  for (int mi = 0; mi < n_maps; ++mi) { h->map_w[mi] = maps[mi].grid_w; h->map_h[mi] = maps[mi].grid_h; }
-  h->d_rmaps = std::move(d_rmaps); h->d_rtiles = std::move(d_rtiles); h->d_robjs = std::move(d_robjs);
-  h->d_tilerecs = std::move(d_tilerecs);
-  h->n_tilerecs = (int)trecs.size();
-  h->tex_w = tex_w ? tex_w : 1; h->tex_h = tex_h ? tex_h : 1;
-  h->d_qtex = std::move(d_qtex); h->d_qtiles = std::move(d_qtiles);
-  h->n_qtiles = (int)qtiles.size() / 2; h->qlog2 = qlog2; h->q_per_m = q_per_m;
-  for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i) h->d_render[i] = std::move(obj_slabs[i]);
-  h->max_tris = max_tris;
+  next.M.blobs = next.d_blobs.get();
+  next.M.dyn = next.d_dyn.get();
+  next.renderable = true;
+  h->maps = std::move(next);
   h->have_maps = true;
   h->have_reset = false;
   return DTSIM_OK;
@@ -714,24 +457,8 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
   if (rmapx && !(h->cfg.flags & DTSIM_F_DISTORTION)) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_DISTORTION");
   HIPCHK(hipSetDevice(h->cfg.device));
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
-  std::vector<float> lut((size_t)W * H * 4);
-  for (int r = 0; r < H; ++r)
-    for (int c = 0; c < W; ++c) {
-      long sx = c, sy = r;
-      if (rmapx) {
-        // cv2.remap(INTER_NEAREST): cvRound = round-half-to-even of the float map
-        // (distortion.py:118-124); outside the source image => BORDER_CONSTANT 0.
-        sx = std::lrint((double)rmapx[(size_t)r * W + c]);
-        sy = std::lrint((double)rmapy[(size_t)r * W + c]);
-      }
-      float* o = &lut[((size_t)r * W + c) * 4];
-      const bool ok = sx >= 0 && sx < W && sy >= 0 && sy < H;
-      // NDC of the centre of rectilinear pixel (sy, sx); row 0 = image top (simulator.py:1949)
-      o[0] = ok ? (float)((2.0 * (sx + 0.5)) / W - 1.0) : 0.f;
-      o[1] = ok ? (float)(1.0 - (2.0 * (sy + 0.5)) / H) : 0.f;
-      o[2] = ok ? 1.f : 0.f;
-      o[3] = 0.f;
-    }
+  std::vector<float> lut;
+  dt_pack_lut(W, H, rmapx, rmapy, lut);
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(dev_upload(h->d_lut, lut.data(), lut.size()));
   drop_luts(h);
@@ -802,7 +529,7 @@ static int check_states(const dtsim* h, const dtsim_init_state* st, int n, const
   for (int e = 0; e < n; ++e) {
     if (mask && !mask[e]) continue;
     const int mid = st[e].map_id & ~DTSIM_MAP_RELOAD;
-    if (st[e].map_id < 0 || mid >= h->M.n_maps) return fail(DTSIM_E_INVALID, "state %d: map_id %d out of range", e, st[e].map_id);
+    if (st[e].map_id < 0 || mid >= h->maps.M.n_maps) return fail(DTSIM_E_INVALID, "state %d: map_id %d out of range", e, st[e].map_id);
   }
   return DTSIM_OK;
 }
@@ -818,10 +545,10 @@ int dtsim_set_reset_sampler(dtsim_t* h, const dtsim_reset_sampler* sampler) {
   if (!h->have_maps) return fail(DTSIM_E_STATE, "dtsim_set_reset_sampler before dtsim_set_maps");
   if (sampler->max_attempts <= 0 || !(sampler->accept_start_angle_deg > 0))
     return fail(DTSIM_E_INVALID, "sampler: max_attempts %d, accept_start_angle_deg %g", sampler->max_attempts, sampler->accept_start_angle_deg);
-  for (int m = 0; m < h->M.n_maps; ++m) {
+  for (int m = 0; m < h->maps.M.n_maps; ++m) {
     const int i = sampler->start_tile[m][0], j = sampler->start_tile[m][1];
     if (i < 0) continue;
-    if (i >= h->map_w[m] || j < 0 || j >= h->map_h[m]) return fail(DTSIM_E_INVALID, "sampler: start tile (%d,%d) outside map %d", i, j, m);
+    if (i >= h->maps.grid_w[m] || j < 0 || j >= h->maps.grid_h[m]) return fail(DTSIM_E_INVALID, "sampler: start tile (%d,%d) outside map %d", i, j, m);
   }
   HIPCHK(dev_upload(h->d_sampler, sampler, 1));
   return DTSIM_OK;
@@ -835,7 +562,7 @@ int dtsim_reset_done(dtsim_t* h) {
   HIPCHK(hipSetDevice(h->cfg.device));
   {
     ProfScope ps(h, DTSIM_KERNEL_RESET);
-    dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), h->A.done, nullptr);   // mask = the done flags, on the device
+    dt_launch_reset(h->stream, h->A, h->maps.M, step_params(h, 0), h->A.done, nullptr);   // mask = the done flags, on the device
   }
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
@@ -851,7 +578,7 @@ int dtsim_reset(dtsim_t* h, const uint8_t* mask, const dtsim_init_state* states)
     if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.get(), mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
     {
       ProfScope ps(h, DTSIM_KERNEL_RESET);
-      dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, nullptr);
+      dt_launch_reset(h->stream, h->A, h->maps.M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, nullptr);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -865,13 +592,12 @@ int dtsim_reset(dtsim_t* h, const uint8_t* mask, const dtsim_init_state* states)
   if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.get(), mask, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
   {
     ProfScope ps(h, DTSIM_KERNEL_RESET);
-    dt_launch_reset(h->stream, h->A, h->M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, h->d_states.get());
+    dt_launch_reset(h->stream, h->A, h->maps.M, step_params(h, 0), mask ? h->d_mask.get() : nullptr, h->d_states.get());
   }
   HIPCHK(hipGetLastError());
   // the host buffers may be reused by the caller as soon as we return
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (!mask) h->have_reset = true;
-  else h->have_reset = true;
+  h->have_reset = true;
   return DTSIM_OK;
 }
 
@@ -914,7 +640,7 @@ int dtsim_step_ex(dtsim_t* h, const void* actions, int n_steps, int actions_on_d
     ProfScope ps(h, DTSIM_KERNEL_STEP);
     StepParams sp = step_params(h, n_steps);
     sp.step_flags = flags;
-    dt_launch_step(h->stream, h->A, h->M, sp, dptr, h->d_pool.get());
+    dt_launch_step(h->stream, h->A, h->maps.M, sp, dptr, h->d_pool.get());
   }
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
@@ -938,26 +664,20 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
   if (!h->have_maps || !h->have_reset) return fail(DTSIM_E_STATE, "dtsim_render before dtsim_set_maps/dtsim_reset");
   if (!h->have_lut) return fail(DTSIM_E_STATE, "DTSIM_F_DISTORTION set but dtsim_set_distortion_lut was not called");
+  if (int rc = check_renderable(h, "dtsim_render")) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   RenderParams R{};
   R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height;
   R.distortion = (h->cfg.flags & DTSIM_F_DISTORTION) ? 1 : 0;
   R.domain_rand = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) ? 1 : 0;
-  R.n_maps = h->M.n_maps;
   R.frames = h->n_cal ? h->d_scratch.get() : h->frames;   // camera_rand: the rectilinear frames, gathered into `frames` below
-  R.lut = h->d_lut.get(); R.texels = segment ? h->d_texels_seg.get() : h->d_texels.get(); R.tex = h->d_tex.get();
+  R.lut = h->d_lut.get();
   R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg.get();
-  R.maps = h->d_rmaps.get(); R.tiles = h->d_rtiles.get(); R.objs = h->d_robjs.get(); R.meshes = h->d_meshes.get(); R.tris = h->d_tris.get();
-  R.max_tris = h->d_render[DT_SLAB_STRIS] ? h->max_tris : 0;
+  render_scene(h, segment, &R);
   render_scratch(h, R.max_tris, &R);
   R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
-  R.tile_recs = h->d_tilerecs.get(); R.n_tile_recs = h->n_tilerecs; R.tex_w = h->tex_w; R.tex_h = h->tex_h;
-  R.qtex = (flags & DTSIM_RENDER_GL_FILTER) ? nullptr : h->d_qtex.get();   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
-  R.qtiles = h->d_qtiles.get(); R.n_qtiles = h->n_qtiles; R.qlog2 = h->qlog2; R.q_per_m = h->q_per_m;
-  int grid_rows = 0, grid_cols = 0;                  // the largest padded tile grid of the maps
-  for (int mi = 0; mi < h->M.n_maps; ++mi) { grid_rows = std::max(grid_rows, h->map_h[mi] + 2 * DT_QRING); grid_cols = std::max(grid_cols, h->map_w[mi] + 2 * DT_QRING); }
-  R.qmax_tiles = std::max(grid_rows, grid_cols);
-  const int pipe = dt_raster_pipe(R, grid_rows, grid_cols, h->raster_old);
+  if (flags & DTSIM_RENDER_GL_FILTER) R.qtex = nullptr;   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
+  const int pipe = dt_raster_pipe(R, h->maps.grid_rows, h->maps.grid_cols, h->raster_old);
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
     h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, mask);
@@ -973,6 +693,7 @@ int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int
   if (!h || (n > 0 && !lines)) return fail(DTSIM_E_INVALID, "null argument");
   if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  if (int rc = check_renderable(h, "dtsim_draw_lines")) return rc;
   if (!h->have_maps || !h->have_reset || !h->have_lut || !h->rendered) return fail(DTSIM_E_STATE, "dtsim_draw_lines before the first dtsim_render (the pass writes the cameras the lines go through)");
   if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_lines after dtsim_render_masked: the post-passes need a full dtsim_render");
   if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_lines with per-env distortion tables installed (the overlays read the single table)");
@@ -1009,6 +730,7 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
   if (!h || (n > 0 && !spheres)) return fail(DTSIM_E_INVALID, "null argument");
   if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
   if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  if (int rc = check_renderable(h, "dtsim_draw_leds")) return rc;
   if (!h->rendered || !h->leds_ok || h->last_segment) return fail(DTSIM_E_STATE, "dtsim_draw_leds needs a preceding dtsim_render (colour view): it tests the spheres against that pass's scene");
   if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_leds after dtsim_render_masked: the post-passes need a full dtsim_render");
   if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_leds with per-env distortion tables installed (the overlays read the single table)");
@@ -1178,7 +900,7 @@ int dtsim_query(dtsim_t* h, int n, const int32_t* env_idx, const double* poses, 
   HIPCHK(hipMemcpyAsync(h->d_qpose.get(), poses, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
   {
     ProfScope ps(h, DTSIM_KERNEL_QUERY);
-    dt_launch_query(h->stream, h->A, h->M, step_params(h, 0), n, h->d_qenv.get(), h->d_qpose.get(), safety_factor, h->d_qout.get());
+    dt_launch_query(h->stream, h->A, h->maps.M, step_params(h, 0), n, h->d_qenv.get(), h->d_qpose.get(), safety_factor, h->d_qout.get());
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, h->d_qout.get(), sizeof(dtsim_probe) * n, hipMemcpyDeviceToHost, h->stream));

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "../../include/dtsim.h"
 #include "observe_plan.h"
+#include "scene_tables.h"
 
 // ---- constants of the reference (simulator.py:99-177), evaluated exactly as
 // Python evaluates them (IEEE double, same operation order) -------------------
@@ -23,36 +24,6 @@
 #define DT_SAFETY_RAD_MULT 1.8
 #define DT_AGENT_SAFETY_RAD ((DT_ROBOT_LENGTH / 2) * DT_SAFETY_RAD_MULT) /* max(L,W)=L */
 #define DT_REWARD_INVALID_POSE (-1000.0)
-
-// ---- packed map blob --------------------------------------------------------
-struct MapHdr {            // 8-byte words; offsets are in words from the blob start
-  int32_t grid_w, grid_h;
-  int32_t n_curves, n_static;
-  int32_t n_dyn, n_obj;
-  int32_t off_tiles, off_curves;   // tiles: 1 word each; curves: 8 words each (P0x,P0z..P3x,P3z)
-  int32_t off_heads, off_static;   // heads: 2 words per curve; static: 15 words each
-  int32_t off_objs, total_words;   // objs: OBJ_WORDS words each
-  int32_t n_lights, pad_l;         // traffic lights among the objects (0: k_step skips the light clock)
-  double tile_size;
-};
-static_assert(sizeof(MapHdr) % 8 == 0, "MapHdr must be whole words");
-#define MAPHDR_WORDS (sizeof(MapHdr) / 8)
-
-struct TileRec {           // one 8-byte word
-  uint8_t kind, angle, drivable, curve_cnt;
-  int16_t curve_off, tex;
-};
-static_assert(sizeof(TileRec) == 8, "TileRec is one word");
-
-// static collidable record: corners[8] norms[4] center[2] radius[1]
-#define STATIC_WORDS 15
-#define OBJ_WORDS 6      // x, z, spawn_clear, dyn_slot (-1 static, -2 optional static), light_freq, light_pattern0
-
-struct DynInit {           // per map, per dynamic slot: initial DuckieObj state
-  double cx, cz, corners[8], norm[4], heading_x, heading_z, angle, safety_radius;
-  double walk_distance, vel, wait_time, wiggle;   // DuckieObj; DuckiebotObj: follow_dist, velocity, gain, trim
-  int32_t obj_index, kind;                        // kind: 1 DuckieObj, 2 DuckiebotObj, 3 CheckerboardObj
-};
 
 // ---- per-env SoA ------------------------------------------------------------
 struct SimArrays {
@@ -97,15 +68,6 @@ struct StepParams {
   double gain, trim, radius, k, limit;
 };
 
-// All maps, device side
-struct MapSet {
-  int32_t n_maps;
-  int32_t blob_off[DTSIM_MAX_MAPS];   // word offset of each map blob inside `blobs`
-  int32_t total_words;
-  const uint64_t* blobs;
-  const DynInit* dyn;                 // [n_maps][DTSIM_MAX_DYNAMIC]
-};
-
 // launchers implemented in physics.hip
 void dt_launch_step(hipStream_t s, const SimArrays& A, const MapSet& M, const StepParams& P,
                     const void* actions, const dtsim_init_state* pool);
@@ -115,34 +77,6 @@ void dt_launch_query(hipStream_t s, const SimArrays& A, const MapSet& M, const S
                      const int32_t* env_idx, const double* poses, double safety_factor, dtsim_probe* out);
 
 // ---- raster -----------------------------------------------------------------
-struct TexDev { int32_t w, h, off, pad; };   // off: texel offset into the texel pool; storage is (h+1) x (w+1), padded for REPEAT
-struct MeshDev { int32_t n_tris, off; float mn[3], mx[3]; };   // off: triangle offset into the pool; model-space AABB
-struct TriDev { float v[3][3]; float n[3][3]; float c[3][3]; float uv[3][2]; int32_t tex, pad; };   // tex: texture index or -1
-
-struct RenderMapDev {       // per map, raster view of the grid + objects
-  int32_t grid_w, grid_h, n_obj, n_tris;   // n_tris: total mesh triangles of the map's objects
-  float tile_size, inv_tile_size;
-  int32_t tile_off;         // offset into tile table (uint32 per tile: tex | angle<<8 | present<<15)
-  int32_t obj_off;          // offset into object-instance table
-  int32_t qt_off, qt_pitch; // quad-texture tile table of the map: first entry, row pitch (grid_w + 2*DT_QRING)
-};
-
-struct ObjInstDev {         // static render instance (dynamic ones are patched per env)
-  float x, y, z, scale, yrot_deg;
-  int32_t mesh_id, dyn_slot;
-  int32_t light_tris, light_tex0, light_tex1;   // traffic light: first `light_tris` triangles take texture 0 / 1 by pattern
-  int32_t pad[2];
-};
-static_assert(sizeof(ObjInstDev) == 48, "ObjInstDev is 48 bytes");
-
-// LDS-staged raster tile record: texel base of the (padded) texture, flags (bit0 present,
-// bit1 textured), and the affine map tile-fraction (fx, fz) -> texel coordinates
-// x = mxx*fx + mxz*fz + ox, y = myx*fx + myz*fz + oy encoding glRotatef(angle*90+180)
-// about y, uv = (pu, 1-pv) (simulator.py:394-401,1872-1873) and the GL_LINEAR half-texel shift.
-struct alignas(16) TileLds { uint32_t tex_off, flags; float mxx, mxz, ox, myx, myz, oy; };
-static_assert(sizeof(TileLds) == 32, "TileLds is 32 bytes");
-#define DTSIM_LDS_TILES 1024   // raster tile records of all maps together (32 KB of LDS)
-
 // One mesh triangle of one env after model/view/projection and per-vertex lighting
 // (objects.py:123-148, objmesh.py:360-375): rectilinear pixel coordinates, 1/w, lit colour/w.
 struct alignas(16) ScreenTri {
@@ -180,14 +114,6 @@ struct ObjBox { float bx0, bx1, by0, by1; int32_t first, count, pad[2]; };      
 #define DT_ITEM_B 8                          // 64-entry edge batches per k_resolve work item
 #endif
 #define DT_ITEMS_PER_WG (4 * (DT_PPT * DT_ENVS_PER_BLOCK) / DT_ITEM_B) // worst case: 4 regions x (64*PPT px x envs / 64) batches
-// Quad-layout tile textures for the one-ray fast path (render.hip k_raster_q): per (texture, tile angle) pair one
-// block of S x S records of 16 bytes, record (x0, z0) = the four GL_LINEAR taps of the pre-rotated tile texture around
-// quad cell (x0, z0) as channel-planar bytes {R00 R10 R01 R11}, {G..}, {B..} + a meta dword (see DT_QMETA_*).
-#define DT_QRING 4                           // ring of off-grid cells around each map's tile table, in tiles
-// The pool starts with two single records every cell of a non-textured tile maps to: record 0 = off the grid (ground
-// quad / sky), record 1 = present but untextured tile (exact path).
-// DT_QMETA -- meta dword: low 16 bits = cells to the nearest tile boundary if the cell belongs to a textured tile (else 0),
-// high 16 bits = 1 if the cell is off the grid (else 0); 0 / 0 = always the exact path.
 static inline size_t dt_raster_tiles(int W, int H) {
   return (size_t)((W + DT_TILE_W - 1) / DT_TILE_W) * (size_t)((H + DT_TILE_H - 1) / DT_TILE_H);
 }

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -25,6 +26,71 @@ class DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2, "strides": None}
         self._owner = owner
+
+
+def load_scene(library, map_names, datas, transform_uses_width=False, render=True):
+    """Host prep of the maps `datas` (MapFormat1 dicts named map_names) against `library`: what scene_ffi takes, as attributes --
+    meshes, mesh_order, texture_kinds, textures, mesh_tex_base, light_tex, maps."""
+    use_lib = library if library.root else None
+    meshes: Dict[str, assets.MeshData] = {"duckie": assets.get_mesh("duckie"), "*": assets.get_mesh("*")}
+    first = [maps.interpret_map(d, n, meshes, transform_uses_width, library=use_lib) for d, n in zip(datas, map_names)]
+    mesh_order = list(meshes)                      # "duckie", "*", then every object mesh the library loaded
+    tex_kinds: List[str] = []
+    for mt in first:
+        for kd in mt.texture_kinds:
+            if kd not in tex_kinds:
+                tex_kinds.append(kd)
+    tile_tex = [library.tile_texture(kd) for kd in tex_kinds]
+    if tile_tex:                                   # the raster needs one size for all tile textures
+        side = max(max(t.shape[0], t.shape[1]) for t in tile_tex)
+        tile_tex = [assets.to_pow2(t, side) if t.shape[:2] != (side, side) else t for t in tile_tex]
+    textures = list(tile_tex)
+    mesh_tex_base: Dict[str, int] = {}             # mesh key -> index of its first texture
+    for mk in mesh_order:
+        mesh_tex_base[mk] = len(textures)
+        textures.extend(meshes[mk].textures)
+    light_tex = (-1, -1)                           # traffic-light cards (only when a map has lights and the tree has cards)
+    if any(o.light_freq > 0 for mt in first for o in mt.objects):
+        cards = library.light_cards()
+        if cards is not None:
+            light_tex = (len(textures), len(textures) + 1)
+            textures.extend(cards)
+    tex_ids = {kd: i for i, kd in enumerate(tex_kinds)} if render else None
+    map_tables = [maps.interpret_map(d, n, meshes, transform_uses_width, texture_ids=tex_ids, library=use_lib)
+                  for d, n in zip(datas, map_names)]
+    return SimpleNamespace(meshes=meshes, mesh_order=mesh_order, texture_kinds=tex_kinds, textures=textures, mesh_tex_base=mesh_tex_base,
+                           light_tex=light_tex, maps=map_tables)
+
+
+def scene_ffi(sc, render=True):
+    """The arguments of dtsim_set_assets and dtsim_set_maps for load_scene's `sc`: (Texture array, Mesh array, Map array, keep).  The
+    ctypes arrays borrow numpy arrays: `keep` and `sc` must outlive their use.  render=False: no assets (null arrays), and maps that
+    name no mesh or light texture."""
+    textures, meshes, mesh_order, mesh_tex_base = sc.textures, sc.meshes, sc.mesh_order, sc.mesh_tex_base
+    keep = []
+    tarr = marr = None
+    if render:
+        tarr = (_ffi.Texture * max(len(textures), 1))()
+        for i, t in enumerate(textures):
+            tarr[i].width, tarr[i].height = t.shape[1], t.shape[0]
+            tarr[i].rgba = t.ctypes.data_as(C.POINTER(C.c_uint8))
+        marr = (_ffi.Mesh * len(mesh_order))()
+        for i, mk in enumerate(mesh_order):
+            m = meshes[mk]
+            marr[i].n_tris = m.n_tris
+            marr[i].verts = m.verts.ctypes.data_as(C.POINTER(C.c_float))
+            marr[i].normals = m.normals.ctypes.data_as(C.POINTER(C.c_float))
+            marr[i].colors = m.colors.ctypes.data_as(C.POINTER(C.c_float))
+            if m.textures:
+                gt = np.where(m.tri_tex >= 0, m.tri_tex + mesh_tex_base[mk], -1).astype(np.int32)
+                keep.append(gt)
+                marr[i].uvs = m.uvs.ctypes.data_as(C.POINTER(C.c_float))
+                marr[i].tri_tex = gt.ctypes.data_as(C.POINTER(C.c_int32))
+    mesh_ids = {mk: i for i, mk in enumerate(mesh_order)} if render else {}
+    farr = (_ffi.Map * len(sc.maps))()
+    for i, mt in enumerate(sc.maps):
+        farr[i] = mt.to_ffi(mesh_ids, sc.light_tex if render else (-1, -1))
+    return tarr, marr, farr, keep
 
 
 class BatchedSimulator:
@@ -117,64 +183,17 @@ class BatchedSimulator:
         # with the deterministic fixtures of dtsim/assets.py as the fallback.
         self.state_version = 0
         self.library = assets.AssetLibrary(asset_root, style)
-        use_lib = self.library if self.library.root else None
         names = [map_name] if isinstance(map_name, str) else list(map_name)
         datas = [map_data] if (map_data is not None) else [self.library.map_data(n) for n in names]
         self.map_names = [assets.map_basename(n) for n in names]
         self.map_datas, self._ctor_map_names = datas, names
-        self.meshes: Dict[str, assets.MeshData] = {"duckie": assets.get_mesh("duckie"), "*": assets.get_mesh("*")}
-        first = [maps.interpret_map(d, n, self.meshes, transform_uses_width, library=use_lib)
-                 for d, n in zip(datas, self.map_names)]
-        mesh_order = list(self.meshes)                 # "duckie", "*", then every object mesh the library loaded
-        self._mesh_order, self._have_segment_assets = mesh_order, False
-        tex_kinds: List[str] = []
-        for mt in first:
-            for kd in mt.texture_kinds:
-                if kd not in tex_kinds:
-                    tex_kinds.append(kd)
-        self.texture_kinds = tex_kinds
-        tile_tex = [self.library.tile_texture(kd) for kd in tex_kinds]
-        if tile_tex:                                   # the raster needs one size for all tile textures
-            side = max(max(t.shape[0], t.shape[1]) for t in tile_tex)
-            tile_tex = [assets.to_pow2(t, side) if t.shape[:2] != (side, side) else t for t in tile_tex]
-        self.textures = list(tile_tex)
-        mesh_tex_base: Dict[str, int] = {}             # mesh key -> index of its first texture
-        for mk in mesh_order:
-            mesh_tex_base[mk] = len(self.textures)
-            self.textures.extend(self.meshes[mk].textures)
-        self.light_tex = (-1, -1)                      # traffic-light cards (only when a map has lights and the tree has cards)
-        if any(o.light_freq > 0 for mt in first for o in mt.objects):
-            cards = self.library.light_cards()
-            if cards is not None:
-                self.light_tex = (len(self.textures), len(self.textures) + 1)
-                self.textures.extend(cards)
-        tex_ids = {kd: i for i, kd in enumerate(tex_kinds)} if render else None
-        self.maps: List[maps.MapTables] = [
-            maps.interpret_map(d, n, self.meshes, transform_uses_width, texture_ids=tex_ids, library=use_lib)
-            for d, n in zip(datas, self.map_names)]
+        sc = load_scene(self.library, self.map_names, datas, transform_uses_width, render)
+        self.meshes, self._mesh_order, self.texture_kinds, self.textures = sc.meshes, sc.mesh_order, sc.texture_kinds, sc.textures
+        self.light_tex, self.maps = sc.light_tex, sc.maps
+        self._have_segment_assets = False
+        tarr, marr, farr, self._scene_keep = scene_ffi(sc, render)
         if render:
-            keep = []
-            tarr = (_ffi.Texture * max(len(self.textures), 1))()
-            for i, t in enumerate(self.textures):
-                tarr[i].width, tarr[i].height = t.shape[1], t.shape[0]
-                tarr[i].rgba = t.ctypes.data_as(C.POINTER(C.c_uint8))
-            marr = (_ffi.Mesh * len(mesh_order))()
-            for i, mk in enumerate(mesh_order):
-                m = self.meshes[mk]
-                marr[i].n_tris = m.n_tris
-                marr[i].verts = m.verts.ctypes.data_as(C.POINTER(C.c_float))
-                marr[i].normals = m.normals.ctypes.data_as(C.POINTER(C.c_float))
-                marr[i].colors = m.colors.ctypes.data_as(C.POINTER(C.c_float))
-                if m.textures:
-                    gt = np.where(m.tri_tex >= 0, m.tri_tex + mesh_tex_base[mk], -1).astype(np.int32)
-                    keep.append(gt)
-                    marr[i].uvs = m.uvs.ctypes.data_as(C.POINTER(C.c_float))
-                    marr[i].tri_tex = gt.ctypes.data_as(C.POINTER(C.c_int32))
-            _ffi.check(self._lib, self._lib.dtsim_set_assets(self._h, tarr, len(self.textures), marr, len(mesh_order)))
-        mesh_ids = {mk: i for i, mk in enumerate(mesh_order)} if render else {}
-        farr = (_ffi.Map * len(self.maps))()
-        for i, mt in enumerate(self.maps):
-            farr[i] = mt.to_ffi(mesh_ids, self.light_tex if render else (-1, -1))
+            _ffi.check(self._lib, self._lib.dtsim_set_assets(self._h, tarr, len(self.textures), marr, len(sc.mesh_order)))
         _ffi.check(self._lib, self._lib.dtsim_set_maps(self._h, farr, len(self.maps)))
         self.undistort = bool(undistort and distortion)
         self._skip_distort = False

@@ -282,7 +282,11 @@ void dtsim_destroy(dtsim_t* h);
 
 /* The setters -- dtsim_set_assets, dtsim_set_maps, dtsim_set_distortion_lut(s), dtsim_set_reset_sampler, dtsim_set_spawn_pool,
  * dtsim_set_segment_assets -- and the table caches of dtsim_observe / dtsim_observe_cubic: on failure the handle keeps what it
- * had.  Only what the last render pass left for the post-passes may be dropped: dtsim_draw_leds then waits for a dtsim_render. */
+ * had.  Only what the last render pass left for the post-passes may be dropped: dtsim_draw_leds then waits for a dtsim_render.
+ * dtsim_set_maps packs the maps against the assets installed at that moment (texture, mesh and triangle indices), so the order is
+ * dtsim_set_assets, then dtsim_set_maps.  A dtsim_set_assets that succeeds while maps are installed releases their render-side
+ * tables: physics, reset, query and the reset sampler go on from the maps, and dtsim_render*, dtsim_draw_lines and dtsim_draw_leds
+ * return DTSIM_E_STATE until the next dtsim_set_maps. */
 
 /* Textures (graphics.py:69-169 load_texture) and meshes (objmesh.py:62-293). */
 int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures,
