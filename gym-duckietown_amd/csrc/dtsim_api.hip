@@ -319,6 +319,7 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
   // lanes of a wavefront per env in k_step: as many (up to 4) as keep the launch within ~32 K threads -- a small batch is a
   // latency problem (one f64 chain per env, 64 wavefronts on 1024 SIMDs at N = 4096), a large one a throughput problem,
   // where the redundant lanes would cost (profiles/r03_c2_lanes_ab.txt)
+  // (tests/test_gpu_step_lanes.py runs one batch size per lane count: move N_LANES_4 / N_LANES_2 / N_LANES_1 there with these thresholds)
   h->step_lanes = cfg->num_envs * 4 <= 32768 ? 4 : cfg->num_envs * 2 <= 32768 ? 2 : 1;
   h->cfg = *cfg;
   h->N = cfg->num_envs;
