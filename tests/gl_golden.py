@@ -20,11 +20,21 @@ def cases():
     return sorted(os.path.basename(p)[len("ref_gl_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "ref_gl_*.npz")))
 
 
-def load(case):
-    z = np.load(os.path.join(GOLDEN, f"ref_gl_{case}.npz"))
+def _load(name):
+    z = np.load(os.path.join(GOLDEN, f"{name}.npz"))
     d = {k: z[k] for k in z.files}
     d["meta"] = json.loads(str(d["meta"]))
     return d
+
+
+def load(case):
+    return _load(f"ref_gl_{case}")
+
+
+# the later-episode goldens without domain randomisation (tests/golden/make_lightcap.py; outside the glob of cases() on purpose)
+LIGHTCAP_RESET_CASES = ["lightcap_small_loop_t256_160", "lightcap_small_loop_t256_640", "lightcap_town_t128_320"]
+LIGHTCAP_FLOW = "lightcap_flow_t256_160"
+load_lightcap = _load
 
 
 _scenes = {}
@@ -112,12 +122,6 @@ def oracle_frame(d, k, lighting="gouraud", with_lines=True):
     return raster.render_obs(cam, scene, lighting, obj_states=obj_states(d, k))
 
 
-def stats(a, b):
-    e = np.abs(a.astype(np.int32) - b.astype(np.int32))
-    m = e.max(axis=-1)
-    return dict(mean=float(e.mean()), gt1=float((m > 1).mean()), gt2=float((m > 2).mean()), gt8=float((m > 8).mean()), max=int(m.max()))
-
-
 def line_mask(d, k, grow=1):
     """Pixels of a "bbox" record that the GL_LINE_LOOPs may touch (the oracle with its lines against the oracle without, grown by `grow` pixels):
     the reference leaves texturing and lighting on while it draws them, so their COLOUR is not something dtsim
@@ -129,10 +133,3 @@ def line_mask(d, k, grow=1):
         g[1:] |= m[:-1]; g[:-1] |= m[1:]; g[:, 1:] |= m[:, :-1]; g[:, :-1] |= m[:, 1:]
         m = g
     return m
-
-
-def stats_masked(a, b, mask):
-    keep = ~mask
-    e = np.abs(a.astype(np.int32) - b.astype(np.int32))[keep]
-    m = e.max(axis=-1)
-    return dict(mean=float(e.mean()), gt1=float((m > 1).mean()), gt2=float((m > 2).mean()), gt8=float((m > 8).mean()), max=int(m.max()))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import gl_golden as G
+from frame_parity import ORACLE_GL, ORACLE_PIXEL_GL, REFERENCE_GL, assert_within, stats
 
 CASES = G.cases()
 
@@ -36,14 +37,14 @@ def test_oracle_raster_matches_reference_gl(case):
         if d["meta"].get("view") == "bbox":              # the debugging view: everything but the colour of its GL_LINE_LOOPs (see gl_golden.line_mask)
             mask = G.line_mask(d, k)
             assert 0.002 < mask.mean() < 0.08, mask.mean()
-            s = G.stats_masked(o, d["frame"][k], mask)
+            s = stats(o, d["frame"][k], mask)
             s["any"] = float(((o != d["frame"][k]).any(axis=-1) & ~mask).mean())
             lines_gl = (d["frame"][k][..., 0].astype(int) - d["frame"][k][..., 1] > 25) & mask     # the reference did draw reddish lines there
             assert lines_gl.sum() > 20, int(lines_gl.sum())
         else:
-            s = G.stats(o, d["frame"][k])
+            s = stats(o, d["frame"][k])
             s["any"] = float((o != d["frame"][k]).any(axis=-1).mean())
-        assert s["gt1"] <= 2e-3 and s["mean"] <= 0.02, (case, k, s)
+        assert_within(s, ORACLE_GL, (case, k))
         for key in worst:
             worst[key] = max(worst[key], s[key])
     print(f"\n{case}: worst frame of {len(ks)}: differing pixels {worst['any']:.5f}, beyond +-1 {worst['gt1']:.5f}, mean abs {worst['mean']:.5f} / 255")
@@ -54,8 +55,7 @@ def test_per_fragment_tile_light_is_within_one_level_of_gl():
     the oracle in "pixel" mode stays within +-1/255 of GL on >= 99.8 % of the pixels (the price of that design choice)."""
     d = G.load("small_loop_t256_160")
     for k in (0, 5, 9):
-        s = G.stats(G.oracle_frame(d, k, "pixel"), d["frame"][k])
-        assert s["gt1"] <= 2e-3 and s["mean"] <= 0.2, (k, s)
+        assert_within(stats(G.oracle_frame(d, k, "pixel"), d["frame"][k]), ORACLE_PIXEL_GL, k)
 
 
 def test_quad_filter_distance_to_gl():
@@ -67,10 +67,10 @@ def test_quad_filter_distance_to_gl():
         d = G.load(case)
         for k in ks:
             o = G.oracle_frame(d, k, "pixel")
-            s = G.stats(o, d["frame"][k])
+            s = stats(o, d["frame"][k])
             differ = float((o != d["frame"][k]).any(axis=-1).mean())
             print(f"\n{case}[{k}] byte-weight filter vs GL: pixels that differ {differ:.3f}, beyond +-1 {s['gt1']:.5f}, beyond +-2 {s['gt2']:.5f}, mean abs {s['mean']:.4f} / 255")
-            assert s["gt1"] <= 1e-2 and s["gt2"] <= 4e-3 and s["mean"] <= 0.35, (case, k, s)
+            assert_within(s, REFERENCE_GL, (case, k))
 
 
 @pytest.mark.parametrize("case", ["small_loop_t256_160", "small_loop_dr_t256_160", "town_t128_320", "town_dr_t128_320", "episode2_t256_160", "small_loop_t256_640"])
@@ -89,7 +89,7 @@ def test_gl_port_reproduces_the_reference_s_frames(case):
         got = r.render(d["pos"][k], float(d["angle"][k]), cam_height=float(d["cam_height"][k]), cam_angle_deg=float(d["cam_angle"][k]),
                        cam_fov_y_deg=float(d["cam_fov_y"][k]), camera_noise=d["camera_noise"][k], domain_rand=bool(d["meta"]["dr"]),
                        horizon=d["horizon"][k], ground=d["ground"][k], obj_states=G.obj_states(d, k))
-        assert np.array_equal(got, d["frame"][k]), (case, k, G.stats(got, d["frame"][k]))
+        assert np.array_equal(got, d["frame"][k]), (case, k, stats(got, d["frame"][k]))
 
 
 @pytest.mark.parametrize("case", ["small_loop_dr_t256_160", "episode2_t256_160", "town_dr_t128_320", "view_bbox_t256_320"])

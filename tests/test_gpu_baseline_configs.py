@@ -12,47 +12,19 @@
       every XCD's eighth of the chunks, the tail chunk), each rendered by the oracle directly.
 
 Reference: simulator.py:1707-1951 (_render_img), objects.py:384-431 (DuckieObj.step), envs/multimap_env.py:44-49.
-Thresholds ("Tolerances"): plane-only scenes 1e-3 / 5e-4 / 0.02 (fraction of pixels beyond +-1, beyond +-2, mean |error| in
-1/255); scenes with mesh objects 2e-3 / 1e-3 / 0.03 (silhouette pixels of the meshes flip coverage where float32 edge functions
-meet the oracle's float64 ones).  The oracle is oracle/raster.py in its "pixel" lighting mode.
+Thresholds ("Tolerances"; tests/frame_parity.py): ORACLE_PLANE for plane-only scenes; ORACLE_MESH for scenes with mesh objects
+(silhouette pixels of the meshes flip coverage where float32 edge functions meet the oracle's float64 ones).  The oracle is
+oracle/raster.py in its "pixel" lighting mode.
 """
 import numpy as np
 import pytest
 
 from dtsim import BatchedSimulator, _ffi
 from dtsim import distortion as pdist
-from oracle import raster
-from test_gpu_render import _camera, _obj_states, _scene, _stats
+from frame_parity import ORACLE_MESH, ORACLE_PLANE, compare_envs, frames_of, scene, stratified_picks
 
 pytestmark = pytest.mark.gpu
 W, H = 640, 480
-OBJ_TOL = dict(frac_gt1=2e-3, frac_gt2=1e-3, mean=0.03)     # scenes with mesh objects (DESIGN.md 4)
-
-
-def _stratified_picks(sim, N, n_min, seed):
-    """Env indices of an N-env batch that exercise the raster's work decomposition.  The decomposition goes by POSITION in the
-    render order of the pass that just ran (DTSIM_FIELD_RENDER_POS: k_env_sort's order on the quad-record paths, the identity
-    elsewhere): 64 consecutive positions (32 before round 6) share a workgroup chunk, XCD x owns the x-th eighth of the chunks (render_v3.inc:
-    XCD-affine workgroup map).  Picked positions: the first / last of the order, both sides of chunk borders, the middle of
-    every XCD's eighth (a chunk border there), the tail chunk -- mapped back to env indices -- plus envs 0 and N - 1."""
-    pos = sim.read(_ffi.FIELD_RENDER_POS)
-    assert sorted(pos.tolist()) == list(range(N))          # a permutation of the batch
-    env_at = np.argsort(pos, kind="stable")                # position -> env
-    at = [0, 1, 31, 32, 33, 63, 64, N - 1, N - 2, N - 32, N - 33]
-    for x in range(8):
-        m = x * (N // 8) + N // 16
-        at += [m - 1, m]
-    picks = [int(env_at[p]) for p in at if 0 <= p < N] + [0, N - 1]
-    rng = np.random.default_rng(seed)
-    while len(set(picks)) < n_min:
-        picks.append(int(rng.integers(N)))
-    return sorted(set(picks))
-
-
-def _frames_of(sim, picks):
-    import torch
-    frames = torch.as_tensor(sim.frames_device(), device="cuda:0")
-    return frames[torch.as_tensor(np.array(picks), device="cuda:0")].cpu().numpy()
 
 
 def test_c3_full_size_batch_matches_oracle_directly():
@@ -84,18 +56,7 @@ def test_c3_full_size_batch_matches_oracle_directly():
         picks.append(int(rng.integers(N)))
     picks = sorted(set(picks))
     assert len(picks) >= 64
-    import torch
-    frames = torch.as_tensor(sim.frames_device(), device="cuda:0")
-    sub = frames[torch.as_tensor(np.array(picks), device="cuda:0")].cpu().numpy()
-    scene = _scene("small_loop")
-    rmap = pdist.distortion_maps(W, H)
-    worst = dict(frac_gt1=0.0, frac_gt2=0.0, mean=0.0)
-    for k, e in enumerate(picks):
-        ref = raster.render_obs(_camera(sim, e, W, H, False), scene, "pixel", rmap)
-        s = _stats(sub[k], ref)
-        assert s["frac_gt1"] <= 1e-3 and s["frac_gt2"] <= 5e-4 and s["mean"] <= 0.02, (e, s)
-        for f in worst:
-            worst[f] = max(worst[f], s[f])
+    worst, _ = compare_envs(sim, frames_of(sim, picks), picks, scene("small_loop"), pdist.distortion_maps(W, H), ORACLE_PLANE, dr=False, mode="pixel")
     print("C3 4096-env batch, %d envs against the oracle: worst" % len(picks), worst)
     sim.close()
 
@@ -109,17 +70,8 @@ def test_c4_config_matches_oracle():
     assert sim.read(_ffi.FIELD_OBJ_ACTIVE).any()           # somebody is walking
     sim.render()
     frames = sim.frames_host()
-    scene = _scene("loop_pedestrians")
-    rmap = pdist.distortion_maps(W, H)
-    n_obj_px = 0
-    for e in range(N):
-        cam = _camera(sim, e, W, H, True)
-        st = _obj_states(sim, e, scene)
-        ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st)
-        no_obj = raster.render_obs(cam, scene, "pixel", rmap, obj_states=[dict(s_, visible=False) for s_ in st])
-        n_obj_px += int((np.abs(ref.astype(int) - no_obj.astype(int)).max(-1) > 0).sum())
-        s = _stats(frames[e], ref)
-        assert s["frac_gt1"] <= 2e-3 and s["frac_gt2"] <= 1e-3 and s["mean"] <= 0.03, (e, s)
+    _, n_obj_px = compare_envs(sim, frames, range(N), scene("loop_pedestrians"), pdist.distortion_maps(W, H), ORACLE_MESH, dr=True, mode="pixel",
+                               count_objects=N)
     assert n_obj_px > 200, n_obj_px
     sim.close()
 
@@ -139,18 +91,10 @@ def test_c5_config_matches_oracle():
     frames = sim.frames_host()
     mid = sim.read(_ffi.FIELD_MAP_ID)
     assert set(np.unique(mid)) == {0, 1} and mid[0] != mid[1]
-    scenes = [_scene(n) for n in names]
-    rmap = pdist.distortion_maps(W, H)
-    n_obj_px = 0
-    for e in (0, 1, 30, 31, 32, 33, 63, 64, 71):           # both maps, chunk borders (64 envs per chunk; 32 before round 6), the tail chunk
-        scene = scenes[int(mid[e])]
-        cam = _camera(sim, e, W, H, False)
-        st = _obj_states(sim, e, scene)
-        ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st)
-        no_obj = raster.render_obs(cam, scene, "pixel", rmap, obj_states=[dict(s_, visible=False) for s_ in st])
-        n_obj_px += int((np.abs(ref.astype(int) - no_obj.astype(int)).max(-1) > 0).sum())
-        s = _stats(frames[e], ref)
-        assert s["frac_gt1"] <= 2e-3 and s["frac_gt2"] <= 1e-3 and s["mean"] <= 0.03, (e, int(mid[e]), s)
+    scenes = [scene(n) for n in names]
+    envs = [0, 1, 30, 31, 32, 33, 63, 64, 71]              # both maps, chunk borders (64 envs per chunk; 32 before round 6), the tail chunk
+    _, n_obj_px = compare_envs(sim, frames[envs], envs, lambda e: scenes[int(mid[e])], pdist.distortion_maps(W, H), ORACLE_MESH, dr=False,
+                               mode="pixel", count_objects=len(envs))
     assert n_obj_px > 200, n_obj_px
     sim.close()
 
@@ -166,24 +110,10 @@ def test_c4_full_size_batch_matches_oracle_directly():
     assert sim.read(_ffi.FIELD_OBJ_ACTIVE).any()
     sim.render()
     sim.sync()
-    picks = _stratified_picks(sim, N, 32, 2)
+    picks = stratified_picks(sim, N, 32, 2)
     assert len(picks) >= 32
-    sub = _frames_of(sim, picks)
-    scene = _scene("loop_pedestrians")
-    rmap = pdist.distortion_maps(W, H)
-    worst = dict(frac_gt1=0.0, frac_gt2=0.0, mean=0.0)
-    n_obj_px = 0
-    for k, e in enumerate(picks):
-        cam = _camera(sim, e, W, H, True)
-        st = _obj_states(sim, e, scene)
-        ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st)
-        if k < 6:
-            no_obj = raster.render_obs(cam, scene, "pixel", rmap, obj_states=[dict(s_, visible=False) for s_ in st])
-            n_obj_px += int((np.abs(ref.astype(int) - no_obj.astype(int)).max(-1) > 0).sum())
-        s = _stats(sub[k], ref)
-        assert all(s[f] <= OBJ_TOL[f] for f in OBJ_TOL), (e, s)
-        for f in worst:
-            worst[f] = max(worst[f], s[f])
+    worst, n_obj_px = compare_envs(sim, frames_of(sim, picks), picks, scene("loop_pedestrians"), pdist.distortion_maps(W, H), ORACLE_MESH, dr=True,
+                                   mode="pixel", count_objects=6)
     assert n_obj_px > 200, n_obj_px
     print("C4 4096-env batch, %d envs against the oracle: worst" % len(picks), worst)
     sim.close()
@@ -203,19 +133,11 @@ def test_c5_full_size_batch_matches_oracle_directly():
     sim.sync()
     mid = sim.read(_ffi.FIELD_MAP_ID)
     assert set(np.unique(mid)) == {0, 1}
-    picks = _stratified_picks(sim, N, 16, 3)
+    picks = stratified_picks(sim, N, 16, 3)
     assert len(picks) >= 16 and {int(mid[e]) for e in picks} == {0, 1}
-    sub = _frames_of(sim, picks)
-    scenes = [_scene(n) for n in names]
-    rmap = pdist.distortion_maps(W, H)
-    worst = dict(frac_gt1=0.0, frac_gt2=0.0, mean=0.0)
-    for k, e in enumerate(picks):
-        scene = scenes[int(mid[e])]
-        ref = raster.render_obs(_camera(sim, e, W, H, False), scene, "pixel", rmap, obj_states=_obj_states(sim, e, scene))
-        s = _stats(sub[k], ref)
-        assert all(s[f] <= OBJ_TOL[f] for f in OBJ_TOL), (e, int(mid[e]), s)
-        for f in worst:
-            worst[f] = max(worst[f], s[f])
+    scenes = [scene(n) for n in names]
+    worst, _ = compare_envs(sim, frames_of(sim, picks), picks, lambda e: scenes[int(mid[e])], pdist.distortion_maps(W, H), ORACLE_MESH, dr=False,
+                            mode="pixel")
     print("C5 4096-env batch, %d envs against the oracle: worst" % len(picks), worst)
     sim.close()
 

@@ -12,6 +12,7 @@ import pytest
 
 from dtsim import BatchedSimulator, DuckietownVecEnv, _ffi, assets
 from dtsim import distortion as pdist
+from frame_parity import ORACLE_MESH, assert_within, stats
 from oracle import raster, sim as osim
 
 pytestmark = pytest.mark.gpu
@@ -100,9 +101,7 @@ def test_per_env_calibrations_against_the_oracle(size):
         objs = [dict(pos=o.pos, y_rot=o.y_rot, visible=bool(vis[e][k])) for k, o in enumerate(scene.m.objects)]
         # camera_rand renders through the per-env camera path (k_raster_v3dr): the per-channel light of "pixel-dr", as per_env_camera
         ref = raster.render_obs(cam, scene, "pixel-dr", (rx[c], ry[c]), obj_states=objs)
-        d = np.abs(fa[e].astype(np.int32) - ref.astype(np.int32))
-        dm = d.max(axis=-1)
-        assert (dm > 1).mean() <= 2e-3 and (dm > 2).mean() <= 1e-3 and d.mean() <= 0.03, (e, float((dm > 1).mean()), float(d.mean()))
+        assert_within(stats(fa[e], ref), ORACLE_MESH, e)
     a.close()
 
 

@@ -4,9 +4,10 @@ HIP library) behaves like the reference's API, incl. the properties run_tests.py
 import numpy as np
 import pytest
 
+import frame_parity as fp
 from dtsim import BatchedSimulator, _ffi
 from oracle import sim as osim
-from util import make_oracle
+from util import EXT, make_oracle, oracle_mode
 from dtsim import distortion as pdist
 
 pytestmark = pytest.mark.gpu
@@ -145,7 +146,7 @@ def test_render_modes_window_views_match_oracle():
     top = env.render("top_down")
     assert np.array_equal(free, img) and top.shape == (WH, WW, 3)
 
-    om = osim.OracleMap(assets.get_map("small_loop_only_duckies"), __import__("util").EXT)
+    om = osim.OracleMap(assets.get_map("small_loop_only_duckies"), EXT)
     kinds = {t["kind"] for t in om.grid if t is not None}
     meshes = {"duckie": assets.get_mesh("duckie"), "*": assets.get_mesh("*")}
     scene = raster.Scene(om, {k: assets.get_texture(k) for k in kinds}, meshes)
@@ -153,10 +154,9 @@ def test_render_modes_window_views_match_oracle():
     states = [dict(pos=o.pos, y_rot=o.y_rot, visible=True) for o in om.objects]
     cam = raster.Camera(env.cur_pos, env.cur_angle, width=WW, height=WH, horizon_color=list(st.horizon_color),
                         ground_color=list(st.ground_color), light_pos=list(st.light_pos))
-    mode = __import__("util").oracle_mode(next(v for (_d, sz), v in env._viewers.items() if sz == (WW, WH)))   # the window views come from a per-env-camera handle
+    mode = oracle_mode(next(v for (_d, sz), v in env._viewers.items() if sz == (WW, WH)))   # the window views come from a per-env-camera handle
     ref = raster.render_obs(cam, scene, mode, None, obj_states=states)
-    d = np.abs(free.astype(int) - ref.astype(int)).max(-1)
-    assert (d > 1).mean() <= 2e-3 and np.abs(free.astype(int) - ref.astype(int)).mean() <= 0.03, ((d > 1).mean(),)
+    fp.assert_within(fp.stats(free, ref), fp.ORACLE_MESH_GT1, "free_cam")
 
     # top-down: oracle camera straight from the reference's gluLookAt arguments
     a, b = env.grid_width * env.road_tile_size / 2, env.grid_height * env.road_tile_size / 2
@@ -171,13 +171,12 @@ def test_render_modes_window_views_match_oracle():
     import copy
     md = copy.deepcopy(assets.get_map("small_loop_only_duckies"))
     md["objects"] = list(md["objects"]) + [{"kind": "duckiebot", "pos": [0.5, 0.5], "rotate": 0, "static": False, "height": 0.12}]
-    om2 = osim.OracleMap(md, __import__("util").EXT)
+    om2 = osim.OracleMap(md, EXT)
     scene2 = raster.Scene(om2, scene.textures, meshes)
     states2 = states + [dict(pos=env.cur_pos, y_rot=math.degrees(env.cur_angle), visible=True)]
     rmap = None
     tref = raster.render_obs(tcam, scene2, mode, rmap, obj_states=states2)
-    d = np.abs(top.astype(int) - tref.astype(int)).max(-1)
-    assert (d > 1).mean() <= 3e-3 and np.abs(top.astype(int) - tref.astype(int)).mean() <= 0.05, ((d > 1).mean(),)
+    fp.assert_within(fp.stats(top, tref), fp.FACADE_TOP_DOWN, "top_down")
     no_agent = raster.render_obs(tcam, scene2, mode, rmap, obj_states=states + [dict(states2[-1], visible=False)])
     assert (np.abs(tref.astype(int) - no_agent.astype(int)).max(-1) > 0).sum() > 30     # the marker is in the picture
     seg = env.render("top_down", segment=True)
@@ -566,10 +565,8 @@ def test_reset_captures_the_light_through_the_last_frame_s_model_view():
     hands the device the eye-space light accordingly; frames of the second episode against the oracle lit the same way.  Domain randomisation:
     the drawn DIRECTION is rotated only.  gl_light_capture=False keeps the light as given."""
     from gym_duckietown.simulator import Simulator
-    from oracle import raster
-    from test_gpu_render import _camera, _scene, _stats
     W, H = 320, 240
-    scene = _scene("small_loop")
+    scene = fp.scene("small_loop")
     for dr in (False, True):
         env = Simulator(map_name="small_loop", domain_rand=dr, camera_width=W, camera_height=H, seed=6, distortion=False)
         first = [float(v) for v in env._sim.init_states[0].light_pos]
@@ -577,7 +574,7 @@ def test_reset_captures_the_light_through_the_last_frame_s_model_view():
             assert first == [0.0, 3.0, 0.0, 1.0]                               # nothing drawn before the first reset: the identity
         for _ in range(7):
             env.step(np.array([0.6, 0.3]))
-        cam_prev = _camera(env._sim, 0, W, H, dr)                              # the camera of the last frame of episode 1
+        cam_prev = fp.camera(env._sim, 0, W, H, dr)                              # the camera of the last frame of episode 1
         obs = env.reset()
         st = env._sim.init_states[0]
         got = [float(v) for v in st.light_pos]
@@ -587,9 +584,8 @@ def test_reset_captures_the_light_through_the_last_frame_s_model_view():
         assert not np.allclose(got[:3], raw[:3], atol=1e-3)                    # it did move
         col = env._sim.read(_ffi.FIELD_COLORS)[0]
         assert np.allclose(col[12:16], got, rtol=1e-6, atol=1e-6)
-        ref = raster.render_obs(_camera(env._sim, 0, W, H, dr), scene, __import__("util").oracle_mode(env._sim), None)   # (reads the init state's light)
-        s = _stats(obs, ref)
-        assert s["mean"] <= 0.05 and s["frac_gt2"] <= 1e-3, (dr, s)
+        ref = fp.oracle_frame(env._sim, 0, scene, None, dr=dr)                  # (reads the init state's light)
+        fp.assert_within(fp.stats(obs, ref), fp.FACADE_LIGHT, dr)
         env.close()
     env = Simulator(map_name="small_loop", domain_rand=False, camera_width=W, camera_height=H, seed=6, distortion=False, gl_light_capture=False)
     env.step(np.array([0.6, 0.3])); env.reset()

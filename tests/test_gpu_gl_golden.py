@@ -6,7 +6,7 @@ dtsim_reset(states) / dtsim_write; assets are the files the reference read (orac
 Tolerance vs Mesa 23.2.1 llvmpipe (DESIGN.md section 4 derives it; measured values are printed with -s):
   one-ray filter: GL filters RGBA8 textures with 8-bit weights and an 8-bit intermediate (profiles/r06_gl_filter_precision.txt);
   the HIP raster folds the lit factor into 8-bit weights and rounds once -> a +-1/255 difference on a fraction of the textured
-  pixels, nothing systematic:  >= 99 % of pixels within +-1/255, <= 0.4 % beyond +-2/255, mean abs error <= 0.35 / 255.
+  pixels, nothing systematic:  frame_parity.REFERENCE_GL (>= 99 % of pixels within +-1/255, <= 0.4 % beyond +-2/255, mean abs error <= 0.35 / 255).
 """
 import ctypes as C
 
@@ -15,11 +15,11 @@ import pytest
 
 import gl_golden as G
 from dtsim import BatchedSimulator, _ffi
+from frame_parity import GL_FILTER_DIFFER, ORACLE_MESH_GT1, REFERENCE_GL, assert_within, stats
 from oracle.gl import asset_trees
 
 pytestmark = pytest.mark.gpu
 CASES = [c for c in G.cases() if not c.startswith(("view_", "trajectory_"))]          # (the window / debugging views go through the facade: last test of the file)
-TOL = dict(gt1=1e-2, gt2=4e-3, mean=0.35)
 
 
 def render_case(d, per_env_camera=None, gl_filter=False):
@@ -57,13 +57,13 @@ def render_case(d, per_env_camera=None, gl_filter=False):
 def test_frames_match_reference_gl(case):
     d = G.load(case)
     frames = render_case(d)
-    all_stats = [G.stats(frames[k], d["frame"][k]) for k in range(len(frames))]
+    all_stats = [stats(frames[k], d["frame"][k]) for k in range(len(frames))]
     worst = {key: max(s[key] for s in all_stats) for key in ("gt1", "gt2", "gt8", "mean")}
     differ = max(float((frames[k] != d["frame"][k]).any(axis=-1).mean()) for k in range(len(frames)))
     print(f"\n{case}: worst of {len(frames)} frames vs GL: pixels that differ {differ:.3f}, beyond +-1 {worst['gt1']:.5f}, beyond +-2 {worst['gt2']:.5f}, "
           f"beyond +-8 {worst['gt8']:.5f}, mean abs {worst['mean']:.4f} / 255")
     for k, s in enumerate(all_stats):
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (case, k, s)
+        assert_within(s, REFERENCE_GL, (case, k))
 
 
 @pytest.mark.parametrize("case,seeds", [("small_loop_t256_160", list(range(10, 26))), ("small_loop_dr_t256_160", list(range(30, 46))),
@@ -84,10 +84,10 @@ def test_drop_in_facade_reproduces_the_reference_s_first_frames(case, seeds):
         assert np.array_equal(np.asarray(env.cur_pos, dtype=np.float64), d["pos"][k]) and float(env.cur_angle) == float(d["angle"][k]), (case, seed)
         assert np.allclose(np.asarray(env.horizon_color, dtype=np.float64)[:3], d["horizon"][k], rtol=0, atol=0), (case, seed)
         obs = env.render_obs()
-        s = G.stats(obs, d["frame"][k])
+        s = stats(obs, d["frame"][k])
         for key in worst:
             worst[key] = max(worst[key], s[key])
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (case, seed, s)
+        assert_within(s, REFERENCE_GL, (case, seed))
         env.close()
     print(f"\n{case}: facade vs reference, worst of {len(seeds)} seeds: beyond +-1 {worst['gt1']:.5f}, beyond +-2 {worst['gt2']:.5f}, mean abs {worst['mean']:.4f} / 255")
 
@@ -109,13 +109,13 @@ def test_facade_views_match_the_reference_s(case, seeds):
         assert img.shape == d["frame"][k].shape
         if bbox:
             mask = G.line_mask(d, k)
-            s = G.stats_masked(img, d["frame"][k], mask)
+            s = stats(img, d["frame"][k], mask)
             red = lambda f: ((f[..., 0].astype(int) - f[..., 1] > 25) & mask).sum()
             assert red(img) > 20 and red(d["frame"][k]) > 20, (red(img), red(d["frame"][k]))
         else:
-            s = G.stats(img, d["frame"][k])
+            s = stats(img, d["frame"][k])
         print(f"\n{case} seed {seed}: beyond +-1 {s['gt1']:.5f}, beyond +-2 {s['gt2']:.5f}, mean abs {s['mean']:.4f} / 255")
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (case, seed, s)
+        assert_within(s, REFERENCE_GL, (case, seed))
         env.close()
 
 
@@ -127,9 +127,11 @@ def test_gl_filter_mode_is_bit_faithful(case):
     d = G.load(case)
     frames = render_case(d, gl_filter=True)
     differ = [float((frames[k] != d["frame"][k]).any(axis=-1).mean()) for k in range(len(frames))]
-    st = [G.stats(frames[k], d["frame"][k]) for k in range(len(frames))]
+    st = [stats(frames[k], d["frame"][k]) for k in range(len(frames))]
     print(f"\n{case} (GL filter mode): worst of {len(frames)} frames: pixels that differ {max(differ):.4f}, beyond +-1 {max(s['gt1'] for s in st):.5f}, mean abs {max(s['mean'] for s in st):.4f} / 255")
-    assert max(differ) <= 2.5e-2 and max(s["gt1"] for s in st) <= 2e-3 and max(s["mean"] for s in st) <= 0.03, (case, max(differ))
+    assert max(differ) <= GL_FILTER_DIFFER, (case, max(differ))
+    for k, s in enumerate(st):
+        assert_within(s, ORACLE_MESH_GT1, (case, k))
 
 
 @pytest.mark.parametrize("case", ["trajectory_t256_160", "trajectory_dr_t256_160"])
@@ -158,9 +160,9 @@ def test_drop_in_env_follows_the_reference_s_trajectory(case):
         frames[t + 1] = obs
     assert bool(d["traj_done"][0][-1])                   # the recorded episode did end (and so did this one, at the same step)
     for step, k in kept.items():
-        s = G.stats(frames[step], d["frame"][k])
+        s = stats(frames[step], d["frame"][k])
         print(f"\n{case} step {step}: beyond +-1 {s['gt1']:.5f}, beyond +-2 {s['gt2']:.5f}, mean abs {s['mean']:.4f} / 255")
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (case, step, s)
+        assert_within(s, REFERENCE_GL, (case, step))
     env.close()
 
 
@@ -205,6 +207,6 @@ def test_device_side_light_capture_matches_gl():
     sim.render()
     frames = sim.frames_host()
     for j in range(n):
-        s = G.stats(frames[j], d["frame"][after[j]])
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (j, s)
+        s = stats(frames[j], d["frame"][after[j]])
+        assert_within(s, REFERENCE_GL, j)
     sim.close()

@@ -14,8 +14,8 @@ import pytest
 
 from dtsim import BatchedSimulator, _ffi
 from dtsim import distortion as pdist
+import frame_parity as fp
 from oracle import raster
-from test_gpu_render import _camera, _obj_states, _scene, _stats
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +39,7 @@ def _spheres(sim, e, scene, seed):
     out.append([*c, 0.04, 0, 1, 0, 1.0])                   # centre on the road surface: half of it below the tile plane
     out.append([*(pos + d * 0.066 + up * 0.1), 0.05, 1, 1, 0, 1.0])   # around the camera: across the near plane
     out.append([*(pos + d * 0.5 + r * 0.62 + up * 0.05), 0.06, 1, 0, 1, 0.2])   # at the image border
-    st = _obj_states(sim, e, scene)
+    st = fp.obj_states(sim, e, scene)
     objs = [(np.linalg.norm(np.asarray(s["pos"]) - pos), np.asarray(s["pos"], dtype=np.float64)) for s in st if s["visible"]]
     if objs:
         p = min(objs, key=lambda t: t[0])[1]
@@ -58,13 +58,13 @@ def test_draw_leds_match_oracle_on_the_rendered_frame(map_name, W, H, dr):
     sim.step(np.random.default_rng(4).uniform(0.2, 0.7, (6, N, 2)).astype(np.float32), n_steps=6)
     sim.render()
     before = sim.frames_host().copy()
-    scene = _scene(map_name)
+    scene = fp.scene(map_name)
     sps = [_spheres(sim, e, scene, 50 + e) for e in range(N)]
     sim.draw_leds(np.concatenate(sps), np.repeat(np.arange(N), [len(s) for s in sps]))
     after = sim.frames_host()
     for e in range(N):
-        cam = _camera(sim, e, W, H, dr)
-        _, depths = raster.render_rectilinear(cam, scene, "pixel", _obj_states(sim, e, scene), return_depth=True)
+        cam = fp.camera(sim, e, W, H, dr)
+        _, depths = raster.render_rectilinear(cam, scene, "pixel", fp.obj_states(sim, e, scene), return_depth=True)
         want = raster.overlay_leds(before[e], cam, depths, sps[e])
         touched = (want != before[e]).any(-1)
         assert touched.sum() > 150, int(touched.sum())    # the spheres are in view
@@ -92,24 +92,21 @@ def test_draw_leds_through_the_fisheye_and_state_rules():
     sim.step(np.random.default_rng(3).uniform(0.2, 0.7, (4, N, 2)).astype(np.float32), n_steps=4)
     sim.render()
     before = sim.frames_host().copy()
-    scene = _scene("loop_dyn_duckiebots")
+    scene = fp.scene("loop_dyn_duckiebots")
     sps = [_spheres(sim, e, scene, 70 + e) for e in range(N)]
     sim.draw_leds(np.concatenate(sps), np.repeat(np.arange(N), [len(s) for s in sps]))
     after = sim.frames_host()
     rmap = pdist.distortion_maps(W, H)
     for e in range(N):
-        cam = _camera(sim, e, W, H, False)
-        st = _obj_states(sim, e, scene)
-        plain = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st)
-        ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st, leds=sps[e])
+        plain = fp.oracle_frame(sim, e, scene, rmap, dr=False, mode="pixel")
+        ref = fp.oracle_frame(sim, e, scene, rmap, dr=False, mode="pixel", leds=sps[e])
         touched = (ref != plain).any(-1)
         assert touched.sum() > 300
         got = after[e].astype(int) - before[e].astype(int)
         want = ref.astype(int) - plain.astype(int)
         bad = np.abs(got - want).max(-1) > 2
         assert bad.sum() <= 0.05 * touched.sum() + 4, (e, int(bad.sum()), int(touched.sum()))
-        s = _stats(after[e], ref)
-        assert s["mean"] <= 0.1 and s["frac_gt2"] <= 2e-3 + 0.05 * touched.sum() / (W * H), (e, s)
+        fp.assert_within(fp.stats(after[e], ref), fp.leds_tol(touched.sum(), W, H), e)
     sim.close()
 
 
@@ -122,18 +119,16 @@ def test_simulator_enable_leds():
     for _ in range(3):
         obs, _, _, _ = env.step(np.array([0.4, 0.4]))
     sp = env._led_spheres()
-    scene = _scene("loop_dyn_duckiebots")
-    st = _obj_states(env._sim, 0, scene)
+    scene = fp.scene("loop_dyn_duckiebots")
+    st = fp.obj_states(env._sim, 0, scene)
     ref_sp = raster.led_spheres(scene, st)
     n_bots = sum(1 for o in env.objects if o.kind == "duckiebot")
     assert n_bots >= 1 and sp.shape == (10 * n_bots, 8) and ref_sp.shape == sp.shape
     assert np.allclose(sp, ref_sp, atol=1e-5), float(np.abs(sp - ref_sp).max())
     assert np.allclose(sp[0::2, 7], 1.0) and np.allclose(sp[1::2, 7], 0.2)                    # sphere, halo, sphere, halo ...
     assert np.allclose(sp[1::2, 3], sp[1::2, 4:7].mean(axis=1) * 0.04 * env.objects[0].scale)  # halo radius = mean(colour) x 4 cm (x scale)
-    cam = _camera(env._sim, 0, W, H, False)
-    ref = raster.render_obs(cam, scene, __import__("util").oracle_mode(env._sim), None, obj_states=st, leds=ref_sp)
-    s = _stats(obs, ref)
-    assert s["mean"] <= 0.1 and s["frac_gt2"] <= 3e-3, s
+    ref = fp.oracle_frame(env._sim, 0, scene, None, dr=False, leds=ref_sp)
+    fp.assert_within(fp.stats(obs, ref), fp.FACADE_OVERLAY)
     img = env.render(mode="top_down")                                                          # the window views take the same pass
     assert img.shape[2] == 3
     env.close()
@@ -150,12 +145,12 @@ def test_batched_led_spheres_for_every_env_and_map():
     sim.reset(mask=(np.arange(N) % 2 == 0))
     sim.step(np.random.default_rng(9).uniform(0.2, 0.6, (20, N, 2)).astype(np.float32), n_steps=20)
     sp, idx = sim.led_spheres()
-    scenes = [_scene(n) for n in names]
+    scenes = [fp.scene(n) for n in names]
     mid = sim.read(_ffi.FIELD_MAP_ID)
     assert set(np.unique(mid)) == {0, 1}
     for e in range(N):
         sc = scenes[int(mid[e])]
-        want = raster.led_spheres(sc, _obj_states(sim, e, sc))
+        want = raster.led_spheres(sc, fp.obj_states(sim, e, sc))
         got = sp[idx == e]
         assert got.shape == want.shape and (want.shape[0] > 0) == (int(mid[e]) == 0)       # only the duckiebot map has LEDs
         assert np.allclose(got, want, atol=1e-5)

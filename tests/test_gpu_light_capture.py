@@ -16,14 +16,12 @@ import pytest
 import gl_golden as G
 from dtsim import BatchedSimulator, _ffi
 from dtsim import distortion as pdist
-from oracle import raster
+from frame_parity import (GL_FILTER_DIFFER, ORACLE_MESH, ORACLE_MESH_GT1, ORACLE_PLANE, REFERENCE_GL, assert_within, compare_envs, frames_of, scene,
+                          stats, stratified_picks)
+from gl_golden import LIGHTCAP_FLOW as FLOW, LIGHTCAP_RESET_CASES as LIGHTCAP_CASES, load_lightcap
 from oracle.gl import asset_trees
-from test_gpu_baseline_configs import _frames_of, _stratified_picks
-from test_gpu_render import _obj_states, _scene, _stats
-from test_lightcap_goldens import FLOW, RESET_CASES as LIGHTCAP_CASES, load as load_lightcap
 
 pytestmark = pytest.mark.gpu
-TOL = dict(gt1=1e-2, gt2=4e-3, mean=0.35)                    # test_gpu_gl_golden.py
 FIRST_LIGHT = np.array([0.0, 3.0, 0.0, 1.0])
 # the shared-camera cases of the GL goldens: first-episode frames and the episode-2 golden (the window views go through the facade)
 SHARED_CASES = [c for c in G.cases() if "_dr_" not in c and not c.startswith(("view_", "trajectory_", "segment_"))] + LIGHTCAP_CASES
@@ -71,10 +69,10 @@ def _render_golden(d, light_capture=True, per_env_camera=False, gl_filter=False)
 def _assert_gl(frames, d, idx, label):
     worst = dict(gt1=0.0, gt2=0.0, mean=0.0)
     for j, k in enumerate(idx):
-        s = G.stats(frames[j], d["frame"][k])
+        s = stats(frames[j], d["frame"][k])
         for key in worst:
             worst[key] = max(worst[key], s[key])
-        assert s["gt1"] <= TOL["gt1"] and s["gt2"] <= TOL["gt2"] and s["mean"] <= TOL["mean"], (label, k, s)
+        assert_within(s, REFERENCE_GL, (label, k))
     print(f"\n{label}: worst of {len(idx)} frames vs GL: beyond +-1 {worst['gt1']:.5f}, beyond +-2 {worst['gt2']:.5f}, "
           f"mean abs {worst['mean']:.4f} / 255")
 
@@ -127,10 +125,12 @@ def test_generic_raster_with_each_env_s_light_is_bit_faithful(case):
     frames, pipe = _render_golden(d, gl_filter=True)
     assert pipe == "k_raster_env+light", pipe
     differ = [float((frames[k] != d["frame"][k]).any(axis=-1).mean()) for k in range(len(frames))]
-    st = [G.stats(frames[k], d["frame"][k]) for k in range(len(frames))]
+    st = [stats(frames[k], d["frame"][k]) for k in range(len(frames))]
     print(f"\n{case} (GL filter mode, each env's light): pixels that differ {max(differ):.4f}, beyond +-1 {max(s['gt1'] for s in st):.5f}, "
           f"mean abs {max(s['mean'] for s in st):.4f} / 255")
-    assert max(differ) <= 2.5e-2 and max(s["gt1"] for s in st) <= 2e-3 and max(s["mean"] for s in st) <= 0.03, (case, max(differ))
+    assert max(differ) <= GL_FILTER_DIFFER, (case, max(differ))
+    for k, s in enumerate(st):
+        assert_within(s, ORACLE_MESH_GT1, (case, k))
 
 
 def test_light_on_with_the_first_light_equals_light_off():
@@ -208,28 +208,18 @@ def _full_size(names, N, obj, n_min):
     sim.render()
     sim.sync()
     assert sim.render_pipeline == "k_raster_v3+light", sim.render_pipeline
-    picks = _stratified_picks(sim, N, n_min, 3)
+    picks = stratified_picks(sim, N, n_min, 3)
     idx = np.nonzero(later)[0]
     picks = sorted(set(picks) | {int(e) for e in idx[:: max(1, len(idx) // 8)]})
     n_later = int(sum(later[e] for e in picks))
     assert n_later >= 8
-    sub = _frames_of(sim, picks)
-    cols = sim.read(_ffi.FIELD_COLORS)
-    pos, ang, mid = sim.read(_ffi.FIELD_POS), sim.read(_ffi.FIELD_ANGLE), sim.read(_ffi.FIELD_MAP_ID)
+    cols, mid = sim.read(_ffi.FIELD_COLORS), sim.read(_ffi.FIELD_MAP_ID)
     assert (np.abs(cols[later][:, 12:16] - FIRST_LIGHT).max(-1) > 1e-6).all()
-    scenes = [_scene(n) for n in ([names] if isinstance(names, str) else names)]
-    rmap = pdist.distortion_maps(W, H)
-    tol = (2e-3, 1e-3, 0.03) if obj else (1e-3, 5e-4, 0.02)
-    worst = dict(frac_gt1=0.0, frac_gt2=0.0, mean=0.0)
-    for k, e in enumerate(picks):
-        cam = raster.Camera(pos[e], ang[e], width=W, height=H, horizon_color=[float(v) for v in cols[e, 0:3]],
-                            ground_color=[float(v) for v in cols[e, 3:6]], light_pos=[float(v) for v in cols[e, 12:16]])
-        scene = scenes[int(mid[e])]
-        ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=_obj_states(sim, e, scene) if obj else None)
-        s = _stats(sub[k], ref)
-        assert s["frac_gt1"] <= tol[0] and s["frac_gt2"] <= tol[1] and s["mean"] <= tol[2], (e, bool(later[e]), s)
-        for f in worst:
-            worst[f] = max(worst[f], s[f])
+    scenes = [scene(n) for n in ([names] if isinstance(names, str) else names)]
+    assert obj == all(bool(sc.m.objects) for sc in scenes)
+    # colors=: the light of an env past episode 1 is what the device captured (DTSIM_FIELD_COLORS), not its init state's
+    worst, _ = compare_envs(sim, frames_of(sim, picks), picks, lambda e: scenes[int(mid[e])], pdist.distortion_maps(W, H),
+                            ORACLE_MESH if obj else ORACLE_PLANE, dr=False, mode="pixel", colors=cols)
     print(f"\n{names}, {N} envs, light_capture: {len(picks)} envs ({n_later} past episode 1) against the oracle: worst", worst)
     sim.close()
 
@@ -297,10 +287,10 @@ def test_vector_flow_follows_the_reference_over_episodes():
                 k = kept[(s, t)]
                 assert np.allclose(light[s], d["kept_light_eye"][k], rtol=2e-6, atol=2e-4), (s, t, light[s], d["kept_light_eye"][k])
                 n_later += int(np.abs(d["kept_light_eye"][k] - FIRST_LIGHT).max() > 0.1)
-                st = G.stats(frames[s], d["kept_frame"][k])
+                st = stats(frames[s], d["kept_frame"][k])
                 for key in worst:
                     worst[key] = max(worst[key], st[key])
-                assert st["gt1"] <= TOL["gt1"] and st["gt2"] <= TOL["gt2"] and st["mean"] <= TOL["mean"], (s, t, st)
+                assert_within(st, REFERENCE_GL, (s, t))
             assert sim.render_pipeline == "k_raster_v3+light", sim.render_pipeline
     assert n_later >= 20, n_later
     print(f"\nflow: {S} seeds x {T} steps, {len(kept)} kept frames ({n_later} in later episodes) vs GL: beyond +-1 {worst['gt1']:.5f}, "

@@ -11,8 +11,8 @@ import pytest
 
 from dtsim import BatchedSimulator, _ffi
 from dtsim import distortion as pdist
+import frame_parity as fp
 from oracle import raster
-from test_gpu_render import _camera, _obj_states, _scene, _stats
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,7 @@ def test_draw_lines_match_oracle_on_the_rendered_frame(W, H, dr):
     sim.draw_lines(np.concatenate(segs), np.repeat(np.arange(N), [len(s) for s in segs]))
     after = sim.frames_host()
     for e in range(N):
-        cam = _camera(sim, e, W, H, dr)
+        cam = fp.camera(sim, e, W, H, dr)
         want = raster.overlay_lines(before[e], cam, segs[e])
         touched = (want != before[e]).any(-1)
         assert touched.sum() > 50                         # the lines are in view
@@ -72,16 +72,14 @@ def test_draw_lines_through_the_fisheye_match_oracle():
     segs = [_segments(sim, e, 30, 7 + e) for e in range(N)]
     sim.draw_lines(np.concatenate(segs), np.repeat(np.arange(N), [len(s) for s in segs]))
     frames = sim.frames_host()
-    scene = _scene("small_loop")
+    scene = fp.scene("small_loop")
     rmap = pdist.distortion_maps(W, H)
     for e in range(N):
-        cam = _camera(sim, e, W, H, False)
-        plain = raster.render_obs(cam, scene, "pixel", rmap)
-        ref = raster.render_obs(cam, scene, "pixel", rmap, lines=segs[e])
+        plain = fp.oracle_frame(sim, e, scene, rmap, dr=False, mode="pixel")
+        ref = fp.oracle_frame(sim, e, scene, rmap, dr=False, mode="pixel", lines=segs[e])
         n_line = int((ref != plain).any(-1).sum())
         assert n_line > 200
-        s = _stats(frames[e], ref)
-        assert s["mean"] <= 0.05 and s["frac_gt2"] <= 5e-4 + 0.05 * n_line / (W * H), (e, s, n_line)
+        fp.assert_within(fp.stats(frames[e], ref), fp.overlay_lines_tol(n_line, W, H), (e, n_line))
     sim.close()
 
 
@@ -100,11 +98,8 @@ def test_simulator_draw_curve_and_draw_bbox():
     assert {tuple(c) for c in lines[:, 6:9].tolist()} == {(1.0, 0.0, 0.0), (0.0, 0.0, 1.0)}
     red = (obs[..., 0] > 120) & (obs[..., 1] < 60) & (obs[..., 2] < 60)
     assert red.sum() > 30, int(red.sum())                                      # the curve ahead, drawn red
-    scene = _scene("small_loop")
-    cam = _camera(env._sim, 0, W, H, False)
-    ref = raster.render_obs(cam, scene, __import__("util").oracle_mode(env._sim), None, lines=lines)
-    s = _stats(obs, ref)
-    assert s["mean"] <= 0.1 and s["frac_gt2"] <= 3e-3, s
+    ref = fp.oracle_frame(env._sim, 0, fp.scene("small_loop"), None, dr=False, lines=lines)
+    fp.assert_within(fp.stats(obs, ref), fp.FACADE_OVERLAY)
     env.close()
 
     env = Simulator(map_name="loop_only_duckies", domain_rand=False, draw_bbox=True, camera_width=W, camera_height=H, seed=4, distortion=True)
@@ -118,10 +113,8 @@ def test_simulator_draw_curve_and_draw_bbox():
     ys, xs = np.nonzero(red)
     assert abs(xs.mean() - W / 2) < W / 4 and abs(ys.mean() - H / 2) < H / 3
     v = env._viewers[(False, (W, H))]
-    scene = _scene("loop_only_duckies")
-    cam = _camera(v, 0, W, H, True)
+    cam = fp.camera(v, 0, W, H, True)
     assert abs(cam.sth - 1.0) < 1e-6 and abs(cam.C[1] - 0.8) < 1e-6            # looking straight down from 0.8 m
-    ref = raster.render_obs(cam, scene, __import__("util").oracle_mode(v), None, obj_states=_obj_states(v, 0, scene), lines=lines)
-    s = _stats(obs, ref)
-    assert s["mean"] <= 0.3 and s["frac_gt2"] <= 1e-2, s                       # (the lines are drawn over the meshes here: no depth test against them)
+    ref = fp.oracle_frame(v, 0, fp.scene("loop_only_duckies"), None, dr=True, lines=lines)
+    fp.assert_within(fp.stats(obs, ref), fp.FACADE_BBOX)                       # (the lines are drawn over the meshes here: no depth test against them)
     env.close()

@@ -2,52 +2,24 @@
 
 Tolerances (camera RGB "within stated float tolerance", BASELINE.json north_star; SURVEY
 Appendix B): the HIP raster shades in float32 with per-fragment tile lighting, the oracle in
-float64.  Against the oracle in the SAME lighting mode ("pixel"):
-    >= 99.9 % of pixels identical within +-1/255, mean abs error <= 0.02/255, and no more
-    than 0.05 % of pixels off by more than 2/255 (float32 coverage flips on silhouettes).
-Against the oracle's GL-faithful per-vertex ("gouraud") tile lighting (SURVEY's proposal):
-    >= 99 % of pixels within +-2/255, mean abs error <= 0.5/255.
+float64.  The numbers are the rows of tests/frame_parity.py: against the oracle in the SAME
+lighting mode ("pixel") ORACLE_PLANE, with mesh objects ORACLE_MESH (float32 coverage flips on
+silhouettes); against the oracle's GL-faithful per-vertex ("gouraud") tile lighting (SURVEY's
+proposal) GOURAUD_CROSS.
 """
 import os
 
 import numpy as np
 import pytest
 
+import frame_parity as fp
 from dtsim import BatchedSimulator, _ffi, assets
 from dtsim import distortion as pdist
 from oracle import raster, sim as osim
 from util import EXT, oracle_mode
 
 pytestmark = pytest.mark.gpu
-ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assets")
-
-
-def _scene(map_name):
-    om = osim.OracleMap(assets.get_map(map_name), EXT)
-    kinds = {t["kind"] for t in om.grid if t is not None}
-    tex = {k: assets.get_texture(k) for k in kinds}
-    meshes = {"duckie": assets.get_mesh("duckie"), "*": assets.get_mesh("*")}
-    return raster.Scene(om, tex, meshes)
-
-
-def _camera(sim, e, W, H, dr):
-    st = sim.init_states[e]
-    pos = sim.read(_ffi.FIELD_POS)[e]
-    ang = sim.read(_ffi.FIELD_ANGLE)[e]
-    if not dr:
-        return raster.Camera(pos, ang, width=W, height=H, horizon_color=list(st.horizon_color),
-                             ground_color=list(st.ground_color), light_pos=list(st.light_pos))   # ((0, 3, 0, 1) unless the facade captured it through a model-view)
-    return raster.Camera(pos, ang, cam_height=st.cam_height, cam_angle_deg=st.cam_angle_deg,
-                         cam_fov_y_deg=st.cam_fov_y_deg, camera_noise=list(st.camera_noise), domain_rand=True,
-                         horizon_color=list(st.horizon_color), ground_color=list(st.ground_color),
-                         light_pos=list(st.light_pos), light_ambient=list(st.light_ambient),
-                         light_diffuse=list(st.light_diffuse), width=W, height=H)
-
-
-def _stats(a, b):
-    d = np.abs(a.astype(np.int32) - b.astype(np.int32)).max(axis=-1)
-    return dict(mean=float(np.abs(a.astype(np.int32) - b.astype(np.int32)).mean()), frac_gt1=float((d > 1).mean()),
-                frac_gt2=float((d > 2).mean()), max=int(d.max()))
+ASSETS = fp.ASSETS
 
 
 @pytest.mark.parametrize("map_name,W,H,distortion,dr", [
@@ -66,34 +38,14 @@ def test_frames_match_oracle(map_name, W, H, distortion, dr):
     sim.render()
     frames = sim.frames_host()
     assert frames.shape == (N, H, W, 3) and frames.dtype == np.uint8
-    scene = _scene(map_name)
+    scene = fp.scene(map_name)
     rmap = pdist.distortion_maps(W, H) if distortion else None
     for e in range(N):
-        cam = _camera(sim, e, W, H, dr)
-        ref_px = raster.render_obs(cam, scene, "pixel", rmap)
-        s = _stats(frames[e], ref_px)
-        assert s["frac_gt1"] <= 1e-3 and s["frac_gt2"] <= 5e-4 and s["mean"] <= 0.02, (e, s)
-        ref_g = raster.render_obs(cam, scene, "gouraud", rmap)
-        g = _stats(frames[e], ref_g)
-        assert g["frac_gt2"] <= 1e-2 and g["mean"] <= 0.5, (e, g)
+        fp.assert_within(fp.stats(frames[e], fp.oracle_frame(sim, e, scene, rmap, dr=dr, mode="pixel")), fp.ORACLE_PLANE, e)
+        fp.assert_within(fp.stats(frames[e], fp.oracle_frame(sim, e, scene, rmap, dr=dr, mode="gouraud")), fp.GOURAUD_CROSS, e)
         # run_tests.py:17-22 property: a sane image
         assert 0 < frames[e].mean() < 255
     sim.close()
-
-
-def _obj_states(sim, e, scene):
-    """Per-object render state of env e (static: map pose; DuckieObj: device centre / y_rot)."""
-    cen, yrot = sim.read(_ffi.FIELD_OBJ_CENTER)[e], sim.read(_ffi.FIELD_OBJ_YROT)[e]
-    cy = sim.read(_ffi.FIELD_OBJ_Y)[e]
-    vis = sim.read(_ffi.FIELD_OBJ_VISIBLE)[e]
-    out, slot = [], 0
-    for k, o in enumerate(scene.m.objects):
-        if o.static:
-            out.append(dict(pos=o.pos, y_rot=o.y_rot, visible=bool(vis[k])))
-        else:
-            out.append(dict(pos=np.array([cen[slot, 0], cy[slot], cen[slot, 1]]), y_rot=float(yrot[slot]), visible=bool(vis[k])))
-            slot += 1
-    return out
 
 
 @pytest.mark.parametrize("map_name,W,H,distortion,dr,steps", [
@@ -114,34 +66,10 @@ def test_frames_with_mesh_objects_match_oracle(map_name, W, H, distortion, dr, s
     sim.step(zero, n_steps=steps)
     sim.render()
     frames = sim.frames_host()
-    scene = _scene(map_name)
     rmap = pdist.distortion_maps(W, H) if distortion else None
-    n_obj_px = 0
-    for e in range(N):
-        cam = _camera(sim, e, W, H, dr)
-        st = _obj_states(sim, e, scene)
-        ref_px = raster.render_obs(cam, scene, "pixel", rmap, obj_states=st)
-        no_obj = raster.render_obs(cam, scene, "pixel", rmap, obj_states=[dict(s_, visible=False) for s_ in st])
-        n_obj_px += int((np.abs(ref_px.astype(int) - no_obj.astype(int)).max(-1) > 0).sum())
-        s = _stats(frames[e], ref_px)
-        assert s["frac_gt1"] <= 2e-3 and s["frac_gt2"] <= 1e-3 and s["mean"] <= 0.03, (e, s)
+    _, n_obj_px = fp.compare_envs(sim, frames, range(N), fp.scene(map_name), rmap, fp.ORACLE_MESH, dr=dr, mode="pixel", count_objects=N)
     assert n_obj_px > 200, n_obj_px          # the duckies are actually in view in this sample
     sim.close()
-
-
-def _asset_scene():
-    """Oracle scene of the real-asset fixture (tests/golden/assets): per-kind meshes with textures."""
-    lib = assets.AssetLibrary(ASSETS)
-    md = lib.map_data("test_town")
-    meshes = {"*": assets.get_mesh("*")}
-    for desc in md["objects"]:
-        meshes[desc["kind"]] = lib.object_mesh(desc)[1]
-    ext = {k: (m.min_coords, m.max_coords) for k, m in meshes.items()}
-    om = osim.OracleMap(md, ext)
-    kinds = {t["kind"] for t in om.grid if t is not None}
-    scene = raster.Scene(om, {k: lib.tile_texture(k) for k in kinds}, meshes)
-    scene.light_cards = lib.light_cards()              # TrafficLightObj.texs (objects.py:438-441)
-    return scene, md, ext
 
 
 @pytest.mark.parametrize("W,H,distortion,dr,steps", [(320, 240, False, False, 0), (640, 480, True, False, 0), (320, 240, False, True, 0),
@@ -150,7 +78,7 @@ def test_real_assets_match_oracle(W, H, distortion, dr, steps):
     """MapFormat1 YAML + tile texture files + OBJ/MTL meshes (multi-material, textured
     chunks: GL_MODULATE of the material texture with the lit vertex colour, sign / duckiebot material
     overrides) loaded from an asset tree, rendered by the HIP raster and by the oracle."""
-    scene, md, ext = _asset_scene()
+    scene, md, ext = fp.asset_scene()
     N = 8
     sim = BatchedSimulator("test_town", N, asset_root=ASSETS, camera_width=W, camera_height=H, distortion=distortion,
                            domain_rand=dr, seed=5, max_steps=100000)
@@ -172,16 +100,15 @@ def test_real_assets_match_oracle(W, H, distortion, dr, steps):
     rmap = pdist.distortion_maps(W, H) if distortion else None
     n_obj_px = 0
     for e in range(N):
-        cam = _camera(sim, e, W, H, dr)
-        st = _obj_states(sim, e, scene)
+        cam = fp.camera(sim, e, W, H, dr)
+        st = fp.obj_states(sim, e, scene)
         for k_, s_ in enumerate(st):
             s_["light_pattern"] = int(light[e, k_])
         mode = oracle_mode(sim)                    # 128 x 128 tile images: the per-env path is the generic raster (llvmpipe's filter)
         ref_px = raster.render_obs(cam, scene, mode, rmap, obj_states=st)
         no_obj = raster.render_obs(cam, scene, mode, rmap, obj_states=[dict(s_, visible=False) for s_ in st])
-        n_obj_px += int((np.abs(ref_px.astype(int) - no_obj.astype(int)).max(-1) > 0).sum())
-        s = _stats(frames[e], ref_px)
-        assert s["frac_gt1"] <= 2e-3 and s["frac_gt2"] <= 1e-3 and s["mean"] <= 0.03, (e, s)
+        n_obj_px += fp.object_pixels(ref_px, no_obj)
+        fp.assert_within(fp.stats(frames[e], ref_px), fp.ORACLE_MESH, e)
     assert n_obj_px > 2000, n_obj_px
     sim.close()
 
@@ -205,10 +132,7 @@ def test_file_textures_without_objects_match_oracle(distortion):
     assert {lib.tile_texture(k).shape[0] for k in kinds} == {128}
     scene = raster.Scene(om, {k: lib.tile_texture(k) for k in kinds}, {"*": assets.get_mesh("*")})
     rmap = pdist.distortion_maps(W, H) if distortion else None
-    for e in range(N):
-        cam = _camera(sim, e, W, H, False)
-        s = _stats(frames[e], raster.render_obs(cam, scene, "pixel", rmap))
-        assert s["frac_gt1"] <= 1e-3 and s["frac_gt2"] <= 5e-4 and s["mean"] <= 0.02, (e, s)
+    fp.compare_envs(sim, frames, range(N), scene, rmap, fp.ORACLE_PLANE, dr=False, mode="pixel")
     sim.close()
 
 
@@ -256,12 +180,7 @@ def test_odd_frame_sizes_match_oracle():
         sim.render()
         frames = sim.frames_host()
         assert frames.shape == (N, H, W, 3)
-        scene = _scene("small_loop_only_duckies")
-        for e in range(N):
-            cam = _camera(sim, e, W, H, False)
-            ref_px = raster.render_obs(cam, scene, oracle_mode(sim), None, obj_states=_obj_states(sim, e, scene))
-            s = _stats(frames[e], ref_px)
-            assert s["frac_gt1"] <= 4e-3 and s["mean"] <= 0.05, (W, H, e, s)     # tiny frames: every silhouette pixel counts
+        fp.compare_envs(sim, frames, range(N), fp.scene("small_loop_only_duckies"), None, fp.ORACLE_TINY, dr=False)   # (mode: the generic raster's)
         sim.close()
 
 
@@ -290,12 +209,7 @@ def test_checkerboard_renders_at_its_moving_centre():
     assert 0.02 < sim.read(_ffi.FIELD_OBJ_Y)[0, 0] < 0.2
     sim.render()
     frames = sim.frames_host()
-    for e in range(N):
-        cam = _camera(sim, e, W, H, False)
-        stt = _obj_states(sim, e, scene)
-        ref_px = raster.render_obs(cam, scene, "pixel", None, obj_states=stt)
-        s_ = _stats(frames[e], ref_px)
-        assert s_["frac_gt1"] <= 2e-3 and s_["mean"] <= 0.03, (e, s_)
+    fp.compare_envs(sim, frames, range(N), scene, None, fp.ORACLE_MESH_GT1, dr=False, mode="pixel")
     sim.close()
 
 
@@ -315,18 +229,16 @@ def test_segment_render_matches_oracle(map_name, W, H, distortion, dr):
     frames = sim.frames_host().copy()
     sim.render()
     assert np.array_equal(sim.frames_host(), normal)
-    scene = _scene(map_name)
+    scene = fp.scene(map_name)
     seg_tex, rgb = sim.segment_assets()
     seg_by_kind = {kd: seg_tex[i] for i, kd in enumerate(sim.texture_kinds)}
     cols = {mk: rgb[i] for i, mk in enumerate(sim._mesh_order)}
     rmap = pdist.distortion_maps(W, H) if distortion else None
     n_obj_px = 0
     for e in range(N):
-        cam, sc = raster.segment_view(_camera(sim, e, W, H, dr), scene, seg_by_kind, cols)
-        st = _obj_states(sim, e, scene)
-        ref_px = raster.render_obs(cam, sc, "pixel", rmap, obj_states=st)
-        s_ = _stats(frames[e], ref_px)
-        assert s_["frac_gt1"] <= 2e-3 and s_["frac_gt2"] <= 1e-3 and s_["mean"] <= 0.03, (e, s_)
+        cam, sc = raster.segment_view(fp.camera(sim, e, W, H, dr), scene, seg_by_kind, cols)
+        ref_px = raster.render_obs(cam, sc, "pixel", rmap, obj_states=fp.obj_states(sim, e, scene))
+        fp.assert_within(fp.stats(frames[e], ref_px), fp.ORACLE_MESH, e)
         valid = np.ones((H, W), bool) if rmap is None else (ref_px.sum(-1) > 0) | (frames[e].sum(-1) > 0)
         magenta = (frames[e] == np.array([255, 0, 255], np.uint8)).all(-1)
         assert magenta.mean() > 0.2                      # the sky, at least
@@ -364,9 +276,9 @@ def test_domain_rand_with_a_positional_light_takes_the_exact_paths():
     """Domain randomisation draws a DIRECTIONAL light (simulator.py:565-584: light_pos has w = 0), which is what lets k_raster_v3dr fold the
     tile plane's light into a per-env constant.  A caller can still write a positional light (DTSIM_FIELD_COLORS, w = 1): those envs get an
     empty one-ray range, every tile pixel goes to the exact path, and k_resolve_dr evaluates the light per pixel from the EnvCam.  Frames
-    against the oracle with the same light, plane-only thresholds; envs 0 / 2 positional, 1 / 3 as drawn."""
+    against the oracle with the same light, each map at its own row; envs 0 / 2 positional, 1 / 3 as drawn."""
     N, W, H = 4, 320, 240
-    for map_name, tol in (("small_loop", (1e-3, 5e-4, 0.02)), ("loop_only_duckies", (2e-3, 1e-3, 0.03))):
+    for map_name, tol in (("small_loop", fp.ORACLE_PLANE), ("loop_only_duckies", fp.ORACLE_MESH)):
         sim = BatchedSimulator(map_name, N, camera_width=W, camera_height=H, distortion=True, domain_rand=True, seed=13)
         sim.step(np.random.default_rng(5).uniform(0.2, 0.8, (6, N, 2)).astype(np.float32), n_steps=6)
         col = sim.read(_ffi.FIELD_COLORS).copy()           # [N][16]: horizon, ground, ambient, diffuse, light xyzw
@@ -376,15 +288,14 @@ def test_domain_rand_with_a_positional_light_takes_the_exact_paths():
         sim.write(_ffi.FIELD_COLORS, col)
         sim.render()
         frames = sim.frames_host()
-        scene = _scene(map_name)
+        scene = fp.scene(map_name)
         rmap = pdist.distortion_maps(W, H)
         for e in range(N):
-            cam = _camera(sim, e, W, H, True)
+            cam = fp.camera(sim, e, W, H, True)
             if e in lights:
                 cam.L = np.asarray(lights[e], dtype=np.float64)
-            ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=_obj_states(sim, e, scene) if scene.m.objects else None)
-            s = _stats(frames[e], ref)
-            assert s["frac_gt1"] <= tol[0] and s["frac_gt2"] <= tol[1] and s["mean"] <= tol[2], (map_name, e, s)
+            ref = raster.render_obs(cam, scene, "pixel", rmap, obj_states=fp.obj_states(sim, e, scene) if scene.m.objects else None)
+            fp.assert_within(fp.stats(frames[e], ref), tol, (map_name, e))
         sim.close()
 
 
@@ -403,14 +314,10 @@ def test_domain_rand_over_two_maps_in_the_render_order():
     assert set(np.unique(mid)) == {0, 1}
     rpos = sim.read(_ffi.FIELD_RENDER_POS)
     assert sorted(rpos.tolist()) == list(range(N)) and not np.array_equal(rpos, np.arange(N))     # a real permutation: the sorted order is in use
-    scenes = [_scene(n) for n in names]
-    rmap = pdist.distortion_maps(W, H)
+    scenes = [fp.scene(n) for n in names]
     env_at = np.argsort(rpos)
-    for e in sorted({0, 1, int(env_at[0]), int(env_at[63]), int(env_at[64]), int(env_at[N - 1])}):
-        scene = scenes[int(mid[e])]
-        ref = raster.render_obs(_camera(sim, e, W, H, True), scene, "pixel", rmap, obj_states=_obj_states(sim, e, scene))
-        s = _stats(frames[e], ref)
-        assert s["frac_gt1"] <= 2e-3 and s["frac_gt2"] <= 1e-3 and s["mean"] <= 0.03, (e, int(mid[e]), s)
+    envs = sorted({0, 1, int(env_at[0]), int(env_at[63]), int(env_at[64]), int(env_at[N - 1])})
+    fp.compare_envs(sim, frames[envs], envs, lambda e: scenes[int(mid[e])], pdist.distortion_maps(W, H), fp.ORACLE_MESH, dr=True, mode="pixel")
     sim.close()
 
 

@@ -4,26 +4,18 @@ They are complete; the oracle's GL-faithful mode reproduces their frames at the 
 pixels within +-1/255, mean <= 0.02/255) -- with each record's eye-space light, which from the second episode on is not the first one's;
 and where the reference tree and Mesa are present, the recipe reproduces the committed bytes.
 """
-import json
 import os
 
 import numpy as np
 import pytest
 
 import gl_golden as G
+from frame_parity import ORACLE_GL, assert_within, stats
+from gl_golden import LIGHTCAP_FLOW as FLOW, LIGHTCAP_RESET_CASES as RESET_CASES, load_lightcap as load
 
-RESET_CASES = ["lightcap_small_loop_t256_160", "lightcap_small_loop_t256_640", "lightcap_town_t128_320"]
-FLOW = "lightcap_flow_t256_160"
 FIRST_LIGHT = np.array([0.0, 3.0, 0.0, 1.0])
 STATE_KEYS = ("frame", "pos", "angle", "cam_height", "cam_angle", "cam_fov_y", "camera_noise", "horizon", "ground", "light_eye", "light_raw",
               "light_ambient", "light_diffuse", "obj_pos", "obj_yrot", "obj_visible", "obj_pattern")
-
-
-def load(name):
-    z = np.load(os.path.join(G.GOLDEN, f"{name}.npz"))
-    d = {k: z[k] for k in z.files}
-    d["meta"] = json.loads(str(d["meta"]))
-    return d
 
 
 def records(d, prefix):
@@ -67,8 +59,8 @@ def test_oracle_reproduces_the_lightcap_frames(name):
         d = records(d, "kept_")
     worst = dict(mean=0.0, gt1=0.0)
     for k in range(len(d["frame"])):
-        s = G.stats(G.oracle_frame(d, k, "gouraud"), d["frame"][k])
-        assert s["gt1"] <= 2e-3 and s["mean"] <= 0.02, (name, k, s)
+        s = stats(G.oracle_frame(d, k, "gouraud"), d["frame"][k])
+        assert_within(s, ORACLE_GL, (name, k))
         for key in worst:
             worst[key] = max(worst[key], s[key])
     print(f"\n{name}: worst of {len(d['frame'])} frames: beyond +-1 {worst['gt1']:.5f}, mean abs {worst['mean']:.5f} / 255")
