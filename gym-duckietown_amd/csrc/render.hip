@@ -1154,7 +1154,7 @@ __device__ inline PixInv pix_inv_dr(float nx, float ny, bool valid, const DrCam&
 // Queue entry: pixel of the wavefront block (bits 0..7) | env position in the chunk << 8 (bits 8..13).  Object-box entries
 // (far end of the region, k_resolve_obj's) carry bit 15 when the pixel is ALSO a plane edge, i.e. when what the raster
 // stored for it is not final: k_resolve_obj leaves a pixel alone when no mesh triangle covers any of its samples and the
-// bit is clear (the raster's one-ray colour is the pixel).  k_raster_v3 / k_raster_v3dr tell; the other rasters always set it.
+// bit is clear (the raster's one-ray colour is the pixel).  The quad-record rasters tell; the generic raster always sets it (its filter is the exact path's).
 #define QE_PLANE_EDGE 0x8000u
 #define QE_ALWAYS_EDGE 0x4000u    // front-of-region entry that is never a one-ray pixel (resolve_region_q skips its interior test); no raster sets it at present
 static_assert(ENVS_PER_BLOCK <= 64, "the env position of a queue entry has six bits");
@@ -2059,7 +2059,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   ChunkObjMasks<OBJ> objmasks;
   objmasks.load(R, e0, e1, n_tiles * 4, tile * 4 + __builtin_amdgcn_readfirstlane(wave), lane);
   // pixels of this block inside the screen boxes of the objects in `om` -> appended from the far end of the region
-  auto push_obj = [&](const int e, const uint32_t env, unsigned long long om, bool oedge[PPT]) __attribute__((always_inline)) {
+  // pedge: the pixel is a plane edge too (what this raster stores for it is not final).  A box pixel that is none keeps the stored one-ray colour --
+  // the byte-weight filter's, as every pixel outside the boxes -- unless a mesh triangle covers a sample of it (k_resolve_obj, QE_PLANE_EDGE).
+  auto push_obj = [&](const int e, const uint32_t env, unsigned long long om, bool oedge[PPT], const bool pedge[PPT]) __attribute__((always_inline)) {
     const ObjBox* boxes = R.objbox + (size_t)env * DTSIM_MAX_OBJECTS;
     // The coordinates are kept as halves (registers); their rounding (<= 0.25 px below 1024) is covered by widening the
     // box: a pixel just outside a box may take the exact path for nothing, one inside always does.
@@ -2084,7 +2086,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
         const unsigned long long mk = __ballot(ek);
         if (ek) {
           const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-          w_queue[QREGION - 1 - (qo + rank)] = (uint16_t)(etag | QE_PLANE_EDGE | (uint32_t)(k * 64 + lane));
+          w_queue[QREGION - 1 - (qo + rank)] = (uint16_t)(etag | (pedge[k] ? QE_PLANE_EDGE : 0u) | (uint32_t)(k * 64 + lane));
         }
         qo += __popcll(mk);
       }
@@ -2106,10 +2108,10 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
         d32[0] = f.sky[0] & m0; d32[1] = f.sky[1] & m1; d32[2] = f.sky[2] & m2;
       }
       if (OBJ && om) {                               // mesh objects in front of the sky
-        bool oedge[PPT];
+        bool oedge[PPT], pedge[PPT];                 // (no plane edge in an all-sky block: the stored horizon colour is final)
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) oedge[k] = false;
-        push_obj(e, f.env, om, oedge);
+        for (int k = 0; k < PPT; ++k) oedge[k] = pedge[k] = false;
+        push_obj(e, f.env, om, oedge, pedge);
       }
       if (OBJ) qend_v = lane >= e - e0 ? qo : qend_v;
     }
@@ -2280,7 +2282,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
       }
     }
 
-    if (OBJ && om) push_obj(e, env, om, oedge);   // wave-uniform: some object's screen box meets this block
+    if (OBJ && om) push_obj(e, env, om, oedge, edge);   // wave-uniform: some object's screen box meets this block
 
     if (any_invalid) {                               // wave-uniform, rare: source pixels outside the rectilinear image are 0
 #pragma unroll

@@ -295,7 +295,7 @@ def _shade_planes(cam, scene, lighting, cls, ti, tj, t_s, wx_s, wz_s, rc):
 def _object_instances(scene, obj_states):
     """World-space lit-ready triangles of all visible objects: list of
     (verts [T,3,3], normals [T,3,3], colors [T,3,3], uvs [T,3,2], per-triangle texture image or None
-    -- the chunk's map_Kd texture, objmesh.py:268-275)."""
+    -- the chunk's map_Kd texture, objmesh.py:268-275, index into scene.m.objects)."""
     out = []
     for k, o in enumerate(scene.m.objects):
         st = obj_states[k] if obj_states is not None else None
@@ -328,13 +328,15 @@ def _object_instances(scene, obj_states):
             pat = int(st["light_pattern"]) if (st is not None and "light_pattern" in st) else int(o.light_pattern)
             n0 = int(getattr(mesh, "chunk_sizes", [0])[0])
             tri_img = [cards[pat] if t < n0 else im for t, im in enumerate(tri_img)]
-        out.append((Vw, Nw, mesh.colors.astype(np.float64), uvs, tri_img))
+        out.append((Vw, Nw, mesh.colors.astype(np.float64), uvs, tri_img, k))
     return out
 
 
-def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_depth=False):
+def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_depth=False, return_ids=False):
     """[H,W,3] float (0..255) of the un-distorted frame, row 0 = top.  return_depth: also the four per-sample depth buffers
-    (eye depth of the nearest opaque fragment, inf = clear colour) -- what overlay_leds tests the LED spheres against."""
+    (eye depth of the nearest opaque fragment, inf = clear colour) -- what overlay_leds tests the LED spheres against.
+    return_ids: also (last) four [H,W] int arrays, one per MSAA sample in SAMPLE_OFFSETS' order: the index into scene.m.objects of
+    the object whose triangle won the sample, -1 where a tile, the ground or the sky did."""
     W, H = cam.W, cam.H
     cols, rows = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     nxc = 2 * (cols + 0.5) / W - 1
@@ -344,7 +346,7 @@ def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_d
 
     # objects: eye-space vertices, per-vertex lit colours, screen coordinates
     tris = []
-    for Vw, Nw, Cc, UV, TI in _object_instances(scene, obj_states):
+    for Vw, Nw, Cc, UV, TI, oi in _object_instances(scene, obj_states):
         Pe = cam.to_eye(Vw)
         Ne = cam.normal_to_eye(Nw)
         lit = np.minimum(Cc * (cam.base + cam.dif * cam.ndl(Pe, Ne)[..., None]), 1.0) * 255.0
@@ -354,10 +356,10 @@ def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_d
             sx = (Pe[..., 0] / w / cam.tx + 1) * 0.5 * W       # pixel coords, x right
             sy = (1 - Pe[..., 1] / w / cam.ty) * 0.5 * H       # y down
         for k in np.flatnonzero(ok):
-            tris.append((sx[k], sy[k], w[k], lit[k], UV[k], TI[k]))
+            tris.append((sx[k], sy[k], w[k], lit[k], UV[k], TI[k], oi))
 
     acc = np.zeros((H, W, 3))
-    depths = []
+    depths, ids = [], []
     for (ox, oy) in SAMPLE_OFFSETS:
         nx, ny = nxc + 2 * ox / W, nyc - 2 * oy / H
         xe, ye, yla, fwd = _rays(cam, nx, ny)
@@ -366,6 +368,7 @@ def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_d
         ti = np.zeros((H, W), np.int64)
         tj = np.zeros((H, W), np.int64)
         depth = np.full((H, W), np.inf)
+        owner = np.full((H, W), -1, np.int64)
         t_s = np.zeros((H, W)); wx_s = np.zeros((H, W)); wz_s = np.zeros((H, W))
         # ground
         tg, wxg, wzg = _plane_hit(cam, xe, fwd, yla, cam.C[1] - GROUND_Y)
@@ -385,7 +388,7 @@ def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_d
         depth[tok] = tt[tok]; t_s[tok] = tt[tok]; wx_s[tok] = wxt[tok]; wz_s[tok] = wzt[tok]
         col = _shade_planes(cam, scene, lighting, cls, ti, tj, t_s, wx_s, wz_s, rc)
         # objects: z-buffered triangles, coverage at the sample, colour at the pixel centre
-        for (sx, sy, w, lit, uv, timg) in tris:
+        for (sx, sy, w, lit, uv, timg, oi) in tris:
             x0 = max(int(math.floor(sx.min() - 1)), 0); x1 = min(int(math.ceil(sx.max() + 1)), W - 1)
             y0 = max(int(math.floor(sy.min() - 1)), 0); y1 = min(int(math.ceil(sy.max() + 1)), H - 1)
             if x0 > x1 or y0 > y1:
@@ -427,9 +430,12 @@ def render_rectilinear(cam, scene, lighting="gouraud", obj_states=None, return_d
             sub[win] = d[win]
             csub = col[y0:y1 + 1, x0:x1 + 1]
             csub[win] = colc[win]
+            owner[y0:y1 + 1, x0:x1 + 1][win] = oi
         acc += col
         depths.append(depth)
-    return (acc / 4.0, depths) if return_depth else acc / 4.0
+        ids.append(owner)
+    out = (acc / 4.0,) + ((depths,) if return_depth else ()) + ((ids,) if return_ids else ())
+    return out if len(out) > 1 else out[0]
 
 
 def to_u8(img):
@@ -444,6 +450,18 @@ def distort(img_u8, rmapx, rmapy):
     ok = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H)
     out = np.zeros_like(img_u8)
     out[ok] = img_u8[sy[ok], sx[ok]]
+    return out
+
+
+def distort_ids(ids, rmapx, rmapy):
+    """An [H,W] id array of render_rectilinear(return_ids=True) through the fisheye, as distort() moves the image: nearest source
+    pixel, -1 where the source lies outside the frame."""
+    H, W = ids.shape
+    sx = np.rint(rmapx.astype(np.float64)).astype(np.int64)
+    sy = np.rint(rmapy.astype(np.float64)).astype(np.int64)
+    ok = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H)
+    out = np.full_like(ids, -1)
+    out[ok] = ids[sy[ok], sx[ok]]
     return out
 
 
@@ -584,19 +602,27 @@ def overlay_leds(img_u8, cam, depths, spheres):
     return to_u8(out + 0.25 * add)
 
 
-def render_obs(cam, scene, lighting="gouraud", rmap=None, obj_states=None, lines=None, leds=None):
+def render_obs(cam, scene, lighting="gouraud", rmap=None, obj_states=None, lines=None, leds=None, return_ids=False):
     """Simulator.render_obs (simulator.py:1953-1972): uint8 [H,W,3]; `lines`: draw_curve / draw_bbox overlays (overlay_lines); `leds`: the LED
-    spheres of enable_leds (led_spheres -> overlay_leds)."""
+    spheres of enable_leds (led_spheres -> overlay_leds).  return_ids: (image, the four per-sample object-id arrays of
+    render_rectilinear, moved through the fisheye as the image is)."""
+    ids = None
     if leds is not None and len(leds):
-        f, depths = render_rectilinear(cam, scene, lighting, obj_states, return_depth=True)
+        f, depths, *rest = render_rectilinear(cam, scene, lighting, obj_states, return_depth=True, return_ids=return_ids)
         img = overlay_leds(to_u8(f), cam, depths, leds)
+        ids = rest[0] if return_ids else None
+    elif return_ids:
+        f, ids = render_rectilinear(cam, scene, lighting, obj_states, return_ids=True)
+        img = to_u8(f)
     else:
         img = to_u8(render_rectilinear(cam, scene, lighting, obj_states))
     if lines is not None and len(lines):
         img = overlay_lines(img, cam, lines)
     if rmap is not None:
         img = distort(img, rmap[0], rmap[1])
-    return img
+        if return_ids:
+            ids = [distort_ids(a, rmap[0], rmap[1]) for a in ids]
+    return (img, ids) if return_ids else img
 
 
 def segment_view(cam, scene, seg_textures, mesh_colors):

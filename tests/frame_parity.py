@@ -58,6 +58,28 @@ FACADE_OVERLAY = Tol(None, 3e-3, 0.1)        # draw_curve / enable_leds frames
 FACADE_BBOX = Tol(None, 1e-2, 0.3)           # draw_bbox view (the lines are drawn over the meshes: no depth test against them)
 
 
+class ObjTol(NamedTuple):
+    """The bounds of compare_objects: `frame` on the whole frame; of an object's interior pixels at most obj_share of them + obj_slack
+    beyond +-2; of the pixels away from every object at most outside_gt2 x W x H beyond +-2."""
+    frame: Tol
+    obj_share: float
+    obj_slack: float
+    outside_gt2: float
+
+
+OBJ_MIN_INTERIOR = 16                        # an object is judged on its own from this many interior pixels in the oracle
+# "crowded frames, per object": ORACLE_MESH on the frame; per object the 5 % of the touched pixels that overlay_lines_tol / leds_tol
+# allow, + 2 pixels; away from the objects ORACLE_PLANE's beyond-2 share of the frame
+ORACLE_OBJECTS = ObjTol(ORACLE_MESH, 0.05, 2.0, ORACLE_PLANE.gt2)
+
+
+def tighter(tol, k):
+    """`tol` with every bound divided by k (the oracle's own headroom under a row: tests/test_crowd_scenes_host.py)."""
+    if isinstance(tol, ObjTol):
+        return ObjTol(tighter(tol.frame, k), tol.obj_share / k, tol.obj_slack / k, tol.outside_gt2 / k)
+    return Tol(*(None if b is None else b / k for b in tol))
+
+
 def overlay_lines_tol(n_line, W, H):
     """"`draw_curve` / `draw_bbox` overlays", through the fisheye: ORACLE_PLANE's beyond-2 bound plus 5 % of the n_line line pixels of a W x H frame."""
     return Tol(None, 5e-4 + 0.05 * n_line / (W * H), 0.05)
@@ -97,9 +119,11 @@ def camera(sim, e, W, H, dr, colors=None):
     """Env e's camera.  Colours and light come from its init state ((0, 3, 0, 1) unless the facade captured the light through a
     model-view) -- or, for device-side resets that moved them since, from `colors`: env e's row of DTSIM_FIELD_COLORS
     (horizon, ground, ambient, diffuse, light xyzw)."""
-    st = sim.init_states[e]
-    pos = sim.read(_ffi.FIELD_POS)[e]
-    ang = sim.read(_ffi.FIELD_ANGLE)[e]
+    return camera_of_state(sim.init_states[e], sim.read(_ffi.FIELD_POS)[e], sim.read(_ffi.FIELD_ANGLE)[e], W, H, dr, colors)
+
+
+def camera_of_state(st, pos, ang, W, H, dr, colors=None):
+    """The camera of an env with init state `st` standing at (pos, ang): what camera() builds from a device's state."""
     if colors is None:
         horizon, ground, ambient, diffuse, light = (list(v) for v in (st.horizon_color, st.ground_color, st.light_ambient, st.light_diffuse, st.light_pos))
     else:
@@ -185,3 +209,53 @@ def compare_envs(sim, frames, envs, scene_of, rmap, tol, *, dr, mode=None, count
         assert_within(s, tol, e)
         worst = {f: max(worst[f], s[f]) for f in worst}
     return worst, n_obj_px
+
+
+def interior(ids, k):
+    """Pixels whose four samples all carry object k's id (`ids`: the four per-sample arrays of raster.render_obs(return_ids=True))."""
+    return (ids[0] == k) & (ids[1] == k) & (ids[2] == k) & (ids[3] == k)
+
+
+def away_from_objects(ids):
+    """Pixels none of whose samples, nor any sample of their 3 x 3 neighbourhood, belongs to an object."""
+    obj = (ids[0] >= 0) | (ids[1] >= 0) | (ids[2] >= 0) | (ids[3] >= 0)
+    H, W = obj.shape
+    p = np.zeros((H + 2, W + 2), bool)
+    p[1:-1, 1:-1] = obj
+    near = np.zeros((H, W), bool)
+    for dy in range(3):
+        for dx in range(3):
+            near |= p[dy:dy + H, dx:dx + W]
+    return ~near
+
+
+def compare_objects(frame, ref, ids, tol=ORACLE_OBJECTS, ctx=None):
+    """`frame` against the oracle's `ref` with the oracle's per-sample object ids, asserted in this order: (a) the whole frame within
+    tol.frame; (b) for every object with >= OBJ_MIN_INTERIOR interior pixels, the interior pixels beyond +-2 are at most
+    tol.obj_share of them + tol.obj_slack -- a dropped object, a dropped slice of its triangles, the wrong winner between two objects
+    or an unqueued box pixel move far more; (c) away from the objects (away_from_objects) at most tol.outside_gt2 x W x H pixels are
+    beyond +-2: nothing leaks outside a silhouette.  `ctx` (the env, the case) leads every message.
+    Returns dict(frame=stats(), judged=objects judged, obj_share=the worst share of an object's interior pixels beyond +-2,
+    obj_worst=(object, beyond +-2, interior pixels) of that object, outside=pixels beyond +-2 away from the objects)."""
+    H, W = frame.shape[:2]
+    s = stats(frame, ref)
+    assert_within(s, tol.frame, ctx)
+    bad = np.abs(frame.astype(np.int32) - ref.astype(np.int32)).max(axis=-1) > 2
+    out = dict(frame=s, judged=0, obj_share=0.0, obj_worst=None, outside=0)
+    for k in np.unique(np.stack(ids)):
+        if k < 0:
+            continue
+        inner = interior(ids, k)
+        n = int(inner.sum())
+        if n < OBJ_MIN_INTERIOR:
+            continue
+        n_bad = int((bad & inner).sum())
+        out["judged"] += 1
+        if out["obj_worst"] is None or n_bad / n > out["obj_share"]:
+            out["obj_share"], out["obj_worst"] = n_bad / n, (int(k), n_bad, n)
+        assert n_bad <= tol.obj_share * n + tol.obj_slack, (ctx, f"object {int(k)}: {n_bad} of its {n} interior pixels beyond +-2",
+                                                            [tuple(int(v) for v in yx) for yx in np.argwhere(bad & inner)[:8]])
+    out["outside"] = int((bad & away_from_objects(ids)).sum())
+    assert out["outside"] <= tol.outside_gt2 * W * H, (ctx, f"{out['outside']} pixels beyond +-2 away from every object",
+                                                        [tuple(int(v) for v in yx) for yx in np.argwhere(bad & away_from_objects(ids))[:8]])
+    return out

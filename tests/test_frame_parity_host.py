@@ -69,3 +69,69 @@ def test_stats_on_a_hand_computed_pair():
     mask = np.array([[False, False], [True, False]])                                 # the 9 left out: 3 pixels, 9 values
     assert P.stats(a, b, mask) == dict(mean=5 / 9, gt1=2 / 3, gt2=1 / 3, gt8=0.0, max=3)
     assert P.stats(b, a) == P.stats(a, b) and P.stats(a, a)["max"] == 0
+
+
+# ---- compare_objects: the per-object and outside-the-objects bounds bite at their bounds ---------------------------------------------
+
+OH = OW = 200           # 40000 pixels: ORACLE_MESH allows 40 beyond +-2 on the frame, more than any count below, so rows (b) and (c) decide
+
+
+def _object_scene():
+    """A grey frame pair and the four per-sample id arrays: object 0 owns a 20 x 20 square (400 interior pixels: 5 % + 2 = 22), object 1 a
+    4 x 4 one (16: 2.8, i.e. 2), object 2 a 3 x 5 one (15 interior pixels: not judged on its own); object 3 owns only three of the four samples
+    of an 8 x 8 square (no interior pixel)."""
+    ref = np.full((OH, OW, 3), 100, np.uint8)
+    ids = np.full((4, OH, OW), -1, np.int64)
+    ids[:, 10:30, 10:30] = 0
+    ids[:, 50:54, 50:54] = 1
+    ids[:, 80:83, 80:85] = 2
+    ids[:3, 120:128, 120:128] = 3
+    return ref, ids
+
+
+def _spoil(frame, ys, xs, n):
+    frame[np.asarray(ys)[:n], np.asarray(xs)[:n], 1] += 3          # beyond +-2 in one channel
+    return frame
+
+
+def test_compare_objects_bounds_the_interior_of_each_object():
+    ref, ids = _object_scene()
+    assert P.ORACLE_OBJECTS == P.ObjTol(P.ORACLE_MESH, 0.05, 2.0, P.ORACLE_PLANE.gt2) and P.OBJ_MIN_INTERIOR == 16
+    yy, xx = np.nonzero(P.interior(ids, 0))
+    r = P.compare_objects(_spoil(ref.copy(), yy, xx, 22), ref, ids)
+    assert r["judged"] == 2 and r["obj_worst"] == (0, 22, 400) and r["obj_share"] == 22 / 400 and r["outside"] == 0
+    with pytest.raises(AssertionError, match="object 0: 23 of its 400 interior pixels"):
+        P.compare_objects(_spoil(ref.copy(), yy, xx, 23), ref, ids, ctx="env 5")
+    yy, xx = np.nonzero(P.interior(ids, 1))
+    assert P.compare_objects(_spoil(ref.copy(), yy, xx, 2), ref, ids)["obj_worst"] == (1, 2, 16)
+    with pytest.raises(AssertionError, match="object 1: 3 of its 16 interior pixels"):
+        P.compare_objects(_spoil(ref.copy(), yy, xx, 3), ref, ids)
+    # an object that is not drawn at all (what shows instead is 5 / 255 away: the frame's mean stays inside its row)
+    gone = ref.copy(); gone[50:54, 50:54] = 95
+    with pytest.raises(AssertionError, match="object 1: 16 of its 16"):
+        P.compare_objects(gone, ref, ids)
+    # objects without a countable interior are not judged on their own: rows (a) and (c) still see them
+    small = ref.copy(); small[80:83, 80:85] = 95
+    assert P.compare_objects(small, ref, ids)["judged"] == 2
+
+
+def test_compare_objects_bounds_what_leaks_outside_the_objects():
+    ref, ids = _object_scene()
+    away = P.away_from_objects(ids)
+    assert not away[9:31, 9:31].any() and away[8, 8] and away[31, 31] and not away[119, 119] and away[118, 118]      # one pixel around every object sample
+    yy, xx = np.nonzero(away)
+    assert P.compare_objects(_spoil(ref.copy(), yy, xx, 20), ref, ids)["outside"] == 20          # ORACLE_PLANE.gt2 x 40000 = 20
+    with pytest.raises(AssertionError, match="21 pixels beyond \\+-2 away from every object"):
+        P.compare_objects(_spoil(ref.copy(), yy, xx, 21), ref, ids)
+    ring = ~away & ~(ids >= 0).any(axis=0)                                                        # the ring next to a silhouette belongs to neither row
+    yy, xx = np.nonzero(ring)
+    r = P.compare_objects(_spoil(ref.copy(), yy, xx, 30), ref, ids)
+    assert r["outside"] == 0 and r["obj_share"] == 0.0 and r["frame"]["gt2"] == 30 / (OH * OW)
+    with pytest.raises(AssertionError, match="'gt2'"):                                            # ... but to the frame's row, asserted first
+        P.compare_objects(_spoil(ref.copy(), yy, xx, 41), ref, ids)
+
+
+def test_tighter_divides_every_bound():
+    t = P.tighter(P.ORACLE_OBJECTS, 4)
+    assert t == P.ObjTol(P.Tol(5e-4, 2.5e-4, 0.0075), 0.0125, 0.5, 1.25e-4)
+    assert P.tighter(P.ORACLE_MESH_GT1, 2) == P.Tol(1e-3, None, 0.015)
