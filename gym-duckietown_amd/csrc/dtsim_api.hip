@@ -180,45 +180,6 @@ struct dtsim {
 
 namespace {
 
-template <typename T>
-T* carve(char*& p, size_t count) {
-  T* r = reinterpret_cast<T*>(p);
-  size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
-  p += bytes;
-  return r;
-}
-
-size_t layout_arrays(SimArrays& A, int N, char* base) {
-  char* p = base;
-  const size_t n = (size_t)N;
-  A.N = N;
-  A.pos_x = carve<double>(p, n); A.pos_z = carve<double>(p, n); A.angle = carve<double>(p, n);
-  A.q_x = carve<double>(p, n); A.q_y = carve<double>(p, n); A.q_c = carve<double>(p, n); A.q_s = carve<double>(p, n);
-  A.vel_u = carve<double>(p, n); A.vel_w = carve<double>(p, n);
-  A.ring = carve<double>(p, n * DTSIM_MAX_DELAY * 2);
-  A.war = carve<double>(p, n); A.wal = carve<double>(p, n); A.wheel_dist = carve<double>(p, n);
-  A.timestamp = carve<double>(p, n); A.speed = carve<double>(p, n); A.reward = carve<double>(p, n);
-  A.lane = carve<double>(p, n * 4); A.prox = carve<double>(p, n); A.wheels = carve<double>(p, n * 2);
-  A.ob_cx = carve<double>(p, n * DTSIM_MAX_DYNAMIC); A.ob_cz = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_sx = carve<double>(p, n * DTSIM_MAX_DYNAMIC); A.ob_sz = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_corners = carve<double>(p, n * DTSIM_MAX_DYNAMIC * 8);
-  A.ob_vel = carve<double>(p, n * DTSIM_MAX_DYNAMIC); A.ob_wait = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_time = carve<double>(p, n * DTSIM_MAX_DYNAMIC); A.ob_angle = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_wiggle = carve<double>(p, n * DTSIM_MAX_DYNAMIC); A.ob_yrot = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.cam = carve<float>(p, n * 6); A.colors = carve<float>(p, n * 16);
-  A.ring_head = carve<int32_t>(p, n); A.step_count = carve<int32_t>(p, n);
-  A.tile_i = carve<int32_t>(p, n); A.tile_j = carve<int32_t>(p, n);
-  A.map_id = carve<int32_t>(p, n); A.episode = carve<int32_t>(p, n);
-  A.done = carve<uint8_t>(p, n); A.done_code = carve<uint8_t>(p, n); A.in_lane = carve<uint8_t>(p, n);
-  A.ob_active = carve<uint8_t>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_visible = carve<uint8_t>(p, n * DTSIM_MAX_OBJECTS);
-  A.ob_light = carve<uint8_t>(p, n * DTSIM_MAX_OBJECTS);
-  A.tl_time = carve<double>(p, n);
-  A.ob_cy = carve<double>(p, n * DTSIM_MAX_DYNAMIC);
-  A.ob_ext = carve<double>(p, n * DTSIM_MAX_DYNAMIC * 5);
-  return (size_t)(p - base);
-}
-
 StepParams step_params(const dtsim* h, int n_steps) {
   StepParams P{};
   P.n_steps = n_steps;
@@ -329,12 +290,11 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     if (e != hipSuccess) { delete h; return fail(DTSIM_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     h->own_stream = true;
   }
-  SimArrays tmp{};
-  h->slab_bytes = layout_arrays(tmp, h->N, reinterpret_cast<char*>(4096));
+  h->slab_bytes = dt_state_layout(h->A, h->N, nullptr);
   hipError_t e = dev_alloc(h->slab, h->slab_bytes);
   if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(state %zu B): %s", h->slab_bytes, hipGetErrorString(e)); }
   (void)hipMemsetAsync(h->slab.get(), 0, h->slab_bytes, h->stream);
-  layout_arrays(h->A, h->N, h->slab.get());
+  dt_state_layout(h->A, h->N, h->slab.get());
   // map_id = -1 everywhere so the first reset creates the world objects
   (void)hipMemsetAsync(h->A.map_id, 0xFF, sizeof(int32_t) * (size_t)h->N, h->stream);
   e = dev_alloc(h->d_states, (size_t)h->N);
@@ -911,80 +871,6 @@ int dtsim_query(dtsim_t* h, int n, const int32_t* env_idx, const double* poses, 
 
 // ---- field access -------------------------------------------------------------
 namespace {
-struct FieldDesc { void* base; size_t elem; int comps; size_t comp_stride_elems; bool planar; };
-
-// planar == true: device layout is [comps][N]; the public layout is [N][comps].
-bool field_desc(dtsim* h, int field, FieldDesc& d) {
-  const SimArrays& A = h->A;
-  const size_t N = (size_t)h->N;
-  switch (field) {
-    case DTSIM_FIELD_ANGLE: d = {A.angle, 8, 1, N, true}; return true;
-    case DTSIM_FIELD_REWARD: d = {A.reward, 8, 1, N, true}; return true;
-    case DTSIM_FIELD_DONE: d = {A.done, 1, 1, N, true}; return true;
-    case DTSIM_FIELD_DONE_CODE: d = {A.done_code, 1, 1, N, true}; return true;
-    case DTSIM_FIELD_STEP_COUNT: d = {A.step_count, 4, 1, N, true}; return true;
-    case DTSIM_FIELD_LANE: d = {A.lane, 8, 4, N, true}; return true;
-    case DTSIM_FIELD_IN_LANE: d = {A.in_lane, 1, 1, N, true}; return true;
-    case DTSIM_FIELD_PROX: d = {A.prox, 8, 1, N, true}; return true;
-    case DTSIM_FIELD_SPEED: d = {A.speed, 8, 1, N, true}; return true;
-    case DTSIM_FIELD_TIMESTAMP: d = {A.timestamp, 8, 1, N, true}; return true;
-    case DTSIM_FIELD_WHEELS: d = {A.wheels, 8, 2, N, true}; return true;
-    case DTSIM_FIELD_MAP_ID: d = {A.map_id, 4, 1, N, true}; return true;
-    case DTSIM_FIELD_OBJ_ACTIVE: d = {A.ob_active, 1, DTSIM_MAX_DYNAMIC, N, true}; return true;
-    case DTSIM_FIELD_OBJ_YROT: d = {A.ob_yrot, 8, DTSIM_MAX_DYNAMIC, N, true}; return true;
-    case DTSIM_FIELD_OBJ_VISIBLE: d = {A.ob_visible, 1, DTSIM_MAX_OBJECTS, N, true}; return true;
-    case DTSIM_FIELD_OBJ_LIGHT: d = {A.ob_light, 1, DTSIM_MAX_OBJECTS, N, true}; return true;
-    case DTSIM_FIELD_OBJ_Y: d = {A.ob_cy, 8, DTSIM_MAX_DYNAMIC, N, true}; return true;
-    case DTSIM_FIELD_EPISODE: d = {A.episode, 4, 1, N, true}; return true;
-    case DTSIM_FIELD_CAMERA: d = {A.cam, 4, 6, N, true}; return true;
-    case DTSIM_FIELD_COLORS: d = {A.colors, 4, 16, N, true}; return true;
-    case DTSIM_FIELD_WHEEL_DIST: d = {A.wheel_dist, 8, 1, N, true}; return true;
-    default: return false;
-  }
-}
-
-size_t public_bytes(const dtsim* h, int field) {
-  const size_t N = (size_t)h->N;
-  switch (field) {
-    case DTSIM_FIELD_POS: return N * 3 * 8;
-    case DTSIM_FIELD_TILE: return N * 2 * 4;
-    case DTSIM_FIELD_OBJ_CENTER: return N * DTSIM_MAX_DYNAMIC * 2 * 8;
-    case DTSIM_FIELD_OBJ_PARAMS: return N * DTSIM_MAX_DYNAMIC * 3 * 8;
-    case DTSIM_FIELD_OBJ_EXTRA: return N * DTSIM_MAX_DYNAMIC * 5 * 8;
-    case DTSIM_FIELD_STATE_BLOB: return h->slab_bytes;
-    case DTSIM_FIELD_RENDER_POS: return N * 4;
-    case DTSIM_FIELD_RENDER_PIPE: return N * 4;
-    default: {
-      FieldDesc d;
-      if (!field_desc(const_cast<dtsim*>(h), field, d)) return 0;
-      return N * d.comps * d.elem;
-    }
-  }
-}
-
-// copy `ncomp` planar device arrays ([c][N], given per-component base pointers) into the
-// public [N][ncomp] layout (or back).
-int xfer_planar(dtsim* h, void* const* bases, int ncomp, size_t elem, void* host, bool to_host) {
-  const size_t N = (size_t)h->N;
-  std::vector<char> tmp(N * elem);
-  for (int c = 0; c < ncomp; ++c) {
-    if (to_host) {
-      if (bases[c] == nullptr) { memset(tmp.data(), 0, tmp.size()); }
-      else {
-        hipError_t e = hipMemcpy(tmp.data(), bases[c], N * elem, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy D2H: %s", hipGetErrorString(e));
-      }
-      for (size_t i = 0; i < N; ++i) memcpy((char*)host + (i * ncomp + c) * elem, tmp.data() + i * elem, elem);
-    } else {
-      if (bases[c] == nullptr) continue;
-      for (size_t i = 0; i < N; ++i) memcpy(tmp.data() + i * elem, (const char*)host + (i * ncomp + c) * elem, elem);
-      hipError_t e = hipMemcpy(bases[c], tmp.data(), N * elem, hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy H2D: %s", hipGetErrorString(e));
-    }
-  }
-  return DTSIM_OK;
-}
-
 __global__ void k_agent_info(SimArrays A, int e, dtsim_agent_info* out) {
   const size_t N = A.N;
   dtsim_agent_info r;
@@ -998,32 +884,30 @@ __global__ void k_agent_info(SimArrays A, int e, dtsim_agent_info* out) {
   *out = r;
 }
 
+// dtsim_read / dtsim_write: a field of state_fields.h's table, one hipMemcpy per plane through the interleave of its public layout
 int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
   if (!h || !host) return fail(DTSIM_E_INVALID, "null argument");
-  const size_t need = public_bytes(h, field);
+  const StateField* f = dt_state_field(field);
+  const size_t N = (size_t)h->N, need = f ? dt_field_bytes(*f, N, h->slab_bytes) : 0;
   if (need == 0) return fail(DTSIM_E_INVALID, "unknown field %d", field);
   if (bytes != need) return fail(DTSIM_E_INVALID, "field %d: %zu bytes given, %zu expected", field, bytes, need);
   hipError_t e0 = hipSetDevice(h->cfg.device);
   if (e0 == hipSuccess) e0 = hipStreamSynchronize(h->stream);
   if (e0 != hipSuccess) return fail(DTSIM_E_HIP, "sync: %s", hipGetErrorString(e0));
-  const SimArrays& A = h->A;
-  const size_t N = (size_t)h->N;
-  std::vector<void*> bases;
-  switch (field) {
+  if (!to_host && !f->writable) return fail(DTSIM_E_INVALID, "%s is read-only", f->name);
+  switch (field) {                                    // what is no view of the slab's arrays
     case DTSIM_FIELD_STATE_BLOB: {
       hipError_t e = to_host ? hipMemcpy(host, h->slab.get(), need, hipMemcpyDeviceToHost)
                              : hipMemcpy(h->slab.get(), host, need, hipMemcpyHostToDevice);
       if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy blob: %s", hipGetErrorString(e));
       return DTSIM_OK;
     }
-    case DTSIM_FIELD_RENDER_PIPE: {                   // read-only
-      if (!to_host) return fail(DTSIM_E_INVALID, "DTSIM_FIELD_RENDER_PIPE is read-only");
+    case DTSIM_FIELD_RENDER_PIPE: {
       int32_t* out = static_cast<int32_t*>(host);
       for (size_t i = 0; i < N; ++i) out[i] = (int32_t)h->render_pipe;
       return DTSIM_OK;
     }
-    case DTSIM_FIELD_RENDER_POS: {                    // read-only; the identity until a render pass ran in k_env_sort's order
-      if (!to_host) return fail(DTSIM_E_INVALID, "DTSIM_FIELD_RENDER_POS is read-only");
+    case DTSIM_FIELD_RENDER_POS: {                    // the identity until a render pass ran in k_env_sort's order
       int32_t* out = static_cast<int32_t*>(host);
       if (h->render_tables & 4) {
         RenderParams R{}; render_scratch(h, 0, &R);
@@ -1034,25 +918,22 @@ int field_xfer(dtsim* h, int field, void* host, size_t bytes, bool to_host) {
       }
       return DTSIM_OK;
     }
-    case DTSIM_FIELD_POS: bases = {A.pos_x, nullptr, A.pos_z}; return xfer_planar(h, bases.data(), 3, 8, host, to_host);
-    case DTSIM_FIELD_TILE: bases = {A.tile_i, A.tile_j}; return xfer_planar(h, bases.data(), 2, 4, host, to_host);
-    case DTSIM_FIELD_OBJ_CENTER:
-      for (int d = 0; d < DTSIM_MAX_DYNAMIC; ++d) { bases.push_back(A.ob_cx + d * N); bases.push_back(A.ob_cz + d * N); }
-      return xfer_planar(h, bases.data(), DTSIM_MAX_DYNAMIC * 2, 8, host, to_host);
-    case DTSIM_FIELD_OBJ_PARAMS:
-      for (int d = 0; d < DTSIM_MAX_DYNAMIC; ++d) { bases.push_back(A.ob_vel + d * N); bases.push_back(A.ob_wait + d * N); bases.push_back(A.ob_wiggle + d * N); }
-      return xfer_planar(h, bases.data(), DTSIM_MAX_DYNAMIC * 3, 8, host, to_host);
-    case DTSIM_FIELD_OBJ_EXTRA:
-      for (int d = 0; d < DTSIM_MAX_DYNAMIC; ++d)
-        for (int k = 0; k < 5; ++k) bases.push_back(A.ob_ext + ((size_t)k * DTSIM_MAX_DYNAMIC + d) * N);
-      return xfer_planar(h, bases.data(), DTSIM_MAX_DYNAMIC * 5, 8, host, to_host);
-    default: {
-      FieldDesc d;
-      field_desc(h, field, d);
-      for (int c = 0; c < d.comps; ++c) bases.push_back((char*)d.base + c * d.comp_stride_elems * d.elem);
-      return xfer_planar(h, bases.data(), d.comps, d.elem, host, to_host);
+  }
+  const int comps = dt_field_comps(*f);
+  std::vector<char> tmp(N * f->elem);
+  for (int c = 0; c < comps; ++c) {
+    char* plane = dt_field_plane(h->A, *f, c);
+    if (to_host) {
+      hipError_t e = plane ? hipMemcpy(tmp.data(), plane, tmp.size(), hipMemcpyDeviceToHost) : hipSuccess;
+      if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy D2H: %s", hipGetErrorString(e));
+      dt_plane_to_public(host, plane ? tmp.data() : nullptr, N, comps, c, f->elem);
+    } else if (plane) {
+      dt_public_to_plane(tmp.data(), host, N, comps, c, f->elem);
+      hipError_t e = hipMemcpy(plane, tmp.data(), tmp.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) return fail(DTSIM_E_HIP, "hipMemcpy H2D: %s", hipGetErrorString(e));
     }
   }
+  return DTSIM_OK;
 }
 }  // namespace
 
@@ -1075,15 +956,15 @@ int dtsim_write(dtsim_t* h, int field, const void* src, size_t bytes) {
 }
 
 void* dtsim_field_devptr(dtsim_t* h, int field) {
-  if (!h) return nullptr;
-  if (field == DTSIM_FIELD_STATE_BLOB) return h->slab.get();
-  if (field == DTSIM_FIELD_POS) return h->A.pos_x;  // planar: x plane; z plane = pos_z
-  FieldDesc d;
-  if (!field_desc(h, field, d)) return nullptr;
-  return d.base;
+  const StateField* f = h ? dt_state_field(field) : nullptr;
+  if (!f || !f->view) return nullptr;
+  return f->outer ? dt_field_plane(h->A, *f, 0) : h->slab.get();   // POS: the x plane; the z plane is pos_z
 }
 
-size_t dtsim_field_bytes(const dtsim_t* h, int field) { return h ? public_bytes(h, field) : 0; }
+size_t dtsim_field_bytes(const dtsim_t* h, int field) {
+  const StateField* f = h ? dt_state_field(field) : nullptr;
+  return f ? dt_field_bytes(*f, (size_t)h->N, h->slab_bytes) : 0;
+}
 size_t dtsim_state_bytes(const dtsim_t* h) { return h ? h->slab_bytes : 0; }
 
 int dtsim_sync(dtsim_t* h) {

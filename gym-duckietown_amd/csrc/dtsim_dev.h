@@ -2,7 +2,7 @@
 //
 // HBM layout (DESIGN.md "Data layout"):
 //   * per-env state is struct-of-arrays, one array per scalar, index = env, all carved
-//     from ONE slab so a checkpoint is a single memcpy (DTSIM_FIELD_STATE_BLOB);
+//     from ONE slab so a checkpoint is a single memcpy (SimArrays and the slab's layout: state_fields.h);
 //     thread e of the step kernel touches element e of each array => every load/store
 //     of a wavefront is one fully coalesced 512-byte (f64) transaction.
 //   * per-map tables are one packed blob of 8-byte words per map, copied into LDS by
@@ -14,6 +14,7 @@
 #include "../../include/dtsim.h"
 #include "observe_plan.h"
 #include "scene_tables.h"
+#include "state_fields.h"
 
 // ---- constants of the reference (simulator.py:99-177), evaluated exactly as
 // Python evaluates them (IEEE double, same operation order) -------------------
@@ -24,37 +25,6 @@
 #define DT_SAFETY_RAD_MULT 1.8
 #define DT_AGENT_SAFETY_RAD ((DT_ROBOT_LENGTH / 2) * DT_SAFETY_RAD_MULT) /* max(L,W)=L */
 #define DT_REWARD_INVALID_POSE (-1000.0)
-
-// ---- per-env SoA ------------------------------------------------------------
-struct SimArrays {
-  int32_t N;
-  // pose + dynamics (duckietown_world state, restated)
-  double *pos_x, *pos_z, *angle;
-  double *q_x, *q_y, *q_c, *q_s, *vel_u, *vel_w;
-  double *ring;            // [DTSIM_MAX_DELAY][2][N]  delayed [left,right] duty
-  double *war, *wal;       // angular input gains (trim)
-  double *wheel_dist;
-  double *timestamp, *speed;
-  double *reward;
-  double *lane;            // [4][N]
-  double *prox;
-  double *wheels;          // [2][N]
-  // dynamic objects [slot][N]
-  double *ob_cx, *ob_cz, *ob_sx, *ob_sz;
-  double *ob_corners;      // [8][DTSIM_MAX_DYNAMIC][N]
-  double *ob_vel, *ob_wait, *ob_time, *ob_angle, *ob_wiggle, *ob_yrot;
-  // render / DR parameters (f32, consumed by the raster)
-  float *cam;              // [6][N] height, pitch(rad), fov_y(rad), noise x,y,z
-  float *colors;           // [16][N] horizon rgb, ground rgb, ambient rgb, diffuse rgb, light xyzw
-  int32_t *ring_head, *step_count, *tile_i, *tile_j, *map_id, *episode;
-  uint8_t *done, *done_code, *in_lane;
-  uint8_t *ob_active;      // [DTSIM_MAX_DYNAMIC][N]
-  uint8_t *ob_visible;     // [DTSIM_MAX_OBJECTS][N]
-  uint8_t *ob_light;       // [DTSIM_MAX_OBJECTS][N] TrafficLightObj.pattern
-  double *ob_cy;           // [DTSIM_MAX_DYNAMIC][N] centre height (CheckerboardObj; 0 for the others)
-  double *ob_ext;          // [5][DTSIM_MAX_DYNAMIC][N] DuckiebotObj follow_dist, radius, wheel_dist, robot_width, robot_length
-  double *tl_time;         // [N] TrafficLightObj.time (object clock: not reset with the env, objects.py:441,459)
-};
 
 struct StepParams {
   int32_t n_steps, frame_skip, max_steps, delay_steps;
