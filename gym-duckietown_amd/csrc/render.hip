@@ -47,6 +47,9 @@
 //                 state and the magenta clear / ground colour, k_obj_setup folds the mesh's flat colour into Kd.
 //   Scaffolding shared by the rasters (ahead of k_raster): the XCD-affine workgroup map and its launch size (raster_wg / raster_wg_grid), the v3 LDS
 //                 tile table fill, the chunk's object masks, the packed source-pixel centres (spxy).
+//   Scaffolding shared by the exact paths (same place): the owner tile and ground-quad hit of an MSAA sample (v3_sample_owner, ground_quad_*), the work-list
+//                 grabs (work_n_grabs / work_next_grab over the DT_WORK_* slots of dtsim_dev.h), the tile-record LDS fill; elsewhere the ground quad's
+//                 shading rule (ground_corner_ndl / ground_lit, at ground_ndl), the queue-entry decoders (qe_*) and the 3-byte pixel patch (store_rgb).
 //   Host side: dt_render_layout lays out the render scratch (per-env records, per-pixel tables, queues, work lists); dt_raster_pipe picks the raster.
 //
 // Roofline: algorithmic bytes per env-step = W*H*3 (921 600 B at 640x480), written once (+ the ~1.3 % edge
@@ -522,12 +525,17 @@ __device__ inline void mesh_texel(const RenderParams& R, int tex, float u, float
   for (int k = 0; k < 3; ++k) out[k] = (float)T[k] * (1.f / 255.f);
 }
 
-__device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {
+// ---- ground quad (simulator.py:1806-1812): N.L is lit at the four corners (EnvCam.gndl) and interpolated bilinearly at (a, b) in [0, 1]^2; a channel is
+// gnd * min(base + dif * N.L, 1) -- ground_lit, and still written out in shade, shade_msaa and the env loops of k_raster, k_raster_q and k_raster_v3dr.
+__device__ inline float ground_corner_ndl(const float a, const float b, const float g0, const float g1, const float g2, const float g3) {
+  const float n0 = g0 + a * (g1 - g0), n1 = g2 + a * (g3 - g2);
+  return n0 + b * (n1 - n0);
+}
+__device__ inline float ground_lit(const float gnd, const float base, const float dif, const float ndl) { return gnd * fminf(base + dif * ndl, 1.f); }
+__device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {      // at a world position
   const float a = fminf(fmaxf((wx + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
   const float b = fminf(fmaxf((wz + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
-  const float n0 = c.gndl[0] + a * (c.gndl[1] - c.gndl[0]);
-  const float n1 = c.gndl[2] + a * (c.gndl[3] - c.gndl[2]);
-  return n0 + b * (n1 - n0);
+  return ground_corner_ndl(a, b, c.gndl[0], c.gndl[1], c.gndl[2], c.gndl[3]);
 }
 
 
@@ -1156,7 +1164,9 @@ __device__ inline PixInv pix_inv_dr(float nx, float ny, bool valid, const DrCam&
 // stored for it is not final: k_resolve_obj leaves a pixel alone when no mesh triangle covers any of its samples and the
 // bit is clear (the raster's one-ray colour is the pixel).  The quad-record rasters tell; the generic raster always sets it (its filter is the exact path's).
 #define QE_PLANE_EDGE 0x8000u
-#define QE_ALWAYS_EDGE 0x4000u    // front-of-region entry that is never a one-ray pixel (resolve_region_q skips its interior test); no raster sets it at present
+__device__ inline int qe_pixel(const uint32_t ent) { return (int)(ent & 255u); }            // row-major pixel number in the wavefront block
+__device__ inline int qe_envpos(const uint32_t ent) { return (int)((ent >> 8) & 63u); }     // env position in the chunk (k_resolve reads ent >> 8: front entries carry no flags, the mask costs it 13 instructions)
+__device__ inline bool qe_plane_edge(const uint32_t ent) { return (ent & QE_PLANE_EDGE) != 0u; }
 static_assert(ENVS_PER_BLOCK <= 64, "the env position of a queue entry has six bits");
 #define ITEM_B DT_ITEM_B   // 64-entry batches per k_resolve work item
 #define ITEMS_PER_WG DT_ITEMS_PER_WG
@@ -1169,7 +1179,7 @@ static_assert(ENVS_PER_BLOCK % RES_ENVS == 0 && ENVS_PER_BLOCK / RES_ENVS <= ITE
 
 // The live count of a masked pass (positions [0, live) of the render order), written by k_env_sort<true> after the pass's work-list clear.
 __device__ inline int dt_sub_live(const RenderParams& R) { return __builtin_amdgcn_readfirstlane(R.work[DT_WORK_LIVE]); }
-// Work items of k_resolve_obj (its own list: R.work[2] = count, [3] = cursor; second part of R.items): one per RES_ENVS
+// Work items of k_resolve_obj (its own list: the DT_WORK_OBJ_* slots of R.work; R.items2): one per RES_ENVS
 // env positions of a raster workgroup that queued object-box pixels.
 // groups: bit g = env group g of the chunk (RES_ENVS positions) has object-box entries in some region of the workgroup; the
 // quad-record rasters pass what they queued (round 4: 60 % of the items used to be empty), the others every group.
@@ -1177,7 +1187,7 @@ __device__ inline int dt_sub_live(const RenderParams& R) { return __builtin_amdg
 // order, the others to the back (from the last slot down); k_resolve_obj walks front to back, so the units of close-up objects -- up to
 // 1 024 pixels against every triangle of the object, 100 - 250 us of one wavefront -- start first instead of wherever their raster
 // workgroup happened to finish (the launch used to end on a third of the wavefronts, profiles/r04_wave_spans.txt).
-// work[2] = front count, work[6] = back count, work[3] = cursor; capacity = one slot per (raster workgroup, env group).
+// DT_WORK_OBJ_FRONT / DT_WORK_OBJ_BACK count the two ends, DT_WORK_OBJ_CURSOR is the cursor; capacity = one slot per (raster workgroup, env group).
 __device__ inline size_t obj_items_cap(const RenderParams& R) {
   const int n_tiles = ((R.W + DT_TILE_W - 1) / DT_TILE_W) * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
   return (size_t)((R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK) * n_tiles * (ENVS_PER_BLOCK / RES_ENVS);
@@ -1190,11 +1200,11 @@ __device__ inline void push_obj_items(const RenderParams& R, uint32_t rwg, envma
   const envmask_t light = groups & ~heavy;
   const int nh = __popcll(heavy), nl = __popcll(light);
   if (nh) {
-    int pos = atomicAdd(R.work + 2, nh);
+    int pos = atomicAdd(R.work + DT_WORK_OBJ_FRONT, nh);
     for (int i = 0; i < ng; ++i) if ((heavy >> i) & 1ull) R.items2[pos++] = rwg * ITEMS_PER_WG + (uint32_t)i;
   }
   if (nl) {
-    size_t pos = obj_items_cap(R) - 1 - (size_t)atomicAdd(R.work + 6, nl);
+    size_t pos = obj_items_cap(R) - 1 - (size_t)atomicAdd(R.work + DT_WORK_OBJ_BACK, nl);
     for (int i = 0; i < ng; ++i) if ((light >> i) & 1ull) R.items2[pos--] = rwg * ITEMS_PER_WG + (uint32_t)i;
   }
 }
@@ -1219,8 +1229,12 @@ __device__ inline envmask_t obj_groups_of(int qend_v, int lane, envmask_t* heavy
 
 // ==== scaffolding shared by the rasters ===================================================================================================
 // What every raster must agree on with the host and the exact-path kernels, stated once: the workgroup map and its launch size, the v3 LDS
-// tile table, the chunk's object masks and the packed source-pixel centres.  (The queue appends, push_obj, the four-pixel transposes and the
-// hand-over epilogues are still written out per kernel: as helpers they changed the code generated for the env loops.)  What a kernel does differently is an argument at its call site.
+// tile table, the chunk's object masks and the packed source-pixel centres; further down the exact paths' rules (below; ground_lit at ground_ndl,
+// qe_* at the entry layout, store_rgb at resolve_region_q).  A helper stays only where the compiled kernel is unchanged (tools/isa_compare.py,
+// profiles/exact_path_identity.txt).  Still written out per kernel, because as helpers they changed the generated code: the queue appends, push_obj,
+// the transposes and the hand-over epilogues (the env loops); the item -> workgroup / part / tile / chunk decode and the four regions' batch lookup of
+// k_resolve / k_resolve_dr / k_resolve_obj (a struct, a struct with lazy members, free functions over rn[] / rb[]: 35 - 65 instructions more); k_raster's
+// tile-record fill; ground_lit in k_raster_v3dr's env loop; k_resolve's unmasked env position.  What a kernel does differently is an argument at its call site.
 
 // ---- XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr) and its launch size.
 // Workgroup b runs on XCD b % 8 (round-robin dispatch), and XCD x is given the x-th eighth of the env chunks (all frame tiles of each): with
@@ -1286,6 +1300,45 @@ __device__ inline void v3_fill_tile_table(const RenderParams& R, const uint32_t*
       s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
     }
   }
+}
+
+// ---- the raster tile records of every map -> LDS (k_resolve, k_resolve_obj: [n_tile_recs] TileLds at the start of the workgroup's
+// dynamic LDS).  The caller's barrier follows.  (k_raster keeps the same loop written out: the call moved an instruction of its prologue.)
+__device__ inline void fill_tile_recs(const RenderParams& R, uint32_t* s_mem, const int tid) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(R.tile_recs);
+  for (int i = tid; i < R.n_tile_recs * (int)(sizeof(TileLds) / 4); i += RB) s_mem[i] = src[i];
+}
+
+// ==== scaffolding shared by the exact paths: what resolve_region_q / _v3, k_resolve, k_resolve_dr and k_resolve_obj must agree on, stated once ====
+// ---- the tile that OWNS an MSAA sample at padded quad coordinates (Xs, Zs), on the v3 LDS tile table (qtb; tab: byte offset of the env's map
+// columns): tile boundaries sit at k * 256 + 0.5 (GL_LINEAR's half-texel shift), so ownership goes by (X - 0.5, Z - 0.5), clamped into the padded
+// grid.  tb: the tile's block byte offset (0: none), sel: its record-offset mask; returns s_in: inside the grid.  (resolve_region_q: tile_entry.)
+__device__ inline float med3f(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
+__device__ inline bool v3_sample_owner(const float Xs, const float Zs, const float lo, const float Xhi, const float Zhi, const char* qtb,
+                                       const uint32_t tab, uint32_t& tb, uint32_t& sel) {
+  const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
+  const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
+  const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
+  const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
+  tb = tp[0]; sel = tp[V3_TAB_PITCH / 2];
+  return (Xc == Xo) & (Zc == Zo);
+}
+// ---- ground-quad hit in padded quad coordinates, per axis: camera + kg * (tile-plane hit - camera); inside +-50 m (goff: world 0, ghalf: 50 m)
+__device__ inline float ground_quad_at(const float kg, const float X, const float C) { return fmaf(kg, X - C, C); }
+__device__ inline bool ground_quad_in(const float G, const float goff, const float ghalf) { return fabsf(G - goff) <= ghalf; }
+
+// ---- work lists of the persistent kernels (k_resolve, k_resolve_dr, k_resolve_obj).  One atomic buys `grab` items, taken with stride n_grabs through
+// the list: same-address atomics are serialised by the L2 (~0.2 ms per 100 k), and the stride keeps the consecutive items of one hot raster
+// workgroup on different wavefronts.  Granularity: ~4 grabs per resident wavefront, <= GRAB_MAX items.
+__device__ inline int work_n_grabs(const int n_items) {
+  const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
+  return (n_items + grab - 1) / grab;
+}
+// A wavefront's first grab is its own index (round 4: the launch holds exactly the resident workgroups; 5 000 wavefronts starting on one cursor atomic
+// waited 30 - 60 us each, profiles/r04_wave_spans.txt); this is every later one, from the list's cursor slot (g: the previous grab, kept by lanes > 0).
+__device__ inline int work_next_grab(const RenderParams& R, const int cursor, int g, const int lane) {
+  if (lane == 0) g = (int)gridDim.x * (RB / 64) + atomicAdd(R.work + cursor, 1);
+  return __builtin_amdgcn_readfirstlane(g);
 }
 
 // ---- object masks (k_obj_setup: bit o = object o's screen box meets the block) of the chunk's envs for one wavefront block.  One vector
@@ -1612,7 +1665,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
     for (int r = 0; r < RB / 64; ++r) { nb += s_nb[r]; no += s_no[r]; }
     if (nb > 0) {                                    // k_resolve: ITEM_B batches of plane-edge entries per item
       const int ni = (nb + ITEM_B - 1) / ITEM_B;
-      const int pos = atomicAdd(R.work, ni);
+      const int pos = atomicAdd(R.work + DT_WORK_ITEMS, ni);
       for (int i = 0; i < ni; ++i) R.items[pos + i] = (uint32_t)blockIdx.x * ITEMS_PER_WG + (uint32_t)i;
     }
     if (OBJ && no > 0) push_obj_items(R, (uint32_t)blockIdx.x);
@@ -1678,7 +1731,6 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
   samptab[pix] = sp;
 }
 
-__device__ inline float med3f(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
 
 // ---- resolve_region_q: exact path of k_raster_q (shared camera, no mesh objects) ------------------------------------
 // Called by every wavefront of k_raster_q at the end of its env loop on ITS OWN queue region (the entries it appended):
@@ -1792,6 +1844,7 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
   const char* qtb = reinterpret_cast<const char*>(s_qt);
   const uint32_t tex_min = 32u;                        // block offsets from here on are textured tiles
 
+  // (k_raster_q's table layout, any power-of-two tile size: not v3_sample_owner's.)
   // Table entry (block byte offset, record-offset mask) of the tile that OWNS padded quad coordinates (X, Z): tile
   // boundaries sit at k*S + 0.5 (the GL_LINEAR half-texel shift folded into the coordinates), so ownership is decided
   // on (X - 0.5, Z - 0.5) -- unlike the record lookup, which goes by whole cells.  (ox, oz): the tile's origin.
@@ -1818,7 +1871,7 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
   auto phase1 = [&](auto utag, const int r0) __attribute__((always_inline)) -> int {
     constexpr int U = decltype(utag)::value;
     int n_list = 0;                                  // wave-uniform
-    bool have[U], interior[U], tagged[U], skip[U];
+    bool have[U], interior[U], skip[U];
     int pix[U], el[U], env[U];
     PixTab pt[U];
     float Xu[U], Zu[U];
@@ -1829,12 +1882,9 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
       const int qoff = r0 + u * 64 + lane;
       // the entries were written by this wavefront (workgroup) a moment ago: bypass the (possibly stale) L1 line
       const uint32_t ent = have[u] ? (uint32_t)__builtin_nontemporal_load(w_queue + qoff) : 0u;
-      el[u] = (int)((ent >> 8) & 63u);
-      // QE_ALWAYS_EDGE: the pixel can never be a one-ray pixel (horizon band, near / far limits): it goes to the list without
-      // the interior test -- and without its loads when the whole batch is such (these entries come in runs)
-      tagged[u] = (ent & QE_ALWAYS_EDGE) != 0u;
-      skip[u] = !__ballot(have[u] && !tagged[u]);    // wave-uniform
-      const int lp = (int)(ent & 255u);
+      el[u] = qe_envpos(ent);
+      skip[u] = !__ballot(have[u]);                  // wave-uniform: a batch past the region's fill
+      const int lp = qe_pixel(ent);
       pix[u] = (wave_y0 + lp / WAVE_W) * R.W + tile_x0 + lp % WAVE_W;
     }
     float4 qa[U];
@@ -1867,7 +1917,7 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
       const float ux = Xu[u] - ox, uz = Zu[u] - oz;        // in [0, S) inside the owner tile
       const float d = fminf(fminf(ux, Sf - ux), fminf(uz, Sf - uz));
       const bool in_range = Xu[u] - 0.5f >= lo && Xu[u] - 0.5f <= Xhi && Zu[u] - 0.5f >= lo && Zu[u] - 0.5f <= Zhi;
-      interior[u] = have[u] && !tagged[u] && in_range && te_c[u].x >= tex_min && pt[u].lit > 0.f && (pt[u].mi & 0xFFFFu) < 0xFFF0u && d > mrg * R.q_per_m;
+      interior[u] = have[u] && in_range && te_c[u].x >= tex_min && pt[u].lit > 0.f && (pt[u].mi & 0xFFFFu) < 0xFFF0u && d > mrg * R.q_per_m;
     }
     uint4 qc[U];
 #pragma unroll
@@ -1944,10 +1994,9 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
         }
         const float a_ = fminf(fmaxf((gwx + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
         const float b_ = fminf(fmaxf((gwz + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
-        const float n0 = c->gndl[0] + a_ * (c->gndl[1] - c->gndl[0]), n1 = c->gndl[2] + a_ * (c->gndl[3] - c->gndl[2]);
-        const float ndl = n0 + b_ * (n1 - n0);
+        const float ndl = ground_corner_ndl(a_, b_, c->gndl[0], c->gndl[1], c->gndl[2], c->gndl[3]);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] += (float)n_gnd * (c->gnd[k] * fminf(c->base[k] + c->dif[k] * ndl, 1.f));
+        for (int k = 0; k < 3; ++k) acc[k] += (float)n_gnd * ground_lit(c->gnd[k], c->base[k], c->dif[k], ndl);
       }
       uint32_t todo = 0u;
 #pragma unroll
@@ -2371,29 +2420,16 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
   const int wave = tid >> 6, lane = tid & 63;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(R.tile_recs);
-    for (int i = tid; i < R.n_tile_recs * (int)(sizeof(TileLds) / 4); i += RB) s_mem[i] = src[i];
-  }
+  fill_tile_recs(R, s_mem, tid);
   __syncthreads();
   uint32_t* s_wave = s_mem + R.n_tile_recs * (sizeof(TileLds) / 4);
   EnvCam* w_cams = reinterpret_cast<EnvCam*>(s_wave) + wave * ENVS_PER_BLOCK;                    // wavefront-local
-  const int n_items = R.work[0];                     // written by the raster launch
-  // One atomic buys `grab` items, taken with stride n_grabs through the list: same-address atomics are
-  // serialised by the L2 (~0.2 ms per 100 k of them), and the stride keeps the consecutive items of one hot
-  // raster workgroup on different wavefronts.  Granularity: ~4 grabs per resident wavefront, <= GRAB_MAX items.
-  const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
-  const int n_grabs = (n_items + grab - 1) / grab;
-  // Round 4: the first grab of a wavefront is its own index (the launch holds exactly the resident workgroups, resident_blocks()):
-  // 5 000 wavefronts starting on one cursor atomic spent 30 - 60 us each waiting for it (profiles/r04_wave_spans.txt).
-  const int n_waves = (int)gridDim.x * (RB / 64);
+  const int n_items = R.work[DT_WORK_ITEMS];         // written by the raster launch
+  const int n_grabs = work_n_grabs(n_items);
   bool first_grab = true;
   while (true) {
     int g = wave * (int)gridDim.x + (int)blockIdx.x;
-    if (!first_grab) {
-      if (lane == 0) g = n_waves + atomicAdd(R.work + 1, 1);
-      g = __builtin_amdgcn_readfirstlane(g);
-    }
+    if (!first_grab) g = work_next_grab(R, DT_WORK_CURSOR, g, lane);
     first_grab = false;
     if (g >= n_grabs) break;
     for (int it = g; it < n_items; it += n_grabs) {  // wave-uniform
@@ -2428,7 +2464,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
         const int wave_y0 = tile_y0 + reg * (WAVE_PIX / WAVE_W);
         const bool have = q0 + lane < n;
         const uint32_t ent = have ? w_queue[q0 + lane] : 0u;
-        const int el = have ? (int)(ent >> 8) : -1, lp = ent & 255;
+        const int el = have ? (int)(ent >> 8) : -1, lp = qe_pixel(ent);
         const int pix = (wave_y0 + lp / WAVE_W) * R.W + tile_x0 + lp % WAVE_W;      // entries only exist for in-image pixels
         const float4 l = reinterpret_cast<const float4*>(R.lut)[pix];
         if (have) {
@@ -2437,6 +2473,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
           const EnvCam c = w_cams[el];
           const MapU m = map_u(R.maps[c.map_id]);
           const uint32_t v = shade_msaa<false>(c, m, R, s_tiles, l.x, l.y, nullptr, wb, tb);
+          // three byte stores, here and in k_resolve_obj: another memory pattern than store_rgb (the quad-record exact paths'), kept as tuned
           uint8_t* dst = R.frames + ((size_t)(e0 + el) * npix + pix) * 3;
           dst[0] = (uint8_t)v; dst[1] = (uint8_t)(v >> 8); dst[2] = (uint8_t)(v >> 16);
         }
@@ -2445,7 +2482,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
   }
 }
 
-// Exact path of the pixels inside mesh-object screen boxes (and, after the generic raster, of every queued pixel).
+// Exact path of the pixels inside mesh-object screen boxes (the entries every raster appends from the far end of its queue regions).
 // Work unit = (raster tile, env): the entries one env left in the four wavefront regions of a raster workgroup are taken
 // together, up to NB 64-entry batches at a time, so that the env's triangles are streamed, culled and staged ONCE for
 // the 128 x 8 pixels of the tile instead of once per 128 x 2 block (the round-1 kernel: one pass per
@@ -2459,35 +2496,27 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RES_WAVES
 #endif
 template <int NB>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES, DT_RO_WAVES))) void k_resolve_obj(RenderParams R, const EnvCam* __restrict__ cams, const uint16_t* __restrict__ queue,
-                                                    const int back, const EnvQ* __restrict__ envq) {
+                                                    const EnvQ* __restrict__ envq) {
   extern __shared__ uint32_t s_mem[];
   TileLds* s_tiles = reinterpret_cast<TileLds*>(s_mem);
   const int tid = threadIdx.x;
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
   const int wave = tid >> 6, lane = tid & 63;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(R.tile_recs);
-    for (int i = tid; i < R.n_tile_recs * (int)(sizeof(TileLds) / 4); i += RB) s_mem[i] = src[i];
-  }
+  fill_tile_recs(R, s_mem, tid);
   __syncthreads();
   uint32_t* s_wave = s_mem + R.n_tile_recs * (sizeof(TileLds) / 4);
   static_assert(RES_ENVS == 1, "a work item is ONE (raster tile, env) unit: everything about it is wave-uniform");
   TriCov* w_tris = reinterpret_cast<TriCov*>(s_wave) + wave * TRI_CAP;                             // wavefront-local
   uint32_t* w_scr = reinterpret_cast<uint32_t*>(reinterpret_cast<TriCov*>(s_wave) + (RB / 64) * TRI_CAP) + wave * (RO_SCR_BYTES / 4);   // z-buffer scratch of the pair schedule
-  const int n_front = R.work[2], n_items = n_front + R.work[6];   // written by the raster launch (push_obj_items): heavy items first
+  const int n_front = R.work[DT_WORK_OBJ_FRONT], n_items = n_front + R.work[DT_WORK_OBJ_BACK];   // written by the raster launch (push_obj_items): heavy items first
   const size_t items_cap = obj_items_cap(R);
   auto item_at = [&](int i) -> uint32_t { return R.items2[i < n_front ? (size_t)i : items_cap - 1 - (size_t)(i - n_front)]; };
-  const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
-  const int n_grabs = (n_items + grab - 1) / grab;
-  const int n_waves = (int)gridDim.x * (RB / 64);     // first grab = the wavefront's own index, as in k_resolve
+  const int n_grabs = work_n_grabs(n_items);
   bool first_grab = true;
   while (true) {
     int g = wave * (int)gridDim.x + (int)blockIdx.x;
-    if (!first_grab) {
-      if (lane == 0) g = n_waves + atomicAdd(R.work + 3, 1);
-      g = __builtin_amdgcn_readfirstlane(g);
-    }
+    if (!first_grab) g = work_next_grab(R, DT_WORK_OBJ_CURSOR, g, lane);
     first_grab = false;
     if (g >= n_grabs) break;
     // The item loop is software-pipelined: everything a unit needs before it can touch its entries -- the id of the item after next, and for
@@ -2553,10 +2582,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
             const int r = (idx >= t1) + (idx >= t2) + (idx >= t3);
             const int li = idx - (r == 0 ? 0 : r == 1 ? t1 : r == 2 ? t2 : t3) + (r == 0 ? s_[0] : r == 1 ? s_[1] : r == 2 ? s_[2] : s_[3]);
             const uint16_t* w_queue = queue + ((size_t)rwg * 4 + r) * QREGION;
-            // back: the entries were appended from the far end of the region (k_raster_q<OBJ>: object-box pixels)
-            const uint32_t ent = have[j] ? w_queue[back ? QREGION - 1 - li : li] : 0u;
-            pedge[j] = (ent & QE_PLANE_EDGE) != 0u || !back;
-            const int lp = ent & 255;
+            const uint32_t ent = have[j] ? w_queue[QREGION - 1 - li] : 0u;   // appended from the far end of the region
+            pedge[j] = qe_plane_edge(ent);
+            const int lp = qe_pixel(ent);
             pix[j] = (tile_y0 + r * (WAVE_PIX / WAVE_W) + lp / WAVE_W) * R.W + tile_x0 + lp % WAVE_W;   // entries only exist for in-image pixels
             if (!have[j]) pix[j] = 0;
             const float4 l = reinterpret_cast<const float4*>(R.lut)[pix[j]];
@@ -2994,7 +3022,7 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   if (obj) {
     const size_t lds4 = lds + (size_t)(RB / 64) * TRI_CAP * sizeof(TriCov) + (size_t)(RB / 64) * RO_SCR_BYTES;
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_obj<DT_RES_NB>, lds4)));
-    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s, R, x.cams, R.queue, 1, has_pos ? x.envq : (const EnvQ*)nullptr);
+    hipLaunchKernelGGL(k_resolve_obj<DT_RES_NB>, rgrid, dim3(RB), lds4, s, R, x.cams, R.queue, has_pos ? x.envq : (const EnvQ*)nullptr);
   }
 }
 

@@ -1,7 +1,7 @@
 // render_v3.inc -- k_raster_v3: the quad-record one-ray path of k_raster_q on an instruction diet (included by render.hip
 // inside its anonymous namespace; shares EnvCam / EnvFast / EnvQ / PixTab / SampTab and the queue protocol with k_raster_q).
-// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"); the queue
-// appends, push_obj, the transpose and the hand-over epilogue are this kernel's own copies.
+// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"), and so are resolve_region_v3's
+// entry decode, sample ownership, ground-quad rules and store_rgb ("... by the exact paths"); the queue appends, push_obj, the transpose and the hand-over epilogue are this kernel's own copies.
 //
 // Replaces the same reference code as k_raster_q: simulator.py:1853-1884 (tile quads, GL_LINEAR / GL_REPEAT),
 // simulator.py:1806-1812 (ground quad), graphics.py:172-251 (4x MSAA resolve), distortion.py:85-125 (remap, folded in).
@@ -100,8 +100,7 @@ __device__ inline void resolve_region_v3(const RenderParams& R, const EnvCam* __
       const bool have = l0 + lane < n_list;
       // the entries were written by this wavefront a moment ago: bypass the (possibly stale) L1 line
       const uint32_t ent = have ? (uint32_t)__builtin_nontemporal_load(w_queue + r0 + l0 + lane) : 0u;
-      const int lp = (int)(ent & 255u);
-      const int el = (int)((ent >> 8) & 63u);
+      const int lp = qe_pixel(ent), el = qe_envpos(ent);
       const int pix = have ? (by0 + lp / DT_V3_WW) * R.W + bx0 + lp % DT_V3_WW : 0;
       const SampTab sp = samptab[pix];
       PixTab pt;                                       // the PixTab's hit and lit factor, from the SampTab (one table, two 16-byte loads)
@@ -135,17 +134,11 @@ __device__ inline void resolve_region_v3(const RenderParams& R, const EnvCam* __
         const float slr = pt.lr + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hr >> 16 : hr)));
         const float slf = pt.lf + __half2float(__ushort_as_half((unsigned short)((s & 1) ? hf >> 16 : hf)));
         const float Xs = fmaf(slf, B, fmaf(slr, A, Cx)), Zs = fmaf(slf, -A, fmaf(slr, B, Cz));
-        // the tile that OWNS the sample (ownership on (X - 0.5, Z - 0.5), clamped into the padded grid)
-        const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
-        const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
-        const bool s_in = (Xc == Xo) & (Zc == Zo);
-        const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
-        const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
-        const uint32_t tb = tp[0], sel = tp[128];
+        uint32_t tb, sel;
+        const bool s_in = v3_sample_owner(Xs, Zs, lo, Xhi, Zhi, qtb, tab, tb, sel);
         const bool is_tile = have & (((sp.flags >> s) & 1u) != 0u) & s_in & (tb != 0u);
-        // ground-quad hit of the sample: camera + kg * (tile-plane hit - camera), inside +-50 m
-        const float Xg = fmaf(kg, Xs - Cx, Cx), Zg = fmaf(kg, Zs - Cz, Cz);
-        const bool is_gnd = have & !is_tile & (((sp.flags >> (4 + s)) & 1u) != 0u) & (fabsf(Xg - goff) <= ghalf) & (fabsf(Zg - goff) <= ghalf);
+        const float Xg = ground_quad_at(kg, Xs, Cx), Zg = ground_quad_at(kg, Zs, Cz);
+        const bool is_gnd = have & !is_tile & (((sp.flags >> (4 + s)) & 1u) != 0u) & ground_quad_in(Xg, goff, ghalf) & ground_quad_in(Zg, goff, ghalf);
         n_gnd += is_gnd; n_sky += !(is_tile | is_gnd);
         if (is_gnd) { gX = Xg; gZ = Zg; }
         // one record per DISTINCT tile among the pixel's samples (round 4: the path is texture-unit heavy, its gathers fully divergent;
@@ -168,12 +161,11 @@ __device__ inline void resolve_region_v3(const RenderParams& R, const EnvCam* __
         const float hs = 0.5f / ghalf;
         const float a_ = fminf(fmaxf(fmaf(gX - goff, hs, 0.5f), 0.f), 1.f), b_ = fminf(fmaxf(fmaf(gZ - goff, hs, 0.5f), 0.f), 1.f);
         const float4 q3 = c4[3], q4 = c4[4], q5 = c4[5], q6 = c4[6], q7 = c4[7];
-        const float n0 = q6.y + a_ * (q6.z - q6.y), n1 = q6.w + a_ * (q7.x - q6.w);
-        const float ndl = n0 + b_ * (n1 - n0);
+        const float ndl = ground_corner_ndl(a_, b_, q6.y, q6.z, q6.w, q7.x);
         const float ng = (float)n_gnd;
-        acc[0] += ng * (q3.x * fminf(q3.w + q4.z * ndl, 1.f));
-        acc[1] += ng * (q3.y * fminf(q4.x + q4.w * ndl, 1.f));
-        acc[2] += ng * (q3.z * fminf(q4.y + q5.x * ndl, 1.f));
+        acc[0] += ng * ground_lit(q3.x, q3.w, q4.z, ndl);
+        acc[1] += ng * ground_lit(q3.y, q4.x, q4.w, ndl);
+        acc[2] += ng * ground_lit(q3.z, q4.y, q5.x, ndl);
       }
       const float o[3] = {0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2]};
       if (have) store_rgb(R.frames, npix, e, pix, pack_rgb(o));
@@ -426,12 +418,11 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
       const float wxg = fmaf(c.kg, wx - c.Cx, c.Cx), wzg = fmaf(c.kg, wz - c.Cz, c.Cz);
       const float a = fminf(fmaxf((wxg + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
       const float b = fminf(fmaxf((wzg + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
-      const float n0 = c.gndl[0] + a * (c.gndl[1] - c.gndl[0]), n1 = c.gndl[2] + a * (c.gndl[3] - c.gndl[2]);
-      const float ndl = n0 + b * (n1 - n0);
+      const float ndl = ground_corner_ndl(a, b, c.gndl[0], c.gndl[1], c.gndl[2], c.gndl[3]);
       uint32_t rgb = 0;
-      rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[0] * fminf(c.base[0] + c.dif[0] * ndl, 1.f), 0, rgb);
-      rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[1] * fminf(c.base[1] + c.dif[1] * ndl, 1.f), 1, rgb);
-      rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[2] * fminf(c.base[2] + c.dif[2] * ndl, 1.f), 2, rgb);
+      rgb = __builtin_amdgcn_cvt_pk_u8_f32(ground_lit(c.gnd[0], c.base[0], c.dif[0], ndl), 0, rgb);
+      rgb = __builtin_amdgcn_cvt_pk_u8_f32(ground_lit(c.gnd[1], c.base[1], c.dif[1], ndl), 1, rgb);
+      rgb = __builtin_amdgcn_cvt_pk_u8_f32(ground_lit(c.gnd[2], c.base[2], c.dif[2], ndl), 2, rgb);
       return rgb;
     };
     // plane-edge pixels -> the front of the wavefront's queue region.  The lane sets are SCALAR masks (they come from
@@ -444,7 +435,7 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
         if (!mk) continue;                             // wave-uniform
         if (__builtin_amdgcn_inverse_ballot_w64(mk)) {
           const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-          w_queue[qn + rank] = (uint16_t)(etag | (uint32_t)V3_PIX(k, lane));   // (no QE_ALWAYS_EDGE: resolve_region_v3 runs no interior test)
+          w_queue[qn + rank] = (uint16_t)(etag | (uint32_t)V3_PIX(k, lane));
         }
         qn += __popcll(mk);
       }

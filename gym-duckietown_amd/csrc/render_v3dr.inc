@@ -1,7 +1,7 @@
 // render_v3dr.inc -- k_raster_v3dr: domain randomisation (per-env camera, light, colours) on the quad records of
 // k_raster_v3 (included by render.hip inside its anonymous namespace, after render_v3.inc).
-// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"); the queue
-// appends, push_obj, the transpose and the hand-over epilogue are this kernel's own copies.
+// The workgroup map, the LDS tile table fill, the object masks and spxy are render.hip's ("scaffolding shared by the rasters"), and so are k_resolve_dr's
+// grabs, entry decode, sample ownership, ground-quad rules and store_rgb ("... by the exact paths"); the queue appends, push_obj, the transpose, the hand-over epilogue and k_resolve_dr's item / batch lookup are this file's own copies.
 //
 // Reference: simulator.py:565-614 (the per-reset camera / light / colour perturbations), :1761-1803 (projection and
 // model-view per env), :1853-1884 (tile quads, GL_LINEAR / GL_REPEAT), graphics.py:172-251 (4x MSAA).
@@ -352,9 +352,8 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
           const bool gfast = __builtin_amdgcn_inverse_ballot_w64(gm) & clear & inq;
           const float hs = 0.5f / gh;
           const float a_ = fminf(fmaxf(fmaf(Xg, hs, 0.5f), 0.f), 1.f), b_ = fminf(fmaxf(fmaf(Zg, hs, 0.5f), 0.f), 1.f);
-          const float n0 = c.gndl[0] + a_ * (c.gndl[1] - c.gndl[0]), n1 = c.gndl[2] + a_ * (c.gndl[3] - c.gndl[2]);
-          const float ndl = n0 + b_ * (n1 - n0);
-          uint32_t rgb = 0u;
+          const float ndl = ground_corner_ndl(a_, b_, c.gndl[0], c.gndl[1], c.gndl[2], c.gndl[3]);
+          uint32_t rgb = 0u;                         // (ground_lit, written out: the call reordered scalar moves of the masked instantiation)
           rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[0] * fminf(c.base[0] + c.dif[0] * ndl, 1.f), 0, rgb);
           rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[1] * fminf(c.base[1] + c.dif[1] * ndl, 1.f), 1, rgb);
           rgb = __builtin_amdgcn_cvt_pk_u8_f32(c.gnd[2] * fminf(c.base[2] + c.dif[2] * ndl, 1.f), 2, rgb);
@@ -401,7 +400,7 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
     for (int r = 0; r < RB / 64; ++r) { nb += s_nb[r]; no |= s_no[r]; nh |= s_nh[r]; }
     if (nb > 0) {
       const int ni = (nb + ITEM_B - 1) / ITEM_B;
-      const int pos = atomicAdd(R.work, ni);
+      const int pos = atomicAdd(R.work + DT_WORK_ITEMS, ni);
       for (int i = 0; i < ni; ++i) R.items[pos + i] = (uint32_t)rwg * ITEMS_PER_WG + (uint32_t)i;
     }
     if (OBJ && no) push_obj_items(R, (uint32_t)rwg, no, nh);
@@ -441,17 +440,12 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
   const float lo = 0.5f * 256.f;
   const float goff = (float)DT_QRING * 256.f + 0.5f;   // world 0 in padded quad coordinates
   const float sxn = 2.f / (float)R.W, syn = 2.f / (float)R.H;
-  const int n_items = R.work[0];                     // written by the raster launch
-  const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
-  const int n_grabs = (n_items + grab - 1) / grab;
-  const int n_waves = (int)gridDim.x * (RB / 64);
+  const int n_items = R.work[DT_WORK_ITEMS];         // written by the raster launch
+  const int n_grabs = work_n_grabs(n_items);
   bool first_grab = true;
   while (true) {
-    int g = wave * (int)gridDim.x + (int)blockIdx.x;   // the first grab of a wavefront is its own index (the launch is the resident workgroups)
-    if (!first_grab) {
-      if (lane == 0) g = n_waves + atomicAdd(R.work + 1, 1);
-      g = __builtin_amdgcn_readfirstlane(g);
-    }
+    int g = wave * (int)gridDim.x + (int)blockIdx.x;
+    if (!first_grab) g = work_next_grab(R, DT_WORK_CURSOR, g, lane);
     first_grab = false;
     if (g >= n_grabs) break;
     for (int it = g; it < n_items; it += n_grabs) {  // wave-uniform
@@ -474,7 +468,7 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
         const int wave_y0 = tile_y0 + reg * (WAVE_PIX / WAVE_W);
         const bool have = q0 + lane < n;
         const uint32_t ent = have ? w_queue[q0 + lane] : 0u;
-        const int el = (int)((ent >> 8) & 63u), lp = (int)(ent & 255u);
+        const int el = qe_envpos(ent), lp = qe_pixel(ent);
         const int pix = (wave_y0 + lp / WAVE_W) * R.W + tile_x0 + lp % WAVE_W;      // entries only exist for in-image pixels
         const float4 l = lut[pix];
         const float nx = l.x, ny = l.y;
@@ -509,17 +503,11 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
           const float inv = down ? frcp(den) : 0.f;
           const float t = Cy * inv, tg = kg * t;
           const float Xs = fmaf(inv, fmaf(nxs, hx0, fmaf(nys, hx1, hx2)), Cx), Zs = fmaf(inv, fmaf(nxs, hz0, fmaf(nys, hz1, hz2)), Cz);
-          // the tile that OWNS the sample (ownership on (X - 0.5, Z - 0.5), clamped into the padded grid)
-          const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
-          const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
-          const bool s_in = (Xc == Xo) & (Zc == Zo);
-          const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
-          const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
-          const uint32_t tb = tp[0], sel = tp[128];
+          uint32_t tb, sel;
+          const bool s_in = v3_sample_owner(Xs, Zs, lo, Xhi, Zhi, qtb, tab, tb, sel);
           const bool is_tile = have & down & (t >= NEAR_Z) & (t <= FAR_Z) & s_in & (tb != 0u);
-          // ground-quad hit of the sample: camera + kg * (tile-plane hit - camera), inside +-50 m
-          const float Xg = fmaf(kg, Xs - Cx, Cx), Zg = fmaf(kg, Zs - Cz, Cz);
-          const bool is_gnd = have & !is_tile & down & (tg >= NEAR_Z) & (tg <= FAR_Z) & (fabsf(Xg - goff) <= ghalf) & (fabsf(Zg - goff) <= ghalf);
+          const float Xg = ground_quad_at(kg, Xs, Cx), Zg = ground_quad_at(kg, Zs, Cz);
+          const bool is_gnd = have & !is_tile & down & (tg >= NEAR_Z) & (tg <= FAR_Z) & ground_quad_in(Xg, goff, ghalf) & ground_quad_in(Zg, goff, ghalf);
           n_gnd += is_gnd; n_sky += !(is_tile | is_gnd);
           if (is_gnd) { gX = Xg; gZ = Zg; }
           raddr[s] = is_tile ? (tb | q8_rec256(xic, zic, sel)) : 0u;
@@ -563,23 +551,14 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
           const float hs = 0.5f / ghalf;
           const float a_ = fminf(fmaxf(fmaf(gX - goff, hs, 0.5f), 0.f), 1.f), b_ = fminf(fmaxf(fmaf(gZ - goff, hs, 0.5f), 0.f), 1.f);
           const float4 q6 = X[6], q7 = X[7], q8 = X[8], q9 = X[9];   // gnd[3], gndl0 | gndl1..3 | base[3], dif0 | dif1, dif2
-          const float n0 = q6.w + a_ * (q7.x - q6.w), n1 = q7.y + a_ * (q7.z - q7.y);
-          const float ndl = n0 + b_ * (n1 - n0);
+          const float ndl = ground_corner_ndl(a_, b_, q6.w, q7.x, q7.y, q7.z);
           const float ng = (float)n_gnd;
-          acc[0] += ng * (q6.x * fminf(q8.x + q8.w * ndl, 1.f));
-          acc[1] += ng * (q6.y * fminf(q8.y + q9.x * ndl, 1.f));
-          acc[2] += ng * (q6.z * fminf(q8.z + q9.y * ndl, 1.f));
+          acc[0] += ng * ground_lit(q6.x, q8.x, q8.w, ndl);
+          acc[1] += ng * ground_lit(q6.y, q8.y, q9.x, ndl);
+          acc[2] += ng * ground_lit(q6.z, q8.z, q9.y, ndl);
         }
         const float o[3] = {0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2]};
-        if (have) {
-          const uint32_t v = pack_rgb(o);
-          uint8_t* dst = R.frames + ((size_t)e * npix + pix) * 3;
-          const bool odd = (reinterpret_cast<uintptr_t>(dst) & 1u) != 0u;     // two stores: an aligned half + one byte
-          uint8_t* p8 = odd ? dst : dst + 2;
-          uint16_t* p16 = reinterpret_cast<uint16_t*>(odd ? dst + 1 : dst);
-          *p8 = (uint8_t)(odd ? v : v >> 16);
-          *p16 = (uint16_t)(odd ? v >> 8 : v);
-        }
+        if (have) store_rgb(R.frames, npix, e, pix, pack_rgb(o));
       }
     }
   }
