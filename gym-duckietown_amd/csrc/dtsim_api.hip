@@ -843,6 +843,18 @@ int dtsim_copy_rows(dtsim_t* h, void* dst, const void* src, size_t row_bytes, co
   return DTSIM_OK;
 }
 
+int dtsim_obs_push(dtsim_t* h, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, int flags, const uint8_t* first, const uint8_t* mask) {
+  if (!h || !stack || !obs) return fail(DTSIM_E_INVALID, "dtsim_obs_push: null argument");
+  if (depth < 1 || depth > DTSIM_OBS_MAX_DEPTH) return fail(DTSIM_E_INVALID, "dtsim_obs_push: depth %d outside 1 .. %d", depth, DTSIM_OBS_MAX_DEPTH);
+  if (out_h <= 0 || out_w <= 0) return fail(DTSIM_E_INVALID, "dtsim_obs_push: output size %dx%d", out_w, out_h);
+  if (!(flags & DTSIM_OBS_CHW)) return fail(DTSIM_E_INVALID, "dtsim_obs_push: stacks are CHW (DTSIM_OBS_CHW)");
+  if (flags & ~(DTSIM_OBS_CHW | DTSIM_OBS_F32 | DTSIM_OBS_GRAY)) return fail(DTSIM_E_INVALID, "dtsim_obs_push: unknown flags 0x%x", flags);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_obs_push(h->stream, h->N, stack, obs, depth, out_h, out_w, (flags & DTSIM_OBS_F32) != 0, (flags & DTSIM_OBS_GRAY) != 0, first, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
 int dtsim_query(dtsim_t* h, int n, const int32_t* env_idx, const double* poses, double safety_factor,
                 dtsim_probe* out) {
   if (!h || n <= 0 || !env_idx || !poses || !out) return fail(DTSIM_E_INVALID, "bad argument");

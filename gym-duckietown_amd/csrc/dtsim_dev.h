@@ -175,3 +175,7 @@ void dt_fill_pack_remap(int W, int H, int n_cal, float* rx, float* ry, const int
 void dt_launch_observe(hipStream_t s, const ObservePlan& plan, const ObserveParams& P, const uint8_t* mask = nullptr);
 // row e of src -> row e of dst (row_bytes each) for every e < N with mask[e] != 0 (device pointers; dtsim_copy_rows)
 void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);
+// the observation history (dtsim_obs_push): obs ([N][3][out_h][out_w] uint8) -> the newest slot of stack ([N][depth][3 or 1][out_h][out_w], uint8 or
+// float32), the older slots move one down; first / mask: device, [N] bytes, or null (no env starts anew / every env)
+void dt_launch_obs_push(hipStream_t s, int N, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, bool f32, bool gray,
+                        const uint8_t* first, const uint8_t* mask);

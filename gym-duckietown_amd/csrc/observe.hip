@@ -423,6 +423,72 @@ __global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ dst, co
   }
 }
 
+// ---- observation history (dtsim_obs_push): stack[e] = [depth][C][oh * ow] slots of T, oldest first; obs[e] = [3][oh * ow] uint8 ----
+// ObsBytes<n>: n consecutive bytes as one access (1, 4 or 16 bytes: byte, dword, four dwords).
+template <int NB> struct ObsBytes;
+template <> struct ObsBytes<1> { using type = uint8_t; };
+template <> struct ObsBytes<4> { using type = uint32_t; };
+template <> struct ObsBytes<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
+
+// Pillow's convert("L") (ImagingConvert rgb2l: L24 with the rounding half), on the resized uint8 values
+__device__ inline uint32_t gray_l(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16; }
+
+// One env's push, in place.  Item i of a slot = its elements [VP i, VP i + VP) (VP = 1, or 16 bytes' worth); a thread loads item i of slots
+// 1 .. depth - 1 (all loads first), then stores them one slot down and the converted observation into the last slot -- or the observation into
+// every slot when the env starts anew.  It touches item i only, in every slot: no two threads meet.  `row` may alias itself across slots
+// (not __restrict__); obs does not overlap it.
+template <typename T, bool GRAY, int VP>
+__device__ inline void obs_push_items(T* row, const uint8_t* __restrict__ obs_e, size_t slot, size_t plane, int depth, bool anew, size_t i0, size_t stride) {
+  using A = typename ObsBytes<VP * (int)sizeof(T)>::type;     // VP elements of a slot
+  using L = typename ObsBytes<VP>::type;                      // their VP bytes of one plane of obs
+  const size_t items = slot / VP;
+  for (size_t i = i0; i < items; i += stride) {
+    union { L l; uint8_t b[VP]; } in[GRAY ? 3 : 1];
+    in[0].l = *reinterpret_cast<const L*>(obs_e + i * VP);
+    if (GRAY) {
+      in[1].l = *reinterpret_cast<const L*>(obs_e + plane + i * VP);
+      in[2 % (GRAY ? 3 : 1)].l = *reinterpret_cast<const L*>(obs_e + 2 * plane + i * VP);
+    }
+    union { A a; T t[VP]; } nv;
+#pragma unroll
+    for (int q = 0; q < VP; ++q) {
+      const uint32_t v = GRAY ? gray_l(in[0].b[q], in[1 % (GRAY ? 3 : 1)].b[q], in[2 % (GRAY ? 3 : 1)].b[q]) : in[0].b[q];
+      if (sizeof(T) == 4) nv.t[q] = (T)((float)v / 255.0f);   // NormalizeWrapper, as k_observe*
+      else nv.t[q] = (T)v;
+    }
+    A* s0 = reinterpret_cast<A*>(row) + i;
+    if (anew) {
+      for (int k = 0; k < depth; ++k) s0[(size_t)k * items] = nv.a;
+      continue;
+    }
+    A keep[DTSIM_OBS_MAX_DEPTH - 1];
+#pragma unroll
+    for (int k = 0; k < DTSIM_OBS_MAX_DEPTH - 1; ++k)
+      if (k < depth - 1) keep[k] = s0[(size_t)(k + 1) * items];
+#pragma unroll
+    for (int k = 0; k < DTSIM_OBS_MAX_DEPTH - 1; ++k)
+      if (k < depth - 1) s0[(size_t)k * items] = keep[k];
+    s0[(size_t)(depth - 1) * items] = nv.a;
+  }
+}
+
+// Grid: N x blocks_per_env workgroups, an env's workgroups stride over its items.  vec: 16-byte slot accesses (the launcher checked the bases
+// and the slot size), else element by element.  Workgroups of envs with mask[e] == 0 leave at once (mask null: every env); first[e] != 0
+// (first null: none) replicates the observation into every slot.
+template <typename T, bool GRAY>
+__global__ __launch_bounds__(256) void k_obs_push(T* stack, const uint8_t* __restrict__ obs, size_t plane, int depth, int blocks_per_env,
+                                                  const uint8_t* __restrict__ first, const uint8_t* __restrict__ mask, int vec) {
+  const int e = blockIdx.x / blocks_per_env;
+  if (mask && !mask[e]) return;
+  const bool anew = first && first[e];
+  const size_t slot = (GRAY ? 1 : 3) * plane;
+  T* row = stack + (size_t)e * depth * slot;
+  const uint8_t* obs_e = obs + (size_t)e * 3 * plane;
+  const size_t i0 = (size_t)(blockIdx.x % blocks_per_env) * 256 + threadIdx.x, stride = (size_t)blocks_per_env * 256;
+  if (vec) obs_push_items<T, GRAY, 16 / (int)sizeof(T)>(row, obs_e, slot, plane, depth, anew, i0, stride);
+  else obs_push_items<T, GRAY, 1>(row, obs_e, slot, plane, depth, anew, i0, stride);
+}
+
 }  // namespace
 
 void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask) {
@@ -431,6 +497,26 @@ void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_
   const int vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | row_bytes) & 15) == 0;
   hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((size_t)N * per_row)), dim3(256), 0, s, static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src),
                      row_bytes, per_row, mask, vec);
+}
+
+void dt_launch_obs_push(hipStream_t s, int N, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, bool f32, bool gray,
+                        const uint8_t* first, const uint8_t* mask) {
+  const size_t plane = (size_t)out_h * out_w, slot = (gray ? 1 : 3) * plane, esz = f32 ? 4 : 1;
+  // 16-byte slot accesses with the matching 4 (float32) or 16 (uint8) bytes per plane of obs: every slot (and, in grey, every plane of obs)
+  // then starts on such a boundary
+  const int vec = (reinterpret_cast<uintptr_t>(stack) & 15) == 0 && (slot * esz & 15) == 0 && (reinterpret_cast<uintptr_t>(obs) & (16 / esz - 1)) == 0;
+  const size_t items = vec ? slot * esz / 16 : slot;
+  const int per_env = (int)std::min<size_t>((items + 255) / 256, 16);    // (as dt_launch_copy_rows: the grid stays small when few envs are selected)
+  const dim3 grid((unsigned)((size_t)N * per_env)), block(256);
+  if (f32) {
+    float* st = static_cast<float*>(stack);
+    if (gray) hipLaunchKernelGGL((k_obs_push<float, true>), grid, block, 0, s, st, obs, plane, depth, per_env, first, mask, vec);
+    else hipLaunchKernelGGL((k_obs_push<float, false>), grid, block, 0, s, st, obs, plane, depth, per_env, first, mask, vec);
+  } else {
+    uint8_t* st = static_cast<uint8_t*>(stack);
+    if (gray) hipLaunchKernelGGL((k_obs_push<uint8_t, true>), grid, block, 0, s, st, obs, plane, depth, per_env, first, mask, vec);
+    else hipLaunchKernelGGL((k_obs_push<uint8_t, false>), grid, block, 0, s, st, obs, plane, depth, per_env, first, mask, vec);
+  }
 }
 
 void dt_launch_observe(hipStream_t s, const ObservePlan& plan, const ObserveParams& P, const uint8_t* mask) {

@@ -723,6 +723,36 @@ class BatchedSimulator:
         _ffi.check(self._lib, self._lib.dtsim_copy_rows(self._h, C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(row), C.c_void_p(mp)))
         return dst
 
+    def push_observation(self, stack, obs, first=None, mask=None, grayscale: bool = False):
+        """The observation history on the device (dtsim_obs_push, include/dtsim.h): push `obs` (uint8 [N, 3, h, w], what
+        observe(chw=True) returns) into `stack` ([N, depth, C, h, w], uint8 or float32 = / 255, C = 1 with grayscale -- Pillow's convert("L") --
+        else 3; slot 0 is the oldest), in place and stream-ordered.  For every env selected by `mask` (as render's; None = all): with
+        first[e] set all `depth` slots become the new observation, else the slots move one down and the last takes it; the other envs' rows
+        keep every byte.  `first`: a mask like `mask`, or None = no env starts anew.  Both tensors are contiguous CUDA tensors on the handle's
+        device and must not overlap; anything else raises ValueError before a launch.  Returns `stack`."""
+        import torch
+        fp = None if first is None else self._mask_ptr(first)
+        mp = None if mask is None else self._mask_ptr(mask)
+        dev = torch.device("cuda", self.device_index)
+        for name, t in (("stack", stack), ("obs", obs)):
+            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"push_observation: {name} must be a contiguous CUDA tensor on {dev}")
+        if obs.dtype != torch.uint8 or obs.dim() != 4 or obs.shape[0] != self.num_envs or obs.shape[1] != 3 or obs[0].numel() == 0:
+            raise ValueError(f"push_observation: obs must be uint8 of shape ({self.num_envs}, 3, h, w), got {obs.dtype} {tuple(obs.shape)}")
+        h, w = int(obs.shape[2]), int(obs.shape[3])
+        c = 1 if grayscale else 3
+        if stack.dtype not in (torch.uint8, torch.float32) or stack.dim() != 5 or (stack.shape[0], *stack.shape[2:]) != (self.num_envs, c, h, w) \
+                or not 1 <= stack.shape[1] <= _ffi.OBS_MAX_DEPTH:
+            raise ValueError(f"push_observation: stack must be uint8 / float32 of shape ({self.num_envs}, 1 .. {_ffi.OBS_MAX_DEPTH}, {c}, {h}, {w}), "
+                             f"got {stack.dtype} {tuple(stack.shape)}")
+        s0, o0 = stack.data_ptr(), obs.data_ptr()
+        if s0 < o0 + obs.numel() and o0 < s0 + stack.numel() * stack.element_size():
+            raise ValueError("push_observation: stack and obs overlap")
+        flags = _ffi.OBS_CHW | (_ffi.OBS_F32 if stack.dtype == torch.float32 else 0) | (_ffi.OBS_GRAY if grayscale else 0)
+        _ffi.check(self._lib, self._lib.dtsim_obs_push(self._h, C.c_void_p(s0), C.c_void_p(o0), int(stack.shape[1]), h, w, flags,
+                                                       None if fp is None else C.c_void_p(fp), None if mp is None else C.c_void_p(mp)))
+        return stack
+
     def frames_host(self) -> np.ndarray:
         """Synchronous copy of the frame batch to the host (tests / N=1 facade)."""
         import torch

@@ -19,6 +19,15 @@ whole batch BEFORE the reset -- the frames the reference's step() returns --, ke
 its rows where `info["final_obs_mask"]` (= done) is set hold the final observations, the other rows are unspecified.
 Always: `info["truncated"]` = done with done_code DTSIM_DONE_MAX_STEPS (the time limit: bootstrap on V(final obs)),
 `info["terminated"]` = the other finished envs (invalid pose).
+
+Observation history (`frame_stack=K`, 1 .. 16, and / or `grayscale=True`; needs `obs_shape` and `chw=True`): `obs` is `[N, K * C, h, w]`, the
+last K observations of every env, oldest first and channel-concatenated -- C = 3, or 1 in grey (Pillow's convert("L") of the resized frame);
+float32 with `normalize=True`, uint8 without.  It is a view of one persistent `[N, K, C, h, w]` tensor the env keeps on the device
+(`dtsim_obs_push`: one in-place kernel per step): as with the plain observations, the returned tensor is the env's own buffer and the next
+step rewrites it -- clone what has to outlive the step.  The first observation of an episode fills all K slots (gym's FrameStack), so no frame of
+the previous episode leaks into the next one's stack.  With `final_obs=True`, `info["final_obs"]` (same shape) holds for a finished env its
+history ENDING WITH its final frame, and the returned `obs` of that env is its new episode's first frame, K times.
+`frame_stack=1, grayscale=False` (the default) runs the plain path, call for call.
 """
 from __future__ import annotations
 
@@ -33,7 +42,16 @@ from .batched import BatchedSimulator
 class DuckietownVecEnv:
     def __init__(self, map_name="small_loop", num_envs: int = 1024, obs_shape: Optional[Tuple[int, int]] = (120, 160),
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
-                 seed: Optional[int] = 0, final_obs: bool = False, **sim_kwargs):
+                 seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False, **sim_kwargs):
+        # (the argument errors come before a device or the simulator is touched)
+        if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
+            raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
+        self.frame_stack, self.grayscale = int(frame_stack), bool(grayscale)
+        self._stacked = self.frame_stack > 1 or self.grayscale
+        if self._stacked and obs_shape is None:
+            raise ValueError("frame_stack > 1 / grayscale need obs_shape (the raw camera frames are not stacked)")
+        if self._stacked and not chw:
+            raise ValueError("frame_stack > 1 / grayscale need chw=True (there are no HWC stacks)")
         import torch
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -53,6 +71,12 @@ class DuckietownVecEnv:
         self._steps = torch.as_tensor(sim.field_device(_ffi.FIELD_STEP_COUNT), device=self.device)
         self._frames = torch.as_tensor(sim.frames_device(), device=self.device)
         self.action_shape = (num_envs, 2)
+        if self._stacked:
+            h, w = int(obs_shape[0]), int(obs_shape[1])
+            self._stack = torch.zeros((num_envs, self.frame_stack, 1 if self.grayscale else 3, h, w),
+                                      dtype=torch.float32 if normalize else torch.uint8, device=self.device)
+            self._all = torch.ones(num_envs, dtype=torch.uint8, device=self.device)     # `first` of reset(): every env starts anew
+            self._stack_shape = (num_envs, self._stack.shape[1] * self._stack.shape[2], h, w)
 
     # ------------------------------------------------------------------------------------------------
     def _observe(self, mask=None):
@@ -61,6 +85,13 @@ class DuckietownVecEnv:
             return self._frames                                     # [N, H, W, 3] uint8, the raw camera frames
         return self.torch.as_tensor(self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=self.chw,
                                                      normalize=self.normalize, mask=mask), device=self.device)
+
+    def _push(self, first=None, mask=None):
+        """render -> observe (uint8 CHW, the simulator's own buffer) -> push into the history; `mask`: only those envs, all three."""
+        self.sim.render(mask=mask)
+        o = self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=True, normalize=False, mask=mask)
+        self.sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
+        return self._stack.view(self._stack_shape)
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -72,7 +103,7 @@ class DuckietownVecEnv:
         self._enter()
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
-            obs = self._observe()
+            obs = self._push(first=self._all) if self._stacked else self._observe()
         self._leave()
         return obs
 
@@ -92,7 +123,18 @@ class DuckietownVecEnv:
             # (dtsim_step sets done_code nonzero exactly when done: one comparison each)
             info = {"done_code": code, "episode_steps": self._steps.clone(), "truncated": code == _ffi.DONE_MAX_STEPS,
                     "terminated": code == _ffi.DONE_INVALID_POSE}
-            if self.final_obs:
+            if self._stacked and self.final_obs:
+                self._push()                                        # every env's history now ends with what the reference's step() returns
+                if self._final is None:
+                    self._final = t.empty_like(self._stack)
+                self.sim.copy_rows(self._final, self._stack, done)
+                self.sim.reset_done()
+                obs = self._push(first=done, mask=done)             # the restarted envs: their first frame in every slot
+                info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape), done
+            elif self._stacked:
+                self.sim.reset_done()
+                obs = self._push(first=done)
+            elif self.final_obs:
                 obs = self._observe()                               # what the reference's step() returns, every env
                 if self._final is None:
                     self._final = t.empty_like(obs)

@@ -484,6 +484,24 @@ int dtsim_observe_cubic_masked(dtsim_t* h, void* out, int out_h, int out_w, int 
  * num_envs bytes); other rows of dst are left untouched.  16-byte accesses when both pointers and row_bytes are 16-byte aligned.  For the
  * final observations (or frames) of the envs that finished a step, before dtsim_reset_done.  Asynchronous, stream-ordered. */
 int dtsim_copy_rows(dtsim_t* h, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);
+/* The observation history of every env, kept by the caller on the device (gym's FrameStack, for the whole batch): push this step's
+ * observation into a stack of the last `depth` ones.
+ *   obs:   DEVICE pointer to [num_envs][3][out_h][out_w] uint8 -- what dtsim_observe* writes with DTSIM_OBS_CHW and without DTSIM_OBS_F32.
+ *   stack: DEVICE pointer to [num_envs][depth][C][out_h][out_w], C = 3, or 1 with DTSIM_OBS_GRAY; uint8, or float32 with DTSIM_OBS_F32.
+ *          Slot 0 is the oldest.  The caller owns it and the handle keeps no history: the call is stateless.  obs and stack must not overlap.
+ *   first, mask: DEVICE pointers to num_envs bytes, or NULL (no env starts anew / every env is selected).
+ * For every selected env e: with first[e] != 0 all `depth` slots become the new observation (an episode's first observation is replicated),
+ * else slot k takes slot k + 1 for k < depth - 1; the last slot takes the new observation.  The rows of unselected envs keep every byte,
+ * whatever `first` says.  The new observation is converted on the way: DTSIM_OBS_GRAY is Pillow's convert("L") of the resized uint8 pixel,
+ * (19595 R + 38470 G + 7471 B + 0x8000) >> 16; DTSIM_OBS_F32 stores (float)v / 255.0f as dtsim_observe does, so the newest slot of a colour
+ * float32 stack equals dtsim_observe(CHW | F32) of the same frames bit for bit.  depth == 1 is the pure conversion.
+ * flags must hold DTSIM_OBS_CHW (there are no HWC stacks) and nothing but DTSIM_OBS_CHW | DTSIM_OBS_F32 | DTSIM_OBS_GRAY; a null handle, stack
+ * or obs, depth outside 1 .. DTSIM_OBS_MAX_DEPTH, a non-positive size or such flags return DTSIM_E_INVALID before anything touches a device.
+ * In place, 16-byte accesses when the bases and the slot's size in bytes are 16-byte aligned.  Asynchronous, stream-ordered (as dtsim_copy_rows). */
+enum { DTSIM_OBS_GRAY = 4 };          /* dtsim_obs_push only */
+#define DTSIM_OBS_MAX_DEPTH 16
+int dtsim_obs_push(dtsim_t* h, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, int flags,
+                   const uint8_t* first, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

@@ -1,5 +1,9 @@
 """Throughput of the learner-facing loop (DuckietownVecEnv): step + device reset + render + 160x120 CHW float obs.
-FINAL_OBS=1: with final observations (full pass before the reset, row copy, masked render / observe of the restarted envs after it)."""
+FINAL_OBS=1: with final observations (full pass before the reset, row copy, masked render / observe of the restarted envs after it).
+STACK=K, GRAY=1, NORMALIZE=0: the observation history kept by the env (frame_stack / grayscale / normalize of DuckietownVecEnv).
+EMULATE=1: the plain env plus the history a user keeps in torch (torch.roll of [N, K * 3, h, w], masked refill of the restarted envs).
+VARIANTS=a,b,...: several variants in ONE process, each warmed up, then timed in alternating order (ROUNDS rounds of K steps each, the
+median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -7,16 +11,68 @@ import torch
 from dtsim import DuckietownVecEnv
 N = int(os.environ.get("N", "4096"))
 FINAL = os.environ.get("FINAL_OBS", "0") == "1"
-env = DuckietownVecEnv("small_loop", N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL)
-obs = env.reset()
+STACK = int(os.environ.get("STACK", "1"))
+GRAY = os.environ.get("GRAY", "0") == "1"
+NORMALIZE = os.environ.get("NORMALIZE", "1") == "1"
+EMULATE = os.environ.get("EMULATE", "0") == "1"
+VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
+K = int(os.environ.get("K", "30"))
+ROUNDS = int(os.environ.get("ROUNDS", "1"))
 a = torch.rand((N, 2), device="cuda") * 2 - 1
-for _ in range(5):
-    env.step(a)
-torch.cuda.synchronize()
-K = 30
-t = time.perf_counter()
-for _ in range(K):
-    obs, r, d, info = env.step(a)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t) / K
-print(f"VecEnv N={N}{' final_obs' if FINAL else ''}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with [N,3,120,160] float32 observations")
+
+
+class Variant:
+    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False):
+        self.name, self.emulate, self.depth = name, emulate, stack
+        kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
+        self.env = DuckietownVecEnv("small_loop", N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
+                                    normalize=normalize, **kw)
+        obs = self.env.reset()
+        self.hist = obs.repeat(1, stack, 1, 1) if emulate else None
+        self.shape, self.dtype = tuple(self.hist.shape if emulate else obs.shape), obs.dtype
+        self.ms = []
+
+    def step(self):
+        obs, r, d, info = self.env.step(a)
+        if self.emulate:                                   # what a learner does without frame_stack: roll, append, refill the restarted envs
+            h = torch.roll(self.hist, -3, dims=1)
+            h[:, -3:] = obs
+            self.hist = torch.where(d[:, None, None, None], obs.repeat(1, self.depth, 1, 1), h)
+
+    def run(self, steps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(steps):
+            self.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / steps
+
+
+def make(name):
+    d = STACK if STACK > 1 else 4
+    return {"plain": lambda: Variant("plain"),
+            "stack": lambda: Variant(f"K={d} colour float32", d),
+            "stack_u8": lambda: Variant(f"K={d} colour uint8", d, normalize=False),
+            "gray": lambda: Variant(f"K={d} grey float32", d, gray=True),
+            "gray_u8": lambda: Variant(f"K={d} grey uint8", d, gray=True, normalize=False),
+            "emulate": lambda: Variant(f"K={d} colour float32, torch emulation", d, emulate=True)}[name]()
+
+
+if VARIANTS:
+    vs = [make(v) for v in VARIANTS]
+    for v in vs:
+        v.run(5)
+    for r in range(ROUNDS):
+        for v in (vs if r % 2 == 0 else vs[::-1]):
+            v.ms.append(v.run(K) * 1e3)
+    for v in vs:
+        s = sorted(v.ms)
+        print(f"VecEnv N={N}{' final_obs' if FINAL else ''} {v.name:40s} {list(v.shape)} {str(v.dtype)[6:]}: median {s[len(s) // 2]:.3f} ms per step "
+              f"(min {s[0]:.3f}, max {s[-1]:.3f}; {ROUNDS} rounds of {K} steps)")
+else:
+    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE)
+    v.run(5)
+    dt = v.run(K)
+    what = (f" emulated K={STACK}" if EMULATE else "") + (f" frame_stack={STACK}" if STACK > 1 and not EMULATE else "") + (" grey" if GRAY else "")
+    print(f"VecEnv N={N}{' final_obs' if FINAL else ''}{what}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with "
+          f"{list(v.shape)} {str(v.dtype)[6:]} observations")
