@@ -855,6 +855,27 @@ int dtsim_obs_push(dtsim_t* h, void* stack, const uint8_t* obs, int depth, int o
   return DTSIM_OK;
 }
 
+int dtsim_blend_frames(dtsim_t* h, void* out, const void* const* frames, const uint32_t* weights, int n, int flags, const uint8_t* mask) {
+  if (!h || !out || !frames || !weights) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: null argument");
+  if (n < 1 || n > DTSIM_BLEND_MAX) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: n = %d outside 1 .. %d", n, DTSIM_BLEND_MAX);
+  if (flags & ~DTSIM_OBS_F32) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: unknown flags 0x%x", flags);
+  BlendArgs B{};
+  B.n = n;
+  uint32_t D = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!frames[i]) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: frames[%d] is null", i);
+    if (weights[i] > 255u) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: weights[%d] = %u above 255", i, weights[i]);
+    B.f[i] = static_cast<const uint8_t*>(frames[i]); B.w[i] = weights[i];
+    D += weights[i];
+  }
+  if (D < 1 || D > 256) return fail(DTSIM_E_INVALID, "dtsim_blend_frames: the weights sum to %u, outside 1 .. 256", D);
+  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_blend_frames(h->stream, h->N, out, B, (size_t)h->cfg.cam_height * h->cfg.cam_width * 3, (flags & DTSIM_OBS_F32) != 0, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
 int dtsim_query(dtsim_t* h, int n, const int32_t* env_idx, const double* poses, double safety_factor,
                 dtsim_probe* out) {
   if (!h || n <= 0 || !env_idx || !poses || !out) return fail(DTSIM_E_INVALID, "bad argument");

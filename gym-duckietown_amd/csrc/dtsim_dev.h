@@ -179,3 +179,11 @@ void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_
 // float32), the older slots move one down; first / mask: device, [N] bytes, or null (no env starts anew / every env)
 void dt_launch_obs_push(hipStream_t s, int N, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, bool f32, bool gray,
                         const uint8_t* first, const uint8_t* mask);
+// the weighted frame blend (dtsim_blend_frames): out[j] = sum of w[i] * f[i][j] over D = sum of w[i], rounded half up (uint8) or as one float
+// division (f32), for the frame_bytes bytes of every env (mask: device, [N] bytes, or null = every env).  Passed to the kernel by value.
+struct BlendArgs {
+  const uint8_t* f[DTSIM_BLEND_MAX];   // device pointers, oldest first; entries past n are unused
+  uint32_t w[DTSIM_BLEND_MAX];         // 0 .. 255 each, 1 <= D <= 256 (the launcher's caller checked)
+  int n;
+};
+void dt_launch_blend_frames(hipStream_t s, int N, void* out, const BlendArgs& B, size_t frame_bytes, bool f32, const uint8_t* mask);

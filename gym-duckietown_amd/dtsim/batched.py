@@ -753,6 +753,42 @@ class BatchedSimulator:
                                                        None if fp is None else C.c_void_p(fp), None if mp is None else C.c_void_p(mp)))
         return stack
 
+    def blend_frames(self, out, frames, weights, mask=None):
+        """The weighted sum of several frame batches on the device (dtsim_blend_frames, include/dtsim.h; the blend of the reference's
+        MotionBlurWrapper): `frames` is a sequence of 1 .. 8 uint8 [N, H, W, 3] tensors (the handle's camera size), oldest first, `weights` as
+        many integers in 0 .. 255 with the sum D in 1 .. 256.  `out` of the same shape takes sum(w[i] * frames[i]) / D: uint8, rounded half up
+        (it may be one of `frames`), or float32, one IEEE division (it must not overlap a frame).  `mask` (as render's): only the rows of the
+        selected envs are written.  All tensors are contiguous CUDA tensors on the handle's device; anything else raises ValueError before a
+        launch.  Stream-ordered; returns `out`."""
+        import torch
+        mp = None if mask is None else self._mask_ptr(mask)
+        dev = torch.device("cuda", self.device_index)
+        shape = (self.num_envs, self.camera_height, self.camera_width, 3)
+        frames = list(frames) if isinstance(frames, (list, tuple)) else None
+        if not frames or len(frames) > _ffi.BLEND_MAX:
+            raise ValueError(f"blend_frames: frames must be a sequence of 1 .. {_ffi.BLEND_MAX} tensors")
+        for name, t in [("out", out)] + [(f"frames[{i}]", f) for i, f in enumerate(frames)]:
+            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"blend_frames: {name} must be a contiguous CUDA tensor on {dev} of shape {shape}")
+            if t.dtype != torch.uint8 and (t is not out or t.dtype != torch.float32):
+                raise ValueError(f"blend_frames: {name} must be uint8{' or float32' if t is out else ''}, got {t.dtype}")
+        try:
+            w = [int(v) for v in weights]
+            exact = all(v == x for v, x in zip(w, weights))
+        except (TypeError, ValueError):
+            w, exact = [], False
+        if not exact or len(w) != len(frames) or any(not 0 <= v <= 255 for v in w) or not 1 <= sum(w) <= 256:
+            raise ValueError(f"blend_frames: weights must be {len(frames)} integers in 0 .. 255 with a sum in 1 .. 256, got {weights!r}")
+        o0, o1 = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
+        for f in frames:                                    # (the blend is element-wise at equal index: a uint8 out may BE a frame, nothing else)
+            if f.data_ptr() < o1 and o0 < f.data_ptr() + f.numel() and (out.dtype == torch.float32 or f.data_ptr() != o0):
+                raise ValueError("blend_frames: out overlaps a frame (a uint8 out may be one of the frames, a float32 out none)")
+        fp = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
+        wp = (C.c_uint32 * len(w))(*w)
+        _ffi.check(self._lib, self._lib.dtsim_blend_frames(self._h, C.c_void_p(out.data_ptr()), fp, wp, len(w),
+                                                           _ffi.OBS_F32 if out.dtype == torch.float32 else 0, None if mp is None else C.c_void_p(mp)))
+        return out
+
     def frames_host(self) -> np.ndarray:
         """Synchronous copy of the frame batch to the host (tests / N=1 facade)."""
         import torch

@@ -28,10 +28,27 @@ step rewrites it -- clone what has to outlive the step.  The first observation o
 the previous episode leaks into the next one's stack.  With `final_obs=True`, `info["final_obs"]` (same shape) holds for a finished env its
 history ENDING WITH its final frame, and the returned `obs` of that env is its new episode's first frame, K times.
 `frame_stack=1, grayscale=False` (the default) runs the plain path, call for call.
+
+Motion blur (`motion_blur=True`, or a window of 2 .. 8 integer weights, oldest frame first; needs `action_mode="wheels"` and `frame_skip=1`):
+the reference's MotionBlurWrapper (learning/utils/wrappers.py:8-36), its only model of a camera's exposure, taken literally.  The wrapper cuts
+the env's delta_time in three, and per step clips the action to [-1, 1], does `render_obs(); update_physics(a)` three times, renders a fourth
+frame and returns np.average of the four with the weights 0.8 / 0.15 / 0.04 / 0.01, the OLDEST frame weighted 0.8.  Here a window of L weights
+(True = (80, 15, 4, 1)) builds the simulator with `frame_rate * (L - 1)` -- a frame_rate whose 0.15 s actuation delay exceeds DTSIM_MAX_DELAY
+steps fails with BatchedSimulator's error --, and a step is L - 1 times `dtsim_step_ex(DTSIM_STEP_ONE_UPDATE)` (update_physics: the wheel pair
+as given, which is why the env clips it) + a render into the next slot of a ring of L raw frame batches, then one `dtsim_blend_frames` of the
+ring in age order: sum(w[i] * frame[i]) / sum(w) in exact integers.  The window's first frame is the last frame of the previous window (one
+state renders to the same bytes every time), so a step costs L - 1 renders, not L.  Reward and done are those of the state after the last
+sub-update; an env that leaves the road mid-window keeps being updated, as in the reference; `step_count` advances once per sub-update, so
+`info["episode_steps"]` and `max_steps` count sub-updates.  `reset()` returns the plain frame (the reference's reset() is render_obs()), and
+so is the first observation of a restarted env; `info["final_obs"]` is the blurred final observation, at no extra render.  `final_obs`,
+`frame_stack`, `grayscale`, `obs_shape=None`, `normalize` and `chw` compose as without the blur.  Deviation: the reference returns the float64
+average (its learners' imresize then rescales by the array's min and max); here the blend is rounded half up to uint8 and takes the PIL-exact
+resize of every other frame -- `BatchedSimulator.blend_frames(out=float32)` gives the unrounded value.  Memory: L extra frame batches (15 GB for
+the default window at N = 4096, 640 x 480).  `motion_blur=False` (the default) runs the paths above, call for call.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -42,7 +59,8 @@ from .batched import BatchedSimulator
 class DuckietownVecEnv:
     def __init__(self, map_name="small_loop", num_envs: int = 1024, obs_shape: Optional[Tuple[int, int]] = (120, 160),
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
-                 seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False, **sim_kwargs):
+                 seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False,
+                 motion_blur: Union[bool, Sequence[int]] = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -52,6 +70,14 @@ class DuckietownVecEnv:
             raise ValueError("frame_stack > 1 / grayscale need obs_shape (the raw camera frames are not stacked)")
         if self._stacked and not chw:
             raise ValueError("frame_stack > 1 / grayscale need chw=True (there are no HWC stacks)")
+        self._blur = self._blur_window(motion_blur)                 # the window's integer weights, oldest frame first, or None
+        if self._blur:
+            if action_mode != "wheels":
+                raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
+            if sim_kwargs.get("frame_skip", 1) != 1:
+                raise ValueError(f"motion_blur needs frame_skip=1 (the window's sub-updates are the step), got {sim_kwargs['frame_skip']!r}")
+            # MotionBlurWrapper: env.delta_time / frame_skip, with one sub-update per frame after the window's first
+            sim_kwargs["frame_rate"] = sim_kwargs.get("frame_rate", 30) * (len(self._blur) - 1)
         import torch
         self.torch = torch
         self.device = torch.device("cuda", device)
@@ -77,18 +103,39 @@ class DuckietownVecEnv:
                                       dtype=torch.float32 if normalize else torch.uint8, device=self.device)
             self._all = torch.ones(num_envs, dtype=torch.uint8, device=self.device)     # `first` of reset(): every env starts anew
             self._stack_shape = (num_envs, self._stack.shape[1] * self._stack.shape[2], h, w)
+        if self._blur:
+            self._ring = [torch.empty_like(self._frames) for _ in self._blur]     # slot _cur holds the frame of the current state
+            self._cur = 0
+
+    @staticmethod
+    def _blur_window(motion_blur):
+        if motion_blur is None or motion_blur is False:
+            return None
+        if motion_blur is True:
+            return (80, 15, 4, 1)                                   # wrappers.py:29, in hundredths
+        try:
+            w = tuple(motion_blur)
+            ok = all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in w)
+        except TypeError:
+            w, ok = (), False
+        if not ok or not 2 <= len(w) <= _ffi.BLEND_MAX or any(not 0 <= v <= 255 for v in w) or not 1 <= sum(w) <= 256:
+            raise ValueError(f"motion_blur must be a bool or 2 .. {_ffi.BLEND_MAX} integer weights in 0 .. 255 with a sum in 1 .. 256 "
+                             f"(oldest frame first), got {motion_blur!r}")
+        return tuple(int(v) for v in w)
 
     # ------------------------------------------------------------------------------------------------
-    def _observe(self, mask=None):
-        self.sim.render(mask=mask)
+    def _observe(self, mask=None, render=True):
+        if render:
+            self.sim.render(mask=mask)
         if self.obs_shape is None:
             return self._frames                                     # [N, H, W, 3] uint8, the raw camera frames
         return self.torch.as_tensor(self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=self.chw,
                                                      normalize=self.normalize, mask=mask), device=self.device)
 
-    def _push(self, first=None, mask=None):
+    def _push(self, first=None, mask=None, render=True):
         """render -> observe (uint8 CHW, the simulator's own buffer) -> push into the history; `mask`: only those envs, all three."""
-        self.sim.render(mask=mask)
+        if render:
+            self.sim.render(mask=mask)
         o = self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=True, normalize=False, mask=mask)
         self.sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
         return self._stack.view(self._stack_shape)
@@ -104,11 +151,59 @@ class DuckietownVecEnv:
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
             obs = self._push(first=self._all) if self._stacked else self._observe()
+            if self._blur:
+                self._ring[0].copy_(self._frames)                   # the next window's first frame
+                self._cur = 0
         self._leave()
         return obs
 
+    def _step_blurred(self, actions):
+        """motion_blur: L - 1 sub-updates, each rendered into the next ring slot; the blend of the L slots into the handle's own frame buffer is
+        the observation of every env (and the final one of the finished envs); the restarted envs then show their first frame, unblurred."""
+        t, sim, L = self.torch, self.sim, len(self._blur)
+        if isinstance(actions, np.ndarray):
+            a = np.clip(np.ascontiguousarray(actions, np.float32).reshape(1, self.num_envs, 2), -1.0, 1.0)
+        else:
+            a = actions.to(device=self.device, dtype=t.float32).clamp(-1.0, 1.0).contiguous()   # (a new tensor, made on our stream)
+        for j in range(1, L):
+            sim.step(a, flags=_ffi.STEP_ONE_UPDATE)
+            sim.bind_frames(self._ring[(self._cur + j) % L].data_ptr())
+            sim.render()
+        reward = self._reward.to(t.float32)
+        done = self._done.to(t.bool)
+        code = self._code.clone()
+        info = {"done_code": code, "episode_steps": self._steps.clone(), "truncated": code == _ffi.DONE_MAX_STEPS,
+                "terminated": code == _ffi.DONE_INVALID_POSE}
+        sim.blend_frames(self._frames, [self._ring[(self._cur + j) % L] for j in range(L)], self._blur)
+        sim.bind_frames(None)
+        obs = self._push(render=False) if self._stacked else self._observe(render=False)
+        if self.final_obs:
+            if self._final is None:
+                self._final = t.empty_like(self._stack if self._stacked else obs)
+            sim.copy_rows(self._final, self._stack if self._stacked else obs, done)
+            info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape) if self._stacked else self._final, done
+        sim.reset_done()
+        self._cur = (self._cur + L - 1) % L                         # the newest slot opens the next window
+        newest = self._ring[self._cur]
+        sim.bind_frames(newest.data_ptr())
+        sim.render(mask=done)
+        if self._stacked:
+            obs = self._push(first=done, mask=done, render=False)
+        elif self.obs_shape is None:
+            sim.copy_rows(self._frames, newest, done)
+        else:
+            obs = self._observe(mask=done, render=False)
+        sim.bind_frames(None)
+        return obs, reward, done, info
+
     def step(self, actions):
         t = self.torch
+        if self._blur:
+            self._enter()
+            with t.cuda.stream(self.stream):
+                out = self._step_blurred(actions)
+            self._leave()
+            return out
         self._enter()
         with t.cuda.stream(self.stream):
             if isinstance(actions, np.ndarray):

@@ -502,6 +502,25 @@ enum { DTSIM_OBS_GRAY = 4 };          /* dtsim_obs_push only */
 #define DTSIM_OBS_MAX_DEPTH 16
 int dtsim_obs_push(dtsim_t* h, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, int flags,
                    const uint8_t* first, const uint8_t* mask);
+/* A weighted sum of several whole frame batches, element by element: the blend of the reference's MotionBlurWrapper
+ * (learning/utils/wrappers.py:8-36: np.average of the four frames of a step's sub-updates, weights 0.8 / 0.15 / 0.04 / 0.01, oldest first) in
+ * exact integer arithmetic -- the weights as integers w[i] with the sum D, here 80, 15, 4, 1 hundredths.
+ *   frames:  HOST array of n DEVICE pointers, each to [num_envs][cam_height][cam_width][3] uint8, oldest first.
+ *   weights: HOST array of n integers, each 0 .. 255, with D = sum of them in 1 .. 256: every S = sum of w[i] * frames[i][j] fits 16 bits.
+ *            Both arrays are read during the call and passed to the kernel by value.
+ *   out:     DEVICE pointer to [num_envs][cam_height][cam_width][3]: uint8 (flags 0), out[j] = (2 S + D) / (2 D) in integer division, i.e. S / D
+ *            rounded half up; or float32 (DTSIM_OBS_F32, the only flag), out[j] = (float)S / (float)D, one IEEE division -- for the reference's
+ *            weights bit for bit np.float32 of what np.average returns.  A uint8 `out` may be any of frames[i] (every input of an element is
+ *            loaded before the element is stored); a float32 `out` must not overlap an input.
+ *   mask:    DEVICE pointer to num_envs bytes, or NULL = every env; as dtsim_copy_rows: the rows of unselected envs keep every byte.
+ * A null handle, out, frames, weights or frames[i], n outside 1 .. DTSIM_BLEND_MAX, a weight above 255, D outside 1 .. 256 or any other flag
+ * return DTSIM_E_INVALID before anything touches a device; a handle without DTSIM_F_RENDER returns DTSIM_E_STATE.  16-byte accesses when every
+ * base and the frame size in bytes are 16-byte aligned.  Asynchronous, stream-ordered.
+ * DuckietownVecEnv(motion_blur=...) renders a step's sub-updates into a ring of frame batches and blends them with this call.
+ * Deviation: the reference hands the float64 average on (its learners' imresize then rescales by the array's min and max); the env rounds the
+ * blend half up to uint8 and resizes it like every other frame.  The float32 output is the unrounded value. */
+#define DTSIM_BLEND_MAX 8
+int dtsim_blend_frames(dtsim_t* h, void* out, const void* const* frames, const uint32_t* weights, int n, int flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

@@ -2,8 +2,12 @@
 FINAL_OBS=1: with final observations (full pass before the reset, row copy, masked render / observe of the restarted envs after it).
 STACK=K, GRAY=1, NORMALIZE=0: the observation history kept by the env (frame_stack / grayscale / normalize of DuckietownVecEnv).
 EMULATE=1: the plain env plus the history a user keeps in torch (torch.roll of [N, K * 3, h, w], masked refill of the restarted envs).
+MOTION_BLUR=1: DuckietownVecEnv(motion_blur=True, action_mode="wheels") -- three sub-updates and renders per step and the blend of four frame
+batches; MOTION_BLUR=rerender: the same with the window's first frame rendered again at every step, as the reference's wrapper does (what
+reusing the previous window's last frame saves).
 VARIANTS=a,b,...: several variants in ONE process, each warmed up, then timed in alternating order (ROUNDS rounds of K steps each, the
-median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4)."""
+median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4) | wheels (the plain env with
+action_mode="wheels", the blur's baseline) | blur | blur_rerender."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -15,6 +19,7 @@ STACK = int(os.environ.get("STACK", "1"))
 GRAY = os.environ.get("GRAY", "0") == "1"
 NORMALIZE = os.environ.get("NORMALIZE", "1") == "1"
 EMULATE = os.environ.get("EMULATE", "0") == "1"
+MOTION_BLUR = os.environ.get("MOTION_BLUR", "0")
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
 K = int(os.environ.get("K", "30"))
 ROUNDS = int(os.environ.get("ROUNDS", "1"))
@@ -22,9 +27,13 @@ a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
-    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False):
-        self.name, self.emulate, self.depth = name, emulate, stack
+    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False):
+        self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
+        if blur != "0":
+            kw.update(motion_blur=True, action_mode="wheels")
+        elif wheels:
+            kw.update(action_mode="wheels")
         self.env = DuckietownVecEnv("small_loop", N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -33,6 +42,11 @@ class Variant:
         self.ms = []
 
     def step(self):
+        if self.rerender:                                  # the literal wrapper's first render_obs() of a step: the same state, the same bytes
+            env = self.env
+            env.sim.bind_frames(env._ring[env._cur].data_ptr())
+            env.sim.render()
+            env.sim.bind_frames(None)
         obs, r, d, info = self.env.step(a)
         if self.emulate:                                   # what a learner does without frame_stack: roll, append, refill the restarted envs
             h = torch.roll(self.hist, -3, dims=1)
@@ -55,7 +69,9 @@ def make(name):
             "stack_u8": lambda: Variant(f"K={d} colour uint8", d, normalize=False),
             "gray": lambda: Variant(f"K={d} grey float32", d, gray=True),
             "gray_u8": lambda: Variant(f"K={d} grey uint8", d, gray=True, normalize=False),
-            "emulate": lambda: Variant(f"K={d} colour float32, torch emulation", d, emulate=True)}[name]()
+            "emulate": lambda: Variant(f"K={d} colour float32, torch emulation", d, emulate=True),
+            "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
+            "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
 
 if VARIANTS:
@@ -70,9 +86,10 @@ if VARIANTS:
         print(f"VecEnv N={N}{' final_obs' if FINAL else ''} {v.name:40s} {list(v.shape)} {str(v.dtype)[6:]}: median {s[len(s) // 2]:.3f} ms per step "
               f"(min {s[0]:.3f}, max {s[-1]:.3f}; {ROUNDS} rounds of {K} steps)")
 else:
-    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE)
+    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE, MOTION_BLUR)
     v.run(5)
     dt = v.run(K)
-    what = (f" emulated K={STACK}" if EMULATE else "") + (f" frame_stack={STACK}" if STACK > 1 and not EMULATE else "") + (" grey" if GRAY else "")
+    what = (f" emulated K={STACK}" if EMULATE else "") + (f" frame_stack={STACK}" if STACK > 1 and not EMULATE else "") + (" grey" if GRAY else "") + \
+        ({"0": "", "1": " motion_blur", "rerender": " motion_blur + first frame rendered again"}[MOTION_BLUR])
     print(f"VecEnv N={N}{' final_obs' if FINAL else ''}{what}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with "
           f"{list(v.shape)} {str(v.dtype)[6:]} observations")
