@@ -308,6 +308,9 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     e = dev_alloc(h->d_lut, 4 * (size_t)cfg->cam_height * cfg->cam_width);
     size_t bytes[DT_SLABS]; dt_render_layout(h->N, cfg->cam_width, cfg->cam_height, 0, bytes);
     for (int i = DT_SLAB_ENV; i <= DT_SLAB_QEND && e == hipSuccess; ++i) e = dev_alloc(h->d_render[i], bytes[i]);
+    // the per-env records start zeroed: a post-pass that is wrongly pointed at an env no pass has written (dtsim_depth_masked with another mask
+    // than the pass's: the caller's error, its result undefined) then reads no object and no map index outside the tables
+    if (e == hipSuccess) e = hipMemset(h->d_render[DT_SLAB_ENV].get(), 0, bytes[DT_SLAB_ENV]);
     RenderParams R{}; render_scratch(h, 0, &R);
     if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(render scratch): %s", hipGetErrorString(e)); }
@@ -392,6 +395,7 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, T.max_tris, bytes);
   for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i)     // the object slabs: only with mesh objects
     if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(dev_alloc(next.d_obj[i], bytes[i]));
+  if (next.d_obj[DT_SLAB_OBJBOX]) HIPCHK(hipMemset(next.d_obj[DT_SLAB_OBJBOX].get(), 0, bytes[DT_SLAB_OBJBOX]));   // no object boxes until a pass writes them (as the records of dtsim_create)
   // worlds must be re-created against the new maps
   HIPCHK(hipMemsetAsync(h->A.map_id, 0xFF, sizeof(int32_t) * (size_t)h->N, h->stream));
   next.M.blobs = next.d_blobs.get();
@@ -721,6 +725,31 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));           // `spheres` is pageable host memory: the copy must have left it
   return DTSIM_OK;
+}
+
+// The shared body of dtsim_depth / dtsim_depth_masked.  masked: the masked form (its device mask must be given).
+static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+  if (!h || !out || (masked && !mask)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
+  if (flags & ~(uint32_t)DTSIM_DEPTH_F16) return fail(DTSIM_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+  const int W = h->cfg.cam_width, H = h->cfg.cam_height;
+  if (oh <= 0 || ow <= 0 || H % oh || W % ow)
+    return fail(DTSIM_E_INVALID, "%s: a %d x %d map of %d x %d frames (the map is point-sampled: each size must divide the camera's)", who, ow, oh, W, H);
+  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
+  if (int rc = check_renderable(h, who)) return rc;
+  if (!h->rendered || !h->leds_ok || h->last_segment)
+    return fail(DTSIM_E_STATE, "%s needs a preceding dtsim_render (colour view) of the current state: it reads that pass's cameras and projected triangles", who);
+  // the masked pass of the quad-record pipelines writes neither the camera (k_cam_setup) nor the triangles (k_obj_setup) of an unselected env
+  if (h->masked && !masked) return fail(DTSIM_E_STATE, "%s after dtsim_render_masked: only dtsim_depth_masked, with the pass's mask", who);
+  if (h->n_cal) return fail(DTSIM_E_STATE, "%s with per-env distortion tables installed (it reads the single table)", who);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags) { return depth_run(h, "dtsim_depth", out, oh, ow, flags, false, nullptr); }
+int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return depth_run(h, "dtsim_depth_masked", out, oh, ow, flags, true, mask);
 }
 
 void* dtsim_frames_devptr(dtsim_t* h) { return h ? h->frames : nullptr; }

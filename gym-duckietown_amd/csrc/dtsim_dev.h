@@ -162,6 +162,10 @@ int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, i
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);
 // the LED spheres of enable_leds (render.hip k_overlay_leds): [count] spheres of env `env` from d_spheres[first..], world space, R = the last render pass's parameters
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env);
+// the depth maps of dtsim_depth (render.hip k_depth): out = [N][oh][ow] float32 (f16: half), output pixel (i, j) = camera pixel
+// (i * (H / oh) + H / oh / 2, j * (W / ow) + W / ow / 2); R = the last render pass's parameters; mask (device, [N] bytes, or null = every
+// env): the rows of the other envs are not written.  The caller checked that oh divides H and ow divides W.
+void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask);
 // camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
 // envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
 void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,

@@ -2783,6 +2783,95 @@ __global__ __launch_bounds__(256) void k_overlay_lines(RenderParams R, const Env
 // emit before the front face would add a second layer), lit per sample instead of per vertex, and all spheres after ALL opaque objects (GL
 // interleaves them with the objects in map order).  Not a hot path: one thread per pixel, the triangle loop only under a sphere's screen box.
 struct LedS { float ex, ey, ez, r, cr, cg, cb, a, bx0, bx1, by0, by1; };     // eye-space centre, radius, colour, alpha, source-pixel box
+
+// The opaque scene's eye depth at the four MSAA samples of ONE source pixel of one env (k_overlay_leds, k_depth): centre (nx, ny) in NDC =
+// (sxp, syp) in pixels, sample q at NDC (nx + ox[q] sxn, ny - oy[q] syn).  The planes by classify() -- the frame's own ownership test: tile
+// present / ground extent / sky --, the meshes by z-buffering the env's projected triangles (boxes / tb: the env's ObjBox and ScreenTri rows that
+// the render pass's k_obj_setup left, n_obj of them; boxes null: no mesh objects) for the lanes inside an object's screen box.  depth[q] = t of
+// the eye-space ray (dx, dy, -1) t; `sky` where the sample sees the clear colour.
+__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
+                                    const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
+                                    const float sky, float depth[4]) {
+  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
+  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
+  float wbest[4] = {0.f, 0.f, 0.f, 0.f};
+  int tbest[4] = {-1, -1, -1, -1};
+  if (boxes) {
+    for (int o = 0; o < n_obj; ++o) {
+      const ObjBox ob = boxes[o];
+      if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
+      for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    // the steps stated here round one way wherever they are inlined: the sample position is an explicit fused multiply-add, the mesh depth one
+    // IEEE division, the minimum exact (PARITY.md 4, "frames of ONE state rendered again"); classify() and test_tri are the frame's own code
+    const Ray rs = make_ray(fmaf(ox[q], sxn, nx), fmaf(-oy[q], syn, ny), c.tx, c.ty, c.sth, c.cth);
+    const Hit h = classify(c, m, tiles, rs);
+    float d = h.cls == CLS_SKY ? sky : h.t;
+    if (tbest[q] >= 0) d = fminf(d, 1.f / wbest[q]);
+    depth[q] = d;
+  }
+}
+
+// ---- k_depth: the depth map of every env's camera frame (dtsim_depth; the quantity: include/dtsim.h) -------------------------------------
+// Output pixel (i, j) of the [oh][ow] map is camera pixel (i sy + sy / 2, j sx + sx / 2), sy = H / oh, sx = W / ow: point-sampled, only those
+// pixels are traced.  A thread owns one output pixel -- its table entry (source-pixel NDC, live flag) is loaded once -- and loops over the
+// DEPTH_ENVS envs of its chunk (grid: pixel blocks x env chunks); the env's camera record, map and object boxes are wave-uniform (read-only
+// __restrict__ pointers at a uniform index: scalar loads), and every store is one coalesced row segment of one env's map.  Per env the depth
+// is scene_depth4 -- the code under the LED spheres, i.e. classify() per sample and the z-buffer of the triangles the pass projected -- and
+// the minimum of the four.
+// One state, one result: the env loop is kept as ONE copy of its body (no unrolling, no peeled iteration), so every env of every chunk, the
+// tail chunk included, runs the same instructions on its record, whatever the compiler fuses inside classify() (which is the frame's own
+// code and stays as it is, so its products are not restated as explicit fused multiply-adds here); the pixel's part (table entry, sample
+// offsets) does not depend on the env.  That the compiler keeps one copy is its choice, not a property of this source: the guarantee rests on
+// tests/test_gpu_depth.py::test_env_positions_and_the_tail_chunk_give_the_same_bytes (envs e, e + 64, e + 128 of one state, a second call, a
+// second render: byte-identical), which fails if a peeled or versioned copy ever rounds differently.
+#define DEPTH_ENVS ENVS_PER_BLOCK
+template <bool F16>
+__global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
+                                               const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
+                                               const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
+                                               void* __restrict__ out, const uint8_t* __restrict__ mask) {
+  const int n_out = oh * ow;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const bool in = pix < n_out;
+  const int sy = H / oh, sx = W / ow;
+  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
+  bool live = false;
+  if (in) {
+    const int i = pix / ow, j = pix - i * ow;
+    const float4 l = lut[(size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2)];
+    live = l.z != 0.f;                                 // 0: the fisheye leaves this pixel without a source (the frame's black border)
+    nx = l.x; ny = l.y;
+    sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;       // centre of the source pixel
+  }
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
+  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+#pragma clang loop unroll(disable)
+  for (int e = e0; e < e1; ++e) {
+    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
+    const EnvCam c = cams[e];
+    // (calling the masked form with another mask than the pass's is the caller's error -- include/dtsim.h -- and its result is undefined: the
+    // record of a skipped env is an older state's, or the zeros the scratch starts with.  The clamp only keeps that error from indexing
+    // outside the map table on a device others share.)
+    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];
+    const MapU m = map_u(rm);
+    float d = 0.f;
+    if (live) {
+      float ds[4];
+      scene_depth4(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
+                   objbox ? rm.n_obj : 0, nx, ny, sxp, syp, sxn, syn, __builtin_inff(), ds);
+      d = fminf(fminf(ds[0], ds[1]), fminf(ds[2], ds[3]));
+    }
+    if (in) {
+      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
+      if (F16) static_cast<__half*>(out)[at] = __float2half_rn(d);
+      else static_cast<float*>(out)[at] = d;
+    }
+  }
+}
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
                                                       const int first, const int count, const int env) {
   __shared__ LedS s_led[64];
@@ -2834,26 +2923,9 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
       if (!(sp.r > 0.f) || sxp < sp.bx0 || sxp > sp.bx1 || syp < sp.by0 || syp > sp.by1) continue;
       if (!have_depth) {                               // the opaque scene's depth at the four samples, once per pixel that any sphere may touch
         have_depth = true;
-        float wbest[4] = {0.f, 0.f, 0.f, 0.f};
-        int tbest[4] = {-1, -1, -1, -1};
-        if (R.stris && R.objbox) {
-          const ObjBox* boxes = R.objbox + (size_t)env * DTSIM_MAX_OBJECTS;
-          const ScreenTri* tb = R.stris + (size_t)env * R.max_tris;
-          const int n_obj = R.maps[c.map_id].n_obj;
-          for (int o = 0; o < n_obj; ++o) {
-            const ObjBox ob = boxes[o];
-            if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
-            for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const Ray rs = make_ray(nx + ox[q] * sxn, ny - oy[q] * syn, c.tx, c.ty, c.sth, c.cth);
-          const Hit h = classify(c, m, tiles, rs);
-          float d = h.cls == CLS_SKY ? 3.0e38f : h.t;
-          if (tbest[q] >= 0) d = fminf(d, 1.f / wbest[q]);
-          depth[q] = d;
-        }
+        const bool obj = R.stris && R.objbox;
+        scene_depth4(c, m, tiles, obj ? R.objbox + (size_t)env * DTSIM_MAX_OBJECTS : nullptr, obj ? R.stris + (size_t)env * R.max_tris : nullptr,
+                     obj ? R.maps[c.map_id].n_obj : 0, nx, ny, sxp, syp, sxn, syn, 3.0e38f, depth);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -2895,6 +2967,17 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env) {
   if (count <= 0) return;
   hipLaunchKernelGGL(k_overlay_leds, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, reinterpret_cast<const EnvCam*>(R.envcam), d_spheres, first, count, env);
+}
+
+void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask) {
+  if (R.N <= 0) return;
+  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
+  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
+#define LAUNCH_DEPTH(F16_) hipLaunchKernelGGL(k_depth<F16_>, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs, \
+                                              reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.max_tris,    \
+                                              R.n_maps, R.N, R.W, R.H, oh, ow, out, mask)
+  if (f16) LAUNCH_DEPTH(true); else LAUNCH_DEPTH(false);
+#undef LAUNCH_DEPTH
 }
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {

@@ -709,6 +709,52 @@ class BatchedSimulator:
             _ffi.check(self._lib, self._lib.dtsim_observe_masked(self._h, C.c_void_p(ptr), h, w, flags, mp, bx, kx, nkx, by, ky, nky))
         return out
 
+    _DEPTH_DTYPES = {"float32": ("<f4", 4), "float16": ("<f2", 2)}
+
+    def depth(self, height=None, width=None, dtype: str = "float32", out=None, mask=None):
+        """The depth map of every env's camera frame, on the device (dtsim_depth, include/dtsim.h): [N, h, w], per pixel the smallest eye depth
+        (distance along the optical axis) of the nearest opaque surface -- tiles, ground, mesh objects -- over the four MSAA samples of the
+        frame's source pixel; +inf where all four see the sky, 0 in the fisheye's black border.  Needs a preceding render() of the current state.
+        Default size: the camera's; a smaller (h, w) must divide it and is the slice full[:, sy // 2::sy, sx // 2::sx] (sy = H // h, sx = W // w),
+        of which only those pixels are traced.  dtype "float32" or "float16".  `out` may be any C-contiguous object with
+        __cuda_array_interface__ of that shape and dtype; `mask` as render()'s (after render(mask=m) pass the same m): only the selected envs'
+        rows are written (the others keep their content; in the simulator's own buffer that is whatever an earlier call left).  A bad size, dtype, out or mask raises ValueError before anything is launched."""
+        import torch
+        if dtype not in self._DEPTH_DTYPES:
+            raise ValueError(f"depth: dtype {dtype!r}: 'float32' or 'float16'")
+        typestr, item = self._DEPTH_DTYPES[dtype]
+        h = self.camera_height if height is None else int(height)
+        w = self.camera_width if width is None else int(width)
+        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
+            raise ValueError(f"depth: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
+                             "(depth is point-sampled, never filtered)")
+        mp = None if mask is None else C.c_void_p(self._mask_ptr(mask))
+        shape = (self.num_envs, h, w)
+        if out is None:
+            key = (h, w, dtype)
+            if getattr(self, "_depth_key", None) != key:
+                # (empty, as observe()'s buffer: a fill would run on torch's stream, unordered against the handle's own, and race with the
+                # kernel's stores; a first call that is masked leaves the other rows uninitialised)
+                self._depth_buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device_index}")
+                self._depth_key = key
+            out = self._depth_buf
+        ai = getattr(out, "__cuda_array_interface__", None)
+        if ai is None:
+            raise ValueError(f"depth: out needs __cuda_array_interface__ (a device array), got {type(out).__name__}")
+        c_strides = tuple(int(np.prod(shape[i + 1:])) * item for i in range(len(shape)))
+        strides = ai.get("strides")
+        if tuple(ai["shape"]) != shape or ai["typestr"] != typestr or not (
+                strides is None or all(s == c for s, c, n in zip(strides, c_strides, shape) if n > 1)):
+            raise ValueError(f"depth: out: need a C-contiguous {typestr} array of shape {shape}, got shape {tuple(ai['shape'])}, "
+                             f"typestr {ai['typestr']!r}, strides {strides}")
+        ptr = C.c_void_p(ai["data"][0])
+        flags = _ffi.DEPTH_F16 if dtype == "float16" else 0
+        if mp is None:
+            _ffi.check(self._lib, self._lib.dtsim_depth(self._h, ptr, h, w, flags))
+        else:
+            _ffi.check(self._lib, self._lib.dtsim_depth_masked(self._h, ptr, h, w, flags, mp))
+        return out
+
     def copy_rows(self, dst, src, mask):
         """dst[e] = src[e] for every env selected by `mask` (as render's), on the device, stream-ordered; the other rows of dst keep their
         content.  dst / src: CUDA tensors on the handle's device, C-contiguous, same shape and dtype, leading dimension N."""

@@ -45,6 +45,16 @@ so is the first observation of a restarted env; `info["final_obs"]` is the blurr
 average (its learners' imresize then rescales by the array's min and max); here the blend is rounded half up to uint8 and takes the PIL-exact
 resize of every other frame -- `BatchedSimulator.blend_frames(out=float32)` gives the unrounded value.  Memory: L extra frame batches (15 GB for
 the default window at N = 4096, 640 x 480).  `motion_blur=False` (the default) runs the paths above, call for call.
+
+Depth (`depth_shape=(h, w)`, each dividing the camera's size; `depth_dtype` "float32" or "float16"): `info["depth"]` is one persistent
+`[N, h, w]` device tensor with the depth map (`dtsim_depth`, include/dtsim.h: smallest eye depth over the four MSAA samples of the frame's
+source pixel, +inf = sky, 0 = the fisheye's black border; point-sampled, never filtered) of the state whose observation `obs` shows -- for an
+env restarted in the step, the first frame of its new episode.  `reset()` keeps returning `obs` alone; the map of the first frames is
+`env.depth`, the same tensor.  With `final_obs=True`, `info["final_depth"]` is a second persistent tensor whose rows where
+`info["final_obs_mask"]` is set hold the depth of the final state (the other rows are unspecified); the order is full render -> observe ->
+depth -> `dtsim_copy_rows` -> `dtsim_reset_done` -> masked render -> masked observe -> `dtsim_depth_masked`.  `frame_stack`, `grayscale` and
+`obs_shape=None` compose (depth is never stacked); `motion_blur` (its observation shows three states) and `camera_rand` (a distortion table
+per env) raise ValueError.  `depth_shape=None` (the default) runs the paths above, call for call.
 """
 from __future__ import annotations
 
@@ -60,7 +70,8 @@ class DuckietownVecEnv:
     def __init__(self, map_name="small_loop", num_envs: int = 1024, obs_shape: Optional[Tuple[int, int]] = (120, 160),
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
                  seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False,
-                 motion_blur: Union[bool, Sequence[int]] = False, **sim_kwargs):
+                 motion_blur: Union[bool, Sequence[int]] = False, depth_shape: Optional[Tuple[int, int]] = None,
+                 depth_dtype: str = "float32", **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -71,6 +82,24 @@ class DuckietownVecEnv:
         if self._stacked and not chw:
             raise ValueError("frame_stack > 1 / grayscale need chw=True (there are no HWC stacks)")
         self._blur = self._blur_window(motion_blur)                 # the window's integer weights, oldest frame first, or None
+        if depth_dtype not in BatchedSimulator._DEPTH_DTYPES:
+            raise ValueError(f"depth_dtype {depth_dtype!r}: 'float32' or 'float16'")
+        self.depth_shape, self.depth_dtype = None, depth_dtype
+        if depth_shape is not None:
+            if self._blur:
+                raise ValueError("depth_shape with motion_blur is not supported (the blurred observation shows the three states of its window: "
+                                 "no single state's depth belongs to it)")
+            if sim_kwargs.get("camera_rand"):
+                raise ValueError("depth_shape with camera_rand is not supported (dtsim_depth reads the single distortion table, camera_rand "
+                                 "installs one per env)")
+            try:
+                dh, dw = (int(v) for v in depth_shape)
+            except (TypeError, ValueError):
+                raise ValueError(f"depth_shape must be (h, w), got {depth_shape!r}") from None
+            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
+            if dh <= 0 or dw <= 0 or H % dh or W % dw:
+                raise ValueError(f"depth_shape {(dh, dw)}: each size must divide the camera's {(H, W)} (depth is point-sampled, never filtered)")
+            self.depth_shape = (dh, dw)
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -90,6 +119,11 @@ class DuckietownVecEnv:
         self.obs_shape, self.chw, self.normalize = obs_shape, chw, normalize
         self.final_obs = bool(final_obs)
         self._final = None                                          # info["final_obs"], allocated at the first step
+        self.depth = self._final_depth = None                       # info["depth"] / info["final_depth"]: persistent [N, h, w] tensors
+        if self.depth_shape is not None:
+            self.depth = torch.zeros((num_envs, *self.depth_shape), dtype=getattr(torch, depth_dtype), device=self.device)
+            if self.final_obs:
+                self._final_depth = torch.zeros_like(self.depth)
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -140,6 +174,16 @@ class DuckietownVecEnv:
         self.sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
         return self._stack.view(self._stack_shape)
 
+    def _depth_pass(self, mask=None):
+        """depth_shape: the depth of the state the last render() showed, into self.depth (`mask`: only those envs' rows)."""
+        if self.depth is not None:
+            self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
+
+    def _keep_final_depth(self, done, info):
+        if self.depth is not None:
+            self.sim.copy_rows(self._final_depth, self.depth, done)
+            info["final_depth"] = self._final_depth
+
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
 
@@ -151,6 +195,7 @@ class DuckietownVecEnv:
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
             obs = self._push(first=self._all) if self._stacked else self._observe()
+            self._depth_pass()
             if self._blur:
                 self._ring[0].copy_(self._frames)                   # the next window's first frame
                 self._cur = 0
@@ -220,26 +265,36 @@ class DuckietownVecEnv:
                     "terminated": code == _ffi.DONE_INVALID_POSE}
             if self._stacked and self.final_obs:
                 self._push()                                        # every env's history now ends with what the reference's step() returns
+                self._depth_pass()
                 if self._final is None:
                     self._final = t.empty_like(self._stack)
                 self.sim.copy_rows(self._final, self._stack, done)
+                self._keep_final_depth(done, info)
                 self.sim.reset_done()
                 obs = self._push(first=done, mask=done)             # the restarted envs: their first frame in every slot
+                self._depth_pass(mask=done)
                 info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape), done
             elif self._stacked:
                 self.sim.reset_done()
                 obs = self._push(first=done)
+                self._depth_pass()
             elif self.final_obs:
                 obs = self._observe()                               # what the reference's step() returns, every env
+                self._depth_pass()
                 if self._final is None:
                     self._final = t.empty_like(obs)
                 self.sim.copy_rows(self._final, obs, done)          # kept for the finished envs
+                self._keep_final_depth(done, info)
                 self.sim.reset_done()
                 obs = self._observe(mask=done)                      # their first frames, only theirs
+                self._depth_pass(mask=done)
                 info["final_obs"], info["final_obs_mask"] = self._final, done
             else:
                 self.sim.reset_done()
                 obs = self._observe()
+                self._depth_pass()
+            if self.depth is not None:
+                info["depth"] = self.depth
         self._leave()
         return obs, reward, done, info
 

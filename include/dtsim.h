@@ -521,6 +521,35 @@ int dtsim_obs_push(dtsim_t* h, void* stack, const uint8_t* obs, int depth, int o
  * blend half up to uint8 and resizes it like every other frame.  The float32 output is the unrounded value. */
 #define DTSIM_BLEND_MAX 8
 int dtsim_blend_frames(dtsim_t* h, void* out, const void* const* frames, const uint32_t* weights, int n, int flags, const uint8_t* mask);
+/* The depth map of every camera frame, on the device: ground-truth geometry beside the observation (no counterpart in the reference, whose
+ * only per-pixel output is the frame).
+ * THE QUANTITY.  For camera pixel (r, c) of env e, depth is the smallest, over the four MSAA samples of the frame's SOURCE pixel, of the eye
+ * depth of the nearest opaque surface: tile plane, ground quad, mesh triangles.
+ *   - The source pixel is (r, c) itself without the fisheye; with it, the pixel the handle's distortion table names for (r, c).
+ *   - Eye depth is the t of the eye-space ray (dx, dy, -1) t: distance along the optical axis, not range.
+ *   - The samples, their offsets and the near / far limits (0.04 / 100) are those of the colour pass; plane ownership (tile present, ground
+ *     extent, sky) is the colour pass's own test, mesh depth that of its z-buffer.
+ *   - A pixel whose four samples all see the clear colour has depth +inf.
+ *   - A pixel the fisheye leaves without a source (the frame's black border) has depth 0.
+ *   - LED spheres and line overlays are not part of it.
+ * The minimum (not a vote or a mean): a thin silhouette that colours a pixel also sets its depth, and it is conservative for obstacle distance.
+ * SIZE.  out: DEVICE pointer to [num_envs][oh][ow], float32, or IEEE half (round to nearest even, inf stays inf) with DTSIM_DEPTH_F16.  The map
+ * is point-sampled, never filtered (depth must not be blended across a silhouette): cam_height % oh == 0 and cam_width % ow == 0, else
+ * DTSIM_E_INVALID; with sy = cam_height / oh and sx = cam_width / ow, out[e][i][j] is the depth of camera pixel (i sy + sy / 2, j sx + sx / 2)
+ * in integer division -- the small map is full[:, sy/2::sy, sx/2::sx], and only those pixels are traced.
+ * STATE.  A post-pass of a render, under the rules of dtsim_draw_leds: it reads the cameras and projected triangles the last pass left, so a
+ * colour dtsim_render / dtsim_render_ex (not the segment view) of the CURRENT state must precede it -- dtsim_step, dtsim_reset,
+ * dtsim_reset_done, dtsim_write, dtsim_set_maps, dtsim_set_assets and dtsim_set_distortion_lut invalidate -- and per-env distortion tables
+ * (dtsim_set_distortion_luts) are refused; all of these DTSIM_E_STATE.  After a full pass both entry points are valid.  After
+ * dtsim_render_masked only dtsim_depth_masked is, and it must be given the mask the pass was given: on the quad-record pipelines both the
+ * camera and the triangle set-up of the pass skip the unselected envs, whose records describe an older state (the generic pipelines write
+ * every env's; the rule does not depend on the pipeline).  The masked call writes the rows of the selected envs only; the other rows keep
+ * every byte.  One state gives the same bytes on every call, for every env index and whatever the other envs hold.
+ * A null handle, out or mask, a non-positive or non-dividing size or an unknown flag return DTSIM_E_INVALID; a failed call launches
+ * nothing and writes nothing.  Asynchronous, stream-ordered. */
+enum { DTSIM_DEPTH_F16 = 1u };
+int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags);
+int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

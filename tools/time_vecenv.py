@@ -5,9 +5,11 @@ EMULATE=1: the plain env plus the history a user keeps in torch (torch.roll of [
 MOTION_BLUR=1: DuckietownVecEnv(motion_blur=True, action_mode="wheels") -- three sub-updates and renders per step and the blend of four frame
 batches; MOTION_BLUR=rerender: the same with the window's first frame rendered again at every step, as the reference's wrapper does (what
 reusing the previous window's last frame saves).
+DEPTH=1: info["depth"] beside the observation (DuckietownVecEnv(depth_shape=(120, 160)): dtsim_depth after every observe); DEPTH=full: the
+camera's own 480 x 640; DEPTH_DTYPE=float16: half maps.  MAP=loop_pedestrians: another map (mesh objects: the depth kernel's triangle loop).
 VARIANTS=a,b,...: several variants in ONE process, each warmed up, then timed in alternating order (ROUNDS rounds of K steps each, the
 median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4) | wheels (the plain env with
-action_mode="wheels", the blur's baseline) | blur | blur_rerender."""
+action_mode="wheels", the blur's baseline) | blur | blur_rerender | depth | depth_f16 | depth_full | depth_full_f16."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -20,6 +22,10 @@ GRAY = os.environ.get("GRAY", "0") == "1"
 NORMALIZE = os.environ.get("NORMALIZE", "1") == "1"
 EMULATE = os.environ.get("EMULATE", "0") == "1"
 MOTION_BLUR = os.environ.get("MOTION_BLUR", "0")
+DEPTH = os.environ.get("DEPTH", "0")
+DEPTH_DTYPE = os.environ.get("DEPTH_DTYPE", "float32")
+MAP = os.environ.get("MAP", "small_loop")
+MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
 K = int(os.environ.get("K", "30"))
 ROUNDS = int(os.environ.get("ROUNDS", "1"))
@@ -27,14 +33,16 @@ a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
-    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False):
+    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32"):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
             kw.update(motion_blur=True, action_mode="wheels")
         elif wheels:
             kw.update(action_mode="wheels")
-        self.env = DuckietownVecEnv("small_loop", N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
+        if depth != "0":
+            kw.update(depth_shape=(480, 640) if depth == "full" else (120, 160), depth_dtype=depth_dtype)
+        self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
         self.hist = obs.repeat(1, stack, 1, 1) if emulate else None
@@ -70,6 +78,9 @@ def make(name):
             "gray": lambda: Variant(f"K={d} grey float32", d, gray=True),
             "gray_u8": lambda: Variant(f"K={d} grey uint8", d, gray=True, normalize=False),
             "emulate": lambda: Variant(f"K={d} colour float32, torch emulation", d, emulate=True),
+            "depth": lambda: Variant("depth 120 x 160 float32", depth="1"), "depth_f16": lambda: Variant("depth 120 x 160 float16", depth="1", depth_dtype="float16"),
+            "depth_full": lambda: Variant("depth 480 x 640 float32", depth="full"),
+            "depth_full_f16": lambda: Variant("depth 480 x 640 float16", depth="full", depth_dtype="float16"),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
@@ -83,13 +94,14 @@ if VARIANTS:
             v.ms.append(v.run(K) * 1e3)
     for v in vs:
         s = sorted(v.ms)
-        print(f"VecEnv N={N}{' final_obs' if FINAL else ''} {v.name:40s} {list(v.shape)} {str(v.dtype)[6:]}: median {s[len(s) // 2]:.3f} ms per step "
+        print(f"VecEnv{MAP_TAG} N={N}{' final_obs' if FINAL else ''} {v.name:40s} {list(v.shape)} {str(v.dtype)[6:]}: median {s[len(s) // 2]:.3f} ms per step "
               f"(min {s[0]:.3f}, max {s[-1]:.3f}; {ROUNDS} rounds of {K} steps)")
 else:
-    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE, MOTION_BLUR)
+    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE, MOTION_BLUR, depth=DEPTH, depth_dtype=DEPTH_DTYPE)
     v.run(5)
     dt = v.run(K)
     what = (f" emulated K={STACK}" if EMULATE else "") + (f" frame_stack={STACK}" if STACK > 1 and not EMULATE else "") + (" grey" if GRAY else "") + \
-        ({"0": "", "1": " motion_blur", "rerender": " motion_blur + first frame rendered again"}[MOTION_BLUR])
-    print(f"VecEnv N={N}{' final_obs' if FINAL else ''}{what}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with "
+        ({"0": "", "1": " motion_blur", "rerender": " motion_blur + first frame rendered again"}[MOTION_BLUR]) + \
+        ("" if DEPTH == "0" else f" depth {list(v.env.depth.shape[1:])} {DEPTH_DTYPE}")
+    print(f"VecEnv{MAP_TAG} N={N}{' final_obs' if FINAL else ''}{what}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with "
           f"{list(v.shape)} {str(v.dtype)[6:]} observations")
