@@ -654,77 +654,68 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   return DTSIM_OK;
 }
 
-int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int n) {
-  if (!h || (n > 0 && !lines)) return fail(DTSIM_E_INVALID, "null argument");
-  if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
-  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
-  if (int rc = check_renderable(h, "dtsim_draw_lines")) return rc;
-  if (!h->have_maps || !h->have_reset || !h->have_lut || !h->rendered) return fail(DTSIM_E_STATE, "dtsim_draw_lines before the first dtsim_render (the pass writes the cameras the lines go through)");
-  if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_lines after dtsim_render_masked: the post-passes need a full dtsim_render");
-  if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_lines with per-env distortion tables installed (the overlays read the single table)");
+// The shared body of dtsim_draw_lines / dtsim_draw_leds: `n` host records of `width` floats, grouped by env_idx (null: all env 0), are
+// uploaded into the handle's buffer `buf` (capacity `cap`, in records; grown to at least min_cap) and drawn onto the frames with one
+// `launch` per env that has records.  prepare(h, &R): the entry point's own state precondition -- false refuses the call, `need` says
+// why -- and the RenderParams of its launches.
+static int overlay_run(dtsim_t* h, const char* who, const float* recs, int width, const int32_t* env_idx, int n, DevPtr<float> dtsim::*buf,
+                       int dtsim::*cap, int min_cap, const char* need, bool (*prepare)(const dtsim*, RenderParams*),
+                       void (*launch)(hipStream_t, const RenderParams&, const float*, int first, int count, int env)) {
+  if (!h || (n > 0 && !recs)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
+  if (n < 0) return fail(DTSIM_E_INVALID, "%s: n = %d", who, n);
+  if (!h->frames) return fail(DTSIM_E_STATE, "%s: handle created without DTSIM_F_RENDER", who);
+  if (int rc = check_renderable(h, who)) return rc;
+  RenderParams R{};
+  if (!prepare(h, &R)) return fail(DTSIM_E_STATE, "%s %s", who, need);
+  if (h->masked) return fail(DTSIM_E_STATE, "%s after dtsim_render_masked: the post-passes need a full dtsim_render", who);
+  if (h->n_cal) return fail(DTSIM_E_STATE, "%s with per-env distortion tables installed (the overlays read the single table)", who);
   if (n == 0) return DTSIM_OK;
   for (int i = 0; i < n; ++i) {
     const int e = env_idx ? env_idx[i] : 0;
-    if (e < 0 || e >= h->N) return fail(DTSIM_E_INVALID, "env_idx[%d] = %d out of range [0, %d)", i, e, h->N);
-    if (env_idx && i && env_idx[i] < env_idx[i - 1]) return fail(DTSIM_E_INVALID, "env_idx must be non-decreasing (segments grouped by env)");
+    if (e < 0 || e >= h->N) return fail(DTSIM_E_INVALID, "%s: env_idx[%d] = %d out of range [0, %d)", who, i, e, h->N);
+    if (env_idx && i && env_idx[i] < env_idx[i - 1]) return fail(DTSIM_E_INVALID, "%s: env_idx must be non-decreasing (records grouped by env, in draw order)", who);
   }
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->lines_cap < n) {
-    const int cap = std::max(n, 1024);
-    HIPCHK(dev_grow(h->d_lines, 9 * (size_t)cap, h->stream));
-    h->lines_cap = cap;
+  if (h->*cap < n) {
+    const int grown = std::max(n, min_cap);
+    HIPCHK(dev_grow(h->*buf, width * (size_t)grown, h->stream));
+    h->*cap = grown;
   }
-  HIPCHK(hipMemcpyAsync(h->d_lines.get(), lines, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  RenderParams R{};
-  R.N = h->N; R.W = h->cfg.cam_width; R.H = h->cfg.cam_height; R.frames = h->frames; R.lut = h->d_lut.get();
-  render_scratch(h, 0, &R);   // (the overlays read the EnvCam records the pass wrote)
+  float* d_recs = (h->*buf).get();
+  HIPCHK(hipMemcpyAsync(d_recs, recs, sizeof(float) * width * (size_t)n, hipMemcpyHostToDevice, h->stream));
   int i0 = 0;
-  while (i0 < n) {                                    // one launch per env that has segments
+  while (i0 < n) {                                    // one launch per env that has records
     const int e = env_idx ? env_idx[i0] : 0;
     int i1 = i0;
     while (i1 < n && (env_idx ? env_idx[i1] : 0) == e) ++i1;
-    dt_launch_overlay_lines(h->stream, R, h->d_lines.get(), i0, i1 - i0, e);
+    launch(h->stream, R, d_recs, i0, i1 - i0, e);
     i0 = i1;
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));           // `lines` is pageable host memory: the copy must have left it
+  HIPCHK(hipStreamSynchronize(h->stream));           // `recs` is pageable host memory: the copy must have left it
   return DTSIM_OK;
 }
 
+int dtsim_draw_lines(dtsim_t* h, const float* lines, const int32_t* env_idx, int n) {
+  return overlay_run(h, "dtsim_draw_lines", lines, 9, env_idx, n, &dtsim::d_lines, &dtsim::lines_cap, 1024,
+                     "before the first dtsim_render (the pass writes the cameras the lines go through)",
+                     [](const dtsim* h, RenderParams* R) {
+                       if (!h->have_maps || !h->have_reset || !h->have_lut || !h->rendered) return false;
+                       R->N = h->N; R->W = h->cfg.cam_width; R->H = h->cfg.cam_height; R->frames = h->frames; R->lut = h->d_lut.get();
+                       render_scratch(h, 0, R);      // (the overlays read the EnvCam records the pass wrote)
+                       return true;
+                     }, dt_launch_overlay_lines);
+}
+
 int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, int n) {
-  if (!h || (n > 0 && !spheres)) return fail(DTSIM_E_INVALID, "null argument");
-  if (n < 0) return fail(DTSIM_E_INVALID, "n = %d", n);
-  if (!h->frames) return fail(DTSIM_E_STATE, "handle created without DTSIM_F_RENDER");
-  if (int rc = check_renderable(h, "dtsim_draw_leds")) return rc;
-  if (!h->rendered || !h->leds_ok || h->last_segment) return fail(DTSIM_E_STATE, "dtsim_draw_leds needs a preceding dtsim_render (colour view): it tests the spheres against that pass's scene");
-  if (h->masked) return fail(DTSIM_E_STATE, "dtsim_draw_leds after dtsim_render_masked: the post-passes need a full dtsim_render");
-  if (h->n_cal) return fail(DTSIM_E_STATE, "dtsim_draw_leds with per-env distortion tables installed (the overlays read the single table)");
-  if (n == 0) return DTSIM_OK;
-  for (int i = 0; i < n; ++i) {
-    const int e = env_idx ? env_idx[i] : 0;
-    if (e < 0 || e >= h->N) return fail(DTSIM_E_INVALID, "env_idx[%d] = %d out of range [0, %d)", i, e, h->N);
-    if (env_idx && i && env_idx[i] < env_idx[i - 1]) return fail(DTSIM_E_INVALID, "env_idx must be non-decreasing (spheres grouped by env, in draw order)");
-  }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  if (h->leds_cap < n) {
-    const int cap = std::max(n, 256);
-    HIPCHK(dev_grow(h->d_leds, 8 * (size_t)cap, h->stream));
-    h->leds_cap = cap;
-  }
-  HIPCHK(hipMemcpyAsync(h->d_leds.get(), spheres, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  RenderParams R = h->last_R;
-  R.frames = h->frames;                               // (dtsim_bind_frames may have moved the output since the pass)
-  int i0 = 0;
-  while (i0 < n) {                                    // one launch per env that has spheres
-    const int e = env_idx ? env_idx[i0] : 0;
-    int i1 = i0;
-    while (i1 < n && (env_idx ? env_idx[i1] : 0) == e) ++i1;
-    dt_launch_overlay_leds(h->stream, R, h->d_leds.get(), i0, i1 - i0, e);
-    i0 = i1;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));           // `spheres` is pageable host memory: the copy must have left it
-  return DTSIM_OK;
+  return overlay_run(h, "dtsim_draw_leds", spheres, 8, env_idx, n, &dtsim::d_leds, &dtsim::leds_cap, 256,
+                     "needs a preceding dtsim_render (colour view): it tests the spheres against that pass's scene",
+                     [](const dtsim* h, RenderParams* R) {
+                       if (!h->rendered || !h->leds_ok || h->last_segment) return false;
+                       *R = h->last_R;
+                       R->frames = h->frames;        // (dtsim_bind_frames may have moved the output since the pass)
+                       return true;
+                     }, dt_launch_overlay_leds);
 }
 
 // The shared body of dtsim_depth / dtsim_depth_masked.  masked: the masked form (its device mask must be given).

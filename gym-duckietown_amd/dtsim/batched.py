@@ -497,6 +497,39 @@ class BatchedSimulator:
             raise ValueError(f"mask: need a contiguous uint8 / bool tensor of shape ({self.num_envs},), got {mask.dtype} of shape {tuple(mask.shape)}")
         return mask.data_ptr()
 
+    def _mask_arg(self, mask):
+        """An optional per-env mask as the C argument: None, or the device pointer of a mask _mask_ptr accepts."""
+        return None if mask is None else C.c_void_p(self._mask_ptr(mask))
+
+    def _dev_tensor(self, t, who: str, lead: Optional[int] = None, shape=None, dtypes=None):
+        """`t` if it is a contiguous CUDA tensor on the handle's device -- with leading dimension `lead`, of exactly `shape`, of one of
+        `dtypes`, where given --, else ValueError."""
+        import torch
+        dev = torch.device("cuda", self.device_index)
+        if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() \
+                or (lead is not None and (t.dim() < 1 or t.shape[0] != lead)) or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError(f"{who} must be a contiguous CUDA tensor on {dev}" + (f" with leading dimension {lead}" if lead is not None else "")
+                             + (f" of shape {tuple(shape)}" if shape is not None else ""))
+        if dtypes is not None and t.dtype not in dtypes:
+            raise ValueError(f"{who} must be {' or '.join(str(d)[6:] for d in dtypes)}, got {t.dtype}")
+        return t
+
+    @staticmethod
+    def _out_ptr(out, shape, typestr: str, item: int, who: str) -> int:
+        """The data pointer of a device output: any object with __cuda_array_interface__ of exactly `shape` and `typestr` (`item` bytes per
+        element), C-contiguous, else ValueError -- the kernels write exactly this layout from the pointer: anything else would be misread
+        or overrun."""
+        ai = getattr(out, "__cuda_array_interface__", None)
+        if ai is None:
+            raise ValueError(f"{who}: out needs __cuda_array_interface__ (a device array), got {type(out).__name__}")
+        c_strides = tuple(int(np.prod(shape[i + 1:])) * item for i in range(len(shape)))
+        strides = ai.get("strides")
+        if tuple(ai["shape"]) != shape or ai["typestr"] != typestr or not (
+                strides is None or all(s == c for s, c, n in zip(strides, c_strides, shape) if n > 1)):
+            raise ValueError(f"{who}: out: need a C-contiguous {typestr} array of shape {shape}, got shape {tuple(ai['shape'])}, "
+                             f"typestr {ai['typestr']!r}, strides {strides}")
+        return ai["data"][0]
+
     def render(self, segment: bool = False, gl_filter: bool = False, mask=None):
         """render_obs() of every env into the frame batch; `segment=True` is the reference's segmentation render
         (simulator.py:1730-1737,1753,1808,1879).  `gl_filter=True` (DTSIM_RENDER_GL_FILTER): tile textures filtered with the arithmetic of the
@@ -505,7 +538,7 @@ class BatchedSimulator:
         `mask` (CUDA uint8 / bool tensor [N] on the handle's device; anything else raises ValueError before a launch): dtsim_render_masked --
         only the selected envs are rendered, the other frames keep their bytes (the generic pipelines re-render them unchanged)."""
         flags = _ffi.RENDER_GL_FILTER if gl_filter else 0
-        mp = None if mask is None else self._mask_ptr(mask)
+        mp = self._mask_arg(mask)
         if segment:
             if not self._have_segment_assets:
                 self._install_segment_assets()
@@ -513,7 +546,7 @@ class BatchedSimulator:
         if mp is None:
             _ffi.check(self._lib, self._lib.dtsim_render_ex(self._h, flags))
         else:
-            _ffi.check(self._lib, self._lib.dtsim_render_masked(self._h, flags, C.c_void_p(mp)))
+            _ffi.check(self._lib, self._lib.dtsim_render_masked(self._h, flags, mp))
 
     _PIPE_NAMES = {_ffi.PIPE_GENERIC: "k_raster", _ffi.PIPE_GENERIC_ENV: "k_raster_env", _ffi.PIPE_Q: "k_raster_q",
                    _ffi.PIPE_V3: "k_raster_v3", _ffi.PIPE_V3DR: "k_raster_v3dr"}
@@ -571,9 +604,13 @@ class BatchedSimulator:
         """GL_LINE overlays (the reference's draw_curve / draw_bbox) as a post-pass on the frames of the last render():
         lines [n, 9] = world-space segment (ax, ay, az, bx, by, bz) + colour (r, g, b in 0..1); env_idx [n] (non-decreasing) or None =
         env 0.  dtsim_draw_lines (include/dtsim.h)."""
+        self._overlay("draw_lines", self._lib.dtsim_draw_lines, lines, 9, "segment", env_idx)
+
+    def _overlay(self, who: str, cfn, records, width: int, noun: str, env_idx):
+        """The body of draw_lines / draw_leds: `records` as [n, width] float32 and env_idx [n] (or None) to the post-pass `cfn`."""
         if self._cal is not None and not self._skip_distort:
-            raise ValueError("draw_lines with per-env camera calibrations (camera_rand) is not supported")
-        a = np.ascontiguousarray(np.asarray(lines, dtype=np.float32).reshape(-1, 9))
+            raise ValueError(f"{who} with per-env camera calibrations (camera_rand) is not supported")
+        a = np.ascontiguousarray(np.asarray(records, dtype=np.float32).reshape(-1, width))
         n = a.shape[0]
         if n == 0:
             return
@@ -581,9 +618,9 @@ class BatchedSimulator:
         if env_idx is not None:
             ei = np.ascontiguousarray(np.asarray(env_idx, dtype=np.int32).reshape(-1))
             if ei.shape[0] != n:
-                raise ValueError("env_idx needs one entry per segment")
+                raise ValueError(f"{who}: env_idx needs one entry per {noun}")
             ip = ei.ctypes.data_as(C.POINTER(C.c_int32))
-        _ffi.check(self._lib, self._lib.dtsim_draw_lines(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), ip, int(n)))
+        _ffi.check(self._lib, cfn(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), ip, int(n)))
 
     _LED_POS = ((0.1, 0.05, -0.05), (0.1, 0.05, 0.05), (0.1, 0.05, 0.0), (-0.1, 0.05, -0.05), (-0.1, 0.05, 0.05))   # glTranslatef(px, pz, py): front_left,
     # front_right, center, back_left, back_right in the dict's order (objects.py:74-80, 96)
@@ -620,19 +657,7 @@ class BatchedSimulator:
         """The LED spheres of the reference's enable_leds (objects.py:68-121) as a post-pass on the frames of the last render(): spheres [n, 8] =
         world-space centre (x, y, z), radius, colour (r, g, b in 0..1), alpha, in draw order; env_idx [n] (non-decreasing) or None = env 0.
         dtsim_draw_leds (include/dtsim.h)."""
-        if self._cal is not None and not self._skip_distort:
-            raise ValueError("draw_leds with per-env camera calibrations (camera_rand) is not supported")
-        a = np.ascontiguousarray(np.asarray(spheres, dtype=np.float32).reshape(-1, 8))
-        n = a.shape[0]
-        if n == 0:
-            return
-        ip = None
-        if env_idx is not None:
-            ei = np.ascontiguousarray(np.asarray(env_idx, dtype=np.int32).reshape(-1))
-            if ei.shape[0] != n:
-                raise ValueError("env_idx needs one entry per sphere")
-            ip = ei.ctypes.data_as(C.POINTER(C.c_int32))
-        _ffi.check(self._lib, self._lib.dtsim_draw_leds(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), ip, int(n)))
+        self._overlay("draw_leds", self._lib.dtsim_draw_leds, spheres, 8, "sphere", env_idx)
 
     def bind_frames(self, devptr: Optional[int]):
         _ffi.check(self._lib, self._lib.dtsim_bind_frames(self._h, C.c_void_p(devptr) if devptr else None))
@@ -662,7 +687,7 @@ class BatchedSimulator:
         from . import resample
         if interpolation not in ("pil_bilinear", "cv_cubic"):
             raise ValueError(f"interpolation {interpolation!r}: 'pil_bilinear' or 'cv_cubic'")
-        mp = None if mask is None else C.c_void_p(self._mask_ptr(mask))
+        mp = self._mask_arg(mask)
         h, w = int(height), int(width)
         shape = (self.num_envs, 3, h, w) if chw else (self.num_envs, h, w, 3)
         if out is None:
@@ -672,17 +697,7 @@ class BatchedSimulator:
                                             device=f"cuda:{self.device_index}")
                 self._obs_key = key
             out = self._obs_buf
-        ai = out.__cuda_array_interface__
-        typestr = "<f4" if normalize else "|u1"
-        item = 4 if normalize else 1
-        c_strides = tuple(int(np.prod(shape[i + 1:])) * item for i in range(len(shape)))
-        strides = ai.get("strides")
-        if tuple(ai["shape"]) != shape or ai["typestr"] != typestr or not (
-                strides is None or all(s == c for s, c, n in zip(strides, c_strides, shape) if n > 1)):
-            # the kernel writes exactly this layout from the data pointer: anything else would be misread or overrun
-            raise ValueError(f"out: need a C-contiguous {typestr} array of shape {shape}, got shape {tuple(ai['shape'])}, "
-                             f"typestr {ai['typestr']!r}, strides {strides}")
-        ptr = ai["data"][0]
+        ptr = self._out_ptr(out, shape, "<f4" if normalize else "|u1", 4 if normalize else 1, "observe")
         ip = C.POINTER(C.c_int32)
         flags = (_ffi.OBS_CHW if chw else 0) | (_ffi.OBS_F32 if normalize else 0)
         if interpolation == "cv_cubic":
@@ -728,7 +743,7 @@ class BatchedSimulator:
         if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
             raise ValueError(f"depth: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
                              "(depth is point-sampled, never filtered)")
-        mp = None if mask is None else C.c_void_p(self._mask_ptr(mask))
+        mp = self._mask_arg(mask)
         shape = (self.num_envs, h, w)
         if out is None:
             key = (h, w, dtype)
@@ -738,16 +753,7 @@ class BatchedSimulator:
                 self._depth_buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device_index}")
                 self._depth_key = key
             out = self._depth_buf
-        ai = getattr(out, "__cuda_array_interface__", None)
-        if ai is None:
-            raise ValueError(f"depth: out needs __cuda_array_interface__ (a device array), got {type(out).__name__}")
-        c_strides = tuple(int(np.prod(shape[i + 1:])) * item for i in range(len(shape)))
-        strides = ai.get("strides")
-        if tuple(ai["shape"]) != shape or ai["typestr"] != typestr or not (
-                strides is None or all(s == c for s, c, n in zip(strides, c_strides, shape) if n > 1)):
-            raise ValueError(f"depth: out: need a C-contiguous {typestr} array of shape {shape}, got shape {tuple(ai['shape'])}, "
-                             f"typestr {ai['typestr']!r}, strides {strides}")
-        ptr = C.c_void_p(ai["data"][0])
+        ptr = C.c_void_p(self._out_ptr(out, shape, typestr, item, "depth"))
         flags = _ffi.DEPTH_F16 if dtype == "float16" else 0
         if mp is None:
             _ffi.check(self._lib, self._lib.dtsim_depth(self._h, ptr, h, w, flags))
@@ -758,11 +764,9 @@ class BatchedSimulator:
     def copy_rows(self, dst, src, mask):
         """dst[e] = src[e] for every env selected by `mask` (as render's), on the device, stream-ordered; the other rows of dst keep their
         content.  dst / src: CUDA tensors on the handle's device, C-contiguous, same shape and dtype, leading dimension N."""
-        import torch
         mp = self._mask_ptr(mask)
         for name, t in (("dst", dst), ("src", src)):
-            if not isinstance(t, torch.Tensor) or t.device != mask.device or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != self.num_envs:
-                raise ValueError(f"copy_rows: {name} must be a contiguous CUDA tensor on {mask.device} with leading dimension {self.num_envs}")
+            self._dev_tensor(t, "copy_rows: " + name, lead=self.num_envs)
         if dst.shape != src.shape or dst.dtype != src.dtype:
             raise ValueError(f"copy_rows: dst {tuple(dst.shape)} {dst.dtype} and src {tuple(src.shape)} {src.dtype} differ")
         row = src[0].numel() * src.element_size() if self.num_envs else 0
@@ -777,12 +781,9 @@ class BatchedSimulator:
         keep every byte.  `first`: a mask like `mask`, or None = no env starts anew.  Both tensors are contiguous CUDA tensors on the handle's
         device and must not overlap; anything else raises ValueError before a launch.  Returns `stack`."""
         import torch
-        fp = None if first is None else self._mask_ptr(first)
-        mp = None if mask is None else self._mask_ptr(mask)
-        dev = torch.device("cuda", self.device_index)
+        fp, mp = self._mask_arg(first), self._mask_arg(mask)
         for name, t in (("stack", stack), ("obs", obs)):
-            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"push_observation: {name} must be a contiguous CUDA tensor on {dev}")
+            self._dev_tensor(t, "push_observation: " + name)
         if obs.dtype != torch.uint8 or obs.dim() != 4 or obs.shape[0] != self.num_envs or obs.shape[1] != 3 or obs[0].numel() == 0:
             raise ValueError(f"push_observation: obs must be uint8 of shape ({self.num_envs}, 3, h, w), got {obs.dtype} {tuple(obs.shape)}")
         h, w = int(obs.shape[2]), int(obs.shape[3])
@@ -795,8 +796,7 @@ class BatchedSimulator:
         if s0 < o0 + obs.numel() and o0 < s0 + stack.numel() * stack.element_size():
             raise ValueError("push_observation: stack and obs overlap")
         flags = _ffi.OBS_CHW | (_ffi.OBS_F32 if stack.dtype == torch.float32 else 0) | (_ffi.OBS_GRAY if grayscale else 0)
-        _ffi.check(self._lib, self._lib.dtsim_obs_push(self._h, C.c_void_p(s0), C.c_void_p(o0), int(stack.shape[1]), h, w, flags,
-                                                       None if fp is None else C.c_void_p(fp), None if mp is None else C.c_void_p(mp)))
+        _ffi.check(self._lib, self._lib.dtsim_obs_push(self._h, C.c_void_p(s0), C.c_void_p(o0), int(stack.shape[1]), h, w, flags, fp, mp))
         return stack
 
     def blend_frames(self, out, frames, weights, mask=None):
@@ -807,17 +807,13 @@ class BatchedSimulator:
         selected envs are written.  All tensors are contiguous CUDA tensors on the handle's device; anything else raises ValueError before a
         launch.  Stream-ordered; returns `out`."""
         import torch
-        mp = None if mask is None else self._mask_ptr(mask)
-        dev = torch.device("cuda", self.device_index)
+        mp = self._mask_arg(mask)
         shape = (self.num_envs, self.camera_height, self.camera_width, 3)
         frames = list(frames) if isinstance(frames, (list, tuple)) else None
         if not frames or len(frames) > _ffi.BLEND_MAX:
             raise ValueError(f"blend_frames: frames must be a sequence of 1 .. {_ffi.BLEND_MAX} tensors")
         for name, t in [("out", out)] + [(f"frames[{i}]", f) for i, f in enumerate(frames)]:
-            if not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"blend_frames: {name} must be a contiguous CUDA tensor on {dev} of shape {shape}")
-            if t.dtype != torch.uint8 and (t is not out or t.dtype != torch.float32):
-                raise ValueError(f"blend_frames: {name} must be uint8{' or float32' if t is out else ''}, got {t.dtype}")
+            self._dev_tensor(t, "blend_frames: " + name, shape=shape, dtypes=(torch.uint8, torch.float32) if name == "out" else (torch.uint8,))
         try:
             w = [int(v) for v in weights]
             exact = all(v == x for v, x in zip(w, weights))
@@ -832,7 +828,7 @@ class BatchedSimulator:
         fp = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
         wp = (C.c_uint32 * len(w))(*w)
         _ffi.check(self._lib, self._lib.dtsim_blend_frames(self._h, C.c_void_p(out.data_ptr()), fp, wp, len(w),
-                                                           _ffi.OBS_F32 if out.dtype == torch.float32 else 0, None if mp is None else C.c_void_p(mp)))
+                                                           _ffi.OBS_F32 if out.dtype == torch.float32 else 0, mp))
         return out
 
     def frames_host(self) -> np.ndarray:

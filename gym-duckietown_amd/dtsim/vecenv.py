@@ -131,11 +131,12 @@ class DuckietownVecEnv:
         self._steps = torch.as_tensor(sim.field_device(_ffi.FIELD_STEP_COUNT), device=self.device)
         self._frames = torch.as_tensor(sim.frames_device(), device=self.device)
         self.action_shape = (num_envs, 2)
+        self._all = None                                            # `first` of reset(): every env starts anew (a mask when stacked)
         if self._stacked:
             h, w = int(obs_shape[0]), int(obs_shape[1])
             self._stack = torch.zeros((num_envs, self.frame_stack, 1 if self.grayscale else 3, h, w),
                                       dtype=torch.float32 if normalize else torch.uint8, device=self.device)
-            self._all = torch.ones(num_envs, dtype=torch.uint8, device=self.device)     # `first` of reset(): every env starts anew
+            self._all = torch.ones(num_envs, dtype=torch.uint8, device=self.device)
             self._stack_shape = (num_envs, self._stack.shape[1] * self._stack.shape[2], h, w)
         if self._blur:
             self._ring = [torch.empty_like(self._frames) for _ in self._blur]     # slot _cur holds the frame of the current state
@@ -158,20 +159,20 @@ class DuckietownVecEnv:
         return tuple(int(v) for v in w)
 
     # ------------------------------------------------------------------------------------------------
-    def _observe(self, mask=None, render=True):
+    def _show(self, mask=None, first=None, render=True):
+        """render -> `obs` of the frame batch in the form the env was built with: the raw frames, the observe buffer, or the history view
+        (observe as uint8 CHW into the simulator's own buffer -> push; `first`: the envs whose history starts anew).  `mask`: only those
+        envs, every call of it."""
+        sim = self.sim
         if render:
-            self.sim.render(mask=mask)
+            sim.render(mask=mask)
         if self.obs_shape is None:
             return self._frames                                     # [N, H, W, 3] uint8, the raw camera frames
-        return self.torch.as_tensor(self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=self.chw,
-                                                     normalize=self.normalize, mask=mask), device=self.device)
-
-    def _push(self, first=None, mask=None, render=True):
-        """render -> observe (uint8 CHW, the simulator's own buffer) -> push into the history; `mask`: only those envs, all three."""
-        if render:
-            self.sim.render(mask=mask)
-        o = self.sim.observe(self.obs_shape[0], self.obs_shape[1], chw=True, normalize=False, mask=mask)
-        self.sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
+        h, w = self.obs_shape[0], self.obs_shape[1]
+        if not self._stacked:
+            return self.torch.as_tensor(sim.observe(h, w, chw=self.chw, normalize=self.normalize, mask=mask), device=self.device)
+        o = sim.observe(h, w, chw=True, normalize=False, mask=mask)
+        sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
         return self._stack.view(self._stack_shape)
 
     def _depth_pass(self, mask=None):
@@ -179,7 +180,13 @@ class DuckietownVecEnv:
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
 
-    def _keep_final_depth(self, done, info):
+    def _keep_final(self, obs, done, info):
+        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history) and of the depth map, before the reset rewrites them."""
+        src = self._stack if self._stacked else obs
+        if self._final is None:
+            self._final = self.torch.empty_like(src)
+        self.sim.copy_rows(self._final, src, done)
+        info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape) if self._stacked else self._final, done
         if self.depth is not None:
             self.sim.copy_rows(self._final_depth, self.depth, done)
             info["final_depth"] = self._final_depth
@@ -194,7 +201,7 @@ class DuckietownVecEnv:
         self._enter()
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
-            obs = self._push(first=self._all) if self._stacked else self._observe()
+            obs = self._show(first=self._all)
             self._depth_pass()
             if self._blur:
                 self._ring[0].copy_(self._frames)                   # the next window's first frame
@@ -202,96 +209,65 @@ class DuckietownVecEnv:
         self._leave()
         return obs
 
-    def _step_blurred(self, actions):
-        """motion_blur: L - 1 sub-updates, each rendered into the next ring slot; the blend of the L slots into the handle's own frame buffer is
-        the observation of every env (and the final one of the finished envs); the restarted envs then show their first frame, unblurred."""
-        t, sim, L = self.torch, self.sim, len(self._blur)
+    def _advance(self, actions):
+        """The step of the state: dtsim_step, or with motion_blur the clipped wheel pair in L - 1 sub-updates, each rendered into the next
+        ring slot (the handle is left bound to the last one)."""
+        t, sim, blur = self.torch, self.sim, self._blur
         if isinstance(actions, np.ndarray):
-            a = np.clip(np.ascontiguousarray(actions, np.float32).reshape(1, self.num_envs, 2), -1.0, 1.0)
-        else:
+            a = np.ascontiguousarray(actions, np.float32).reshape(1, self.num_envs, 2)
+            if blur:
+                a = np.clip(a, -1.0, 1.0)
+        elif blur:
             a = actions.to(device=self.device, dtype=t.float32).clamp(-1.0, 1.0).contiguous()   # (a new tensor, made on our stream)
+        else:
+            a = actions.to(device=self.device, dtype=t.float32).contiguous()
+            a.record_stream(self.stream)
+        if not blur:
+            sim.step(a)
+            return
+        L = len(blur)
         for j in range(1, L):
             sim.step(a, flags=_ffi.STEP_ONE_UPDATE)
             sim.bind_frames(self._ring[(self._cur + j) % L].data_ptr())
             sim.render()
-        reward = self._reward.to(t.float32)
-        done = self._done.to(t.bool)
-        code = self._code.clone()
-        info = {"done_code": code, "episode_steps": self._steps.clone(), "truncated": code == _ffi.DONE_MAX_STEPS,
-                "terminated": code == _ffi.DONE_INVALID_POSE}
-        sim.blend_frames(self._frames, [self._ring[(self._cur + j) % L] for j in range(L)], self._blur)
-        sim.bind_frames(None)
-        obs = self._push(render=False) if self._stacked else self._observe(render=False)
-        if self.final_obs:
-            if self._final is None:
-                self._final = t.empty_like(self._stack if self._stacked else obs)
-            sim.copy_rows(self._final, self._stack if self._stacked else obs, done)
-            info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape) if self._stacked else self._final, done
-        sim.reset_done()
-        self._cur = (self._cur + L - 1) % L                         # the newest slot opens the next window
-        newest = self._ring[self._cur]
-        sim.bind_frames(newest.data_ptr())
-        sim.render(mask=done)
-        if self._stacked:
-            obs = self._push(first=done, mask=done, render=False)
-        elif self.obs_shape is None:
-            sim.copy_rows(self._frames, newest, done)
-        else:
-            obs = self._observe(mask=done, render=False)
-        sim.bind_frames(None)
-        return obs, reward, done, info
 
     def step(self, actions):
-        t = self.torch
-        if self._blur:
-            self._enter()
-            with t.cuda.stream(self.stream):
-                out = self._step_blurred(actions)
-            self._leave()
-            return out
+        """One sequence for every configuration.  With final_obs or motion_blur the batch is shown BEFORE the reset -- what the reference's
+        step() returns, blurred: the blend of the ring's L slots in the handle's own frame buffer -- and the restarted envs alone are shown
+        again after it, unblurred; else the reset comes first and one pass shows every env.  A post-pass of a new output goes where
+        _depth_pass stands."""
+        t, sim, blur = self.torch, self.sim, self._blur
         self._enter()
         with t.cuda.stream(self.stream):
-            if isinstance(actions, np.ndarray):
-                self.sim.step(np.ascontiguousarray(actions, np.float32).reshape(1, self.num_envs, 2))
-            else:
-                a = actions.to(device=self.device, dtype=t.float32).contiguous()
-                a.record_stream(self.stream)
-                self.sim.step(a)
+            self._advance(actions)
             reward = self._reward.to(t.float32)                     # copies: the reset below clears the fields
             done = self._done.to(t.bool)
             code = self._code.clone()
             # (dtsim_step sets done_code nonzero exactly when done: one comparison each)
             info = {"done_code": code, "episode_steps": self._steps.clone(), "truncated": code == _ffi.DONE_MAX_STEPS,
                     "terminated": code == _ffi.DONE_INVALID_POSE}
-            if self._stacked and self.final_obs:
-                self._push()                                        # every env's history now ends with what the reference's step() returns
+            if blur:
+                L = len(blur)
+                sim.blend_frames(self._frames, [self._ring[(self._cur + j) % L] for j in range(L)], blur)
+                sim.bind_frames(None)
+            if self.final_obs or blur:
+                obs = self._show(render=not blur)                   # every env; stacked: every history now ends with this frame
                 self._depth_pass()
-                if self._final is None:
-                    self._final = t.empty_like(self._stack)
-                self.sim.copy_rows(self._final, self._stack, done)
-                self._keep_final_depth(done, info)
-                self.sim.reset_done()
-                obs = self._push(first=done, mask=done)             # the restarted envs: their first frame in every slot
+                if self.final_obs:
+                    self._keep_final(obs, done, info)
+                sim.reset_done()
+                if blur:
+                    self._cur = (self._cur + L - 1) % L             # the newest slot opens the next window
+                    sim.bind_frames(self._ring[self._cur].data_ptr())
+                obs = self._show(mask=done, first=done)             # the restarted envs, only they: their first frame (in every slot)
                 self._depth_pass(mask=done)
-                info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape), done
-            elif self._stacked:
-                self.sim.reset_done()
-                obs = self._push(first=done)
-                self._depth_pass()
-            elif self.final_obs:
-                obs = self._observe()                               # what the reference's step() returns, every env
-                self._depth_pass()
-                if self._final is None:
-                    self._final = t.empty_like(obs)
-                self.sim.copy_rows(self._final, obs, done)          # kept for the finished envs
-                self._keep_final_depth(done, info)
-                self.sim.reset_done()
-                obs = self._observe(mask=done)                      # their first frames, only theirs
-                self._depth_pass(mask=done)
-                info["final_obs"], info["final_obs_mask"] = self._final, done
+                if blur:
+                    if self.obs_shape is None:
+                        sim.copy_rows(self._frames, self._ring[self._cur], done)   # (`obs` is the handle's own batch, the render went into the slot)
+                    sim.bind_frames(None)
             else:
-                self.sim.reset_done()
-                obs = self._observe()
+                sim.reset_done()
+                obs = self._show(first=done)
                 self._depth_pass()
             if self.depth is not None:
                 info["depth"] = self.depth

@@ -44,7 +44,9 @@ def test_observe_into_caller_buffer_and_errors():
     out = sim.observe(60, 80, chw=True, normalize=True, out=buf)
     sim.sync()
     assert out is buf and float(buf.max()) <= 1.0 and float(buf.mean()) > 0.0
-    nor = BatchedSimulator("small_loop", 2, render=False, seed=2)
+    with pytest.raises(ValueError):                          # an `out` without __cuda_array_interface__: a host array
+        sim.observe(60, 80, chw=True, normalize=True, out=np.zeros((3, 3, 60, 80), np.float32))
+    nor =BatchedSimulator("small_loop", 2, render=False, seed=2)
     with pytest.raises(Exception):
         nor.observe(60, 80)
     nor.close(); sim.close()
