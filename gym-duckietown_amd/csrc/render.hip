@@ -198,6 +198,8 @@ __device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const E
 // independent, so the order never changes a result).  pos[e] = position of env e.
 // MASKED (dtsim_render_masked): only the envs with mask[e] != 0 are binned; they take positions [0, live), the others pos = -1, and the
 // live count goes to *live (the SUB rasters read it at entry).
+// Past KEEP * 1024 envs bin_of runs twice per env, and nothing here makes the two evaluations round alike: that they agree, on envs within a float32
+// ulp of a tile or quadrant border too, is what tests/test_gpu_render_order.py holds (a permutation at N = 8193 ... 16385, every frame written once).
 #define SORT_BINS 4096
 template <bool MASKED = false>
 __global__ __launch_bounds__(1024) void k_env_sort(SimArrays A, const RenderMapDev* __restrict__ maps, int32_t* __restrict__ pos,
