@@ -170,6 +170,9 @@ struct dtsim {
   AssetSlot assets;
   DevPtr<uint32_t> d_texels_seg;      // segmented versions, same layout as assets.d_texels (dtsim_set_segment_assets)
   DevPtr<uint8_t> d_mesh_seg;         // [n_meshes][4] flat segmentation colour per mesh
+  DevPtr<uint8_t> d_texel_class;      // one class byte per texel in assets.d_texels' layout (dtsim_set_label_assets)
+  DevPtr<uint8_t> d_mesh_class;       // [n_meshes] class per mesh
+  int n_mesh_class = 0;               // entries of d_mesh_class (at least 1)
   DevPtr<char> d_render[DT_SLABS];    // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND, allocated at dtsim_create (the object slabs: maps.d_obj)
   bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop): 1, 2 or 4
@@ -354,6 +357,7 @@ int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, 
   h->assets = std::move(next);
   h->maps.release_render();       // the installed maps' render tables index the old lists: the render entry points wait for dtsim_set_maps
   h->d_texels_seg.reset();        // mirrors the old list
+  h->d_texel_class.reset(); h->d_mesh_class.reset(); h->n_mesh_class = 0;   // so do the label tables
   return DTSIM_OK;
 }
 
@@ -370,6 +374,20 @@ int dtsim_set_segment_assets(dtsim_t* h, const dtsim_texture* textures, int n_te
   HIPCHK(dev_upload(d_texels_seg, pool.data(), pool.size(), 1));
   HIPCHK(dev_upload(d_mesh_seg, rgbx.data(), rgbx.size()));
   h->d_texels_seg = std::move(d_texels_seg); h->d_mesh_seg = std::move(d_mesh_seg);
+  return DTSIM_OK;
+}
+
+int dtsim_set_label_assets(dtsim_t* h, const uint8_t* const* texel_class, int n_textures, const uint8_t* mesh_class, int n_meshes) {
+  if (!h) return fail(DTSIM_E_INVALID, "null handle");
+  std::vector<uint8_t> pool, mesh_tab;
+  std::string err;
+  if (int rc = dt_pack_label_tables(pool, mesh_tab, err, texel_class, n_textures, mesh_class, n_meshes, h->assets.T)) return fail(rc, "%s", err.c_str());
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  DevPtr<uint8_t> d_texel_class, d_mesh_class;
+  HIPCHK(dev_upload(d_texel_class, pool.data(), pool.size(), 1));
+  HIPCHK(dev_upload(d_mesh_class, mesh_tab.data(), mesh_tab.size()));
+  h->d_texel_class = std::move(d_texel_class); h->d_mesh_class = std::move(d_mesh_class); h->n_mesh_class = (int)mesh_tab.size();
   return DTSIM_OK;
 }
 
@@ -718,10 +736,11 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
                      }, dt_launch_overlay_leds);
 }
 
-// The shared body of dtsim_depth / dtsim_depth_masked.  masked: the masked form (its device mask must be given).
-static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+// The checks dtsim_depth, dtsim_labels and their masked forms share: the arguments (flags: only the bits of `allowed`), then the state -- a
+// colour pass of the current state whose cameras and projected triangles the post-pass reads.  masked: the masked form (its device mask must be given).
+static int map_pass_check(dtsim_t* h, const char* who, const void* out, int oh, int ow, uint32_t flags, uint32_t allowed, bool masked, const uint8_t* mask) {
   if (!h || !out || (masked && !mask)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
-  if (flags & ~(uint32_t)DTSIM_DEPTH_F16) return fail(DTSIM_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+  if (flags & ~allowed) return fail(DTSIM_E_INVALID, "%s: unknown flags 0x%x", who, flags);
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
   if (oh <= 0 || ow <= 0 || H % oh || W % ow)
     return fail(DTSIM_E_INVALID, "%s: a %d x %d map of %d x %d frames (the map is point-sampled: each size must divide the camera's)", who, ow, oh, W, H);
@@ -730,8 +749,14 @@ static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uin
   if (!h->rendered || !h->leds_ok || h->last_segment)
     return fail(DTSIM_E_STATE, "%s needs a preceding dtsim_render (colour view) of the current state: it reads that pass's cameras and projected triangles", who);
   // the masked pass of the quad-record pipelines writes neither the camera (k_cam_setup) nor the triangles (k_obj_setup) of an unselected env
-  if (h->masked && !masked) return fail(DTSIM_E_STATE, "%s after dtsim_render_masked: only dtsim_depth_masked, with the pass's mask", who);
+  if (h->masked && !masked) return fail(DTSIM_E_STATE, "%s after dtsim_render_masked: only the masked form, with the pass's mask", who);
   if (h->n_cal) return fail(DTSIM_E_STATE, "%s with per-env distortion tables installed (it reads the single table)", who);
+  return DTSIM_OK;
+}
+
+// The shared body of dtsim_depth / dtsim_depth_masked.
+static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+  if (int rc = map_pass_check(h, who, out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, masked, mask)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device));
   dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask);
   HIPCHK(hipGetLastError());
@@ -741,6 +766,21 @@ static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uin
 int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags) { return depth_run(h, "dtsim_depth", out, oh, ow, flags, false, nullptr); }
 int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
   return depth_run(h, "dtsim_depth_masked", out, oh, ow, flags, true, mask);
+}
+
+// The shared body of dtsim_labels / dtsim_labels_masked: depth's checks, and the label tables.
+static int labels_run(dtsim_t* h, const char* who, uint8_t* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+  if (int rc = map_pass_check(h, who, out, oh, ow, flags, 0u, masked, mask)) return rc;
+  if (!h->d_texel_class || !h->d_mesh_class) return fail(DTSIM_E_STATE, "%s before dtsim_set_label_assets", who);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, out, oh, ow, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags) { return labels_run(h, "dtsim_labels", out, oh, ow, flags, false, nullptr); }
+int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return labels_run(h, "dtsim_labels_masked", out, oh, ow, flags, true, mask);
 }
 
 void* dtsim_frames_devptr(dtsim_t* h) { return h ? h->frames : nullptr; }

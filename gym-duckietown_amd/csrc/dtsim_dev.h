@@ -166,6 +166,10 @@ void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d
 // (i * (H / oh) + H / oh / 2, j * (W / ow) + W / ow / 2); R = the last render pass's parameters; mask (device, [N] bytes, or null = every
 // env): the rows of the other envs are not written.  The caller checked that oh divides H and ow divides W.
 void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask);
+// the label maps of dtsim_labels (render.hip k_labels): out = [N][oh][ow] bytes, sized, sampled and masked as dt_launch_depth's; texel_class:
+// one byte per texel in the layout of R.texels (dt_pack_label_tables), mesh_class: [n_mesh_class] bytes
+void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
+                      int oh, int ow, const uint8_t* mask);
 // camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
 // envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
 void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,

@@ -493,6 +493,12 @@ __device__ inline void gl_linear_rgb(uint32_t t00, uint32_t t10, uint32_t t01, u
   }
 }
 
+// The texel coordinates of a textured tile at tile fraction (fx, fz): the record's affine map (tile angle, uv = (pu, 1 - pv), the GL_LINEAR
+// half-texel shift: x = u TW - 0.5, y = v TH - 0.5).  tile_color filters there; k_labels takes the nearest texel.
+__device__ inline void tile_texel_xy(const TileLds& tr, const float fx, const float fz, float& x, float& y) {
+  x = fmaf(tr.mxz, fz, fmaf(tr.mxx, fx, tr.ox)); y = fmaf(tr.myz, fz, fmaf(tr.myx, fx, tr.oy));
+}
+
 // GL_LINEAR/GL_REPEAT fetch from the padded texture (the exact paths and the generic raster: llvmpipe's arithmetic), times the lit
 // vertex colour I.
 __device__ inline void tile_color(const RenderParams& R, const TileLds& tr, float fx, float fz, const float I[3],
@@ -501,7 +507,8 @@ __device__ inline void tile_color(const RenderParams& R, const TileLds& tr, floa
     out[0] = 255.f * I[0]; out[1] = 255.f * I[1]; out[2] = 255.f * I[2];
     return;
   }
-  const float x = fmaf(tr.mxz, fz, fmaf(tr.mxx, fx, tr.ox)), y = fmaf(tr.myz, fz, fmaf(tr.myx, fx, tr.oy));
+  float x, y;
+  tile_texel_xy(tr, fx, fz, x, y);
   const int xf = gl_fix(x), yf = gl_fix(y);
   const int x0 = (xf >> 8) & (R.tex_w - 1), y0 = (yf >> 8) & (R.tex_h - 1);
   const uint32_t* pt = R.texels + tr.tex_off + y0 * (R.tex_w + 1) + x0;
@@ -2791,18 +2798,28 @@ struct LedS { float ex, ey, ez, r, cr, cg, cb, a, bx0, bx1, by0, by1; };     // 
 // present / ground extent / sky --, the meshes by z-buffering the env's projected triangles (boxes / tb: the env's ObjBox and ScreenTri rows that
 // the render pass's k_obj_setup left, n_obj of them; boxes null: no mesh objects) for the lanes inside an object's screen box.  depth[q] = t of
 // the eye-space ray (dx, dy, -1) t; `sky` where the sample sees the clear colour.
-__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
-                                    const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
-                                    const float sky, float depth[4]) {
+// WHO (k_labels): also who owns each sample -- hits[q] = classify()'s plane hit (class, tile, world hit), obj[q] = the object (the o of the
+// ObjBox loop) whose triangle won the sample's z-buffer AND lies strictly nearer than the plane (the colour pass's depth test, shade_msaa),
+// else -1.  Without WHO (hits, obj unused, may be null) nothing of that is compiled: the depth arithmetic is the same statements in both.
+template <bool WHO>
+__device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
+                                      const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
+                                      const float sky, float depth[4], Hit* hits, int* obj) {
   const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
   const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
   float wbest[4] = {0.f, 0.f, 0.f, 0.f};
   int tbest[4] = {-1, -1, -1, -1};
+  int obest[4] = {-1, -1, -1, -1};
   if (boxes) {
     for (int o = 0; o < n_obj; ++o) {
       const ObjBox ob = boxes[o];
       if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
       for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
+      if constexpr (WHO) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)                   // the sample's winner so far is one of this object's triangles
+          if (tbest[q] >= ob.first && tbest[q] < ob.first + ob.count) obest[q] = o;
+      }
     }
   }
 #pragma unroll
@@ -2812,9 +2829,19 @@ __device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLd
     const Ray rs = make_ray(fmaf(ox[q], sxn, nx), fmaf(-oy[q], syn, ny), c.tx, c.ty, c.sth, c.cth);
     const Hit h = classify(c, m, tiles, rs);
     float d = h.cls == CLS_SKY ? sky : h.t;
-    if (tbest[q] >= 0) d = fminf(d, 1.f / wbest[q]);
+    if constexpr (WHO) { hits[q] = h; obj[q] = -1; }
+    if (tbest[q] >= 0) {
+      const float dm = 1.f / wbest[q];
+      if constexpr (WHO) obj[q] = dm < d ? obest[q] : -1;
+      d = fminf(d, dm);
+    }
     depth[q] = d;
   }
+}
+__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
+                                    const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
+                                    const float sky, float depth[4]) {
+  scene_samples4<false>(c, m, tiles, boxes, tb, n_obj, nx, ny, sxp, syp, sxn, syn, sky, depth, nullptr, nullptr);
 }
 
 // ---- k_depth: the depth map of every env's camera frame (dtsim_depth; the quantity: include/dtsim.h) -------------------------------------
@@ -2872,6 +2899,79 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
       if (F16) static_cast<__half*>(out)[at] = __float2half_rn(d);
       else static_cast<float*>(out)[at] = d;
     }
+  }
+}
+
+// ---- k_labels: the semantic label map of every env's camera frame (dtsim_labels; the quantity: include/dtsim.h) ---------------------------
+// The sibling of k_depth: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once, the env's camera
+// record, map and object boxes at a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_labels.py holds envs e, e + 64,
+// e + 128 to the same bytes).  Per env it runs scene_samples4<true> -- scene_depth4's statements plus who owns each sample --, takes the sample
+// with the smallest depth (ties: the lowest index; sky = +inf, so it wins only when all four are sky) and maps its owner to a class: the mesh
+// table through the map's object-instance table, the two fixed plane classes, or for a tile the class of the nearest texel -- the texel
+// coordinates are tile_texel_xy's, the ones tile_color filters at, with the half-texel shift taken back: floor(x + 0.5), wrapped.
+// A thread owns ONE pixel, not four adjacent ones: the pass is bound by the four classify() calls and the triangle loop per pixel and env, not
+// by its stores (k_depth takes the same time for half maps as for float32 ones, profiles/depth_timing.txt; k_labels, with a quarter of the
+// bytes, takes 1.4 x k_depth's time on planes and the same time under meshes, profiles/labels_timing.txt); four pixels per lane would serialise
+// four of those per lane for the sake of one wider store, and a wavefront's 64 byte stores are still one contiguous 64-byte row segment.
+// tex_w, tex_h: the one (power-of-two) size of all tile textures; texel_class: dt_pack_label_tables' pool, addressed like R.texels.
+__global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
+                                                const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
+                                                const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
+                                                const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h,
+                                                const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
+                                                uint8_t* __restrict__ out, const uint8_t* __restrict__ mask) {
+  const int n_out = oh * ow;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const bool in = pix < n_out;
+  const int sy = H / oh, sx = W / ow;
+  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
+  bool live = false;
+  if (in) {
+    const int i = pix / ow, j = pix - i * ow;
+    const float4 l = lut[(size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2)];
+    live = l.z != 0.f;                                 // 0: the fisheye leaves this pixel without a source (the frame's black border)
+    nx = l.x; ny = l.y;
+    sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;       // centre of the source pixel
+  }
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
+  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+#pragma clang loop unroll(disable)
+  for (int e = e0; e < e1; ++e) {
+    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
+    const EnvCam c = cams[e];
+    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
+    const MapU m = map_u(rm);
+    uint32_t cls = DTSIM_LABEL_NONE;
+    if (live) {
+      float ds[4];
+      Hit hs[4];
+      int os[4];
+      scene_samples4<true>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
+                           objbox ? rm.n_obj : 0, nx, ny, sxp, syp, sxn, syn, __builtin_inff(), ds, hs, os);
+      float db = ds[0];
+      Hit hb = hs[0];
+      int ob = os[0];
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+        if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; }
+      if (ob >= 0) {
+        const int mid = objs[rm.obj_off + ob].mesh_id;
+        cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
+      } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
+      else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
+      else {
+        const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
+        cls = DTSIM_LABEL_GROUND;                      // a present tile without a texture has no texel table
+        if (tr.flags & 2u) {
+          const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade() takes it
+          float x, y;
+          tile_texel_xy(tr, fx, fz, x, y);
+          const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
+          cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+        }
+      }
+    }
+    if (in) out[(size_t)e * (size_t)n_out + (size_t)pix] = (uint8_t)cls;
   }
 }
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
@@ -2980,6 +3080,16 @@ void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, in
                                               R.n_maps, R.N, R.W, R.H, oh, ow, out, mask)
   if (f16) LAUNCH_DEPTH(true); else LAUNCH_DEPTH(false);
 #undef LAUNCH_DEPTH
+}
+
+void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
+                      int oh, int ow, const uint8_t* mask) {
+  if (R.N <= 0) return;
+  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
+  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
+  hipLaunchKernelGGL(k_labels, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
+                     reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
+                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, mask);
 }
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {

@@ -183,6 +183,33 @@ inline int dt_pack_segment_texels(std::vector<uint32_t>& pool, std::vector<uint8
   return DTSIM_OK;
 }
 
+// dtsim_set_label_assets: the class of every texel in A.pool's layout, one byte per texel (texture t at A.tex[t].off, padded to
+// (h+1) x (w+1) by GL_REPEAT as the texels are, so that a tile record's tex_off addresses both pools), and [max(n_meshes, 1)] mesh classes.
+// texel_class[t]: [h][w] bytes of texture t, in its row order.
+inline int dt_pack_label_tables(std::vector<uint8_t>& pool, std::vector<uint8_t>& mesh_tab, std::string& err, const uint8_t* const* texel_class,
+                                int n_textures, const uint8_t* mesh_class, int n_meshes, const AssetTables& A) {
+  const int n_tex = (int)A.tex.size(), n_mesh = (int)A.meshes.size();
+  if (n_textures != n_tex || n_meshes != n_mesh)
+    return dt_scene_fail(err, DTSIM_E_INVALID, "label assets must mirror dtsim_set_assets (%d textures, %d meshes), got %d / %d", n_tex, n_mesh,
+                         n_textures, n_meshes);
+  if ((n_textures > 0 && !texel_class) || (n_meshes > 0 && !mesh_class)) return dt_scene_fail(err, DTSIM_E_INVALID, "null argument");
+  for (int t = 0; t < n_textures; ++t)
+    if (!texel_class[t]) return dt_scene_fail(err, DTSIM_E_INVALID, "texel classes of texture %d: null", t);
+  std::vector<uint8_t> p(A.pool.size(), 0);
+  for (int t = 0; t < n_textures; ++t) {
+    const TexDev& d = A.tex[t];
+    const size_t pw = (size_t)d.w + 1;
+    if ((size_t)d.off + pw * ((size_t)d.h + 1) > p.size()) return dt_scene_fail(err, DTSIM_E_INVALID, "texture %d lies outside the texel pool", t);
+    uint8_t* dst = p.data() + d.off;
+    for (int y = 0; y <= d.h; ++y)
+      for (int x = 0; x <= d.w; ++x) dst[(size_t)y * pw + x] = texel_class[t][(size_t)(y % d.h) * d.w + (x % d.w)];
+  }
+  std::vector<uint8_t> mt((size_t)std::max(n_meshes, 1), 0);
+  for (int m = 0; m < n_meshes; ++m) mt[m] = mesh_class[m];
+  pool = std::move(p); mesh_tab = std::move(mt);
+  return DTSIM_OK;
+}
+
 // ---- maps ---------------------------------------------------------------------------------------------------------------------
 // How a tile's texture lies in the tile frame: glRotatef(angle*90+180) about y with uv = (pu, 1-pv) (simulator.py:394-401,1872-1873)
 // gives, at tile fraction (fx, fz), u = {1-fx, fz, fx, 1-fz}[angle] and v = {fz, fx, 1-fz, 1-fx}[angle] -- u takes fz instead of fx

@@ -4,7 +4,7 @@ The HIP library is the product.  Importing this package does not need a GPU; cre
 BatchedSimulator does (dtsim_create fails with DTSIM_E_NOGPU otherwise -- there is no CPU
 fallback).
 """
-from . import _ffi, assets, maps  # noqa: F401
+from . import _ffi, assets, labels, maps  # noqa: F401
 from ._ffi import DtsimError, DtsimLibraryError  # noqa: F401
 from .batched import BatchedSimulator  # noqa: F401
 from .vecenv import DuckietownVecEnv  # noqa: F401

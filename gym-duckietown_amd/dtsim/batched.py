@@ -761,6 +761,73 @@ class BatchedSimulator:
             _ffi.check(self._lib, self._lib.dtsim_depth_masked(self._h, ptr, h, w, flags, mp))
         return out
 
+    def label_assets(self):
+        """(per-texture class maps mirroring self.textures -- [h, w] uint8 each, in the texture's row order --, per-mesh classes [n_meshes] uint8):
+        the default tables of labels() (dtsim/labels.py).  Tile textures: FLOOR on the kinds without lane curves, else ROAD where
+        segment_assets() blacked the texel out and a marking class by the stated rule elsewhere; the other textures (mesh materials,
+        traffic-light cards), which no tile shows, are all 0; meshes by the kind's name."""
+        from . import labels
+        seg_tex, _ = self.segment_assets()
+        texel = [labels.texel_classes(self.textures[i], seg_tex[i], kd) for i, kd in enumerate(self.texture_kinds)]
+        texel += [np.zeros(t.shape[:2], np.uint8) for t in self.textures[len(texel):]]
+        return texel, labels.mesh_classes(self._mesh_order)
+
+    def set_label_assets(self, texel_class=None, mesh_class=None):
+        """Install the tables of labels() (dtsim_set_label_assets): texel_class = one [h, w] uint8 array per entry of self.textures, of its
+        size and row order; mesh_class = [n_meshes] uint8 in the order of the simulator's meshes.  None: the default of label_assets().  A
+        table of the wrong count, size or type raises ValueError before the library is called; a failed call leaves the installed tables."""
+        if texel_class is None or mesh_class is None:
+            d_texel, d_mesh = self.label_assets()
+            texel_class = d_texel if texel_class is None else texel_class
+            mesh_class = d_mesh if mesh_class is None else mesh_class
+        if len(texel_class) != len(self.textures):
+            raise ValueError(f"set_label_assets: {len(texel_class)} texel class maps for {len(self.textures)} textures")
+        tc = []
+        for i, (a, t) in enumerate(zip(texel_class, self.textures)):
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.shape != t.shape[:2]:
+                raise ValueError(f"set_label_assets: texel_class[{i}] must be uint8 of shape {t.shape[:2]}, got {a.dtype} {a.shape}")
+            tc.append(np.ascontiguousarray(a))
+        mc = np.asarray(mesh_class)
+        if mc.dtype != np.uint8 or mc.shape != (len(self._mesh_order),):
+            raise ValueError(f"set_label_assets: mesh_class must be uint8 of shape ({len(self._mesh_order)},), got {mc.dtype} {mc.shape}")
+        mc = np.ascontiguousarray(mc)
+        u8p = C.POINTER(C.c_uint8)
+        parr = (u8p * max(len(tc), 1))()
+        for i, a in enumerate(tc):
+            parr[i] = a.ctypes.data_as(u8p)
+        _ffi.check(self._lib, self._lib.dtsim_set_label_assets(self._h, parr, len(tc), mc.ctypes.data_as(u8p), len(mc)))
+        self._have_label_assets = True
+
+    def labels(self, height=None, width=None, out=None, mask=None):
+        """The semantic label map of every env's camera frame, on the device (dtsim_labels, include/dtsim.h): [N, h, w] uint8, per pixel the
+        class of the surface that sets depth()'s value there -- of the four MSAA samples of the frame's source pixel the nearest one (ties: the
+        lowest index; sky only when all four are sky): 0 in the fisheye's black border, 1 sky, 2 the ground quad, for a tile the class of the
+        nearest texel of its texture, for a mesh object the class of its mesh (the tables of set_label_assets(); the defaults, installed at
+        the first call: dtsim/labels.py).  Never filtered.  Needs a preceding render() of the current state.  Size, `out` and `mask` as
+        depth()'s; a bad size, out or mask raises ValueError before anything is launched."""
+        import torch
+        h = self.camera_height if height is None else int(height)
+        w = self.camera_width if width is None else int(width)
+        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
+            raise ValueError(f"labels: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
+                             "(labels are point-sampled, never filtered)")
+        mp = self._mask_arg(mask)
+        shape = (self.num_envs, h, w)
+        if out is None:
+            if getattr(self, "_labels_key", None) != (h, w):
+                self._labels_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")     # (empty: as depth()'s buffer)
+                self._labels_key = (h, w)
+            out = self._labels_buf
+        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "labels"))
+        if not getattr(self, "_have_label_assets", False):
+            self.set_label_assets()
+        if mp is None:
+            _ffi.check(self._lib, self._lib.dtsim_labels(self._h, ptr, h, w, 0))
+        else:
+            _ffi.check(self._lib, self._lib.dtsim_labels_masked(self._h, ptr, h, w, 0, mp))
+        return out
+
     def copy_rows(self, dst, src, mask):
         """dst[e] = src[e] for every env selected by `mask` (as render's), on the device, stream-ordered; the other rows of dst keep their
         content.  dst / src: CUDA tensors on the handle's device, C-contiguous, same shape and dtype, leading dimension N."""

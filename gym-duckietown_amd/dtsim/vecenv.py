@@ -55,6 +55,14 @@ env restarted in the step, the first frame of its new episode.  `reset()` keeps 
 depth -> `dtsim_copy_rows` -> `dtsim_reset_done` -> masked render -> masked observe -> `dtsim_depth_masked`.  `frame_stack`, `grayscale` and
 `obs_shape=None` compose (depth is never stacked); `motion_blur` (its observation shows three states) and `camera_rand` (a distortion table
 per env) raise ValueError.  `depth_shape=None` (the default) runs the paths above, call for call.
+
+Labels (`label_shape=(h, w)`, each dividing the camera's size): `info["labels"]` is one persistent `[N, h, w]` `torch.uint8` device tensor
+with the semantic label map (`dtsim_labels`, include/dtsim.h: per pixel the class of the surface that sets the depth there -- 0 the fisheye's
+black border, 1 sky, 2 ground, tiles by the nearest texel's class, mesh objects by their mesh's; the default classes: dtsim/labels.py;
+point-sampled, never filtered) of the state `obs` shows; after `reset()` it is `env.labels`, the same tensor.  With `final_obs=True`,
+`info["final_labels"]` holds the finished envs' rows as `info["final_depth"]` does.  The pass stands where the depth pass does, after it
+when both are on, and composes with `depth_shape`, `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand`; `motion_blur` and
+`camera_rand` raise ValueError, for depth's reasons.  `label_shape=None` (the default) makes no new call.
 """
 from __future__ import annotations
 
@@ -71,7 +79,7 @@ class DuckietownVecEnv:
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
                  seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False,
                  motion_blur: Union[bool, Sequence[int]] = False, depth_shape: Optional[Tuple[int, int]] = None,
-                 depth_dtype: str = "float32", **sim_kwargs):
+                 depth_dtype: str = "float32", label_shape: Optional[Tuple[int, int]] = None, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -100,6 +108,22 @@ class DuckietownVecEnv:
             if dh <= 0 or dw <= 0 or H % dh or W % dw:
                 raise ValueError(f"depth_shape {(dh, dw)}: each size must divide the camera's {(H, W)} (depth is point-sampled, never filtered)")
             self.depth_shape = (dh, dw)
+        self.label_shape = None
+        if label_shape is not None:
+            if self._blur:
+                raise ValueError("label_shape with motion_blur is not supported (the blurred observation shows the three states of its window: "
+                                 "no single state's labels belong to it)")
+            if sim_kwargs.get("camera_rand"):
+                raise ValueError("label_shape with camera_rand is not supported (dtsim_labels reads the single distortion table, camera_rand "
+                                 "installs one per env)")
+            try:
+                lh, lw = (int(v) for v in label_shape)
+            except (TypeError, ValueError):
+                raise ValueError(f"label_shape must be (h, w), got {label_shape!r}") from None
+            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
+            if lh <= 0 or lw <= 0 or H % lh or W % lw:
+                raise ValueError(f"label_shape {(lh, lw)}: each size must divide the camera's {(H, W)} (labels are point-sampled, never filtered)")
+            self.label_shape = (lh, lw)
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -124,6 +148,11 @@ class DuckietownVecEnv:
             self.depth = torch.zeros((num_envs, *self.depth_shape), dtype=getattr(torch, depth_dtype), device=self.device)
             if self.final_obs:
                 self._final_depth = torch.zeros_like(self.depth)
+        self.labels = self._final_labels = None                     # info["labels"] / info["final_labels"]: persistent [N, h, w] uint8 tensors
+        if self.label_shape is not None:
+            self.labels = torch.zeros((num_envs, *self.label_shape), dtype=torch.uint8, device=self.device)
+            if self.final_obs:
+                self._final_labels = torch.zeros_like(self.labels)
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -176,12 +205,16 @@ class DuckietownVecEnv:
         return self._stack.view(self._stack_shape)
 
     def _depth_pass(self, mask=None):
-        """depth_shape: the depth of the state the last render() showed, into self.depth (`mask`: only those envs' rows)."""
+        """depth_shape / label_shape: the depth, then the labels, of the state the last render() showed, into self.depth / self.labels
+        (`mask`: only those envs' rows)."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
+        if self.labels is not None:
+            self.sim.labels(self.label_shape[0], self.label_shape[1], out=self.labels, mask=mask)
 
     def _keep_final(self, obs, done, info):
-        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history) and of the depth map, before the reset rewrites them."""
+        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map and of the label map, before the
+        reset rewrites them."""
         src = self._stack if self._stacked else obs
         if self._final is None:
             self._final = self.torch.empty_like(src)
@@ -190,6 +223,9 @@ class DuckietownVecEnv:
         if self.depth is not None:
             self.sim.copy_rows(self._final_depth, self.depth, done)
             info["final_depth"] = self._final_depth
+        if self.labels is not None:
+            self.sim.copy_rows(self._final_labels, self.labels, done)
+            info["final_labels"] = self._final_labels
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -271,6 +307,8 @@ class DuckietownVecEnv:
                 self._depth_pass()
             if self.depth is not None:
                 info["depth"] = self.depth
+            if self.labels is not None:
+                info["labels"] = self.labels
         self._leave()
         return obs, reward, done, info
 

@@ -281,7 +281,7 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out);
 void dtsim_destroy(dtsim_t* h);
 
 /* The setters -- dtsim_set_assets, dtsim_set_maps, dtsim_set_distortion_lut(s), dtsim_set_reset_sampler, dtsim_set_spawn_pool,
- * dtsim_set_segment_assets -- and the table caches of dtsim_observe / dtsim_observe_cubic: on failure the handle keeps what it
+ * dtsim_set_segment_assets, dtsim_set_label_assets -- and the table caches of dtsim_observe / dtsim_observe_cubic: on failure the handle keeps what it
  * had.  Only what the last render pass left for the post-passes may be dropped: dtsim_draw_leds then waits for a dtsim_render.
  * dtsim_set_maps packs the maps against the assets installed at that moment (texture, mesh and triangle indices), so the order is
  * dtsim_set_assets, then dtsim_set_maps.  A dtsim_set_assets that succeeds while maps are installed releases their render-side
@@ -550,6 +550,40 @@ int dtsim_blend_frames(dtsim_t* h, void* out, const void* const* frames, const u
 enum { DTSIM_DEPTH_F16 = 1u };
 int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags);
 int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
+/* The semantic label map of every camera frame, on the device: WHICH surface a pixel shows, as a class id beside the observation and the
+ * depth map (the reference has only the segment view: a colour picture with blended edges, in place of the frame).
+ * THE QUANTITY.  labels[e][i][j], a uint8, is the class of the surface that sets depth[e][i][j] of dtsim_depth: of the four MSAA samples
+ * of the frame's source pixel, the sample with the smallest eye depth.
+ *   - Ties go to the lowest sample index.
+ *   - A sky sample counts as +inf: it wins only if all four are sky.
+ *   - Within a sample a mesh owns it only where its z-buffer depth is strictly smaller than the plane's (the colour pass's depth test).
+ * The owner of that sample maps to the class:
+ *   - a pixel the distortion table leaves without a source    DTSIM_LABEL_NONE
+ *   - the clear colour                                         DTSIM_LABEL_SKY
+ *   - the ground quad                                          DTSIM_LABEL_GROUND
+ *   - a tile              texel_class[tex][v][u], the class of the NEAREST texel of the tile's texture at the hit: the texel coordinates are
+ *                         those the generic raster filters at (from the tile's angle and the hit's wx, wz), rounded down after the
+ *                         half-texel shift is taken back, wrapped as GL_REPEAT; a present tile without a texture: DTSIM_LABEL_GROUND
+ *   - mesh object o       mesh_class[mesh id of o]
+ * The device applies no colour rule and knows no class beyond these three: every other id is what the tables of
+ * dtsim_set_label_assets say.  Ids 3 .. 7 are reserved for the default tile classes of the host (dtsim/labels.py), 8 .. 255 for objects.
+ * Never filtered, never blended: an edge pixel carries the class of its nearest sample, not a mixture.
+ * SIZE.  out: DEVICE pointer to [num_envs][oh][ow] bytes; size and sampling are dtsim_depth's: cam_height % oh == 0 and cam_width % ow == 0,
+ * out[e][i][j] belongs to camera pixel (i sy + sy / 2, j sx + sx / 2), and only those pixels are traced.  flags must be 0.
+ * TABLES.  dtsim_set_label_assets: texel_class[t] is [height][width] bytes in the row order and size of texture t of dtsim_set_assets,
+ * mesh_class is [n_meshes]; both counts must mirror dtsim_set_assets (else DTSIM_E_INVALID), host pointers, copied during the call.  A
+ * failed call changes nothing; dtsim_set_assets drops the tables (the list they mirror is gone).
+ * STATE.  The rules of dtsim_depth, word for word (a colour render of the current state, the same calls invalidate, after
+ * dtsim_render_masked only the masked form with the pass's mask, per-env distortion tables refused), and DTSIM_E_STATE without label
+ * tables.  A null handle, out or mask, a bad size or a nonzero flag return DTSIM_E_INVALID; a failed call launches nothing and writes
+ * nothing.  Asynchronous, stream-ordered.  One state gives the same bytes on every call and for every env index. */
+enum { DTSIM_LABEL_NONE = 0, DTSIM_LABEL_SKY = 1, DTSIM_LABEL_GROUND = 2,
+       DTSIM_LABEL_FLOOR = 3,        /* a non-drivable tile */
+       DTSIM_LABEL_ROAD = 4, DTSIM_LABEL_MARK_WHITE = 5, DTSIM_LABEL_MARK_YELLOW = 6, DTSIM_LABEL_MARK_RED = 7,
+       DTSIM_LABEL_OBJECT_FIRST = 8 };
+int dtsim_set_label_assets(dtsim_t* h, const uint8_t* const* texel_class, int n_textures, const uint8_t* mesh_class, int n_meshes);
+int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags);
+int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

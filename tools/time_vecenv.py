@@ -7,9 +7,11 @@ batches; MOTION_BLUR=rerender: the same with the window's first frame rendered a
 reusing the previous window's last frame saves).
 DEPTH=1: info["depth"] beside the observation (DuckietownVecEnv(depth_shape=(120, 160)): dtsim_depth after every observe); DEPTH=full: the
 camera's own 480 x 640; DEPTH_DTYPE=float16: half maps.  MAP=loop_pedestrians: another map (mesh objects: the depth kernel's triangle loop).
+LABELS=1: info["labels"] beside the observation (DuckietownVecEnv(label_shape=(120, 160)): dtsim_labels after every observe); LABELS=full: 480 x 640.
 VARIANTS=a,b,...: several variants in ONE process, each warmed up, then timed in alternating order (ROUNDS rounds of K steps each, the
 median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4) | wheels (the plain env with
-action_mode="wheels", the blur's baseline) | blur | blur_rerender | depth | depth_f16 | depth_full | depth_full_f16."""
+action_mode="wheels", the blur's baseline) | blur | blur_rerender | depth | depth_f16 | depth_full | depth_full_f16 | labels | labels_full |
+depth_labels (both maps at 120 x 160)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -24,6 +26,7 @@ EMULATE = os.environ.get("EMULATE", "0") == "1"
 MOTION_BLUR = os.environ.get("MOTION_BLUR", "0")
 DEPTH = os.environ.get("DEPTH", "0")
 DEPTH_DTYPE = os.environ.get("DEPTH_DTYPE", "float32")
+LABELS = os.environ.get("LABELS", "0")
 MAP = os.environ.get("MAP", "small_loop")
 MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
@@ -33,7 +36,7 @@ a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
-    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32"):
+    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0"):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
@@ -42,6 +45,8 @@ class Variant:
             kw.update(action_mode="wheels")
         if depth != "0":
             kw.update(depth_shape=(480, 640) if depth == "full" else (120, 160), depth_dtype=depth_dtype)
+        if labels != "0":
+            kw.update(label_shape=(480, 640) if labels == "full" else (120, 160))
         self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -81,6 +86,8 @@ def make(name):
             "depth": lambda: Variant("depth 120 x 160 float32", depth="1"), "depth_f16": lambda: Variant("depth 120 x 160 float16", depth="1", depth_dtype="float16"),
             "depth_full": lambda: Variant("depth 480 x 640 float32", depth="full"),
             "depth_full_f16": lambda: Variant("depth 480 x 640 float16", depth="full", depth_dtype="float16"),
+            "labels": lambda: Variant("labels 120 x 160", labels="1"), "labels_full": lambda: Variant("labels 480 x 640", labels="full"),
+            "depth_labels": lambda: Variant("depth float32 + labels 120 x 160", depth="1", labels="1"),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
@@ -97,11 +104,12 @@ if VARIANTS:
         print(f"VecEnv{MAP_TAG} N={N}{' final_obs' if FINAL else ''} {v.name:40s} {list(v.shape)} {str(v.dtype)[6:]}: median {s[len(s) // 2]:.3f} ms per step "
               f"(min {s[0]:.3f}, max {s[-1]:.3f}; {ROUNDS} rounds of {K} steps)")
 else:
-    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE, MOTION_BLUR, depth=DEPTH, depth_dtype=DEPTH_DTYPE)
+    v = Variant("", STACK, GRAY, NORMALIZE, EMULATE, MOTION_BLUR, depth=DEPTH, depth_dtype=DEPTH_DTYPE, labels=LABELS)
     v.run(5)
     dt = v.run(K)
     what = (f" emulated K={STACK}" if EMULATE else "") + (f" frame_stack={STACK}" if STACK > 1 and not EMULATE else "") + (" grey" if GRAY else "") + \
         ({"0": "", "1": " motion_blur", "rerender": " motion_blur + first frame rendered again"}[MOTION_BLUR]) + \
-        ("" if DEPTH == "0" else f" depth {list(v.env.depth.shape[1:])} {DEPTH_DTYPE}")
+        ("" if DEPTH == "0" else f" depth {list(v.env.depth.shape[1:])} {DEPTH_DTYPE}") + \
+        ("" if LABELS == "0" else f" labels {list(v.env.labels.shape[1:])}")
     print(f"VecEnv{MAP_TAG} N={N}{' final_obs' if FINAL else ''}{what}: {dt*1e3:.3f} ms per step -> {N/dt/1e6:.3f} M env-steps/s with "
           f"{list(v.shape)} {str(v.dtype)[6:]} observations")
