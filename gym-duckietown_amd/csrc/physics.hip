@@ -19,6 +19,7 @@
 // read+write of the SoA state; at N=4096 the working set is L2-resident and the kernel
 // is latency-bound, so n_steps are fused per launch.
 #include "dtsim_dev.h"
+#include "philox_rng.h"
 
 #pragma clang fp contract(off)
 
@@ -301,57 +302,7 @@ __device__ inline double compute_reward(const Lane& L, double prox, double speed
   return ((1.0 * speed) * L.dot_dir + (-10 * fabs(L.dist))) + (40 * prox);
 }
 
-// ---- device-side reset sampler (dtsim_reset_sampler) ----------------------------------
-// Philox4x32-10 (Salmon et al. 2011): counter-based, so an env's draws for episode k depend only on
-// (seed, env, k) -- reproducible regardless of which step the reset happens in or how envs are sharded.
-struct Philox {
-  uint32_t key[2], ctr[4], out[4];
-  int left;
-};
-__device__ inline void philox_round(uint32_t c[4], const uint32_t k[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
-  c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-}
-__device__ inline void philox_refill(Philox& g) {
-  uint32_t c[4] = {g.ctr[0], g.ctr[1], g.ctr[2], g.ctr[3]}, k[2] = {g.key[0], g.key[1]};
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k);
-    k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
-  }
-  for (int i = 0; i < 4; ++i) g.out[i] = c[i];
-  g.left = 4;
-  if (++g.ctr[0] == 0) ++g.ctr[1];
-}
-__device__ inline Philox philox_init(uint64_t seed, uint32_t env, uint32_t episode) {
-  Philox g;
-  g.key[0] = (uint32_t)seed; g.key[1] = (uint32_t)(seed >> 32) ^ (env * 0x9E3779B1u + 0x7F4A7C15u);
-  g.ctr[0] = 0; g.ctr[1] = 0; g.ctr[2] = episode; g.ctr[3] = env;
-  g.left = 0;
-  return g;
-}
-__device__ inline uint32_t rng_u32(Philox& g) {
-  if (g.left == 0) philox_refill(g);
-  return g.out[--g.left];
-}
-__device__ inline double rng_double(Philox& g) {     // [0,1) with 53 random bits (numpy's construction)
-  const uint32_t a = rng_u32(g) >> 5, b = rng_u32(g) >> 6;
-  return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-}
-__device__ inline double rng_uniform(Philox& g, double lo, double hi) { return lo + (hi - lo) * rng_double(g); }
-__device__ inline int rng_below(Philox& g, int n) { return (int)(((uint64_t)rng_u32(g) * (uint64_t)n) >> 32); }
-__device__ inline double rng_normal(Philox& g, double loc, double scale) {   // Box-Muller
-  const double u1 = 1.0 - rng_double(g), u2 = rng_double(g);
-  return loc + scale * sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-}
-// Stream of one dynamic object's domain-randomisation draws: same key as the env's reset stream, counter space
-// disjoint from it (word 1 carries a tag + the dynamic slot, word 0 the event: creation or the step of a finish_walk).
-__device__ inline Philox philox_object(uint64_t seed, uint32_t env, uint32_t episode, uint32_t slot, uint32_t event) {
-  Philox g = philox_init(seed, env, episode);
-  g.ctr[0] = event; g.ctr[1] = 0x4F424A00u + slot;
-  return g;
-}
-#define DT_OBJ_EVENT_CREATE 0xFFFFFFFFu
+// ---- device-side reset sampler (dtsim_reset_sampler): its generator, draw functions and counter layout are philox_rng.h
 
 // objects.py:384-431 DuckieObj.step.  The reference draws a DuckieObj's domain-randomised parameters from the
 // unseeded global np.random (objects.py:349-350, 424-427), so there is no stream to reproduce: on the host path they
@@ -387,7 +338,7 @@ __device__ inline void duckie_step(const SimArrays& A, const DynInit& di, int d,
     A.ob_angle[ix] = ang;
     A.ob_active[ix] = 0;
     if (rs != nullptr && rs->domain_rand) {
-      Philox g = philox_object(rs->seed, (uint32_t)e, (uint32_t)A.episode[e], (uint32_t)d, (uint32_t)step_count);
+      Philox g = philox_object(rs->seed, (uint32_t)e, (uint32_t)A.episode[e], (uint32_t)d, DT_OBJ_EVENT_WALK(step_count));
       const double mag = fabs(rng_normal(g, 0.02, 0.005));
       A.ob_vel[ix] = vel > 0 ? -mag : (vel < 0 ? mag : -0.0 * mag);   // -1 * np.sign(vel) * |N|
       A.ob_wait[ix] = (double)(3 + rng_below(g, 17));
@@ -759,7 +710,7 @@ __device__ inline int sampler_next_map(const dtsim_reset_sampler& rs, int n_maps
   if (rs.map_cycle == 1) return (cur + 1) % n_maps;
   if (rs.map_cycle == 2) {
     Philox g = philox_init(rs.seed, (uint32_t)e, (uint32_t)episode);
-    g.ctr[1] = 0x4D415000u;
+    g.ctr[1] = DT_RNG_TAG_MAP;
     return rng_below(g, n_maps);
   }
   return cur;

@@ -1,6 +1,7 @@
 """GPU: device-side reset sampler.  Same distributions and acceptance test as the
 reference's reset() (simulator.py:546-738), different RNG stream (Philox): checked through the properties
-the reference's reset guarantees, not through RNG-order parity (tests/test_gpu_physics.py covers that mode)."""
+the reference's reset guarantees, not through RNG-order parity (tests/test_gpu_physics.py covers that mode).  The
+device's own stream is held draw for draw to a numpy model of it in tests/test_gpu_reset_sampler.py."""
 import numpy as np
 import pytest
 
