@@ -407,6 +407,17 @@ void k_raster_v3dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* 
   }
 }
 
+// The pixel centre of an exact-path entry in padded quad coordinates, as q8_rec256 / quad_weights8 take it (cell and fraction inside the SAMPLE's
+// tile).  Inside the padded grid: itself.  Past it -- a sample on the last tiles of a grid whose border lies metres away, the centre of its pixel
+// further out than the DT_QRING ring: one image row under the horizon -- wrapped by whole tiles, as GL_REPEAT wraps the texture coordinate that GL
+// extrapolates to the centre (a clamp to the ring's edge put the border's cell there: 43 pixels of a row off by 28 - 37 at a border 9 m away).
+// nan, or too far for a fraction to be left: lo.
+__device__ inline float dr_centre_wrap(float u, float lo, float hi) {
+  if (u >= lo && u <= hi) return u;
+  if (!(fabsf(u) < 4194304.f)) return lo;
+  return u - 256.f * floorf(u * (1.f / 256.f)) + 256.f;
+}
+
 // ---- k_resolve_dr: the exact path of the plane-edge pixels k_raster_v3dr queues (round 5) -----------------------------
 // Replaces the generic k_resolve behind k_raster_v3dr: same work items (one per 8 queue batches of a raster workgroup, persistent
 // wavefronts, static first grab), but a pixel is resolved the way resolve_region_v3 (render_v3.inc) resolves one for the shared camera --
@@ -487,7 +498,7 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
         const bool c_down = den_c > 0.f;
         const float inv_c = c_down ? frcp(den_c) : 0.f;
         const float Xu = fmaf(inv_c, fmaf(nx, hx0, fmaf(ny, hx1, hx2)), Cx), Zu = fmaf(inv_c, fmaf(nx, hz0, fmaf(ny, hz1, hz2)), Cz);
-        const uint32_t xic = q8_bits(med3f(Xu, lo, Xhi)), zic = q8_bits(med3f(Zu, lo, Zhi));   // the centre's snapped coordinates (q8_rec256 works on these bits)
+        const uint32_t xic = q8_bits(dr_centre_wrap(Xu, lo, Xhi)), zic = q8_bits(dr_centre_wrap(Zu, lo, Zhi));   // the centre's snapped coordinates (q8_rec256 works on these bits)
         const uint32_t W8 = quad_weights8(q8_frac(xic), q8_frac(zic), Q8_LIT);   // unlit byte weights (sum 256): the light is applied per channel below
         uint32_t aS[3] = {0u, 0u, 0u};
         int n_sky = 0, n_gnd = 0;

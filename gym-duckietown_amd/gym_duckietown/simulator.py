@@ -176,8 +176,11 @@ class Simulator(_EnvBase):
         except KeyError as e:
             raise InvalidMapException("Cannot load map data", map_name=map_name) from e
         except Exception as e:
-            # every resident map's tables are staged into LDS by k_step (60 KB budget, dtsim_set_maps: DTSIM_E_LIMIT), and more
-            # than 4 maps leave the quad-record rasters for the generic ones (slower, same frames): say so where it happens
+            # every resident map's tables are staged into LDS by k_step (60 KB budget, dtsim_set_maps: DTSIM_E_LIMIT): say so where
+            # it happens.  (More than 4 maps, or a map beyond 24 x 16 tiles, fit and render, on other rasters -- dt_raster_pipe: the
+            # shared camera goes from k_raster_v3 to k_raster_q, the older quad-record raster, same records and filter; domain
+            # randomisation and per-env cameras from k_raster_v3dr to the generic per-env raster, slower and with llvmpipe's texture
+            # filter instead of the byte-weight one.)
             from dtsim import _ffi
             if self.randomize_maps_on_reset and getattr(e, "code", None) == _ffi.E_LIMIT:
                 raise ValueError(f"randomize_maps_on_reset: the {len(maps_arg)} maps do not fit the library's resident-map budget ({e}); "

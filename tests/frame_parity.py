@@ -58,6 +58,25 @@ FACADE_OVERLAY = Tol(None, 3e-3, 0.1)        # draw_curve / enable_leds frames
 FACADE_BBOX = Tol(None, 1e-2, 0.3)           # draw_bbox view (the lines are drawn over the meshes: no depth test against them)
 
 
+# one HIP raster against another on the same batch:
+class PairTol(NamedTuple):
+    """Upper bounds (<=) on the fraction of pixels that differ at all, and that differ by more than 1."""
+    differ: float
+    gt1: float
+
+
+Q_VS_V3 = PairTol(2e-3, 1e-5)                # "k_raster_q against k_raster_v3": same records, same snapped coordinates, same byte-weight filter; the exact
+#                                              paths differ in form, which may move a rounding tie on a queued pixel
+
+
+def assert_pair(a, b, tol, ctx=None):
+    """Frames a against b (uint8, same shape) within PairTol `tol`; returns (fraction that differ, fraction beyond 1, the largest difference)."""
+    d = np.abs(a.astype(np.int32) - b.astype(np.int32)).max(axis=-1)
+    out = (float((d > 0).mean()), float((d > 1).mean()), int(d.max()))
+    assert out[0] <= tol.differ and out[1] <= tol.gt1, (ctx, out)
+    return out
+
+
 class ObjTol(NamedTuple):
     """The bounds of compare_objects: `frame` on the whole frame; of an object's interior pixels at most obj_share of them + obj_slack
     beyond +-2; of the pixels away from every object at most outside_gt2 x W x H beyond +-2."""

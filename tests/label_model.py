@@ -113,6 +113,19 @@ def tile_class_at(sc, tiles, wx, wz):
     return out
 
 
+def world_hit(cam, depth, tile, q):
+    """World (x, z) [H, W] of sample q's hit on the tile plane, rebuilt in float64 from the sample's depth and ray; the camera's own (x, z) where
+    `tile` (the sample's surface is the tile plane) is False."""
+    cols, rows = np.meshgrid(np.arange(cam.W, dtype=np.float64), np.arange(cam.H, dtype=np.float64))
+    ox, oy = raster.SAMPLE_OFFSETS[q]
+    nx = 2 * (cols + 0.5) / cam.W - 1 + 2 * ox / cam.W
+    ny = 1 - 2 * (rows + 0.5) / cam.H - 2 * oy / cam.H
+    xe, ye, yla, fwd = raster._rays(cam, nx, ny)
+    t = np.where(tile, depth, 0.0)
+    rr, ff = t * xe, t * fwd
+    return cam.C[0] + rr * cam.sa + ff * cam.ca, cam.C[2] + rr * cam.ca - ff * cam.sa
+
+
 def sample_classes(name, e, nudge=False, tables=None):
     """(cls [4, H, W] the class of every sample's surface, same [4, H, W] bool: the 3 x 3 texel neighbourhood of a tile sample holds one
     class; True for the other surfaces).  tables: (tile kind -> classes, object -> class) in place of host_tables(name)."""
@@ -120,18 +133,12 @@ def sample_classes(name, e, nudge=False, tables=None):
     tiles, obj_cls = host_tables(name) if tables is None else tables
     cam = dm.host_camera(case, e, nudge)
     depths, srf = host_buffers(name, e, nudge)
-    cols, rows = np.meshgrid(np.arange(cam.W, dtype=np.float64), np.arange(cam.H, dtype=np.float64))
     cls = np.empty(srf.shape, np.int64)
     same = np.ones(srf.shape, bool)
     texel = sc.m.tile_size / max(t.shape[0] for t in tiles.values())
-    for q, (ox, oy) in enumerate(raster.SAMPLE_OFFSETS):
-        nx = 2 * (cols + 0.5) / cam.W - 1 + 2 * ox / cam.W
-        ny = 1 - 2 * (rows + 0.5) / cam.H - 2 * oy / cam.H
-        xe, ye, yla, fwd = raster._rays(cam, nx, ny)
+    for q in range(len(raster.SAMPLE_OFFSETS)):
         tile = srf[q] == -1
-        t = np.where(tile, depths[q], 0.0)
-        rr, ff = t * xe, t * fwd
-        wx, wz = cam.C[0] + rr * cam.sa + ff * cam.ca, cam.C[2] + rr * cam.ca - ff * cam.sa
+        wx, wz = world_hit(cam, depths[q], tile, q)
         c = tile_class_at(sc, tiles, wx, wz)
         ok = np.ones(tile.shape, bool)
         for dx in (-texel, 0.0, texel):

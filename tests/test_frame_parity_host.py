@@ -135,3 +135,17 @@ def test_tighter_divides_every_bound():
     t = P.tighter(P.ORACLE_OBJECTS, 4)
     assert t == P.ObjTol(P.Tol(5e-4, 2.5e-4, 0.0075), 0.0125, 0.5, 1.25e-4)
     assert P.tighter(P.ORACLE_MESH_GT1, 2) == P.Tol(1e-3, None, 0.015)
+
+
+def test_the_raster_pair_row_bites_at_its_bounds():
+    """Q_VS_V3 on 10000 pixels: 20 may differ, none by more than 1."""
+    assert P.Q_VS_V3 == P.PairTol(2e-3, 1e-5)
+    a = np.zeros((H, W, 3), np.uint8)
+    b = a.copy(); b.reshape(-1, 3)[:20, 1] = 1
+    assert P.assert_pair(a, b, P.Q_VS_V3) == (20 / (H * W), 0.0, 1)
+    c = a.copy(); c.reshape(-1, 3)[:21, 1] = 1
+    with pytest.raises(AssertionError):
+        P.assert_pair(a, c, P.Q_VS_V3, "one too many")
+    d = a.copy(); d[0, 0, 2] = 2
+    with pytest.raises(AssertionError):
+        P.assert_pair(a, d, P.Q_VS_V3, "one pixel beyond 1")

@@ -55,10 +55,16 @@ def oracle_mode(sim, segment=False):
     csrc/render.hip dt_raster_pipe): the quad-record kernels filter tile textures with byte weights -- the lit factor folded into them on
     the shared-camera path ("pixel": k_raster_v3 / k_raster_q), applied per channel afterwards on the per-env path ("pixel-dr":
     k_raster_v3dr, domain randomisation or per_env_camera) -- and the generic raster (segment view, widths that are not a multiple of 4,
-    per-env cameras over tile textures that are not 256 x 256) with llvmpipe's own arithmetic ("pixel-gl")."""
+    per-env cameras over tile textures that are not 256 x 256) with llvmpipe's own arithmetic ("pixel-gl").
+    The answer comes from the handle's configuration, so a raster that quietly fell back still fails its test.  One fall is the dispatch's own:
+    per-env cameras over more than four maps, or over a padded grid beyond 24 x 32 tiles, leave k_raster_v3dr for the generic raster.  Only on
+    such a handle, and once a pass has run, the raster of that pass (sim.render_pipeline) turns "pixel-dr" into "pixel-gl"."""
     side = sim.textures[0].shape[0] if sim.textures else 256
     quad_ok = sim.camera_width % 4 == 0 and not segment
     if sim.domain_rand or sim.per_env_camera:
         v3dr = quad_ok and side == 256 and os.environ.get("DTSIM_RASTER_OLD", "0") != "1"   # (the A/B switch that keeps k_raster_q also keeps the generic per-env raster)
+        past_v3 = len(sim.maps) > 4 or any(m.grid_h + 8 > 24 or m.grid_w + 8 > 32 for m in sim.maps)
+        if v3dr and past_v3 and (sim.render_pipeline or "").split("+")[0] in ("k_raster_env", "k_raster"):
+            v3dr = False
         return "pixel-dr" if v3dr else "pixel-gl"
     return "pixel" if quad_ok else "pixel-gl"
