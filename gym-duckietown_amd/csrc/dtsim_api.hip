@@ -773,7 +773,34 @@ static int labels_run(dtsim_t* h, const char* who, uint8_t* out, int oh, int ow,
   if (int rc = map_pass_check(h, who, out, oh, ow, flags, 0u, masked, mask)) return rc;
   if (!h->d_texel_class || !h->d_mesh_class) return fail(DTSIM_E_STATE, "%s before dtsim_set_label_assets", who);
   HIPCHK(hipSetDevice(h->cfg.device));
-  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, out, oh, ow, mask);
+  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, out, nullptr, oh, ow, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+// The shared body of dtsim_instances / dtsim_instances_masked: depth's checks; the label tables only when a label map is asked for too.
+static int instances_run(dtsim_t* h, const char* who, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+  if (int rc = map_pass_check(h, who, inst, oh, ow, flags, 0u, masked, mask)) return rc;
+  if (labels && (!h->d_texel_class || !h->d_mesh_class)) return fail(DTSIM_E_STATE, "%s with a label map before dtsim_set_label_assets", who);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, labels, inst, oh, ow, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags) {
+  return instances_run(h, "dtsim_instances", inst, labels, oh, ow, flags, false, nullptr);
+}
+int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return instances_run(h, "dtsim_instances_masked", inst, labels, oh, ow, flags, true, mask);
+}
+
+int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask) {
+  if (!h || !inst || !out) return fail(DTSIM_E_INVALID, "dtsim_boxes: null argument");
+  if (flags) return fail(DTSIM_E_INVALID, "dtsim_boxes: unknown flags 0x%x", flags);
+  if (oh <= 0 || ow <= 0 || (int64_t)oh * ow > INT32_MAX) return fail(DTSIM_E_INVALID, "dtsim_boxes: a %d x %d map", ow, oh);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  dt_launch_boxes(h->stream, h->N, inst, oh, ow, out, mask);
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }

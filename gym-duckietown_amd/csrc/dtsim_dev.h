@@ -167,9 +167,11 @@ void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d
 // env): the rows of the other envs are not written.  The caller checked that oh divides H and ow divides W.
 void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask);
 // the label maps of dtsim_labels (render.hip k_labels): out = [N][oh][ow] bytes, sized, sampled and masked as dt_launch_depth's; texel_class:
-// one byte per texel in the layout of R.texels (dt_pack_label_tables), mesh_class: [n_mesh_class] bytes
+// one byte per texel in the layout of R.texels (dt_pack_label_tables), mesh_class: [n_mesh_class] bytes.  inst: the instance map of
+// dtsim_instances, same shape, written in the same launch from the same classification.  Either of out / inst may be null (the tables are
+// read only with out); they must not overlap.
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
-                      int oh, int ow, const uint8_t* mask);
+                      uint8_t* inst, int oh, int ow, const uint8_t* mask);
 // camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
 // envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
 void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,
@@ -183,6 +185,9 @@ void dt_fill_pack_remap(int W, int H, int n_cal, float* rx, float* ry, const int
 void dt_launch_observe(hipStream_t s, const ObservePlan& plan, const ObserveParams& P, const uint8_t* mask = nullptr);
 // row e of src -> row e of dst (row_bytes each) for every e < N with mask[e] != 0 (device pointers; dtsim_copy_rows)
 void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_t row_bytes, const uint8_t* mask);
+// one box and pixel count per id and env (dtsim_boxes, k_boxes): inst = [N][oh][ow] bytes -> out = [N][DTSIM_MAX_OBJECTS][5] int32; mask:
+// device, [N] bytes, or null = every env.  The caller checked that oh * ow fits an int.
+void dt_launch_boxes(hipStream_t s, int N, const uint8_t* inst, int oh, int ow, int32_t* out, const uint8_t* mask);
 // the observation history (dtsim_obs_push): obs ([N][3][out_h][out_w] uint8) -> the newest slot of stack ([N][depth][3 or 1][out_h][out_w], uint8 or
 // float32), the older slots move one down; first / mask: device, [N] bytes, or null (no env starts anew / every env)
 void dt_launch_obs_push(hipStream_t s, int N, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, bool f32, bool gray,

@@ -423,7 +423,68 @@ __global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ dst, co
   }
 }
 
-// ---- observation history (dtsim_obs_push): stack[e] = [depth][C][oh * ow] slots of T, oldest first; obs[e] = [3][oh * ow] uint8 ----
+// ---- dtsim_boxes: one box and pixel count per id of an [N][oh][ow] byte map -------------------------------------------------------------
+// s_box[k] = x0, y0, x1, y1, n of id k + 1: min / max / add atomics of the workgroup's LDS, integers, so the order of arrival does not show.
+#define BOX_IDS DTSIM_MAX_OBJECTS
+// `len` pixels of `id` in row `row` from column `col` on (one row: the caller cuts a run at the row's end); other ids (0, above BOX_IDS): nothing
+__device__ inline void box_run(int (*s_box)[5], const uint32_t id, const int row, const int col, const int len) {
+  if (id - 1u >= (uint32_t)BOX_IDS || len <= 0) return;
+  int* b = s_box[id - 1u];
+  atomicMin(&b[0], col); atomicMin(&b[1], row); atomicMax(&b[2], col + len); atomicMax(&b[3], row + 1); atomicAdd(&b[4], len);
+}
+
+// One workgroup per env (a masked env's leaves at once, wave-uniformly).  The env's n = oh * ow bytes: the `head` bytes up to the first 16-byte
+// boundary of its address and the bytes after the last whole 16-byte chunk one per lane, the chunks between as one 16-byte load each, chunk c
+// of the workgroup's stride to lane c.  A lane skips an all-zero chunk (one OR), and an all-zero word of another; within its chunk it merges the
+// pixels of one id that follow each other in one row -- (row, col) of the chunk's first pixel by one division, then counted on, so a chunk
+// may span any number of rows (ow < 16) -- into one box_run: five LDS atomics per run, not per pixel.  After the barrier the table goes out as
+// 5 BOX_IDS consecutive ints, the rows of absent ids zeroed.  No global atomics: one map gives one result, bit for bit.
+__global__ __launch_bounds__(256) void k_boxes(const uint8_t* __restrict__ inst, const int oh, const int ow, int32_t* __restrict__ out,
+                                               const uint8_t* __restrict__ mask) {
+  __shared__ int s_box[BOX_IDS][5];
+  const int e = blockIdx.x, tid = threadIdx.x;
+  if (mask && !mask[e]) return;
+  for (int i = tid; i < BOX_IDS; i += 256) { s_box[i][0] = s_box[i][1] = 0x7fffffff; s_box[i][2] = s_box[i][3] = s_box[i][4] = 0; }
+  __syncthreads();
+  const int n = oh * ow;
+  const uint8_t* p = inst + (size_t)e * (size_t)n;
+  const int head = min(n, (int)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u));
+  const int chunks = (n - head) >> 4, tail0 = head + (chunks << 4);
+  if (tid < head) box_run(s_box, p[tid], tid / ow, tid % ow, 1);
+  if (tid < n - tail0) { const int q = tail0 + tid; box_run(s_box, p[q], q / ow, q % ow, 1); }
+  for (int c = tid; c < chunks; c += 256) {
+    const int q0 = head + (c << 4);
+    const uint4 v = *reinterpret_cast<const uint4*>(p + q0);
+    if ((v.x | v.y | v.z | v.w) == 0u) continue;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    int row = q0 / ow, col = q0 - row * ow;
+    uint32_t cur = 0;                                  // the run: `len` pixels of `cur` from (row, start) on
+    int start = 0, len = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (w[k] == 0u) {                                // four empty pixels: close the run, count on
+        box_run(s_box, cur, row, start, len);
+        cur = 0; len = 0;
+        col += 4;
+        while (col >= ow) { col -= ow; ++row; }
+        continue;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t id = (w[k] >> (8 * j)) & 255u;
+        if (id != cur) { box_run(s_box, cur, row, start, len); cur = id; start = col; len = 0; }
+        ++len;
+        if (++col == ow) { box_run(s_box, cur, row, start, len); cur = 0; len = 0; col = 0; ++row; }
+      }
+    }
+    box_run(s_box, cur, row, start, len);
+  }
+  __syncthreads();
+  int32_t* o = out + (size_t)e * (BOX_IDS * 5);
+  for (int i = tid; i < BOX_IDS * 5; i += 256) o[i] = s_box[i / 5][4] ? s_box[i / 5][i % 5] : 0;
+}
+
+// ---- observation history (dtsim_obs_push): stack[e] =[depth][C][oh * ow] slots of T, oldest first; obs[e] = [3][oh * ow] uint8 ----
 // ObsBytes<n>: n consecutive bytes as one access (1, 4 or 16 bytes: byte, dword, four dwords).
 template <int NB> struct ObsBytes;
 template <> struct ObsBytes<1> { using type = uint8_t; };
@@ -579,6 +640,11 @@ void dt_launch_copy_rows(hipStream_t s, int N, void* dst, const void* src, size_
   const int vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | row_bytes) & 15) == 0;
   hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((size_t)N * per_row)), dim3(256), 0, s, static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src),
                      row_bytes, per_row, mask, vec);
+}
+
+void dt_launch_boxes(hipStream_t s, int N, const uint8_t* inst, int oh, int ow, int32_t* out, const uint8_t* mask) {
+  if (N <= 0) return;
+  hipLaunchKernelGGL(k_boxes, dim3((unsigned)N), dim3(256), 0, s, inst, oh, ow, out, mask);
 }
 
 void dt_launch_obs_push(hipStream_t s, int N, void* stack, const uint8_t* obs, int depth, int out_h, int out_w, bool f32, bool gray,

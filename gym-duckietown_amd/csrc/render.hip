@@ -2914,12 +2914,19 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
 // bytes, takes 1.4 x k_depth's time on planes and the same time under meshes, profiles/labels_timing.txt); four pixels per lane would serialise
 // four of those per lane for the sake of one wider store, and a wavefront's 64 byte stores are still one contiguous 64-byte row segment.
 // tex_w, tex_h: the one (power-of-two) size of all tile textures; texel_class: dt_pack_label_tables' pool, addressed like R.texels.
+// LAB / INST (dtsim_labels: <true, false>; dtsim_instances: <false, true>, or <true, true> when it is given a label map too): which of the two
+// maps the launch writes, from the ONE classification of the pixel -- `inst` takes o + 1 of the winning sample's object (the o of
+// scene_samples4<true>: the env's map's object list), DTSIM_INSTANCE_NONE for every other owner and for a pixel without a source; a second
+// byte store at the same offset, as coalesced as the first.  Without LAB the class mapping -- mesh table, tile record, texel gather -- is not
+// compiled, and the plane hits it alone reads are dead.
+static_assert(DTSIM_MAX_OBJECTS <= 255, "an instance id o + 1 must fit the map's byte");
+template <bool LAB, bool INST>
 __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                 const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
                                                 const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
                                                 const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h,
                                                 const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                                uint8_t* __restrict__ out, const uint8_t* __restrict__ mask) {
+                                                uint8_t* __restrict__ out, uint8_t* __restrict__ inst, const uint8_t* __restrict__ mask) {
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
@@ -2941,7 +2948,7 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
     const EnvCam c = cams[e];
     const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
     const MapU m = map_u(rm);
-    uint32_t cls = DTSIM_LABEL_NONE;
+    uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
     if (live) {
       float ds[4];
       Hit hs[4];
@@ -2954,24 +2961,31 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
 #pragma unroll
       for (int q = 1; q < 4; ++q)
         if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; }
-      if (ob >= 0) {
-        const int mid = objs[rm.obj_off + ob].mesh_id;
-        cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
-      } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
-      else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
-      else {
-        const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
-        cls = DTSIM_LABEL_GROUND;                      // a present tile without a texture has no texel table
-        if (tr.flags & 2u) {
-          const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade() takes it
-          float x, y;
-          tile_texel_xy(tr, fx, fz, x, y);
-          const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-          cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+      if constexpr (INST) who = ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE;
+      if constexpr (LAB) {
+        if (ob >= 0) {
+          const int mid = objs[rm.obj_off + ob].mesh_id;
+          cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
+        } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
+        else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
+        else {
+          const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
+          cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
+          if (tr.flags & 2u) {
+            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade() takes it
+            float x, y;
+            tile_texel_xy(tr, fx, fz, x, y);
+            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
+            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+          }
         }
       }
     }
-    if (in) out[(size_t)e * (size_t)n_out + (size_t)pix] = (uint8_t)cls;
+    if (in) {
+      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
+      if constexpr (LAB) out[at] = (uint8_t)cls;
+      if constexpr (INST) inst[at] = (uint8_t)who;
+    }
   }
 }
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
@@ -3083,13 +3097,14 @@ void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, in
 }
 
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
-                      int oh, int ow, const uint8_t* mask) {
-  if (R.N <= 0) return;
+                      uint8_t* inst, int oh, int ow, const uint8_t* mask) {
+  if (R.N <= 0 || (!out && !inst)) return;
   const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  hipLaunchKernelGGL(k_labels, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
+  auto k = out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>;
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
                      reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
-                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, mask);
+                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask);
 }
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {

@@ -798,6 +798,7 @@ class BatchedSimulator:
             parr[i] = a.ctypes.data_as(u8p)
         _ffi.check(self._lib, self._lib.dtsim_set_label_assets(self._h, parr, len(tc), mc.ctypes.data_as(u8p), len(mc)))
         self._have_label_assets = True
+        self._mesh_class = mc.copy()                                # (object_classes())
 
     def labels(self, height=None, width=None, out=None, mask=None):
         """The semantic label map of every env's camera frame, on the device (dtsim_labels, include/dtsim.h): [N, h, w] uint8, per pixel the
@@ -826,6 +827,76 @@ class BatchedSimulator:
             _ffi.check(self._lib, self._lib.dtsim_labels(self._h, ptr, h, w, 0))
         else:
             _ffi.check(self._lib, self._lib.dtsim_labels_masked(self._h, ptr, h, w, 0, mp))
+        return out
+
+    def instances(self, height=None, width=None, out=None, mask=None, labels_out=None):
+        """The instance map of every env's camera frame, on the device (dtsim_instances, include/dtsim.h): [N, h, w] uint8, per pixel o + 1
+        where the nearest of the four MSAA samples of the frame's source pixel (the one that sets depth()'s value; ties: the lowest index) shows
+        mesh object o -- its index in self.maps[map_id[e]].objects, the column of the FIELD_OBJ_* fields -- and 0 on tiles, ground, sky and in
+        the fisheye's black border.  A hidden object's id never appears.  `labels_out` ([N, h, w] uint8, as labels()'s out): the same launch
+        also writes labels()'s bytes into it, from the same classification (the default tables are installed at first use, as labels()
+        does); without it no table is needed.  Needs a preceding render() of the current state.  Size, `out` and `mask` as labels()'s; a bad
+        size, out, labels_out or mask raises ValueError before anything is launched."""
+        import torch
+        h = self.camera_height if height is None else int(height)
+        w = self.camera_width if width is None else int(width)
+        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
+            raise ValueError(f"instances: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
+                             "(instance ids are point-sampled, never filtered)")
+        mp = self._mask_arg(mask)
+        shape = (self.num_envs, h, w)
+        if out is None:
+            if getattr(self, "_inst_key", None) != (h, w):
+                self._inst_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")       # (empty: as depth()'s buffer)
+                self._inst_key = (h, w)
+            out = self._inst_buf
+        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "instances"))
+        lp = None
+        if labels_out is not None:
+            lp = C.c_void_p(self._out_ptr(labels_out, shape, "|u1", 1, "instances: labels_out"))
+            if lp.value == ptr.value:
+                raise ValueError("instances: labels_out and out are one buffer")
+            if not getattr(self, "_have_label_assets", False):
+                self.set_label_assets()
+        if mp is None:
+            _ffi.check(self._lib, self._lib.dtsim_instances(self._h, ptr, lp, h, w, 0))
+        else:
+            _ffi.check(self._lib, self._lib.dtsim_instances_masked(self._h, ptr, lp, h, w, 0, mp))
+        return out
+
+    def boxes(self, inst, out=None, mask=None):
+        """One 2-D box and pixel count per id and env of an id map, on the device (dtsim_boxes, include/dtsim.h): `inst` is any C-contiguous
+        uint8 CUDA tensor [N, h, w] on the handle's device (instances()'s map, or any other); returns [N, MAX_OBJECTS, 5] torch.int32, row k =
+        x0, y0, x1, y1, n of id k + 1 -- n pixels, tightly bounded by columns [x0, x1) and rows [y0, y1) of the map; all 0 when the id is
+        absent.  Stateless and stream-ordered; `out` (such a tensor) and `mask` (as render()'s: the other envs' rows keep every byte) are
+        checked before anything is launched (ValueError)."""
+        import torch
+        self._dev_tensor(inst, "boxes: inst", lead=self.num_envs, dtypes=(torch.uint8,))
+        if inst.dim() != 3 or inst.shape[1] < 1 or inst.shape[2] < 1 or inst.shape[1] * inst.shape[2] >= 2 ** 31:
+            raise ValueError(f"boxes: inst must be [N, h, w] with h, w >= 1 and h * w below 2^31, got shape {tuple(inst.shape)}")
+        mp = self._mask_arg(mask)
+        shape = (self.num_envs, _ffi.MAX_OBJECTS, 5)
+        if out is None:
+            if getattr(self, "_boxes_buf", None) is None:
+                self._boxes_buf = torch.empty(shape, dtype=torch.int32, device=f"cuda:{self.device_index}")      # (empty: as depth()'s buffer)
+            out = self._boxes_buf
+        else:
+            self._dev_tensor(out, "boxes: out", shape=shape, dtypes=(torch.int32,))
+        _ffi.check(self._lib, self._lib.dtsim_boxes(self._h, C.c_void_p(inst.data_ptr()), int(inst.shape[1]), int(inst.shape[2]),
+                                                    C.c_void_p(out.data_ptr()), 0, mp))
+        return out
+
+    def object_classes(self):
+        """[n_maps, MAX_OBJECTS] uint8 (numpy): the class labels() gives each object slot of each resident map -- mesh_class[mesh of object k
+        of map m] under the table installed through set_label_assets(), or the default one (label_assets()) while none is -- and 0 past a
+        map's object count.  A detector's class target for row k of boxes() in env e is object_classes()[map_id[e], k]."""
+        mc = getattr(self, "_mesh_class", None)
+        if mc is None:
+            mc = self.label_assets()[1]
+        out = np.zeros((len(self.maps), _ffi.MAX_OBJECTS), np.uint8)
+        for m, mp in enumerate(self.maps):
+            for k, o in enumerate(mp.objects):
+                out[m, k] = mc[self._mesh_order.index(o.mesh_kind)]
         return out
 
     def copy_rows(self, dst, src, mask):

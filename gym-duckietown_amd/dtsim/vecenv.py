@@ -63,6 +63,17 @@ point-sampled, never filtered) of the state `obs` shows; after `reset()` it is `
 `info["final_labels"]` holds the finished envs' rows as `info["final_depth"]` does.  The pass stands where the depth pass does, after it
 when both are on, and composes with `depth_shape`, `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand`; `motion_blur` and
 `camera_rand` raise ValueError, for depth's reasons.  `label_shape=None` (the default) makes no new call.
+
+Instances and boxes (`instance_shape=(h, w)`, each dividing the camera's size; `boxes=True` needs it): `info["instances"]` is one persistent
+`[N, h, w]` `torch.uint8` device tensor with the instance map (`dtsim_instances`, include/dtsim.h: per pixel o + 1 where the surface that sets
+the depth there is mesh object o of the env's own map -- the column of the `DTSIM_FIELD_OBJ_*` fields --, 0 on every other surface and in the
+fisheye's black border) of the state `obs` shows, and with `boxes=True` `info["boxes"]` one persistent `[N, 64, 5]` `torch.int32` tensor, row k
+= x0, y0, x1, y1, n of object k in that map's pixels (`dtsim_boxes`; all 0 for an object not in view; its class:
+`sim.object_classes()[map_id, k]`).  After `reset()` they are `env.instances` / `env.boxes`, the same tensors.  With `final_obs=True`,
+`info["final_instances"]` / `info["final_boxes"]` hold the finished envs' rows as `info["final_labels"]` does.  The pass stands where the
+depth pass does, after depth and labels; with `label_shape == instance_shape` ONE `dtsim_instances` launch fills both maps from one
+classification and `dtsim_labels` is not called.  `motion_blur` and `camera_rand` raise ValueError, for depth's reasons.
+`instance_shape=None` (the default) makes no new call.
 """
 from __future__ import annotations
 
@@ -79,7 +90,8 @@ class DuckietownVecEnv:
                  chw: bool = True, normalize: bool = True, action_mode: str = "vel_steer", device: int = 0,
                  seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False,
                  motion_blur: Union[bool, Sequence[int]] = False, depth_shape: Optional[Tuple[int, int]] = None,
-                 depth_dtype: str = "float32", label_shape: Optional[Tuple[int, int]] = None, **sim_kwargs):
+                 depth_dtype: str = "float32", label_shape: Optional[Tuple[int, int]] = None,
+                 instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -124,6 +136,26 @@ class DuckietownVecEnv:
             if lh <= 0 or lw <= 0 or H % lh or W % lw:
                 raise ValueError(f"label_shape {(lh, lw)}: each size must divide the camera's {(H, W)} (labels are point-sampled, never filtered)")
             self.label_shape = (lh, lw)
+        self.instance_shape, self._want_boxes = None, bool(boxes)
+        if instance_shape is None:
+            if boxes:
+                raise ValueError("boxes=True needs instance_shape (the boxes are those of the instance map, in its pixels)")
+        else:
+            if self._blur:
+                raise ValueError("instance_shape with motion_blur is not supported (the blurred observation shows the three states of its "
+                                 "window: no single state's instances belong to it)")
+            if sim_kwargs.get("camera_rand"):
+                raise ValueError("instance_shape with camera_rand is not supported (dtsim_instances reads the single distortion table, "
+                                 "camera_rand installs one per env)")
+            try:
+                ih, iw = (int(v) for v in instance_shape)
+            except (TypeError, ValueError):
+                raise ValueError(f"instance_shape must be (h, w), got {instance_shape!r}") from None
+            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
+            if ih <= 0 or iw <= 0 or H % ih or W % iw:
+                raise ValueError(f"instance_shape {(ih, iw)}: each size must divide the camera's {(H, W)} (instance ids are point-sampled, "
+                                 "never filtered)")
+            self.instance_shape = (ih, iw)
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -153,6 +185,15 @@ class DuckietownVecEnv:
             self.labels = torch.zeros((num_envs, *self.label_shape), dtype=torch.uint8, device=self.device)
             if self.final_obs:
                 self._final_labels = torch.zeros_like(self.labels)
+        # info["instances"] / info["boxes"] and their final_ rows: persistent [N, h, w] uint8 / [N, MAX_OBJECTS, 5] int32 tensors
+        self.instances = self.boxes = self._final_instances = self._final_boxes = None
+        if self.instance_shape is not None:
+            self.instances = torch.zeros((num_envs, *self.instance_shape), dtype=torch.uint8, device=self.device)
+            if self._want_boxes:
+                self.boxes = torch.zeros((num_envs, _ffi.MAX_OBJECTS, 5), dtype=torch.int32, device=self.device)
+            if self.final_obs:
+                self._final_instances = torch.zeros_like(self.instances)
+                self._final_boxes = torch.zeros_like(self.boxes) if self._want_boxes else None
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -205,19 +246,28 @@ class DuckietownVecEnv:
         return self._stack.view(self._stack_shape)
 
     def _depth_pass(self, mask=None):
-        """depth_shape / label_shape: the depth, then the labels, of the state the last render() showed, into self.depth / self.labels
-        (`mask`: only those envs' rows)."""
+        """depth_shape / label_shape / instance_shape: the depth, then the labels, then the instances and their boxes, of the state the last
+        render() showed, into self.depth / self.labels / self.instances / self.boxes (`mask`: only those envs' rows).  Labels and instances
+        of one shape come from one launch."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
-        if self.labels is not None:
+        fused = self.labels is not None and self.label_shape == self.instance_shape
+        if self.labels is not None and not fused:
             self.sim.labels(self.label_shape[0], self.label_shape[1], out=self.labels, mask=mask)
+        if self.instances is not None:
+            self.sim.instances(self.instance_shape[0], self.instance_shape[1], out=self.instances, mask=mask,
+                               labels_out=self.labels if fused else None)
+            if self.boxes is not None:
+                self.sim.boxes(self.instances, out=self.boxes, mask=mask)
 
     def _keep_final(self, obs, done, info):
-        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map and of the label map, before the
-        reset rewrites them."""
+        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map, the label map, the instance map
+        and the boxes, before the reset rewrites them."""
         src = self._stack if self._stacked else obs
         if self._final is None:
-            self._final = self.torch.empty_like(src)
+            # (zeros, once, on our stream: the rows of envs that have not finished yet hold no stale memory -- two envs run alike then
+            # return the same bytes in EVERY row, whatever the allocator handed out; as the depth / label / instance buffers)
+            self._final = self.torch.zeros_like(src)
         self.sim.copy_rows(self._final, src, done)
         info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape) if self._stacked else self._final, done
         if self.depth is not None:
@@ -226,6 +276,12 @@ class DuckietownVecEnv:
         if self.labels is not None:
             self.sim.copy_rows(self._final_labels, self.labels, done)
             info["final_labels"] = self._final_labels
+        if self.instances is not None:
+            self.sim.copy_rows(self._final_instances, self.instances, done)
+            info["final_instances"] = self._final_instances
+        if self.boxes is not None:
+            self.sim.copy_rows(self._final_boxes, self.boxes, done)
+            info["final_boxes"] = self._final_boxes
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -309,6 +365,10 @@ class DuckietownVecEnv:
                 info["depth"] = self.depth
             if self.labels is not None:
                 info["labels"] = self.labels
+            if self.instances is not None:
+                info["instances"] = self.instances
+            if self.boxes is not None:
+                info["boxes"] = self.boxes
         self._leave()
         return obs, reward, done, info
 

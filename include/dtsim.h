@@ -584,6 +584,39 @@ enum { DTSIM_LABEL_NONE = 0, DTSIM_LABEL_SKY = 1, DTSIM_LABEL_GROUND = 2,
 int dtsim_set_label_assets(dtsim_t* h, const uint8_t* const* texel_class, int n_textures, const uint8_t* mesh_class, int n_meshes);
 int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags);
 int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
+/* The instance map of every camera frame, on the device: WHICH OBJECT a pixel shows, beside the class the label map gives -- the ground
+ * truth of detection (the label map says "duckie", not which one; connected components of it merge duckies that touch or occlude each other).
+ * THE QUANTITY.  inst[e][i][j], a uint8, names the owner of the sample that sets depth[e][i][j] of dtsim_depth: of the four MSAA samples of
+ * the frame's source pixel, the sample with the smallest eye depth.
+ *   - Ties go to the lowest sample index.
+ *   - A sky sample counts as +inf: it wins only if all four are sky.
+ *   - Within a sample a mesh owns it only where its z-buffer depth is strictly smaller than the plane's (the colour pass's depth test).
+ * The value is o + 1 where that owner is mesh object o, and DTSIM_INSTANCE_NONE = 0 everywhere else: tile, ground quad, sky, or a pixel the
+ * distortion table leaves without a source.  o is the object's index in the object list of the env's OWN map (dtsim_map.objects in the
+ * order given to dtsim_set_maps): the column of the DTSIM_FIELD_OBJ_* fields, 0 .. DTSIM_MAX_OBJECTS - 1, so the id fits the byte.  An
+ * invisible object (DTSIM_FIELD_OBJ_VISIBLE = 0) has no triangles in the pass: its id never appears.  Never filtered, never blended.
+ * LABELS.  `labels` may be NULL.  If it is not, it receives exactly the bytes dtsim_labels writes for the same size -- from the same
+ * classification of every pixel, in the same launch -- and the call needs the label tables (else DTSIM_E_STATE); where inst is o + 1 the
+ * label is mesh_class[mesh id of o], where inst is 0 it is a plane's or a texel's class.  inst and labels must not overlap.
+ * SIZE, STATE.  dtsim_depth's, word for word: [num_envs][oh][ow] bytes, cam_height % oh == 0 and cam_width % ow == 0, point-sampled at
+ * camera pixel (i sy + sy / 2, j sx + sx / 2); a colour render of the current state must precede, the same calls invalidate, after
+ * dtsim_render_masked only the masked form with the pass's mask (it writes the selected envs' rows only), per-env distortion tables are
+ * refused.  flags must be 0.  A null handle, inst or mask, a bad size or a nonzero flag return DTSIM_E_INVALID; a failed call launches
+ * nothing and writes nothing.  Asynchronous, stream-ordered.  One state gives the same bytes on every call and for every env index. */
+enum { DTSIM_INSTANCE_NONE = 0 };
+int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags);
+int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, const uint8_t* mask);
+/* One 2-D box and one visible-pixel count per id and env of an id map, on the device: the reduction of dtsim_instances' map to detection
+ * targets.  Pure and stateless: not a post-pass of a render, it reads nothing but `inst`, any [num_envs][oh][ow] uint8 DEVICE map with
+ * oh, ow >= 1 and oh * ow <= INT32_MAX (the size is not tied to the camera's).
+ *   out: DEVICE pointer to [num_envs][DTSIM_MAX_OBJECTS][5] int32.  Row k describes id k + 1: x0, y0, x1, y1, n -- n the number of map
+ *        pixels with that id, [x0, x1) x [y0, y1) their tight bound in map pixel coordinates (column, row); all five 0 when n == 0.
+ *        Id 0 and ids above DTSIM_MAX_OBJECTS are ignored.  The boxes are in the map's own resolution.
+ *   mask: DEVICE pointer to num_envs bytes, or NULL = every env; as dtsim_obs_push: the rows of unselected envs keep every byte.
+ * Integer min / max / sums within one workgroup per env: one map gives one result, bit for bit.  16-byte loads over the part of an env's
+ * bytes that lies between 16-byte boundaries, whatever the base's alignment.  A null handle, inst or out, a non-positive size, a product
+ * beyond int32 or nonzero flags return DTSIM_E_INVALID, and nothing is launched.  Asynchronous, stream-ordered. */
+int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

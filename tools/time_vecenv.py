@@ -11,7 +11,11 @@ LABELS=1: info["labels"] beside the observation (DuckietownVecEnv(label_shape=(1
 VARIANTS=a,b,...: several variants in ONE process, each warmed up, then timed in alternating order (ROUNDS rounds of K steps each, the
 median round is reported); a variant is plain | stack | stack_u8 | gray | gray_u8 | emulate (STACK gives the depth, default 4) | wheels (the plain env with
 action_mode="wheels", the blur's baseline) | blur | blur_rerender | depth | depth_f16 | depth_full | depth_full_f16 | labels | labels_full |
-depth_labels (both maps at 120 x 160)."""
+depth_labels (both maps at 120 x 160) | instances (info["instances"] + info["boxes"] at 120 x 160: dtsim_instances and dtsim_boxes after every
+observe) | instances_full (480 x 640) | instances_only (no boxes) | labels_instances (labels + instances + boxes at 120 x 160: one fused launch
+for the two maps).
+INSTANCES=1 (or full): the whole step with instances and boxes against the plain step in the SAME run -- VARIANTS=plain,instances (or
+plain,instances_full) with ROUNDS=5 unless given."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -27,16 +31,20 @@ MOTION_BLUR = os.environ.get("MOTION_BLUR", "0")
 DEPTH = os.environ.get("DEPTH", "0")
 DEPTH_DTYPE = os.environ.get("DEPTH_DTYPE", "float32")
 LABELS = os.environ.get("LABELS", "0")
+INSTANCES = os.environ.get("INSTANCES", "0")
 MAP = os.environ.get("MAP", "small_loop")
 MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
 K = int(os.environ.get("K", "30"))
 ROUNDS = int(os.environ.get("ROUNDS", "1"))
+if INSTANCES != "0" and not VARIANTS:
+    VARIANTS, ROUNDS = ["plain", "instances_full" if INSTANCES == "full" else "instances"], int(os.environ.get("ROUNDS", "5"))
 a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
-    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0"):
+    def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0", instances="0",
+                 boxes=True):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
@@ -47,6 +55,8 @@ class Variant:
             kw.update(depth_shape=(480, 640) if depth == "full" else (120, 160), depth_dtype=depth_dtype)
         if labels != "0":
             kw.update(label_shape=(480, 640) if labels == "full" else (120, 160))
+        if instances != "0":
+            kw.update(instance_shape=(480, 640) if instances == "full" else (120, 160), boxes=boxes)
         self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -88,6 +98,10 @@ def make(name):
             "depth_full_f16": lambda: Variant("depth 480 x 640 float16", depth="full", depth_dtype="float16"),
             "labels": lambda: Variant("labels 120 x 160", labels="1"), "labels_full": lambda: Variant("labels 480 x 640", labels="full"),
             "depth_labels": lambda: Variant("depth float32 + labels 120 x 160", depth="1", labels="1"),
+            "instances": lambda: Variant("instances + boxes 120 x 160", instances="1"),
+            "instances_full": lambda: Variant("instances + boxes 480 x 640", instances="full"),
+            "instances_only": lambda: Variant("instances 120 x 160, no boxes", instances="1", boxes=False),
+            "labels_instances": lambda: Variant("labels + instances + boxes 120 x 160", labels="1", instances="1"),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
