@@ -107,10 +107,11 @@ struct MapSlot : MapScalars {
   DevPtr<ObjInstDev> d_robjs;
   DevPtr<uint8_t> d_qtex;             // quad-layout blocks for k_raster_q
   DevPtr<uint32_t> d_qtiles;
+  DevPtr<double> d_ocorners;          // dt_pack_object_corners: the objects' collision rectangles, in d_robjs' order (dtsim_bev)
   DevPtr<char> d_obj[DT_SLABS];       // DT_SLAB_STRIS .. DT_SLAB_OBJMASK of the render scratch (dt_render_layout): only with mesh objects
   void release_render() {
     renderable = false;
-    d_rmaps.reset(); d_rtiles.reset(); d_tilerecs.reset(); d_robjs.reset(); d_qtex.reset(); d_qtiles.reset();
+    d_rmaps.reset(); d_rtiles.reset(); d_tilerecs.reset(); d_robjs.reset(); d_qtex.reset(); d_qtiles.reset(); d_ocorners.reset();
     for (auto& p : d_obj) p.reset();
   }
 };
@@ -410,6 +411,7 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   HIPCHK(dev_upload(next.d_tilerecs, T.trecs.data(), T.trecs.size(), 1));
   HIPCHK(dev_upload(next.d_qtex, reinterpret_cast<const uint8_t*>(T.qblocks.data()), T.qblocks.size() * 4));
   HIPCHK(dev_upload(next.d_qtiles, T.qtiles.data(), T.qtiles.size()));
+  HIPCHK(dev_upload(next.d_ocorners, T.ocorners.data(), T.ocorners.size(), 8));
   size_t bytes[DT_SLABS]; dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, T.max_tris, bytes);
   for (int i = DT_SLAB_STRIS; i <= DT_SLAB_OBJMASK; ++i)     // the object slabs: only with mesh objects
     if (bytes[i] && (h->cfg.flags & DTSIM_F_RENDER)) HIPCHK(dev_alloc(next.d_obj[i], bytes[i]));
@@ -801,6 +803,28 @@ int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, u
   if (oh <= 0 || ow <= 0 || (int64_t)oh * ow > INT32_MAX) return fail(DTSIM_E_INVALID, "dtsim_boxes: a %d x %d map", ow, oh);
   HIPCHK(hipSetDevice(h->cfg.device));
   dt_launch_boxes(h->stream, h->N, inst, oh, ow, out, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind, uint32_t flags, const uint8_t* mask) {
+  if (!h || (!cls && !inst)) return fail(DTSIM_E_INVALID, "dtsim_bev: null argument");
+  if (cls == inst) return fail(DTSIM_E_INVALID, "dtsim_bev: cls and inst are one buffer");
+  if (flags) return fail(DTSIM_E_INVALID, "dtsim_bev: unknown flags 0x%x", flags);
+  if (oh < 1 || ow < 1 || oh > DTSIM_BEV_MAX_SIDE || ow > DTSIM_BEV_MAX_SIDE)
+    return fail(DTSIM_E_INVALID, "dtsim_bev: a %d x %d map (each size 1 .. %d)", ow, oh, DTSIM_BEV_MAX_SIDE);
+  if (!std::isfinite(cell) || !(cell > 0.0)) return fail(DTSIM_E_INVALID, "dtsim_bev: cell %g (metres per cell: finite, > 0)", cell);
+  if (rows_behind < 0 || rows_behind > oh) return fail(DTSIM_E_INVALID, "dtsim_bev: rows_behind %d outside [0, %d]", rows_behind, oh);
+  // the render tables: the tile records, the object instances and the texel pool the class pool mirrors (no pass of the raster is needed)
+  if (!h->frames || !h->have_maps || !h->maps.renderable || !h->maps.d_rmaps || !h->maps.d_tilerecs || !h->maps.d_robjs || !h->maps.d_ocorners)
+    return fail(DTSIM_E_INVALID, "dtsim_bev: the handle holds no render tables (DTSIM_F_RENDER, dtsim_set_assets, then dtsim_set_maps)");
+  if (cls && (!h->d_texel_class || !h->d_mesh_class)) return fail(DTSIM_E_INVALID, "dtsim_bev with a class map before dtsim_set_label_assets");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  RenderParams R{};
+  R.N = h->N;
+  render_scene(h, false, &R);
+  dt_launch_bev(h->stream, R, h->A, h->maps.d_ocorners.get(), h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, cls, inst, oh, ow, cell,
+                rows_behind, mask);
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }

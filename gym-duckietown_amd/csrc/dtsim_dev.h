@@ -172,6 +172,13 @@ void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, in
 // read only with out); they must not overlap.
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
                       uint8_t* inst, int oh, int ow, const uint8_t* mask);
+// the bird's-eye maps of dtsim_bev (render.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
+// rows_behind of the oh rows behind the agent.  Of R only the scene of render_scene is read (maps, tile_recs, n_tile_recs, objs, tex_w, tex_h, n_maps) and
+// N: no camera, no table of a pass.  ocorners: dt_pack_object_corners' table; texel_class / mesh_class as dt_launch_labels' (read only with
+// cls); mask: device, [N] bytes, or null = every env.  The caller checked the sizes (1 .. DTSIM_BEV_MAX_SIDE) and cell (finite, > 0).
+void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
+                   const uint8_t* mesh_class, int n_mesh_class, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind,
+                   const uint8_t* mask);
 // camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
 // envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
 void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,

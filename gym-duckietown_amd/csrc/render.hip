@@ -2988,6 +2988,167 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
     }
   }
 }
+// ---- k_bev: the egocentric bird's-eye label map of every env (dtsim_bev; the quantity: include/dtsim.h) ------------------------------------
+// The grid of k_depth / k_labels: cell blocks x env chunks of DEPTH_ENVS.  A thread owns ONE cell; its place in the agent's frame -- f cells
+// ahead, s cells to the right, both multiples of one half and exact in float32 -- does not depend on the env and is computed once.  The env
+// loop is ONE copy of its body (tests/test_gpu_bev.py holds envs e, e + 64 and e + 128 to the same bytes), and a wavefront's 64 byte stores
+// are one contiguous segment of one env's map.
+// Per (workgroup, env), once, by the first wavefront.  Before the loop its lane l takes env e0 + l of the chunk: the pose in double, sincos of
+// the double angle in double (cur_angle is unbounded: a float32 of it would lose the direction), kept in LDS in double for the objects and
+// rounded to float32 for the cells, beside what a cell needs of the env's map (the map id clamped as k_depth clamps it) -- one chain of load
+// latencies and one sincos for the chunk, not one per env (measured: profiles/bev_timing.txt).  The tile records of all maps (at most
+// DTSIM_LDS_TILES of 32 bytes) are staged in dynamic LDS as well: a cell's iteration is a chain of dependent reads -- its env, its tile's
+// record, its texel's class -- and with 64 envs in series per thread the pass is bound by that chain's latency, not by its stores.
+// In the loop, for an env whose map has objects, lane o brings object o into the agent's frame -- a BevRect: the centre of its collision
+// rectangle and the two half-axes u, v in cell units, kept as the dual pair (A, B) with P - centre = a u + b v, a = (P - centre) . A,
+// b = (P - centre) . B, so that the cell's test is |a| <= 1 and |b| <= 1 -- from the packed corners of a static object (ocorners) or the env's
+// current SimArrays::ob_corners of a dynamic one.  Hidden objects, objects without a mesh and objects whose bounding circle misses the window
+// are dropped and the rest compacted in lane order (ballot + prefix count): the list in LDS is in ascending object index, its length is
+// wave-uniform, and most envs loop over none.  The list is double-buffered in LDS, so one barrier per such env suffices: the first
+// wavefront fills slot (it + 1) & 1 while the others may still read slot it & 1, which is not written again before the next barrier.  An
+// env on a map without objects (workgroup-uniform) meets no barrier and no work of the first wavefront at all.
+// Per cell: the first rectangle of the list that holds the cell gives the class and the id; else the tile under P = (x, z) + f d + s r
+// (float32 from the rounded pose: five roundings, < 1e-5 m below 32 m), found and sampled by k_labels' statements -- floorf(w * its), the tile
+// fraction w * its - tile, tile_texel_xy, floor(x + 0.5) wrapped, the texel_class pool -- so a camera label pixel and a cell that hit one
+// world point name one class.  No camera record, no distortion table, nothing a render pass leaves behind is read.
+struct alignas(16) BevRect { float cf, cs, af, as, bf, bs; uint32_t cls, id; };
+struct alignas(16) BevEnv {                                        // what a cell needs of its env, in LDS:
+  float x, z, dc, ds;                                              // the pose; cell * cos, cell * sin of the angle
+  float its; int tile_off, gw, gh;                                 // its map: 1 / tile size, first tile record, grid size
+  int n_obj, obj_off, pad[2];                                      // ... object count, first object instance
+};
+struct alignas(16) BevPose { double x, z, cs, sn; };               // the same in double: the pose, cos and sin of the angle
+static_assert(DTSIM_MAX_OBJECTS <= 64, "one lane of the first wavefront per object");
+template <bool LAB, bool INST>
+__global__ __launch_bounds__(256) void k_bev(const double* __restrict__ pos_x, const double* __restrict__ pos_z, const double* __restrict__ angle,
+                                             const int32_t* __restrict__ map_id, const double* __restrict__ ob_corners,
+                                             const uint8_t* __restrict__ ob_visible, const RenderMapDev* __restrict__ maps,
+                                             const TileLds* __restrict__ tiles, const ObjInstDev* __restrict__ objs, const double* __restrict__ ocorners,
+                                             const uint8_t* __restrict__ texel_class, const uint8_t* __restrict__ mesh_class, const int n_mesh_class,
+                                             const int tex_w, const int tex_h, const int n_maps, const int n_tile_recs, const int N, const int oh,
+                                             const int ow, const double cell, const int rows_behind, uint8_t* __restrict__ out, uint8_t* __restrict__ inst,
+                                             const uint8_t* __restrict__ mask) {
+  __shared__ BevRect s_rect[2][DTSIM_MAX_OBJECTS];
+  __shared__ int s_n[2];
+  __shared__ BevEnv s_env[DEPTH_ENVS];
+  __shared__ BevPose s_pose[DEPTH_ENVS];
+  extern __shared__ __align__(16) unsigned char s_bev_dyn[];          // [n_tile_recs] TileLds: the tile records of all maps
+  TileLds* s_tiles = reinterpret_cast<TileLds*>(s_bev_dyn);
+  const int n_out = oh * ow;
+  const int tid = threadIdx.x;
+  const int pix = blockIdx.x * 256 + tid;
+  const bool in = pix < n_out;
+  const int i = in ? pix / ow : 0, j = in ? pix - i * ow : 0;
+  const float f = (float)(oh - rows_behind - i) - 0.5f;               // cells ahead of the agent (row 0 is the farthest)
+  const float sd = ((float)j + 0.5f) - 0.5f * (float)ow;              // cells to its right (column 0 is the leftmost)
+  // the window in cell units, for the cull
+  const double f_lo = -(double)rows_behind, f_hi = (double)(oh - rows_behind), s_hi = 0.5 * (double)ow;
+  const double inv_cell = 1.0 / cell;
+  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+  static_assert(DEPTH_ENVS <= 64, "one lane of the first wavefront per env of the chunk");
+  for (int t = tid; t < n_tile_recs; t += 256) s_tiles[t] = tiles[t];
+  if (tid < DEPTH_ENVS && e0 + tid < e1) {
+    BevPose p;
+    p.x = pos_x[e0 + tid]; p.z = pos_z[e0 + tid];
+    sincos(angle[e0 + tid], &p.sn, &p.cs);
+    s_pose[tid] = p;
+    const RenderMapDev rm = maps[min((unsigned)map_id[e0 + tid], (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
+    BevEnv ev{};
+    ev.x = (float)p.x; ev.z = (float)p.z; ev.dc = (float)(cell * p.cs); ev.ds = (float)(cell * p.sn);
+    ev.its = rm.inv_tile_size; ev.tile_off = rm.tile_off; ev.gw = rm.grid_w; ev.gh = rm.grid_h;
+    ev.n_obj = min(rm.n_obj, DTSIM_MAX_OBJECTS); ev.obj_off = rm.obj_off;
+    s_env[tid] = ev;
+  }
+  __syncthreads();
+  int it = 0;
+#pragma clang loop unroll(disable)
+  for (int e = e0; e < e1; ++e) {
+    if (mask && !mask[e]) continue;                    // (workgroup-uniform) the masked call: this env's row keeps its bytes
+    const BevEnv ev = s_env[e - e0];
+    const int n_obj = __builtin_amdgcn_readfirstlane(ev.n_obj), obj_off = __builtin_amdgcn_readfirstlane(ev.obj_off);
+    const int b = it & 1;
+    int n_rect = 0;
+    if (n_obj > 0) {                                   // (workgroup-uniform)
+      ++it;
+      if (tid < 64) {
+        const BevPose p = s_pose[e - e0];
+        const double x = p.x, z = p.z, sn = p.sn, cs = p.cs;
+        bool keep = false;
+        BevRect r{};
+        if (tid < n_obj) {
+          const ObjInstDev oi = objs[obj_off + tid];
+          if (oi.mesh_id >= 0 && ob_visible[(size_t)tid * N + e]) {
+            double c[8];
+            if (oi.dyn_slot >= 0) {
+              const int d = min(oi.dyn_slot, DTSIM_MAX_DYNAMIC - 1);
+#pragma unroll
+              for (int k = 0; k < 8; ++k) c[k] = ob_corners[(size_t)(k * DTSIM_MAX_DYNAMIC + d) * N + e];
+            } else {
+#pragma unroll
+              for (int k = 0; k < 8; ++k) c[k] = ocorners[(size_t)(obj_off + tid) * 8 + k];
+            }
+            // corners 0, 1, 3 in the agent's frame, cell units: ahead = (c - pos) . d, right = (c - pos) . r, d = (cos, -sin), r = (sin, cos)
+            double pf[3], ps[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              const int q = k == 2 ? 3 : k;
+              const double dx = c[2 * q] - x, dz = c[2 * q + 1] - z;
+              pf[k] = (dx * cs - dz * sn) * inv_cell; ps[k] = (dx * sn + dz * cs) * inv_cell;
+            }
+            const double uf = 0.5 * (pf[1] - pf[0]), us = 0.5 * (ps[1] - ps[0]), vf = 0.5 * (pf[2] - pf[0]), vs = 0.5 * (ps[2] - ps[0]);
+            const double cf = pf[0] + uf + vf, cs_ = ps[0] + us + vs;
+            const double det = uf * vs - us * vf;
+            const double rad = sqrt(fmax((uf + vf) * (uf + vf) + (us + vs) * (us + vs), (uf - vf) * (uf - vf) + (us - vs) * (us - vs))) + 1.0;
+            const double df = fmax(fmax(f_lo - cf, cf - f_hi), 0.0), dsd = fmax(fabs(cs_) - s_hi, 0.0);
+            keep = det != 0.0 && df * df + dsd * dsd <= rad * rad;          // (a NaN anywhere: dropped)
+            r.cf = (float)cf; r.cs = (float)cs_;
+            r.af = (float)(vs / det); r.as = (float)(-vf / det); r.bf = (float)(-us / det); r.bs = (float)(uf / det);
+            r.cls = LAB ? (uint32_t)mesh_class[min((unsigned)oi.mesh_id, (unsigned)(n_mesh_class - 1))] : 0u;
+            r.id = (uint32_t)tid + 1u;
+          }
+        }
+        const unsigned long long kept = __ballot(keep);
+        if (keep) s_rect[b][__popcll(kept & ((1ull << tid) - 1ull))] = r;
+        if (tid == 0) s_n[b] = __popcll(kept);
+      }
+      __syncthreads();
+      n_rect = __builtin_amdgcn_readfirstlane(s_n[b]);
+    }
+    uint32_t cls = DTSIM_LABEL_GROUND, who = DTSIM_INSTANCE_NONE;
+    bool hit = false;
+    for (int k = 0; k < n_rect; ++k) {                 // (wave-uniform count; LDS broadcast reads)
+      const BevRect r = s_rect[b][k];
+      const float pf = f - r.cf, ps = sd - r.cs;
+      const float a = fmaf(ps, r.as, pf * r.af), bb = fmaf(ps, r.bs, pf * r.bf);
+      if (fabsf(a) <= 1.f && fabsf(bb) <= 1.f) { cls = r.cls; who = r.id; hit = true; break; }
+    }
+    if constexpr (LAB) {
+      if (!hit) {
+        const float wx = fmaf(sd, ev.ds, fmaf(f, ev.dc, ev.x));
+        const float wz = fmaf(sd, ev.dc, fmaf(-f, ev.ds, ev.z));
+        const float its = ev.its;
+        const float fi = floorf(wx * its), fj = floorf(wz * its);
+        if (fi >= 0.f && fj >= 0.f && fi < (float)ev.gw && fj < (float)ev.gh) {
+          const int ti = (int)fi, tj = (int)fj;
+          const TileLds tr = s_tiles[ev.tile_off + tj * ev.gw + ti];
+          if ((tr.flags & 3u) == 3u) {                 // present and textured (else: the ground's class)
+            const float fx = wx * its - (float)ti, fz = wz * its - (float)tj;     // the tile fraction, as k_labels takes it
+            float x, y;
+            tile_texel_xy(tr, fx, fz, x, y);
+            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
+            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+          }
+        }
+      }
+    }
+    if (in) {
+      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
+      if constexpr (LAB) out[at] = (uint8_t)cls;
+      if constexpr (INST) inst[at] = (uint8_t)who;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
                                                       const int first, const int count, const int env) {
   __shared__ LedS s_led[64];
@@ -3105,6 +3266,19 @@ void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel
   hipLaunchKernelGGL(k, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
                      reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
                      n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask);
+}
+
+void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
+                   const uint8_t* mesh_class, int n_mesh_class, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind,
+                   const uint8_t* mask) {
+  if (R.N <= 0 || (!cls && !inst)) return;
+  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
+  auto k = cls && inst ? k_bev<true, true> : cls ? k_bev<true, false> : k_bev<false, true>;
+  static_assert(DTSIM_LDS_TILES * sizeof(TileLds) <= 32768, "the tile records of all maps fit the workgroup's LDS beside its 10 KB of lists");
+  const int n_recs = min(R.n_tile_recs, DTSIM_LDS_TILES);   // (dt_pack_maps refuses more)
+  hipLaunchKernelGGL(k, grid, dim3(256), (size_t)n_recs * sizeof(TileLds), s, A.pos_x, A.pos_z, A.angle, A.map_id, A.ob_corners, A.ob_visible, R.maps,
+                     R.tile_recs, R.objs, ocorners, texel_class, mesh_class, n_mesh_class, R.tex_w, R.tex_h, R.n_maps, n_recs, R.N, oh, ow, cell, rows_behind,
+                     cls, inst, mask);
 }
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {

@@ -259,6 +259,23 @@ inline void dt_pack_quad_block(std::vector<uint32_t>& out, const uint32_t* pool,
     }
 }
 
+// The collision rectangles of the maps' objects as the host packed them (dtsim_object.corners: four (x, z) corners in order, float64), maps
+// concatenated in the order of MapTables.robjs -- object o of map m at [RenderMapDev.obj_off + o][8] -- for dtsim_bev (render.hip k_bev),
+// which draws a static object's footprint from here and a dynamic one's (ObjInstDev.dyn_slot >= 0) from the env's SimArrays::ob_corners.
+// The maps are dt_pack_maps' arguments, already checked by it (object counts within DTSIM_MAX_OBJECTS, non-null lists).
+inline int dt_pack_object_corners(std::vector<double>& out, std::string& err, const dtsim_map* maps, int n_maps) {
+  if (!maps || n_maps <= 0) return dt_scene_fail(err, DTSIM_E_INVALID, "null argument");
+  std::vector<double> t;
+  for (int mi = 0; mi < n_maps; ++mi) {
+    const dtsim_map& mp = maps[mi];
+    if (mp.n_objects < 0 || mp.n_objects > DTSIM_MAX_OBJECTS || (mp.n_objects > 0 && !mp.objects))
+      return dt_scene_fail(err, DTSIM_E_INVALID, "map %d: object list", mi);
+    for (int o = 0; o < mp.n_objects; ++o) t.insert(t.end(), mp.objects[o].corners, mp.objects[o].corners + 8);
+  }
+  out = std::move(t);
+  return DTSIM_OK;
+}
+
 // what a handle keeps of the packed maps besides the tables themselves
 struct MapScalars {
   MapSet M{};                                  // blob offsets; blobs / dyn are the owner's device copies (null in MapTables)
@@ -278,6 +295,7 @@ struct MapTables : MapScalars {
   std::vector<TileLds> trecs;
   std::vector<ObjInstDev> robjs;
   std::vector<uint32_t> qblocks, qtiles;       // quad records (4 dwords each); [n_qtiles][2] block offset, record mask
+  std::vector<double> ocorners;                // dt_pack_object_corners: [robjs.size()][8]
 };
 
 // render: the handle's DTSIM_F_RENDER, without which no quad tables are built
@@ -402,6 +420,7 @@ inline int dt_pack_maps(MapTables& out, std::string& err, const dtsim_map* maps,
     }
   }
   T.M.total_words = (int32_t)T.blobs.size();
+  if (int rc = dt_pack_object_corners(T.ocorners, err, maps, n_maps)) return rc;
   if ((size_t)T.M.total_words * 8 > 60000)
     return dt_scene_fail(err, DTSIM_E_LIMIT, "map tables %zu B exceed the 60 KB LDS staging budget", (size_t)T.M.total_words * 8);
   if (T.trecs.size() > DTSIM_LDS_TILES)

@@ -886,6 +886,94 @@ class BatchedSimulator:
                                                     C.c_void_p(out.data_ptr()), 0, mp))
         return out
 
+    def bev(self, height: int, width: int, cell: float = 0.02, rows_behind: int = 0, out=None, mask=None, instances_out=None):
+        """The egocentric bird's-eye label map of every env, on the device (dtsim_bev, include/dtsim.h): [N, height, width] uint8, cell
+        (i, j) = the class at the world point f metres ahead of the agent and s to its right, f = (height - rows_behind - i - 0.5) * cell,
+        s = (j + 0.5 - width / 2) * cell (row 0 the farthest ahead, column 0 the leftmost; the agent's pose, not the camera's): the class of
+        the mesh of the lowest-indexed visible object whose collision rectangle (object_footprints()) holds the point, else of the nearest
+        texel of the tile under it (the tables of set_label_assets(), the defaults installed at first use, as labels() does), else 2, the
+        ground.  0 and 1 never occur; never filtered; the agent's own rectangle is not drawn.  `instances_out` ([N, height, width] uint8):
+        the same launch also writes o + 1 where object o owns the cell and 0 elsewhere -- instances()'s ids.  Not a post-pass: it reads the
+        current state and needs no render().  `out` as labels()'s, `mask` as render()'s (only the selected envs' rows are written).  A size
+        outside 1 .. 1024, a cell that is not finite and positive, rows_behind outside 0 .. height, a bad out, instances_out or mask
+        raise ValueError before the library is called."""
+        import torch
+        try:
+            h, w, rb, c = int(height), int(width), int(rows_behind), float(cell)
+            whole = h == height and w == width and rb == rows_behind
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError(f"bev: height, width and rows_behind must be integers and cell a number, got {height!r}, {width!r}, {rows_behind!r}, {cell!r}")
+        if not (1 <= h <= _ffi.BEV_MAX_SIDE and 1 <= w <= _ffi.BEV_MAX_SIDE):
+            raise ValueError(f"bev: a {h} x {w} map: each size must be in 1 .. {_ffi.BEV_MAX_SIDE}")
+        if not (math.isfinite(c) and c > 0.0):
+            raise ValueError(f"bev: cell {cell!r}: metres per cell, finite and > 0")
+        if not 0 <= rb <= h:
+            raise ValueError(f"bev: rows_behind {rows_behind!r} outside 0 .. {h}")
+        if not self.render_enabled:
+            raise ValueError("bev: the simulator was built with render=False and holds no render tables")
+        mp = self._mask_arg(mask)
+        shape = (self.num_envs, h, w)
+        if out is None:
+            if getattr(self, "_bev_key", None) != (h, w):
+                self._bev_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")        # (empty: as depth()'s buffer)
+                self._bev_key = (h, w)
+            out = self._bev_buf
+        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "bev"))
+        ip = None
+        if instances_out is not None:
+            ip = C.c_void_p(self._out_ptr(instances_out, shape, "|u1", 1, "bev: instances_out"))
+            if ip.value == ptr.value:
+                raise ValueError("bev: instances_out and out are one buffer")
+        if not getattr(self, "_have_label_assets", False):
+            self.set_label_assets()
+        _ffi.check(self._lib, self._lib.dtsim_bev(self._h, ptr, ip, h, w, c, rb, 0, mp))
+        return out
+
+    @staticmethod
+    def _state_array_offset(name: str, n: int) -> int:
+        """Byte offset of array `name` in the state blob of n envs (csrc/state_fields.h DT_STATE_ARRAYS: [planes][n] float64 arrays in slab
+        order, each starting on the next multiple of 256 bytes) -- for the arrays up to ob_corners, which no public field shows."""
+        order = [("pos_x", 1), ("pos_z", 1), ("angle", 1), ("q_x", 1), ("q_y", 1), ("q_c", 1), ("q_s", 1), ("vel_u", 1), ("vel_w", 1),
+                 ("ring", _ffi.MAX_DELAY * 2), ("war", 1), ("wal", 1), ("wheel_dist", 1), ("timestamp", 1), ("speed", 1), ("reward", 1),
+                 ("lane", 4), ("prox", 1), ("wheels", 2), ("ob_cx", _ffi.MAX_DYNAMIC), ("ob_cz", _ffi.MAX_DYNAMIC), ("ob_sx", _ffi.MAX_DYNAMIC),
+                 ("ob_sz", _ffi.MAX_DYNAMIC), ("ob_corners", _ffi.MAX_DYNAMIC * 8)]
+        off = 0
+        for nm, planes in order:
+            if nm == name:
+                return off
+            off += (n * planes * 8 + 255) & ~255
+        raise KeyError(name)
+
+    def object_footprints(self):
+        """(corners [N, MAX_OBJECTS, 4, 2] float64, drawn [N, MAX_OBJECTS] bool), on the host, synchronous: the collision rectangle of
+        object k of env e's map as four (x, z) corners in order -- a static object's as the map packed it (self.maps[map_id].objects[k]
+        .corners), a dynamic one's (duckies, followers, the checkerboard) the env's current one from the state blob (ob_corners: what the
+        physics collides with) -- and whether bev() draws it: visible (FIELD_OBJ_VISIBLE) and with a mesh.  Rows past a map's object count
+        are zero / False.  What a user overlays on the bev() map."""
+        n = self.num_envs
+        corners = np.zeros((n, _ffi.MAX_OBJECTS, 4, 2), np.float64)
+        drawn = np.zeros((n, _ffi.MAX_OBJECTS), bool)
+        map_id = self.read(_ffi.FIELD_MAP_ID)
+        vis = self.read(_ffi.FIELD_OBJ_VISIBLE) != 0
+        blob = self.read(_ffi.FIELD_STATE_BLOB)
+        off = self._state_array_offset("ob_corners", n)
+        dyn = blob[off:off + 8 * _ffi.MAX_DYNAMIC * n * 8].view(np.float64).reshape(8, _ffi.MAX_DYNAMIC, n)      # [coordinate][slot][env]
+        for m, mt in enumerate(self.maps):
+            envs = np.nonzero(map_id == m)[0]
+            if not len(envs):
+                continue
+            slot = 0
+            for k, o in enumerate(mt.objects):
+                if o.static or not o.dyn_kind:                  # (dtsim_object.dynamic == 0: no slot)
+                    corners[envs, k] = np.asarray(o.corners, np.float64).reshape(4, 2)
+                else:
+                    corners[envs, k] = dyn[:, slot, envs].T.reshape(-1, 4, 2)
+                    slot += 1
+                drawn[envs, k] = vis[envs, k] & (self.render_enabled and o.mesh_kind in self._mesh_order)
+        return corners, drawn
+
     def object_classes(self):
         """[n_maps, MAX_OBJECTS] uint8 (numpy): the class labels() gives each object slot of each resident map -- mesh_class[mesh of object k
         of map m] under the table installed through set_label_assets(), or the default one (label_assets()) while none is -- and 0 past a

@@ -74,6 +74,18 @@ fisheye's black border) of the state `obs` shows, and with `boxes=True` `info["b
 depth pass does, after depth and labels; with `label_shape == instance_shape` ONE `dtsim_instances` launch fills both maps from one
 classification and `dtsim_labels` is not called.  `motion_blur` and `camera_rand` raise ValueError, for depth's reasons.
 `instance_shape=None` (the default) makes no new call.
+
+Bird's-eye view (`bev_shape=(h, w)`, each 1 .. 1024; `bev_cell` metres per cell, `bev_rows_behind` of the h rows behind the agent;
+`bev_instances=True` needs it): `info["bev"]` is one persistent `[N, h, w]` `torch.uint8` device tensor with the egocentric label map
+(`dtsim_bev`, include/dtsim.h: cell (i, j) = the class at the point (h - rows_behind - i - 0.5) cells ahead of the AGENT and (j + 0.5 - w / 2)
+cells to its right -- the mesh class of the lowest-indexed visible object whose collision rectangle holds the point, else the nearest
+texel's class of the tile under it, else 2, the ground; never 0 or 1, never filtered) of the state `obs` shows -- for a restarted env its new
+episode's first state --, and with `bev_instances=True` `info["bev_instances"]` the id map of the same launch (o + 1 / 0, the ids of
+`info["instances"]`).  After `reset()` they are `env.bev` / `env.bev_instances`, the same tensors.  With `final_obs=True`,
+`info["final_bev"]` / `info["final_bev_instances"]` hold the finished envs' rows as `info["final_labels"]` does.  The pass stands where the
+depth pass does, after the instance pass, masked where that one is masked.  It reads the state, not the camera, so it composes with
+everything: `camera_rand` and `motion_blur` are allowed -- under `motion_blur` the observation blends the frames of the window's states,
+and the map is that of the state after the last sub-update, the newest of them.  `bev_shape=None` (the default) makes no new call.
 """
 from __future__ import annotations
 
@@ -91,7 +103,9 @@ class DuckietownVecEnv:
                  seed: Optional[int] = 0, final_obs: bool = False, frame_stack: int = 1, grayscale: bool = False,
                  motion_blur: Union[bool, Sequence[int]] = False, depth_shape: Optional[Tuple[int, int]] = None,
                  depth_dtype: str = "float32", label_shape: Optional[Tuple[int, int]] = None,
-                 instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False, **sim_kwargs):
+                 instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False,
+                 bev_shape: Optional[Tuple[int, int]] = None, bev_cell: float = 0.02, bev_rows_behind: int = 0,
+                 bev_instances: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -156,6 +170,26 @@ class DuckietownVecEnv:
                 raise ValueError(f"instance_shape {(ih, iw)}: each size must divide the camera's {(H, W)} (instance ids are point-sampled, "
                                  "never filtered)")
             self.instance_shape = (ih, iw)
+        self.bev_shape, self.bev_cell, self.bev_rows_behind, self._want_bev_inst = None, bev_cell, bev_rows_behind, bool(bev_instances)
+        if bev_shape is None:
+            if bev_instances:
+                raise ValueError("bev_instances=True needs bev_shape (the ids are those of the bird's-eye map, in its cells)")
+        else:
+            try:
+                bh, bw = (int(v) for v in bev_shape)
+                brb, bc = int(bev_rows_behind), float(bev_cell)
+            except (TypeError, ValueError):
+                raise ValueError(f"bev_shape must be (h, w), bev_rows_behind an integer and bev_cell a number, got {bev_shape!r}, "
+                                 f"{bev_rows_behind!r}, {bev_cell!r}") from None
+            if not (1 <= bh <= _ffi.BEV_MAX_SIDE and 1 <= bw <= _ffi.BEV_MAX_SIDE):
+                raise ValueError(f"bev_shape {(bh, bw)}: each size must be in 1 .. {_ffi.BEV_MAX_SIDE}")
+            if not (np.isfinite(bc) and bc > 0.0):
+                raise ValueError(f"bev_cell {bev_cell!r}: metres per cell, finite and > 0")
+            if brb != bev_rows_behind or not 0 <= brb <= bh:
+                raise ValueError(f"bev_rows_behind {bev_rows_behind!r}: an integer in 0 .. {bh}")
+            if sim_kwargs.get("render") is False:
+                raise ValueError("bev_shape needs render=True (the pass reads the render tables)")
+            self.bev_shape, self.bev_cell, self.bev_rows_behind = (bh, bw), bc, brb
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -194,6 +228,15 @@ class DuckietownVecEnv:
             if self.final_obs:
                 self._final_instances = torch.zeros_like(self.instances)
                 self._final_boxes = torch.zeros_like(self.boxes) if self._want_boxes else None
+        # info["bev"] / info["bev_instances"] and their final_ rows: persistent [N, h, w] uint8 tensors
+        self.bev = self.bev_instances = self._final_bev = self._final_bev_instances = None
+        if self.bev_shape is not None:
+            self.bev = torch.zeros((num_envs, *self.bev_shape), dtype=torch.uint8, device=self.device)
+            if self._want_bev_inst:
+                self.bev_instances = torch.zeros_like(self.bev)
+            if self.final_obs:
+                self._final_bev = torch.zeros_like(self.bev)
+                self._final_bev_instances = torch.zeros_like(self.bev) if self._want_bev_inst else None
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -248,7 +291,8 @@ class DuckietownVecEnv:
     def _depth_pass(self, mask=None):
         """depth_shape / label_shape / instance_shape: the depth, then the labels, then the instances and their boxes, of the state the last
         render() showed, into self.depth / self.labels / self.instances / self.boxes (`mask`: only those envs' rows).  Labels and instances
-        of one shape come from one launch."""
+        of one shape come from one launch.  bev_shape: then the bird's-eye map (and its ids) of the current state into self.bev
+        (/ self.bev_instances)."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
         fused = self.labels is not None and self.label_shape == self.instance_shape
@@ -259,10 +303,13 @@ class DuckietownVecEnv:
                                labels_out=self.labels if fused else None)
             if self.boxes is not None:
                 self.sim.boxes(self.instances, out=self.boxes, mask=mask)
+        if self.bev is not None:
+            self.sim.bev(self.bev_shape[0], self.bev_shape[1], cell=self.bev_cell, rows_behind=self.bev_rows_behind, out=self.bev, mask=mask,
+                         instances_out=self.bev_instances)
 
     def _keep_final(self, obs, done, info):
-        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map, the label map, the instance map
-        and the boxes, before the reset rewrites them."""
+        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map, the label map, the instance map,
+        the boxes and the bird's-eye maps, before the reset rewrites them."""
         src = self._stack if self._stacked else obs
         if self._final is None:
             # (zeros, once, on our stream: the rows of envs that have not finished yet hold no stale memory -- two envs run alike then
@@ -282,6 +329,12 @@ class DuckietownVecEnv:
         if self.boxes is not None:
             self.sim.copy_rows(self._final_boxes, self.boxes, done)
             info["final_boxes"] = self._final_boxes
+        if self.bev is not None:
+            self.sim.copy_rows(self._final_bev, self.bev, done)
+            info["final_bev"] = self._final_bev
+        if self.bev_instances is not None:
+            self.sim.copy_rows(self._final_bev_instances, self.bev_instances, done)
+            info["final_bev_instances"] = self._final_bev_instances
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -369,6 +422,10 @@ class DuckietownVecEnv:
                 info["instances"] = self.instances
             if self.boxes is not None:
                 info["boxes"] = self.boxes
+            if self.bev is not None:
+                info["bev"] = self.bev
+            if self.bev_instances is not None:
+                info["bev_instances"] = self.bev_instances
         self._leave()
         return obs, reward, done, info
 

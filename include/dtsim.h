@@ -617,6 +617,38 @@ int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, i
  * bytes that lies between 16-byte boundaries, whatever the base's alignment.  A null handle, inst or out, a non-positive size, a product
  * beyond int32 or nonzero flags return DTSIM_E_INVALID, and nothing is launched.  Asynchronous, stream-ordered. */
 int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask);
+/* The egocentric bird's-eye label map of every env, on the device: WHAT LIES ON THE FLOOR around the robot, in metres and in the robot's own
+ * frame -- the target of camera-to-BEV heads, the input of a privileged critic or planner.  It is the one per-cell output that does not
+ * depend on the camera: defined under per-env distortion tables, under any fisheye, with or without a render pass.  The reference has no
+ * such output (its nearest relatives: the top_down render mode); a learner-side addition like depth, labels and instances.
+ * THE QUANTITY.  The call gives (oh, ow), cell (metres per cell, finite, > 0) and rows_behind (0 .. oh).  Env e has the AGENT's pose
+ * (x, z, theta) = (cur_pos.x, cur_pos.z, cur_angle) -- DTSIM_FIELD_POS / DTSIM_FIELD_ANGLE, not the camera's --, forward d = (cos theta,
+ * -sin theta) and right r = (sin theta, cos theta), both in (x, z), as get_dir_vec / get_right_vec.  Cell (i, j), row 0 the farthest ahead
+ * and column 0 the leftmost, stands for the world point
+ *     P = (x, z) + f d + s r,   f = (oh - rows_behind - i - 0.5) cell,   s = (j + 0.5 - ow / 2) cell      (ow / 2 is not rounded)
+ * and the map is point-sampled at P, never filtered.  cls[e][i][j], a uint8, is the first of these that applies:
+ *   1. a visible object's footprint: the lowest object index o of the env's own map with DTSIM_FIELD_OBJ_VISIBLE set and a mesh
+ *      (mesh_id >= 0) whose collision rectangle contains P -- for a static object the four corners the host packed (dtsim_object.corners),
+ *      for a dynamic one (duckies, followers, the checkerboard) the env's current corners, the rectangle _collision tests and draw_bbox
+ *      draws, as stale as the physics leaves its axes.  The class is mesh_class[mesh id of o] of dtsim_set_label_assets.
+ *   2. a present, textured tile that P lies on: the class of the NEAREST texel of its texture, by dtsim_labels' own statement (the texel
+ *      coordinates the generic raster filters at, rounded down after the half-texel shift is taken back, wrapped as GL_REPEAT, the same
+ *      texel_class pool): a camera label pixel and a cell that hit one world point name one class.
+ *   3. anything else -- an untextured or absent tile, any point off the grid: DTSIM_LABEL_GROUND.
+ * DTSIM_LABEL_NONE and DTSIM_LABEL_SKY never occur.  inst[e][i][j], from the same classification in the same launch, is o + 1 in case 1 and
+ * DTSIM_INSTANCE_NONE otherwise: the ids of dtsim_instances.  Not drawn: the agent's own rectangle (the same cells in every env), heights,
+ * occlusion (the view sees through everything).  The pose is read in float64 and the sine and cosine are taken of the float64 angle
+ * (cur_angle is unbounded); a cell's P is then float32 arithmetic, within 1e-5 m of the float64 value while coordinates stay below 32 m.
+ * SIZE.  cls, inst: DEVICE pointers to [num_envs][oh][ow] bytes each; either may be NULL, not both, and they must not be one buffer.
+ * 1 <= oh, ow <= DTSIM_BEV_MAX_SIDE.  mask: DEVICE pointer to num_envs bytes, or NULL = every env; the rows of unselected envs keep every byte.
+ * STATE.  Not a post-pass: it reads the pose, map id, object visibility and dynamic corners of the CURRENT state and the scene tables, so no
+ * dtsim_render need precede it; the handle must hold the render tables (DTSIM_F_RENDER, dtsim_set_assets, dtsim_set_maps) and, with cls,
+ * the label tables.  DTSIM_E_INVALID, before anything is launched or written, for: a null handle, both maps null or one buffer, a handle
+ * without render tables, cls without label tables, a size outside 1 .. DTSIM_BEV_MAX_SIDE, a non-finite or non-positive cell, rows_behind
+ * outside 0 .. oh, nonzero flags.  Asynchronous, stream-ordered, no host synchronisation.  One state gives the same bytes on every call,
+ * for every env index and whichever of the two maps are asked for. */
+#define DTSIM_BEV_MAX_SIDE 1024
+int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

@@ -15,7 +15,10 @@ depth_labels (both maps at 120 x 160) | instances (info["instances"] + info["box
 observe) | instances_full (480 x 640) | instances_only (no boxes) | labels_instances (labels + instances + boxes at 120 x 160: one fused launch
 for the two maps).
 INSTANCES=1 (or full): the whole step with instances and boxes against the plain step in the SAME run -- VARIANTS=plain,instances (or
-plain,instances_full) with ROUNDS=5 unless given."""
+plain,instances_full) with ROUNDS=5 unless given.
+BEV=1 (or small): the whole step with info["bev"] + info["bev_instances"] (DuckietownVecEnv(bev_shape=(128, 128), bev_cell=0.02,
+bev_instances=True); small: (64, 64) at 0.04) against the plain step in the SAME run -- VARIANTS=plain,bev (or plain,bev_small) with ROUNDS=5
+unless given; the variants bev | bev_small | bev_only (no id map) can be listed like any other."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -32,6 +35,7 @@ DEPTH = os.environ.get("DEPTH", "0")
 DEPTH_DTYPE = os.environ.get("DEPTH_DTYPE", "float32")
 LABELS = os.environ.get("LABELS", "0")
 INSTANCES = os.environ.get("INSTANCES", "0")
+BEV = os.environ.get("BEV", "0")
 MAP = os.environ.get("MAP", "small_loop")
 MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
@@ -39,12 +43,14 @@ K = int(os.environ.get("K", "30"))
 ROUNDS = int(os.environ.get("ROUNDS", "1"))
 if INSTANCES != "0" and not VARIANTS:
     VARIANTS, ROUNDS = ["plain", "instances_full" if INSTANCES == "full" else "instances"], int(os.environ.get("ROUNDS", "5"))
+if BEV != "0" and not VARIANTS:
+    VARIANTS, ROUNDS = ["plain", "bev_small" if BEV == "small" else "bev"], int(os.environ.get("ROUNDS", "5"))
 a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
     def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0", instances="0",
-                 boxes=True):
+                 boxes=True, bev="0", bev_instances=True):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
@@ -57,6 +63,8 @@ class Variant:
             kw.update(label_shape=(480, 640) if labels == "full" else (120, 160))
         if instances != "0":
             kw.update(instance_shape=(480, 640) if instances == "full" else (120, 160), boxes=boxes)
+        if bev != "0":
+            kw.update(bev_shape=(64, 64) if bev == "small" else (128, 128), bev_cell=0.04 if bev == "small" else 0.02, bev_instances=bev_instances)
         self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -102,6 +110,8 @@ def make(name):
             "instances_full": lambda: Variant("instances + boxes 480 x 640", instances="full"),
             "instances_only": lambda: Variant("instances 120 x 160, no boxes", instances="1", boxes=False),
             "labels_instances": lambda: Variant("labels + instances + boxes 120 x 160", labels="1", instances="1"),
+            "bev": lambda: Variant("bev + ids 128 x 128 at 0.02 m", bev="1"), "bev_small": lambda: Variant("bev + ids 64 x 64 at 0.04 m", bev="small"),
+            "bev_only": lambda: Variant("bev 128 x 128 at 0.02 m, no ids", bev="1", bev_instances=False),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
