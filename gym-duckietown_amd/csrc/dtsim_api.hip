@@ -756,45 +756,53 @@ static int map_pass_check(dtsim_t* h, const char* who, const void* out, int oh, 
   return DTSIM_OK;
 }
 
-// The shared body of dtsim_depth / dtsim_depth_masked.
-static int depth_run(dtsim_t* h, const char* who, void* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
-  if (int rc = map_pass_check(h, who, out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, masked, mask)) return rc;
+// The shared body of the camera post-passes -- dtsim_depth, dtsim_labels, dtsim_instances and their masked forms: map_pass_check with `out`,
+// the output the entry point cannot do without; the label tables where the launch reads them (`tables`: how the refusal reads, null when
+// it reads none); then `launch`.
+extern "C++" {
+template <class Launch>
+static int map_pass_run(dtsim_t* h, const char* who, const void* out, int oh, int ow, uint32_t flags, uint32_t allowed, bool masked,
+                        const uint8_t* mask, const char* tables, Launch launch) {
+  if (int rc = map_pass_check(h, who, out, oh, ow, flags, allowed, masked, mask)) return rc;
+  if (tables && (!h->d_texel_class || !h->d_mesh_class)) return fail(DTSIM_E_STATE, "%s %s", who, tables);
   HIPCHK(hipSetDevice(h->cfg.device));
-  dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask);
+  launch();
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }
+}  // extern "C++"
 
-int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags) { return depth_run(h, "dtsim_depth", out, oh, ow, flags, false, nullptr); }
+int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags) {
+  return map_pass_run(h, "dtsim_depth", out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, false, nullptr, nullptr,
+                      [=] { dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, nullptr); });
+}
 int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
-  return depth_run(h, "dtsim_depth_masked", out, oh, ow, flags, true, mask);
+  return map_pass_run(h, "dtsim_depth_masked", out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, true, mask, nullptr,
+                      [=] { dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask); });
 }
 
-// The shared body of dtsim_labels / dtsim_labels_masked: depth's checks, and the label tables.
-static int labels_run(dtsim_t* h, const char* who, uint8_t* out, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
-  if (int rc = map_pass_check(h, who, out, oh, ow, flags, 0u, masked, mask)) return rc;
-  if (!h->d_texel_class || !h->d_mesh_class) return fail(DTSIM_E_STATE, "%s before dtsim_set_label_assets", who);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, out, nullptr, oh, ow, mask);
-  HIPCHK(hipGetLastError());
-  return DTSIM_OK;
-}
-
-// The shared body of dtsim_instances / dtsim_instances_masked: depth's checks; the label tables only when a label map is asked for too.
-static int instances_run(dtsim_t* h, const char* who, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
-  if (int rc = map_pass_check(h, who, inst, oh, ow, flags, 0u, masked, mask)) return rc;
-  if (labels && (!h->d_texel_class || !h->d_mesh_class)) return fail(DTSIM_E_STATE, "%s with a label map before dtsim_set_label_assets", who);
-  HIPCHK(hipSetDevice(h->cfg.device));
+// (one kernel classifies for dtsim_labels and dtsim_instances: it fills whichever of the two maps is given)
+static void labels_launch(const dtsim* h, uint8_t* labels, uint8_t* inst, int oh, int ow, const uint8_t* mask) {
   dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, labels, inst, oh, ow, mask);
-  HIPCHK(hipGetLastError());
-  return DTSIM_OK;
 }
 
+int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags) {
+  return map_pass_run(h, "dtsim_labels", out, oh, ow, flags, 0u, false, nullptr, "before dtsim_set_label_assets",
+                      [=] { labels_launch(h, out, nullptr, oh, ow, nullptr); });
+}
+int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return map_pass_run(h, "dtsim_labels_masked", out, oh, ow, flags, 0u, true, mask, "before dtsim_set_label_assets",
+                      [=] { labels_launch(h, out, nullptr, oh, ow, mask); });
+}
+
+// (the label tables only when a label map is asked for too)
 int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags) {
-  return instances_run(h, "dtsim_instances", inst, labels, oh, ow, flags, false, nullptr);
+  return map_pass_run(h, "dtsim_instances", inst, oh, ow, flags, 0u, false, nullptr, labels ? "with a label map before dtsim_set_label_assets" : nullptr,
+                      [=] { labels_launch(h, labels, inst, oh, ow, nullptr); });
 }
 int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, const uint8_t* mask) {
-  return instances_run(h, "dtsim_instances_masked", inst, labels, oh, ow, flags, true, mask);
+  return map_pass_run(h, "dtsim_instances_masked", inst, oh, ow, flags, 0u, true, mask, labels ? "with a label map before dtsim_set_label_assets" : nullptr,
+                      [=] { labels_launch(h, labels, inst, oh, ow, mask); });
 }
 
 int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask) {
@@ -827,11 +835,6 @@ int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double ce
                 rows_behind, mask);
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
-}
-
-int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags) { return labels_run(h, "dtsim_labels", out, oh, ow, flags, false, nullptr); }
-int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
-  return labels_run(h, "dtsim_labels_masked", out, oh, ow, flags, true, mask);
 }
 
 void* dtsim_frames_devptr(dtsim_t* h) { return h ? h->frames : nullptr; }

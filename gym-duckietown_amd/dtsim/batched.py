@@ -139,6 +139,9 @@ class BatchedSimulator:
         self.map_cycle = bool(map_cycle)
         self.map_random = bool(map_random)     # randomize_maps_on_reset: a uniformly drawn map, reloaded, at every reset
         self.seed_value = seed
+        self._bufs = {}                         # the methods' own result buffers, by method name (_result)
+        self._have_label_assets = False         # set_label_assets() has run (_need_label_assets)
+        self._mesh_class = None                 # its mesh table (object_classes())
 
         flags = 0
         flags |= _ffi.F_RENDER if render else 0
@@ -530,6 +533,38 @@ class BatchedSimulator:
                              f"typestr {ai['typestr']!r}, strides {strides}")
         return ai["data"][0]
 
+    _TYPESTR = {"float32": ("<f4", 4), "float16": ("<f2", 2), "uint8": ("|u1", 1), "int32": ("<i4", 4)}
+
+    def _result(self, who: str, out, shape, dtype: str = "uint8"):
+        """(out, its device pointer) of method `who`: `out` as _out_ptr accepts it or, for None, the method's own buffer -- allocated at first
+        use and again when the shape or dtype asked for changes."""
+        if out is None:
+            import torch
+            out = self._bufs.get(who)
+            if out is None or tuple(out.shape) != shape or out.dtype != getattr(torch, dtype):
+                # (empty: a fill would run on torch's stream, unordered against the handle's own, and race with the kernel's stores; a
+                # first call that is masked leaves the other rows uninitialised)
+                out = self._bufs[who] = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device_index}")
+        return out, C.c_void_p(self._out_ptr(out, shape, *self._TYPESTR[dtype], who))
+
+    def _map_size(self, who: str, noun: str, height, width):
+        """(h, w) of a camera post-pass's map: the camera's size, or a divisor of it, else ValueError."""
+        h = self.camera_height if height is None else int(height)
+        w = self.camera_width if width is None else int(width)
+        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
+            raise ValueError(f"{who}: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
+                             f"({noun} point-sampled, never filtered)")
+        return h, w
+
+    def _need_label_assets(self):
+        """The default label tables, installed at the first use of a pass that reads them."""
+        if not self._have_label_assets:
+            self.set_label_assets()
+
+    def _map_pass(self, fn, fn_masked, mp, *args):
+        """fn(handle, *args), or with a mask fn_masked(handle, *args, mask): a pass whose masked form takes the mask last."""
+        _ffi.check(self._lib, fn(self._h, *args) if mp is None else fn_masked(self._h, *args, mp))
+
     def render(self, segment: bool = False, gl_filter: bool = False, mask=None):
         """render_obs() of every env into the frame batch; `segment=True` is the reference's segmentation render
         (simulator.py:1730-1737,1753,1808,1879).  `gl_filter=True` (DTSIM_RENDER_GL_FILTER): tile textures filtered with the arithmetic of the
@@ -683,21 +718,13 @@ class BatchedSimulator:
         __cuda_array_interface__ of that shape/dtype, C-contiguous (e.g. the send buffer of the frame all-gather); any other `out` raises
         ValueError before anything is launched.  `mask` (as render's): only the rows of the selected envs are written, the others keep
         their content."""
-        import torch
         from . import resample
         if interpolation not in ("pil_bilinear", "cv_cubic"):
             raise ValueError(f"interpolation {interpolation!r}: 'pil_bilinear' or 'cv_cubic'")
         mp = self._mask_arg(mask)
         h, w = int(height), int(width)
         shape = (self.num_envs, 3, h, w) if chw else (self.num_envs, h, w, 3)
-        if out is None:
-            key = (h, w, chw, normalize)
-            if getattr(self, "_obs_key", None) != key:
-                self._obs_buf = torch.empty(shape, dtype=torch.float32 if normalize else torch.uint8,
-                                            device=f"cuda:{self.device_index}")
-                self._obs_key = key
-            out = self._obs_buf
-        ptr = self._out_ptr(out, shape, "<f4" if normalize else "|u1", 4 if normalize else 1, "observe")
+        out, ptr = self._result("observe", out, shape, "float32" if normalize else "uint8")
         ip = C.POINTER(C.c_int32)
         flags = (_ffi.OBS_CHW if chw else 0) | (_ffi.OBS_F32 if normalize else 0)
         if interpolation == "cv_cubic":
@@ -706,9 +733,9 @@ class BatchedSimulator:
             fx, tx, fy, ty = (np.ascontiguousarray(a, dtype=np.int32) for a in (fx, tx, fy, ty))
             tabs = (fx.ctypes.data_as(ip), tx.ctypes.data_as(ip), fy.ctypes.data_as(ip), ty.ctypes.data_as(ip))
             if mp is None:
-                _ffi.check(self._lib, self._lib.dtsim_observe_cubic(self._h, C.c_void_p(ptr), h, w, flags, *tabs))
+                _ffi.check(self._lib, self._lib.dtsim_observe_cubic(self._h, ptr, h, w, flags, *tabs))
             else:
-                _ffi.check(self._lib, self._lib.dtsim_observe_cubic_masked(self._h, C.c_void_p(ptr), h, w, flags, mp, *tabs))
+                _ffi.check(self._lib, self._lib.dtsim_observe_cubic_masked(self._h, ptr, h, w, flags, mp, *tabs))
             return out
         bx = kx = by = ky = None
         nkx = nky = 0
@@ -719,12 +746,12 @@ class BatchedSimulator:
             b, k = resample.coeffs(self.camera_height, h)
             by, ky, nky = b.ctypes.data_as(ip), k.ctypes.data_as(ip), k.shape[1]
         if mp is None:
-            _ffi.check(self._lib, self._lib.dtsim_observe(self._h, C.c_void_p(ptr), h, w, flags, bx, kx, nkx, by, ky, nky))
+            _ffi.check(self._lib, self._lib.dtsim_observe(self._h, ptr, h, w, flags, bx, kx, nkx, by, ky, nky))
         else:
-            _ffi.check(self._lib, self._lib.dtsim_observe_masked(self._h, C.c_void_p(ptr), h, w, flags, mp, bx, kx, nkx, by, ky, nky))
+            _ffi.check(self._lib, self._lib.dtsim_observe_masked(self._h, ptr, h, w, flags, mp, bx, kx, nkx, by, ky, nky))
         return out
 
-    _DEPTH_DTYPES = {"float32": ("<f4", 4), "float16": ("<f2", 2)}
+    _DEPTH_DTYPES = ("float32", "float16")
 
     def depth(self, height=None, width=None, dtype: str = "float32", out=None, mask=None):
         """The depth map of every env's camera frame, on the device (dtsim_depth, include/dtsim.h): [N, h, w], per pixel the smallest eye depth
@@ -734,31 +761,13 @@ class BatchedSimulator:
         of which only those pixels are traced.  dtype "float32" or "float16".  `out` may be any C-contiguous object with
         __cuda_array_interface__ of that shape and dtype; `mask` as render()'s (after render(mask=m) pass the same m): only the selected envs'
         rows are written (the others keep their content; in the simulator's own buffer that is whatever an earlier call left).  A bad size, dtype, out or mask raises ValueError before anything is launched."""
-        import torch
         if dtype not in self._DEPTH_DTYPES:
             raise ValueError(f"depth: dtype {dtype!r}: 'float32' or 'float16'")
-        typestr, item = self._DEPTH_DTYPES[dtype]
-        h = self.camera_height if height is None else int(height)
-        w = self.camera_width if width is None else int(width)
-        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
-            raise ValueError(f"depth: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
-                             "(depth is point-sampled, never filtered)")
+        h, w = self._map_size("depth", "depth is", height, width)
         mp = self._mask_arg(mask)
-        shape = (self.num_envs, h, w)
-        if out is None:
-            key = (h, w, dtype)
-            if getattr(self, "_depth_key", None) != key:
-                # (empty, as observe()'s buffer: a fill would run on torch's stream, unordered against the handle's own, and race with the
-                # kernel's stores; a first call that is masked leaves the other rows uninitialised)
-                self._depth_buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device_index}")
-                self._depth_key = key
-            out = self._depth_buf
-        ptr = C.c_void_p(self._out_ptr(out, shape, typestr, item, "depth"))
+        out, ptr = self._result("depth", out, (self.num_envs, h, w), dtype)
         flags = _ffi.DEPTH_F16 if dtype == "float16" else 0
-        if mp is None:
-            _ffi.check(self._lib, self._lib.dtsim_depth(self._h, ptr, h, w, flags))
-        else:
-            _ffi.check(self._lib, self._lib.dtsim_depth_masked(self._h, ptr, h, w, flags, mp))
+        self._map_pass(self._lib.dtsim_depth, self._lib.dtsim_depth_masked, mp, ptr, h, w, flags)
         return out
 
     def label_assets(self):
@@ -807,26 +816,11 @@ class BatchedSimulator:
         nearest texel of its texture, for a mesh object the class of its mesh (the tables of set_label_assets(); the defaults, installed at
         the first call: dtsim/labels.py).  Never filtered.  Needs a preceding render() of the current state.  Size, `out` and `mask` as
         depth()'s; a bad size, out or mask raises ValueError before anything is launched."""
-        import torch
-        h = self.camera_height if height is None else int(height)
-        w = self.camera_width if width is None else int(width)
-        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
-            raise ValueError(f"labels: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
-                             "(labels are point-sampled, never filtered)")
+        h, w = self._map_size("labels", "labels are", height, width)
         mp = self._mask_arg(mask)
-        shape = (self.num_envs, h, w)
-        if out is None:
-            if getattr(self, "_labels_key", None) != (h, w):
-                self._labels_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")     # (empty: as depth()'s buffer)
-                self._labels_key = (h, w)
-            out = self._labels_buf
-        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "labels"))
-        if not getattr(self, "_have_label_assets", False):
-            self.set_label_assets()
-        if mp is None:
-            _ffi.check(self._lib, self._lib.dtsim_labels(self._h, ptr, h, w, 0))
-        else:
-            _ffi.check(self._lib, self._lib.dtsim_labels_masked(self._h, ptr, h, w, 0, mp))
+        out, ptr = self._result("labels", out, (self.num_envs, h, w))
+        self._need_label_assets()
+        self._map_pass(self._lib.dtsim_labels, self._lib.dtsim_labels_masked, mp, ptr, h, w, 0)
         return out
 
     def instances(self, height=None, width=None, out=None, mask=None, labels_out=None):
@@ -837,31 +831,17 @@ class BatchedSimulator:
         also writes labels()'s bytes into it, from the same classification (the default tables are installed at first use, as labels()
         does); without it no table is needed.  Needs a preceding render() of the current state.  Size, `out` and `mask` as labels()'s; a bad
         size, out, labels_out or mask raises ValueError before anything is launched."""
-        import torch
-        h = self.camera_height if height is None else int(height)
-        w = self.camera_width if width is None else int(width)
-        if h <= 0 or w <= 0 or self.camera_height % h or self.camera_width % w:
-            raise ValueError(f"instances: a {h} x {w} map of {self.camera_height} x {self.camera_width} frames -- each size must divide the camera's "
-                             "(instance ids are point-sampled, never filtered)")
+        h, w = self._map_size("instances", "instance ids are", height, width)
         mp = self._mask_arg(mask)
         shape = (self.num_envs, h, w)
-        if out is None:
-            if getattr(self, "_inst_key", None) != (h, w):
-                self._inst_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")       # (empty: as depth()'s buffer)
-                self._inst_key = (h, w)
-            out = self._inst_buf
-        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "instances"))
+        out, ptr = self._result("instances", out, shape)
         lp = None
         if labels_out is not None:
             lp = C.c_void_p(self._out_ptr(labels_out, shape, "|u1", 1, "instances: labels_out"))
             if lp.value == ptr.value:
                 raise ValueError("instances: labels_out and out are one buffer")
-            if not getattr(self, "_have_label_assets", False):
-                self.set_label_assets()
-        if mp is None:
-            _ffi.check(self._lib, self._lib.dtsim_instances(self._h, ptr, lp, h, w, 0))
-        else:
-            _ffi.check(self._lib, self._lib.dtsim_instances_masked(self._h, ptr, lp, h, w, 0, mp))
+            self._need_label_assets()
+        self._map_pass(self._lib.dtsim_instances, self._lib.dtsim_instances_masked, mp, ptr, lp, h, w, 0)
         return out
 
     def boxes(self, inst, out=None, mask=None):
@@ -877,9 +857,7 @@ class BatchedSimulator:
         mp = self._mask_arg(mask)
         shape = (self.num_envs, _ffi.MAX_OBJECTS, 5)
         if out is None:
-            if getattr(self, "_boxes_buf", None) is None:
-                self._boxes_buf = torch.empty(shape, dtype=torch.int32, device=f"cuda:{self.device_index}")      # (empty: as depth()'s buffer)
-            out = self._boxes_buf
+            out, _ = self._result("boxes", None, shape, "int32")
         else:
             self._dev_tensor(out, "boxes: out", shape=shape, dtypes=(torch.int32,))
         _ffi.check(self._lib, self._lib.dtsim_boxes(self._h, C.c_void_p(inst.data_ptr()), int(inst.shape[1]), int(inst.shape[2]),
@@ -897,7 +875,6 @@ class BatchedSimulator:
         current state and needs no render().  `out` as labels()'s, `mask` as render()'s (only the selected envs' rows are written).  A size
         outside 1 .. 1024, a cell that is not finite and positive, rows_behind outside 0 .. height, a bad out, instances_out or mask
         raise ValueError before the library is called."""
-        import torch
         try:
             h, w, rb, c = int(height), int(width), int(rows_behind), float(cell)
             whole = h == height and w == width and rb == rows_behind
@@ -915,19 +892,13 @@ class BatchedSimulator:
             raise ValueError("bev: the simulator was built with render=False and holds no render tables")
         mp = self._mask_arg(mask)
         shape = (self.num_envs, h, w)
-        if out is None:
-            if getattr(self, "_bev_key", None) != (h, w):
-                self._bev_buf = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device_index}")        # (empty: as depth()'s buffer)
-                self._bev_key = (h, w)
-            out = self._bev_buf
-        ptr = C.c_void_p(self._out_ptr(out, shape, "|u1", 1, "bev"))
+        out, ptr = self._result("bev", out, shape)
         ip = None
         if instances_out is not None:
             ip = C.c_void_p(self._out_ptr(instances_out, shape, "|u1", 1, "bev: instances_out"))
             if ip.value == ptr.value:
                 raise ValueError("bev: instances_out and out are one buffer")
-        if not getattr(self, "_have_label_assets", False):
-            self.set_label_assets()
+        self._need_label_assets()
         _ffi.check(self._lib, self._lib.dtsim_bev(self._h, ptr, ip, h, w, c, rb, 0, mp))
         return out
 
@@ -978,9 +949,7 @@ class BatchedSimulator:
         """[n_maps, MAX_OBJECTS] uint8 (numpy): the class labels() gives each object slot of each resident map -- mesh_class[mesh of object k
         of map m] under the table installed through set_label_assets(), or the default one (label_assets()) while none is -- and 0 past a
         map's object count.  A detector's class target for row k of boxes() in env e is object_classes()[map_id[e], k]."""
-        mc = getattr(self, "_mesh_class", None)
-        if mc is None:
-            mc = self.label_assets()[1]
+        mc = self._mesh_class if self._mesh_class is not None else self.label_assets()[1]
         out = np.zeros((len(self.maps), _ffi.MAX_OBJECTS), np.uint8)
         for m, mp in enumerate(self.maps):
             for k, o in enumerate(mp.objects):

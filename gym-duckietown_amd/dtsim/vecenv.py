@@ -46,55 +46,58 @@ average (its learners' imresize then rescales by the array's min and max); here 
 resize of every other frame -- `BatchedSimulator.blend_frames(out=float32)` gives the unrounded value.  Memory: L extra frame batches (15 GB for
 the default window at N = 4096, 640 x 480).  `motion_blur=False` (the default) runs the paths above, call for call.
 
-Depth (`depth_shape=(h, w)`, each dividing the camera's size; `depth_dtype` "float32" or "float16"): `info["depth"]` is one persistent
-`[N, h, w]` device tensor with the depth map (`dtsim_depth`, include/dtsim.h: smallest eye depth over the four MSAA samples of the frame's
-source pixel, +inf = sky, 0 = the fisheye's black border; point-sampled, never filtered) of the state whose observation `obs` shows -- for an
-env restarted in the step, the first frame of its new episode.  `reset()` keeps returning `obs` alone; the map of the first frames is
-`env.depth`, the same tensor.  With `final_obs=True`, `info["final_depth"]` is a second persistent tensor whose rows where
-`info["final_obs_mask"]` is set hold the depth of the final state (the other rows are unspecified); the order is full render -> observe ->
-depth -> `dtsim_copy_rows` -> `dtsim_reset_done` -> masked render -> masked observe -> `dtsim_depth_masked`.  `frame_stack`, `grayscale` and
-`obs_shape=None` compose (depth is never stacked); `motion_blur` (its observation shows three states) and `camera_rand` (a distortion table
-per env) raise ValueError.  `depth_shape=None` (the default) runs the paths above, call for call.
+Auxiliary outputs (depth, labels, instances, boxes, bev, bev_instances; each off by default, and an option left off makes no new call).  What
+they share, said once.  Output X is one persistent device tensor, `info["X"]`, of the state whose observation `obs` shows -- for an env
+restarted in the step, the first state of its new episode.  `reset()` keeps returning `obs` alone: after it the output is `env.X`, the same
+tensor (None while X is off).  With `final_obs=True`, `info["final_X"]` is a second persistent tensor whose rows where
+`info["final_obs_mask"]` is set hold X of the final state (the other rows are unspecified).  The passes stand together after every observe,
+in the order depth, labels, instances, boxes, bev, masked where the observe is masked: full render -> observe -> passes ->
+`dtsim_copy_rows` of each -> `dtsim_reset_done` -> masked render -> masked observe -> masked passes.  They compose with one another and with
+`frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand` (no output is ever stacked).  Depth, labels, instances and boxes are CAMERA
+post-passes: point-sampled from the frame's source pixels, never filtered, so each size of their `(h, w)` must divide the camera's; and they
+read the single distortion table and one rendered state, so `motion_blur` (its observation shows the states of its window) and
+`camera_rand` (a distortion table per env) raise ValueError.
 
-Labels (`label_shape=(h, w)`, each dividing the camera's size): `info["labels"]` is one persistent `[N, h, w]` `torch.uint8` device tensor
-with the semantic label map (`dtsim_labels`, include/dtsim.h: per pixel the class of the surface that sets the depth there -- 0 the fisheye's
-black border, 1 sky, 2 ground, tiles by the nearest texel's class, mesh objects by their mesh's; the default classes: dtsim/labels.py;
-point-sampled, never filtered) of the state `obs` shows; after `reset()` it is `env.labels`, the same tensor.  With `final_obs=True`,
-`info["final_labels"]` holds the finished envs' rows as `info["final_depth"]` does.  The pass stands where the depth pass does, after it
-when both are on, and composes with `depth_shape`, `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand`; `motion_blur` and
-`camera_rand` raise ValueError, for depth's reasons.  `label_shape=None` (the default) makes no new call.
+Depth (`depth_shape=(h, w)`; `depth_dtype` "float32" or "float16"): `info["depth"]` is the `[N, h, w]` depth map (`dtsim_depth`,
+include/dtsim.h: smallest eye depth over the four MSAA samples of the frame's source pixel, +inf = sky, 0 = the fisheye's black border).
 
-Instances and boxes (`instance_shape=(h, w)`, each dividing the camera's size; `boxes=True` needs it): `info["instances"]` is one persistent
-`[N, h, w]` `torch.uint8` device tensor with the instance map (`dtsim_instances`, include/dtsim.h: per pixel o + 1 where the surface that sets
-the depth there is mesh object o of the env's own map -- the column of the `DTSIM_FIELD_OBJ_*` fields --, 0 on every other surface and in the
-fisheye's black border) of the state `obs` shows, and with `boxes=True` `info["boxes"]` one persistent `[N, 64, 5]` `torch.int32` tensor, row k
-= x0, y0, x1, y1, n of object k in that map's pixels (`dtsim_boxes`; all 0 for an object not in view; its class:
-`sim.object_classes()[map_id, k]`).  After `reset()` they are `env.instances` / `env.boxes`, the same tensors.  With `final_obs=True`,
-`info["final_instances"]` / `info["final_boxes"]` hold the finished envs' rows as `info["final_labels"]` does.  The pass stands where the
-depth pass does, after depth and labels; with `label_shape == instance_shape` ONE `dtsim_instances` launch fills both maps from one
-classification and `dtsim_labels` is not called.  `motion_blur` and `camera_rand` raise ValueError, for depth's reasons.
-`instance_shape=None` (the default) makes no new call.
+Labels (`label_shape=(h, w)`): `info["labels"]` is the `[N, h, w]` `torch.uint8` semantic label map (`dtsim_labels`, include/dtsim.h: per
+pixel the class of the surface that sets the depth there -- 0 the fisheye's black border, 1 sky, 2 ground, tiles by the nearest texel's
+class, mesh objects by their mesh's; the default classes: dtsim/labels.py).
+
+Instances and boxes (`instance_shape=(h, w)`; `boxes=True` needs it): `info["instances"]` is the `[N, h, w]` `torch.uint8` instance map
+(`dtsim_instances`, include/dtsim.h: per pixel o + 1 where the surface that sets the depth there is mesh object o of the env's own map --
+the column of the `DTSIM_FIELD_OBJ_*` fields --, 0 on every other surface and in the fisheye's black border), and with `boxes=True`
+`info["boxes"]` a `[N, 64, 5]` `torch.int32` tensor, row k = x0, y0, x1, y1, n of object k in that map's pixels (`dtsim_boxes`; all 0 for an
+object not in view; its class: `sim.object_classes()[map_id, k]`).  With `label_shape == instance_shape` ONE `dtsim_instances` launch fills
+both maps from one classification and `dtsim_labels` is not called.
 
 Bird's-eye view (`bev_shape=(h, w)`, each 1 .. 1024; `bev_cell` metres per cell, `bev_rows_behind` of the h rows behind the agent;
-`bev_instances=True` needs it): `info["bev"]` is one persistent `[N, h, w]` `torch.uint8` device tensor with the egocentric label map
-(`dtsim_bev`, include/dtsim.h: cell (i, j) = the class at the point (h - rows_behind - i - 0.5) cells ahead of the AGENT and (j + 0.5 - w / 2)
-cells to its right -- the mesh class of the lowest-indexed visible object whose collision rectangle holds the point, else the nearest
-texel's class of the tile under it, else 2, the ground; never 0 or 1, never filtered) of the state `obs` shows -- for a restarted env its new
-episode's first state --, and with `bev_instances=True` `info["bev_instances"]` the id map of the same launch (o + 1 / 0, the ids of
-`info["instances"]`).  After `reset()` they are `env.bev` / `env.bev_instances`, the same tensors.  With `final_obs=True`,
-`info["final_bev"]` / `info["final_bev_instances"]` hold the finished envs' rows as `info["final_labels"]` does.  The pass stands where the
-depth pass does, after the instance pass, masked where that one is masked.  It reads the state, not the camera, so it composes with
-everything: `camera_rand` and `motion_blur` are allowed -- under `motion_blur` the observation blends the frames of the window's states,
-and the map is that of the state after the last sub-update, the newest of them.  `bev_shape=None` (the default) makes no new call.
+`bev_instances=True` needs it): `info["bev"]` is the `[N, h, w]` `torch.uint8` egocentric label map (`dtsim_bev`, include/dtsim.h: cell
+(i, j) = the class at the point (h - rows_behind - i - 0.5) cells ahead of the AGENT and (j + 0.5 - w / 2) cells to its right -- the mesh
+class of the lowest-indexed visible object whose collision rectangle holds the point, else the nearest texel's class of the tile under it,
+else 2, the ground; never 0 or 1, never filtered), and with `bev_instances=True` `info["bev_instances"]` the id map of the same launch
+(o + 1 / 0, the ids of `info["instances"]`).  It reads the state, not the camera, so it composes with everything: `camera_rand` and
+`motion_blur` are allowed -- under `motion_blur` the observation blends the frames of the window's states, and the map is that of the state
+after the last sub-update, the newest of them.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple, Union
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import _ffi
 from .batched import BatchedSimulator
+
+
+class _Aux(NamedTuple):
+    """One auxiliary output of the env.  The constructor lists them in pass order; allocation, the final rows and `info` go by that list."""
+    name: str                       # env.<name> and info["<name>"]; the finished envs' rows: info["final_<name>"]
+    dtype: str                      # torch's name of the element type
+    tail: Optional[Tuple[int, ...]]  # the shape after N; None: the output is off
+    camera: bool                    # a camera post-pass: it reads the single distortion table and ONE rendered state, so its option went
+    #                                 through _camera_map_shape (no motion_blur, no camera_rand, a size that divides the camera's)
 
 
 class DuckietownVecEnv:
@@ -118,59 +121,14 @@ class DuckietownVecEnv:
         self._blur = self._blur_window(motion_blur)                 # the window's integer weights, oldest frame first, or None
         if depth_dtype not in BatchedSimulator._DEPTH_DTYPES:
             raise ValueError(f"depth_dtype {depth_dtype!r}: 'float32' or 'float16'")
-        self.depth_shape, self.depth_dtype = None, depth_dtype
-        if depth_shape is not None:
-            if self._blur:
-                raise ValueError("depth_shape with motion_blur is not supported (the blurred observation shows the three states of its window: "
-                                 "no single state's depth belongs to it)")
-            if sim_kwargs.get("camera_rand"):
-                raise ValueError("depth_shape with camera_rand is not supported (dtsim_depth reads the single distortion table, camera_rand "
-                                 "installs one per env)")
-            try:
-                dh, dw = (int(v) for v in depth_shape)
-            except (TypeError, ValueError):
-                raise ValueError(f"depth_shape must be (h, w), got {depth_shape!r}") from None
-            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
-            if dh <= 0 or dw <= 0 or H % dh or W % dw:
-                raise ValueError(f"depth_shape {(dh, dw)}: each size must divide the camera's {(H, W)} (depth is point-sampled, never filtered)")
-            self.depth_shape = (dh, dw)
-        self.label_shape = None
-        if label_shape is not None:
-            if self._blur:
-                raise ValueError("label_shape with motion_blur is not supported (the blurred observation shows the three states of its window: "
-                                 "no single state's labels belong to it)")
-            if sim_kwargs.get("camera_rand"):
-                raise ValueError("label_shape with camera_rand is not supported (dtsim_labels reads the single distortion table, camera_rand "
-                                 "installs one per env)")
-            try:
-                lh, lw = (int(v) for v in label_shape)
-            except (TypeError, ValueError):
-                raise ValueError(f"label_shape must be (h, w), got {label_shape!r}") from None
-            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
-            if lh <= 0 or lw <= 0 or H % lh or W % lw:
-                raise ValueError(f"label_shape {(lh, lw)}: each size must divide the camera's {(H, W)} (labels are point-sampled, never filtered)")
-            self.label_shape = (lh, lw)
-        self.instance_shape, self._want_boxes = None, bool(boxes)
-        if instance_shape is None:
-            if boxes:
-                raise ValueError("boxes=True needs instance_shape (the boxes are those of the instance map, in its pixels)")
-        else:
-            if self._blur:
-                raise ValueError("instance_shape with motion_blur is not supported (the blurred observation shows the three states of its "
-                                 "window: no single state's instances belong to it)")
-            if sim_kwargs.get("camera_rand"):
-                raise ValueError("instance_shape with camera_rand is not supported (dtsim_instances reads the single distortion table, "
-                                 "camera_rand installs one per env)")
-            try:
-                ih, iw = (int(v) for v in instance_shape)
-            except (TypeError, ValueError):
-                raise ValueError(f"instance_shape must be (h, w), got {instance_shape!r}") from None
-            H, W = int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640))
-            if ih <= 0 or iw <= 0 or H % ih or W % iw:
-                raise ValueError(f"instance_shape {(ih, iw)}: each size must divide the camera's {(H, W)} (instance ids are point-sampled, "
-                                 "never filtered)")
-            self.instance_shape = (ih, iw)
-        self.bev_shape, self.bev_cell, self.bev_rows_behind, self._want_bev_inst = None, bev_cell, bev_rows_behind, bool(bev_instances)
+        self.depth_dtype = depth_dtype
+        cam = (int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640)))
+        self.depth_shape = self._camera_map_shape("depth_shape", depth_shape, cam, sim_kwargs)
+        self.label_shape = self._camera_map_shape("label_shape", label_shape, cam, sim_kwargs)
+        if boxes and instance_shape is None:
+            raise ValueError("boxes=True needs instance_shape (the boxes are those of the instance map, in its pixels)")
+        self.instance_shape = self._camera_map_shape("instance_shape", instance_shape, cam, sim_kwargs)
+        self.bev_shape, self.bev_cell, self.bev_rows_behind = None, bev_cell, bev_rows_behind
         if bev_shape is None:
             if bev_instances:
                 raise ValueError("bev_instances=True needs bev_shape (the ids are those of the bird's-eye map, in its cells)")
@@ -190,6 +148,12 @@ class DuckietownVecEnv:
             if sim_kwargs.get("render") is False:
                 raise ValueError("bev_shape needs render=True (the pass reads the render tables)")
             self.bev_shape, self.bev_cell, self.bev_rows_behind = (bh, bw), bc, brb
+        outputs = (_Aux("depth", depth_dtype, self.depth_shape, True),
+                   _Aux("labels", "uint8", self.label_shape, True),
+                   _Aux("instances", "uint8", self.instance_shape, True),
+                   _Aux("boxes", "int32", (_ffi.MAX_OBJECTS, 5) if boxes else None, True),
+                   _Aux("bev", "uint8", self.bev_shape, False),
+                   _Aux("bev_instances", "uint8", self.bev_shape if bev_instances else None, False))
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -209,34 +173,17 @@ class DuckietownVecEnv:
         self.obs_shape, self.chw, self.normalize = obs_shape, chw, normalize
         self.final_obs = bool(final_obs)
         self._final = None                                          # info["final_obs"], allocated at the first step
-        self.depth = self._final_depth = None                       # info["depth"] / info["final_depth"]: persistent [N, h, w] tensors
-        if self.depth_shape is not None:
-            self.depth = torch.zeros((num_envs, *self.depth_shape), dtype=getattr(torch, depth_dtype), device=self.device)
-            if self.final_obs:
-                self._final_depth = torch.zeros_like(self.depth)
-        self.labels = self._final_labels = None                     # info["labels"] / info["final_labels"]: persistent [N, h, w] uint8 tensors
-        if self.label_shape is not None:
-            self.labels = torch.zeros((num_envs, *self.label_shape), dtype=torch.uint8, device=self.device)
-            if self.final_obs:
-                self._final_labels = torch.zeros_like(self.labels)
-        # info["instances"] / info["boxes"] and their final_ rows: persistent [N, h, w] uint8 / [N, MAX_OBJECTS, 5] int32 tensors
-        self.instances = self.boxes = self._final_instances = self._final_boxes = None
-        if self.instance_shape is not None:
-            self.instances = torch.zeros((num_envs, *self.instance_shape), dtype=torch.uint8, device=self.device)
-            if self._want_boxes:
-                self.boxes = torch.zeros((num_envs, _ffi.MAX_OBJECTS, 5), dtype=torch.int32, device=self.device)
-            if self.final_obs:
-                self._final_instances = torch.zeros_like(self.instances)
-                self._final_boxes = torch.zeros_like(self.boxes) if self._want_boxes else None
-        # info["bev"] / info["bev_instances"] and their final_ rows: persistent [N, h, w] uint8 tensors
-        self.bev = self.bev_instances = self._final_bev = self._final_bev_instances = None
-        if self.bev_shape is not None:
-            self.bev = torch.zeros((num_envs, *self.bev_shape), dtype=torch.uint8, device=self.device)
-            if self._want_bev_inst:
-                self.bev_instances = torch.zeros_like(self.bev)
-            if self.final_obs:
-                self._final_bev = torch.zeros_like(self.bev)
-                self._final_bev_instances = torch.zeros_like(self.bev) if self._want_bev_inst else None
+        # The live tensor of every output and, with final_obs, its final_ twin.  (zeros, once: the rows of envs that have not finished yet, or
+        # that a first masked pass leaves out, hold no stale memory -- two envs run alike then return the same bytes in EVERY row, whatever
+        # the allocator handed out.)
+        self._aux = []                                              # (name, live tensor, final_ twin or None) of the outputs that are on
+        for a in outputs:
+            live = final = None
+            if a.tail is not None:
+                live = torch.zeros((num_envs, *a.tail), dtype=getattr(torch, a.dtype), device=self.device)
+                final = torch.zeros_like(live) if self.final_obs else None
+                self._aux.append((a.name, live, final))
+            setattr(self, a.name, live)                             # env.depth, env.labels, ...: the tensor info[name] returns, or None
         sim = self.sim
         self._reward = torch.as_tensor(sim.field_device(_ffi.FIELD_REWARD), device=self.device)
         self._done = torch.as_tensor(sim.field_device(_ffi.FIELD_DONE), device=self.device)
@@ -254,6 +201,27 @@ class DuckietownVecEnv:
         if self._blur:
             self._ring = [torch.empty_like(self._frames) for _ in self._blur]     # slot _cur holds the frame of the current state
             self._cur = 0
+
+    def _camera_map_shape(self, option, shape, cam, sim_kwargs):
+        """The (h, w) of a camera post-pass's option (None: off), or the ValueError that names the option and the cause."""
+        if shape is None:
+            return None
+        cause = None
+        if self._blur:
+            cause = "with motion_blur is not supported (the blurred observation shows the states of its window: no single state's map belongs to it)"
+        elif sim_kwargs.get("camera_rand"):
+            cause = "with camera_rand is not supported (the pass reads the single distortion table, camera_rand installs one per env)"
+        else:
+            try:
+                h, w = (int(v) for v in shape)
+            except (TypeError, ValueError):
+                cause = f"must be (h, w), got {shape!r}"
+            else:
+                if h <= 0 or w <= 0 or cam[0] % h or cam[1] % w:
+                    cause = f"{(h, w)}: each size must divide the camera's {cam} (the map is point-sampled, never filtered)"
+        if cause:
+            raise ValueError(f"{option} {cause}")
+        return h, w
 
     @staticmethod
     def _blur_window(motion_blur):
@@ -288,11 +256,10 @@ class DuckietownVecEnv:
         sim.push_observation(self._stack, o, first=first, mask=mask, grayscale=self.grayscale)
         return self._stack.view(self._stack_shape)
 
-    def _depth_pass(self, mask=None):
-        """depth_shape / label_shape / instance_shape: the depth, then the labels, then the instances and their boxes, of the state the last
-        render() showed, into self.depth / self.labels / self.instances / self.boxes (`mask`: only those envs' rows).  Labels and instances
-        of one shape come from one launch.  bev_shape: then the bird's-eye map (and its ids) of the current state into self.bev
-        (/ self.bev_instances)."""
+    def _map_passes(self, mask=None):
+        """The passes of the outputs that are on, in the table's order, each into the env's own tensor (`mask`: only those envs' rows): of the
+        state the last render() showed the depth, then the labels, then the instances and their boxes -- labels and instances of one shape
+        come from one launch --; then, of the current state, the bird's-eye map (and its ids)."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
         fused = self.labels is not None and self.label_shape == self.instance_shape
@@ -308,33 +275,17 @@ class DuckietownVecEnv:
                          instances_out=self.bev_instances)
 
     def _keep_final(self, obs, done, info):
-        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history), of the depth map, the label map, the instance map,
-        the boxes and the bird's-eye maps, before the reset rewrites them."""
+        """final_obs: the finished envs' rows of `obs` (stacked: of the whole history) and of every output that is on, before the reset
+        rewrites them."""
         src = self._stack if self._stacked else obs
         if self._final is None:
-            # (zeros, once, on our stream: the rows of envs that have not finished yet hold no stale memory -- two envs run alike then
-            # return the same bytes in EVERY row, whatever the allocator handed out; as the depth / label / instance buffers)
+            # (zeros, once, on our stream: for the reason the outputs' tensors are)
             self._final = self.torch.zeros_like(src)
         self.sim.copy_rows(self._final, src, done)
         info["final_obs"], info["final_obs_mask"] = self._final.view(self._stack_shape) if self._stacked else self._final, done
-        if self.depth is not None:
-            self.sim.copy_rows(self._final_depth, self.depth, done)
-            info["final_depth"] = self._final_depth
-        if self.labels is not None:
-            self.sim.copy_rows(self._final_labels, self.labels, done)
-            info["final_labels"] = self._final_labels
-        if self.instances is not None:
-            self.sim.copy_rows(self._final_instances, self.instances, done)
-            info["final_instances"] = self._final_instances
-        if self.boxes is not None:
-            self.sim.copy_rows(self._final_boxes, self.boxes, done)
-            info["final_boxes"] = self._final_boxes
-        if self.bev is not None:
-            self.sim.copy_rows(self._final_bev, self.bev, done)
-            info["final_bev"] = self._final_bev
-        if self.bev_instances is not None:
-            self.sim.copy_rows(self._final_bev_instances, self.bev_instances, done)
-            info["final_bev_instances"] = self._final_bev_instances
+        for name, live, final in self._aux:
+            self.sim.copy_rows(final, live, done)
+            info["final_" + name] = final
 
     def _enter(self):
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))     # e.g. the policy that produced the actions
@@ -347,7 +298,7 @@ class DuckietownVecEnv:
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
             obs = self._show(first=self._all)
-            self._depth_pass()
+            self._map_passes()
             if self._blur:
                 self._ring[0].copy_(self._frames)                   # the next window's first frame
                 self._cur = 0
@@ -379,8 +330,7 @@ class DuckietownVecEnv:
     def step(self, actions):
         """One sequence for every configuration.  With final_obs or motion_blur the batch is shown BEFORE the reset -- what the reference's
         step() returns, blurred: the blend of the ring's L slots in the handle's own frame buffer -- and the restarted envs alone are shown
-        again after it, unblurred; else the reset comes first and one pass shows every env.  A post-pass of a new output goes where
-        _depth_pass stands."""
+        again after it, unblurred; else the reset comes first and one pass shows every env.  The pass of a new output goes into _map_passes."""
         t, sim, blur = self.torch, self.sim, self._blur
         self._enter()
         with t.cuda.stream(self.stream):
@@ -397,7 +347,7 @@ class DuckietownVecEnv:
                 sim.bind_frames(None)
             if self.final_obs or blur:
                 obs = self._show(render=not blur)                   # every env; stacked: every history now ends with this frame
-                self._depth_pass()
+                self._map_passes()
                 if self.final_obs:
                     self._keep_final(obs, done, info)
                 sim.reset_done()
@@ -405,7 +355,7 @@ class DuckietownVecEnv:
                     self._cur = (self._cur + L - 1) % L             # the newest slot opens the next window
                     sim.bind_frames(self._ring[self._cur].data_ptr())
                 obs = self._show(mask=done, first=done)             # the restarted envs, only they: their first frame (in every slot)
-                self._depth_pass(mask=done)
+                self._map_passes(mask=done)
                 if blur:
                     if self.obs_shape is None:
                         sim.copy_rows(self._frames, self._ring[self._cur], done)   # (`obs` is the handle's own batch, the render went into the slot)
@@ -413,19 +363,9 @@ class DuckietownVecEnv:
             else:
                 sim.reset_done()
                 obs = self._show(first=done)
-                self._depth_pass()
-            if self.depth is not None:
-                info["depth"] = self.depth
-            if self.labels is not None:
-                info["labels"] = self.labels
-            if self.instances is not None:
-                info["instances"] = self.instances
-            if self.boxes is not None:
-                info["boxes"] = self.boxes
-            if self.bev is not None:
-                info["bev"] = self.bev
-            if self.bev_instances is not None:
-                info["bev_instances"] = self.bev_instances
+                self._map_passes()
+            for name, live, _ in self._aux:
+                info[name] = live
         self._leave()
         return obs, reward, done, info
 

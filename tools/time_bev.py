@@ -12,6 +12,7 @@ sys.path[:0] = [os.path.join(ROOT, "gym-duckietown_amd"), os.path.join(ROOT, "te
 import numpy as np
 import torch
 from dtsim import BatchedSimulator, _ffi, assets
+from timing import alternating_rounds, median_spread
 
 N = int(os.environ.get("N", "4096"))
 MAPS = os.environ.get("MAPS", "small_loop,loop_pedestrians,crowd").split(",")
@@ -59,22 +60,8 @@ for MAP in MAPS:
                  "bev (classes + ids)": lambda: sim.bev(oh, ow, cell=cell, rows_behind=rb, out=out, instances_out=ids),
                  "copy of the map (d2d)": lambda: copy.copy_(out),
                  "labels 120 x 160": lambda: sim.labels(120, 160, out=lab)}
-        ms = {k: [] for k in calls}
-        torch.cuda.synchronize()
-        with torch.cuda.stream(stream):
-            for f in calls.values():
-                for _ in range(3):
-                    f()
-            for _ in range(ROUNDS):
-                for k, f in calls.items():
-                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    t0.record(stream)
-                    for _ in range(REPS):
-                        f()
-                    t1.record(stream)
-                    t1.synchronize()
-                    ms[k].append(t0.elapsed_time(t1) / REPS)
-        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        ms = alternating_rounds(stream, calls, REPS, ROUNDS)
+        med = {k: median_spread(v)[0] for k, v in ms.items()}
         kept, drawn = survivors(sim, oh, ow, cell, rb)
         for k, v in ms.items():
             print(f"  {oh:3d} x {ow:3d} at {cell:.2f} m  {k:22s}: median {med[k]:7.3f} ms per call (of {ROUNDS}: {min(v):.3f} .. {max(v):.3f})")

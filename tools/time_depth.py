@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
 import numpy as np
 import torch
 from dtsim import BatchedSimulator
+from timing import alternating_rounds, median_spread
 
 N = int(os.environ.get("N", "4096"))
 MAP = os.environ.get("MAP", "small_loop")
@@ -26,21 +27,9 @@ print(f"depth pass alone: {MAP} N={N} {W} x {H}{' fisheye' if FISHEYE else ''}{'
 for (h, w) in ((H // 4, W // 4), (H, W)):
     for dtype, item in (("float32", 4), ("float16", 2)):
         out = torch.empty((N, h, w), dtype=getattr(torch, dtype), device="cuda")
-        torch.cuda.synchronize()
-        with torch.cuda.stream(stream):
-            for _ in range(3):
-                sim.depth(h, w, dtype=dtype, out=out)
-            ms = []
-            for _ in range(3):                                  # three figures: the spread
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record(stream)
-                for _ in range(REPS):
-                    sim.depth(h, w, dtype=dtype, out=out)
-                t1.record(stream)
-                t1.synchronize()
-                ms.append(t0.elapsed_time(t1) / REPS)
+        # (three rounds: the spread)
+        m, lo, hi = median_spread(alternating_rounds(stream, {"depth": lambda: sim.depth(h, w, dtype=dtype, out=out)}, REPS, 3)["depth"])
         by = N * h * w * item
-        m = sorted(ms)[1]
-        print(f"  {h:3d} x {w:3d} {dtype}: {m:7.3f} ms per call (of three: {min(ms):.3f} .. {max(ms):.3f}), {by / 1e6:7.1f} MB written, {by / m / 1e9:6.3f} TB/s, "
+        print(f"  {h:3d} x {w:3d} {dtype}: {m:7.3f} ms per call (of three: {lo:.3f} .. {hi:.3f}), {by / 1e6:7.1f} MB written, {by / m / 1e9:6.3f} TB/s, "
               f"{N * h * w / m / 1e6:7.1f} G pixels/s")
 sim.close()

@@ -8,6 +8,7 @@ sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
 import numpy as np
 import torch
 from dtsim import BatchedSimulator
+from timing import alternating_rounds, median_spread
 
 N = int(os.environ.get("N", "4096"))
 MAP = os.environ.get("MAP", "small_loop")
@@ -30,22 +31,8 @@ for (h, w) in ((H // 4, W // 4), (H, W)):
     lab = torch.empty((N, h, w), dtype=torch.uint8, device="cuda")
     dep = torch.empty((N, h, w), dtype=torch.float32, device="cuda")
     calls = {"k_labels uint8": lambda: sim.labels(h, w, out=lab), "k_depth float32": lambda: sim.depth(h, w, out=dep)}
-    ms = {k: [] for k in calls}
-    torch.cuda.synchronize()
-    with torch.cuda.stream(stream):
-        for f in calls.values():
-            for _ in range(3):
-                f()
-        for _ in range(ROUNDS):
-            for k, f in calls.items():
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record(stream)
-                for _ in range(REPS):
-                    f()
-                t1.record(stream)
-                t1.synchronize()
-                ms[k].append(t0.elapsed_time(t1) / REPS)
-    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    ms = alternating_rounds(stream, calls, REPS, ROUNDS)
+    med = {k: median_spread(v)[0] for k, v in ms.items()}
     for k, v in ms.items():
         by = N * h * w * (1 if "labels" in k else 4)
         print(f"  {h:3d} x {w:3d} {k:16s}: median {med[k]:7.3f} ms per call (of {ROUNDS}: {min(v):.3f} .. {max(v):.3f}), {by / 1e6:7.1f} MB written, "
