@@ -179,6 +179,13 @@ struct dtsim {
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop): 1, 2 or 4
   DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
   ObserveSlot obs, obsc;          // dtsim_observe / dtsim_observe_cubic (and their masked forms)
+  // dtsim_ipm: the calibrations of dtsim_set_ipm_calibrations, and the shared camera's table of source pixels with the key it was built for
+  int n_ipm_cal = 0;
+  DevPtr<IpmCal> d_ipm_cal;         // [n_ipm_cal]
+  DevPtr<int32_t> d_ipm_env_cal;    // [N], or null: calibration 0 for every env
+  DevPtr<int32_t> d_ipm_table;      // [DTSIM_BEV_MAX_SIDE^2]: allocated at the first use and never moved, so a rebuild is stream-ordered
+  struct IpmKey { int oh = 0, ow = 0, rows_behind = 0; double cell = 0.0; uint64_t cal = 0; } ipm_key;   // cal = 0: no table yet
+  uint64_t ipm_cal_version = 1;     // counts the installs: a new calibration is a new key
   ProfSlot prof[DTSIM_KERNEL__COUNT];
 };
 
@@ -833,6 +840,65 @@ int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double ce
   render_scene(h, false, &R);
   dt_launch_bev(h->stream, R, h->A, h->maps.d_ocorners.get(), h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, cls, inst, oh, ow, cell,
                 rows_behind, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+int dtsim_set_ipm_calibrations(dtsim_t* h, int n_cal, const double* K, const double* D, const double* new_K, const int32_t* env_cal) {
+  if (!h) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: null handle");
+  if (n_cal < 0) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: n_cal %d", n_cal);
+  if (n_cal == 0 && (K || D || new_K || env_cal)) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: n_cal = 0 takes no tables");
+  if (n_cal > 0 && (!K || !D || !new_K)) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: null K, D or new_K");
+  if (n_cal > 1 && !env_cal) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: %d calibrations need env_cal", n_cal);
+  if (!h->frames) return fail(DTSIM_E_STATE, "dtsim_set_ipm_calibrations: handle created without DTSIM_F_RENDER");
+  std::vector<IpmCal> cals((size_t)n_cal);
+  for (int i = 0; i < n_cal; ++i)
+    if (!dt_ipm_pack_cal(cals[i], K + 9 * (size_t)i, D + 5 * (size_t)i, new_K + 9 * (size_t)i))
+      return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: calibration %d holds a value that is not finite, or its new_K has no inverse", i);
+  if (env_cal)
+    for (int e = 0; e < h->N; ++e)
+      if (env_cal[e] < 0 || env_cal[e] >= n_cal) return fail(DTSIM_E_INVALID, "dtsim_set_ipm_calibrations: env_cal[%d] = %d outside [0, %d)", e, env_cal[e], n_cal);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  DevPtr<IpmCal> d_cal;
+  DevPtr<int32_t> d_env;
+  if (n_cal) HIPCHK(dev_upload(d_cal, cals.data(), cals.size()));
+  if (env_cal) HIPCHK(dev_upload(d_env, env_cal, (size_t)h->N));
+  HIPCHK(hipStreamSynchronize(h->stream));           // the stream may still read the old tables
+  h->d_ipm_cal = std::move(d_cal); h->d_ipm_env_cal = std::move(d_env);
+  h->n_ipm_cal = n_cal;
+  ++h->ipm_cal_version;
+  return DTSIM_OK;
+}
+
+int dtsim_ipm(dtsim_t* h, uint8_t* img, uint8_t* valid, int32_t* src, int oh, int ow, double cell, int rows_behind, uint32_t flags,
+              const uint8_t* mask) {
+  if (!h || (!img && !valid && !src)) return fail(DTSIM_E_INVALID, "dtsim_ipm: null argument");
+  const void *pi = img, *pv = valid, *ps = src;
+  if ((pi && (pi == pv || pi == ps)) || (pv && pv == ps)) return fail(DTSIM_E_INVALID, "dtsim_ipm: two outputs are one buffer");
+  if (flags & ~(uint32_t)DTSIM_IPM_CHW) return fail(DTSIM_E_INVALID, "dtsim_ipm: unknown flags 0x%x", flags);
+  if (oh < 1 || ow < 1 || oh > DTSIM_BEV_MAX_SIDE || ow > DTSIM_BEV_MAX_SIDE)
+    return fail(DTSIM_E_INVALID, "dtsim_ipm: a %d x %d map (each size 1 .. %d)", ow, oh, DTSIM_BEV_MAX_SIDE);
+  if (!std::isfinite(cell) || !(cell > 0.0)) return fail(DTSIM_E_INVALID, "dtsim_ipm: cell %g (metres per cell: finite, > 0)", cell);
+  if (rows_behind < 0 || rows_behind > oh) return fail(DTSIM_E_INVALID, "dtsim_ipm: rows_behind %d outside [0, %d]", rows_behind, oh);
+  if (!h->frames) return fail(DTSIM_E_STATE, "dtsim_ipm: handle created without DTSIM_F_RENDER");
+  if (!h->have_reset) return fail(DTSIM_E_STATE, "dtsim_ipm before dtsim_reset");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  IpmArgs a{};
+  a.frames = h->frames; a.N = h->N; a.W = h->cfg.cam_width; a.H = h->cfg.cam_height;
+  a.img = img; a.valid = valid; a.src = src; a.oh = oh; a.ow = ow; a.cell = cell; a.rows_behind = rows_behind;
+  a.chw = (flags & DTSIM_IPM_CHW) != 0; a.mask = mask;
+  const bool per_env = (h->cfg.flags & DTSIM_F_DOMAIN_RAND) != 0;
+  if (!per_env && h->n_ipm_cal <= 1) {               // the shared camera is rigid in the agent's frame: one table for every env and step
+    if (!h->d_ipm_table) HIPCHK(dev_alloc(h->d_ipm_table, (size_t)DTSIM_BEV_MAX_SIDE * DTSIM_BEV_MAX_SIDE));
+    dtsim::IpmKey& k = h->ipm_key;
+    if (k.cal != h->ipm_cal_version || k.oh != oh || k.ow != ow || k.rows_behind != rows_behind || k.cell != cell) {
+      dt_launch_ipm_table(h->stream, h->d_ipm_table.get(), h->d_ipm_cal.get(), a.W, a.H, oh, ow, cell, rows_behind);
+      k.cal = h->ipm_cal_version; k.oh = oh; k.ow = ow; k.rows_behind = rows_behind; k.cell = cell;
+    }
+    dt_launch_ipm_gather(h->stream, a, h->d_ipm_table.get());
+  } else {
+    dt_launch_ipm_env(h->stream, a, h->A, per_env, h->d_ipm_cal.get(), h->n_ipm_cal, h->d_ipm_env_cal.get());
+  }
   HIPCHK(hipGetLastError());
   return DTSIM_OK;
 }

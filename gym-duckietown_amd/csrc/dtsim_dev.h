@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dtsim.h"
+#include "ipm_project.h"
 #include "observe_plan.h"
 #include "scene_tables.h"
 #include "state_fields.h"
@@ -179,6 +180,27 @@ void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
                    const uint8_t* mesh_class, int n_mesh_class, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind,
                    const uint8_t* mask);
+// the ground-projected camera image of dtsim_ipm (render_ipm.inc; the projection: ipm_project.h).  One call's arguments: img = [N][oh][ow][3]
+// bytes, or [N][3][oh][ow] with chw, valid = [N][oh][ow] bytes, src = [N][oh][ow] int32 -- any may be null --, taken from `frames`
+// ([N][H][W][3]); mask: device, [N] bytes, or null = every env.  The caller checked the sizes, cell and rows_behind as dtsim_bev's.
+struct IpmArgs {
+  const uint8_t* frames;
+  int N, W, H;
+  uint8_t *img, *valid;
+  int32_t* src;
+  int oh, ow;
+  double cell;
+  int rows_behind;
+  bool chw;
+  const uint8_t* mask;
+};
+// the shared camera's table [oh * ow] of source pixels (-1: invalid); cal: the one calibration (device), or null = rectilinear
+void dt_launch_ipm_table(hipStream_t s, int32_t* table, const IpmCal* cal, int W, int H, int oh, int ow, double cell, int rows_behind);
+// the shared camera: every env through `table`
+void dt_launch_ipm_gather(hipStream_t s, const IpmArgs& a, const int32_t* table);
+// per-env cameras (per_env: those of SimArrays::cam, else the shared one) and / or calibrations: cals = [n_cal] (device; 0: rectilinear),
+// env_cal = [N] indices into it (device), or null = calibration 0 for every env
+void dt_launch_ipm_env(hipStream_t s, const IpmArgs& a, const SimArrays& A, bool per_env, const IpmCal* cals, int n_cal, const int32_t* env_cal);
 // camera_rand (remap.hip): frames[e] = scratch[e] gathered through table env_cal[e] of src ([n_cal][H*W] int32, -1 = black); only the
 // envs with mask[e] != 0 when mask (device) is given.  Host builders of the tables, bit-identical to dtsim/distortion.py.
 void dt_launch_remap_cal(hipStream_t s, const uint8_t* scratch, uint8_t* frames, const int32_t* src, const int32_t* env_cal,

@@ -3149,6 +3149,8 @@ __global__ __launch_bounds__(256) void k_bev(const double* __restrict__ pos_x, c
   }
 }
 
+#include "render_ipm.inc"
+
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
                                                       const int first, const int count, const int env) {
   __shared__ LedS s_led[64];
@@ -3279,6 +3281,26 @@ void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, con
   hipLaunchKernelGGL(k, grid, dim3(256), (size_t)n_recs * sizeof(TileLds), s, A.pos_x, A.pos_z, A.angle, A.map_id, A.ob_corners, A.ob_visible, R.maps,
                      R.tile_recs, R.objs, ocorners, texel_class, mesh_class, n_mesh_class, R.tex_w, R.tex_h, R.n_maps, n_recs, R.N, oh, ow, cell, rows_behind,
                      cls, inst, mask);
+}
+
+void dt_launch_ipm_table(hipStream_t s, int32_t* table, const IpmCal* cal, int W, int H, int oh, int ow, double cell, int rows_behind) {
+  hipLaunchKernelGGL(k_ipm_table, dim3((unsigned)((oh * ow + 255) / 256)), dim3(256), 0, s, dt_ipm_shared_camera(W, H), cal, W, H, oh, ow, cell,
+                     rows_behind, table);
+}
+
+void dt_launch_ipm_gather(hipStream_t s, const IpmArgs& a, const int32_t* table) {
+  if (a.N <= 0) return;
+  const bool vec = dt_ipm_vec(a);
+  auto k = a.chw ? (vec ? k_ipm_gather<true, true> : k_ipm_gather<true, false>) : (vec ? k_ipm_gather<false, true> : k_ipm_gather<false, false>);
+  hipLaunchKernelGGL(k, dt_ipm_grid(a), dim3(256), 0, s, a.frames, table, a.N, a.oh * a.ow, (size_t)a.W * a.H * 3, a.img, a.valid, a.src, a.mask);
+}
+
+void dt_launch_ipm_env(hipStream_t s, const IpmArgs& a, const SimArrays& A, bool per_env, const IpmCal* cals, int n_cal, const int32_t* env_cal) {
+  if (a.N <= 0) return;
+  const bool vec = dt_ipm_vec(a);
+  auto k = a.chw ? (vec ? k_ipm_env<true, true> : k_ipm_env<true, false>) : (vec ? k_ipm_env<false, true> : k_ipm_env<false, false>);
+  hipLaunchKernelGGL(k, dt_ipm_grid(a), dim3(256), 0, s, a.frames, A.angle, A.cam, per_env ? 1 : 0, dt_ipm_shared_camera(a.W, a.H), cals, n_cal, env_cal,
+                     a.N, a.W, a.H, a.oh, a.ow, a.cell, a.rows_behind, a.img, a.valid, a.src, a.mask);
 }
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {

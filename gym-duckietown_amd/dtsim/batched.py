@@ -219,6 +219,7 @@ class BatchedSimulator:
                 # undistort=True with camera_rand: no per-env tables (the wrapper skips the simulator's fisheye), but the device reset
                 # sampler still scales the camera and zeroes its noise (the per-env camera path would apply a drawn one)
                 _ffi.check(self._lib, self._lib.dtsim_set_distortion_luts(self._h, 0, None, None, _ffi.LUTS_CAMERA_RAND))
+            self._install_ipm_calibrations()                 # ipm() projects through the nominal calibration
 
         # ---- per-env host reset state (RNG order lives on the host; reset.py)
         self.env_state = [R.EnvResetState(None if seed is None else seed + e) for e in range(self.num_envs)]
@@ -437,6 +438,7 @@ class BatchedSimulator:
             _ffi.check(self._lib, self._lib.dtsim_set_distortion_lut(self._h, fp(), fp()))
         else:
             _ffi.check(self._lib, self._lib.dtsim_set_distortion_lut(self._h, self.rmapx.ctypes.data_as(fp), self.rmapy.ctypes.data_as(fp)))
+        self._install_ipm_calibrations()
 
     def set_camera_calibrations(self, K, D, env_cal):
         """Install calibrations for the fisheye (camera_rand): K [P,3,3], D [P,5] (plumb-bob k1, k2, p1, p2, k3 -- e.g. a real
@@ -462,6 +464,7 @@ class BatchedSimulator:
         self._cal = (K, D, new_K, env_cal, src)
         if not self._skip_distort:
             self._install_calibrations()
+        self._install_ipm_calibrations()
 
     def _install_calibrations(self):
         _, _, _, env_cal, src = self._cal
@@ -900,6 +903,72 @@ class BatchedSimulator:
                 raise ValueError("bev: instances_out and out are one buffer")
         self._need_label_assets()
         _ffi.check(self._lib, self._lib.dtsim_bev(self._h, ptr, ip, h, w, c, rb, 0, mp))
+        return out
+
+    def _install_ipm_calibrations(self):
+        """The forward models ipm() projects through (dtsim_set_ipm_calibrations), kept in step with the frames' fisheye: the installed
+        calibrations (camera_rand, set_camera_calibrations), else the nominal one when distortion=True, none while the frames are
+        rectilinear (distortion=False, skip_distort) or show UndistortWrapper's view (undistort=True: ipm() refuses)."""
+        if not self.render_enabled:
+            return
+        dp = C.POINTER(C.c_double)
+        if not self.distortion or self.undistort or self._skip_distort:
+            _ffi.check(self._lib, self._lib.dtsim_set_ipm_calibrations(self._h, 0, None, None, None, None))
+            return
+        if self._cal is not None:
+            K, D, new_K, env_cal = self._cal[:4]
+        else:
+            K, D = dist_mod.CAMERA_MATRIX[None], dist_mod.DIST_COEFS[None]
+            new_K, env_cal = dist_mod.optimal_new_camera_matrix()[None], None
+        K, D, new_K = (np.ascontiguousarray(a, np.float64) for a in (K, D, new_K))
+        ep = None if env_cal is None else env_cal.ctypes.data_as(C.POINTER(C.c_int32))
+        _ffi.check(self._lib, self._lib.dtsim_set_ipm_calibrations(self._h, int(K.shape[0]), K.ctypes.data_as(dp), D.ctypes.data_as(dp),
+                                                                   new_K.ctypes.data_as(dp), ep))
+
+    def ipm(self, height: int, width: int, cell: float = 0.02, rows_behind: int = 0, chw: bool = True, out=None, mask=None, valid_out=None,
+            index_out=None):
+        """The ground-projected camera image of every env, on the device (dtsim_ipm, include/dtsim.h): Duckietown's ground projection
+        (inverse perspective mapping) of the current frame batch in bev()'s cell geometry -- [N, 3, height, width] uint8, or
+        [N, height, width, 3] with chw=False; cell (i, j) shows the frame pixel that the floor point of bev()'s cell (i, j) projects to
+        through the env's own camera (height, pitch, fov and noise under domain_rand) and, with distortion=True, its calibration's forward
+        model (the nominal one, or the env's own of camera_rand / set_camera_calibrations); 0, 0, 0 where the point is behind the near plane
+        or outside the image.  Nearest pixel, never filtered; a flat-world projection: no occlusion, and what stands on the floor smears away
+        from the camera.  `valid_out` ([N, height, width] uint8): 1 / 0 per cell; `index_out` ([N, height, width] int32): the source pixel
+        r * W + c, or -1 -- `torch.gather` of any camera map through it ground-projects that map.  It reads the frames as they are: call
+        render() first.  `out` as labels()'s, `mask` as render()'s (only the selected envs' rows are written).  Sizes, cell and rows_behind as
+        bev()'s; a bad one, a bad out, valid_out, index_out or mask, render=False and undistort=True (the frames show UndistortWrapper's
+        view, not the camera's) raise ValueError before the library is called."""
+        try:
+            h, w, rb, c = int(height), int(width), int(rows_behind), float(cell)
+            whole = h == height and w == width and rb == rows_behind
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError(f"ipm: height, width and rows_behind must be integers and cell a number, got {height!r}, {width!r}, {rows_behind!r}, {cell!r}")
+        if not (1 <= h <= _ffi.BEV_MAX_SIDE and 1 <= w <= _ffi.BEV_MAX_SIDE):
+            raise ValueError(f"ipm: a {h} x {w} map: each size must be in 1 .. {_ffi.BEV_MAX_SIDE}")
+        if not (math.isfinite(c) and c > 0.0):
+            raise ValueError(f"ipm: cell {cell!r}: metres per cell, finite and > 0")
+        if not 0 <= rb <= h:
+            raise ValueError(f"ipm: rows_behind {rows_behind!r} outside 0 .. {h}")
+        if not self.render_enabled:
+            raise ValueError("ipm: the simulator was built with render=False and has no frames")
+        if self.undistort:
+            raise ValueError("ipm with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
+        mp = self._mask_arg(mask)
+        shape = (self.num_envs, h, w)
+        out, ptr = self._result("ipm", out, (self.num_envs, 3, h, w) if chw else (self.num_envs, h, w, 3))
+        ptrs = [ptr.value]
+        vp = ip = None
+        if valid_out is not None:
+            vp = C.c_void_p(self._out_ptr(valid_out, shape, "|u1", 1, "ipm: valid_out"))
+            ptrs.append(vp.value)
+        if index_out is not None:
+            ip = C.c_void_p(self._out_ptr(index_out, shape, "<i4", 4, "ipm: index_out"))
+            ptrs.append(ip.value)
+        if len(set(ptrs)) != len(ptrs):
+            raise ValueError("ipm: out, valid_out and index_out must be three buffers")
+        _ffi.check(self._lib, self._lib.dtsim_ipm(self._h, ptr, vp, ip, h, w, c, rb, _ffi.IPM_CHW if chw else 0, mp))
         return out
 
     @staticmethod

@@ -46,12 +46,12 @@ average (its learners' imresize then rescales by the array's min and max); here 
 resize of every other frame -- `BatchedSimulator.blend_frames(out=float32)` gives the unrounded value.  Memory: L extra frame batches (15 GB for
 the default window at N = 4096, 640 x 480).  `motion_blur=False` (the default) runs the paths above, call for call.
 
-Auxiliary outputs (depth, labels, instances, boxes, bev, bev_instances; each off by default, and an option left off makes no new call).  What
+Auxiliary outputs (depth, labels, instances, boxes, bev, bev_instances, ipm, ipm_valid; each off by default, and an option left off makes no new call).  What
 they share, said once.  Output X is one persistent device tensor, `info["X"]`, of the state whose observation `obs` shows -- for an env
 restarted in the step, the first state of its new episode.  `reset()` keeps returning `obs` alone: after it the output is `env.X`, the same
 tensor (None while X is off).  With `final_obs=True`, `info["final_X"]` is a second persistent tensor whose rows where
 `info["final_obs_mask"]` is set hold X of the final state (the other rows are unspecified).  The passes stand together after every observe,
-in the order depth, labels, instances, boxes, bev, masked where the observe is masked: full render -> observe -> passes ->
+in the order depth, labels, instances, boxes, bev, ipm, masked where the observe is masked: full render -> observe -> passes ->
 `dtsim_copy_rows` of each -> `dtsim_reset_done` -> masked render -> masked observe -> masked passes.  They compose with one another and with
 `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand` (no output is ever stacked).  Depth, labels, instances and boxes are CAMERA
 post-passes: point-sampled from the frame's source pixels, never filtered, so each size of their `(h, w)` must divide the camera's; and they
@@ -80,6 +80,15 @@ else 2, the ground; never 0 or 1, never filtered), and with `bev_instances=True`
 (o + 1 / 0, the ids of `info["instances"]`).  It reads the state, not the camera, so it composes with everything: `camera_rand` and
 `motion_blur` are allowed -- under `motion_blur` the observation blends the frames of the window's states, and the map is that of the state
 after the last sub-update, the newest of them.
+
+Ground projection (`ipm_shape=(h, w)`, `ipm_cell`, `ipm_rows_behind` as the bird's-eye options; `ipm_valid=True` needs it): `info["ipm"]` is
+the camera frame warped onto the floor plane in `info["bev"]`'s cell geometry (`dtsim_ipm`, include/dtsim.h: Duckietown's ground projection,
+inverse perspective mapping) -- `[N, 3, h, w]` `torch.uint8`, `[N, h, w, 3]` with `chw=False`; cell (i, j) shows the frame pixel that the
+floor point of `info["bev"]`'s cell (i, j) projects to through the env's own camera and fisheye, 0, 0, 0 where there is none -- and with
+`ipm_valid=True` `info["ipm_valid"]` the `[N, h, w]` flags (1 / 0) of the same launch.  Input and target of a camera-to-BEV head come
+aligned.  Nearest pixel, never filtered; a flat-world projection (no occlusion; what stands on the floor smears away from the camera).  It
+projects through each env's camera and calibration itself and reads no table, so `domain_rand` and `camera_rand` are allowed;
+`motion_blur` (the blended frame shows several cameras), `undistort=True` and `render=False` raise ValueError.
 """
 from __future__ import annotations
 
@@ -108,7 +117,8 @@ class DuckietownVecEnv:
                  depth_dtype: str = "float32", label_shape: Optional[Tuple[int, int]] = None,
                  instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False,
                  bev_shape: Optional[Tuple[int, int]] = None, bev_cell: float = 0.02, bev_rows_behind: int = 0,
-                 bev_instances: bool = False, **sim_kwargs):
+                 bev_instances: bool = False, ipm_shape: Optional[Tuple[int, int]] = None, ipm_cell: float = 0.02,
+                 ipm_rows_behind: int = 0, ipm_valid: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -148,12 +158,39 @@ class DuckietownVecEnv:
             if sim_kwargs.get("render") is False:
                 raise ValueError("bev_shape needs render=True (the pass reads the render tables)")
             self.bev_shape, self.bev_cell, self.bev_rows_behind = (bh, bw), bc, brb
+        self.ipm_shape, self.ipm_cell, self.ipm_rows_behind = None, ipm_cell, ipm_rows_behind
+        if ipm_shape is None:
+            if ipm_valid:
+                raise ValueError("ipm_valid=True needs ipm_shape (the flags are those of the ground-projected image, in its cells)")
+        else:
+            try:
+                ih, iw = (int(v) for v in ipm_shape)
+                irb, ic = int(ipm_rows_behind), float(ipm_cell)
+            except (TypeError, ValueError):
+                raise ValueError(f"ipm_shape must be (h, w), ipm_rows_behind an integer and ipm_cell a number, got {ipm_shape!r}, "
+                                 f"{ipm_rows_behind!r}, {ipm_cell!r}") from None
+            if not (1 <= ih <= _ffi.BEV_MAX_SIDE and 1 <= iw <= _ffi.BEV_MAX_SIDE):
+                raise ValueError(f"ipm_shape {(ih, iw)}: each size must be in 1 .. {_ffi.BEV_MAX_SIDE}")
+            if not (np.isfinite(ic) and ic > 0.0):
+                raise ValueError(f"ipm_cell {ipm_cell!r}: metres per cell, finite and > 0")
+            if irb != ipm_rows_behind or not 0 <= irb <= ih:
+                raise ValueError(f"ipm_rows_behind {ipm_rows_behind!r}: an integer in 0 .. {ih}")
+            if sim_kwargs.get("render") is False:
+                raise ValueError("ipm_shape needs render=True (the pass reads the camera frames)")
+            if self._blur:
+                raise ValueError("ipm_shape with motion_blur is not supported (the blended frame shows the cameras of its window's states: "
+                                 "no single camera projects it)")
+            if sim_kwargs.get("undistort"):
+                raise ValueError("ipm_shape with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
+            self.ipm_shape, self.ipm_cell, self.ipm_rows_behind = (ih, iw), ic, irb
         outputs = (_Aux("depth", depth_dtype, self.depth_shape, True),
                    _Aux("labels", "uint8", self.label_shape, True),
                    _Aux("instances", "uint8", self.instance_shape, True),
                    _Aux("boxes", "int32", (_ffi.MAX_OBJECTS, 5) if boxes else None, True),
                    _Aux("bev", "uint8", self.bev_shape, False),
-                   _Aux("bev_instances", "uint8", self.bev_shape if bev_instances else None, False))
+                   _Aux("bev_instances", "uint8", self.bev_shape if bev_instances else None, False),
+                   _Aux("ipm", "uint8", self.ipm_shape and ((3, *self.ipm_shape) if chw else (*self.ipm_shape, 3)), False),
+                   _Aux("ipm_valid", "uint8", self.ipm_shape if ipm_valid else None, False))
         if self._blur:
             if action_mode != "wheels":
                 raise ValueError(f"motion_blur needs action_mode='wheels' (update_physics takes the wheel pair), got {action_mode!r}")
@@ -259,7 +296,8 @@ class DuckietownVecEnv:
     def _map_passes(self, mask=None):
         """The passes of the outputs that are on, in the table's order, each into the env's own tensor (`mask`: only those envs' rows): of the
         state the last render() showed the depth, then the labels, then the instances and their boxes -- labels and instances of one shape
-        come from one launch --; then, of the current state, the bird's-eye map (and its ids)."""
+        come from one launch --; then, of the current state, the bird's-eye map (and its ids); last, of the frame batch as it stands, the
+        ground-projected image (and its flags)."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
         fused = self.labels is not None and self.label_shape == self.instance_shape
@@ -273,6 +311,9 @@ class DuckietownVecEnv:
         if self.bev is not None:
             self.sim.bev(self.bev_shape[0], self.bev_shape[1], cell=self.bev_cell, rows_behind=self.bev_rows_behind, out=self.bev, mask=mask,
                          instances_out=self.bev_instances)
+        if self.ipm is not None:
+            self.sim.ipm(self.ipm_shape[0], self.ipm_shape[1], cell=self.ipm_cell, rows_behind=self.ipm_rows_behind, chw=self.chw, out=self.ipm,
+                         mask=mask, valid_out=self.ipm_valid)
 
     def _keep_final(self, obs, done, info):
         """final_obs: the finished envs' rows of `obs` (stacked: of the whole history) and of every output that is on, before the reset

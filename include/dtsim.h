@@ -649,6 +649,50 @@ int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, u
  * for every env index and whichever of the two maps are asked for. */
 #define DTSIM_BEV_MAX_SIDE 1024
 int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind, uint32_t flags, const uint8_t* mask);
+/* The ground-projected camera image of every env, on the device: Duckietown's ground projection (inverse perspective mapping), the CAMERA
+ * FRAME WARPED ONTO THE FLOOR PLANE in the robot's own frame -- the input a camera-to-BEV head is compared against, in dtsim_bev's cell
+ * geometry: cell (i, j) here and cell (i, j) of dtsim_bev with the same (oh, ow), cell and rows_behind name one world point.  A learner-side
+ * addition; the reference has no such output.
+ * THE QUANTITY.  (oh, ow), cell and rows_behind mean what they mean in dtsim_bev and have its limits.  Cell (i, j) of env e stands for the
+ * point P = (x, z) + f d + s r on the TILE PLANE y = 0, with dtsim_bev's f, s, d, r of the agent's pose.  Everything below is float64.
+ *   1. The camera (oracle/raster.py Camera).  Centre C = pos [+ the camera noise of DTSIM_FIELD_CAMERA, in world axes, where the handle
+ *      renders per-env cameras: DTSIM_F_DOMAIN_RAND] + (0.066 cos theta, cam_height, -0.066 sin theta); pitch and fov_y the env's own
+ *      float32 values of DTSIM_FIELD_CAMERA promoted to double, or on the shared camera 0.108 m, 19.15 and 75 degrees; ty = tan(fov_y / 2),
+ *      tx = ty W / H.  Eye coordinates as Camera.to_eye; w = -z_eye; u = (x_eye / w / tx + 1) W / 2, v = (1 - y_eye / w / ty) H / 2 -- pixel c
+ *      spans [c, c + 1): the projection of dtsim_draw_lines.
+ *   2. Rectilinear frames (no calibration installed): the source pixel is (r, c) = (floor v, floor u).
+ *   3. Fisheye frames (dtsim_set_ipm_calibrations): the calibration's forward model -- cv::initUndistortRectifyMap's arithmetic with the
+ *      env's own K, D and new_K at the real-valued index coordinates (u - 0.5, v - 0.5) -- gives the distorted coordinates (xd, yd), and
+ *      (r, c) = (floor(yd + 0.5), floor(xd + 0.5)).  No table is read, so a calibration per env is defined too.  A PROPERTY OF THE
+ *      REFERENCE'S FISHEYE, not a tolerance: its frames are made with an approximate INVERSE table (_invert_map, _fill_holes), so the
+ *      rectilinear pixel that frame pixel (r, c) actually shows lies a median 0.8 px from the aimed (u, v), p99 2.1 px, at most 4.2 px
+ *      (640 x 480, four map shapes, measured on the host).
+ *   4. The cell is valid iff w >= 0.04 (the near plane), with a fisheye (u, v) lies inside [0, W) x [0, H), and (r, c) lies inside the frame.
+ *   5. img[e][i][j][0..2] -- [e][0..2][i][j] with DTSIM_IPM_CHW -- are the three bytes at (r, c) of env e's frame in the handle's current
+ *      frame batch (dtsim_bind_frames' buffer or the internal one, as dtsim_observe reads it), 0, 0, 0 where the cell is invalid;
+ *      valid[e][i][j] is 1 or 0; src[e][i][j] is r W + c, or -1: with it any camera map of the frame's size (depth, labels, instances) is
+ *      ground-projected by one gather.
+ * Sampling is nearest-pixel, never filtered.  It is a FLAT-WORLD projection: no occlusion, and whatever stands on the floor smears away
+ * from the camera.  The frames are read as they are: no dtsim_render need precede the call, and it does not know which state they show.
+ * SIZE.  img: DEVICE pointer to num_envs * oh * ow * 3 bytes, valid: to num_envs * oh * ow bytes, src: to as many int32.  Any subset, not
+ * none, no two one buffer.  mask: DEVICE pointer to num_envs bytes, or NULL = every env; the rows of unselected envs keep every byte.
+ * DTSIM_E_INVALID, before anything is launched or written, for: a null handle, every output null or two of them one buffer, flags other
+ * than DTSIM_IPM_CHW, a size outside 1 .. DTSIM_BEV_MAX_SIDE, a non-finite or non-positive cell, rows_behind outside 0 .. oh.  DTSIM_E_STATE
+ * before the first dtsim_reset or on a handle without DTSIM_F_RENDER.  Asynchronous, stream-ordered, no host synchronisation.  One state
+ * and one frame batch give the same bytes on every call, for every env index and whichever outputs are asked for.
+ * With the shared camera and at most one calibration the cell -> pixel map is the same for every env and step: the handle computes it
+ * once per (oh, ow, cell, rows_behind, calibration) into a table of its own and the call is one gather (the first such call of a handle
+ * allocates the table, 4 MB, which is the one device allocation the entry point ever makes).
+ *
+ * dtsim_set_ipm_calibrations: the calibrations of step 3.  K, new_K: [n_cal][3][3], D: [n_cal][5] (k1, k2, p1, p2, k3), env_cal: [num_envs]
+ * indices in [0, n_cal) -- all HOST pointers, copied.  new_K is the caller's (the reference computes it for 640 x 480 at any camera
+ * size); it must have an inverse.  env_cal may be NULL when n_cal = 1.  n_cal = 0 (every pointer NULL): rectilinear, a new handle's state.
+ * DTSIM_E_INVALID for a null handle, n_cal < 0, a missing table, a value that is not finite, an index out of range; DTSIM_E_STATE without
+ * DTSIM_F_RENDER.  A failed call changes nothing.  Synchronises the stream. */
+#define DTSIM_IPM_CHW 1u
+int dtsim_set_ipm_calibrations(dtsim_t* h, int n_cal, const double* K, const double* D, const double* new_K, const int32_t* env_cal);
+int dtsim_ipm(dtsim_t* h, uint8_t* img, uint8_t* valid, int32_t* src, int oh, int ow, double cell, int rows_behind, uint32_t flags,
+              const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,
