@@ -116,7 +116,7 @@ struct RenderParams {
   uint16_t* queue;              // MSAA edge-pixel queue regions, [workgroups][4][256*16]
   int32_t* qcount;              // [workgroups][4]
   uint16_t* qend;               // [workgroups][4][DT_ENVS_PER_BLOCK] queue fill of each region after each env of the chunk (mesh-object renders)
-  int32_t* work;                // [DT_WORK_INTS] counts and cursors of the exact paths' work lists (the DT_WORK_* slots below); zeroed per render
+  int32_t* work;                // [DT_WORK_INTS] counts and cursors of the exact paths' work lists, k_raster_v3's ticket counters (the DT_WORK_* slots below); zeroed per render
   uint32_t* items;              // [workgroups * DT_ITEMS_PER_WG] work items: raster workgroup * DT_ITEMS_PER_WG + part
   uint32_t* items2;             // [workgroups * DT_ENVS_PER_BLOCK] work items of k_resolve_obj: raster workgroup * DT_ITEMS_PER_WG + env group
   const uint8_t* mesh_seg;      // [n_meshes][4] flat segmentation colour per mesh (segment renders only)
@@ -134,13 +134,14 @@ struct RenderParams {
   int32_t q3_rows;              // k_raster_v3 / k_raster_v3dr: rows of their LDS tile table (largest padded grid height); 0: they cannot run (dt_raster_pipe)
   int32_t light;                // DTSIM_F_LIGHT_CAPTURE with the shared camera: every env lit by its own eye-space light (k_cam_setup, the LIGHT kernels)
 };
-#define DT_WORK_INTS 8           // RenderParams.work: the slots
+#define DT_WORK_INTS (32 + 8 * 32)   // RenderParams.work: the slots, then k_raster_v3's ticket counters
 #define DT_WORK_ITEMS 0          //   work items of k_resolve / k_resolve_dr in RenderParams.items (the rasters append)
 #define DT_WORK_CURSOR 1         //   their grab cursor
 #define DT_WORK_OBJ_FRONT 2      //   k_resolve_obj's heavy items, from the front of RenderParams.items2
 #define DT_WORK_OBJ_CURSOR 3     //   its grab cursor
 #define DT_WORK_OBJ_BACK 6       //   its other items, from the back of items2
 #define DT_WORK_LIVE 7           //   envs of a masked pass (k_env_sort_masked), read by the SUB rasters
+#define DT_WORK_TICKETS 32       //   k_raster_v3's ticket counters (raster_map.h): XCD x's at DT_WORK_TICKETS + 32 * x, 128 bytes apart and from the slots above
 // RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane)
 struct RenderDump { uint8_t store[64 * 16]; };
 // The render scratch (render.hip dt_render_layout): the allocations RenderParams points into, each a run of arrays -- ENV: per env EnvCam, EnvFast,

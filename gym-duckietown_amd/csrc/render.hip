@@ -45,7 +45,7 @@
 //                 1/depth space, then the same shading.
 //   Segmentation render (dtsim_render_ex): same kernels on the segmented texel pool, k_cam_setup forces the unlit
 //                 state and the magenta clear / ground colour, k_obj_setup folds the mesh's flat colour into Kd.
-//   Scaffolding shared by the rasters (ahead of k_raster): the XCD-affine workgroup map and its launch size (raster_wg / raster_wg_grid), the v3 LDS
+//   Scaffolding shared by the rasters (ahead of k_raster): the XCD-affine workgroup map (raster_map.h; raster_wg and k_raster_v3's raster_claim_* here), the v3 LDS
 //                 tile table fill, the chunk's object masks, the packed source-pixel centres (spxy).
 //   Scaffolding shared by the exact paths (same place): the owner tile and ground-quad hit of an MSAA sample (v3_sample_owner, ground_quad_*), the work-list
 //                 grabs (work_n_grabs / work_next_grab over the DT_WORK_* slots of dtsim_dev.h), the tile-record LDS fill; elsewhere the ground quad's
@@ -59,6 +59,7 @@
 // filter at the precision GL's own GL_LINEAR has on the reference's renderer, uint8 output.
 // Parity: every pipeline is held to frames the unmodified reference rendered on Mesa llvmpipe (tests/test_gpu_gl_golden.py).
 #include "dtsim_dev.h"
+#include "raster_map.h"
 #include <hip/hip_fp16.h>
 #include <type_traits>
 #include <algorithm>
@@ -1245,27 +1246,14 @@ __device__ inline envmask_t obj_groups_of(int qend_v, int lane, envmask_t* heavy
 // k_resolve / k_resolve_dr / k_resolve_obj (a struct, a struct with lazy members, free functions over rn[] / rb[]: 35 - 65 instructions more); k_raster's
 // tile-record fill; ground_lit in k_raster_v3dr's env loop; k_resolve's unmasked env position.  What a kernel does differently is an argument at its call site.
 
-// ---- XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr) and its launch size.
-// Workgroup b runs on XCD b % 8 (round-robin dispatch), and XCD x is given the x-th eighth of the env chunks (all frame tiles of each): with
-// the envs in k_env_sort order, one L2 serves the envs of one region of the map for the whole launch.  Within an XCD: groups of
-// dt_q_tile_group() frame tiles, all chunks of the slice for one group before the next group, so that a tile's PixTab slice (16 KB) is read
-// from HBM once per XCD instead of once per chunk, while the workgroups in flight still belong to few chunks.  The mapping only matters for speed.
-// Group size, round 6: HALF the frame (150 tiles at 640 x 480; 10 before) -- with 64 envs per workgroup the tiles of ONE chunk fill an XCD.
-// C3 - 4.6 %, C5 - 1.8 %; the whole frame as one group is + 5 ... 12 % (profiles/r06_variants_ab.txt block P).
-#ifndef DT_Q_TILE_SPLIT
-#define DT_Q_TILE_SPLIT 2
-#endif
-__host__ __device__ inline int dt_q_tile_group(int n_tiles) { return (n_tiles + DT_Q_TILE_SPLIT - 1) / DT_Q_TILE_SPLIT; }
-// launch size: 8 slices of ceil(n_chunks / 8) chunks, frame tiles in groups of dt_q_tile_group() (the last group padded); n_chunks: of all N envs, also
-// when the pass is masked (SUB: the workgroups past the live chunks leave at once)
-inline size_t raster_wg_grid(size_t n_tiles, int n_chunks) {
-  const int q_tg = dt_q_tile_group((int)n_tiles);
-  return ((n_tiles + q_tg - 1) / q_tg) * q_tg * ((n_chunks + 7) / 8) * 8;
-}
+// ---- XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr): raster_map.h states the lists, the launch
+// size and the prefix / suffix split; here is what a workgroup does with them.
 // NL: envs of the pass; live: false for a workgroup of the grid's padding (the whole workgroup leaves, before anything else is derived);
-// rwg: the logical workgroup index (queue regions, counts, work items); [e0, e1): the chunk's positions in the render order.
+// rwg: the logical workgroup index (queue regions, counts, work items) -- of the ITEM, whichever workgroup runs it; [e0, e1): the chunk's
+// positions in the render order.  claims (TICKET only): the workgroup draws its item (raster_claim_*) instead of decoding it; thief: its slot
+// lies past the lists.
 struct RasterWg {
-  int NL, tile, chunk; bool live;
+  int NL, tile, chunk; bool live, claims, thief;
   __device__ int rwg(const int n_tiles) const { return chunk * n_tiles + tile; }
   __device__ int e0() const { return chunk * ENVS_PER_BLOCK; }
   __device__ int e1() const { return min(e0() + ENVS_PER_BLOCK, NL); }
@@ -1274,22 +1262,58 @@ struct RasterWg {
 // b / n_tiles, so that every chunk's tiles spread over all eight XCDs.
 // SCALAR: tile and chunk through readfirstlane -- the divisions run on the vector ALU, and without it the env loop's counter and the per-env
 // address arithmetic of k_raster_v3 / k_raster_v3dr stay vector instructions; k_raster_q was tuned without it and keeps its form.
-template <bool SUB, bool SCALAR>
+// TICKET (k_raster_v3's full pass): the list's last DT_RASTER_TICKET_UNITS units are claimed, not decoded, and the launch carries raster_thieves() more slots
+// per XCD -- with the static map the XCDs ended up to 4 % of the launch apart (sorted render order: the scenes of the slices differ); an XCD whose list is
+// dry now takes what is left of a late one's suffix, and they end within 0.6 % (C3 - 1.5 %, C5 - 1.8 %: profiles/raster_ticket_map.txt).
+template <bool SUB, bool SCALAR, bool TICKET = false>
 __device__ inline RasterWg raster_wg(const RenderParams& R, const int n_tiles, const unsigned bx) {
+  static_assert(!(SUB && TICKET), "the masked pass keeps its linear map");
   RasterWg w;
   w.NL = SUB ? dt_sub_live(R) : R.N;                 // (SUB: the live chunks)
-  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK, cpx = (n_chunks + 7) / 8;
+  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
   const int xcd = bx & 7, bi = bx >> 3;
-  const int q_tg = dt_q_tile_group(n_tiles);
-  const int per_group = q_tg * cpx;
-  const int grp = bi / per_group, gi = bi % per_group;
-  const int g_tiles = min(q_tg, n_tiles - grp * q_tg);        // the last group may be short
-  const int tile = SUB ? (int)bx % n_tiles : grp * q_tg + gi % g_tiles;
+  const bool thief = TICKET && bi >= raster_list_slots(n_tiles, n_chunks);   // a slot past the lists (raster_ticket_grid): nothing to decode
+  const RasterItem it = raster_item(n_tiles, n_chunks, xcd, thief ? 0 : bi);
+  const int tile = SUB ? (int)bx % n_tiles : it.tile;
   w.tile = SCALAR ? __builtin_amdgcn_readfirstlane(tile) : tile;
-  const int chunk = SUB ? (int)bx / n_tiles : xcd * cpx + gi / g_tiles;
+  const int chunk = SUB ? (int)bx / n_tiles : it.chunk;
   w.chunk = SCALAR ? __builtin_amdgcn_readfirstlane(chunk) : chunk;
-  w.live = SUB ? w.chunk < n_chunks : (gi < g_tiles * cpx && w.chunk < n_chunks);
+  w.live = SUB ? w.chunk < n_chunks : (it.live && !thief);
+  w.claims = TICKET && __builtin_amdgcn_readfirstlane((int)(thief || !raster_slot_static(n_tiles, n_chunks, xcd, thief ? 0 : bi, DT_RASTER_TICKET_UNITS))) != 0;
+  w.thief = thief;
   return w;
+}
+// The claim of a workgroup with w.claims, in two halves so that work which does not depend on the item (the LDS tile table) hides the
+// round trip: raster_claim_issue draws the first ticket (thread 0, the own XCD's counter; a device-scope atomic like the cursors of
+// k_resolve_*; a thief starts when its XCD's own slots have all started and draws none), raster_claim_finish turns it into the item -- with
+// the own list dry it reads the other seven counters at once and draws from those that are not dry, in rotation from xcd + 1 -- and hands the
+// item to the workgroup through LDS (one barrier, claimers only).  At most DT_RASTER_XCDS atomic adds, no waiting on another workgroup.
+static_assert(DT_WORK_TICKETS >= DT_TICKET_STRIDE && DT_WORK_TICKETS + DT_RASTER_XCDS * DT_TICKET_STRIDE <= DT_WORK_INTS, "the ticket counters lie inside R.work (zeroed before every pass)");
+__device__ inline int raster_claim_issue(const RenderParams& R, const unsigned bx, const int tid, const RasterWg& w) {
+  if (w.thief) return 0x7fffffff;
+  return tid == 0 ? atomicAdd(R.work + DT_WORK_TICKETS + (int)(bx & 7) * DT_TICKET_STRIDE, 1) : 0;
+}
+__device__ inline void raster_claim_finish(const RenderParams& R, const int n_tiles, const unsigned bx, const int first, int* s_claim, const int tid, RasterWg& w) {
+  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  if (tid == 0) {
+    RasterItem it = raster_ticket_item(n_tiles, n_chunks, (int)(bx & 7), first, DT_RASTER_TICKET_UNITS);
+    if (!it.live) {
+      int seen[DT_RASTER_XCDS];
+#pragma unroll
+      for (int a = 1; a < DT_RASTER_XCDS; ++a)
+        seen[a] = __hip_atomic_load(R.work + DT_WORK_TICKETS + raster_claim_xcd((int)(bx & 7), a) * DT_TICKET_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+      for (int a = 1; a < DT_RASTER_XCDS; ++a) {
+        const int x = raster_claim_xcd((int)(bx & 7), a);
+        if (it.live || seen[a] >= raster_ticket_len(n_tiles, n_chunks, x, DT_RASTER_TICKET_UNITS)) continue;   // a counter only grows: dry stays dry
+        it = raster_ticket_item(n_tiles, n_chunks, x, atomicAdd(R.work + DT_WORK_TICKETS + x * DT_TICKET_STRIDE, 1), DT_RASTER_TICKET_UNITS);
+      }
+    }
+    s_claim[0] = it.live ? it.tile : -1; s_claim[1] = it.chunk;
+  }
+  __syncthreads();
+  w.tile = __builtin_amdgcn_readfirstlane(s_claim[0]); w.chunk = __builtin_amdgcn_readfirstlane(s_claim[1]);
+  w.live = w.tile >= 0;
 }
 
 // ---- LDS tile table of k_raster_v3 / k_raster_v3dr / k_resolve_dr: the tile tables of all maps in rows of V3_TAB_PITCH entries, block byte
@@ -3384,6 +3408,7 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   const size_t lds2 = lds + (size_t)(RB / 64) * ENVS_PER_BLOCK * sizeof(EnvCam);
   const dim3 grid((unsigned)(dt_raster_tiles(R.W, R.H) * n_chunks));
   const dim3 gridq((unsigned)raster_wg_grid(dt_raster_tiles(R.W, R.H), n_chunks));   // the quad-record rasters' XCD-affine map (raster_wg)
+  const dim3 gridv3(SUB ? gridq.x : (unsigned)raster_ticket_grid(dt_raster_tiles(R.W, R.H), n_chunks, DT_RASTER_TICKET_UNITS));   // k_raster_v3's full pass: + the thieves
   const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
   const size_t lds_tab = (size_t)R.q3_rows * V3_TAB_PITCH * 4;   // the v3 kernels' LDS tile table
   const size_t lds3 = lds_tab + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // + per-wavefront buffers, the chunk's EnvQ records
@@ -3396,9 +3421,9 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
                                            R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
                                 else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, false, SUB>), gridq, dim3(RB), ldsq, s, R, x.cams, x.fasts, x.envq, R.frames, R.qtex, \
                                            reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
-#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridq, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, \
+#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridv3, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, \
                                            R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
-                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridq, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, R.qtex, \
+                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridv3, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, R.qtex, \
                                            reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
   switch (pipe) {
     case DTSIM_PIPE_V3: if (obj) LAUNCH_V3(true); else LAUNCH_V3(false); break;

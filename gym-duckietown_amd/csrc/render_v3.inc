@@ -189,10 +189,16 @@ void k_raster_v3(RenderParams R, const EnvCam* __restrict__ cams, const EnvFast*
   const int tid = threadIdx.x;
   const int npix = R.W * R.H;
   const int tiles_x = (R.W + DT_TILE_W - 1) / DT_TILE_W, n_tiles = tiles_x * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
-  const RasterWg wg = raster_wg<SUB, /*SCALAR=*/true>(R, n_tiles, blockIdx.x);   // (tile and chunk in scalar registers: the env loop's counter and the EnvQ addresses follow)
-  if (!wg.live) return;
-  const int NL = wg.NL, tile = wg.tile, rwg = wg.rwg(n_tiles), e0 = wg.e0(), e1 = wg.e1();
+  RasterWg wg = raster_wg<SUB, /*SCALAR=*/true, /*TICKET=*/!SUB>(R, n_tiles, blockIdx.x);   // (tile and chunk in scalar registers: the env loop's counter and the EnvQ addresses follow)
+  if (!wg.live && !wg.claims) return;
+  int* s_claim = reinterpret_cast<int*>(s_mem + R.q3_rows * V3_TAB_PITCH);   // two words of the first transpose buffer, idle until the env loop
+  const int ticket = wg.claims ? raster_claim_issue(R, blockIdx.x, tid, wg) : 0;   // (the table fill does not depend on the item: it hides the round trip)
   v3_fill_tile_table(R, qtiles, s_qt, tid);
+  if (wg.claims) {                                     // workgroup-uniform
+    raster_claim_finish(R, n_tiles, blockIdx.x, ticket, s_claim, tid, wg);
+    if (!wg.live) return;                              // every list is dry
+  }
+  const int NL = wg.NL, tile = wg.tile, rwg = wg.rwg(n_tiles), e0 = wg.e0(), e1 = wg.e1();
   // the EnvQ records of the chunk's positions (the exact path reads them per entry: resolve_region_v3), 16 bytes per thread
   uint4* s_envq = reinterpret_cast<uint4*>(s_mem + R.q3_rows * V3_TAB_PITCH + (RB / 64) * V3_WAVE_LDS);
   static_assert(ENVS_PER_BLOCK * 4 <= RB, "one 16-byte piece per thread");
