@@ -1,12 +1,13 @@
-"""Build libdtsim.so (HIP, gfx950) in-tree.
+"""Build libdtsim.so (HIP, gfx950) in-tree; hipcc cross-compiles without a GPU, lib/ is git-ignored.
 
-    python gym-duckietown_amd/build.py [--force]
+    python gym-duckietown_amd/build.py [--force]                      -> lib/libdtsim.so
+    python gym-duckietown_amd/build.py --variant NAME [-DFOO=1 ...]   -> lib/libdtsim_NAME.so (objects in lib/NAME/: the default build's stay)
+    python gym-duckietown_amd/build.py --asm SRC.hip OUT.s [-D...]    -> the device assembly of one unit (any tree's copy of it)
 
-hipcc cross-compiles without a GPU.  Output: gym-duckietown_amd/lib/libdtsim.so
-(git-ignored, travels to the GPU box with the gpurun snapshot).
-physics.hip and remap.hip (the camera_rand table builder, pinned to numpy) are compiled with
--ffp-contract=off (separately rounded ops, in the reference's operation order); render.hip with
-contraction allowed (speed, f32).
+UNITS is the one statement of the library's units and their flags: tools/isa_*.py, .sh and tools/build_variant.sh take them from here.
+physics.hip and remap.hip (the camera_rand table builder, pinned to numpy) are compiled with contraction off (separately rounded ops, in
+the reference's operation order); render.hip with contraction allowed (speed, f32), and render_views.hip as render.hip, whose classify()
+and test_tri it shares (csrc/render_scene.h).
 """
 from __future__ import annotations
 
@@ -21,15 +22,15 @@ LIB = os.path.join(LIBDIR, "libdtsim.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-UNITS = [
-    ("physics.hip", ["-ffp-contract=off"]),
-    ("render.hip", ["-ffp-contract=fast"]),
-    ("observe.hip", []),
-    ("dtsim_api.hip", []),
-    ("remap.hip", ["-ffp-contract=off"]),
-]
+UNITS = {"physics.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=fast"], "render_views.hip": ["-ffp-contract=fast"],
+         "observe.hip": [], "dtsim_api.hip": [], "remap.hip": ["-ffp-contract=off"]}
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical",
           "-I" + os.path.join(HERE, "..", "include")]
+
+
+def compile_cmd(src: str, out: str, extra=(), asm: bool = False) -> list:
+    """hipcc's command line for one unit (flags by its file name; src may be another tree's copy): an object, or its device assembly."""
+    return [HIPCC] + COMMON + UNITS[os.path.basename(src)] + list(extra) + (["-S", "--cuda-device-only"] if asm else ["-c"]) + [src, "-o", out]
 
 
 def _newer(src_list, target):
@@ -39,27 +40,33 @@ def _newer(src_list, target):
     return any(os.path.getmtime(s) > t for s in src_list)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    os.makedirs(LIBDIR, exist_ok=True)
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+def build(force: bool = False, verbose: bool = True, variant: str = "", defines=()) -> str:
+    objdir = os.path.join(LIBDIR, variant) if variant else LIBDIR
+    lib = os.path.join(LIBDIR, f"libdtsim_{variant}.so") if variant else LIB
+    os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers.append(os.path.join(HERE, "..", "include", "dtsim.h"))
-    objs = []
-    for name, flags in UNITS:
+    objs = [os.path.join(objdir, name.replace(".hip", ".o")) for name in UNITS]
+    for name, obj in zip(UNITS, objs):
         src = os.path.join(CSRC, name)
-        obj = os.path.join(LIBDIR, name.replace(".hip", ".o"))
-        objs.append(obj)
-        if force or _newer([src] + headers, obj):
-            cmd = [HIPCC] + COMMON + flags + ["-c", src, "-o", obj]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-    if force or _newer(objs, LIB):
-        cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return LIB
+        if force or variant or _newer([src] + headers, obj):      # (a variant's defines are in no time stamp: always compiled)
+            _run(compile_cmd(src, obj, defines), verbose)
+    if force or _newer(objs, lib):
+        _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs, verbose)
+    return lib
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv))
+    args = sys.argv[1:]
+    if args[:1] == ["--asm"]:
+        _run(compile_cmd(args[1], args[2], args[3:], asm=True), False)
+    elif args[:1] == ["--variant"]:
+        print(build(verbose=False, variant=args[1], defines=" ".join(args[2:]).split()))
+    else:
+        print(build(force="--force" in args))

@@ -51,7 +51,7 @@ void dt_launch_query(hipStream_t s, const SimArrays& A, const MapSet& M, const S
 // One mesh triangle of one env after model/view/projection and per-vertex lighting
 // (objects.py:123-148, objmesh.py:360-375): rectilinear pixel coordinates, 1/w, lit colour/w.
 struct alignas(16) ScreenTri {
-  // first 64 bytes: coverage / depth (all k_resolve's z-buffer pass reads; same layout as render.hip TriCov)
+  // first 64 bytes: coverage / depth (all k_resolve's z-buffer pass reads; same layout as render_scene.h TriCov)
   float bx0, bx1, by0, by1;  // pixel bounding box (+-1 px); empty (bx0 > bx1) when culled
   float sx[3], sy[3], iw[3];
   float inv_area;            // 0 => culled (behind the near plane / degenerate / invisible)
@@ -159,29 +159,29 @@ int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_ol
 // mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
 // only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
 int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int pipe, int tables, const uint8_t* mask = nullptr);
-// GL_LINE overlays (draw_curve / draw_bbox) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
+// GL_LINE overlays (draw_curve / draw_bbox; render_views.hip k_overlay_lines) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);
-// the LED spheres of enable_leds (render.hip k_overlay_leds): [count] spheres of env `env` from d_spheres[first..], world space, R = the last render pass's parameters
+// the LED spheres of enable_leds (render_views.hip k_overlay_leds): [count] spheres of env `env` from d_spheres[first..], world space, R = the last render pass's parameters
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env);
-// the depth maps of dtsim_depth (render.hip k_depth): out = [N][oh][ow] float32 (f16: half), output pixel (i, j) = camera pixel
+// the depth maps of dtsim_depth (render_views.hip k_depth): out = [N][oh][ow] float32 (f16: half), output pixel (i, j) = camera pixel
 // (i * (H / oh) + H / oh / 2, j * (W / ow) + W / ow / 2); R = the last render pass's parameters; mask (device, [N] bytes, or null = every
 // env): the rows of the other envs are not written.  The caller checked that oh divides H and ow divides W.
 void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask);
-// the label maps of dtsim_labels (render.hip k_labels): out = [N][oh][ow] bytes, sized, sampled and masked as dt_launch_depth's; texel_class:
+// the label maps of dtsim_labels (render_views.hip k_labels): out = [N][oh][ow] bytes, sized, sampled and masked as dt_launch_depth's; texel_class:
 // one byte per texel in the layout of R.texels (dt_pack_label_tables), mesh_class: [n_mesh_class] bytes.  inst: the instance map of
 // dtsim_instances, same shape, written in the same launch from the same classification.  Either of out / inst may be null (the tables are
 // read only with out); they must not overlap.
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
                       uint8_t* inst, int oh, int ow, const uint8_t* mask);
-// the bird's-eye maps of dtsim_bev (render.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
+// the bird's-eye maps of dtsim_bev (render_views.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
 // rows_behind of the oh rows behind the agent.  Of R only the scene of render_scene is read (maps, tile_recs, n_tile_recs, objs, tex_w, tex_h, n_maps) and
 // N: no camera, no table of a pass.  ocorners: dt_pack_object_corners' table; texel_class / mesh_class as dt_launch_labels' (read only with
 // cls); mask: device, [N] bytes, or null = every env.  The caller checked the sizes (1 .. DTSIM_BEV_MAX_SIDE) and cell (finite, > 0).
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
                    const uint8_t* mesh_class, int n_mesh_class, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind,
                    const uint8_t* mask);
-// the ground-projected camera image of dtsim_ipm (render_ipm.inc; the projection: ipm_project.h).  One call's arguments: img = [N][oh][ow][3]
+// the ground-projected camera image of dtsim_ipm (render_views.hip k_ipm_*; the projection: ipm_project.h).  One call's arguments: img = [N][oh][ow][3]
 // bytes, or [N][3][oh][ow] with chw, valid = [N][oh][ow] bytes, src = [N][oh][ow] int32 -- any may be null --, taken from `frames`
 // ([N][H][W][3]); mask: device, [N] bytes, or null = every env.  The caller checked the sizes, cell and rows_behind as dtsim_bev's.
 struct IpmArgs {

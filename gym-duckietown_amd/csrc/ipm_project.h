@@ -1,4 +1,4 @@
-// ipm_project.h -- the ground projection of dtsim_ipm (the quantity: include/dtsim.h), stated once for the device kernels (render.hip
+// ipm_project.h -- the ground projection of dtsim_ipm (the quantity: include/dtsim.h), stated once for the device kernels (render_views.hip
 // k_ipm_table, k_ipm_env) and for host programs: floor cell -> source pixel of the env's camera frame, in float64.  Plain C++ without a HIP
 // header, so a host program can include it (tests/test_ipm_model_host.py compiles it with g++ under the sanitizers).
 #pragma once

@@ -51,6 +51,9 @@
 //                 grabs (work_n_grabs / work_next_grab over the DT_WORK_* slots of dtsim_dev.h), the tile-record LDS fill; elsewhere the ground quad's
 //                 shading rule (ground_corner_ndl / ground_lit, at ground_ndl), the queue-entry decoders (qe_*) and the 3-byte pixel patch (store_rgb).
 //   Host side: dt_render_layout lays out the render scratch (per-env records, per-pixel tables, queues, work lists); dt_raster_pipe picks the raster.
+//   Elsewhere: render_scene.h -- EnvCam, the planes and classify(), test_tri, the MSAA sample positions (MSAA_POS) and the source-pixel centre (src_px) --
+//                 is shared with render_views.hip, which holds every kernel that reads what this pass leaves behind (overlay lines and LEDs, depth,
+//                 labels / instances, bird's-eye map, ground projection) and uses none of the machinery above.
 //
 // Roofline: algorithmic bytes per env-step = W*H*3 (921 600 B at 640x480), written once (+ the ~1.3 % edge
 // pixels a second time); LUT / textures / tables are shared by all envs and stay in registers / LDS / L2.
@@ -60,6 +63,7 @@
 // Parity: every pipeline is held to frames the unmodified reference rendered on Mesa llvmpipe (tests/test_gpu_gl_golden.py).
 #include "dtsim_dev.h"
 #include "raster_map.h"
+#include "render_scene.h"
 #include <hip/hip_fp16.h>
 #include <type_traits>
 #include <algorithm>
@@ -81,7 +85,6 @@ __device__ inline v3_i32x4 v3_rsrc(const void* p, uint32_t bytes) {
   return r;
 }
 
-
 #define RB 256            // threads per workgroup (4 wavefronts)
 #define PPT DT_PPT         // pixels per thread
 #define WAVE_W DT_WAVE_W  // pixel columns per wavefront block (dtsim_dev.h)
@@ -97,31 +100,6 @@ __device__ inline v3_i32x4 v3_rsrc(const void* p, uint32_t bytes) {
 #define DT_TRI_PAD 0.5f        // round 3: was 1 px; a quarter fewer box candidates per pixel in k_resolve_obj's z-buffer, same frames
 #endif
 #define TRI_CAP DT_TRI_CAP  // LDS triangle slots per wavefront in k_resolve_obj (streamed chunks)
-
-#define CLS_SKY 0
-#define CLS_GROUND 1
-#define CLS_TILE 2
-
-#define NEAR_Z 0.04f
-#define FAR_Z 100.0f
-#define GROUND_Y (-0.008f)   // ground quad: y=-0.8 scaled by 0.01 (simulator.py:510-526,1810)
-#define GROUND_HALF 50.0f
-
-struct alignas(16) EnvCam {          // 32 floats = 128 B, written by k_cam_setup
-  float Cx, Cy, Cz;      // camera centre (world)
-  float sa, ca;          // yaw
-  float sth, cth;        // pitch (cam_angle[0])
-  float tx, ty;          // tan(fov_y/2)*aspect, tan(fov_y/2)
-  float hor[3];          // horizon colour * 255
-  float gnd[3];          // ground colour * 255
-  float base[3];         // scene ambient 0.3 + light ambient
-  float dif[3];          // light diffuse
-  float L[4];            // light position, eye space (w=0: direction, pre-normalised)
-  float gndl[4];         // max(0, N.L) at the 4 ground-quad corners (-x-z, +x-z, -x+z, +x+z)
-  int32_t map_id;
-  float pad[2];
-};
-static_assert(sizeof(EnvCam) == 128, "EnvCam is 128 bytes");
 
 // Everything the fast path needs per env, fully precomputed by k_cam_setup so that the env loop of
 // k_raster does no wave-uniform arithmetic on the vector ALU (there is no scalar float ALU on gfx950):
@@ -168,26 +146,7 @@ static_assert(sizeof(EnvV) == 64, "EnvV is 64 bytes");
 struct alignas(16) EnvL { float Lr, Lf, h2, kd8; };
 static_assert(sizeof(EnvL) == 16, "EnvL is 16 bytes");
 
-// coverage-only part of a ScreenTri kept in LDS by k_resolve_obj; the winner's colours are fetched
-// from global memory.
-struct alignas(16) TriCov { float bx0, bx1, by0, by1; float sx[3], sy[3], iw[3]; float inv_area; int32_t index; int32_t pad; };   // == first half of ScreenTri
-static_assert(sizeof(TriCov) == 64, "TriCov is 64 bytes");
-
 namespace {
-
-// Camera intrinsics / light shared by all envs when DTSIM_F_DOMAIN_RAND is off
-// (simulator.py:119-131 CAMERA_ANGLE / CAMERA_FOV_Y / CAMERA_FLOOR_DIST, :570-576).
-struct CamShared { float sth, cth, tx, ty, Cy, base, dif; float L[4]; };
-
-__device__ inline CamShared default_cam(float aspect) {
-  CamShared s;
-  const float th = 19.15f * 0.017453292519943295f;
-  s.sth = sinf(th); s.cth = cosf(th);
-  s.ty = tanf(0.5f * 75.0f * 0.017453292519943295f); s.tx = s.ty * aspect;
-  s.Cy = 0.108f; s.base = 0.3f + 0.25f; s.dif = 0.35f;
-  s.L[0] = 0.f; s.L[1] = 3.f; s.L[2] = 0.f; s.L[3] = 1.f;
-  return s;
-}
 
 struct EnvD;                                          // render_v3dr.inc: per-env constants of k_raster_v3dr
 __device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const EnvQ& q, const RenderMapDev& m, float q_cells, int H, int W);
@@ -415,7 +374,8 @@ __global__ __launch_bounds__(RB) void k_blk_setup(RenderParams R, const float4* 
     if (x < R.W && y < R.H) {
       const float4 l = lut[y * R.W + x];
       if (l.z != 0.f) {
-        const float sx = (l.x + 1.f) * 0.5f * (float)R.W, sy = (1.f - l.y) * 0.5f * (float)R.H;
+        float sx, sy;
+        src_px(l.x, l.y, R.W, R.H, sx, sy);
         x0 = fminf(x0, sx); x1 = fmaxf(x1, sx); y0 = fminf(y0, sy); y1 = fmaxf(y1, sy);
       }
     }
@@ -441,43 +401,6 @@ __global__ __launch_bounds__(RB) void k_blk_setup(RenderParams R, const float4* 
   }
 }
 
-// ---- per-map constants the raster needs (wave-uniform) -------------------------------
-struct MapU { float its, ts, gwf, ghf; int gw, gh, tile_off; };
-
-__device__ inline MapU map_u(const RenderMapDev& m) {
-  MapU u;
-  u.its = m.inv_tile_size; u.ts = m.tile_size; u.gw = m.grid_w; u.gh = m.grid_h;
-  u.gwf = (float)m.grid_w; u.ghf = (float)m.grid_h; u.tile_off = m.tile_off;
-  return u;
-}
-
-// 1-ulp hardware reciprocal / rsqrt / sqrt: a relative error of 1e-7 moves a ground hit by < 1e-3 texel
-__device__ inline float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ inline float frsq(float x) { return __builtin_amdgcn_rsqf(x); }
-__device__ inline float fsqrt_(float x) { return __builtin_amdgcn_sqrtf(x); }
-
-struct Ray { float xe, ye, yla, fwd; };
-
-__device__ inline Ray make_ray(float nx, float ny, float tx, float ty, float sth, float cth) {
-  Ray r;
-  r.xe = nx * tx; r.ye = ny * ty;
-  r.yla = r.ye * cth - sth;      // world-up component of the ray
-  r.fwd = r.ye * sth + cth;      // component along dir
-  return r;
-}
-
-// positional / directional light on a surface with eye-space normal (0, cth, sth) at the
-// eye-space point t*(xe, ye, -1): max(0, N.L)   (tiles; simulator.py:565-591)
-__device__ inline float plane_ndl(const float L[4], float sth, float cth, const Ray& r, float t) {
-  float ndl;
-  if (L[3] == 0.f) ndl = cth * L[1] + sth * L[2];
-  else {
-    const float lx = L[0] - t * r.xe, ly = L[1] - t * r.ye, lz = L[2] + t;
-    ndl = (cth * ly + sth * lz) * frsq(lx * lx + ly * ly + lz * lz);
-  }
-  return fmaxf(ndl, 0.f);
-}
-
 // ---- GL_LINEAR as the reference's renderer computes it -------------------------------------------------------------------
 // GL leaves the filter's precision to the implementation.  The reference's CI renderer -- Mesa llvmpipe, the one the GL goldens
 // come from (tests/golden/ref_gl_*.npz) -- filters RGBA8 textures in integers (measured bit-exact, profiles/r06_gl_filter_precision.txt):
@@ -492,12 +415,6 @@ __device__ inline void gl_linear_rgb(uint32_t t00, uint32_t t10, uint32_t t01, u
     const int c01 = (int)((t01 >> (8 * k)) & 255u), c11 = (int)((t11 >> (8 * k)) & 255u);
     out[k] = gl_lerp8(wy, gl_lerp8(wx, c00, c10), gl_lerp8(wx, c01, c11));
   }
-}
-
-// The texel coordinates of a textured tile at tile fraction (fx, fz): the record's affine map (tile angle, uv = (pu, 1 - pv), the GL_LINEAR
-// half-texel shift: x = u TW - 0.5, y = v TH - 0.5).  tile_color filters there; k_labels takes the nearest texel.
-__device__ inline void tile_texel_xy(const TileLds& tr, const float fx, const float fz, float& x, float& y) {
-  x = fmaf(tr.mxz, fz, fmaf(tr.mxx, fx, tr.ox)); y = fmaf(tr.myz, fz, fmaf(tr.myx, fx, tr.oy));
 }
 
 // GL_LINEAR/GL_REPEAT fetch from the padded texture (the exact paths and the generic raster: llvmpipe's arithmetic), times the lit
@@ -547,7 +464,6 @@ __device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {      /
   const float b = fminf(fmaxf((wz + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
   return ground_corner_ndl(a, b, c.gndl[0], c.gndl[1], c.gndl[2], c.gndl[3]);
 }
-
 
 #ifndef DT_OBJSETUP_T
 #define DT_OBJSETUP_T 256           // threads of a k_obj_setup workgroup (one workgroup per env)
@@ -736,7 +652,6 @@ __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, Render
   }
 }
 
-
 // max(|a|, |b|) in one instruction (source modifiers; no NaN canonicalisation needed: inputs are finite)
 __device__ inline float absmax(float a, float b) { float r; asm("v_max_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // floor(x) as int in one instruction
@@ -754,38 +669,6 @@ __device__ inline uint32_t pack_rgb(const float col[3]) {  // glReadPixels float
 }
 
 // ---- generic (exact) per-sample path, used for edge pixels ---------------------------
-struct Hit { int cls; int ti, tj; float t, wx, wz; };
-
-__device__ inline void plane_hit(const EnvCam& c, const Ray& r, float h, float& t, float& wx, float& wz) {
-  t = h * frcp(-r.yla);
-  const float rr = t * r.xe, ff = t * r.fwd;
-  wx = c.Cx + rr * c.sa + ff * c.ca;
-  wz = c.Cz + rr * c.ca - ff * c.sa;
-}
-
-__device__ inline Hit classify(const EnvCam& c, const MapU& m, const TileLds* tiles, const Ray& r) {
-  Hit h;
-  h.cls = CLS_SKY; h.ti = h.tj = 0; h.t = 0.f; h.wx = h.wz = 0.f;
-  if (!(r.yla < 0.f)) return h;
-  float t, wx, wz;
-  plane_hit(c, r, c.Cy, t, wx, wz);                 // tile plane y = 0
-  if (t >= NEAR_Z && t <= FAR_Z) {
-    const float fi = floorf(wx * m.its), fj = floorf(wz * m.its);
-    if (fi >= 0.f && fj >= 0.f && fi < m.gwf && fj < m.ghf) {
-      const int i = (int)fi, j = (int)fj;
-      if (tiles[m.tile_off + j * m.gw + i].flags & 1u) {
-        h.cls = CLS_TILE; h.ti = i; h.tj = j; h.t = t; h.wx = wx; h.wz = wz;
-        return h;
-      }
-    }
-  }
-  plane_hit(c, r, c.Cy - GROUND_Y, t, wx, wz);      // ground quad y = -0.008
-  if (t >= NEAR_Z && t <= FAR_Z && fabsf(wx) <= GROUND_HALF && fabsf(wz) <= GROUND_HALF) {
-    h.cls = CLS_GROUND; h.t = t; h.wx = wx; h.wz = wz;
-  }
-  return h;
-}
-
 // Colour (0..255 floats) of primitive `h` evaluated at the pixel-centre ray `rc`
 // (MSAA: coverage per sample, shading once per primitive at the pixel centre).
 __device__ inline void shade(const EnvCam& c, const MapU& m, const RenderParams& R, const TileLds* tiles,
@@ -807,43 +690,6 @@ __device__ inline void shade(const EnvCam& c, const MapU& m, const RenderParams&
   for (int k = 0; k < 3; ++k) I[k] = fminf(c.base[k] + c.dif[k] * ndl, 1.f);
   const float fx = wx * m.its - (float)h.ti, fz = wz * m.its - (float)h.tj;
   tile_color(R, tiles[m.tile_off + h.tj * m.gw + h.ti], fx, fz, I, out);
-}
-
-
-// z-buffer one mesh triangle against the 4 samples of the pixel centred at (pcx, pcy) px.  Depth is kept as
-// w = 1 / depth (larger = nearer; 0 = nothing yet): barycentrics and w are affine in the sample position, so a triangle
-// costs one set-up at the pixel centre + two fused multiply-adds per quantity and sample, and no division.
-template <typename Tri>
-__device__ inline void test_tri_inside(const Tri& st, float pcx, float pcy, float wbest[4], int tbest[4]);
-template <typename Tri>
-__device__ inline void test_tri(const Tri& st, float pcx, float pcy, float wbest[4], int tbest[4]) {
-  if (pcx < st.bx0 || pcx > st.bx1 || pcy < st.by0 || pcy > st.by1) return;
-  test_tri_inside(st, pcx, pcy, wbest, tbest);
-}
-// ... the pixel centre is already known to lie in the triangle's (padded) screen box
-template <typename Tri>
-__device__ inline void test_tri_inside(const Tri& st, float pcx, float pcy, float wbest[4], int tbest[4]) {
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
-  // b0(q) = ((x1-qx)(y2-qy) - (x2-qx)(y1-qy)) / area: d/dqx = (y1-y2)/area, d/dqy = (x2-x1)/area; b1 likewise;
-  // w(q) = iw2 + b0 (iw0 - iw2) + b1 (iw1 - iw2)
-  const float ia = st.inv_area;
-  const float e0x = st.sx[0] - pcx, e0y = st.sy[0] - pcy, e1x = st.sx[1] - pcx, e1y = st.sy[1] - pcy, e2x = st.sx[2] - pcx, e2y = st.sy[2] - pcy;
-  const float b0c = (e1x * e2y - e2x * e1y) * ia, b1c = (e2x * e0y - e0x * e2y) * ia;
-  const float g0x = (e1y - e2y) * ia, g0y = (e2x - e1x) * ia, g1x = (e2y - e0y) * ia, g1y = (e0x - e2x) * ia;
-  const float d0 = st.iw[0] - st.iw[2], d1 = st.iw[1] - st.iw[2];
-  const float wc = fmaf(b1c, d1, fmaf(b0c, d0, st.iw[2]));
-  const float gwx = fmaf(g1x, d1, g0x * d0), gwy = fmaf(g1y, d1, g0y * d0);
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float b0 = fmaf(g0y, oy[s], fmaf(g0x, ox[s], b0c));
-    const float b1 = fmaf(g1y, oy[s], fmaf(g1x, ox[s], b1c));
-    const float b2 = 1.f - b0 - b1;
-    const float w = fmaf(gwy, oy[s], fmaf(gwx, ox[s], wc));
-    // depth func LESS within [near, far]; equal depth: the earlier triangle in draw order keeps the sample
-    const bool in = fminf(fminf(b0, b1), b2) >= 0.f && w <= 1.f / NEAR_Z && w >= 1.f / FAR_Z;
-    if (in && (w > wbest[s] || (w == wbest[s] && st.index < tbest[s]))) { wbest[s] = w; tbest[s] = st.index; }
-  }
 }
 
 // z-buffer the `fill` staged triangles of the wavefront-local LDS chunk against the pixels of the
@@ -919,8 +765,7 @@ __device__ inline void zbuffer_chunk(const TriCov* w_tris, uint32_t* w_scr, int 
         const float qx = __shfl(pcx, src), qy = __shfl(pcy, src);
         if (act) {
           const TriCov& st = w_tris[pr >> 6];
-          const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-          const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
+          const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
           const float ia = st.inv_area;
           const float e0x = st.sx[0] - qx, e0y = st.sy[0] - qy, e1x = st.sx[1] - qx, e1y = st.sy[1] - qy, e2x = st.sx[2] - qx, e2y = st.sy[2] - qy;
           const float b0c = (e1x * e2y - e2x * e1y) * ia, b1c = (e2x * e0y - e0x * e2y) * ia;
@@ -978,8 +823,7 @@ template <bool OBJ>
 __device__ inline uint32_t shade_msaa(const EnvCam& c, const MapU& m, const RenderParams& R,
                                       const TileLds* tiles, float nx, float ny, const ScreenTri* tris,
                                       const float zbest[4], const int tbest[4]) {
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
+  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
   const float sxn = 2.f / (float)R.W, syn = 2.f / (float)R.H;
   const Ray rc = make_ray(nx, ny, c.tx, c.ty, c.sth, c.cth);
   // 1. coverage: which primitive owns each sample.  key: 0 sky, 1 ground, 2|tj<<2|ti<<14 tile,
@@ -1047,7 +891,8 @@ __device__ inline uint32_t shade_msaa(const EnvCam& c, const MapU& m, const Rend
       tile_color(R, tiles[m.tile_off + tj * m.gw + ti], fx, fz, tI, col);
     } else if (OBJ) {
       const ScreenTri& st = tris[k0 >> 2];
-      const float pcx = (nx + 1.f) * 0.5f * (float)R.W, pcy = (1.f - ny) * 0.5f * (float)R.H;   // pixel centre, px
+      float pcx, pcy;                                     // pixel centre, px
+      src_px(nx, ny, R.W, R.H, pcx, pcy);
       const float b0 = ((st.sx[1] - pcx) * (st.sy[2] - pcy) - (st.sx[2] - pcx) * (st.sy[1] - pcy)) * st.inv_area;
       const float b1 = ((st.sx[2] - pcx) * (st.sy[0] - pcy) - (st.sx[0] - pcx) * (st.sy[2] - pcy)) * st.inv_area;
       const float b2 = 1.f - b0 - b1;
@@ -1400,7 +1245,8 @@ struct ChunkObjMasks {
 // 1024, which the object-box margin covers.  The unpack sits behind a register barrier: it is redone per env, not hoisted ahead of the env
 // loop (8 registers).
 __device__ inline uint32_t spxy_pack(const float4& l, const int W, const int H) {
-  const float sx = (l.x + 1.f) * 0.5f * (float)W, sy = (1.f - l.y) * 0.5f * (float)H;
+  float sx, sy;
+  src_px(l.x, l.y, W, H, sx, sy);
   return (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
 }
 __device__ inline void spxy_unpack(uint32_t t, float& sx, float& sy) {
@@ -1469,7 +1315,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
   float wbx0 = 1e30f, wbx1 = -1e30f, wby0 = 1e30f, wby1 = -1e30f;
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
-    spx[k] = (nx[k] + 1.f) * 0.5f * (float)R.W; spy[k] = (1.f - ny[k]) * 0.5f * (float)R.H;
+    src_px(nx[k], ny[k], R.W, R.H, spx[k], spy[k]);
     if (ok[k]) { wbx0 = fminf(wbx0, spx[k]); wbx1 = fmaxf(wbx1, spx[k]); wby0 = fminf(wby0, spy[k]); wby1 = fmaxf(wby1, spy[k]); }
   }
 #pragma unroll
@@ -1705,7 +1551,6 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
   }
 }
 
-
 // ---- per-pixel tables of the shared camera (env-invariant; built by k_pix_setup) ----------------------------------
 // PixTab: what k_raster_q keeps in registers per pixel.  lit: < 0 source pixel outside the image (BORDER_CONSTANT 0),
 // 0 sky for all four samples, > 0 the lit factor min(base + dif * N.L, 1) of the tile plane at the pixel-centre hit.
@@ -1738,8 +1583,7 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
   t.mi |= (uint32_t)__half_as_ushort(__float2half_ru(fminf(p.mrg, 60000.f))) << 16;
   pixtab[pix] = t;
   SampTab sp;
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
+  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
   const float sxn = 2.f / (float)R.W, syn = 2.f / (float)R.H;
   sp.flags = 0u;
   float dlr[4], dlf[4];
@@ -1763,7 +1607,6 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
   sp.pad[0] = __float_as_uint(t.lr); sp.pad[1] = __float_as_uint(t.lf); sp.pad[2] = __float_as_uint(t.lit);   // the PixTab's hit and lit factor once more: phase 2 of the exact path reads ONE table
   samptab[pix] = sp;
 }
-
 
 // ---- resolve_region_q: exact path of k_raster_q (shared camera, no mesh objects) ------------------------------------
 // Called by every wavefront of k_raster_q at the end of its env loop on ITS OWN queue region (the entries it appended):
@@ -2622,7 +2465,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
             if (!have[j]) pix[j] = 0;
             const float4 l = reinterpret_cast<const float4*>(R.lut)[pix[j]];
             nxv[j] = l.x; nyv[j] = l.y;
-            const float pcx = (l.x + 1.f) * 0.5f * (float)R.W, pcy = (1.f - l.y) * 0.5f * (float)R.H;
+            float pcx, pcy;
+            src_px(l.x, l.y, R.W, R.H, pcx, pcy);
             if (have[j]) { x0 = fminf(x0, pcx); x1 = fmaxf(x1, pcx); y0 = fminf(y0, pcy); y1 = fmaxf(y1, pcy); }
 #pragma unroll
             for (int q = 0; q < 4; ++q) { zbest[j][q] = 0.f; tbest[j][q] = -1; }   // w = 1 / depth: 0 = nothing yet
@@ -2674,8 +2518,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                   if (j > 0 && g0 + j * 64 >= n_p) break;            // wave-uniform
-                  zbuffer_chunk(w_tris, w_scr, fill, have[j], lane, (nxv[j] + 1.f) * 0.5f * (float)R.W, (1.f - nyv[j]) * 0.5f * (float)R.H,
-                                zbest[j], tbest[j]);
+                  float pcx, pcy;
+                  src_px(nxv[j], nyv[j], R.W, R.H, pcx, pcy);
+                  zbuffer_chunk(w_tris, w_scr, fill, have[j], lane, pcx, pcy, zbest[j], tbest[j]);
                 }
                 fill = 0;
               }
@@ -2700,637 +2545,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
   }
 }
 
-
-// ---- k_overlay_lines: the reference's GL_LINE overlays as a post-pass on the resolved frames --------------------------------------
-// draw_curve (simulator.py:1886-1904, graphics.py:336-349: the lane curves of every drivable tile, 19 segments each, the one most aligned
-// with the heading red, the others blue) and draw_bbox (simulator.py:1907-1918, objects.py:131-146: the collision rectangles of the
-// objects and of the agent at y = 0.01, red).  The host states the segments in WORLD space (dtsim_draw_lines); here every segment is
-// taken through the env's camera (EnvCam: shared or domain-randomised), clipped at the near plane, and rasterised as GL rasterises a
-// 1-pixel line under multisampling: the rectangle of width 1 px around the projected segment, coverage per MSAA sample.  The pass works on
-// the RESOLVED frame, per OUTPUT pixel (its source pixel comes from the LUT, so the fisheye remap is honoured): a pixel with n of its four
-// samples covered becomes ((4 - n) frame + sum of the covering lines' colours) / 4 -- what the multisample resolve gives when the line is
-// the nearest thing in the pixel.  Documented deviations from the GL state machine: lines are not depth-tested against
-// mesh objects (they lie 1 cm above the tile plane: in front of tiles and ground always); their colour is the glColor lit as a surface
-// with normal +y (GL_COLOR_MATERIAL, the normal the tile draw leaves behind), the texel of whatever texture is still bound is not applied;
-// where two lines cover one sample the first in the list wins (depth func LESS on equal depths).
-struct OvSeg { float ax, ay, bx, by, inv_len2, r, g, b; };     // projected segment in source-pixel space, lit colour 0..255
-__global__ __launch_bounds__(256) void k_overlay_lines(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ lines,
-                                                       const int first, const int count, const int env) {
-  __shared__ OvSeg s_seg[256];
-  const int tid = threadIdx.x;
-  const int pix = blockIdx.x * 256 + tid;
-  const EnvCam c = cams[env];
-  float sxp = 0.f, syp = 0.f;
-  bool live = false;
-  if (pix < R.W * R.H) {
-    const float4 l = reinterpret_cast<const float4*>(R.lut)[pix];
-    live = l.z != 0.f;
-    sxp = (l.x + 1.f) * 0.5f * (float)R.W; syp = (1.f - l.y) * 0.5f * (float)R.H;       // centre of the source pixel
-  }
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
-  float acc[3] = {0.f, 0.f, 0.f};
-  uint32_t covered = 0u;
-  for (int base = 0; base < count; base += 256) {
-    __syncthreads();
-    {                                                  // stage up to 256 projected segments
-      OvSeg sg; sg.ax = sg.ay = sg.bx = sg.by = 0.f; sg.inv_len2 = -1.f; sg.r = sg.g = sg.b = 0.f;
-      if (base + tid < count) {
-        const float* L = lines + (size_t)(first + base + tid) * 9;
-        float pe[2][3], lit[2];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-          const float rx = L[3 * v] - c.Cx, ry = L[3 * v + 1] - c.Cy, rz = L[3 * v + 2] - c.Cz;
-          const float xla = rx * c.sa + rz * c.ca, zla = -(rx * c.ca - rz * c.sa);
-          pe[v][0] = xla; pe[v][1] = ry * c.cth - zla * c.sth; pe[v][2] = ry * c.sth + zla * c.cth;      // eye space, -z forward
-        }
-        float w0 = -pe[0][2], w1 = -pe[1][2];
-        const float wn = NEAR_Z * 1.0001f;
-        bool ok = !(w0 < wn && w1 < wn);
-        if (ok && (w0 < wn || w1 < wn)) {              // clip the end behind the near plane
-          const int vb = w0 < wn ? 0 : 1, vf = 1 - vb;
-          const float t = (wn - (-pe[vb][2])) / ((-pe[vf][2]) - (-pe[vb][2]));
-#pragma unroll
-          for (int k = 0; k < 3; ++k) pe[vb][k] += t * (pe[vf][k] - pe[vb][k]);
-          w0 = -pe[0][2]; w1 = -pe[1][2];
-        }
-        if (ok) {
-#pragma unroll
-          for (int v = 0; v < 2; ++v) {                // lit as a surface with world normal +y: eye-space normal (0, cth, sth)
-            float ndl;
-            if (c.L[3] == 0.f) ndl = c.cth * c.L[1] + c.sth * c.L[2];
-            else {
-              const float lx = c.L[0] - pe[v][0], ly = c.L[1] - pe[v][1], lz = c.L[2] - pe[v][2];
-              ndl = (c.cth * ly + c.sth * lz) * rsqrtf(lx * lx + ly * ly + lz * lz);
-            }
-            lit[v] = fmaxf(ndl, 0.f);
-          }
-          const float ndl = 0.5f * (lit[0] + lit[1]);  // one colour per segment: the light at its middle
-          sg.ax = (pe[0][0] / w0 / c.tx + 1.f) * 0.5f * (float)R.W; sg.ay = (1.f - pe[0][1] / w0 / c.ty) * 0.5f * (float)R.H;
-          sg.bx = (pe[1][0] / w1 / c.tx + 1.f) * 0.5f * (float)R.W; sg.by = (1.f - pe[1][1] / w1 / c.ty) * 0.5f * (float)R.H;
-          const float dx = sg.bx - sg.ax, dy = sg.by - sg.ay, l2 = dx * dx + dy * dy;
-          sg.inv_len2 = l2 > 1e-12f ? 1.f / l2 : -1.f;
-          sg.r = 255.f * fminf(L[6] * (c.base[0] + c.dif[0] * ndl), 1.f);
-          sg.g = 255.f * fminf(L[7] * (c.base[1] + c.dif[1] * ndl), 1.f);
-          sg.b = 255.f * fminf(L[8] * (c.base[2] + c.dif[2] * ndl), 1.f);
-        }
-      }
-      s_seg[tid] = sg;
-    }
-    __syncthreads();
-    if (!live) continue;
-    const int n = min(256, count - base);
-    for (int i = 0; i < n; ++i) {
-      const OvSeg sg = s_seg[i];
-      if (sg.inv_len2 < 0.f) continue;
-      if (sxp < fminf(sg.ax, sg.bx) - 1.f || sxp > fmaxf(sg.ax, sg.bx) + 1.f || syp < fminf(sg.ay, sg.by) - 1.f || syp > fmaxf(sg.ay, sg.by) + 1.f) continue;
-      const float dx = sg.bx - sg.ax, dy = sg.by - sg.ay;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float qx = sxp + ox[q] - sg.ax, qy = syp + oy[q] - sg.ay;
-        const float u = (qx * dx + qy * dy) * sg.inv_len2;                       // along the segment, 0..1
-        const float cr = qx * dy - qy * dx;                                      // |cross| = distance x length
-        const bool in = u >= 0.f && u <= 1.f && cr * cr * sg.inv_len2 <= 0.25f;   // within half a pixel of the line
-        if (in && !((covered >> q) & 1u)) { covered |= 1u << q; acc[0] += sg.r; acc[1] += sg.g; acc[2] += sg.b; }
-      }
-    }
-  }
-  if (live && covered) {
-    const float nf = (float)(4 - __popc(covered));
-    uint8_t* dst = R.frames + ((size_t)env * R.W * R.H + pix) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dst[k] = (uint8_t)(fminf(fmaxf(0.25f * (nf * (float)dst[k] + acc[k]), 0.f), 255.f) + 0.5f);
-  }
-}
-
-
-// ---- k_overlay_leds: the additively blended LED spheres of enable_leds as a post-pass on the resolved frames --------------------------
-// objects.py:68-121: after a duckiebot's mesh, WorldObj.render_mesh draws per LED a 1 cm gluSphere at alpha 1 and a halo at alpha 0.2 with
-// glBlendFunc(GL_SRC_ALPHA, GL_ONE), depth test and depth writes on, lighting on, no texture.  The host states the spheres in WORLD space in
-// draw order (dtsim_draw_leds: centre, radius, glColor, alpha).  Per OUTPUT pixel (source pixel through the LUT) and MSAA sample: the depth of
-// the opaque scene is recomputed -- the planes by classify(), the meshes by z-buffering the env's projected triangles (ScreenTri, left by the
-// render pass's k_obj_setup) -- and every sphere whose FRONT surface is nearer than the sample's depth adds alpha x its lit colour (GL_COLOR_MATERIAL:
-// colour x (ambient + diffuse N.L) at the hit, clamped) and writes its depth; the pixel becomes frame + sum / 4.  Additive blending is linear, so
-// adding to the resolved frame equals blending into the samples.  Documented deviations (oracle/raster.py overlay_leds states the same
-// interpretation): the analytic sphere for the 10 x 10 tessellation, front surfaces only (a back face that gluSphere happens to
-// emit before the front face would add a second layer), lit per sample instead of per vertex, and all spheres after ALL opaque objects (GL
-// interleaves them with the objects in map order).  Not a hot path: one thread per pixel, the triangle loop only under a sphere's screen box.
-struct LedS { float ex, ey, ez, r, cr, cg, cb, a, bx0, bx1, by0, by1; };     // eye-space centre, radius, colour, alpha, source-pixel box
-
-// The opaque scene's eye depth at the four MSAA samples of ONE source pixel of one env (k_overlay_leds, k_depth): centre (nx, ny) in NDC =
-// (sxp, syp) in pixels, sample q at NDC (nx + ox[q] sxn, ny - oy[q] syn).  The planes by classify() -- the frame's own ownership test: tile
-// present / ground extent / sky --, the meshes by z-buffering the env's projected triangles (boxes / tb: the env's ObjBox and ScreenTri rows that
-// the render pass's k_obj_setup left, n_obj of them; boxes null: no mesh objects) for the lanes inside an object's screen box.  depth[q] = t of
-// the eye-space ray (dx, dy, -1) t; `sky` where the sample sees the clear colour.
-// WHO (k_labels): also who owns each sample -- hits[q] = classify()'s plane hit (class, tile, world hit), obj[q] = the object (the o of the
-// ObjBox loop) whose triangle won the sample's z-buffer AND lies strictly nearer than the plane (the colour pass's depth test, shade_msaa),
-// else -1.  Without WHO (hits, obj unused, may be null) nothing of that is compiled: the depth arithmetic is the same statements in both.
-template <bool WHO>
-__device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
-                                      const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
-                                      const float sky, float depth[4], Hit* hits, int* obj) {
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
-  float wbest[4] = {0.f, 0.f, 0.f, 0.f};
-  int tbest[4] = {-1, -1, -1, -1};
-  int obest[4] = {-1, -1, -1, -1};
-  if (boxes) {
-    for (int o = 0; o < n_obj; ++o) {
-      const ObjBox ob = boxes[o];
-      if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
-      for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
-      if constexpr (WHO) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)                   // the sample's winner so far is one of this object's triangles
-          if (tbest[q] >= ob.first && tbest[q] < ob.first + ob.count) obest[q] = o;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    // the steps stated here round one way wherever they are inlined: the sample position is an explicit fused multiply-add, the mesh depth one
-    // IEEE division, the minimum exact (PARITY.md 4, "frames of ONE state rendered again"); classify() and test_tri are the frame's own code
-    const Ray rs = make_ray(fmaf(ox[q], sxn, nx), fmaf(-oy[q], syn, ny), c.tx, c.ty, c.sth, c.cth);
-    const Hit h = classify(c, m, tiles, rs);
-    float d = h.cls == CLS_SKY ? sky : h.t;
-    if constexpr (WHO) { hits[q] = h; obj[q] = -1; }
-    if (tbest[q] >= 0) {
-      const float dm = 1.f / wbest[q];
-      if constexpr (WHO) obj[q] = dm < d ? obest[q] : -1;
-      d = fminf(d, dm);
-    }
-    depth[q] = d;
-  }
-}
-__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
-                                    const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
-                                    const float sky, float depth[4]) {
-  scene_samples4<false>(c, m, tiles, boxes, tb, n_obj, nx, ny, sxp, syp, sxn, syn, sky, depth, nullptr, nullptr);
-}
-
-// ---- k_depth: the depth map of every env's camera frame (dtsim_depth; the quantity: include/dtsim.h) -------------------------------------
-// Output pixel (i, j) of the [oh][ow] map is camera pixel (i sy + sy / 2, j sx + sx / 2), sy = H / oh, sx = W / ow: point-sampled, only those
-// pixels are traced.  A thread owns one output pixel -- its table entry (source-pixel NDC, live flag) is loaded once -- and loops over the
-// DEPTH_ENVS envs of its chunk (grid: pixel blocks x env chunks); the env's camera record, map and object boxes are wave-uniform (read-only
-// __restrict__ pointers at a uniform index: scalar loads), and every store is one coalesced row segment of one env's map.  Per env the depth
-// is scene_depth4 -- the code under the LED spheres, i.e. classify() per sample and the z-buffer of the triangles the pass projected -- and
-// the minimum of the four.
-// One state, one result: the env loop is kept as ONE copy of its body (no unrolling, no peeled iteration), so every env of every chunk, the
-// tail chunk included, runs the same instructions on its record, whatever the compiler fuses inside classify() (which is the frame's own
-// code and stays as it is, so its products are not restated as explicit fused multiply-adds here); the pixel's part (table entry, sample
-// offsets) does not depend on the env.  That the compiler keeps one copy is its choice, not a property of this source: the guarantee rests on
-// tests/test_gpu_depth.py::test_env_positions_and_the_tail_chunk_give_the_same_bytes (envs e, e + 64, e + 128 of one state, a second call, a
-// second render: byte-identical), which fails if a peeled or versioned copy ever rounds differently.
-#define DEPTH_ENVS ENVS_PER_BLOCK
-template <bool F16>
-__global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
-                                               const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
-                                               const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                               void* __restrict__ out, const uint8_t* __restrict__ mask) {
-  const int n_out = oh * ow;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
-  const bool in = pix < n_out;
-  const int sy = H / oh, sx = W / ow;
-  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
-  bool live = false;
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    const float4 l = lut[(size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2)];
-    live = l.z != 0.f;                                 // 0: the fisheye leaves this pixel without a source (the frame's black border)
-    nx = l.x; ny = l.y;
-    sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;       // centre of the source pixel
-  }
-  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
-  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-#pragma clang loop unroll(disable)
-  for (int e = e0; e < e1; ++e) {
-    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvCam c = cams[e];
-    // (calling the masked form with another mask than the pass's is the caller's error -- include/dtsim.h -- and its result is undefined: the
-    // record of a skipped env is an older state's, or the zeros the scratch starts with.  The clamp only keeps that error from indexing
-    // outside the map table on a device others share.)
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];
-    const MapU m = map_u(rm);
-    float d = 0.f;
-    if (live) {
-      float ds[4];
-      scene_depth4(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
-                   objbox ? rm.n_obj : 0, nx, ny, sxp, syp, sxn, syn, __builtin_inff(), ds);
-      d = fminf(fminf(ds[0], ds[1]), fminf(ds[2], ds[3]));
-    }
-    if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if (F16) static_cast<__half*>(out)[at] = __float2half_rn(d);
-      else static_cast<float*>(out)[at] = d;
-    }
-  }
-}
-
-// ---- k_labels: the semantic label map of every env's camera frame (dtsim_labels; the quantity: include/dtsim.h) ---------------------------
-// The sibling of k_depth: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once, the env's camera
-// record, map and object boxes at a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_labels.py holds envs e, e + 64,
-// e + 128 to the same bytes).  Per env it runs scene_samples4<true> -- scene_depth4's statements plus who owns each sample --, takes the sample
-// with the smallest depth (ties: the lowest index; sky = +inf, so it wins only when all four are sky) and maps its owner to a class: the mesh
-// table through the map's object-instance table, the two fixed plane classes, or for a tile the class of the nearest texel -- the texel
-// coordinates are tile_texel_xy's, the ones tile_color filters at, with the half-texel shift taken back: floor(x + 0.5), wrapped.
-// A thread owns ONE pixel, not four adjacent ones: the pass is bound by the four classify() calls and the triangle loop per pixel and env, not
-// by its stores (k_depth takes the same time for half maps as for float32 ones, profiles/depth_timing.txt; k_labels, with a quarter of the
-// bytes, takes 1.4 x k_depth's time on planes and the same time under meshes, profiles/labels_timing.txt); four pixels per lane would serialise
-// four of those per lane for the sake of one wider store, and a wavefront's 64 byte stores are still one contiguous 64-byte row segment.
-// tex_w, tex_h: the one (power-of-two) size of all tile textures; texel_class: dt_pack_label_tables' pool, addressed like R.texels.
-// LAB / INST (dtsim_labels: <true, false>; dtsim_instances: <false, true>, or <true, true> when it is given a label map too): which of the two
-// maps the launch writes, from the ONE classification of the pixel -- `inst` takes o + 1 of the winning sample's object (the o of
-// scene_samples4<true>: the env's map's object list), DTSIM_INSTANCE_NONE for every other owner and for a pixel without a source; a second
-// byte store at the same offset, as coalesced as the first.  Without LAB the class mapping -- mesh table, tile record, texel gather -- is not
-// compiled, and the plane hits it alone reads are dead.
-static_assert(DTSIM_MAX_OBJECTS <= 255, "an instance id o + 1 must fit the map's byte");
-template <bool LAB, bool INST>
-__global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
-                                                const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
-                                                const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
-                                                const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h,
-                                                const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                                uint8_t* __restrict__ out, uint8_t* __restrict__ inst, const uint8_t* __restrict__ mask) {
-  const int n_out = oh * ow;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
-  const bool in = pix < n_out;
-  const int sy = H / oh, sx = W / ow;
-  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
-  bool live = false;
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    const float4 l = lut[(size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2)];
-    live = l.z != 0.f;                                 // 0: the fisheye leaves this pixel without a source (the frame's black border)
-    nx = l.x; ny = l.y;
-    sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;       // centre of the source pixel
-  }
-  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
-  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-#pragma clang loop unroll(disable)
-  for (int e = e0; e < e1; ++e) {
-    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvCam c = cams[e];
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
-    const MapU m = map_u(rm);
-    uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
-    if (live) {
-      float ds[4];
-      Hit hs[4];
-      int os[4];
-      scene_samples4<true>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
-                           objbox ? rm.n_obj : 0, nx, ny, sxp, syp, sxn, syn, __builtin_inff(), ds, hs, os);
-      float db = ds[0];
-      Hit hb = hs[0];
-      int ob = os[0];
-#pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; }
-      if constexpr (INST) who = ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE;
-      if constexpr (LAB) {
-        if (ob >= 0) {
-          const int mid = objs[rm.obj_off + ob].mesh_id;
-          cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
-        } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
-        else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
-        else {
-          const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
-          cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
-          if (tr.flags & 2u) {
-            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade() takes it
-            float x, y;
-            tile_texel_xy(tr, fx, fz, x, y);
-            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
-          }
-        }
-      }
-    }
-    if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if constexpr (LAB) out[at] = (uint8_t)cls;
-      if constexpr (INST) inst[at] = (uint8_t)who;
-    }
-  }
-}
-// ---- k_bev: the egocentric bird's-eye label map of every env (dtsim_bev; the quantity: include/dtsim.h) ------------------------------------
-// The grid of k_depth / k_labels: cell blocks x env chunks of DEPTH_ENVS.  A thread owns ONE cell; its place in the agent's frame -- f cells
-// ahead, s cells to the right, both multiples of one half and exact in float32 -- does not depend on the env and is computed once.  The env
-// loop is ONE copy of its body (tests/test_gpu_bev.py holds envs e, e + 64 and e + 128 to the same bytes), and a wavefront's 64 byte stores
-// are one contiguous segment of one env's map.
-// Per (workgroup, env), once, by the first wavefront.  Before the loop its lane l takes env e0 + l of the chunk: the pose in double, sincos of
-// the double angle in double (cur_angle is unbounded: a float32 of it would lose the direction), kept in LDS in double for the objects and
-// rounded to float32 for the cells, beside what a cell needs of the env's map (the map id clamped as k_depth clamps it) -- one chain of load
-// latencies and one sincos for the chunk, not one per env (measured: profiles/bev_timing.txt).  The tile records of all maps (at most
-// DTSIM_LDS_TILES of 32 bytes) are staged in dynamic LDS as well: a cell's iteration is a chain of dependent reads -- its env, its tile's
-// record, its texel's class -- and with 64 envs in series per thread the pass is bound by that chain's latency, not by its stores.
-// In the loop, for an env whose map has objects, lane o brings object o into the agent's frame -- a BevRect: the centre of its collision
-// rectangle and the two half-axes u, v in cell units, kept as the dual pair (A, B) with P - centre = a u + b v, a = (P - centre) . A,
-// b = (P - centre) . B, so that the cell's test is |a| <= 1 and |b| <= 1 -- from the packed corners of a static object (ocorners) or the env's
-// current SimArrays::ob_corners of a dynamic one.  Hidden objects, objects without a mesh and objects whose bounding circle misses the window
-// are dropped and the rest compacted in lane order (ballot + prefix count): the list in LDS is in ascending object index, its length is
-// wave-uniform, and most envs loop over none.  The list is double-buffered in LDS, so one barrier per such env suffices: the first
-// wavefront fills slot (it + 1) & 1 while the others may still read slot it & 1, which is not written again before the next barrier.  An
-// env on a map without objects (workgroup-uniform) meets no barrier and no work of the first wavefront at all.
-// Per cell: the first rectangle of the list that holds the cell gives the class and the id; else the tile under P = (x, z) + f d + s r
-// (float32 from the rounded pose: five roundings, < 1e-5 m below 32 m), found and sampled by k_labels' statements -- floorf(w * its), the tile
-// fraction w * its - tile, tile_texel_xy, floor(x + 0.5) wrapped, the texel_class pool -- so a camera label pixel and a cell that hit one
-// world point name one class.  No camera record, no distortion table, nothing a render pass leaves behind is read.
-struct alignas(16) BevRect { float cf, cs, af, as, bf, bs; uint32_t cls, id; };
-struct alignas(16) BevEnv {                                        // what a cell needs of its env, in LDS:
-  float x, z, dc, ds;                                              // the pose; cell * cos, cell * sin of the angle
-  float its; int tile_off, gw, gh;                                 // its map: 1 / tile size, first tile record, grid size
-  int n_obj, obj_off, pad[2];                                      // ... object count, first object instance
-};
-struct alignas(16) BevPose { double x, z, cs, sn; };               // the same in double: the pose, cos and sin of the angle
-static_assert(DTSIM_MAX_OBJECTS <= 64, "one lane of the first wavefront per object");
-template <bool LAB, bool INST>
-__global__ __launch_bounds__(256) void k_bev(const double* __restrict__ pos_x, const double* __restrict__ pos_z, const double* __restrict__ angle,
-                                             const int32_t* __restrict__ map_id, const double* __restrict__ ob_corners,
-                                             const uint8_t* __restrict__ ob_visible, const RenderMapDev* __restrict__ maps,
-                                             const TileLds* __restrict__ tiles, const ObjInstDev* __restrict__ objs, const double* __restrict__ ocorners,
-                                             const uint8_t* __restrict__ texel_class, const uint8_t* __restrict__ mesh_class, const int n_mesh_class,
-                                             const int tex_w, const int tex_h, const int n_maps, const int n_tile_recs, const int N, const int oh,
-                                             const int ow, const double cell, const int rows_behind, uint8_t* __restrict__ out, uint8_t* __restrict__ inst,
-                                             const uint8_t* __restrict__ mask) {
-  __shared__ BevRect s_rect[2][DTSIM_MAX_OBJECTS];
-  __shared__ int s_n[2];
-  __shared__ BevEnv s_env[DEPTH_ENVS];
-  __shared__ BevPose s_pose[DEPTH_ENVS];
-  extern __shared__ __align__(16) unsigned char s_bev_dyn[];          // [n_tile_recs] TileLds: the tile records of all maps
-  TileLds* s_tiles = reinterpret_cast<TileLds*>(s_bev_dyn);
-  const int n_out = oh * ow;
-  const int tid = threadIdx.x;
-  const int pix = blockIdx.x * 256 + tid;
-  const bool in = pix < n_out;
-  const int i = in ? pix / ow : 0, j = in ? pix - i * ow : 0;
-  const float f = (float)(oh - rows_behind - i) - 0.5f;               // cells ahead of the agent (row 0 is the farthest)
-  const float sd = ((float)j + 0.5f) - 0.5f * (float)ow;              // cells to its right (column 0 is the leftmost)
-  // the window in cell units, for the cull
-  const double f_lo = -(double)rows_behind, f_hi = (double)(oh - rows_behind), s_hi = 0.5 * (double)ow;
-  const double inv_cell = 1.0 / cell;
-  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-  static_assert(DEPTH_ENVS <= 64, "one lane of the first wavefront per env of the chunk");
-  for (int t = tid; t < n_tile_recs; t += 256) s_tiles[t] = tiles[t];
-  if (tid < DEPTH_ENVS && e0 + tid < e1) {
-    BevPose p;
-    p.x = pos_x[e0 + tid]; p.z = pos_z[e0 + tid];
-    sincos(angle[e0 + tid], &p.sn, &p.cs);
-    s_pose[tid] = p;
-    const RenderMapDev rm = maps[min((unsigned)map_id[e0 + tid], (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
-    BevEnv ev{};
-    ev.x = (float)p.x; ev.z = (float)p.z; ev.dc = (float)(cell * p.cs); ev.ds = (float)(cell * p.sn);
-    ev.its = rm.inv_tile_size; ev.tile_off = rm.tile_off; ev.gw = rm.grid_w; ev.gh = rm.grid_h;
-    ev.n_obj = min(rm.n_obj, DTSIM_MAX_OBJECTS); ev.obj_off = rm.obj_off;
-    s_env[tid] = ev;
-  }
-  __syncthreads();
-  int it = 0;
-#pragma clang loop unroll(disable)
-  for (int e = e0; e < e1; ++e) {
-    if (mask && !mask[e]) continue;                    // (workgroup-uniform) the masked call: this env's row keeps its bytes
-    const BevEnv ev = s_env[e - e0];
-    const int n_obj = __builtin_amdgcn_readfirstlane(ev.n_obj), obj_off = __builtin_amdgcn_readfirstlane(ev.obj_off);
-    const int b = it & 1;
-    int n_rect = 0;
-    if (n_obj > 0) {                                   // (workgroup-uniform)
-      ++it;
-      if (tid < 64) {
-        const BevPose p = s_pose[e - e0];
-        const double x = p.x, z = p.z, sn = p.sn, cs = p.cs;
-        bool keep = false;
-        BevRect r{};
-        if (tid < n_obj) {
-          const ObjInstDev oi = objs[obj_off + tid];
-          if (oi.mesh_id >= 0 && ob_visible[(size_t)tid * N + e]) {
-            double c[8];
-            if (oi.dyn_slot >= 0) {
-              const int d = min(oi.dyn_slot, DTSIM_MAX_DYNAMIC - 1);
-#pragma unroll
-              for (int k = 0; k < 8; ++k) c[k] = ob_corners[(size_t)(k * DTSIM_MAX_DYNAMIC + d) * N + e];
-            } else {
-#pragma unroll
-              for (int k = 0; k < 8; ++k) c[k] = ocorners[(size_t)(obj_off + tid) * 8 + k];
-            }
-            // corners 0, 1, 3 in the agent's frame, cell units: ahead = (c - pos) . d, right = (c - pos) . r, d = (cos, -sin), r = (sin, cos)
-            double pf[3], ps[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              const int q = k == 2 ? 3 : k;
-              const double dx = c[2 * q] - x, dz = c[2 * q + 1] - z;
-              pf[k] = (dx * cs - dz * sn) * inv_cell; ps[k] = (dx * sn + dz * cs) * inv_cell;
-            }
-            const double uf = 0.5 * (pf[1] - pf[0]), us = 0.5 * (ps[1] - ps[0]), vf = 0.5 * (pf[2] - pf[0]), vs = 0.5 * (ps[2] - ps[0]);
-            const double cf = pf[0] + uf + vf, cs_ = ps[0] + us + vs;
-            const double det = uf * vs - us * vf;
-            const double rad = sqrt(fmax((uf + vf) * (uf + vf) + (us + vs) * (us + vs), (uf - vf) * (uf - vf) + (us - vs) * (us - vs))) + 1.0;
-            const double df = fmax(fmax(f_lo - cf, cf - f_hi), 0.0), dsd = fmax(fabs(cs_) - s_hi, 0.0);
-            keep = det != 0.0 && df * df + dsd * dsd <= rad * rad;          // (a NaN anywhere: dropped)
-            r.cf = (float)cf; r.cs = (float)cs_;
-            r.af = (float)(vs / det); r.as = (float)(-vf / det); r.bf = (float)(-us / det); r.bs = (float)(uf / det);
-            r.cls = LAB ? (uint32_t)mesh_class[min((unsigned)oi.mesh_id, (unsigned)(n_mesh_class - 1))] : 0u;
-            r.id = (uint32_t)tid + 1u;
-          }
-        }
-        const unsigned long long kept = __ballot(keep);
-        if (keep) s_rect[b][__popcll(kept & ((1ull << tid) - 1ull))] = r;
-        if (tid == 0) s_n[b] = __popcll(kept);
-      }
-      __syncthreads();
-      n_rect = __builtin_amdgcn_readfirstlane(s_n[b]);
-    }
-    uint32_t cls = DTSIM_LABEL_GROUND, who = DTSIM_INSTANCE_NONE;
-    bool hit = false;
-    for (int k = 0; k < n_rect; ++k) {                 // (wave-uniform count; LDS broadcast reads)
-      const BevRect r = s_rect[b][k];
-      const float pf = f - r.cf, ps = sd - r.cs;
-      const float a = fmaf(ps, r.as, pf * r.af), bb = fmaf(ps, r.bs, pf * r.bf);
-      if (fabsf(a) <= 1.f && fabsf(bb) <= 1.f) { cls = r.cls; who = r.id; hit = true; break; }
-    }
-    if constexpr (LAB) {
-      if (!hit) {
-        const float wx = fmaf(sd, ev.ds, fmaf(f, ev.dc, ev.x));
-        const float wz = fmaf(sd, ev.dc, fmaf(-f, ev.ds, ev.z));
-        const float its = ev.its;
-        const float fi = floorf(wx * its), fj = floorf(wz * its);
-        if (fi >= 0.f && fj >= 0.f && fi < (float)ev.gw && fj < (float)ev.gh) {
-          const int ti = (int)fi, tj = (int)fj;
-          const TileLds tr = s_tiles[ev.tile_off + tj * ev.gw + ti];
-          if ((tr.flags & 3u) == 3u) {                 // present and textured (else: the ground's class)
-            const float fx = wx * its - (float)ti, fz = wz * its - (float)tj;     // the tile fraction, as k_labels takes it
-            float x, y;
-            tile_texel_xy(tr, fx, fz, x, y);
-            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
-          }
-        }
-      }
-    }
-    if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if constexpr (LAB) out[at] = (uint8_t)cls;
-      if constexpr (INST) inst[at] = (uint8_t)who;
-    }
-  }
-}
-
-#include "render_ipm.inc"
-
-__global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
-                                                      const int first, const int count, const int env) {
-  __shared__ LedS s_led[64];
-  const int tid = threadIdx.x;
-  const int pix = blockIdx.x * 256 + tid;
-  const EnvCam c = cams[env];
-  const MapU m = map_u(R.maps[c.map_id]);
-  const TileLds* tiles = reinterpret_cast<const TileLds*>(R.tile_recs);
-  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
-  bool live = false;
-  if (pix < R.W * R.H) {
-    const float4 l = reinterpret_cast<const float4*>(R.lut)[pix];
-    live = l.z != 0.f;
-    nx = l.x; ny = l.y;
-    sxp = (l.x + 1.f) * 0.5f * (float)R.W; syp = (1.f - l.y) * 0.5f * (float)R.H;       // centre of the source pixel
-  }
-  const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-  const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
-  const float sxn = 2.f / (float)R.W, syn = 2.f / (float)R.H;
-  float add[3] = {0.f, 0.f, 0.f};
-  float depth[4] = {0.f, 0.f, 0.f, 0.f};
-  bool have_depth = false, any = false;
-  for (int base = 0; base < count; base += 64) {
-    __syncthreads();
-    if (tid < 64) {
-      LedS sp; sp.r = -1.f; sp.ex = sp.ey = sp.ez = sp.cr = sp.cg = sp.cb = sp.a = 0.f; sp.bx0 = sp.by0 = 1.f; sp.bx1 = sp.by1 = 0.f;
-      if (base + tid < count) {
-        const float* S = spheres + (size_t)(first + base + tid) * 8;
-        const float rx = S[0] - c.Cx, ry = S[1] - c.Cy, rz = S[2] - c.Cz;
-        const float xla = rx * c.sa + rz * c.ca, zla = -(rx * c.ca - rz * c.sa);
-        sp.ex = xla; sp.ey = ry * c.cth - zla * c.sth; sp.ez = ry * c.sth + zla * c.cth;                 // eye space, -z forward
-        const float w = -sp.ez, r = S[3];
-        if (r > 0.f && w + r > NEAR_Z) {
-          sp.r = r; sp.cr = S[4]; sp.cg = S[5]; sp.cb = S[6]; sp.a = S[7];
-          const float wn = fmaxf(w - r, NEAR_Z);
-          const float cx = (sp.ex / w / c.tx + 1.f) * 0.5f * (float)R.W, cy = (1.f - sp.ey / w / c.ty) * 0.5f * (float)R.H;
-          const float rad = r / wn / fminf(c.tx / (float)R.W, c.ty / (float)R.H) * 0.5f * 1.5f + 2.f;     // conservative: only prunes
-          sp.bx0 = cx - rad; sp.bx1 = cx + rad; sp.by0 = cy - rad; sp.by1 = cy + rad;
-          if (!(w > 0.f)) { sp.bx0 = sp.by0 = -1e30f; sp.bx1 = sp.by1 = 1e30f; }                          // centre behind the eye: no box, test everything
-        }
-      }
-      s_led[tid] = sp;
-    }
-    __syncthreads();
-    if (!live) continue;
-    const int n = min(64, count - base);
-    for (int i = 0; i < n; ++i) {
-      const LedS sp = s_led[i];
-      if (!(sp.r > 0.f) || sxp < sp.bx0 || sxp > sp.bx1 || syp < sp.by0 || syp > sp.by1) continue;
-      if (!have_depth) {                               // the opaque scene's depth at the four samples, once per pixel that any sphere may touch
-        have_depth = true;
-        const bool obj = R.stris && R.objbox;
-        scene_depth4(c, m, tiles, obj ? R.objbox + (size_t)env * DTSIM_MAX_OBJECTS : nullptr, obj ? R.stris + (size_t)env * R.max_tris : nullptr,
-                     obj ? R.maps[c.map_id].n_obj : 0, nx, ny, sxp, syp, sxn, syn, 3.0e38f, depth);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float dx = (nx + ox[q] * sxn) * c.tx, dy = (ny - oy[q] * syn) * c.ty;       // eye-space ray (dx, dy, -1) t, t = eye depth
-        const float a = dx * dx + dy * dy + 1.f;
-        const float b = dx * sp.ex + dy * sp.ey - sp.ez;
-        const float cc = sp.ex * sp.ex + sp.ey * sp.ey + sp.ez * sp.ez - sp.r * sp.r;
-        const float disc = b * b - a * cc;
-        if (!(disc > 0.f)) continue;
-        const float t = (b - sqrtf(disc)) / a;
-        if (!(t >= NEAR_Z && t <= FAR_Z && t < depth[q])) continue;
-        const float px = t * dx, py = t * dy, pz = -t;
-        const float inv_r = 1.f / sp.r;
-        const float nxe = (px - sp.ex) * inv_r, nye = (py - sp.ey) * inv_r, nze = (pz - sp.ez) * inv_r;
-        float ndl;
-        if (c.L[3] == 0.f) ndl = nxe * c.L[0] + nye * c.L[1] + nze * c.L[2];
-        else {
-          const float lx = c.L[0] - px, ly = c.L[1] - py, lz = c.L[2] - pz;
-          ndl = (nxe * lx + nye * ly + nze * lz) * rsqrtf(lx * lx + ly * ly + lz * lz);
-        }
-        ndl = fmaxf(ndl, 0.f);
-        add[0] += sp.a * 255.f * fminf(sp.cr * (c.base[0] + c.dif[0] * ndl), 1.f);
-        add[1] += sp.a * 255.f * fminf(sp.cg * (c.base[1] + c.dif[1] * ndl), 1.f);
-        add[2] += sp.a * 255.f * fminf(sp.cb * (c.base[2] + c.dif[2] * ndl), 1.f);
-        depth[q] = t;
-        any = true;
-      }
-    }
-  }
-  if (live && any) {
-    uint8_t* dst = R.frames + ((size_t)env * R.W * R.H + pix) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dst[k] = (uint8_t)(fminf(fmaxf((float)dst[k] + 0.25f * add[k], 0.f), 255.f) + 0.5f);
-  }
-}
-
 }  // namespace
-
-void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env) {
-  if (count <= 0) return;
-  hipLaunchKernelGGL(k_overlay_leds, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, reinterpret_cast<const EnvCam*>(R.envcam), d_spheres, first, count, env);
-}
-
-void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask) {
-  if (R.N <= 0) return;
-  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-#define LAUNCH_DEPTH(F16_) hipLaunchKernelGGL(k_depth<F16_>, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs, \
-                                              reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.max_tris,    \
-                                              R.n_maps, R.N, R.W, R.H, oh, ow, out, mask)
-  if (f16) LAUNCH_DEPTH(true); else LAUNCH_DEPTH(false);
-#undef LAUNCH_DEPTH
-}
-
-void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
-                      uint8_t* inst, int oh, int ow, const uint8_t* mask) {
-  if (R.N <= 0 || (!out && !inst)) return;
-  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  auto k = out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>;
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
-                     reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
-                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask);
-}
-
-void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
-                   const uint8_t* mesh_class, int n_mesh_class, uint8_t* cls, uint8_t* inst, int oh, int ow, double cell, int rows_behind,
-                   const uint8_t* mask) {
-  if (R.N <= 0 || (!cls && !inst)) return;
-  const dim3 grid((unsigned)((oh * ow + 255) / 256), (unsigned)((R.N + DEPTH_ENVS - 1) / DEPTH_ENVS));
-  auto k = cls && inst ? k_bev<true, true> : cls ? k_bev<true, false> : k_bev<false, true>;
-  static_assert(DTSIM_LDS_TILES * sizeof(TileLds) <= 32768, "the tile records of all maps fit the workgroup's LDS beside its 10 KB of lists");
-  const int n_recs = min(R.n_tile_recs, DTSIM_LDS_TILES);   // (dt_pack_maps refuses more)
-  hipLaunchKernelGGL(k, grid, dim3(256), (size_t)n_recs * sizeof(TileLds), s, A.pos_x, A.pos_z, A.angle, A.map_id, A.ob_corners, A.ob_visible, R.maps,
-                     R.tile_recs, R.objs, ocorners, texel_class, mesh_class, n_mesh_class, R.tex_w, R.tex_h, R.n_maps, n_recs, R.N, oh, ow, cell, rows_behind,
-                     cls, inst, mask);
-}
-
-void dt_launch_ipm_table(hipStream_t s, int32_t* table, const IpmCal* cal, int W, int H, int oh, int ow, double cell, int rows_behind) {
-  hipLaunchKernelGGL(k_ipm_table, dim3((unsigned)((oh * ow + 255) / 256)), dim3(256), 0, s, dt_ipm_shared_camera(W, H), cal, W, H, oh, ow, cell,
-                     rows_behind, table);
-}
-
-void dt_launch_ipm_gather(hipStream_t s, const IpmArgs& a, const int32_t* table) {
-  if (a.N <= 0) return;
-  const bool vec = dt_ipm_vec(a);
-  auto k = a.chw ? (vec ? k_ipm_gather<true, true> : k_ipm_gather<true, false>) : (vec ? k_ipm_gather<false, true> : k_ipm_gather<false, false>);
-  hipLaunchKernelGGL(k, dt_ipm_grid(a), dim3(256), 0, s, a.frames, table, a.N, a.oh * a.ow, (size_t)a.W * a.H * 3, a.img, a.valid, a.src, a.mask);
-}
-
-void dt_launch_ipm_env(hipStream_t s, const IpmArgs& a, const SimArrays& A, bool per_env, const IpmCal* cals, int n_cal, const int32_t* env_cal) {
-  if (a.N <= 0) return;
-  const bool vec = dt_ipm_vec(a);
-  auto k = a.chw ? (vec ? k_ipm_env<true, true> : k_ipm_env<true, false>) : (vec ? k_ipm_env<false, true> : k_ipm_env<false, false>);
-  hipLaunchKernelGGL(k, dt_ipm_grid(a), dim3(256), 0, s, a.frames, A.angle, A.cam, per_env ? 1 : 0, dt_ipm_shared_camera(a.W, a.H), cals, n_cal, env_cal,
-                     a.N, a.W, a.H, a.oh, a.ow, a.cell, a.rows_behind, a.img, a.valid, a.src, a.mask);
-}
-
-void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {
-  if (count <= 0) return;
-  hipLaunchKernelGGL(k_overlay_lines, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, reinterpret_cast<const EnvCam*>(R.envcam), d_lines, first, count, env);
-}
 
 // Workgroups of `kernel` (RB threads, lds bytes of dynamic LDS) the device holds at once: the launch size of the persistent exact-path kernels.
 template <class K> static size_t resident_blocks(K kernel, size_t lds) {

@@ -504,8 +504,7 @@ void k_resolve_dr(RenderParams R, const EnvCam* __restrict__ cams, const EnvD* _
         int n_sky = 0, n_gnd = 0;
         float gX = 0.f, gZ = 0.f;                      // ground hit (quad coordinates) of the lowest-index ground sample
         uint32_t raddr[4];
-        const float ox[4] = {-0.125f, 0.375f, -0.375f, 0.125f};
-        const float oy[4] = {0.375f, 0.125f, -0.125f, -0.375f};   // GL_SAMPLE_POSITION of Mesa llvmpipe, rows flipped (+y down the image)
+        const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
 #pragma unroll
         for (int s = 3; s >= 0; --s) {
           const float nxs = fmaf(ox[s], sxn, nx), nys = fmaf(-oy[s], syn, ny);

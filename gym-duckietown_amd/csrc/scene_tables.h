@@ -260,7 +260,7 @@ inline void dt_pack_quad_block(std::vector<uint32_t>& out, const uint32_t* pool,
 }
 
 // The collision rectangles of the maps' objects as the host packed them (dtsim_object.corners: four (x, z) corners in order, float64), maps
-// concatenated in the order of MapTables.robjs -- object o of map m at [RenderMapDev.obj_off + o][8] -- for dtsim_bev (render.hip k_bev),
+// concatenated in the order of MapTables.robjs -- object o of map m at [RenderMapDev.obj_off + o][8] -- for dtsim_bev (render_views.hip k_bev),
 // which draws a static object's footprint from here and a dynamic one's (ObjInstDev.dyn_slot >= 0) from the env's SimArrays::ob_corners.
 // The maps are dt_pack_maps' arguments, already checked by it (object counts within DTSIM_MAX_OBJECTS, non-null lists).
 inline int dt_pack_object_corners(std::vector<double>& out, std::string& err, const dtsim_map* maps, int n_maps) {

@@ -1,12 +1,13 @@
 #!/bin/bash
-# dump the ISA of k_raster<DR=0,OBJ=0> and print the instruction mix of its env loop
-cd /tmp && mkdir -p t && cd t
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -I/root/repo/include -I/root/repo/gym-duckietown_amd/csrc -S --cuda-device-only -o render.s ${1:-/root/repo/gym-duckietown_amd/csrc/render.hip} 2>/dev/null
+# dump the ISA of k_raster<DR=0,OBJ=0> and print the instruction mix of its env loop (units, flags: build.py)
+D=$(cd "$(dirname "$0")/../gym-duckietown_amd" && pwd)
+T=$(mktemp -d) && cd $T
+python $D/build.py --asm ${1:-$D/csrc/render.hip} render.s 2>/dev/null
 L=$(grep -n "^_ZN12_GLOBAL__N_18k_rasterILb0ELb0E.*:" render.s | cut -d: -f1)
 awk -v s=$L "NR>=s" render.s | awk "/^.Lfunc_end/{exit} {print}" > kr00.s
 python3 - <<'PY'
 import re,collections
-lines=open('/tmp/t/kr00.s').read().split('\n')
+lines=open('kr00.s').read().split('\n')
 # loop = from the last "Inner Loop Header" label to the last line mentioning "in Loop"
 hdr=[i for i,l in enumerate(lines) if 'Loop Header' in l][-1]
 end=max(i for i,l in enumerate(lines) if 'in Loop: Header' in l)

@@ -1,15 +1,17 @@
 """Instruction mix of the env loops of k_raster_v3<OBJ=0> / k_raster_v3dr<OBJ=0> from the compiler's ISA (no GPU needed).
 
-    python tools/isa_v3.py [render.hip]        # compiles to /tmp/t/render.s with the library's flags
+    python tools/isa_v3.py [render.hip [-DFOO=1 ...]]   # compiles to $TMPDIR/dtsim_isa/render.s with the library's flags (build.py)
 
 Per inner-most loop of the kernel that stores frames (buffer_store): VALU / SALU / VMEM / DS instruction counts of the loop body and,
 as every iteration shades PPT = 4 pixels per lane, VALU per pixel."""
-import collections, os, re, subprocess, sys
-src = sys.argv[1] if len(sys.argv) > 1 else "/root/repo/gym-duckietown_amd/csrc/render.hip"
-os.makedirs("/tmp/t", exist_ok=True)
-if not os.environ.get("ISA_REUSE"): subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "-I/root/repo/include", "-I/root/repo/gym-duckietown_amd/csrc",
-                "-S", "--cuda-device-only", "-o", "/tmp/t/render.s", src] + sys.argv[2:], check=True, stderr=subprocess.DEVNULL)
-txt = open("/tmp/t/render.s").read().split("\n")
+import collections, os, re, subprocess, sys, tempfile
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gym-duckietown_amd"))
+import build as dtbuild
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(dtbuild.CSRC, "render.hip")
+out = os.path.join(tempfile.gettempdir(), "dtsim_isa", "render.s")
+os.makedirs(os.path.dirname(out), exist_ok=True)
+if not os.environ.get("ISA_REUSE"): subprocess.run(dtbuild.compile_cmd(src, out, sys.argv[2:], asm=True), check=True, stderr=subprocess.DEVNULL)
+txt = open(out).read().split("\n")
 for kern in ("k_raster_v3ILb0E", "k_raster_v3drILb0E", "k_raster_v3ILb1E", "k_raster_v3drILb1E"):
     starts = [i for i, l in enumerate(txt) if re.match(rf"^_ZN\d+_GLOBAL__N_1\d+{kern}\S*:", l)]
     if not starts:
