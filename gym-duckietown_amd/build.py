@@ -6,8 +6,8 @@
 
 UNITS is the one statement of the library's units and their flags: tools/isa_*.py, .sh and tools/build_variant.sh take them from here.
 physics.hip and remap.hip (the camera_rand table builder, pinned to numpy) are compiled with contraction off (separately rounded ops, in
-the reference's operation order); render.hip with contraction allowed (speed, f32), and render_views.hip as render.hip, whose classify()
-and test_tri it shares (csrc/render_scene.h).
+the reference's operation order); render.hip and render_v3.hip with contraction allowed (speed, f32), and render_views.hip as render.hip,
+whose classify() and test_tri it shares (csrc/render_scene.h).
 """
 from __future__ import annotations
 
@@ -22,8 +22,8 @@ LIB = os.path.join(LIBDIR, "libdtsim.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-UNITS = {"physics.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=fast"], "render_views.hip": ["-ffp-contract=fast"],
-         "observe.hip": [], "dtsim_api.hip": [], "remap.hip": ["-ffp-contract=off"]}
+UNITS = {"physics.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=fast"], "render_v3.hip": ["-ffp-contract=fast"],
+         "render_views.hip": ["-ffp-contract=fast"], "observe.hip": [], "dtsim_api.hip": [], "remap.hip": ["-ffp-contract=off"]}
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical",
           "-I" + os.path.join(HERE, "..", "include")]
 
@@ -50,7 +50,7 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
     objdir = os.path.join(LIBDIR, variant) if variant else LIBDIR
     lib = os.path.join(LIBDIR, f"libdtsim_{variant}.so") if variant else LIB
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(HERE, "..", "include", "dtsim.h"))
     objs = [os.path.join(objdir, name.replace(".hip", ".o")) for name in UNITS]
     for name, obj in zip(UNITS, objs):

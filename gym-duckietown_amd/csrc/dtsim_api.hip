@@ -175,6 +175,7 @@ struct dtsim {
   DevPtr<uint8_t> d_mesh_class;       // [n_meshes] class per mesh
   int n_mesh_class = 0;               // entries of d_mesh_class (at least 1)
   DevPtr<char> d_render[DT_SLABS];    // the render scratch (dt_render_layout): DT_SLAB_ENV .. DT_SLAB_QEND, allocated at dtsim_create (the object slabs: maps.d_obj)
+  EnvRecs recs{};                     // the typed per-env records and per-pixel tables inside d_render (dt_render_layout's, set with the slabs)
   bool raster_old = false;            // DTSIM_RASTER_OLD=1 at dtsim_create: neither k_raster_v3 nor k_raster_v3dr (A/B timing only; dt_raster_pipe)
   int step_lanes = 1;                 // lanes of a wavefront per env in k_step (physics.hip Coop): 1, 2 or 4
   DevPtr<dtsim_reset_sampler> d_sampler;      // device copy when a reset sampler is installed
@@ -212,11 +213,11 @@ StepParams step_params(const dtsim* h, int n_steps) {
   return P;
 }
 
-// points R's scratch fields into the handle's render slabs (dt_render_layout)
-void render_scratch(const dtsim* h, int max_tris, RenderParams* R) {
+// points R's scratch fields into the handle's render slabs (dt_render_layout); returns the slabs' typed records
+EnvRecs render_scratch(const dtsim* h, int max_tris, RenderParams* R) {
   void* base[DT_SLABS];
   for (int i = 0; i < DT_SLABS; ++i) base[i] = i < DT_SLAB_STRIS ? h->d_render[i].get() : h->maps.d_obj[i].get();
-  dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, nullptr, base, R);
+  return dt_render_layout(h->N, h->cfg.cam_width, h->cfg.cam_height, max_tris, nullptr, base, R);
 }
 
 // the scene of a pass: the assets (segment: their segmented texels) and the render side of the maps
@@ -322,7 +323,7 @@ int dtsim_create(const dtsim_config* cfg, dtsim_t** out) {
     // the per-env records start zeroed: a post-pass that is wrongly pointed at an env no pass has written (dtsim_depth_masked with another mask
     // than the pass's: the caller's error, its result undefined) then reads no object and no map index outside the tables
     if (e == hipSuccess) e = hipMemset(h->d_render[DT_SLAB_ENV].get(), 0, bytes[DT_SLAB_ENV]);
-    RenderParams R{}; render_scratch(h, 0, &R);
+    RenderParams R{}; h->recs = render_scratch(h, 0, &R);
     if (e == hipSuccess) e = hipMemset(R.dump, 0, sizeof(RenderDump));
     if (e != hipSuccess) { dtsim_destroy(h); return fail(DTSIM_E_HIP, "hipMalloc(render scratch): %s", hipGetErrorString(e)); }
     if (!(cfg->flags & DTSIM_F_DISTORTION)) {
@@ -666,13 +667,13 @@ static int render_pass(dtsim_t* h, uint32_t flags, const uint8_t* mask) {
   R.lut = h->d_lut.get();
   R.segment = segment ? 1 : 0; R.mesh_seg = h->d_mesh_seg.get();
   render_scene(h, segment, &R);
-  render_scratch(h, R.max_tris, &R);
+  render_scratch(h, R.max_tris, &R);                     // (its typed records are h->recs, kept since dtsim_create: the ENV and PIX slabs do not move)
   R.light = ((h->cfg.flags & DTSIM_F_LIGHT_CAPTURE) && !R.domain_rand) ? 1 : 0;   // (the per-env camera path lights from EnvCam anyway)
   if (flags & DTSIM_RENDER_GL_FILTER) R.qtex = nullptr;   // no quad records: the generic raster (llvmpipe's GL_LINEAR arithmetic) takes the pass
   const int pipe = dt_raster_pipe(R, h->maps.grid_rows, h->maps.grid_cols, h->raster_old);
   {
     ProfScope ps(h, DTSIM_KERNEL_RENDER);
-    h->render_tables = dt_launch_render(h->stream, h->A, R, pipe, h->render_tables, mask);
+    h->render_tables = dt_launch_render(h->stream, h->A, R, h->recs, pipe, h->render_tables, mask);
     h->render_pipe = pipe | (R.light ? DTSIM_PIPE_ENV_LIGHT : 0);
     if (h->n_cal) dt_launch_remap_cal(h->stream, h->d_scratch.get(), h->frames, h->d_cal_src.get(), h->d_env_cal.get(), mask, h->N, R.W, R.H);
   }

@@ -14,6 +14,7 @@
 #include "../../include/dtsim.h"
 #include "ipm_project.h"
 #include "observe_plan.h"
+#include "render_records.h"
 #include "scene_tables.h"
 #include "state_fields.h"
 
@@ -73,7 +74,7 @@ struct ObjBox { float bx0, bx1, by0, by1; int32_t first, count, pad[2]; };      
 #define DT_PPT 4                           // pixels per lane: a wavefront's block is 64 * DT_PPT pixels
 #endif
 #ifndef DT_V3_WW
-#define DT_V3_WW 128                       // k_raster_v3 (render_v3.inc): pixel columns of ITS wavefront block (128 / 64 / 32); the workgroup tile stays 128 x 8
+#define DT_V3_WW 128                       // k_raster_v3 (render_v3.hip): pixel columns of ITS wavefront block (128 / 64 / 32); the workgroup tile stays 128 x 8
 #endif
 #define DT_TILE_W DT_WAVE_W
 #define DT_TILE_H (4 * (64 * DT_PPT / DT_WAVE_W))  // 4 wavefronts stacked vertically
@@ -104,7 +105,7 @@ struct RenderParams {
   const ObjInstDev* objs;
   const MeshDev* meshes;
   const TriDev* tris;
-  void* envcam;                 // [N] EnvCam written by the setup kernel (the render scratch: dt_render_layout)
+  EnvCam* envcam;               // [N] EnvCam written by the setup kernel (the render scratch: dt_render_layout; the records: render_records.h)
   // mesh objects: per-env screen-space triangles written by the object setup kernel
   int32_t max_tris, segment;    // triangle slots per env (max over maps), 0 = no objects anywhere; segment: DTSIM_RENDER_SEGMENT
   ScreenTri* stris;             // [N][max_tris]
@@ -127,10 +128,10 @@ struct RenderParams {
   float q_per_m;                // quad cells per metre (S / tile_size), max over maps: scales the MSAA margin
   int32_t qmax_tiles;           // largest padded grid extent over the maps (tiles)
   int32_t* envpos;              // [N] position of each env in the render order (k_env_sort)
-  void* dump;                   // RenderDump: masked lanes of the unconditional frame store write here
-  void* pixtab;                 // [H*W] PixTab (16 B), then [H*W] SampTab (32 B) (render.hip): per-pixel tables of the shared camera
-  void* envv;                   // [N + 1] EnvV (render.hip): k_raster_v3's per-env constants in render order
-  void* envd;                   // [N] EnvD (render_v3dr.inc, 320 B, render order): k_raster_v3dr's per-env constants (domain randomisation)
+  RenderDump* dump;             // masked lanes of the unconditional frame store write here
+  PixTab* pixtab;               // [H*W] PixTab (16 B), then [H*W] SampTab (32 B): per-pixel tables of the shared camera (k_pix_setup)
+  EnvV* envv;                   // [N + 1] EnvV: k_raster_v3's per-env constants in render order
+  EnvD* envd;                   // [N] EnvD (320 B, render order): k_raster_v3dr's per-env constants (domain randomisation)
   int32_t q3_rows;              // k_raster_v3 / k_raster_v3dr: rows of their LDS tile table (largest padded grid height); 0: they cannot run (dt_raster_pipe)
   int32_t light;                // DTSIM_F_LIGHT_CAPTURE with the shared camera: every env lit by its own eye-space light (k_cam_setup, the LIGHT kernels)
 };
@@ -142,14 +143,14 @@ struct RenderParams {
 #define DT_WORK_OBJ_BACK 6       //   its other items, from the back of items2
 #define DT_WORK_LIVE 7           //   envs of a masked pass (k_env_sort_masked), read by the SUB rasters
 #define DT_WORK_TICKETS 32       //   k_raster_v3's ticket counters (raster_map.h): XCD x's at DT_WORK_TICKETS + 32 * x, 128 bytes apart and from the slots above
-// RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane)
-struct RenderDump { uint8_t store[64 * 16]; };
 // The render scratch (render.hip dt_render_layout): the allocations RenderParams points into, each a run of arrays -- ENV: per env EnvCam, EnvFast,
 // EnvQ, envpos, EnvV [N + 1], EnvD, EnvL [N + 1]; PIX: PixTab, SampTab, RenderDump; QCOUNT: qcount, work; ITEMS: items, items2; STRIS: stris, tribox.
 enum RenderSlab { DT_SLAB_ENV, DT_SLAB_PIX, DT_SLAB_QUEUE, DT_SLAB_QCOUNT, DT_SLAB_ITEMS, DT_SLAB_QEND, DT_SLAB_STRIS, DT_SLAB_OBJBOX, DT_SLAB_OBJMASK, DT_SLABS };
 // With bytes: bytes[s] = the size of slab s for N envs, W x H frames and max_tris triangle slots per env (0: no such slab).  With R: points
 // R's scratch fields (envcam .. objmask; the object arrays only with max_tris > 0) into base[DT_SLABS] (null bases: null arrays).
-void dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base = nullptr, RenderParams* R = nullptr);
+// Returns the typed records of the ENV and PIX slabs: the arrays the launchers of a pass reach beside RenderParams (the handle keeps them).
+struct EnvRecs { EnvCam* cams; EnvFast* fasts; EnvQ* envq; EnvV* envv; EnvD* envd; EnvL* envl; PixTab* pixtab; SampTab* samptab; };
+EnvRecs dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base = nullptr, RenderParams* R = nullptr);
 // The raster of a pass (DTSIM_PIPE_*) from R, the largest padded tile grid of the maps (grid_rows x grid_cols, DT_QRING ring included) and
 // DTSIM_RASTER_OLD (raster_old: k_raster_q / the generic raster instead of k_raster_v3 / k_raster_v3dr); sets R.q3_rows.
 int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_old);
@@ -158,7 +159,12 @@ int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_ol
 // plus bit 2 when the pass ran in k_env_sort's render order (RenderParams.envpos holds it: DTSIM_FIELD_RENDER_POS).
 // mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
 // only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, int pipe, int tables, const uint8_t* mask = nullptr);
+// x: dt_render_layout's records of R's slabs.
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, const EnvRecs& x, int pipe, int tables, const uint8_t* mask = nullptr);
+// The rasters of render_v3.hip, called by dt_launch_render after its setup kernels; sub: the masked pass (the SUB instantiations over positions
+// [0, live)).  k_raster_v3 (DTSIM_PIPE_V3) resolves its plane-edge pixels inside; k_raster_v3dr (DTSIM_PIPE_V3DR) is followed by k_resolve_dr.
+void dt_launch_raster_v3(hipStream_t s, const RenderParams& R, const EnvRecs& x, bool sub);
+void dt_launch_raster_v3dr(hipStream_t s, const RenderParams& R, const EnvRecs& x, bool sub);
 // GL_LINE overlays (draw_curve / draw_bbox; render_views.hip k_overlay_lines) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);

@@ -1,6 +1,6 @@
 // raster_map.h -- the XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr): the launch size, the list
 // of (frame tile, env chunk) items each XCD is given, and the split of a list into a static prefix and a ticketed suffix (k_raster_v3 only:
-// raster_wg / raster_claim in render.hip).  Plain C++ without a HIP header: under hipcc every function is __host__ __device__, and a host
+// raster_wg / raster_claim in raster_common.h).  Plain C++ without a HIP header: under hipcc every function is __host__ __device__, and a host
 // compiler sees ordinary inline functions, so a host program can include it (tests/test_raster_map_host.py enumerates the lists and plays
 // the claim protocol with g++).
 //

@@ -32,8 +32,8 @@
 //                 and writes, per (env, block), the mask of the objects whose box meets the block.
 //   k_raster_q<OBJ,S256> (shared camera, square power-of-two tile textures): quad-record one-ray path +
 //                 the exact path of plane-edge pixels inside the same wavefronts (resolve_region_q).
-//   k_raster_v3<OBJ> (render_v3.inc; 256 x 256 tile textures, the BASELINE configurations): k_raster_q on an instruction diet -- the
-//                 headline kernel; k_raster_v3dr<OBJ> (render_v3dr.inc): domain randomisation on the same records (per-env homography).
+//   k_raster_v3<OBJ> (render_v3.hip; 256 x 256 tile textures, the BASELINE configurations): k_raster_q on an instruction diet -- the
+//                 headline kernel; k_raster_v3dr<OBJ> (render_v3.hip too): domain randomisation on the same records (per-env homography).
 //   k_env_sort:   render order of the envs for the quad-record paths (tile under the camera, heading quadrant): an XCD's L2 serves one
 //                 region of the map; DTSIM_FIELD_RENDER_POS reads the order back.
 //   k_resolve:    exact 4-sample resolve of the plane-edge pixels the generic k_raster / k_raster_v3dr queued (front of the queue
@@ -45,13 +45,14 @@
 //                 1/depth space, then the same shading.
 //   Segmentation render (dtsim_render_ex): same kernels on the segmented texel pool, k_cam_setup forces the unlit
 //                 state and the magenta clear / ground colour, k_obj_setup folds the mesh's flat colour into Kd.
-//   Scaffolding shared by the rasters (ahead of k_raster): the XCD-affine workgroup map (raster_map.h; raster_wg and k_raster_v3's raster_claim_* here), the v3 LDS
+//   Scaffolding shared by the rasters (raster_common.h, which holds what this unit and render_v3.hip both use): the XCD-affine workgroup map (raster_map.h; raster_wg and k_raster_v3's raster_claim_* here), the v3 LDS
 //                 tile table fill, the chunk's object masks, the packed source-pixel centres (spxy).
-//   Scaffolding shared by the exact paths (same place): the owner tile and ground-quad hit of an MSAA sample (v3_sample_owner, ground_quad_*), the work-list
+//   Scaffolding shared by the exact paths (raster_common.h too): the owner tile and ground-quad hit of an MSAA sample (v3_sample_owner, ground_quad_*), the work-list
 //                 grabs (work_n_grabs / work_next_grab over the DT_WORK_* slots of dtsim_dev.h), the tile-record LDS fill; elsewhere the ground quad's
 //                 shading rule (ground_corner_ndl / ground_lit, at ground_ndl), the queue-entry decoders (qe_*) and the 3-byte pixel patch (store_rgb).
 //   Host side: dt_render_layout lays out the render scratch (per-env records, per-pixel tables, queues, work lists); dt_raster_pipe picks the raster.
-//   Elsewhere: render_scene.h -- EnvCam, the planes and classify(), test_tri, the MSAA sample positions (MSAA_POS) and the source-pixel centre (src_px) --
+//   Elsewhere: render_records.h -- every record one stage writes and another reads (EnvCam, EnvFast, EnvQ, EnvV, EnvL, EnvD, PixTab, SampTab), typed;
+//                 render_scene.h -- the planes and classify(), test_tri, the MSAA sample positions (MSAA_POS) and the source-pixel centre (src_px) --
 //                 is shared with render_views.hip, which holds every kernel that reads what this pass leaves behind (overlay lines and LEDs, depth,
 //                 labels / instances, bird's-eye map, ground projection) and uses none of the machinery above.
 //
@@ -61,38 +62,8 @@
 // pixel (round 1: 64.8; round 5: 36.9), 12 lines per record gather, vector ALUs 82 % and texture unit 73 % busy -- at 31.5 - 32.3 % of the HBM roofline; float32 geometry, byte-weight
 // filter at the precision GL's own GL_LINEAR has on the reference's renderer, uint8 output.
 // Parity: every pipeline is held to frames the unmodified reference rendered on Mesa llvmpipe (tests/test_gpu_gl_golden.py).
-#include "dtsim_dev.h"
-#include "raster_map.h"
-#include "render_scene.h"
-#include <hip/hip_fp16.h>
-#include <type_traits>
-#include <algorithm>
-#include <map>
-#include <mutex>
-#include <tuple>
+#include "raster_common.h"
 
-// Buffer stores through a raw descriptor (k_raster_v3 / k_raster_v3dr frame rows): clang has no builtin with a scalar-base form, the LLVM
-// intrinsics are reached by name (their immediates must be literals after inlining).
-typedef int v3_i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t v3_u32x3 __attribute__((ext_vector_type(3)));
-__device__ void v3_buf_store_v3i32(v3_u32x3 data, v3_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v3i32");
-typedef uint32_t v3_u32x4 __attribute__((ext_vector_type(4)));
-__device__ void v3_buf_store_v4i32(v3_u32x4 data, v3_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-#define V3_RSRC_W3 0x00027000      // raw buffer descriptor word 3
-__device__ inline v3_i32x4 v3_rsrc(const void* p, uint32_t bytes) {
-  v3_i32x4 r;
-  r.x = (int)(uint32_t)reinterpret_cast<uintptr_t>(p); r.y = (int)((reinterpret_cast<uintptr_t>(p) >> 32) & 0xFFFFu); r.z = (int)bytes; r.w = V3_RSRC_W3;
-  return r;
-}
-
-#define RB 256            // threads per workgroup (4 wavefronts)
-#define PPT DT_PPT         // pixels per thread
-#define WAVE_W DT_WAVE_W  // pixel columns per wavefront block (dtsim_dev.h)
-// pixel slot k of lane l is pixel number k*64 + l of the block, row-major: adjacent lanes = adjacent pixels
-#define SLOT_X(k, l) (((k) * 64 + (l)) % WAVE_W)
-#define SLOT_Y(k, l) (((k) * 64 + (l)) / WAVE_W)
-#define WAVE_PIX (64 * PPT)
-#define ENVS_PER_BLOCK DT_ENVS_PER_BLOCK
 #ifndef DT_TRI_CAP
 #define DT_TRI_CAP 96              // round 3: 128 -> 96 (with 256 pair slots: 40 KB of LDS per workgroup, 4 workgroups per CU; block M)
 #endif
@@ -101,55 +72,51 @@ __device__ inline v3_i32x4 v3_rsrc(const void* p, uint32_t bytes) {
 #endif
 #define TRI_CAP DT_TRI_CAP  // LDS triangle slots per wavefront in k_resolve_obj (streamed chunks)
 
-// Everything the fast path needs per env, fully precomputed by k_cam_setup so that the env loop of
-// k_raster does no wave-uniform arithmetic on the vector ALU (there is no scalar float ALU on gfx950):
-// one 64-byte scalar load per env.
-struct alignas(16) EnvFast {
-  float A, B, Cxi, Czi;        // yaw rotation straight into tile units: gx = Cxi + lr*A + lf*B, gz = Czi + lr*B - lf*A
-  float kg, Cx, Cz, its;       // ground-plane scale (Cy+0.008)/Cy, camera centre, 1/tile_size
-  float ts, gw_m, gh_m, I0;    // tile size, grid extent in metres, shared-camera light base (unused with DR)
-  uint32_t hor_rgb;            // packed horizon colour
-  int32_t gw, gh, tile_off;    // grid size, first tile record of the env's map
-};
-static_assert(sizeof(EnvFast) == 64, "EnvFast is 64 bytes");
-
-// Per-env constants of the quad-layout fast path (k_raster_q): the tile-plane hit (lr, lf) of a pixel in the yaw-local
-// frame goes straight to padded quad coordinates  X = Cx + lr*A + lf*B,  Z = Cz + lr*B - lf*A  (tile units x S, +0.5
-// for the GL_LINEAR half-texel shift, + DT_QRING tiles of off-grid ring).  One 64-byte scalar load per env.
-struct alignas(16) EnvQ {
-  float A, B, Cx, Cz;
-  float Xhi, Zhi;              // clamp range [S/2, hi]: centres of the outermost ring cells
-  uint32_t tab_b, pitch4;      // the map's padded tile table inside the LDS copy (byte offset), row pitch in bytes (8-byte entries)
-  uint32_t hor_rgb;            // packed horizon colour
-  uint32_t sky[3];             // the horizon colour as the three dwords of four consecutive pixels (RGBR GBRG BRGB)
-  uint32_t reach;              // cells from the camera to the border of the padded grid: hits closer than that need no clamp
-  uint32_t env;                // the env (frame index) at this position of the render order (k_env_sort)
-  uint32_t pad[2];             // [0]: k_raster_v3's LDS column offset of the map, [1]: quad cells per metre (float bits)
-};
-static_assert(sizeof(EnvQ) == 64, "EnvQ is 64 bytes");
-// k_raster_v3's per-env constants, in render order: the transform as PAIRS (the scalar operand of a v_pk_fma_f32 is two
-// consecutive scalar registers: loaded as pairs they need no s_mov), everything its env loop reads in one 64-byte scalar
-// load.  [N + 1] entries: the loop prefetches one past its chunk.
-struct alignas(16) EnvV {
-  float A2[2], B2[2], Cx2[2], Cz2[2];
-  float Xhi, Zhi;
-  uint32_t tab3, hor_rgb, reach, env, pad[2];
-};
-static_assert(sizeof(EnvV) == 64, "EnvV is 64 bytes");
-// Per-env light of the shared camera (DTSIM_F_LIGHT_CAPTURE without DTSIM_F_DOMAIN_RAND), in render order, [N + 1] entries: the env's
-// eye-space light rotated into the yaw-local frame (right, up, forward) of the shared camera, where the pixel-centre hit on the tile plane is
-// (lr, -Cy, lf) and the plane normal (0, 1, 0).  lit / 256 = min(base / 256 + kd8 * rsq((Lr - lr)^2 + (Lf - lf)^2 + h2), 1 / 256)  (env_lit8):
-//   position:  Lr, Lf as rotated, h2 = h^2 with h = Lu + Cy (= N.(L - P), the same for every pixel), kd8 = dif * max(h, 0) / 256 (a light
-//              at or below the plane: h2 = 1, kd8 = 0 -- unlit, and no 0 * inf where a pixel lies under it);
-//   direction: Lr = Lf = 0, h2 = 2^120 -- the pixel's own terms vanish beside it, so the root is 2^-60 for every pixel (a wave-uniform
-//              constant) -- and kd8 = dif * max(N.L, 0) * 2^60 / 256.
-struct alignas(16) EnvL { float Lr, Lf, h2, kd8; };
-static_assert(sizeof(EnvL) == 16, "EnvL is 16 bytes");
-
 namespace {
 
-struct EnvD;                                          // render_v3dr.inc: per-env constants of k_raster_v3dr
-__device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const EnvQ& q, const RenderMapDev& m, float q_cells, int H, int W);
+// EnvD (render_records.h) of one env from its EnvCam and EnvQ: the per-env homography and the one-ray bounds of k_raster_v3dr (derived in
+// render_v3.hip, at the kernel), and the same env packed for k_resolve_dr's gathers.  Here, ahead of k_cam_setup, its writer.
+__device__ inline void fill_envd(EnvD& D, const EnvCam& c, const EnvQ& q, const RenderMapDev& m, float q_cells, int H, int W) {
+  const float S = q_cells;                           // cells per tile (256)
+  const float a1 = c.ty * c.cth, a2 = c.ty * c.sth;
+  const float ey = (0.375f * 2.f / (float)H * 1.01f) * c.ty, cex = (0.375f * 2.f / (float)W * 1.01f) * c.tx;
+  const float dy = ey * fabsf(c.cth), eys = ey * fabsf(c.sth);
+  const float qpm = m.inv_tile_size * S;
+  EnvDG& g = D.g; EnvDR& d = D.r;
+  g.hx0 = c.Cy * c.tx * q.A; g.hx1 = c.Cy * a2 * q.B; g.hx2 = c.Cy * c.cth * q.B;
+  g.hz0 = c.Cy * c.tx * q.B; g.hz1 = -c.Cy * a2 * q.A; g.hz2 = -c.Cy * c.cth * q.A;
+  g.Cx = q.Cx; g.Cz = q.Cz;
+  g.na1 = -a1; g.sth = c.sth;
+  g.Xhi = q.Xhi; g.Zhi = q.Zhi; g.tab3 = q.tab3; g.env = q.env; g.pad[0] = g.pad[1] = 0u;
+  d.dy = dy; d.a2 = a2; d.cth = c.cth; d.cE = cex + eys; d.Kr = 1.05f * c.Cy * qpm;
+  d.tx = c.tx; d.ndy = -dy;
+  const float kgc = (c.Cy - GROUND_Y) / c.Cy;
+  // one-ray range of inv = 1 / den (t = Cy inv, rho = dy inv): rho <= 1/4, tg (1 + 2 rho) <= 0.98 far (with rho <= 1/4:
+  // 1.5 tg), t (1 - 2 rho) >= 1.02 near (with rho <= 1/4: t / 2) -- pix_inv_dr's PF_ALWAYS_EDGE / PF_TILE_OK / PF_GROUND_OK,
+  // conservatively
+  d.inv_lo = 2.04f * NEAR_Z / c.Cy;
+  d.inv_hi = fminf(0.25f / dy, 0.98f * FAR_Z / (1.5f * kgc * c.Cy));
+  const float ndl = fmaxf(c.cth * c.L[1] + c.sth * c.L[2], 0.f);   // directional light on the tile plane (eye-space normal (0, cth, sth))
+  if (c.L[3] != 0.f) d.inv_hi = -1.f;                // positional light: per-pixel light term -> everything to the exact path
+  for (int k = 0; k < 3; ++k) d.kc[k] = fminf(c.base[k] + c.dif[k] * ndl, 1.f) * (1.f / 256.f);
+  d.hor_rgb = q.hor_rgb;
+  d.kg = kgc; d.gx1 = (float)m.grid_w * S; d.gz1 = (float)m.grid_h * S; d.qpm = qpm;
+  for (int k = 0; k < 3; ++k) d.kcc[k] = -8388608.f * d.kc[k];
+  EnvDX& x = D.x;
+  x.hx0 = g.hx0; x.hx1 = g.hx1; x.hx2 = g.hx2; x.hz0 = g.hz0; x.hz1 = g.hz1; x.hz2 = g.hz2; x.Cx = q.Cx; x.Cz = q.Cz;
+  x.na1 = -a1; x.sth = c.sth; x.Xhi = q.Xhi; x.Zhi = q.Zhi; x.tab3 = g.tab3; x.env = g.env; x.kg = kgc; x.qpm = qpm;
+  x.Cy = c.Cy; x.positional = c.L[3] != 0.f ? -1.f : 1.f;
+  for (int k = 0; k < 3; ++k) { x.kc[k] = d.kc[k]; x.hor[k] = c.hor[k]; x.gnd[k] = c.gnd[k]; x.base[k] = c.base[k]; }
+  x.gndl0 = c.gndl[0]; x.gndl1 = c.gndl[1]; x.gndl2 = c.gndl[2]; x.gndl3 = c.gndl[3]; x.dif0 = c.dif[0]; x.dif1 = c.dif[1]; x.dif2 = c.dif[2];
+  x.pad0 = x.pad1 = x.pad2 = 0.f;
+  for (int k = 0; k < 16; ++k) D.pad_[k] = 0;
+}
+
+__device__ inline void fill_envd_at(EnvD* arr, int idx, const EnvCam& c, const EnvQ& q, const RenderMapDev& m, float q_cells, int H, int W) {
+  EnvD d;
+  fill_envd(d, c, q, m, q_cells, H, W);
+  arr[idx] = d;
+}
 
 // Render order of the envs for the quad-layout path: envs standing on the same tile (and facing the same way) are
 // made neighbours, so that the 64 envs a raster workgroup loops over -- and, with the XCD-affine workgroup map of
@@ -308,12 +275,11 @@ __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float asp
   c.pad[0] = c.pad[1] = 0.f;
   out[e] = c;
   const RenderMapDev m = maps[c.map_id];
-  EnvFast f;
+  EnvFast f{};                                       // (the pad is written as zero: the scratch bytes stay deterministic)
   f.its = m.inv_tile_size; f.ts = m.tile_size;
   f.A = c.sa * f.its; f.B = c.ca * f.its; f.Cxi = c.Cx * f.its; f.Czi = c.Cz * f.its;
   f.kg = (c.Cy - GROUND_Y) / c.Cy; f.Cx = c.Cx; f.Cz = c.Cz;
   f.gw_m = (float)m.grid_w * m.tile_size; f.gh_m = (float)m.grid_h * m.tile_size;
-  f.I0 = 0.f;
   {
     const uint32_t r = (uint32_t)(fminf(fmaxf(c.hor[0], 0.f), 255.f) + 0.5f), g = (uint32_t)(fminf(fmaxf(c.hor[1], 0.f), 255.f) + 0.5f);
     const uint32_t b = (uint32_t)(fminf(fmaxf(c.hor[2], 0.f), 255.f) + 0.5f);
@@ -338,13 +304,13 @@ __global__ void k_cam_setup(SimArrays A, int domain_rand, int segment, float asp
       const float r = fminf(fminf(q.Cx, xmax - q.Cx), fminf(q.Cz, zmax - q.Cz)) - 2.f;
       q.reach = r > 0.f ? (uint32_t)fminf(r, 1.0e9f) : 0u;      // NaN / outside the padded grid -> 0: always clamp
     }
-    q.env = (uint32_t)e; q.pad[1] = __float_as_uint(m.inv_tile_size * S);   // quad cells per metre of the env's map (the exact path's ground-quad test)
-    q.pad[0] = (uint32_t)c.map_id * (32u * 4u);     // k_raster_v3: byte offset of the map's columns inside an LDS table row (V3_MAP_COLS entries)
+    q.env = (uint32_t)e; q.qpm_bits = __float_as_uint(m.inv_tile_size * S);   // quad cells per metre of the env's map (the exact path's ground-quad test)
+    q.tab3 = (uint32_t)c.map_id * (V3_MAP_COLS * 4);     // k_raster_v3: byte offset of the map's columns inside an LDS table row (V3_MAP_COLS entries)
     envq[pos ? pos[e] : e] = q;
     if (envv) {
       EnvV v;
       v.A2[0] = v.A2[1] = q.A; v.B2[0] = v.B2[1] = q.B; v.Cx2[0] = v.Cx2[1] = q.Cx; v.Cz2[0] = v.Cz2[1] = q.Cz;
-      v.Xhi = q.Xhi; v.Zhi = q.Zhi; v.tab3 = q.pad[0]; v.hor_rgb = q.hor_rgb; v.reach = q.reach; v.env = q.env; v.pad[0] = v.pad[1] = 0u;
+      v.Xhi = q.Xhi; v.Zhi = q.Zhi; v.tab3 = q.tab3; v.hor_rgb = q.hor_rgb; v.reach = q.reach; v.env = q.env; v.pad[0] = v.pad[1] = 0u;
       envv[pos ? pos[e] : e] = v;
       if (e == A.N - 1) envv[A.N] = v;               // the entry past the end (prefetched, never used)
     }
@@ -450,19 +416,6 @@ __device__ inline void mesh_texel(const RenderParams& R, int tex, float u, float
   gl_linear_rgb(pt[0], pt[1], pt[td.w + 1], pt[td.w + 2], xf & 255, yf & 255, T);
 #pragma unroll
   for (int k = 0; k < 3; ++k) out[k] = (float)T[k] * (1.f / 255.f);
-}
-
-// ---- ground quad (simulator.py:1806-1812): N.L is lit at the four corners (EnvCam.gndl) and interpolated bilinearly at (a, b) in [0, 1]^2; a channel is
-// gnd * min(base + dif * N.L, 1) -- ground_lit, and still written out in shade, shade_msaa and the env loops of k_raster, k_raster_q and k_raster_v3dr.
-__device__ inline float ground_corner_ndl(const float a, const float b, const float g0, const float g1, const float g2, const float g3) {
-  const float n0 = g0 + a * (g1 - g0), n1 = g2 + a * (g3 - g2);
-  return n0 + b * (n1 - n0);
-}
-__device__ inline float ground_lit(const float gnd, const float base, const float dif, const float ndl) { return gnd * fminf(base + dif * ndl, 1.f); }
-__device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {      // at a world position
-  const float a = fminf(fmaxf((wx + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
-  const float b = fminf(fmaxf((wz + GROUND_HALF) * (0.5f / GROUND_HALF), 0.f), 1.f);
-  return ground_corner_ndl(a, b, c.gndl[0], c.gndl[1], c.gndl[2], c.gndl[3]);
 }
 
 #ifndef DT_OBJSETUP_T
@@ -650,22 +603,6 @@ __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, Render
       R.objmask[(size_t)(pos ? pos[e] : e) * n_blk + b] = mk;   // indexed by position in the render order
     }
   }
-}
-
-// max(|a|, |b|) in one instruction (source modifiers; no NaN canonicalisation needed: inputs are finite)
-__device__ inline float absmax(float a, float b) { float r; asm("v_max_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// floor(x) as int in one instruction
-__device__ inline int flr_i32(float x) { int r; asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x)); return r; }
-// v_cvt_f32_ubyteN: one instruction per texel channel (the compiler does not pick it)
-__device__ inline float ubyte0(uint32_t x) { float r; asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(x)); return r; }
-__device__ inline float ubyte1(uint32_t x) { float r; asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(r) : "v"(x)); return r; }
-__device__ inline float ubyte2(uint32_t x) { float r; asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(r) : "v"(x)); return r; }
-
-__device__ inline uint32_t pack_rgb(const float col[3]) {  // glReadPixels float -> unorm8: round(255 c)
-  const uint32_t r = (uint32_t)(fminf(fmaxf(col[0], 0.f), 255.f) + 0.5f);
-  const uint32_t g = (uint32_t)(fminf(fmaxf(col[1], 0.f), 255.f) + 0.5f);
-  const uint32_t b = (uint32_t)(fminf(fmaxf(col[2], 0.f), 255.f) + 0.5f);
-  return r | (g << 8) | (b << 16);
 }
 
 // ---- generic (exact) per-sample path, used for edge pixels ---------------------------
@@ -1010,253 +947,6 @@ __device__ inline PixInv pix_inv_dr(float nx, float ny, bool valid, const DrCam&
   return p;
 }
 
-// Edge-pixel queue: one fixed region per (workgroup, wavefront) of the raster launch, worst-case
-// sized (every pixel of every env of the chunk), so appends need no atomics; entry =
-// (env-in-chunk << 8) | (row-slot k << 6 | lane).  k_resolve drains the regions 64 entries at a time.
-#define QREGION (WAVE_PIX * ENVS_PER_BLOCK)
-// Queue entry: pixel of the wavefront block (bits 0..7) | env position in the chunk << 8 (bits 8..13).  Object-box entries
-// (far end of the region, k_resolve_obj's) carry bit 15 when the pixel is ALSO a plane edge, i.e. when what the raster
-// stored for it is not final: k_resolve_obj leaves a pixel alone when no mesh triangle covers any of its samples and the
-// bit is clear (the raster's one-ray colour is the pixel).  The quad-record rasters tell; the generic raster always sets it (its filter is the exact path's).
-#define QE_PLANE_EDGE 0x8000u
-__device__ inline int qe_pixel(const uint32_t ent) { return (int)(ent & 255u); }            // row-major pixel number in the wavefront block
-__device__ inline int qe_envpos(const uint32_t ent) { return (int)((ent >> 8) & 63u); }     // env position in the chunk (k_resolve reads ent >> 8: front entries carry no flags, the mask costs it 13 instructions)
-__device__ inline bool qe_plane_edge(const uint32_t ent) { return (ent & QE_PLANE_EDGE) != 0u; }
-static_assert(ENVS_PER_BLOCK <= 64, "the env position of a queue entry has six bits");
-#define ITEM_B DT_ITEM_B   // 64-entry batches per k_resolve work item
-#define ITEMS_PER_WG DT_ITEMS_PER_WG
-#define GRAB_MAX 16       // work items per cursor atomic, at most
-#ifndef DT_RES_ENVS
-#define DT_RES_ENVS 1             // round 4: 8 -> 1 (one env per item: the launch ended on its longest octet; C5 - 8 %, profiles/r04_wave_spans.txt)
-#endif
-#define RES_ENVS DT_RES_ENVS  // env positions of a chunk per k_resolve_obj work item
-static_assert(ENVS_PER_BLOCK % RES_ENVS == 0 && ENVS_PER_BLOCK / RES_ENVS <= ITEMS_PER_WG, "octet items");
-
-// The live count of a masked pass (positions [0, live) of the render order), written by k_env_sort<true> after the pass's work-list clear.
-__device__ inline int dt_sub_live(const RenderParams& R) { return __builtin_amdgcn_readfirstlane(R.work[DT_WORK_LIVE]); }
-// Work items of k_resolve_obj (its own list: the DT_WORK_OBJ_* slots of R.work; R.items2): one per RES_ENVS
-// env positions of a raster workgroup that queued object-box pixels.
-// groups: bit g = env group g of the chunk (RES_ENVS positions) has object-box entries in some region of the workgroup; the
-// quad-record rasters pass what they queued (round 4: 60 % of the items used to be empty), the others every group.
-// Round 4: the list has two ends.  Items of env groups that queued a lot (heavy: bit g, a subset of groups) go to the front in push
-// order, the others to the back (from the last slot down); k_resolve_obj walks front to back, so the units of close-up objects -- up to
-// 1 024 pixels against every triangle of the object, 100 - 250 us of one wavefront -- start first instead of wherever their raster
-// workgroup happened to finish (the launch used to end on a third of the wavefronts, profiles/r04_wave_spans.txt).
-// DT_WORK_OBJ_FRONT / DT_WORK_OBJ_BACK count the two ends, DT_WORK_OBJ_CURSOR is the cursor; capacity = one slot per (raster workgroup, env group).
-__device__ inline size_t obj_items_cap(const RenderParams& R) {
-  const int n_tiles = ((R.W + DT_TILE_W - 1) / DT_TILE_W) * ((R.H + DT_TILE_H - 1) / DT_TILE_H);
-  return (size_t)((R.N + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK) * n_tiles * (ENVS_PER_BLOCK / RES_ENVS);
-}
-typedef unsigned long long envmask_t;                 // one bit per env group of a chunk (ENVS_PER_BLOCK / RES_ENVS <= 64)
-__device__ inline void push_obj_items(const RenderParams& R, uint32_t rwg, envmask_t groups = ~0ull, envmask_t heavy = 0ull) {
-  const int ng = ENVS_PER_BLOCK / RES_ENVS;
-  if (ng < 64) groups &= (1ull << ng) - 1ull;
-  heavy &= groups;
-  const envmask_t light = groups & ~heavy;
-  const int nh = __popcll(heavy), nl = __popcll(light);
-  if (nh) {
-    int pos = atomicAdd(R.work + DT_WORK_OBJ_FRONT, nh);
-    for (int i = 0; i < ng; ++i) if ((heavy >> i) & 1ull) R.items2[pos++] = rwg * ITEMS_PER_WG + (uint32_t)i;
-  }
-  if (nl) {
-    size_t pos = obj_items_cap(R) - 1 - (size_t)atomicAdd(R.work + DT_WORK_OBJ_BACK, nl);
-    for (int i = 0; i < ng; ++i) if ((light >> i) & 1ull) R.items2[pos--] = rwg * ITEMS_PER_WG + (uint32_t)i;
-  }
-}
-#ifndef DT_RO_HEAVY
-#define DT_RO_HEAVY 128            // entries of one env in one 256-pixel wavefront region from which its unit counts as heavy
-#endif
-// which env groups of the chunk have entries in THIS wavefront's region: qend_v = the region's fill after each env (lane = position)
-__device__ inline envmask_t obj_groups_of(int qend_v, int lane, envmask_t* heavy = nullptr) {
-  static_assert(ENVS_PER_BLOCK / RES_ENVS <= 64, "one bit per env group");
-  const int up = __shfl_up(qend_v, 1);
-  const int cnt = lane < ENVS_PER_BLOCK ? qend_v - (lane == 0 ? 0 : up) : 0;
-  const unsigned long long m = __ballot(cnt != 0), mh = __ballot(cnt >= DT_RO_HEAVY);
-  envmask_t g = 0ull, gh = 0ull;
-#pragma unroll
-  for (int i = 0; i < ENVS_PER_BLOCK / RES_ENVS; ++i) {
-    g |= ((m >> (i * RES_ENVS)) & ((1ull << RES_ENVS) - 1ull)) ? (1ull << i) : 0ull;
-    gh |= ((mh >> (i * RES_ENVS)) & ((1ull << RES_ENVS) - 1ull)) ? (1ull << i) : 0ull;
-  }
-  if (heavy) *heavy = gh;
-  return g;
-}
-
-// ==== scaffolding shared by the rasters ===================================================================================================
-// What every raster must agree on with the host and the exact-path kernels, stated once: the workgroup map and its launch size, the v3 LDS
-// tile table, the chunk's object masks and the packed source-pixel centres; further down the exact paths' rules (below; ground_lit at ground_ndl,
-// qe_* at the entry layout, store_rgb at resolve_region_q).  A helper stays only where the compiled kernel is unchanged (tools/isa_compare.py,
-// profiles/exact_path_identity.txt).  Still written out per kernel, because as helpers they changed the generated code: the queue appends, push_obj,
-// the transposes and the hand-over epilogues (the env loops); the item -> workgroup / part / tile / chunk decode and the four regions' batch lookup of
-// k_resolve / k_resolve_dr / k_resolve_obj (a struct, a struct with lazy members, free functions over rn[] / rb[]: 35 - 65 instructions more); k_raster's
-// tile-record fill; ground_lit in k_raster_v3dr's env loop; k_resolve's unmasked env position.  What a kernel does differently is an argument at its call site.
-
-// ---- XCD-affine workgroup map of the quad-record rasters (k_raster_q, k_raster_v3, k_raster_v3dr): raster_map.h states the lists, the launch
-// size and the prefix / suffix split; here is what a workgroup does with them.
-// NL: envs of the pass; live: false for a workgroup of the grid's padding (the whole workgroup leaves, before anything else is derived);
-// rwg: the logical workgroup index (queue regions, counts, work items) -- of the ITEM, whichever workgroup runs it; [e0, e1): the chunk's
-// positions in the render order.  claims (TICKET only): the workgroup draws its item (raster_claim_*) instead of decoding it; thief: its slot
-// lies past the lists.
-struct RasterWg {
-  int NL, tile, chunk; bool live, claims, thief;
-  __device__ int rwg(const int n_tiles) const { return chunk * n_tiles + tile; }
-  __device__ int e0() const { return chunk * ENVS_PER_BLOCK; }
-  __device__ int e1() const { return min(e0() + ENVS_PER_BLOCK, NL); }
-};
-// SUB: the masked pass -- positions [0, live) of k_env_sort<true>'s order, few live chunks: workgroup b takes tile b % n_tiles of chunk
-// b / n_tiles, so that every chunk's tiles spread over all eight XCDs.
-// SCALAR: tile and chunk through readfirstlane -- the divisions run on the vector ALU, and without it the env loop's counter and the per-env
-// address arithmetic of k_raster_v3 / k_raster_v3dr stay vector instructions; k_raster_q was tuned without it and keeps its form.
-// TICKET (k_raster_v3's full pass): the list's last DT_RASTER_TICKET_UNITS units are claimed, not decoded, and the launch carries raster_thieves() more slots
-// per XCD -- with the static map the XCDs ended up to 4 % of the launch apart (sorted render order: the scenes of the slices differ); an XCD whose list is
-// dry now takes what is left of a late one's suffix, and they end within 0.6 % (C3 - 1.5 %, C5 - 1.8 %: profiles/raster_ticket_map.txt).
-template <bool SUB, bool SCALAR, bool TICKET = false>
-__device__ inline RasterWg raster_wg(const RenderParams& R, const int n_tiles, const unsigned bx) {
-  static_assert(!(SUB && TICKET), "the masked pass keeps its linear map");
-  RasterWg w;
-  w.NL = SUB ? dt_sub_live(R) : R.N;                 // (SUB: the live chunks)
-  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-  const int xcd = bx & 7, bi = bx >> 3;
-  const bool thief = TICKET && bi >= raster_list_slots(n_tiles, n_chunks);   // a slot past the lists (raster_ticket_grid): nothing to decode
-  const RasterItem it = raster_item(n_tiles, n_chunks, xcd, thief ? 0 : bi);
-  const int tile = SUB ? (int)bx % n_tiles : it.tile;
-  w.tile = SCALAR ? __builtin_amdgcn_readfirstlane(tile) : tile;
-  const int chunk = SUB ? (int)bx / n_tiles : it.chunk;
-  w.chunk = SCALAR ? __builtin_amdgcn_readfirstlane(chunk) : chunk;
-  w.live = SUB ? w.chunk < n_chunks : (it.live && !thief);
-  w.claims = TICKET && __builtin_amdgcn_readfirstlane((int)(thief || !raster_slot_static(n_tiles, n_chunks, xcd, thief ? 0 : bi, DT_RASTER_TICKET_UNITS))) != 0;
-  w.thief = thief;
-  return w;
-}
-// The claim of a workgroup with w.claims, in two halves so that work which does not depend on the item (the LDS tile table) hides the
-// round trip: raster_claim_issue draws the first ticket (thread 0, the own XCD's counter; a device-scope atomic like the cursors of
-// k_resolve_*; a thief starts when its XCD's own slots have all started and draws none), raster_claim_finish turns it into the item -- with
-// the own list dry it reads the other seven counters at once and draws from those that are not dry, in rotation from xcd + 1 -- and hands the
-// item to the workgroup through LDS (one barrier, claimers only).  At most DT_RASTER_XCDS atomic adds, no waiting on another workgroup.
-static_assert(DT_WORK_TICKETS >= DT_TICKET_STRIDE && DT_WORK_TICKETS + DT_RASTER_XCDS * DT_TICKET_STRIDE <= DT_WORK_INTS, "the ticket counters lie inside R.work (zeroed before every pass)");
-__device__ inline int raster_claim_issue(const RenderParams& R, const unsigned bx, const int tid, const RasterWg& w) {
-  if (w.thief) return 0x7fffffff;
-  return tid == 0 ? atomicAdd(R.work + DT_WORK_TICKETS + (int)(bx & 7) * DT_TICKET_STRIDE, 1) : 0;
-}
-__device__ inline void raster_claim_finish(const RenderParams& R, const int n_tiles, const unsigned bx, const int first, int* s_claim, const int tid, RasterWg& w) {
-  const int n_chunks = (w.NL + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
-  if (tid == 0) {
-    RasterItem it = raster_ticket_item(n_tiles, n_chunks, (int)(bx & 7), first, DT_RASTER_TICKET_UNITS);
-    if (!it.live) {
-      int seen[DT_RASTER_XCDS];
-#pragma unroll
-      for (int a = 1; a < DT_RASTER_XCDS; ++a)
-        seen[a] = __hip_atomic_load(R.work + DT_WORK_TICKETS + raster_claim_xcd((int)(bx & 7), a) * DT_TICKET_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int a = 1; a < DT_RASTER_XCDS; ++a) {
-        const int x = raster_claim_xcd((int)(bx & 7), a);
-        if (it.live || seen[a] >= raster_ticket_len(n_tiles, n_chunks, x, DT_RASTER_TICKET_UNITS)) continue;   // a counter only grows: dry stays dry
-        it = raster_ticket_item(n_tiles, n_chunks, x, atomicAdd(R.work + DT_WORK_TICKETS + x * DT_TICKET_STRIDE, 1), DT_RASTER_TICKET_UNITS);
-      }
-    }
-    s_claim[0] = it.live ? it.tile : -1; s_claim[1] = it.chunk;
-  }
-  __syncthreads();
-  w.tile = __builtin_amdgcn_readfirstlane(s_claim[0]); w.chunk = __builtin_amdgcn_readfirstlane(s_claim[1]);
-  w.live = w.tile >= 0;
-}
-
-// ---- LDS tile table of k_raster_v3 / k_raster_v3dr / k_resolve_dr: the tile tables of all maps in rows of V3_TAB_PITCH entries, block byte
-// offsets in the first half of a row, record-offset masks in the second (defaults of the unused columns: record 0 = off the grid, mask 0).
-// The caller's barrier follows.
-#define V3_TAB_PITCH 256                              // table entries per LDS row: the tile byte of Z selects the row
-#define V3_MAP_COLS 32                                // columns of one map inside a half row (padded grid width <= 32, up to 4 maps)
-__device__ inline void v3_fill_tile_table(const RenderParams& R, const uint32_t* __restrict__ qtiles, uint32_t* s_qt, const int tid) {
-  for (int i = tid; i < R.q3_rows * V3_TAB_PITCH; i += RB) s_qt[i] = 0u;
-  __syncthreads();
-  for (int mi = 0; mi < R.n_maps; ++mi) {
-    const int pitch = R.maps[mi].qt_pitch, off = R.maps[mi].qt_off, n = pitch * (R.maps[mi].grid_h + 2 * DT_QRING);
-    for (int i = tid; i < n; i += RB) {
-      const int r = i / pitch, c = i - r * pitch;
-      const uint2 te = reinterpret_cast<const uint2*>(qtiles)[off + i];
-      s_qt[r * V3_TAB_PITCH + mi * V3_MAP_COLS + c] = te.x;
-      s_qt[r * V3_TAB_PITCH + V3_TAB_PITCH / 2 + mi * V3_MAP_COLS + c] = te.y;
-    }
-  }
-}
-
-// ---- the raster tile records of every map -> LDS (k_resolve, k_resolve_obj: [n_tile_recs] TileLds at the start of the workgroup's
-// dynamic LDS).  The caller's barrier follows.  (k_raster keeps the same loop written out: the call moved an instruction of its prologue.)
-__device__ inline void fill_tile_recs(const RenderParams& R, uint32_t* s_mem, const int tid) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(R.tile_recs);
-  for (int i = tid; i < R.n_tile_recs * (int)(sizeof(TileLds) / 4); i += RB) s_mem[i] = src[i];
-}
-
-// ==== scaffolding shared by the exact paths: what resolve_region_q / _v3, k_resolve, k_resolve_dr and k_resolve_obj must agree on, stated once ====
-// ---- the tile that OWNS an MSAA sample at padded quad coordinates (Xs, Zs), on the v3 LDS tile table (qtb; tab: byte offset of the env's map
-// columns): tile boundaries sit at k * 256 + 0.5 (GL_LINEAR's half-texel shift), so ownership goes by (X - 0.5, Z - 0.5), clamped into the padded
-// grid.  tb: the tile's block byte offset (0: none), sel: its record-offset mask; returns s_in: inside the grid.  (resolve_region_q: tile_entry.)
-__device__ inline float med3f(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
-__device__ inline bool v3_sample_owner(const float Xs, const float Zs, const float lo, const float Xhi, const float Zhi, const char* qtb,
-                                       const uint32_t tab, uint32_t& tb, uint32_t& sel) {
-  const float Xo = Xs - 0.5f, Zo = Zs - 0.5f;
-  const float Xc = med3f(Xo, lo, Xhi), Zc = med3f(Zo, lo, Zhi);
-  const uint32_t ta = (__builtin_amdgcn_perm((uint32_t)flr_i32(Zc), (uint32_t)flr_i32(Xc), 0x0c0c0501u) << 2) + tab;
-  const uint32_t* tp = reinterpret_cast<const uint32_t*>(qtb + ta);
-  tb = tp[0]; sel = tp[V3_TAB_PITCH / 2];
-  return (Xc == Xo) & (Zc == Zo);
-}
-// ---- ground-quad hit in padded quad coordinates, per axis: camera + kg * (tile-plane hit - camera); inside +-50 m (goff: world 0, ghalf: 50 m)
-__device__ inline float ground_quad_at(const float kg, const float X, const float C) { return fmaf(kg, X - C, C); }
-__device__ inline bool ground_quad_in(const float G, const float goff, const float ghalf) { return fabsf(G - goff) <= ghalf; }
-
-// ---- work lists of the persistent kernels (k_resolve, k_resolve_dr, k_resolve_obj).  One atomic buys `grab` items, taken with stride n_grabs through
-// the list: same-address atomics are serialised by the L2 (~0.2 ms per 100 k), and the stride keeps the consecutive items of one hot raster
-// workgroup on different wavefronts.  Granularity: ~4 grabs per resident wavefront, <= GRAB_MAX items.
-__device__ inline int work_n_grabs(const int n_items) {
-  const int grab = max(1, min(GRAB_MAX, n_items / (int)(gridDim.x * (RB / 64) * 4)));
-  return (n_items + grab - 1) / grab;
-}
-// A wavefront's first grab is its own index (round 4: the launch holds exactly the resident workgroups; 5 000 wavefronts starting on one cursor atomic
-// waited 30 - 60 us each, profiles/r04_wave_spans.txt); this is every later one, from the list's cursor slot (g: the previous grab, kept by lanes > 0).
-__device__ inline int work_next_grab(const RenderParams& R, const int cursor, int g, const int lane) {
-  if (lane == 0) g = (int)gridDim.x * (RB / 64) + atomicAdd(R.work + cursor, 1);
-  return __builtin_amdgcn_readfirstlane(g);
-}
-
-// ---- object masks (k_obj_setup: bit o = object o's screen box meets the block) of the chunk's envs for one wavefront block.  One vector
-// load up front: lane l holds the mask of position e0 + l (a scalar load per env would sit in the same counter as the LDS reads of the env
-// loop and stall them: measured +0.4 ms); per env two v_readlane.
-template <bool OBJ>
-struct ChunkObjMasks {
-  static_assert(ENVS_PER_BLOCK <= 64, "one lane per env of the chunk");
-  uint32_t lo, hi;
-  int e0;
-  __device__ void load(const RenderParams& R, const int e0_, const int e1, const int n_blk, const int blk, const int lane) {
-    uint32_t om_lo = 0u, om_hi = 0u;
-    if (OBJ && lane < e1 - e0_) {
-      const unsigned long long v = R.objmask[(size_t)(e0_ + lane) * n_blk + blk];
-      om_lo = (uint32_t)v; om_hi = (uint32_t)(v >> 32);
-    }
-    lo = om_lo; hi = om_hi; e0 = e0_;
-  }
-  __device__ unsigned long long of(const int e) const {
-    if (!OBJ) return 0ull;
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, e - e0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lo, e - e0);
-  }
-};
-
-// ---- spxy: the source-pixel centre of a pixel (from its LUT entry) as two fp16 in one register (x | y << 16): 0.25 px rounding below
-// 1024, which the object-box margin covers.  The unpack sits behind a register barrier: it is redone per env, not hoisted ahead of the env
-// loop (8 registers).
-__device__ inline uint32_t spxy_pack(const float4& l, const int W, const int H) {
-  float sx, sy;
-  src_px(l.x, l.y, W, H, sx, sy);
-  return (uint32_t)__half_as_ushort(__float2half(sx)) | ((uint32_t)__half_as_ushort(__float2half(sy)) << 16);
-}
-__device__ inline void spxy_unpack(uint32_t t, float& sx, float& sy) {
-  asm volatile("" : "+v"(t));
-  sx = __half2float(__ushort_as_half((unsigned short)(t & 0xFFFFu)));
-  sy = __half2float(__ushort_as_half((unsigned short)(t >> 16)));
-}
-
-struct alignas(4) U3 { uint32_t a, b, c; };           // 4 pixels x RGB: a lane's 12 bytes of a frame row
-
 template <bool DR, bool OBJ>
 __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __restrict__ cams,
                                                const EnvFast* __restrict__ fasts, uint8_t* __restrict__ frames, const uint32_t* __restrict__ texels,
@@ -1551,18 +1241,7 @@ __global__ __launch_bounds__(RB) void k_raster(RenderParams R, const EnvCam* __r
   }
 }
 
-// ---- per-pixel tables of the shared camera (env-invariant; built by k_pix_setup) ----------------------------------
-// PixTab: what k_raster_q keeps in registers per pixel.  lit: < 0 source pixel outside the image (BORDER_CONSTANT 0),
-// 0 sky for all four samples, > 0 the lit factor min(base + dif * N.L, 1) of the tile plane at the pixel-centre hit.
-// mi: low 16 bits = MSAA reach in quad cells (0xFFFF: never a one-ray pixel), high 16 = the reach in metres, fp16 rounded up.
-struct alignas(16) PixTab { float lr, lf, lit; uint32_t mi; };
-// SampTab: the four MSAA sample hits on the tile plane in the yaw-local frame (k_resolve_q), as fp16 offsets from the
-// pixel-centre hit (lr, lf) of the PixTab (a sample sits within a pixel footprint of the centre: an fp16 offset
-// places it to 5e-4 of that footprint; for pixels whose centre ray misses the planes the offsets are the hits
-// themselves).  flags: bit s = sample s hits the tile plane within [near, far], bit 4+s = it hits the ground plane
-// within [near, far] (ground hit = kg * tile-plane hit).
-struct alignas(16) SampTab { uint32_t dlr[2], dlf[2]; uint32_t flags; uint32_t pad[3]; };   // pad: lr, lf, lit of the PixTab (float bits)
-static_assert(sizeof(PixTab) == 16 && sizeof(SampTab) == 32, "table records");
+// ---- per-pixel tables of the shared camera (PixTab, SampTab: render_records.h; env-invariant), built here -----------------
 
 __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixTab* __restrict__ pixtab, SampTab* __restrict__ samptab) {
   const int pix = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1604,7 +1283,7 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
     sp.dlr[j] = (uint32_t)__half_as_ushort(__float2half_rn(dlr[2 * j])) | ((uint32_t)__half_as_ushort(__float2half_rn(dlr[2 * j + 1])) << 16);
     sp.dlf[j] = (uint32_t)__half_as_ushort(__float2half_rn(dlf[2 * j])) | ((uint32_t)__half_as_ushort(__float2half_rn(dlf[2 * j + 1])) << 16);
   }
-  sp.pad[0] = __float_as_uint(t.lr); sp.pad[1] = __float_as_uint(t.lf); sp.pad[2] = __float_as_uint(t.lit);   // the PixTab's hit and lit factor once more: phase 2 of the exact path reads ONE table
+  sp.lr_bits = __float_as_uint(t.lr); sp.lf_bits = __float_as_uint(t.lf); sp.lit_bits = __float_as_uint(t.lit);   // the PixTab's hit and lit factor once more: phase 2 of the exact path reads ONE table
   samptab[pix] = sp;
 }
 
@@ -1622,90 +1301,7 @@ __global__ void k_pix_setup(RenderParams R, const float4* __restrict__ lut, PixT
 //      +-50 m; else the clear colour), shading once per distinct primitive at the pixel centre (GL semantics:
 //      simulator.py:1932-1934, graphics.py:172-251): a tile is shaded with ITS texture at the centre hit -- outside the
 //      tile the coordinate wraps (GL_REPEAT), which the quad records encode -- times the centre's lit factor.
-// k_raster_v3 drains its regions with its own exact path, resolve_region_v3 (render_v3.inc): no interior test, no list.
-// ---- the quad-record filter ("dtsim8") -------------------------------------------------------------------
-// GL's own filter (llvmpipe: gl_linear_rgb above) works with 8-bit weights and 8-bit intermediates, so nothing is gained by filtering
-// finer than that; the quad pipeline filters in ONE v_dot4_u32_u8 per channel: the four bilinear weights, times the lit factor
-// where it is the same for the three channels (shared camera), times 256, rounded to bytes (v_cvt_pk_u8_f32); colour =
-// (sum(texel * weight) + 128) >> 8.  Measured against the GL goldens it differs from llvmpipe by +-1/255 on about a quarter of the
-// textured pixels -- what the 16-bit filter it replaces did too (tests/test_gl_golden.py::test_quad_filter_distance_to_gl).
-// The texture coordinate itself is snapped to 256ths of a texel first -- llvmpipe rounds its coordinates to 8 fractional bits before it
-// splits them into texel index and weight (gl_linear_rgb above) -- by ONE float add: X + 32768 (X in quad cells, 0 <= X < 32768; the host
-// checks the padded grid against it) rounds X to a multiple of 1/256 and leaves it in the sum's bit pattern: byte 0 = the fraction in
-// 256ths, bits 8..22 = the cell number (S = 256: byte 1 = the cell inside the tile, byte 2 = the tile).  A fraction that rounds up to 1
-// carries into the cell number, as in GL.  The hot loops take everything from these bits -- no v_cvt_flr, no v_fract.
-#define Q8_SNAP 32768.f
-#define Q8_LIT (1.f / 256.f)                         // the weights' light argument is lit / 256 (the fractions come as 0..255)
-__device__ inline uint32_t q8_bits(float X) { return __float_as_uint(X + Q8_SNAP); }
-__device__ inline uint32_t q8_cell(uint32_t b) { return (b >> 8) & 0x7FFFu; }      // the cell number (one v_bfe_u32)
-__device__ inline float q8_frac(uint32_t b) { return (float)(b & 255u); }          // the fraction x 256 (one v_cvt_f32_ubyte0)
-// Byte offset of the record of the cell of snapped coordinates (xb, zb) inside a 256 x 256 block, masked by the tile's table entry (0 for the
-// one-record blocks): the records lie 4 x 2 cells to a 128-byte line -- offset = (cx >> 2) << 14 | cz << 6 | (cx & 3) << 4 -- because the texture
-// unit charges a gather per distinct line, and the footprint of a 32 x 2 pixel slot is a slanted strip: 12.0 lines per gather instead of 14.0 with
-// the texture's rows laid end to end (tools/gather_lines_model.py; profiles/r06_variants_ab.txt block H).  cx * 0x1010 puts cx at bits 12.. and
-// 4..; cz (byte 1 of zb, shifted to bits 6..13) goes over the middle: 3 instructions + the v_and_or that masks and adds the block's offset.
-__device__ inline uint32_t q8_rec256(uint32_t xb, uint32_t zb, uint32_t m) {
-  uint32_t P, Zs;                                    // (the byte selects written out: the compiler's SDWA peephole finds them for some of the four pixels only)
-  asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(P) : "v"(xb), "s"(0x1010u));
-  asm("v_lshlrev_b32_sdwa %0, 6, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(Zs) : "v"(zb));
-  return ((P & 0xFC030u) | Zs) & m;
-}
-// a8, b8: the fractions x 256 (0..255); l = lit / 256 (1 / 256 for an unlit filter).  Byte order = the record's texel order:
-// (x0,z0) (x1,z0) (x0,z1) (x1,z1).  (The packed forms in the env loops of k_raster_q / k_raster_v3 are these operations, two pixels each.)
-typedef float f2_t __attribute__((ext_vector_type(2)));
-__device__ inline f2_t fma2(f2_t a, f2_t b, f2_t c) { return __builtin_elementwise_fma(a, b, c); }   // one v_pk_fma_f32, whatever the contraction mode
-__device__ inline uint32_t quad_weights8(float a8, float b8, float l) {
-#pragma clang fp contract(off)                       // which products are fused is part of the definition (the oracle restates it): u and the w*1 are rounded products
-  const float u = a8 * l, v = fmaf(l, 256.f, -u);
-  const float w11 = u * b8, w01 = v * b8, w10 = fmaf(u, 256.f, -w11), w00 = fmaf(v, 256.f, -w01);
-  uint32_t W = __builtin_amdgcn_cvt_pk_u8_f32(w00, 0, 0u);
-  W = __builtin_amdgcn_cvt_pk_u8_f32(w10, 1, W);
-  W = __builtin_amdgcn_cvt_pk_u8_f32(w01, 2, W);
-  return __builtin_amdgcn_cvt_pk_u8_f32(w11, 3, W);
-}
-// The tile plane's lit factor / 256 of one pixel (yaw-local centre hit lr, lf) under an env's own light (EnvL): the raster's env loops and the
-// exact paths all go through these operations, so that a one-ray pixel gets the same bytes from either (the packed form in the env loops is
-// these operations, two pixels each).  base8 = the shared ambient term / 256; the clamp at 1 / 256 is exact (a power of two).
-__device__ inline float env_lit8(const EnvL& l, float lr, float lf, float base8) {
-#pragma clang fp contract(off)
-  const float dx = l.Lr - lr, dz = l.Lf - lf;
-  return fminf(fmaf(l.kd8, frsq(fmaf(dx, dx, fmaf(dz, dz, l.h2))), base8), Q8_LIT);
-}
-__device__ inline float env_base8() { return default_cam(1.f).base * Q8_LIT; }
-__device__ inline f2_t env_lit8_2(const EnvL& l, const f2_t lr, const f2_t lf) {   // env_lit8 of two pixels
-#pragma clang fp contract(off)
-  const f2_t dx = f2_t{l.Lr, l.Lr} - lr, dz = f2_t{l.Lf, l.Lf} - lf;
-  const f2_t d2 = fma2(dx, dx, fma2(dz, dz, f2_t{l.h2, l.h2}));
-  const float b8 = env_base8();
-  const f2_t t = fma2(f2_t{l.kd8, l.kd8}, f2_t{frsq(d2.x), frsq(d2.y)}, f2_t{b8, b8});
-  return f2_t{fminf(t.x, Q8_LIT), fminf(t.y, Q8_LIT)};
-}
-// one-ray colour 0x00BBGGRR of a record (a8, b8 as above; I = lit factor, 0..1)
-__device__ inline uint32_t quad_filter(const uint4& q, float a8, float b8, float I) {
-  const uint32_t W = quad_weights8(a8, b8, I * Q8_LIT);
-  const uint32_t vr = __builtin_amdgcn_udot4(q.x, W, 128u, false), vg = __builtin_amdgcn_udot4(q.y, W, 128u, false),
-                 vb = __builtin_amdgcn_udot4(q.z, W, 128u, false);                 // the channel is byte 1 of each sum
-  const uint32_t rg = __builtin_amdgcn_perm(vg, vr, 0x0c0c0501u);
-  return __builtin_amdgcn_perm(vb, rg, 0x0c050100u);
-}
-__device__ inline void quad_filter3(const uint4& q, float a8, float b8, float I, float out[3]) {   // 0..255 floats, unrounded
-  const uint32_t W = quad_weights8(a8, b8, I * Q8_LIT);
-  out[0] = (float)__builtin_amdgcn_udot4(q.x, W, 0u, false) * (1.f / 256.f);
-  out[1] = (float)__builtin_amdgcn_udot4(q.y, W, 0u, false) * (1.f / 256.f);
-  out[2] = (float)__builtin_amdgcn_udot4(q.z, W, 0u, false) * (1.f / 256.f);
-}
-
-#define RQ_LIST 256                                  // MSAA entries compacted per round (the wavefront's 1 KB of LDS)
-// one pixel's colour 0x00BBGGRR into frame e of the exact paths' byte patches: two stores, a 2-byte aligned half + one byte,
-// whichever way the pixel's 3 bytes fall
-__device__ inline void store_rgb(uint8_t* frames, const int npix, const int e, const int pix, const uint32_t rgb) {
-  uint8_t* dst = frames + ((size_t)e * npix + pix) * 3;
-  const bool odd = (reinterpret_cast<uintptr_t>(dst) & 1u) != 0u;
-  uint8_t* p8 = odd ? dst : dst + 2;
-  uint16_t* p16 = reinterpret_cast<uint16_t*>(odd ? dst + 1 : dst);
-  *p8 = (uint8_t)(odd ? rgb : rgb >> 16);
-  *p16 = (uint16_t)(odd ? rgb >> 8 : rgb);
-}
+// k_raster_v3 drains its regions with its own exact path, resolve_region_v3 (render_v3.hip): no interior test, no list.
 // LIGHT: the shared camera with per-env lights (EnvL in render order, envl): the lit factor of the tile plane is env_lit8's, per entry.
 template <bool S256, bool LIGHT = false>
 __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __restrict__ cams, const EnvQ* __restrict__ envq,
@@ -1774,7 +1370,7 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
       const EnvQ* fq = envq + min(e0 + el[u], R.N - 1);   // position in the render order -> constants, frame index
       qa[u] = *reinterpret_cast<const float4*>(&fq->A);     // A, B, Cx, Cz
       qb[u] = *reinterpret_cast<const uint4*>(&fq->Xhi);    // Xhi, Zhi, tab_b, pitch4
-      const uint4 qd = *reinterpret_cast<const uint4*>(&fq->reach);   // reach, env, pad[0], pad[1] (one 16-byte piece: the path is bound by its vector-memory instruction count)
+      const uint4 qd = *reinterpret_cast<const uint4*>(&fq->reach);   // reach, env, tab3, qpm_bits (one 16-byte piece: the path is bound by its vector-memory instruction count)
       env[u] = (int)qd.y;
       if constexpr (LIGHT) { const EnvL l = envl[min(e0 + el[u], R.N - 1)]; pt[u].lit = pt[u].lit > 0.f ? 256.f * env_lit8(l, pt[u].lr, pt[u].lf, env_base8()) : pt[u].lit; }
     }
@@ -1922,10 +1518,7 @@ __device__ inline void resolve_region_q(const RenderParams& R, const EnvCam* __r
 #ifndef DT_Q_WAVES
 #define DT_Q_WAVES 5                                 // wavefronts per SIMD the register allocation is held to (96 VGPRs)
 #endif
-#ifndef DT_Q_PRIO
-#define DT_Q_PRIO 3                                  // s_setprio level while a wavefront issues its quad loads (0: off)
-#endif
-// LIGHT: per-env lights (EnvL in render order), as k_raster_v3<OBJ, true> (render_v3.inc)
+// LIGHT: per-env lights (EnvL in render order), as k_raster_v3<OBJ, true> (render_v3.hip)
 // SUB: the masked pass -- positions [0, live) of k_env_sort<true>'s order, live = R.work[DT_WORK_LIVE] (dt_sub_live); the grid is sized for
 // R.N and the workgroups past the live chunks leave at once.
 template <bool OBJ, bool S256, bool LIGHT = false, bool SUB = false>
@@ -2279,9 +1872,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(OBJ ? DT_Q_W
   }
 }
 
-#include "render_v3.inc"
-#include "render_v3dr.inc"
-
 // Exact 4-sample resolve of the queued edge pixels, stream-ordered after k_raster so the byte patches
 // land after the fast-path stores.  Persistent wavefronts pull work items (ITEM_B consecutive 64-entry
 // batches of one raster workgroup's four queue regions) from the global list k_raster appended to.
@@ -2547,21 +2137,6 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(DT_RO_WAVES,
 
 }  // namespace
 
-// Workgroups of `kernel` (RB threads, lds bytes of dynamic LDS) the device holds at once: the launch size of the persistent exact-path kernels.
-template <class K> static size_t resident_blocks(K kernel, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::tuple<int, size_t, const void*>, size_t> cache;   // (the template is instantiated per function-pointer TYPE: two kernels of one signature share it)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  const auto key = std::make_tuple(dev, lds, reinterpret_cast<const void*>(kernel));
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int per_cu = 0, n_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RB, lds) != hipSuccess || per_cu < 1) per_cu = 3;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-  return cache[key] = (size_t)per_cu * (size_t)n_cu;
-}
 
 // ---- the render scratch: every array of the slabs (dtsim_dev.h RenderSlab), each from a 64-byte boundary ----------------------------------
 #define DT_SCRATCH_ALIGN 64
@@ -2574,9 +2149,8 @@ struct Slab {                                         // the arrays of one alloc
     bytes = off + n * sizeof(T); return base ? reinterpret_cast<T*>(base + off) : nullptr;
   }
 };
-// the arrays dt_launch_render reaches beside RenderParams
-struct EnvRecs { EnvCam* cams; EnvFast* fasts; EnvQ* envq; EnvV* envv; EnvD* envd; EnvL* envl; PixTab* pixtab; SampTab* samptab; };
-static EnvRecs render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams& R) {
+EnvRecs dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams* R_out) {
+  RenderParams tmp{}; RenderParams& R = R_out ? *R_out : tmp;
   const size_t n = (size_t)N, n_pix = (size_t)W * H, n_tiles = dt_raster_tiles(W, H), n_wg = dt_raster_groups(N, W, H);
   Slab sl[DT_SLABS];                                  // (null bases: sizes only)
   for (int i = 0; i < DT_SLABS; ++i) sl[i].base = base ? static_cast<char*>(base[i]) : nullptr;
@@ -2598,7 +2172,6 @@ static EnvRecs render_layout(int N, int W, int H, int max_tris, size_t* bytes, v
   if (bytes) for (int i = 0; i < DT_SLABS; ++i) bytes[i] = sl[i].bytes;
   return x;
 }
-void dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void* const* base, RenderParams* R) { RenderParams tmp{}; render_layout(N, W, H, max_tris, bytes, base, R ? *R : tmp); }
 
 int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_old) {
   // k_raster_v3 / k_raster_v3dr: 256 x 256 tile textures; the maps' padded grids side by side in one LDS tile table
@@ -2623,11 +2196,7 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   const size_t lds2 = lds + (size_t)(RB / 64) * ENVS_PER_BLOCK * sizeof(EnvCam);
   const dim3 grid((unsigned)(dt_raster_tiles(R.W, R.H) * n_chunks));
   const dim3 gridq((unsigned)raster_wg_grid(dt_raster_tiles(R.W, R.H), n_chunks));   // the quad-record rasters' XCD-affine map (raster_wg)
-  const dim3 gridv3(SUB ? gridq.x : (unsigned)raster_ticket_grid(dt_raster_tiles(R.W, R.H), n_chunks, DT_RASTER_TICKET_UNITS));   // k_raster_v3's full pass: + the thieves
   const size_t ldsq = (size_t)R.n_qtiles * 8 + (size_t)RB * PPT * sizeof(uint32_t);
-  const size_t lds_tab = (size_t)R.q3_rows * V3_TAB_PITCH * 4;   // the v3 kernels' LDS tile table
-  const size_t lds3 = lds_tab + (size_t)(RB / 64) * V3_WAVE_LDS * 4 + (size_t)ENVS_PER_BLOCK * sizeof(EnvQ);   // + per-wavefront buffers, the chunk's EnvQ records
-  const size_t ldsd = lds_tab + (size_t)(RB / 64) * RQ_LIST * 4;
   const bool s256 = R.qlog2 == 8 && R.qmax_tiles < 256;
 #define LAUNCH_RASTER(DR_, OBJ_)                                                                              \
   hipLaunchKernelGGL((k_raster<DR_, OBJ_>), grid, dim3(RB), lds1, s, R, x.cams, x.fasts, R.frames, R.texels,                  \
@@ -2636,21 +2205,13 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
                                            R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
                                 else hipLaunchKernelGGL((k_raster_q<OBJ_, S256_, false, SUB>), gridq, dim3(RB), ldsq, s, R, x.cams, x.fasts, x.envq, R.frames, R.qtex, \
                                            reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
-#define LAUNCH_V3(OBJ_) do { if (R.light) hipLaunchKernelGGL((k_raster_v3<OBJ_, true, SUB>), gridv3, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, \
-                                           R.qtex, reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, x.envl); \
-                                else hipLaunchKernelGGL((k_raster_v3<OBJ_, false, SUB>), gridv3, dim3(RB), lds3, s, R, x.cams, x.fasts, x.envq, x.envv, R.frames, R.qtex, \
-                                           reinterpret_cast<const float4*>(R.lut), x.pixtab, x.samptab, R.qtiles, R.queue, R.qcount, nullptr); } while (0)
   switch (pipe) {
-    case DTSIM_PIPE_V3: if (obj) LAUNCH_V3(true); else LAUNCH_V3(false); break;
+    case DTSIM_PIPE_V3: dt_launch_raster_v3(s, R, x, SUB); break;                     // render_v3.hip
     case DTSIM_PIPE_Q: if (obj) { if (s256) LAUNCH_Q(true, true); else LAUNCH_Q(true, false); } else if (s256) LAUNCH_Q(false, true); else LAUNCH_Q(false, false); break;
-    case DTSIM_PIPE_V3DR:
-      if (obj) hipLaunchKernelGGL((k_raster_v3dr<true, SUB>), gridq, dim3(RB), ldsd, s, R, x.cams, x.envd, R.frames, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-      else hipLaunchKernelGGL((k_raster_v3dr<false, SUB>), gridq, dim3(RB), ldsd, s, R, x.cams, x.envd, R.frames, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-      break;
+    case DTSIM_PIPE_V3DR: dt_launch_raster_v3dr(s, R, x, SUB); break;                 // render_v3.hip: k_raster_v3dr, then k_resolve_dr on its plane-edge pixels
     case DTSIM_PIPE_GENERIC_ENV: if (obj) LAUNCH_RASTER(true, true); else LAUNCH_RASTER(true, false); break;   // per-env EnvCam (light: the shared camera's, with the env's light)
     default: if (obj) LAUNCH_RASTER(false, true); else LAUNCH_RASTER(false, false);
   }
-#undef LAUNCH_V3
 #undef LAUNCH_Q
 #undef LAUNCH_RASTER
   // exact path.  Quad pipeline: the plane-edge pixels were resolved inside k_raster_q (resolve_region_q); generic raster:
@@ -2658,10 +2219,7 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   // are k_resolve_obj's, after either raster.
   // persistent wavefronts pulling work items: enough workgroups to fill every CU at the kernel's occupancy
   // (round 4: EXACTLY the resident workgroups -- every wavefront's first grab is static, a workgroup that waits for a slot would sit on its items)
-  if (pipe == DTSIM_PIPE_V3DR) {                     // plane-edge pixels of k_raster_v3dr: on the quad records, through the env's homography
-    const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve_dr, lds_tab)));
-    hipLaunchKernelGGL(k_resolve_dr, rgrid, dim3(RB), lds_tab, s, R, x.cams, x.envd, R.qtex, reinterpret_cast<const float4*>(R.lut), R.qtiles, R.queue, R.qcount);
-  } else if (!quad) {
+  if (!quad && pipe != DTSIM_PIPE_V3DR) {            // (k_raster_v3dr's plane-edge pixels: k_resolve_dr, launched with it)
     const dim3 rgrid((unsigned)std::min<size_t>(grid.x, resident_blocks(k_resolve, lds2)));
     hipLaunchKernelGGL(k_resolve, rgrid, dim3(RB), lds2, s, R, x.cams, R.queue, R.qcount);
   }
@@ -2672,11 +2230,8 @@ static void launch_raster_resolve(hipStream_t s, const RenderParams& R, const En
   }
 }
 
-int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R_in, int pipe, int tables, const uint8_t* mask) {
-  RenderParams R = R_in;
+int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, const EnvRecs& x, int pipe, int tables, const uint8_t* mask) {
   tables &= 3;                                         // bit 2 (returned): this pass ran in k_env_sort's order (DTSIM_FIELD_RENDER_POS)
-  void* base[DT_SLABS] = {R.envcam, R.pixtab}; RenderParams carved{};   // each slab's first array; R keeps its own pointers
-  const EnvRecs x = render_layout(A.N, R.W, R.H, 0, nullptr, base, carved);
   const bool quad = pipe == DTSIM_PIPE_V3 || pipe == DTSIM_PIPE_Q, v3dr = pipe == DTSIM_PIPE_V3DR;
   // render order (k_env_sort): the quad pipeline indexes by position (EnvQ, object masks, queue entries); env ids come
   // from EnvQ.env

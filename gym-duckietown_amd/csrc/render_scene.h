@@ -1,5 +1,5 @@
 // render_scene.h -- the scene as one camera ray sees it: what the render pass (render.hip) and the kernels that read what a pass leaves
-// behind (render_views.hip) both use, so that an overlay, a depth or a label is decided by the frame's own code.  The per-env camera record,
+// behind (render_views.hip) both use, so that an overlay, a depth or a label is decided by the frame's own code.  On the per-env camera record (EnvCam, render_records.h):
 // the planes and their ownership test (classify), the z-buffer test of one projected mesh triangle (test_tri), and the two GL rules every
 // per-sample path must agree on: the MSAA sample positions (MSAA_POS) and the source-pixel centre of an NDC point (src_px).
 // A device header with internal linkage: each unit compiles its own copy with its own flags (both with render.hip's, build.py).
@@ -15,22 +15,6 @@
 #define FAR_Z 100.0f
 #define GROUND_Y (-0.008f)   // ground quad: y=-0.8 scaled by 0.01 (simulator.py:510-526,1810)
 #define GROUND_HALF 50.0f
-
-struct alignas(16) EnvCam {          // 32 floats = 128 B, written by k_cam_setup
-  float Cx, Cy, Cz;      // camera centre (world)
-  float sa, ca;          // yaw
-  float sth, cth;        // pitch (cam_angle[0])
-  float tx, ty;          // tan(fov_y/2)*aspect, tan(fov_y/2)
-  float hor[3];          // horizon colour * 255
-  float gnd[3];          // ground colour * 255
-  float base[3];         // scene ambient 0.3 + light ambient
-  float dif[3];          // light diffuse
-  float L[4];            // light position, eye space (w=0: direction, pre-normalised)
-  float gndl[4];         // max(0, N.L) at the 4 ground-quad corners (-x-z, +x-z, -x+z, +x+z)
-  int32_t map_id;
-  float pad[2];
-};
-static_assert(sizeof(EnvCam) == 128, "EnvCam is 128 bytes");
 
 // coverage-only part of a ScreenTri kept in LDS by k_resolve_obj; the winner's colours are fetched
 // from global memory.

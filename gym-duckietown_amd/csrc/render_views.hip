@@ -745,14 +745,14 @@ static inline dim3 dt_ipm_grid(const IpmArgs& a) { return view_grid((a.oh * a.ow
 
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(k_overlay_leds, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, reinterpret_cast<const EnvCam*>(R.envcam), d_spheres, first, count, env);
+  hipLaunchKernelGGL(k_overlay_leds, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, R.envcam, d_spheres, first, count, env);
 }
 
 void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask) {
   if (R.N <= 0) return;
   const dim3 grid = view_grid(oh * ow, R.N);
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-#define LAUNCH_DEPTH(F16_) hipLaunchKernelGGL(k_depth<F16_>, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs, \
+#define LAUNCH_DEPTH(F16_) hipLaunchKernelGGL(k_depth<F16_>, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, \
                                               reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.max_tris,    \
                                               R.n_maps, R.N, R.W, R.H, oh, ow, out, mask)
   if (f16) LAUNCH_DEPTH(true); else LAUNCH_DEPTH(false);
@@ -765,7 +765,7 @@ void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel
   const dim3 grid = view_grid(oh * ow, R.N);
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
   auto k = out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>;
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, reinterpret_cast<const EnvCam*>(R.envcam), R.maps, R.tile_recs,
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs,
                      reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
                      n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask);
 }
@@ -805,5 +805,5 @@ void dt_launch_ipm_env(hipStream_t s, const IpmArgs& a, const SimArrays& A, bool
 
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env) {
   if (count <= 0) return;
-  hipLaunchKernelGGL(k_overlay_lines, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, reinterpret_cast<const EnvCam*>(R.envcam), d_lines, first, count, env);
+  hipLaunchKernelGGL(k_overlay_lines, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, R.envcam, d_lines, first, count, env);
 }

@@ -249,7 +249,7 @@ inline void dt_pack_quad_block(std::vector<uint32_t>& out, const uint32_t* pool,
   for (int z0 = 0; z0 < S; ++z0)
     for (int x0 = 0; x0 < S; ++x0) {
       const uint32_t t00 = texel(x0 - 1, z0 - 1), t10 = texel(x0, z0 - 1), t01 = texel(x0 - 1, z0), t11 = texel(x0, z0);
-      // S = 256: 4 x 2 cells per 128-byte line -- record number (x0 >> 2) << 10 | z0 << 2 | (x0 & 3) (render.hip, q8_rec256: a 32 x 2 pixel slot of the
+      // S = 256: 4 x 2 cells per 128-byte line -- record number (x0 >> 2) << 10 | z0 << 2 | (x0 & 3) (raster_common.h, q8_rec256: a 32 x 2 pixel slot of the
       // raster touches ~ 15 % fewer lines than with the rows of the texture laid end to end); other sizes: row-major
       const size_t rec = (S == 256) ? ((size_t)(x0 >> 2) << 10) | ((size_t)z0 << 2) | (size_t)(x0 & 3) : (size_t)z0 * S + x0;
       uint32_t* q = &out[base + rec * 4];
@@ -468,7 +468,7 @@ inline int dt_pack_maps(MapTables& out, std::string& err, const dtsim_map* maps,
         }
     }
     if (32 + (size_t)(n_blocks + 1) * block_bytes >= ((size_t)1 << 32)) qlog2 = -1;   // 32-bit block offsets
-    if ((size_t)(std::max(T.grid_rows, T.grid_cols)) * S >= 32768) qlog2 = -1;          // quad coordinates below 32768 (render.hip, Q8_SNAP): else the generic raster
+    if ((size_t)(std::max(T.grid_rows, T.grid_cols)) * S >= 32768) qlog2 = -1;          // quad coordinates below 32768 (raster_common.h, Q8_SNAP): else the generic raster
   }
   if (qlog2 <= 0 || qtiles.empty()) { qblocks.clear(); qtiles.clear(); qlog2 = 0; q_per_m = 0.f; }   // no quad records: the generic raster
   for (auto& rm : T.rmaps) T.max_tris = std::max(T.max_tris, rm.n_tris);

@@ -153,7 +153,7 @@ def _exact_linear(tex, u, v):
 
 
 def _dtsim8_shade(tex, u, v, I, folded):
-    """Tile colour (0..255 float, unrounded) of the product's quad-record pipeline (csrc/render.hip quad_weights8 / quad_filter,
+    """Tile colour (0..255 float, unrounded) of the product's quad-record pipeline (csrc/raster_common.h quad_weights8 / quad_filter,
     DESIGN.md section 5), at the precision GL's own filter has:
       * the texel coordinate is rounded to 256ths of a texel first (round-to-nearest-even: the product's one float add X + 32768),
         as llvmpipe rounds its own (_gl_linear); the integer part addresses the texels -- a fraction that rounds up to 1 carries;

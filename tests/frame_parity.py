@@ -173,7 +173,7 @@ def obj_states(sim, e, sc):
 def stratified_picks(sim, N, n_min, seed):
     """Env indices of an N-env batch that exercise the raster's work decomposition.  The decomposition goes by POSITION in the
     render order of the pass that just ran (DTSIM_FIELD_RENDER_POS: k_env_sort's order on the quad-record paths, the identity
-    elsewhere): 64 consecutive positions (32 before round 6) share a workgroup chunk, XCD x owns the x-th eighth of the chunks (render_v3.inc:
+    elsewhere): 64 consecutive positions (32 before round 6) share a workgroup chunk, XCD x owns the x-th eighth of the chunks (raster_common.h:
     XCD-affine workgroup map).  Picked positions: the first / last of the order, both sides of chunk borders, the middle of
     every XCD's eighth (a chunk border there), the tail chunk -- mapped back to env indices -- plus envs 0 and N - 1."""
     pos = sim.read(_ffi.FIELD_RENDER_POS)

@@ -38,7 +38,7 @@ from util import EXT
 
 TS = 0.585
 W, H, N = 160, 120, 130
-QRING, V3_MAX_ROWS, V3_MAP_COLS, V3_TAB_PITCH = 4, 24, 32, 256     # csrc/scene_tables.h DT_QRING; csrc/render_v3.inc; csrc/render.hip
+QRING, V3_MAX_ROWS, V3_MAP_COLS, V3_TAB_PITCH = 4, 24, 32, 256     # csrc/scene_tables.h DT_QRING; csrc/raster_common.h; csrc/render_records.h
 MARGIN = 0.1                                                       # metres from the outer border to the nearest pose
 # ... of the outward views, on an object-free map and on a map with objects: the tile under the camera fills 3 % / 7 % of the frame.  At the
 # far corner of the 24 x 16 map the oracle's byte-weight filter moves by +-1 on a tenth of the tile pixels when the pose moves by a float32's

@@ -243,7 +243,7 @@ def order_is_sorted(rpos, key, clear, selected=None):
 
 
 # ---- the workgroup map of the quad-record rasters ----------------------------------------------------------------------------------
-# Written from the comment block above raster_wg in csrc/render.hip: workgroup b runs on XCD b % 8; XCD x is given the x-th eighth of the
+# Written from the comment block above raster_wg in csrc/raster_common.h: workgroup b runs on XCD b % 8; XCD x is given the x-th eighth of the
 # chunks, ceil(n_chunks / 8) of them; within an XCD, groups of dt_q_tile_group() frame tiles (half the frame, the last group padded), all
 # chunks of the slice for one group before the next group.
 

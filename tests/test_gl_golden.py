@@ -60,7 +60,7 @@ def test_per_fragment_tile_light_is_within_one_level_of_gl():
 
 def test_quad_filter_distance_to_gl():
     """The product's quad-record pipeline filters with ONE byte-weight multiply-accumulate per texel and channel (oracle mode "pixel" =
-    per-fragment light + raster._dtsim8_shade, the restatement of csrc/render.hip quad_filter) where llvmpipe lerps twice with an 8-bit
+    per-fragment light + raster._dtsim8_shade, the restatement of csrc/raster_common.h quad_filter) where llvmpipe lerps twice with an 8-bit
     intermediate.  Its distance to the GL frames, measured: a +-1/255 difference on a fraction of the textured pixels, nothing beyond that
     except the silhouette samples -- these numbers are the tolerance tests/test_gpu_gl_golden.py holds the HIP raster to."""
     for case, ks in (("small_loop_t256_160", (0, 7)), ("small_loop_dr_t256_160", (3,)), ("small_loop_t256_640", (1,))):

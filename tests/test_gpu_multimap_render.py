@@ -12,7 +12,7 @@ multimap_scenes.expected_pipeline.  Then:
   c. replicas, a second pass and a masked pass over the envs of the highest map id: the same bytes;
   d. depth() and labels() of S4, S5 and L4 against the one-map handles', byte for byte.
 
-A map id the LDS tile table mixes up (the column offset of k_cam_setup's EnvQ.pad[0], the mi * V3_MAP_COLS stride of v3_fill_tile_table) reads
+A map id the LDS tile table mixes up (the column offset of k_cam_setup's EnvQ.tab3, the mi * V3_MAP_COLS stride of v3_fill_tile_table) reads
 another map's entries of the same table: nothing faults, the frames are wrong.  Both mutants were run: v3_fill_tile_table with (mi & 1) fails
 a. and b. at map id 2 of S3, S4, P4 and L4 (frame mean 0.4 - 26 against 0.03); k_cam_setup with (map_id & 1) fails a. and b. at map id 2 of P4
 and L4 -- S3 and S4 cannot see it, their maps 2 / 3 repeat the tiles of maps 0 / 1.

@@ -1,4 +1,4 @@
-"""GPU: k_raster_v3's workgroup map with a ticketed suffix (csrc/raster_map.h, raster_wg / raster_claim_* in render.hip) writes every frame
+"""GPU: k_raster_v3's workgroup map with a ticketed suffix (csrc/raster_map.h, raster_wg / raster_claim_* in raster_common.h) writes every frame
 tile of every env once, whoever claims the item.
 
 The frame batch is filled with a sentinel; a full pass (the static prefix, the claimed suffix, stealing between the XCDs' lists) must then

@@ -38,7 +38,7 @@ void rm_enumerate(int n_tiles, int n_chunks, int units, int* out) {
 void rm_lists(int n_tiles, int n_chunks, int units, int* out) {
   for (int x = 0; x < DT_RASTER_XCDS; ++x) { out[2 * x] = raster_list_len(n_tiles, n_chunks, x); out[2 * x + 1] = raster_ticket_len(n_tiles, n_chunks, x, units); }
 }
-// the claim protocol of raster_claim_issue / raster_claim_finish (render.hip), one claimer after the other in the given order of workgroups:
+// the claim protocol of raster_claim_issue / raster_claim_finish (raster_common.h), one claimer after the other in the given order of workgroups:
 // the own counter first (a thief draws none there), then a look at the other seven and a draw from each that is not dry, until an item comes;
 // per claimer tile (-1: it leaves), chunk, atomic adds used
 void rm_claims(int n_tiles, int n_chunks, int units, const int* order, int n, int* out) {

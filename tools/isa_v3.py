@@ -1,13 +1,13 @@
 """Instruction mix of the env loops of k_raster_v3<OBJ=0> / k_raster_v3dr<OBJ=0> from the compiler's ISA (no GPU needed).
 
-    python tools/isa_v3.py [render.hip [-DFOO=1 ...]]   # compiles to $TMPDIR/dtsim_isa/render.s with the library's flags (build.py)
+    python tools/isa_v3.py [render_v3.hip [-DFOO=1 ...]]   # compiles to $TMPDIR/dtsim_isa/render.s with the library's flags (build.py)
 
 Per inner-most loop of the kernel that stores frames (buffer_store): VALU / SALU / VMEM / DS instruction counts of the loop body and,
 as every iteration shades PPT = 4 pixels per lane, VALU per pixel."""
 import collections, os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gym-duckietown_amd"))
 import build as dtbuild
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(dtbuild.CSRC, "render.hip")
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(dtbuild.CSRC, "render_v3.hip")
 out = os.path.join(tempfile.gettempdir(), "dtsim_isa", "render.s")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 if not os.environ.get("ISA_REUSE"): subprocess.run(dtbuild.compile_cmd(src, out, sys.argv[2:], asm=True), check=True, stderr=subprocess.DEVNULL)
