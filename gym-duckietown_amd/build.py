@@ -6,8 +6,9 @@
 
 UNITS is the one statement of the library's units and their flags: tools/isa_*.py, .sh and tools/build_variant.sh take them from here.
 physics.hip and remap.hip (the camera_rand table builder, pinned to numpy) are compiled with contraction off (separately rounded ops, in
-the reference's operation order); render.hip and render_v3.hip with contraction allowed (speed, f32), and render_views.hip as render.hip,
-whose classify() and test_tri it shares (csrc/render_scene.h).
+the reference's operation order); render.hip, render_setup.hip, render_exact.hip and render_v3.hip -- the units of a render pass -- with
+contraction allowed (speed, f32), and render_views.hip as they, whose classify() and test_tri it shares (csrc/render_scene.h).
+-Werror=unused-function: a helper nobody calls does not build.
 """
 from __future__ import annotations
 
@@ -22,9 +23,10 @@ LIB = os.path.join(LIBDIR, "libdtsim.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-UNITS = {"physics.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=fast"], "render_v3.hip": ["-ffp-contract=fast"],
+UNITS = {"physics.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=fast"], "render_setup.hip": ["-ffp-contract=fast"],
+         "render_exact.hip": ["-ffp-contract=fast"], "render_v3.hip": ["-ffp-contract=fast"],
          "render_views.hip": ["-ffp-contract=fast"], "observe.hip": [], "dtsim_api.hip": [], "remap.hip": ["-ffp-contract=off"]}
-COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical",
+COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Werror=unused-function", "-Wno-bitwise-instead-of-logical",
           "-I" + os.path.join(HERE, "..", "include")]
 
 

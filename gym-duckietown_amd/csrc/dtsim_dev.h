@@ -52,7 +52,7 @@ void dt_launch_query(hipStream_t s, const SimArrays& A, const MapSet& M, const S
 // One mesh triangle of one env after model/view/projection and per-vertex lighting
 // (objects.py:123-148, objmesh.py:360-375): rectilinear pixel coordinates, 1/w, lit colour/w.
 struct alignas(16) ScreenTri {
-  // first 64 bytes: coverage / depth (all k_resolve's z-buffer pass reads; same layout as render_scene.h TriCov)
+  // first 64 bytes: coverage / depth (all k_resolve's z-buffer pass reads; same layout as render_exact.hip TriCov)
   float bx0, bx1, by0, by1;  // pixel bounding box (+-1 px); empty (bx0 > bx1) when culled
   float sx[3], sy[3], iw[3];
   float inv_area;            // 0 => culled (behind the near plane / degenerate / invisible)
@@ -141,7 +141,7 @@ struct RenderParams {
 #define DT_WORK_OBJ_FRONT 2      //   k_resolve_obj's heavy items, from the front of RenderParams.items2
 #define DT_WORK_OBJ_CURSOR 3     //   its grab cursor
 #define DT_WORK_OBJ_BACK 6       //   its other items, from the back of items2
-#define DT_WORK_LIVE 7           //   envs of a masked pass (k_env_sort_masked), read by the SUB rasters
+#define DT_WORK_LIVE 7           //   envs of a masked pass (k_env_sort<true>), read by the SUB rasters
 #define DT_WORK_TICKETS 32       //   k_raster_v3's ticket counters (raster_map.h): XCD x's at DT_WORK_TICKETS + 32 * x, 128 bytes apart and from the slots above
 // The render scratch (render.hip dt_render_layout): the allocations RenderParams points into, each a run of arrays -- ENV: per env EnvCam, EnvFast,
 // EnvQ, envpos, EnvV [N + 1], EnvD, EnvL [N + 1]; PIX: PixTab, SampTab, RenderDump; QCOUNT: qcount, work; ITEMS: items, items2; STRIS: stris, tribox.
@@ -154,17 +154,26 @@ EnvRecs dt_render_layout(int N, int W, int H, int max_tris, size_t* bytes, void*
 // The raster of a pass (DTSIM_PIPE_*) from R, the largest padded tile grid of the maps (grid_rows x grid_cols, DT_QRING ring included) and
 // DTSIM_RASTER_OLD (raster_old: k_raster_q / the generic raster instead of k_raster_v3 / k_raster_v3dr); sets R.q3_rows.
 int dt_raster_pipe(RenderParams& R, int grid_rows, int grid_cols, bool raster_old);
-// pipe: dt_raster_pipe's choice for R.  tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an
-// earlier launch (they depend on the camera LUT and the maps only); returns the bits that are valid after this launch,
-// plus bit 2 when the pass ran in k_env_sort's render order (RenderParams.envpos holds it: DTSIM_FIELD_RENDER_POS).
+// One render pass on stream s, the one entry point of dtsim_api.hip: the setup kernels (render_setup.hip), the raster of `pipe` (render.hip,
+// render_v3.hip), the exact-path kernels (render_exact.hip).  pipe: dt_raster_pipe's choice for R; x: dt_render_layout's records of R's slabs.
+// tables: bit 0 = the per-pixel tables (k_pix_setup), bit 1 = block boxes / object ranges (k_blk_setup) are valid from an earlier launch (they
+// depend on the camera LUT and the maps only); returns the bits that are valid after this launch, plus bit 2 when the pass ran in k_env_sort's
+// render order (RenderParams.envpos holds it: DTSIM_FIELD_RENDER_POS).
 // mask (device, [N] bytes, nonzero = selected): the masked pass of dtsim_render_masked -- the quad-record pipelines render the selected envs
-// only (positions [0, live) of k_env_sort_masked's order, pos = -1 for the others); the generic rasters render every env.
-// x: dt_render_layout's records of R's slabs.
+// only (positions [0, live) of k_env_sort<true>'s order, pos = -1 for the others); the generic rasters render every env.
 int dt_launch_render(hipStream_t s, const SimArrays& A, const RenderParams& R, const EnvRecs& x, int pipe, int tables, const uint8_t* mask = nullptr);
-// The rasters of render_v3.hip, called by dt_launch_render after its setup kernels; sub: the masked pass (the SUB instantiations over positions
-// [0, live)).  k_raster_v3 (DTSIM_PIPE_V3) resolves its plane-edge pixels inside; k_raster_v3dr (DTSIM_PIPE_V3DR) is followed by k_resolve_dr.
+// Its three steps.  Setup (render_setup.hip): the render order (k_env_sort), R.work zeroed, the per-env records (k_cam_setup), the mesh
+// objects (k_blk_setup, k_obj_setup) and the per-pixel tables (k_pix_setup) a raster of `pipe` reads; tables, mask: as above.  Returns
+// tables: dt_launch_render's return value; sub: this is a masked pass in render order (the rasters' SUB instantiations over positions
+// [0, live)); has_pos: the pass runs in k_env_sort's order (positions become envs through EnvQ.env).
+struct RenderSetup { int tables; bool sub, has_pos; };
+RenderSetup dt_launch_render_setup(hipStream_t s, const SimArrays& A, const RenderParams& R, const EnvRecs& x, int pipe, int tables, const uint8_t* mask);
+// The rasters of render_v3.hip (sub: RenderSetup.sub).  k_raster_v3 (DTSIM_PIPE_V3) resolves its plane-edge pixels inside; k_raster_v3dr (DTSIM_PIPE_V3DR) is followed by k_resolve_dr.
 void dt_launch_raster_v3(hipStream_t s, const RenderParams& R, const EnvRecs& x, bool sub);
 void dt_launch_raster_v3dr(hipStream_t s, const RenderParams& R, const EnvRecs& x, bool sub);
+// Exact path (render_exact.hip): k_resolve on the plane-edge pixels a generic raster queued, k_resolve_obj on the pixels inside mesh-object
+// screen boxes (R.max_tris > 0) after any raster.
+void dt_launch_render_exact(hipStream_t s, const RenderParams& R, const EnvRecs& x, int pipe, bool has_pos);
 // GL_LINE overlays (draw_curve / draw_bbox; render_views.hip k_overlay_lines) as a post-pass on the resolved frame of `env`: d_lines = [..][9] world-space segments + colour
 // (device memory), `count` of them from `first` on; uses the EnvCam the last render wrote.
 void dt_launch_overlay_lines(hipStream_t s, const RenderParams& R, const float* d_lines, int first, int count, int env);

@@ -1,7 +1,8 @@
-// raster_common.h -- the device helpers that both units of the render pass use (render.hip, render_v3.hip): the work decomposition's
-// constants, the ground quad's shading rule, the queue-entry layout and the work lists, the scaffolding the rasters and the exact paths must
-// agree on, the byte-weight ("dtsim8") filter, and the launch size of the persistent kernels.  A helper that one unit alone uses stays in that unit.
-// A device header with internal linkage, like render_scene.h: each unit compiles its own copy with render.hip's flags (build.py).
+// raster_common.h -- the device helpers that two or more units of the render pass use (render_setup.hip, render.hip, render_v3.hip,
+// render_exact.hip): the work decomposition's constants, the ground quad's shading rule, the queue-entry layout and the work lists, the
+// scaffolding the rasters and the exact paths must agree on, the per-pixel invariants of the shared camera (pix_inv), GL's integer filter
+// (gl_linear_rgb) and the byte-weight ("dtsim8") filter, and the launch size of the persistent kernels.  A helper that one unit alone uses stays in that unit.
+// A device header with internal linkage, like render_scene.h: each unit compiles its own copy with the pass's flags (build.py).
 #ifndef DTSIM_RASTER_COMMON_H
 #define DTSIM_RASTER_COMMON_H
 #include "dtsim_dev.h"
@@ -29,7 +30,7 @@
 namespace {
 
 // ---- ground quad (simulator.py:1806-1812): N.L is lit at the four corners (EnvCam.gndl) and interpolated bilinearly at (a, b) in [0, 1]^2; a channel is
-// gnd * min(base + dif * N.L, 1) -- ground_lit, and still written out in shade, shade_msaa and the env loops of k_raster, k_raster_q and k_raster_v3dr.
+// gnd * min(base + dif * N.L, 1) -- ground_lit, and still written out in shade_msaa and the env loops of k_raster, k_raster_q and k_raster_v3dr.
 __device__ inline float ground_corner_ndl(const float a, const float b, const float g0, const float g1, const float g2, const float g3) {
   const float n0 = g0 + a * (g1 - g0), n1 = g2 + a * (g3 - g2);
   return n0 + b * (n1 - n0);
@@ -45,10 +46,6 @@ __device__ inline float ground_ndl(const EnvCam& c, float wx, float wz) {      /
 __device__ inline float absmax(float a, float b) { float r; asm("v_max_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // floor(x) as int in one instruction
 __device__ inline int flr_i32(float x) { int r; asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x)); return r; }
-// v_cvt_f32_ubyteN: one instruction per texel channel (the compiler does not pick it)
-__device__ inline float ubyte0(uint32_t x) { float r; asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(x)); return r; }
-__device__ inline float ubyte1(uint32_t x) { float r; asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(r) : "v"(x)); return r; }
-__device__ inline float ubyte2(uint32_t x) { float r; asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(r) : "v"(x)); return r; }
 
 __device__ inline uint32_t pack_rgb(const float col[3]) {  // glReadPixels float -> unorm8: round(255 c)
   const uint32_t r = (uint32_t)(fminf(fmaxf(col[0], 0.f), 255.f) + 0.5f);
@@ -226,11 +223,56 @@ __device__ inline void v3_fill_tile_table(const RenderParams& R, const uint32_t*
   }
 }
 
-// ---- the raster tile records of every map -> LDS (k_resolve, k_resolve_obj: [n_tile_recs] TileLds at the start of the workgroup's
-// dynamic LDS).  The caller's barrier follows.  (k_raster keeps the same loop written out: the call moved an instruction of its prologue.)
-__device__ inline void fill_tile_recs(const RenderParams& R, uint32_t* s_mem, const int tid) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(R.tile_recs);
-  for (int i = tid; i < R.n_tile_recs * (int)(sizeof(TileLds) / 4); i += RB) s_mem[i] = src[i];
+// ---- per-pixel quantities that do not depend on the env when the camera is shared: k_raster<false, OBJ> keeps them in registers, k_pix_setup
+// (render_setup.hip) turns them into the quad-record rasters' PixTab ------
+struct PixInv {
+  float lr, lf;     // tile-plane hit in the yaw-local frame (right, forward), metres
+  float ndl;        // max(0, N.L) of the tile plane at the hit
+  float mrg;        // conservative world-space footprint radius of the 4 MSAA samples
+  uint32_t flags;   // PF_*
+};
+#define PF_VALID 1u       // inside the source image (else BORDER_CONSTANT 0)
+#define PF_SKY 2u         // all 4 samples certainly miss every plane
+#define PF_ALWAYS_EDGE 4u // horizon band / near-far limits: always take the exact path
+#define PF_TILE_OK 8u     // tile-plane hit within [near, far]
+#define PF_GROUND_OK 16u  // ground-plane hit within [near, far]
+
+__device__ inline PixInv pix_inv(float nx, float ny, bool valid, float tx, float ty, float sth, float cth,
+                                 float Cy, const float L[4], float ex_n, float ey_n) {
+  PixInv p;
+  p.flags = valid ? PF_VALID : 0u;
+  p.lr = p.lf = p.ndl = p.mrg = 0.f;
+  const Ray r = make_ray(nx, ny, tx, ty, sth, cth);
+  const float ex = ex_n * tx, ey = ey_n * ty;
+  const float dy = ey * fabsf(cth);
+  if (!(r.yla < 0.f)) {
+    p.flags |= (r.yla - dy >= 0.f) ? PF_SKY : PF_ALWAYS_EDGE;
+    return p;
+  }
+  const float inv = frcp(-r.yla);
+  const float t = Cy * inv;
+  p.lr = t * r.xe; p.lf = t * r.fwd;
+  p.ndl = plane_ndl(L, sth, cth, r, t);
+  const float rho = dy * inv;
+  // World-space reach of the MSAA samples around the pixel-centre hit.  A sample offset
+  // (dx, dy) px moves the hit by  t*ex*dx  along `right` and, through the change of the ray
+  // parameter (kappa = rho/(1-rho) per full y-offset), by (lr, lf)*kappa*dy + t*ey*|sth|*dy along
+  // (right, forward).  The rotated-grid samples sit at (+-0.375, +-0.125) and (+-0.125, +-0.375):
+  // take the larger of the two reaches (ex/ey already carry the 0.375 and a 1% pad), +5%.
+  {
+    const float kappa = rho * frcp(fmaxf(1.f - rho, 0.25f));
+    const float ax_ = t * ex, ry_ = fabsf(p.lr) * kappa, fy_ = fabsf(p.lf) * kappa + t * ey * fabsf(sth);
+    const float third = 1.f / 3.f;
+    const float r1x = ax_ + third * ry_, r1f = third * fy_;          // (0.375, 0.125)
+    const float r2x = third * ax_ + ry_, r2f = fy_;                  // (0.125, 0.375)
+    p.mrg = 1.05f * fsqrt_(fmaxf(r1x * r1x + r1f * r1f, r2x * r2x + r2f * r2f));
+  }
+  const float tg = (Cy - GROUND_Y) * inv;
+  if (t >= NEAR_Z && t <= FAR_Z) p.flags |= PF_TILE_OK;
+  if (tg >= NEAR_Z && tg <= FAR_Z) p.flags |= PF_GROUND_OK;
+  if (rho > 0.25f || tg * (1.f + 2.f * rho) > FAR_Z * 0.98f || t * (1.f - 2.f * rho) < NEAR_Z * 1.02f)
+    p.flags |= PF_ALWAYS_EDGE;
+  return p;
 }
 
 // ==== scaffolding shared by the exact paths: what resolve_region_q / _v3, k_resolve, k_resolve_dr and k_resolve_obj must agree on, stated once ====
@@ -303,8 +345,25 @@ __device__ inline void spxy_unpack(uint32_t t, float& sx, float& sy) {
 
 struct alignas(4) U3 { uint32_t a, b, c; };           // 4 pixels x RGB: a lane's 12 bytes of a frame row
 
+// ---- GL_LINEAR as the reference's renderer computes it -------------------------------------------------------------------
+// GL leaves the filter's precision to the implementation.  The reference's CI renderer -- Mesa llvmpipe, the one the GL goldens
+// come from (tests/golden/ref_gl_*.npz) -- filters RGBA8 textures in integers (measured bit-exact, profiles/r06_gl_filter_precision.txt):
+// texel coordinate * 256, rounded, minus half a texel; the low 8 bits are the weight; lerp(w, p, q) = p + ((w (q - p) + 128) >> 8),
+// along s for both rows, then along t on the 8-bit results.  gl_fix: coordinate already shifted by the half texel -> fixed point.
+// The generic k_raster (render.hip) and the exact-path shaders (tile_color, mesh_texel: render_exact.hip) filter with it.
+__device__ inline int gl_lerp8(int w, int p, int q) { return p + ((w * (q - p) + 128) >> 8); }
+__device__ inline int gl_fix(float x) { return (int)floorf(fmaf(x, 256.f, 0.5f)); }
+__device__ inline void gl_linear_rgb(uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11, int wx, int wy, int out[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int c00 = (int)((t00 >> (8 * k)) & 255u), c10 = (int)((t10 >> (8 * k)) & 255u);
+    const int c01 = (int)((t01 >> (8 * k)) & 255u), c11 = (int)((t11 >> (8 * k)) & 255u);
+    out[k] = gl_lerp8(wy, gl_lerp8(wx, c00, c10), gl_lerp8(wx, c01, c11));
+  }
+}
+
 // ---- the quad-record filter ("dtsim8") -------------------------------------------------------------------
-// GL's own filter (llvmpipe: gl_linear_rgb, render.hip) works with 8-bit weights and 8-bit intermediates, so nothing is gained by filtering
+// GL's own filter (llvmpipe: gl_linear_rgb, above) works with 8-bit weights and 8-bit intermediates, so nothing is gained by filtering
 // finer than that; the quad pipeline filters in ONE v_dot4_u32_u8 per channel: the four bilinear weights, times the lit factor
 // where it is the same for the three channels (shared camera), times 256, rounded to bytes (v_cvt_pk_u8_f32); colour =
 // (sum(texel * weight) + 128) >> 8.  Measured against the GL goldens it differs from llvmpipe by +-1/255 on about a quarter of the

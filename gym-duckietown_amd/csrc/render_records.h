@@ -1,5 +1,5 @@
 // render_records.h -- the records one stage of the render pass writes and another reads: the per-env constants (EnvCam, EnvFast, EnvQ, EnvV,
-// EnvL, EnvD: written by render.hip's k_cam_setup, read by the rasters, the exact paths and render_views.hip), the per-pixel tables of the
+// EnvL, EnvD: written by render_setup.hip's k_cam_setup, read by the rasters, the exact paths and render_views.hip), the per-pixel tables of the
 // shared camera (PixTab, SampTab: k_pix_setup) and the dump slot of the masked frame stores.  Plain C++: it compiles on the host as
 // scene_tables.h, raster_map.h and observe_plan.h do, and tests/test_render_records_host.py holds the sizes and offsets to numbers.
 // The kernels read several of these as 16-byte pieces or as one scalar load: no size, alignment or offset may change without them.

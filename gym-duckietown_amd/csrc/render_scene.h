@@ -1,8 +1,8 @@
-// render_scene.h -- the scene as one camera ray sees it: what the render pass (render.hip) and the kernels that read what a pass leaves
+// render_scene.h -- the scene as one camera ray sees it: what the render pass (render_setup.hip, the rasters, render_exact.hip) and the kernels that read what a pass leaves
 // behind (render_views.hip) both use, so that an overlay, a depth or a label is decided by the frame's own code.  On the per-env camera record (EnvCam, render_records.h):
 // the planes and their ownership test (classify), the z-buffer test of one projected mesh triangle (test_tri), and the two GL rules every
 // per-sample path must agree on: the MSAA sample positions (MSAA_POS) and the source-pixel centre of an NDC point (src_px).
-// A device header with internal linkage: each unit compiles its own copy with its own flags (both with render.hip's, build.py).
+// A device header with internal linkage: each unit compiles its own copy with its own flags (all with render.hip's, build.py).
 #ifndef DTSIM_RENDER_SCENE_H
 #define DTSIM_RENDER_SCENE_H
 #include "dtsim_dev.h"
@@ -15,11 +15,6 @@
 #define FAR_Z 100.0f
 #define GROUND_Y (-0.008f)   // ground quad: y=-0.8 scaled by 0.01 (simulator.py:510-526,1810)
 #define GROUND_HALF 50.0f
-
-// coverage-only part of a ScreenTri kept in LDS by k_resolve_obj; the winner's colours are fetched
-// from global memory.
-struct alignas(16) TriCov { float bx0, bx1, by0, by1; float sx[3], sy[3], iw[3]; float inv_area; int32_t index; int32_t pad; };   // == first half of ScreenTri
-static_assert(sizeof(TriCov) == 64, "TriCov is 64 bytes");
 
 namespace {
 

@@ -1,4 +1,4 @@
-// render_views.hip -- the kernels that read what a render pass (render.hip) leaves behind: its frames, its per-env camera records (EnvCam),
+// render_views.hip -- the kernels that read what a render pass (dt_launch_render, render.hip) leaves behind: its frames, its per-env camera records (EnvCam),
 // its projected mesh triangles (ScreenTri / ObjBox) and the camera table (lut).  None of them uses the raster's machinery (queues, work
 // lists, quad records, workgroup map, per-pixel tables); what they share with the pass is render_scene.h, and the unit is compiled with
 // render.hip's flags (build.py), so that classify() and test_tri are the frame's own code here.  In order: k_overlay_lines, scene_samples4
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
           const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
           cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
           if (tr.flags & 2u) {
-            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade() takes it
+            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade_msaa hands it to tile_color
             float x, y;
             tile_texel_xy(tr, fx, fz, x, y);
             const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);

@@ -395,7 +395,7 @@ int dtsim_set_segment_assets(dtsim_t* h, const dtsim_texture* textures, int n_te
 enum { DTSIM_RENDER_SEGMENT = 1u, DTSIM_RENDER_GL_FILTER = 2u };
 /* dtsim_render with flags (DTSIM_RENDER_*); dtsim_render(h) == dtsim_render_ex(h, 0).
  * DTSIM_RENDER_GL_FILTER (ABI v11): this pass filters tile textures with the arithmetic of the reference's renderer -- Mesa llvmpipe's 8-bit
- * GL_LINEAR: two lerps with an 8-bit intermediate (csrc/render.hip gl_linear_rgb) -- instead of the quad-record kernels' one-pass byte-weight
+ * GL_LINEAR: two lerps with an 8-bit intermediate (csrc/raster_common.h gl_linear_rgb) -- instead of the quad-record kernels' one-pass byte-weight
  * filter: the generic raster runs, 2 - 4 x slower, and the frames are bit-identical to the reference's on 99.2 - 99.96 % of the pixels instead of
  * within +-1/255 on all but 0.25 % (tests/test_gpu_gl_golden.py).  For validation against reference frames, not for throughput. */
 int dtsim_render_ex(dtsim_t* h, uint32_t flags);

@@ -2,7 +2,7 @@
 layout of a large batch, the host statement of the key with the check of an order against it, and a restatement of the quad-record
 rasters' workgroup map.  tests/test_render_order_scenes_host.py holds all of it to its purpose on a CPU.
 
-k_env_sort (csrc/render.hip) bins env e by the tile under its camera centre (x + 0.066 cos a, z - 0.066 sin a) and its heading quadrant
+k_env_sort (csrc/render_setup.hip) bins env e by the tile under its camera centre (x + 0.066 cos a, z - 0.066 sin a) and its heading quadrant
 floor(a 2/pi + 0.5) & 3, in float32.  The bins of the first 8192 envs stay in registers between the histogram and the scatter; every env
 past them has its bin computed twice.  Only an env ON a border of the key can get two different bins from two evaluations, so the states
 here come in two kinds: border states, which sit within a float32 ulp of a border, and clear states, which keep the distance CLEAR_POS /

@@ -36,7 +36,7 @@ def test_c3_full_size_batch_matches_oracle_directly():
     sim.render()
     sim.sync()
     pos, ang = sim.read(_ffi.FIELD_POS), sim.read(_ffi.FIELD_ANGLE)
-    # the sort key of k_env_sort (render.hip): tile under the camera centre and heading quadrant
+    # the sort key of k_env_sort (render_setup.hip): tile under the camera centre and heading quadrant
     ts = 0.585
     cx, cz = pos[:, 0] + 0.066 * np.cos(ang), pos[:, 2] - 0.066 * np.sin(ang)
     ti, tj = np.clip(np.floor(cx / ts), 0, 31).astype(int), np.clip(np.floor(cz / ts), 0, 31).astype(int)

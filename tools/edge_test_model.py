@@ -2,7 +2,7 @@
 pixels the raster QUEUES for the exact path under its shipped test and under candidate tests, against the pixels that truly
 need it (their four MSAA samples do not all see one primitive).  Prices a change of the test before it is built.
 
-Shipped test (render_v3.inc `fastm`, render.hip k_pix_setup / pix_inv): record meta k = cells to the nearest tile boundary
+Shipped test (render_v3.hip `fastm`, render_setup.hip k_pix_setup / raster_common.h pix_inv): record meta k = cells to the nearest tile boundary
 (min over both axes, per CELL) > floor(reach + 0.5), reach = a CIRCLE (radius = the larger sample displacement, + 5 %) in cells.
 
 Candidates:
