@@ -748,9 +748,10 @@ int dtsim_draw_leds(dtsim_t* h, const float* spheres, const int32_t* env_idx, in
 
 // The checks dtsim_depth, dtsim_labels and their masked forms share: the arguments (flags: only the bits of `allowed`), then the state -- a
 // colour pass of the current state whose cameras and projected triangles the post-pass reads.  masked: the masked form (its device mask must be given).
+// Per-env distortion tables: refused unless the caller asked for them with DTSIM_MAP_ENV_TABLES (every entry point allows that bit).
 static int map_pass_check(dtsim_t* h, const char* who, const void* out, int oh, int ow, uint32_t flags, uint32_t allowed, bool masked, const uint8_t* mask) {
   if (!h || !out || (masked && !mask)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
-  if (flags & ~allowed) return fail(DTSIM_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+  if (flags & ~(allowed | (uint32_t)DTSIM_MAP_ENV_TABLES)) return fail(DTSIM_E_INVALID, "%s: unknown flags 0x%x", who, flags);
   const int W = h->cfg.cam_width, H = h->cfg.cam_height;
   if (oh <= 0 || ow <= 0 || H % oh || W % ow)
     return fail(DTSIM_E_INVALID, "%s: a %d x %d map of %d x %d frames (the map is point-sampled: each size must divide the camera's)", who, ow, oh, W, H);
@@ -760,8 +761,17 @@ static int map_pass_check(dtsim_t* h, const char* who, const void* out, int oh, 
     return fail(DTSIM_E_STATE, "%s needs a preceding dtsim_render (colour view) of the current state: it reads that pass's cameras and projected triangles", who);
   // the masked pass of the quad-record pipelines writes neither the camera (k_cam_setup) nor the triangles (k_obj_setup) of an unselected env
   if (h->masked && !masked) return fail(DTSIM_E_STATE, "%s after dtsim_render_masked: only the masked form, with the pass's mask", who);
-  if (h->n_cal) return fail(DTSIM_E_STATE, "%s with per-env distortion tables installed (it reads the single table)", who);
+  if (h->n_cal && !(flags & DTSIM_MAP_ENV_TABLES))
+    return fail(DTSIM_E_STATE, "%s with per-env distortion tables installed (without DTSIM_MAP_ENV_TABLES it reads the single table)", who);
   return DTSIM_OK;
+}
+
+// The per-env tables a camera post-pass reads: the installed ones when the call asked for them (DTSIM_MAP_ENV_TABLES), else none -- the flag
+// without installed tables changes nothing.
+struct EnvTables { const int32_t *src, *env_cal; int n; };
+static EnvTables env_tables(const dtsim* h, uint32_t flags) {
+  if (!(flags & DTSIM_MAP_ENV_TABLES) || !h->n_cal) return EnvTables{nullptr, nullptr, 0};
+  return EnvTables{h->d_cal_src.get(), h->d_env_cal.get(), h->n_cal};
 }
 
 // The shared body of the camera post-passes -- dtsim_depth, dtsim_labels, dtsim_instances and their masked forms: map_pass_check with `out`,
@@ -780,37 +790,44 @@ static int map_pass_run(dtsim_t* h, const char* who, const void* out, int oh, in
 }
 }  // extern "C++"
 
+static void depth_launch(const dtsim* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  const EnvTables t = env_tables(h, flags);
+  dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask, t.src, t.env_cal, t.n);
+}
+
 int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags) {
   return map_pass_run(h, "dtsim_depth", out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, false, nullptr, nullptr,
-                      [=] { dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, nullptr); });
+                      [=] { depth_launch(h, out, oh, ow, flags, nullptr); });
 }
 int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
   return map_pass_run(h, "dtsim_depth_masked", out, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, true, mask, nullptr,
-                      [=] { dt_launch_depth(h->stream, h->last_R, out, oh, ow, (flags & DTSIM_DEPTH_F16) != 0, mask); });
+                      [=] { depth_launch(h, out, oh, ow, flags, mask); });
 }
 
 // (one kernel classifies for dtsim_labels and dtsim_instances: it fills whichever of the two maps is given)
-static void labels_launch(const dtsim* h, uint8_t* labels, uint8_t* inst, int oh, int ow, const uint8_t* mask) {
-  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, labels, inst, oh, ow, mask);
+static void labels_launch(const dtsim* h, uint8_t* labels, uint8_t* inst, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  const EnvTables t = env_tables(h, flags);
+  dt_launch_labels(h->stream, h->last_R, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, labels, inst, oh, ow, mask, t.src, t.env_cal,
+                   t.n);
 }
 
 int dtsim_labels(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags) {
   return map_pass_run(h, "dtsim_labels", out, oh, ow, flags, 0u, false, nullptr, "before dtsim_set_label_assets",
-                      [=] { labels_launch(h, out, nullptr, oh, ow, nullptr); });
+                      [=] { labels_launch(h, out, nullptr, oh, ow, flags, nullptr); });
 }
 int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
   return map_pass_run(h, "dtsim_labels_masked", out, oh, ow, flags, 0u, true, mask, "before dtsim_set_label_assets",
-                      [=] { labels_launch(h, out, nullptr, oh, ow, mask); });
+                      [=] { labels_launch(h, out, nullptr, oh, ow, flags, mask); });
 }
 
 // (the label tables only when a label map is asked for too)
 int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags) {
   return map_pass_run(h, "dtsim_instances", inst, oh, ow, flags, 0u, false, nullptr, labels ? "with a label map before dtsim_set_label_assets" : nullptr,
-                      [=] { labels_launch(h, labels, inst, oh, ow, nullptr); });
+                      [=] { labels_launch(h, labels, inst, oh, ow, flags, nullptr); });
 }
 int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, const uint8_t* mask) {
   return map_pass_run(h, "dtsim_instances_masked", inst, oh, ow, flags, 0u, true, mask, labels ? "with a label map before dtsim_set_label_assets" : nullptr,
-                      [=] { labels_launch(h, labels, inst, oh, ow, mask); });
+                      [=] { labels_launch(h, labels, inst, oh, ow, flags, mask); });
 }
 
 int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask) {

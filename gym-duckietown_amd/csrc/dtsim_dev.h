@@ -182,13 +182,17 @@ void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d
 // the depth maps of dtsim_depth (render_views.hip k_depth): out = [N][oh][ow] float32 (f16: half), output pixel (i, j) = camera pixel
 // (i * (H / oh) + H / oh / 2, j * (W / ow) + W / ow / 2); R = the last render pass's parameters; mask (device, [N] bytes, or null = every
 // env): the rows of the other envs are not written.  The caller checked that oh divides H and ow divides W.
-void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask);
+// cal_src / env_cal / n_cal: the per-env distortion tables of dtsim_set_distortion_luts (device; dt_launch_remap_cal's) -- env e's pixel then
+// takes the entry R.lut (the identity table of the rectilinear pass) holds at cal_src[env_cal[e]][camera pixel], none where that is -1.  Null
+// pointers: the single table R.lut, the kernels without the per-env path.
+void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask, const int32_t* cal_src,
+                     const int32_t* env_cal, int n_cal);
 // the label maps of dtsim_labels (render_views.hip k_labels): out = [N][oh][ow] bytes, sized, sampled and masked as dt_launch_depth's; texel_class:
 // one byte per texel in the layout of R.texels (dt_pack_label_tables), mesh_class: [n_mesh_class] bytes.  inst: the instance map of
 // dtsim_instances, same shape, written in the same launch from the same classification.  Either of out / inst may be null (the tables are
-// read only with out); they must not overlap.
+// read only with out); they must not overlap.  cal_src / env_cal / n_cal: as dt_launch_depth's.
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
-                      uint8_t* inst, int oh, int ow, const uint8_t* mask);
+                      uint8_t* inst, int oh, int ow, const uint8_t* mask, const int32_t* cal_src, const int32_t* env_cal, int n_cal);
 // the bird's-eye maps of dtsim_bev (render_views.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
 // rows_behind of the oh rows behind the agent.  Of R only the scene of render_scene is read (maps, tile_recs, n_tile_recs, objs, tex_w, tex_h, n_maps) and
 // N: no camera, no table of a pass.  ocorners: dt_pack_object_corners' table; texel_class / mesh_class as dt_launch_labels' (read only with

@@ -24,6 +24,18 @@ __device__ inline ViewPix view_pixel(const float4* __restrict__ lut, const size_
 // chunk, and that loop is ONE copy of its body in every kernel (unroll(disable); why: at k_depth).
 #define DEPTH_ENVS DT_ENVS_PER_BLOCK
 static inline dim3 view_grid(const int cells, const int N) { return dim3((unsigned)((cells + 255) / 256), (unsigned)((N + DEPTH_ENVS - 1) / DEPTH_ENVS)); }
+// Per-env distortion tables (dtsim_set_distortion_luts; k_depth / k_labels with CAL): the table entry of camera pixel `at` for env e is the
+// IDENTITY table's entry at s = cal_src[env_cal[e]][at] -- the rectilinear pixel whose colour k_remap_cal put at frames[e][at], read rather than
+// recomputed so that its bits are the rectilinear pass's own -- and a dead entry (z = 0) where s = -1 or the thread owns no pixel.  env_cal[e]
+// is wave-uniform; the calibration and s are clamped to their tables (the install checked both: the clamps only keep a caller's stale pointer
+// from reading outside them on a device others share).
+__device__ inline float4 cal_entry(const float4* __restrict__ lut, const int32_t* __restrict__ cal_src, const int32_t* __restrict__ env_cal,
+                                   const int n_cal, const int e, const bool in, const size_t at, const int W, const int H) {
+  if (!in) return make_float4(0.f, 0.f, 0.f, 0.f);
+  const size_t hw = (size_t)W * (size_t)H;
+  const int s = cal_src[(size_t)min((unsigned)env_cal[e], (unsigned)(n_cal - 1)) * hw + at];
+  return (unsigned)s < (unsigned)hw ? lut[s] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
 
 // ---- k_overlay_lines: the reference's GL_LINE overlays as a post-pass on the resolved frames --------------------------------------
 // draw_curve (simulator.py:1886-1904, graphics.py:336-349: the lane curves of every drivable tile, 19 segments each, the one most aligned
@@ -282,24 +294,41 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
 // offsets) does not depend on the env.  That the compiler keeps one copy is its choice, not a property of this source: the guarantee rests on
 // tests/test_gpu_depth.py::test_env_positions_and_the_tail_chunk_give_the_same_bytes (envs e, e + 64, e + 128 of one state, a second call, a
 // second render: byte-identical), which fails if a peeled or versioned copy ever rounds differently.
-template <bool F16>
+// CAL (dtsim_set_distortion_luts' tables installed and DTSIM_MAP_ENV_TABLES given; cal_src / env_cal / n_cal are read only then): the same grid,
+// thread and loop, but the pixel's entry is the ENV's -- cal_entry() above -- and is taken inside the loop body, still one copy of it
+// (tests/test_gpu_camera_rand_maps.py holds envs e, e + 64, e + 70 of one state and table to the same bytes).  scene_depth4 is called as
+// without CAL.  CAL = false keeps the instructions it had before the parameter (tools/isa_compare.py; profiles/render_views_isa.txt).
+template <bool F16, bool CAL = false>
 __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
                                                const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                               void* __restrict__ out, const uint8_t* __restrict__ mask) {
+                                               void* __restrict__ out, const uint8_t* __restrict__ mask, const int32_t* __restrict__ cal_src,
+                                               const int32_t* __restrict__ env_cal, const int n_cal) {
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
   const int sy = H / oh, sx = W / ow;
   ViewPix p = NO_PIX;
+  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
   if (in) {
     const int i = pix / ow, j = pix - i * ow;
-    p = view_pixel(lut, (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2), W, H);
+    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
+    if constexpr (!CAL) p = view_pixel(lut, at, W, H);
   }
   const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+  // CAL: the entry depends on the env -- env_cal[e], then the calibration's source index, then the identity table's entry there: three
+  // dependent loads.  The NEXT env's chain is issued at the top of the body and waited for at the top of the next one, behind this env's scene.
+  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
+    if constexpr (CAL) {
+      const float4 l = l_nxt;
+      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
+      p.live = l.z != 0.f; p.nx = l.x; p.ny = l.y;
+      src_px(l.x, l.y, W, H, p.sxp, p.syp);
+    }
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
     const EnvCam c = cams[e];
     // (calling the masked form with another mask than the pass's is the caller's error -- include/dtsim.h -- and its result is undefined: the
@@ -315,9 +344,9 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
       d = fminf(fminf(ds[0], ds[1]), fminf(ds[2], ds[3]));
     }
     if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if (F16) static_cast<__half*>(out)[at] = __float2half_rn(d);
-      else static_cast<float*>(out)[at] = d;
+      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      if (F16) static_cast<__half*>(out)[to] = __float2half_rn(d);
+      else static_cast<float*>(out)[to] = d;
     }
   }
 }
@@ -339,14 +368,16 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
 // scene_samples4<true>: the env's map's object list), DTSIM_INSTANCE_NONE for every other owner and for a pixel without a source; a second
 // byte store at the same offset, as coalesced as the first.  Without LAB the class mapping -- mesh table, tile record, texel gather -- is not
 // compiled, and the plane hits it alone reads are dead.
+// CAL: k_depth's, word for word -- the env's own table entry, taken inside the one loop body; scene_samples4<true> is called as without it.
 static_assert(DTSIM_MAX_OBJECTS <= 255, "an instance id o + 1 must fit the map's byte");
-template <bool LAB, bool INST>
+template <bool LAB, bool INST, bool CAL = false>
 __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                 const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
                                                 const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
                                                 const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h,
                                                 const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                                uint8_t* __restrict__ out, uint8_t* __restrict__ inst, const uint8_t* __restrict__ mask) {
+                                                uint8_t* __restrict__ out, uint8_t* __restrict__ inst, const uint8_t* __restrict__ mask,
+                                                const int32_t* __restrict__ cal_src, const int32_t* __restrict__ env_cal, const int n_cal) {
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
@@ -355,17 +386,30 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
   const int sy = H / oh, sx = W / ow;
   float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
   bool live = false;
+  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
   if (in) {
     const int i = pix / ow, j = pix - i * ow;
-    const float4 l = lut[(size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2)];
-    live = l.z != 0.f;
-    nx = l.x; ny = l.y;
-    sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;       // centre of the source pixel
+    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
+    if constexpr (!CAL) {
+      const float4 l = lut[at];
+      live = l.z != 0.f;
+      nx = l.x; ny = l.y;
+      sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;     // centre of the source pixel
+    }
   }
   const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);      // CAL: the env's own entry, the next env's chain of loads in flight (as k_depth's)
+  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
+    if constexpr (CAL) {
+      const float4 l = l_nxt;
+      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
+      live = l.z != 0.f;
+      nx = l.x; ny = l.y;
+      src_px(l.x, l.y, W, H, sxp, syp);
+    }
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
     const EnvCam c = cams[e];
     const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
@@ -404,9 +448,9 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
       }
     }
     if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if constexpr (LAB) out[at] = (uint8_t)cls;
-      if constexpr (INST) inst[at] = (uint8_t)who;
+      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      if constexpr (LAB) out[to] = (uint8_t)cls;
+      if constexpr (INST) inst[to] = (uint8_t)who;
     }
   }
 }
@@ -564,9 +608,9 @@ __global__ __launch_bounds__(256) void k_bev(const double* __restrict__ pos_x, c
       }
     }
     if (in) {
-      const size_t at = (size_t)e * (size_t)n_out + (size_t)pix;
-      if constexpr (LAB) out[at] = (uint8_t)cls;
-      if constexpr (INST) inst[at] = (uint8_t)who;
+      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      if constexpr (LAB) out[to] = (uint8_t)cls;
+      if constexpr (INST) inst[to] = (uint8_t)who;
     }
   }
 }
@@ -748,26 +792,30 @@ void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d
   hipLaunchKernelGGL(k_overlay_leds, dim3((unsigned)((R.W * R.H + 255) / 256)), dim3(256), 0, s, R, R.envcam, d_spheres, first, count, env);
 }
 
-void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask) {
+void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask, const int32_t* cal_src,
+                     const int32_t* env_cal, int n_cal) {
   if (R.N <= 0) return;
   const dim3 grid = view_grid(oh * ow, R.N);
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-#define LAUNCH_DEPTH(F16_) hipLaunchKernelGGL(k_depth<F16_>, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, \
-                                              reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.max_tris,    \
-                                              R.n_maps, R.N, R.W, R.H, oh, ow, out, mask)
-  if (f16) LAUNCH_DEPTH(true); else LAUNCH_DEPTH(false);
-#undef LAUNCH_DEPTH
+  const bool cal = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations
+  auto k = cal ? (f16 ? k_depth<true, true> : k_depth<false, true>) : (f16 ? k_depth<true> : k_depth<false>);
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr,
+                     obj ? R.stris : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, mask, cal ? cal_src : nullptr, cal ? env_cal : nullptr,
+                     cal ? n_cal : 0);
 }
 
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
-                      uint8_t* inst, int oh, int ow, const uint8_t* mask) {
+                      uint8_t* inst, int oh, int ow, const uint8_t* mask, const int32_t* cal_src, const int32_t* env_cal, int n_cal) {
   if (R.N <= 0 || (!out && !inst)) return;
   const dim3 grid = view_grid(oh * ow, R.N);
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  auto k = out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>;
+  const bool cal = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations
+  auto k = cal ? (out && inst ? k_labels<true, true, true> : out ? k_labels<true, false, true> : k_labels<false, true, true>)
+               : (out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>);
   hipLaunchKernelGGL(k, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs,
                      reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
-                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask);
+                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask, cal ? cal_src : nullptr,
+                     cal ? env_cal : nullptr, cal ? n_cal : 0);
 }
 
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,

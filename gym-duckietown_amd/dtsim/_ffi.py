@@ -38,6 +38,7 @@ OBS_HWC, OBS_CHW, OBS_F32 = 0, 1, 2
 OBS_GRAY, OBS_MAX_DEPTH = 4, 16                # dtsim_obs_push: grey stack slots / the deepest stack
 BLEND_MAX = 8                                 # dtsim_blend_frames: the most frame batches in one blend
 DEPTH_F16 = 1                                 # dtsim_depth flag: IEEE half instead of float32
+MAP_ENV_TABLES = 0x100                        # dtsim_depth / dtsim_labels / dtsim_instances flag: the env's own distortion table, if installed
 # dtsim_labels: the class ids the device itself writes (0 .. 2), the host's default tile classes (dtsim/labels.py), the first object id
 LABEL_NONE, LABEL_SKY, LABEL_GROUND, LABEL_FLOOR, LABEL_ROAD, LABEL_MARK_WHITE, LABEL_MARK_YELLOW, LABEL_MARK_RED, LABEL_OBJECT_FIRST = range(9)
 INSTANCE_NONE = 0                             # dtsim_instances: no mesh object owns the pixel (object o is o + 1)

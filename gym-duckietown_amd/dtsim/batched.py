@@ -568,6 +568,11 @@ class BatchedSimulator:
         """fn(handle, *args), or with a mask fn_masked(handle, *args, mask): a pass whose masked form takes the mask last."""
         _ffi.check(self._lib, fn(self._h, *args) if mp is None else fn_masked(self._h, *args, mp))
 
+    def _env_tables_flag(self) -> int:
+        """DTSIM_MAP_ENV_TABLES exactly while per-env calibrations are active (camera_rand, set_camera_calibrations): depth(), labels() and
+        instances() then read each env's own distortion table.  0 in every other configuration: its calls stay as they are."""
+        return _ffi.MAP_ENV_TABLES if self._cal is not None and not self._skip_distort else 0
+
     def render(self, segment: bool = False, gl_filter: bool = False, mask=None):
         """render_obs() of every env into the frame batch; `segment=True` is the reference's segmentation render
         (simulator.py:1730-1737,1753,1808,1879).  `gl_filter=True` (DTSIM_RENDER_GL_FILTER): tile textures filtered with the arithmetic of the
@@ -760,6 +765,8 @@ class BatchedSimulator:
         """The depth map of every env's camera frame, on the device (dtsim_depth, include/dtsim.h): [N, h, w], per pixel the smallest eye depth
         (distance along the optical axis) of the nearest opaque surface -- tiles, ground, mesh objects -- over the four MSAA samples of the
         frame's source pixel; +inf where all four see the sky, 0 in the fisheye's black border.  Needs a preceding render() of the current state.
+        With per-env calibrations (camera_rand, set_camera_calibrations) the source pixel is the one the env's OWN table names -- the surface
+        whose colour the frame shows there --, and so it is for labels() and instances().
         Default size: the camera's; a smaller (h, w) must divide it and is the slice full[:, sy // 2::sy, sx // 2::sx] (sy = H // h, sx = W // w),
         of which only those pixels are traced.  dtype "float32" or "float16".  `out` may be any C-contiguous object with
         __cuda_array_interface__ of that shape and dtype; `mask` as render()'s (after render(mask=m) pass the same m): only the selected envs'
@@ -769,7 +776,7 @@ class BatchedSimulator:
         h, w = self._map_size("depth", "depth is", height, width)
         mp = self._mask_arg(mask)
         out, ptr = self._result("depth", out, (self.num_envs, h, w), dtype)
-        flags = _ffi.DEPTH_F16 if dtype == "float16" else 0
+        flags = (_ffi.DEPTH_F16 if dtype == "float16" else 0) | self._env_tables_flag()
         self._map_pass(self._lib.dtsim_depth, self._lib.dtsim_depth_masked, mp, ptr, h, w, flags)
         return out
 
@@ -823,7 +830,7 @@ class BatchedSimulator:
         mp = self._mask_arg(mask)
         out, ptr = self._result("labels", out, (self.num_envs, h, w))
         self._need_label_assets()
-        self._map_pass(self._lib.dtsim_labels, self._lib.dtsim_labels_masked, mp, ptr, h, w, 0)
+        self._map_pass(self._lib.dtsim_labels, self._lib.dtsim_labels_masked, mp, ptr, h, w, self._env_tables_flag())
         return out
 
     def instances(self, height=None, width=None, out=None, mask=None, labels_out=None):
@@ -844,7 +851,7 @@ class BatchedSimulator:
             if lp.value == ptr.value:
                 raise ValueError("instances: labels_out and out are one buffer")
             self._need_label_assets()
-        self._map_pass(self._lib.dtsim_instances, self._lib.dtsim_instances_masked, mp, ptr, lp, h, w, 0)
+        self._map_pass(self._lib.dtsim_instances, self._lib.dtsim_instances_masked, mp, ptr, lp, h, w, self._env_tables_flag())
         return out
 
     def boxes(self, inst, out=None, mask=None):

@@ -55,8 +55,10 @@ in the order depth, labels, instances, boxes, bev, ipm, masked where the observe
 `dtsim_copy_rows` of each -> `dtsim_reset_done` -> masked render -> masked observe -> masked passes.  They compose with one another and with
 `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand` (no output is ever stacked).  Depth, labels, instances and boxes are CAMERA
 post-passes: point-sampled from the frame's source pixels, never filtered, so each size of their `(h, w)` must divide the camera's; and they
-read the single distortion table and one rendered state, so `motion_blur` (its observation shows the states of its window) and
-`camera_rand` (a distortion table per env) raise ValueError.
+read one rendered state, so `motion_blur` (its observation shows the states of its window) raises ValueError.  Under `camera_rand` (a
+distortion table per env) they are opt-in, `camera_rand_maps=True`: every env's maps then go through its OWN table (`DTSIM_MAP_ENV_TABLES`,
+include/dtsim.h), pixel-aligned with its frame, and everything above composes as without `camera_rand`; without the option the combination
+keeps raising ValueError, as it always has.  (Still out of scope there: the line and LED overlays, and the N = 1 gym facade.)
 
 Depth (`depth_shape=(h, w)`; `depth_dtype` "float32" or "float16"): `info["depth"]` is the `[N, h, w]` depth map (`dtsim_depth`,
 include/dtsim.h: smallest eye depth over the four MSAA samples of the frame's source pixel, +inf = sky, 0 = the fisheye's black border).
@@ -105,8 +107,8 @@ class _Aux(NamedTuple):
     name: str                       # env.<name> and info["<name>"]; the finished envs' rows: info["final_<name>"]
     dtype: str                      # torch's name of the element type
     tail: Optional[Tuple[int, ...]]  # the shape after N; None: the output is off
-    camera: bool                    # a camera post-pass: it reads the single distortion table and ONE rendered state, so its option went
-    #                                 through _camera_map_shape (no motion_blur, no camera_rand, a size that divides the camera's)
+    camera: bool                    # a camera post-pass: it reads the distortion table(s) and ONE rendered state, so its option went
+    #                                 through _camera_map_shape (no motion_blur, camera_rand only with camera_rand_maps, a size that divides the camera's)
 
 
 class DuckietownVecEnv:
@@ -118,7 +120,7 @@ class DuckietownVecEnv:
                  instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False,
                  bev_shape: Optional[Tuple[int, int]] = None, bev_cell: float = 0.02, bev_rows_behind: int = 0,
                  bev_instances: bool = False, ipm_shape: Optional[Tuple[int, int]] = None, ipm_cell: float = 0.02,
-                 ipm_rows_behind: int = 0, ipm_valid: bool = False, **sim_kwargs):
+                 ipm_rows_behind: int = 0, ipm_valid: bool = False, camera_rand_maps: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -133,11 +135,12 @@ class DuckietownVecEnv:
             raise ValueError(f"depth_dtype {depth_dtype!r}: 'float32' or 'float16'")
         self.depth_dtype = depth_dtype
         cam = (int(sim_kwargs.get("camera_height", 480)), int(sim_kwargs.get("camera_width", 640)))
-        self.depth_shape = self._camera_map_shape("depth_shape", depth_shape, cam, sim_kwargs)
-        self.label_shape = self._camera_map_shape("label_shape", label_shape, cam, sim_kwargs)
+        self._per_env_tables_refused = bool(sim_kwargs.get("camera_rand")) and not camera_rand_maps
+        self.depth_shape = self._camera_map_shape("depth_shape", depth_shape, cam)
+        self.label_shape = self._camera_map_shape("label_shape", label_shape, cam)
         if boxes and instance_shape is None:
             raise ValueError("boxes=True needs instance_shape (the boxes are those of the instance map, in its pixels)")
-        self.instance_shape = self._camera_map_shape("instance_shape", instance_shape, cam, sim_kwargs)
+        self.instance_shape = self._camera_map_shape("instance_shape", instance_shape, cam)
         self.bev_shape, self.bev_cell, self.bev_rows_behind = None, bev_cell, bev_rows_behind
         if bev_shape is None:
             if bev_instances:
@@ -239,15 +242,16 @@ class DuckietownVecEnv:
             self._ring = [torch.empty_like(self._frames) for _ in self._blur]     # slot _cur holds the frame of the current state
             self._cur = 0
 
-    def _camera_map_shape(self, option, shape, cam, sim_kwargs):
+    def _camera_map_shape(self, option, shape, cam):
         """The (h, w) of a camera post-pass's option (None: off), or the ValueError that names the option and the cause."""
         if shape is None:
             return None
         cause = None
         if self._blur:
             cause = "with motion_blur is not supported (the blurred observation shows the states of its window: no single state's map belongs to it)"
-        elif sim_kwargs.get("camera_rand"):
-            cause = "with camera_rand is not supported (the pass reads the single distortion table, camera_rand installs one per env)"
+        elif self._per_env_tables_refused:
+            cause = ("with camera_rand needs camera_rand_maps=True (camera_rand installs a distortion table per env; with the option the pass "
+                     "reads each env's own table, without it the combination is refused as before)")
         else:
             try:
                 h, w = (int(v) for v in shape)

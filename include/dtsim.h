@@ -303,7 +303,10 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
  * cvRound of the float maps) or -1 (outside the image: black, BORDER_CONSTANT) -- and the table of each env,
  * env_cal[num_envs] in [0, n_cal).  Needs DTSIM_F_DISTORTION; not with DTSIM_F_LIGHT_CAPTURE.  While installed, the render
  * pass rasterises rectilinear frames into a scratch batch and gathers every (masked) env's frame through its table;
- * dtsim_draw_lines / dtsim_draw_leds refuse.  n_cal = 0 (tables NULL) uninstalls, and so does dtsim_set_distortion_lut,
+ * dtsim_draw_lines / dtsim_draw_leds refuse (the overlays read the single table), and so do dtsim_depth, dtsim_labels, dtsim_instances and
+ * their masked forms unless they are given DTSIM_MAP_ENV_TABLES: with it, the map of env e at camera pixel p is the pass's value at the
+ * rectilinear pixel s = src_index[env_cal[e]][p] of that env -- the surface whose colour the gather put at frames[e][p], so map and frame
+ * stay pixel-aligned -- and the no-source value (depth 0, DTSIM_LABEL_NONE, DTSIM_INSTANCE_NONE) where s = -1.  n_cal = 0 (tables NULL) uninstalls, and so does dtsim_set_distortion_lut,
  * which installs one table for every env again.  Both copy the tables: the caller's buffers are free on return.
  * DTSIM_LUTS_CAMERA_RAND: device-side resets also scale camera height, angle and fov_y by the randomizer's draws without
  * domain randomisation, and zero the camera noise then (simulator.py:611-614, 1768-1769).  Every call sets this switch from
@@ -540,14 +543,22 @@ int dtsim_blend_frames(dtsim_t* h, void* out, const void* const* frames, const u
  * STATE.  A post-pass of a render, under the rules of dtsim_draw_leds: it reads the cameras and projected triangles the last pass left, so a
  * colour dtsim_render / dtsim_render_ex (not the segment view) of the CURRENT state must precede it -- dtsim_step, dtsim_reset,
  * dtsim_reset_done, dtsim_write, dtsim_set_maps, dtsim_set_assets and dtsim_set_distortion_lut invalidate -- and per-env distortion tables
- * (dtsim_set_distortion_luts) are refused; all of these DTSIM_E_STATE.  After a full pass both entry points are valid.  After
+ * (dtsim_set_distortion_luts) are refused without DTSIM_MAP_ENV_TABLES; all of these DTSIM_E_STATE.  After a full pass both entry points are valid.  After
  * dtsim_render_masked only dtsim_depth_masked is, and it must be given the mask the pass was given: on the quad-record pipelines both the
  * camera and the triangle set-up of the pass skip the unselected envs, whose records describe an older state (the generic pipelines write
  * every env's; the rule does not depend on the pipeline).  The masked call writes the rows of the selected envs only; the other rows keep
  * every byte.  One state gives the same bytes on every call, for every env index and whatever the other envs hold.
  * A null handle, out or mask, a non-positive or non-dividing size or an unknown flag return DTSIM_E_INVALID; a failed call launches
- * nothing and writes nothing.  Asynchronous, stream-ordered. */
+ * nothing and writes nothing.  Asynchronous, stream-ordered.
+ * PER-ENV TABLES.  DTSIM_MAP_ENV_TABLES, accepted by dtsim_depth, dtsim_labels, dtsim_instances and their masked forms: read each env's own
+ * distortion table if per-env tables are installed (dtsim_set_distortion_luts).  Let p = (i sy + sy / 2) cam_width + (j sx + sx / 2) and
+ * s = src_index[env_cal[e]][p].  out[e][i][j] is then the value this pass gives at RECTILINEAR camera pixel s of env e -- the source pixel is
+ * s itself, with its four MSAA samples, and every rule above applies unchanged -- and 0 where s = -1 (as in the black border).  That is the
+ * surface whose colour the render pass's gather put at frames[e][p].  Every other rule of STATE holds as it stands.  Without installed tables
+ * the flag changes nothing: the same kernel, the same bytes.  Without the flag, installed tables are refused as before.
+ * Out of scope under per-env tables: the line and LED overlays (still refused), and folding the tables into the raster. */
 enum { DTSIM_DEPTH_F16 = 1u };
+#define DTSIM_MAP_ENV_TABLES 0x100u
 int dtsim_depth(dtsim_t* h, void* out, int oh, int ow, uint32_t flags);
 int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
 /* The semantic label map of every camera frame, on the device: WHICH surface a pixel shows, as a class id beside the observation and the
@@ -569,13 +580,14 @@ int dtsim_depth_masked(dtsim_t* h, void* out, int oh, int ow, uint32_t flags, co
  * dtsim_set_label_assets say.  Ids 3 .. 7 are reserved for the default tile classes of the host (dtsim/labels.py), 8 .. 255 for objects.
  * Never filtered, never blended: an edge pixel carries the class of its nearest sample, not a mixture.
  * SIZE.  out: DEVICE pointer to [num_envs][oh][ow] bytes; size and sampling are dtsim_depth's: cam_height % oh == 0 and cam_width % ow == 0,
- * out[e][i][j] belongs to camera pixel (i sy + sy / 2, j sx + sx / 2), and only those pixels are traced.  flags must be 0.
+ * out[e][i][j] belongs to camera pixel (i sy + sy / 2, j sx + sx / 2), and only those pixels are traced.  flags: 0 or DTSIM_MAP_ENV_TABLES
+ * (dtsim_depth's PER-ENV TABLES: the class at rectilinear pixel s of the env's own table, DTSIM_LABEL_NONE where s = -1).
  * TABLES.  dtsim_set_label_assets: texel_class[t] is [height][width] bytes in the row order and size of texture t of dtsim_set_assets,
  * mesh_class is [n_meshes]; both counts must mirror dtsim_set_assets (else DTSIM_E_INVALID), host pointers, copied during the call.  A
  * failed call changes nothing; dtsim_set_assets drops the tables (the list they mirror is gone).
  * STATE.  The rules of dtsim_depth, word for word (a colour render of the current state, the same calls invalidate, after
- * dtsim_render_masked only the masked form with the pass's mask, per-env distortion tables refused), and DTSIM_E_STATE without label
- * tables.  A null handle, out or mask, a bad size or a nonzero flag return DTSIM_E_INVALID; a failed call launches nothing and writes
+ * dtsim_render_masked only the masked form with the pass's mask, per-env distortion tables refused without DTSIM_MAP_ENV_TABLES), and
+ * DTSIM_E_STATE without label tables.  A null handle, out or mask, a bad size or an unknown flag return DTSIM_E_INVALID; a failed call launches nothing and writes
  * nothing.  Asynchronous, stream-ordered.  One state gives the same bytes on every call and for every env index. */
 enum { DTSIM_LABEL_NONE = 0, DTSIM_LABEL_SKY = 1, DTSIM_LABEL_GROUND = 2,
        DTSIM_LABEL_FLOOR = 3,        /* a non-drivable tile */
@@ -601,7 +613,9 @@ int dtsim_labels_masked(dtsim_t* h, uint8_t* out, int oh, int ow, uint32_t flags
  * SIZE, STATE.  dtsim_depth's, word for word: [num_envs][oh][ow] bytes, cam_height % oh == 0 and cam_width % ow == 0, point-sampled at
  * camera pixel (i sy + sy / 2, j sx + sx / 2); a colour render of the current state must precede, the same calls invalidate, after
  * dtsim_render_masked only the masked form with the pass's mask (it writes the selected envs' rows only), per-env distortion tables are
- * refused.  flags must be 0.  A null handle, inst or mask, a bad size or a nonzero flag return DTSIM_E_INVALID; a failed call launches
+ * refused without DTSIM_MAP_ENV_TABLES.  flags: 0 or DTSIM_MAP_ENV_TABLES (dtsim_depth's PER-ENV TABLES: the owner at rectilinear pixel s of
+ * the env's own table, DTSIM_INSTANCE_NONE where s = -1; `labels` likewise).  A null handle, inst or mask, a bad size or an unknown flag
+ * return DTSIM_E_INVALID; a failed call launches
  * nothing and writes nothing.  Asynchronous, stream-ordered.  One state gives the same bytes on every call and for every env index. */
 enum { DTSIM_INSTANCE_NONE = 0 };
 int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags);
