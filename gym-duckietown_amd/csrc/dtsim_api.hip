@@ -187,6 +187,11 @@ struct dtsim {
   DevPtr<int32_t> d_ipm_table;      // [DTSIM_BEV_MAX_SIDE^2]: allocated at the first use and never moved, so a rebuild is stream-ordered
   struct IpmKey { int oh = 0, ow = 0, rows_behind = 0; double cell = 0.0; uint64_t cal = 0; } ipm_key;   // cal = 0: no table yet
   uint64_t ipm_cal_version = 1;     // counts the installs: a new calibration is a new key
+  // dtsim_flow: the remembered states of dtsim_flow_mark and the per-env records of a call, both [N], allocated at the first use and never
+  // moved; neither is part of SimArrays or the state slab.  lut_fisheye: the single distortion table is not the identity.
+  DevPtr<FlowMark> d_flow_mark;
+  DevPtr<FlowRec> d_flow_rec;
+  bool lut_fisheye = false;
   ProfSlot prof[DTSIM_KERNEL__COUNT];
 };
 
@@ -348,6 +353,11 @@ void dtsim_destroy(dtsim_t* h) {
   delete h;   // frees every device buffer the handle owns
 }
 
+// dtsim_set_maps / dtsim_set_assets, once they have succeeded: no env has a mark (stream-ordered, like the marks themselves)
+static void drop_flow_marks(dtsim_t* h) {
+  if (h->d_flow_mark) (void)hipMemsetAsync(h->d_flow_mark.get(), 0, sizeof(FlowMark) * (size_t)h->N, h->stream);
+}
+
 int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, const dtsim_mesh* meshes,
                      int n_meshes) {
   if (!h) return fail(DTSIM_E_INVALID, "null handle");
@@ -367,6 +377,7 @@ int dtsim_set_assets(dtsim_t* h, const dtsim_texture* textures, int n_textures, 
   h->maps.release_render();       // the installed maps' render tables index the old lists: the render entry points wait for dtsim_set_maps
   h->d_texels_seg.reset();        // mirrors the old list
   h->d_texel_class.reset(); h->d_mesh_class.reset(); h->n_mesh_class = 0;   // so do the label tables
+  drop_flow_marks(h);
   return DTSIM_OK;
 }
 
@@ -432,6 +443,7 @@ int dtsim_set_maps(dtsim_t* h, const dtsim_map* maps, int n_maps) {
   h->maps = std::move(next);
   h->have_maps = true;
   h->have_reset = false;
+  drop_flow_marks(h);
   return DTSIM_OK;
 }
 
@@ -456,6 +468,7 @@ int dtsim_set_distortion_lut(dtsim_t* h, const float* rmapx, const float* rmapy)
   HIPCHK(dev_upload(h->d_lut, lut.data(), lut.size()));
   drop_luts(h);
   h->have_lut = true;
+  h->lut_fisheye = rmapx != nullptr;
   return DTSIM_OK;
 }
 
@@ -828,6 +841,51 @@ int dtsim_instances(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, 
 int dtsim_instances_masked(dtsim_t* h, uint8_t* inst, uint8_t* labels, int oh, int ow, uint32_t flags, const uint8_t* mask) {
   return map_pass_run(h, "dtsim_instances_masked", inst, oh, ow, flags, 0u, true, mask, labels ? "with a label map before dtsim_set_label_assets" : nullptr,
                       [=] { labels_launch(h, labels, inst, oh, ow, flags, mask); });
+}
+
+// The handle's FlowMark and FlowRec arrays, allocated at the first use; the marks start as "none".
+static int flow_buffers(dtsim_t* h) {
+  if (h->d_flow_mark && h->d_flow_rec) return DTSIM_OK;
+  DevPtr<FlowMark> marks;
+  DevPtr<FlowRec> recs;
+  HIPCHK(dev_alloc(marks, (size_t)h->N));
+  HIPCHK(dev_alloc(recs, (size_t)h->N));
+  HIPCHK(hipMemsetAsync(marks.get(), 0, sizeof(FlowMark) * (size_t)h->N, h->stream));
+  HIPCHK(hipMemsetAsync(recs.get(), 0, sizeof(FlowRec) * (size_t)h->N, h->stream));
+  h->d_flow_mark = std::move(marks); h->d_flow_rec = std::move(recs);
+  return DTSIM_OK;
+}
+
+int dtsim_flow_mark(dtsim_t* h, const uint8_t* mask) {
+  if (!h) return fail(DTSIM_E_INVALID, "dtsim_flow_mark: null handle");
+  if (!h->have_maps || !h->have_reset) return fail(DTSIM_E_STATE, "dtsim_flow_mark before dtsim_set_maps and dtsim_reset: there is no state to remember");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = flow_buffers(h)) return rc;
+  dt_launch_flow_mark(h->stream, h->A, h->d_flow_mark.get(), mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+
+// dtsim_flow and its masked form: dtsim_depth's checks (map_pass_check) with no flag allowed, then the calibration a fisheye handle needs.
+static int flow_run(dtsim_t* h, const char* who, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags, bool masked, const uint8_t* mask) {
+  if (!h || !flow || (masked && !mask)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
+  if (flags) return fail(DTSIM_E_INVALID, "%s: flags 0x%x (must be 0)", who, flags);
+  if ((const void*)flow == (const void*)valid) return fail(DTSIM_E_INVALID, "%s: flow and valid are one buffer", who);
+  if (int rc = map_pass_check(h, who, flow, oh, ow, 0u, 0u, masked, mask)) return rc;
+  if (h->lut_fisheye && h->n_ipm_cal < 1)
+    return fail(DTSIM_E_STATE, "%s on fisheye frames before dtsim_set_ipm_calibrations (the flow goes through the calibration's forward model)", who);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (int rc = flow_buffers(h)) return rc;
+  dt_launch_flow(h->stream, h->last_R, h->A, h->d_flow_mark.get(), h->d_flow_rec.get(), (h->cfg.flags & DTSIM_F_DOMAIN_RAND) != 0,
+                 h->lut_fisheye ? h->d_ipm_cal.get() : nullptr, flow, valid, oh, ow, mask);
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+int dtsim_flow(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags) {
+  return flow_run(h, "dtsim_flow", flow, valid, oh, ow, flags, false, nullptr);
+}
+int dtsim_flow_masked(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return flow_run(h, "dtsim_flow_masked", flow, valid, oh, ow, flags, true, mask);
 }
 
 int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask) {

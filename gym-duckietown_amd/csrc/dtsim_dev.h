@@ -193,6 +193,14 @@ void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, in
 // read only with out); they must not overlap.  cal_src / env_cal / n_cal: as dt_launch_depth's.
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
                       uint8_t* inst, int oh, int ow, const uint8_t* mask, const int32_t* cal_src, const int32_t* env_cal, int n_cal);
+// dtsim_flow_mark (render_views.hip k_flow_mark): the selected envs' current state into marks [N] (mask: device, [N] bytes, or null = every env).
+void dt_launch_flow_mark(hipStream_t s, const SimArrays& A, FlowMark* marks, const uint8_t* mask);
+// the flow maps of dtsim_flow (render_views.hip k_flow_setup, k_flow): flow = [N][2][oh][ow] float32, valid = [N][oh][ow] bytes or null, sized,
+// sampled and masked as dt_launch_depth's.  marks / recs: the handle's [N] FlowMark and FlowRec (the records are rewritten by every call);
+// per_env: the cameras of SimArrays::cam (DTSIM_F_DOMAIN_RAND), else the shared one; cal: the calibration whose forward model the fisheye
+// frames go through, or null (rectilinear).
+void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env, const IpmCal* cal,
+                    float* flow, uint8_t* valid, int oh, int ow, const uint8_t* mask);
 // the bird's-eye maps of dtsim_bev (render_views.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
 // rows_behind of the oh rows behind the agent.  Of R only the scene of render_scene is read (maps, tile_recs, n_tile_recs, objs, tex_w, tex_h, n_maps) and
 // N: no camera, no table of a pass.  ocorners: dt_pack_object_corners' table; texel_class / mesh_class as dt_launch_labels' (read only with

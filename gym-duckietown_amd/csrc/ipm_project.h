@@ -62,6 +62,24 @@ DT_IPM_HD inline void dt_ipm_cell(int i, int j, int oh, int ow, double cell, int
   s = (((double)j + 0.5) - 0.5 * (double)ow) * cell;
 }
 
+// Step 3 of the quantity, the calibration's forward model, stated once for dt_ipm_source and for dtsim_flow (render_views.hip k_flow):
+// dtsim/distortion.py rectify_maps -- cv::initUndistortRectifyMap's arithmetic -- at the real-valued index coordinates (px, py) of the
+// rectified image gives the index coordinates (xd, yd) of the distorted one, plus `off` (0.5: what dt_ipm_source rounds down to a pixel; the
+// sum is written here so that its kernels keep the instructions they had before the function existed -- tools/isa_compare.py).
+DT_IPM_HD inline void dt_ipm_forward(const IpmCal& cal, double px, double py, double off, double& xd, double& yd) {
+  const double _x = py * cal.ir[1] + cal.ir[2] + px * cal.ir[0];
+  const double _y = py * cal.ir[4] + cal.ir[5] + px * cal.ir[3];
+  const double _w = py * cal.ir[7] + cal.ir[8] + px * cal.ir[6];
+  const double iw = 1.0 / _w;
+  const double x = _x * iw, y = _y * iw;
+  const double x2 = x * x, y2 = y * y, r2 = x2 + y2, _2xy = 2.0 * x * y;
+  const double kr = 1.0 + ((cal.k3 * r2 + cal.k2) * r2 + cal.k1) * r2;
+  const double xu = x * kr + cal.p1 * _2xy + cal.p2 * (r2 + 2.0 * x2);
+  const double yu = y * kr + cal.p1 * (r2 + 2.0 * y2) + cal.p2 * _2xy;
+  xd = cal.fx * xu + cal.u0 + off;
+  yd = cal.fy * yu + cal.v0 + off;
+}
+
 // Steps 1 to 4 of the quantity: the source pixel r * W + c of the floor point f ahead and s to the right of the agent, or -1 where the
 // cell is invalid.  cal: the env's calibration (the frames are fisheye), or null (rectilinear).  Every comparison is written so that a
 // NaN fails it, and no value is converted to an integer before it is known to lie inside the frame.
@@ -76,19 +94,7 @@ DT_IPM_HD inline int32_t dt_ipm_source(const IpmCam& c, const IpmCal* cal, int W
   double pc = u, pr = v;               // what is rounded down to the source pixel's column and row
   if (cal) {
     if (!(u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H)) return -1;
-    // dtsim/distortion.py rectify_maps at the real-valued index coordinates (u - 0.5, v - 0.5)
-    const double px = u - 0.5, py = v - 0.5;
-    const double _x = py * cal->ir[1] + cal->ir[2] + px * cal->ir[0];
-    const double _y = py * cal->ir[4] + cal->ir[5] + px * cal->ir[3];
-    const double _w = py * cal->ir[7] + cal->ir[8] + px * cal->ir[6];
-    const double iw = 1.0 / _w;
-    const double x = _x * iw, y = _y * iw;
-    const double x2 = x * x, y2 = y * y, r2 = x2 + y2, _2xy = 2.0 * x * y;
-    const double kr = 1.0 + ((cal->k3 * r2 + cal->k2) * r2 + cal->k1) * r2;
-    const double xd = x * kr + cal->p1 * _2xy + cal->p2 * (r2 + 2.0 * x2);
-    const double yd = y * kr + cal->p1 * (r2 + 2.0 * y2) + cal->p2 * _2xy;
-    pc = cal->fx * xd + cal->u0 + 0.5;
-    pr = cal->fy * yd + cal->v0 + 0.5;
+    dt_ipm_forward(*cal, u - 0.5, v - 0.5, 0.5, pc, pr);
   }
   if (!(pc >= 0.0 && pc < (double)W && pr >= 0.0 && pr < (double)H)) return -1;
   return (int32_t)pr * W + (int32_t)pc;  // (both are >= 0: the conversion rounds down)

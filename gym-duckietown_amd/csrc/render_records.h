@@ -126,6 +126,30 @@ struct alignas(16) PixTab { float lr, lf, lit; uint32_t mi; };
 struct alignas(16) SampTab { uint32_t dlr[2], dlf[2]; uint32_t flags; uint32_t lr_bits, lf_bits, lit_bits; };
 static_assert(sizeof(PixTab) == 16 && sizeof(SampTab) == 32, "table records");
 
+// ---- dtsim_flow (render_views.hip k_flow_mark, k_flow_setup, k_flow; the arithmetic: flow_transform.h) ----------------------------
+// FlowMark: what dtsim_flow_mark remembers of one env's state -- the float64 pose, the six camera floats of DTSIM_FIELD_CAMERA, the
+// episode and map, and per dynamic slot the centre (x, height, z) and y_rot (degrees) k_obj_setup places the mesh with.  has: 0 = no mark
+// (the buffer starts zeroed and dtsim_set_maps / dtsim_set_assets zero it again).
+struct FlowMark {
+  double x, z, ang;
+  float cam[6];
+  int32_t episode, map_id, has, pad;
+  double ob[8][4];                                    // [DTSIM_MAX_DYNAMIC]: cx, cy, cz, y_rot
+};
+static_assert(sizeof(FlowMark) == 320, "FlowMark is 320 bytes");
+// FlowXf: X_prev_eye = M X_cur_eye + t, row-major, float32 (rounded from float64 after the camera centres were subtracted).
+struct alignas(16) FlowXf { float M[9], t[3]; };
+// FlowRec: one env's record of a dtsim_flow call, written by k_flow_setup: the pair of static surfaces, then one per dynamic slot with the
+// object's motion folded in; the image-plane half-extents of the current and of the previous camera (both from the float64 formula, so equal
+// cameras give equal bits); valid: the env has a mark of its current episode and map.
+struct alignas(16) FlowRec {
+  FlowXf fix;
+  float txc, tyc, txp, typ;
+  int32_t valid, pad[3];
+  FlowXf dyn[8];                                      // [DTSIM_MAX_DYNAMIC]
+};
+static_assert(sizeof(FlowXf) == 48 && sizeof(FlowRec) == 464 && offsetof(FlowRec, dyn) == 80, "FlowRec: 48 + 32 + 8 x 48 bytes");
+
 // RenderParams.dump: `store` takes the masked lanes of the unconditional frame store (16 B per lane)
 struct RenderDump { uint8_t store[64 * 16]; };
 

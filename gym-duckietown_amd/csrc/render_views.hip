@@ -5,6 +5,7 @@
 // (the opaque scene at the four samples of a pixel), k_overlay_leds, k_depth, k_labels, k_bev, k_ipm_*, then their dt_launch_* (dtsim_dev.h).
 #include "dtsim_dev.h"
 #include "render_scene.h"
+#include "flow_transform.h"
 #include <hip/hip_fp16.h>
 
 namespace {
@@ -155,10 +156,15 @@ struct LedS { float ex, ey, ez, r, cr, cg, cb, a, bx0, bx1, by0, by1; };     // 
 // WHO (k_labels): also who owns each sample -- hits[q] = classify()'s plane hit (class, tile, world hit), obj[q] = the object (the o of the
 // ObjBox loop) whose triangle won the sample's z-buffer AND lies strictly nearer than the plane (the colour pass's depth test, shade_msaa),
 // else -1.  Without WHO (hits, obj unused, may be null) nothing of that is compiled: the depth arithmetic is the same statements in both.
-template <bool WHO>
+// tbox (k_flow): the env's rows of RenderParams.tribox, the screen boxes k_obj_setup writes for EVERY triangle of a live object in every pass.
+// With that stream the pass rewrites the ScreenTri record of a surviving triangle only, so a triangle culled in this pass (outside the view,
+// behind the near plane) keeps the record -- and the box inside it -- of the last pass it survived: tested by its record's box, as the
+// callers without tbox test it, it is z-buffered where it stood in that older frame.  The flow is asked for after a second render from
+// another pose, which is when that shows; with tbox the box is the stream's and a culled triangle is skipped, as the colour pass skips it.
+template <bool WHO, bool TBOX = false>
 __device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
                                       const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
-                                      const float sky, float depth[4], Hit* hits, int* obj) {
+                                      const float sky, float depth[4], Hit* hits, int* obj, const float4* tbox = nullptr) {
   const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
   float wbest[4] = {0.f, 0.f, 0.f, 0.f};
   int tbest[4] = {-1, -1, -1, -1};
@@ -167,6 +173,12 @@ __device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const Tile
     for (int o = 0; o < n_obj; ++o) {
       const ObjBox ob = boxes[o];
       if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
+      if constexpr (TBOX) {                           // (k_flow) the pass's own cull stream: see the comment above
+        for (int t = ob.first; t < ob.first + ob.count; ++t) {
+          const float4 b = tbox[t];
+          if (!(sxp < b.x || sxp > b.y || syp < b.z || syp > b.w)) test_tri_inside(tb[t], sxp, syp, wbest, tbest);
+        }
+      } else
       for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
       if constexpr (WHO) {
 #pragma unroll
@@ -454,6 +466,132 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
     }
   }
 }
+// ---- k_flow_mark, k_flow_setup, k_flow: the optical-flow map of dtsim_flow (the quantity: include/dtsim.h; the transform: flow_transform.h) ------
+// k_flow_mark: the copy -- a thread per env takes what the flow needs of the CURRENT state out of the state arrays into the handle's FlowMark.
+__global__ __launch_bounds__(64) void k_flow_mark(const SimArrays A, FlowMark* __restrict__ marks, const uint8_t* __restrict__ mask) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= A.N || (mask && !mask[e])) return;
+  const size_t N = (size_t)A.N;
+  FlowMark m;
+  m.x = A.pos_x[e]; m.z = A.pos_z[e]; m.ang = A.angle[e];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) m.cam[k] = A.cam[k * N + e];
+  m.episode = A.episode[e]; m.map_id = A.map_id[e]; m.has = 1; m.pad = 0;
+  static_assert(DTSIM_MAX_DYNAMIC == 8, "FlowMark and FlowRec hold eight dynamic slots");
+#pragma unroll
+  for (int k = 0; k < DTSIM_MAX_DYNAMIC; ++k) {
+    m.ob[k][0] = A.ob_cx[k * N + e]; m.ob[k][1] = A.ob_cy[k * N + e]; m.ob[k][2] = A.ob_cz[k * N + e]; m.ob[k][3] = A.ob_yrot[k * N + e];
+  }
+  marks[e] = m;
+}
+// k_flow_setup: one small launch per dtsim_flow call, a thread per env: dt_flow_record (flow_transform.h) on the mark and the current state
+// arrays, in float64, into the env's FlowRec.
+__global__ __launch_bounds__(64) void k_flow_setup(const SimArrays A, const FlowMark* __restrict__ marks, FlowRec* __restrict__ recs, const int per_env,
+                                                   const int W, const int H, const uint8_t* __restrict__ mask) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= A.N || (mask && !mask[e])) return;
+  const size_t N = (size_t)A.N;
+  FlowState cur;
+  cur.x = A.pos_x[e]; cur.z = A.pos_z[e]; cur.ang = A.angle[e];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) cur.cam[k] = (double)A.cam[k * N + e];
+#pragma unroll
+  for (int k = 0; k < DTSIM_MAX_DYNAMIC; ++k) {
+    cur.ob[k][0] = A.ob_cx[k * N + e]; cur.ob[k][1] = A.ob_cy[k * N + e]; cur.ob[k][2] = A.ob_cz[k * N + e]; cur.ob[k][3] = A.ob_yrot[k * N + e];
+  }
+  FlowRec r;
+  dt_flow_record(marks[e], cur, A.episode[e], A.map_id[e], per_env != 0, W, H, r);
+  recs[e] = r;
+}
+// An eye-space point on the image: w, the rectilinear (u, v) of dtsim_ipm's step 1 and A(u, v) -- the identity, or with a calibration the
+// forward model at (u - 0.5, v - 0.5) (ipm_project.h dt_ipm_forward, in float64: in float32 its 25 operations would take the count of
+// roundings R of tests/test_flow_model_host.py past 32).  Both terms of a flow go through this one function, so one point gives one value.
+struct FlowPt { double ax, ay; float w, u, v; };
+__device__ inline FlowPt flow_image(const float x, const float y, const float z, const float tx, const float ty, const float Wf, const float Hf,
+                                    const IpmCal* __restrict__ cal) {
+  FlowPt p;
+  p.w = -z;
+  p.u = (x / p.w / tx + 1.f) * 0.5f * Wf;             // R: 4 roundings (two divisions, the sum, the product by W; x 0.5 is exact)
+  p.v = (1.f - y / p.w / ty) * 0.5f * Hf;             //    (the same 4, of the other coordinate)
+  p.ax = (double)p.u; p.ay = (double)p.v;
+  if (cal) dt_ipm_forward(*cal, p.ax - 0.5, p.ay - 0.5, 0.0, p.ax, p.ay);   // (wave-uniform) R: none, float64
+  return p;
+}
+// k_flow: the sibling of k_labels -- the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once, the
+// env's camera record, map, object boxes and FlowRec at a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_flow.py holds
+// envs e, e + 64, e + 128 to the same bytes).  Per env it runs scene_samples4<true>, takes the sample k_labels takes (smallest depth, ties to
+// the lowest index, sky = +inf), rebuilds its eye-space hit X = d (xe, ye, -1) from the sample's own ray, applies ONE pair (M, t) -- the
+// static one, or the winning object's dynamic slot's, a per-lane read of the env's record only on lanes a dynamic object owns -- and puts X
+// and M X + t on the image through flow_image.  flow = A(prev) - A(cur), rounded to float32 once.  The two stores of a pixel go to the two
+// planes of its env's map: each a coalesced row segment, as is the byte of `valid`.
+// TBOX: the pass left a box stream (RenderParams.tribox; scene_samples4 says why the flow reads it).
+template <bool TBOX>
+__global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
+                                              const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
+                                              const float4* __restrict__ tribox, const ObjInstDev* __restrict__ objs, const FlowRec* __restrict__ recs,
+                                              const IpmCal* __restrict__ cal, const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
+                                              float* __restrict__ flow, uint8_t* __restrict__ valid, const uint8_t* __restrict__ mask) {
+  const int n_out = oh * ow;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const bool in = pix < n_out;
+  const int sy = H / oh, sx = W / ow;
+  ViewPix p = NO_PIX;
+  if (in) {
+    const int i = pix / ow, j = pix - i * ow;
+    p = view_pixel(lut, (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2), W, H);
+  }
+  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H, Wf = (float)W, Hf = (float)H;
+  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+#pragma clang loop unroll(disable)
+  for (int e = e0; e < e1; ++e) {
+    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's rows keep their bytes
+    const EnvCam c = cams[e];
+    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
+    const MapU m = map_u(rm);
+    const FlowRec& rec = recs[e];
+    float fu = 0.f, fv = 0.f;
+    bool ok = false;
+    if (p.live) {
+      float ds[4];
+      Hit hs[4];
+      int os[4];
+      scene_samples4<true, TBOX>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr,
+                                 objbox ? stris + (size_t)e * max_tris : nullptr, objbox ? rm.n_obj : 0, p.nx, p.ny, p.sxp, p.syp, sxn, syn,
+                                 __builtin_inff(), ds, hs, os, TBOX && objbox ? tribox + (size_t)e * max_tris : nullptr);
+      float db = ds[0], oxq = ox[0], oyq = oy[0];
+      int ob = os[0];
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+        if (ds[q] < db) { db = ds[q]; ob = os[q]; oxq = ox[q]; oyq = oy[q]; }
+      if (db < __builtin_inff() && rec.valid) {        // not sky (sky = +inf wins only when all four are), and a mark of this episode
+        // the eye-space hit of the sample's ray (scene_samples4's statement of it) at the sample's depth
+        const float xe = fmaf(oxq, sxn, p.nx) * c.tx, ye = fmaf(-oyq, syn, p.ny) * c.ty;
+        const float X = db * xe, Y = db * ye, Z = -db;
+        const FlowXf* xf = &rec.fix;
+        if (ob >= 0) {
+          const int slot = objs[rm.obj_off + ob].dyn_slot;
+          if (slot >= 0) xf = &rec.dyn[min(slot, DTSIM_MAX_DYNAMIC - 1)];
+        }
+        // R: 3 roundings per coordinate (three fused multiply-adds), x and w both enter u: 6
+        const float xp = fmaf(xf->M[0], X, fmaf(xf->M[1], Y, fmaf(xf->M[2], Z, xf->t[0])));
+        const float yp = fmaf(xf->M[3], X, fmaf(xf->M[4], Y, fmaf(xf->M[5], Z, xf->t[1])));
+        const float zp = fmaf(xf->M[6], X, fmaf(xf->M[7], Y, fmaf(xf->M[8], Z, xf->t[2])));
+        const FlowPt a = flow_image(X, Y, Z, rec.txc, rec.tyc, Wf, Hf, cal);
+        const FlowPt b = flow_image(xp, yp, zp, rec.txp, rec.typ, Wf, Hf, cal);
+        ok = b.w >= NEAR_Z && b.u >= 0.f && b.u < Wf && b.v >= 0.f && b.v < Hf;      // (a NaN fails every comparison)
+        if (ok) { fu = (float)(b.ax - a.ax); fv = (float)(b.ay - a.ay); }              // R: 1 (the one rounding of the difference)
+      }
+    }
+    if (in) {
+      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      flow[2 * (size_t)e * (size_t)n_out + (size_t)pix] = fu;
+      flow[(2 * (size_t)e + 1) * (size_t)n_out + (size_t)pix] = fv;
+      if (valid) valid[to] = ok ? 1 : 0;
+    }
+  }
+}
+
 // ---- k_bev: the egocentric bird's-eye label map of every env (dtsim_bev; the quantity: include/dtsim.h) ------------------------------------
 // The grid of k_depth / k_labels: cell blocks x env chunks of DEPTH_ENVS.  A thread owns ONE cell; its place in the agent's frame -- f cells
 // ahead, s cells to the right, both multiples of one half and exact in float32 -- does not depend on the env and is computed once.  The env
@@ -816,6 +954,21 @@ void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel
                      reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
                      n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask, cal ? cal_src : nullptr,
                      cal ? env_cal : nullptr, cal ? n_cal : 0);
+}
+
+void dt_launch_flow_mark(hipStream_t s, const SimArrays& A, FlowMark* marks, const uint8_t* mask) {
+  if (A.N <= 0) return;
+  hipLaunchKernelGGL(k_flow_mark, dim3((unsigned)((A.N + 63) / 64)), dim3(64), 0, s, A, marks, mask);
+}
+
+void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env, const IpmCal* cal,
+                    float* flow, uint8_t* valid, int oh, int ow, const uint8_t* mask) {
+  if (R.N <= 0) return;
+  hipLaunchKernelGGL(k_flow_setup, dim3((unsigned)((R.N + 63) / 64)), dim3(64), 0, s, A, marks, recs, per_env ? 1 : 0, R.W, R.H, mask);
+  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
+  auto k = obj && R.tribox ? k_flow<true> : k_flow<false>;
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut),
+                     obj ? R.objbox : nullptr, obj ? R.stris : nullptr, obj ? R.tribox : nullptr, R.objs, recs, cal, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, flow, valid, mask);
 }
 
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,

@@ -978,6 +978,35 @@ class BatchedSimulator:
         _ffi.check(self._lib, self._lib.dtsim_ipm(self._h, ptr, vp, ip, h, w, c, rb, _ffi.IPM_CHW if chw else 0, mp))
         return out
 
+    def flow_mark(self, mask=None):
+        """Remember the current state of the selected envs (`mask` as render()'s; None: every env) as the "previous" state of flow()
+        (dtsim_flow_mark, include/dtsim.h): pose, camera, episode, map and the dynamic objects' poses, read from the state itself -- no
+        render() is needed.  The marks live in the handle, not in the state blob; set_maps / set_assets drop them."""
+        _ffi.check(self._lib, self._lib.dtsim_flow_mark(self._h, self._mask_arg(mask)))
+
+    def flow(self, height=None, width=None, out=None, mask=None, valid_out=None):
+        """The optical-flow map of every env's camera frame since its flow_mark(), on the device (dtsim_flow, include/dtsim.h): [N, 2, h, w]
+        float32, plane 0 = x (to the right), plane 1 = y (down), in CAMERA pixels whatever the map's size; previous minus current, so
+        prev_frame[p + flow] is what cur_frame[p] shows.  Per pixel the surface point that sets depth()'s value there -- moved with its object
+        if a mesh object owns it -- is projected through the marked state's camera and through the current one (with distortion=True both
+        through the calibration's forward model, as ipm() does) and the difference taken; exactly 0.0 where nothing moved.  `valid_out`
+        ([N, h, w] uint8): 1 where the flow is defined -- a surface with a source pixel, a mark of the env's current episode, the previous
+        point in front of the near plane and inside the image --, else 0, and the flow there is 0, 0.  Needs a preceding render() of the
+        current state.  Size, `out` and `mask` as depth()'s.  Per-env calibrations (camera_rand, set_camera_calibrations) and undistort=True
+        raise ValueError, as does a bad size, out, valid_out or mask, before anything is launched."""
+        h, w = self._map_size("flow", "flow is", height, width)
+        if self.undistort:
+            raise ValueError("flow with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
+        if self._cal is not None:
+            raise ValueError("flow with per-env calibrations (camera_rand, set_camera_calibrations) is not supported")
+        mp = self._mask_arg(mask)
+        out, ptr = self._result("flow", out, (self.num_envs, 2, h, w), "float32")
+        vp = None
+        if valid_out is not None:
+            vp = C.c_void_p(self._out_ptr(valid_out, (self.num_envs, h, w), "|u1", 1, "flow: valid_out"))
+        self._map_pass(self._lib.dtsim_flow, self._lib.dtsim_flow_masked, mp, ptr, vp, h, w, 0)
+        return out
+
     @staticmethod
     def _state_array_offset(name: str, n: int) -> int:
         """Byte offset of array `name` in the state blob of n envs (csrc/state_fields.h DT_STATE_ARRAYS: [planes][n] float64 arrays in slab

@@ -46,12 +46,12 @@ average (its learners' imresize then rescales by the array's min and max); here 
 resize of every other frame -- `BatchedSimulator.blend_frames(out=float32)` gives the unrounded value.  Memory: L extra frame batches (15 GB for
 the default window at N = 4096, 640 x 480).  `motion_blur=False` (the default) runs the paths above, call for call.
 
-Auxiliary outputs (depth, labels, instances, boxes, bev, bev_instances, ipm, ipm_valid; each off by default, and an option left off makes no new call).  What
+Auxiliary outputs (depth, labels, instances, boxes, flow, flow_valid, bev, bev_instances, ipm, ipm_valid; each off by default, and an option left off makes no new call).  What
 they share, said once.  Output X is one persistent device tensor, `info["X"]`, of the state whose observation `obs` shows -- for an env
 restarted in the step, the first state of its new episode.  `reset()` keeps returning `obs` alone: after it the output is `env.X`, the same
 tensor (None while X is off).  With `final_obs=True`, `info["final_X"]` is a second persistent tensor whose rows where
 `info["final_obs_mask"]` is set hold X of the final state (the other rows are unspecified).  The passes stand together after every observe,
-in the order depth, labels, instances, boxes, bev, ipm, masked where the observe is masked: full render -> observe -> passes ->
+in the order depth, labels, instances, boxes, flow, bev, ipm, masked where the observe is masked: full render -> observe -> passes ->
 `dtsim_copy_rows` of each -> `dtsim_reset_done` -> masked render -> masked observe -> masked passes.  They compose with one another and with
 `frame_stack`, `grayscale`, `obs_shape=None` and `domain_rand` (no output is ever stacked).  Depth, labels, instances and boxes are CAMERA
 post-passes: point-sampled from the frame's source pixels, never filtered, so each size of their `(h, w)` must divide the camera's; and they
@@ -91,6 +91,17 @@ floor point of `info["bev"]`'s cell (i, j) projects to through the env's own cam
 aligned.  Nearest pixel, never filtered; a flat-world projection (no occlusion; what stands on the floor smears away from the camera).  It
 projects through each env's camera and calibration itself and reads no table, so `domain_rand` and `camera_rand` are allowed;
 `motion_blur` (the blended frame shows several cameras), `undistort=True` and `render=False` raise ValueError.
+
+Optical flow (`flow_shape=(h, w)`; `flow_valid=True` needs it): `info["flow"]` is the `[N, 2, h, w]` `torch.float32` flow map (`dtsim_flow`,
+include/dtsim.h: per pixel where the surface point that sets the depth there -- moved with its duckie, if one owns it -- stood in the
+PREVIOUS shown state's image, minus where it stands now; camera pixels, x right and y down, so `prev_frame[p + flow]` is what
+`cur_frame[p]` shows; through the fisheye's forward model with `distortion=True`), and with `flow_valid=True` `info["flow_valid"]` the
+`[N, h, w]` flags of the same launch (0: sky, the fisheye's border, a previous point behind the camera or outside the image; the flow
+there is 0, 0).  A camera post-pass like depth, under the same rules, but the one output of TWO states: `reset()` and `step()` end with one
+`dtsim_flow_mark` of every env, after all passes, so an env that went on shows the motion since the last step's shown state, across all
+`frame_skip` sub-updates; an env restarted in the step has no mark of its new episode: its rows are all 0 (flow and flags); with
+`final_obs=True` `info["final_flow"]` is the finished env's last flow.  After `reset()` the map is all 0 too.  `motion_blur`,
+`camera_rand` (even with `camera_rand_maps`) and `undistort=True` raise ValueError.
 """
 from __future__ import annotations
 
@@ -120,7 +131,8 @@ class DuckietownVecEnv:
                  instance_shape: Optional[Tuple[int, int]] = None, boxes: bool = False,
                  bev_shape: Optional[Tuple[int, int]] = None, bev_cell: float = 0.02, bev_rows_behind: int = 0,
                  bev_instances: bool = False, ipm_shape: Optional[Tuple[int, int]] = None, ipm_cell: float = 0.02,
-                 ipm_rows_behind: int = 0, ipm_valid: bool = False, camera_rand_maps: bool = False, **sim_kwargs):
+                 ipm_rows_behind: int = 0, ipm_valid: bool = False, camera_rand_maps: bool = False,
+                 flow_shape: Optional[Tuple[int, int]] = None, flow_valid: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -141,6 +153,13 @@ class DuckietownVecEnv:
         if boxes and instance_shape is None:
             raise ValueError("boxes=True needs instance_shape (the boxes are those of the instance map, in its pixels)")
         self.instance_shape = self._camera_map_shape("instance_shape", instance_shape, cam)
+        if flow_valid and flow_shape is None:
+            raise ValueError("flow_valid=True needs flow_shape (the flags are those of the flow map, in its pixels)")
+        if flow_shape is not None and sim_kwargs.get("camera_rand"):
+            raise ValueError("flow_shape with camera_rand is not supported (a distortion table per env: the flow goes through one calibration)")
+        if flow_shape is not None and sim_kwargs.get("undistort"):
+            raise ValueError("flow_shape with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
+        self.flow_shape = self._camera_map_shape("flow_shape", flow_shape, cam)
         self.bev_shape, self.bev_cell, self.bev_rows_behind = None, bev_cell, bev_rows_behind
         if bev_shape is None:
             if bev_instances:
@@ -190,6 +209,8 @@ class DuckietownVecEnv:
                    _Aux("labels", "uint8", self.label_shape, True),
                    _Aux("instances", "uint8", self.instance_shape, True),
                    _Aux("boxes", "int32", (_ffi.MAX_OBJECTS, 5) if boxes else None, True),
+                   _Aux("flow", "float32", self.flow_shape and (2, *self.flow_shape), True),
+                   _Aux("flow_valid", "uint8", self.flow_shape if flow_valid else None, True),
                    _Aux("bev", "uint8", self.bev_shape, False),
                    _Aux("bev_instances", "uint8", self.bev_shape if bev_instances else None, False),
                    _Aux("ipm", "uint8", self.ipm_shape and ((3, *self.ipm_shape) if chw else (*self.ipm_shape, 3)), False),
@@ -300,7 +321,7 @@ class DuckietownVecEnv:
     def _map_passes(self, mask=None):
         """The passes of the outputs that are on, in the table's order, each into the env's own tensor (`mask`: only those envs' rows): of the
         state the last render() showed the depth, then the labels, then the instances and their boxes -- labels and instances of one shape
-        come from one launch --; then, of the current state, the bird's-eye map (and its ids); last, of the frame batch as it stands, the
+        come from one launch --, then the flow since the envs' marks (and its flags); then, of the current state, the bird's-eye map (and its ids); last, of the frame batch as it stands, the
         ground-projected image (and its flags)."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
@@ -312,6 +333,8 @@ class DuckietownVecEnv:
                                labels_out=self.labels if fused else None)
             if self.boxes is not None:
                 self.sim.boxes(self.instances, out=self.boxes, mask=mask)
+        if self.flow is not None:
+            self.sim.flow(self.flow_shape[0], self.flow_shape[1], out=self.flow, mask=mask, valid_out=self.flow_valid)
         if self.bev is not None:
             self.sim.bev(self.bev_shape[0], self.bev_shape[1], cell=self.bev_cell, rows_behind=self.bev_rows_behind, out=self.bev, mask=mask,
                          instances_out=self.bev_instances)
@@ -344,11 +367,17 @@ class DuckietownVecEnv:
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
             obs = self._show(first=self._all)
             self._map_passes()
+            self._mark()
             if self._blur:
                 self._ring[0].copy_(self._frames)                   # the next window's first frame
                 self._cur = 0
         self._leave()
         return obs
+
+    def _mark(self):
+        """flow_shape: the state every env is left in -- the one `obs` shows -- becomes the previous state of the next step's flow."""
+        if self.flow is not None:
+            self.sim.flow_mark()
 
     def _advance(self, actions):
         """The step of the state: dtsim_step, or with motion_blur the clipped wheel pair in L - 1 sub-updates, each rendered into the next
@@ -409,6 +438,7 @@ class DuckietownVecEnv:
                 sim.reset_done()
                 obs = self._show(first=done)
                 self._map_passes()
+            self._mark()
             for name, live, _ in self._aux:
                 info[name] = live
         self._leave()

@@ -707,6 +707,47 @@ int dtsim_bev(dtsim_t* h, uint8_t* cls, uint8_t* inst, int oh, int ow, double ce
 int dtsim_set_ipm_calibrations(dtsim_t* h, int n_cal, const double* K, const double* D, const double* new_K, const int32_t* env_cal);
 int dtsim_ipm(dtsim_t* h, uint8_t* img, uint8_t* valid, int32_t* src, int oh, int ow, double cell, int rows_behind, uint32_t flags,
               const uint8_t* mask);
+/* The optical-flow map of every camera frame, on the device: HOW THE PICTURE MOVED since a remembered state -- the ground truth of
+ * optical-flow and ego-motion heads and of warping losses, beside the maps above, which all describe one state.  A learner-side addition;
+ * the reference has no such output.
+ * THE QUANTITY.  For output pixel (i, j) of env e, camera pixel p is chosen by dtsim_depth's SIZE rule and its source pixel by dtsim_depth's
+ * rule.  Let q be the sample that sets dtsim_depth's value there: the smallest eye depth of the four MSAA samples, ties to the lowest index,
+ * sky counting as +inf; its owner is chosen as dtsim_labels chooses it (a mesh only where its z-buffer depth is strictly smaller than the
+ * plane's).  X is the eye-space hit of q's ray at that depth, P the world point it stands for.
+ *   - The previous point.  If the owner is a plane (tile, ground quad), P_prev = P.  If it is mesh object o, the point moves with the object:
+ *     P_prev = pos_prev(o) + Ry(yrot_prev(o)) Ry(yrot_cur(o))^-1 (P - pos_cur(o)), pos and yrot being what the render pass places the mesh
+ *     with -- a static object's own (the motion is the identity), a dynamic one's DTSIM_FIELD_OBJ_CENTER, its height + DTSIM_FIELD_OBJ_Y and
+ *     DTSIM_FIELD_OBJ_YROT.  "Previous" is the state the last dtsim_flow_mark remembered for the env.
+ *   - flow = A(proj_prev(P_prev)) - A(proj_cur(P)), in CAMERA pixels, x to the right and y down, whatever the map's size.  Previous minus
+ *     current: prev_frame[p + flow] is what cur_frame[p] shows.  proj is dtsim_ipm's step 1 with each state's own camera (height, pitch,
+ *     fov_y and noise of DTSIM_FIELD_CAMERA on per-env cameras, else the shared one), formed in float64 from the float64 poses: the camera
+ *     centres are subtracted before anything is rounded to the float32 record a pixel applies.  A is the identity on rectilinear frames; on
+ *     fisheye frames it is the forward model of dtsim_ipm's step 3 at (u - 0.5, v - 0.5), with calibration 0 of dtsim_set_ipm_calibrations.
+ *     Both terms go through the same functions.  As in dtsim_ipm, A PROPERTY OF THE REFERENCE'S FISHEYE, not a tolerance: the frame itself
+ *     is made with an approximate INVERSE table, so what frame pixel p shows lies a median 0.8 px (at most 4.2 px at 640 x 480) from A's value.
+ *   - valid[e][i][j] is 1 iff the pixel has a source pixel, q is not sky, the env has a mark of its current episode (DTSIM_FIELD_EPISODE
+ *     and DTSIM_FIELD_MAP_ID at the mark equal the current values), w_prev >= 0.04 and the previous rectilinear (u, v) lies in
+ *     [0, W) x [0, H).  An invalid pixel has flow 0, 0.
+ *   - Where nothing moved between the mark and the call (the same pose, the same camera, an object with the same pose) the flow is
+ *     exactly 0.0: every rotation enters the record as the rotation by a float64 angle DIFFERENCE, never as a product that ought to cancel.
+ * Out of scope: sky pixels, forward flow, occlusion masks, half precision, per-env distortion tables (refused, DTSIM_MAP_ENV_TABLES
+ * included), frames that show UndistortWrapper's view.
+ * dtsim_flow_mark remembers, for the selected envs (mask: DEVICE pointer to num_envs bytes, or NULL = every env), what the flow needs of the
+ * CURRENT state: the float64 pose, the six camera floats, episode and map id, and per dynamic slot centre, height and y_rot.  It reads the
+ * state arrays, not what a render left: it needs no render and is valid after a masked pass.  The marks live in a buffer of the handle,
+ * outside the state blob (DTSIM_FIELD_STATE_BLOB does not carry them); dtsim_set_maps and dtsim_set_assets drop all marks.  DTSIM_E_STATE
+ * before the first dtsim_reset.  Asynchronous, stream-ordered.
+ * SIZE.  flow: DEVICE pointer to [num_envs][2][oh][ow] float32 (plane 0: x, plane 1: y); valid: to [num_envs][oh][ow] bytes, or NULL.
+ * cam_height % oh == 0 and cam_width % ow == 0; the map is dtsim_depth's point sample, full[:, :, sy/2::sy, sx/2::sx].  flags must be 0.
+ * STATE.  dtsim_depth's rules, word for word: a colour dtsim_render of the CURRENT state must precede, the same calls invalidate, after
+ * dtsim_render_masked only dtsim_flow_masked with the pass's mask is valid (it writes the selected envs' rows only), installed per-env
+ * distortion tables are refused; and a handle whose distortion table is a fisheye's needs dtsim_set_ipm_calibrations first.  All
+ * DTSIM_E_STATE.  A null handle, flow or mask, flow and valid one buffer, a bad size or nonzero flags return DTSIM_E_INVALID.  A failed call
+ * launches nothing and writes nothing.  Asynchronous, stream-ordered.  One state and one mark give the same bytes on every call and for
+ * every env index. */
+int dtsim_flow_mark(dtsim_t* h, const uint8_t* mask);
+int dtsim_flow(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags);
+int dtsim_flow_masked(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

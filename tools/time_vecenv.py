@@ -21,7 +21,10 @@ bev_instances=True); small: (64, 64) at 0.04) against the plain step in the SAME
 unless given; the variants bev | bev_small | bev_only (no id map) can be listed like any other.
 IPM=1 (or small): the whole step with info["ipm"] + info["ipm_valid"] (DuckietownVecEnv(ipm_shape=(128, 128), ipm_cell=0.02, ipm_valid=True);
 small: (64, 64) at 0.04) against the plain step in the SAME run -- VARIANTS=plain,ipm (or plain,ipm_small) with ROUNDS=5 unless given; the
-variants ipm | ipm_small | ipm_only (no flags) | bev_ipm (the bird's-eye maps and the ground projection, input and target) can be listed."""
+variants ipm | ipm_small | ipm_only (no flags) | bev_ipm (the bird's-eye maps and the ground projection, input and target) can be listed.
+FLOW=1 (or full): the whole step with info["flow"] + info["flow_valid"] (DuckietownVecEnv(flow_shape=(120, 160), flow_valid=True); full:
+480 x 640) against the plain step in the SAME run -- VARIANTS=plain,flow (or plain,flow_full) with ROUNDS=5 unless given; the variants
+flow | flow_full | flow_only (no flags) can be listed."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -40,6 +43,7 @@ LABELS = os.environ.get("LABELS", "0")
 INSTANCES = os.environ.get("INSTANCES", "0")
 BEV = os.environ.get("BEV", "0")
 IPM = os.environ.get("IPM", "0")
+FLOW = os.environ.get("FLOW", "0")
 MAP = os.environ.get("MAP", "small_loop")
 MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
@@ -51,12 +55,14 @@ if BEV != "0" and not VARIANTS:
     VARIANTS, ROUNDS = ["plain", "bev_small" if BEV == "small" else "bev"], int(os.environ.get("ROUNDS", "5"))
 if IPM != "0" and not VARIANTS:
     VARIANTS, ROUNDS = ["plain", "ipm_small" if IPM == "small" else "ipm"], int(os.environ.get("ROUNDS", "5"))
+if FLOW != "0" and not VARIANTS:
+    VARIANTS, ROUNDS = ["plain", "flow_full" if FLOW == "full" else "flow"], int(os.environ.get("ROUNDS", "5"))
 a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
     def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0", instances="0",
-                 boxes=True, bev="0", bev_instances=True, ipm="0", ipm_valid=True):
+                 boxes=True, bev="0", bev_instances=True, ipm="0", ipm_valid=True, flow="0", flow_valid=True):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
@@ -73,6 +79,8 @@ class Variant:
             kw.update(bev_shape=(64, 64) if bev == "small" else (128, 128), bev_cell=0.04 if bev == "small" else 0.02, bev_instances=bev_instances)
         if ipm != "0":
             kw.update(ipm_shape=(64, 64) if ipm == "small" else (128, 128), ipm_cell=0.04 if ipm == "small" else 0.02, ipm_valid=ipm_valid)
+        if flow != "0":
+            kw.update(flow_shape=(480, 640) if flow == "full" else (120, 160), flow_valid=flow_valid)
         self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -123,6 +131,8 @@ def make(name):
             "ipm": lambda: Variant("ipm + valid 128 x 128 at 0.02 m", ipm="1"), "ipm_small": lambda: Variant("ipm + valid 64 x 64 at 0.04 m", ipm="small"),
             "ipm_only": lambda: Variant("ipm 128 x 128 at 0.02 m, no flags", ipm="1", ipm_valid=False),
             "bev_ipm": lambda: Variant("bev + ids + ipm + valid 128 x 128 at 0.02 m", bev="1", ipm="1"),
+            "flow": lambda: Variant("flow + valid 120 x 160", flow="1"), "flow_full": lambda: Variant("flow + valid 480 x 640", flow="full"),
+            "flow_only": lambda: Variant("flow 120 x 160, no flags", flow="1", flow_valid=False),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
