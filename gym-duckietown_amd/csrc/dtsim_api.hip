@@ -888,6 +888,54 @@ int dtsim_flow_masked(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, u
   return flow_run(h, "dtsim_flow_masked", flow, valid, oh, ow, flags, true, mask);
 }
 
+// dtsim_camera_maps and its masked form: the argument checks of its own (which outputs, that they do not overlap), dtsim_depth's checks
+// (map_pass_check), the label tables with `labels`, and with `flow` everything dtsim_flow refuses -- installed per-env tables whatever the
+// flags say, a fisheye handle without its calibration -- plus a handle no dtsim_flow_mark has been called on.
+static int camera_maps_run(dtsim_t* h, const char* who, const dtsim_camera_maps_out* out, int oh, int ow, uint32_t flags, bool masked,
+                           const uint8_t* mask) {
+  if (!h || !out || (masked && !mask)) return fail(DTSIM_E_INVALID, "%s: null argument", who);
+  if (!out->depth && !out->labels && !out->instances && !out->flow && !out->flow_valid) return fail(DTSIM_E_INVALID, "%s: no output", who);
+  if (out->flow_valid && !out->flow) return fail(DTSIM_E_INVALID, "%s: flow_valid without flow", who);
+  if (oh > 0 && ow > 0) {                              // (a bad size is map_pass_check's to name)
+    const size_t px = (size_t)h->N * (size_t)oh * (size_t)ow;
+    const struct { const void* p; size_t bytes; } span[5] = {{out->depth, px * ((flags & DTSIM_DEPTH_F16) ? 2 : 4)}, {out->labels, px},
+                                                             {out->instances, px}, {out->flow, px * 8}, {out->flow_valid, px}};
+    for (int a = 0; a < 5; ++a)
+      for (int b = a + 1; b < 5; ++b) {
+        const uintptr_t pa = (uintptr_t)span[a].p, pb = (uintptr_t)span[b].p;
+        if (pa && pb && pa < pb + span[b].bytes && pb < pa + span[a].bytes) return fail(DTSIM_E_INVALID, "%s: outputs %d and %d overlap", who, a, b);
+      }
+  }
+  const void* any = out->depth ? out->depth : out->labels ? (const void*)out->labels : out->instances ? (const void*)out->instances : (const void*)out->flow;
+  if (out->flow && h->n_cal)                           // (dtsim_flow's refusal and code; DTSIM_MAP_ENV_TABLES does not lift it)
+    flags &= ~(uint32_t)DTSIM_MAP_ENV_TABLES;
+  if (int rc = map_pass_check(h, who, any, oh, ow, flags, (uint32_t)DTSIM_DEPTH_F16, masked, mask)) return rc;
+  if (out->labels && (!h->d_texel_class || !h->d_mesh_class)) return fail(DTSIM_E_STATE, "%s with a label map before dtsim_set_label_assets", who);
+  if (out->flow) {
+    if (h->lut_fisheye && h->n_ipm_cal < 1)
+      return fail(DTSIM_E_STATE, "%s with flow on fisheye frames before dtsim_set_ipm_calibrations (the flow goes through the calibration's forward model)", who);
+    if (!h->d_flow_mark || !h->d_flow_rec) return fail(DTSIM_E_STATE, "%s with flow before the first dtsim_flow_mark", who);
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const EnvTables t = env_tables(h, flags);
+  if (out->flow)
+    dt_launch_flow_setup(h->stream, h->last_R, h->A, h->d_flow_mark.get(), h->d_flow_rec.get(), (h->cfg.flags & DTSIM_F_DOMAIN_RAND) != 0, mask);
+  {
+    ProfScope ps(h, DTSIM_KERNEL_CAMERA_MAPS);
+    const CameraMapsOut o{out->depth, (flags & DTSIM_DEPTH_F16) != 0, out->labels, out->instances, out->flow, out->flow_valid};
+    dt_launch_camera_maps(h->stream, h->last_R, o, h->d_texel_class.get(), h->d_mesh_class.get(), h->n_mesh_class, h->d_flow_rec.get(),
+                          h->lut_fisheye ? h->d_ipm_cal.get() : nullptr, oh, ow, mask, t.src, t.env_cal, t.n);
+  }
+  HIPCHK(hipGetLastError());
+  return DTSIM_OK;
+}
+int dtsim_camera_maps(dtsim_t* h, const dtsim_camera_maps_out* out, int oh, int ow, uint32_t flags) {
+  return camera_maps_run(h, "dtsim_camera_maps", out, oh, ow, flags, false, nullptr);
+}
+int dtsim_camera_maps_masked(dtsim_t* h, const dtsim_camera_maps_out* out, int oh, int ow, uint32_t flags, const uint8_t* mask) {
+  return camera_maps_run(h, "dtsim_camera_maps_masked", out, oh, ow, flags, true, mask);
+}
+
 int dtsim_boxes(dtsim_t* h, const uint8_t* inst, int oh, int ow, int32_t* out, uint32_t flags, const uint8_t* mask) {
   if (!h || !inst || !out) return fail(DTSIM_E_INVALID, "dtsim_boxes: null argument");
   if (flags) return fail(DTSIM_E_INVALID, "dtsim_boxes: unknown flags 0x%x", flags);

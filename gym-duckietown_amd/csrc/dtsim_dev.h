@@ -201,6 +201,18 @@ void dt_launch_flow_mark(hipStream_t s, const SimArrays& A, FlowMark* marks, con
 // frames go through, or null (rectilinear).
 void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env, const IpmCal* cal,
                     float* flow, uint8_t* valid, int oh, int ow, const uint8_t* mask);
+// dt_launch_flow's first launch alone (k_flow_setup): the selected envs' FlowRec from their marks and the current state.
+void dt_launch_flow_setup(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env,
+                          const uint8_t* mask);
+// the maps of dtsim_camera_maps (render_views.hip k_camera_maps), all [N][oh][ow] of ONE size, sampled and masked as dt_launch_depth's, from one
+// classification of the pixel: depth (float32, or half with f16), labels and inst (bytes; the tables of dt_launch_labels are read only with
+// labels), flow [N][2][oh][ow] float32 and valid (only with flow).  Any may be null, not all; they must not overlap.  recs: the FlowRec that
+// dt_launch_flow_setup wrote in this stream, cal: as dt_launch_flow's (both read only with flow).  cal_src / env_cal / n_cal: as
+// dt_launch_depth's, and ignored with flow (the caller refuses that combination).  Reads R.tribox where the pass left it.
+struct CameraMapsOut { void* depth; bool f16; uint8_t *labels, *inst; float* flow; uint8_t* valid; };
+void dt_launch_camera_maps(hipStream_t s, const RenderParams& R, const CameraMapsOut& o, const uint8_t* texel_class, const uint8_t* mesh_class,
+                           int n_mesh_class, const FlowRec* recs, const IpmCal* cal, int oh, int ow, const uint8_t* mask, const int32_t* cal_src,
+                           const int32_t* env_cal, int n_cal);
 // the bird's-eye maps of dtsim_bev (render_views.hip k_bev): cls / inst = [N][oh][ow] bytes (either may be null, not both), cell metres per cell,
 // rows_behind of the oh rows behind the agent.  Of R only the scene of render_scene is read (maps, tile_recs, n_tile_recs, objs, tex_w, tex_h, n_maps) and
 // N: no camera, no table of a pass.  ocorners: dt_pack_object_corners' table; texel_class / mesh_class as dt_launch_labels' (read only with

@@ -2,7 +2,7 @@
 // its projected mesh triangles (ScreenTri / ObjBox) and the camera table (lut).  None of them uses the raster's machinery (queues, work
 // lists, quad records, workgroup map, per-pixel tables); what they share with the pass is render_scene.h, and the unit is compiled with
 // render.hip's flags (build.py), so that classify() and test_tri are the frame's own code here.  In order: k_overlay_lines, scene_samples4
-// (the opaque scene at the four samples of a pixel), k_overlay_leds, k_depth, k_labels, k_bev, k_ipm_*, then their dt_launch_* (dtsim_dev.h).
+// (the opaque scene at the four samples of a pixel), k_overlay_leds, k_depth, k_labels, k_flow*, k_camera_maps, k_bev, k_ipm_*, then their dt_launch_* (dtsim_dev.h).
 #include "dtsim_dev.h"
 #include "render_scene.h"
 #include "flow_transform.h"
@@ -592,6 +592,135 @@ __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, c
   }
 }
 
+// ---- k_camera_maps: depth, labels, instances and flow of one size from ONE classification of the pixel (dtsim_camera_maps) -------------------
+// The sibling of k_labels and k_flow: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once -- with
+// CAL the env's own, cal_entry() with the next env's chain in flight, as k_depth's --, the env's camera record, map, object boxes and FlowRec at
+// a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_camera_maps.py holds envs e, e + 64, e + 128 to the same bytes), the
+// wave-uniform mask skip.  Per env it runs scene_samples4<true, TBOX> ONCE and takes the sample k_labels takes (smallest depth, ties to the
+// lowest index, sky = +inf); every output is that one winner's:
+//   depth      its depth -- the minimum of the four, k_depth's value --, 0 for a pixel without a source; float32, or half (f16, wave-uniform);
+//   labels     k_labels' class mapping, statement for statement;
+//   inst       o + 1 of its object, else DTSIM_INSTANCE_NONE;
+//   flow/valid k_flow's body, statement for statement (FLOW: only then are the float64 forward model and the FlowRec compiled in).
+// depth, labels and inst are branched on at run time (kernel arguments: wave-uniform); with FLOW, flow is written and valid if given.  The
+// four passes it stands for pay the four classify() calls and the triangle loop once each; this one pays them once (the stores are not the
+// cost: k_labels' comment).  TBOX: the pass's box stream whenever it exists, for every output -- scene_samples4 says what that changes for
+// depth, labels and instances against their single passes: a triangle culled in this pass is skipped, as the colour pass skips it.
+// FLOW && CAL does not exist: the flow under per-env tables is refused (dtsim_flow).
+template <bool FLOW, bool CAL, bool TBOX>
+__global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
+                                                     const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
+                                                     const float4* __restrict__ tribox, const ObjInstDev* __restrict__ objs,
+                                                     const uint8_t* __restrict__ texel_class, const uint8_t* __restrict__ mesh_class,
+                                                     const int n_mesh_class, const int tex_w, const int tex_h, const FlowRec* __restrict__ recs,
+                                                     const IpmCal* __restrict__ cal, const int max_tris, const int n_maps, const int N, const int W,
+                                                     const int H, const int oh, const int ow, void* __restrict__ depth, const int f16,
+                                                     uint8_t* __restrict__ labels, uint8_t* __restrict__ inst, float* __restrict__ flow,
+                                                     uint8_t* __restrict__ valid, const uint8_t* __restrict__ mask, const int32_t* __restrict__ cal_src,
+                                                     const int32_t* __restrict__ env_cal, const int n_cal) {
+  static_assert(!(FLOW && CAL), "the flow under per-env tables is refused");
+  const int n_out = oh * ow;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const bool in = pix < n_out;
+  const int sy = H / oh, sx = W / ow;
+  ViewPix p = NO_PIX;
+  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
+  if (in) {
+    const int i = pix / ow, j = pix - i * ow;
+    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
+    if constexpr (!CAL) p = view_pixel(lut, at, W, H);
+  }
+  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
+  const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
+  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);      // CAL: the env's own entry, the next env's chain of loads in flight (as k_depth's)
+  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
+#pragma clang loop unroll(disable)
+  for (int e = e0; e < e1; ++e) {
+    if constexpr (CAL) {
+      const float4 l = l_nxt;
+      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
+      p.live = l.z != 0.f; p.nx = l.x; p.ny = l.y;
+      src_px(l.x, l.y, W, H, p.sxp, p.syp);
+    }
+    if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's rows keep their bytes
+    const EnvCam c = cams[e];
+    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
+    const MapU m = map_u(rm);
+    float d = 0.f, fu = 0.f, fv = 0.f;
+    uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
+    bool ok = false;
+    if (p.live) {
+      float ds[4];
+      Hit hs[4];
+      int os[4];
+      scene_samples4<true, TBOX>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr,
+                                 objbox ? stris + (size_t)e * max_tris : nullptr, objbox ? rm.n_obj : 0, p.nx, p.ny, p.sxp, p.syp, sxn, syn,
+                                 __builtin_inff(), ds, hs, os, TBOX && objbox ? tribox + (size_t)e * max_tris : nullptr);
+      float db = ds[0], oxq = ox[0], oyq = oy[0];
+      Hit hb = hs[0];
+      int ob = os[0];
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+        if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; oxq = ox[q]; oyq = oy[q]; }
+      d = db;
+      who = ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE;
+      if (labels) {                                    // (wave-uniform) k_labels' mapping
+        if (ob >= 0) {
+          const int mid = objs[rm.obj_off + ob].mesh_id;
+          cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
+        } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
+        else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
+        else {
+          const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
+          cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
+          if (tr.flags & 2u) {
+            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade_msaa hands it to tile_color
+            float x, y;
+            tile_texel_xy(tr, fx, fz, x, y);
+            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
+            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+          }
+        }
+      }
+      if constexpr (FLOW) {                            // k_flow's body
+        const FlowRec& rec = recs[e];
+        const float Wf = (float)W, Hf = (float)H;
+        if (db < __builtin_inff() && rec.valid) {      // not sky, and a mark of this episode
+          const float xe = fmaf(oxq, sxn, p.nx) * c.tx, ye = fmaf(-oyq, syn, p.ny) * c.ty;
+          const float X = db * xe, Y = db * ye, Z = -db;
+          const FlowXf* xf = &rec.fix;
+          if (ob >= 0) {
+            const int slot = objs[rm.obj_off + ob].dyn_slot;
+            if (slot >= 0) xf = &rec.dyn[min(slot, DTSIM_MAX_DYNAMIC - 1)];
+          }
+          const float xp = fmaf(xf->M[0], X, fmaf(xf->M[1], Y, fmaf(xf->M[2], Z, xf->t[0])));
+          const float yp = fmaf(xf->M[3], X, fmaf(xf->M[4], Y, fmaf(xf->M[5], Z, xf->t[1])));
+          const float zp = fmaf(xf->M[6], X, fmaf(xf->M[7], Y, fmaf(xf->M[8], Z, xf->t[2])));
+          const FlowPt a = flow_image(X, Y, Z, rec.txc, rec.tyc, Wf, Hf, cal);
+          const FlowPt b = flow_image(xp, yp, zp, rec.txp, rec.typ, Wf, Hf, cal);
+          ok = b.w >= NEAR_Z && b.u >= 0.f && b.u < Wf && b.v >= 0.f && b.v < Hf;      // (a NaN fails every comparison)
+          if (ok) { fu = (float)(b.ax - a.ax); fv = (float)(b.ay - a.ay); }              // the one rounding of the difference
+        }
+      }
+    }
+    if (in) {
+      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      if (depth) {
+        if (f16) static_cast<__half*>(depth)[to] = __float2half_rn(d);
+        else static_cast<float*>(depth)[to] = d;
+      }
+      if (labels) labels[to] = (uint8_t)cls;
+      if (inst) inst[to] = (uint8_t)who;
+      if constexpr (FLOW) {
+        flow[2 * (size_t)e * (size_t)n_out + (size_t)pix] = fu;
+        flow[(2 * (size_t)e + 1) * (size_t)n_out + (size_t)pix] = fv;
+        if (valid) valid[to] = ok ? 1 : 0;
+      }
+    }
+  }
+}
+
 // ---- k_bev: the egocentric bird's-eye label map of every env (dtsim_bev; the quantity: include/dtsim.h) ------------------------------------
 // The grid of k_depth / k_labels: cell blocks x env chunks of DEPTH_ENVS.  A thread owns ONE cell; its place in the agent's frame -- f cells
 // ahead, s cells to the right, both multiples of one half and exact in float32 -- does not depend on the env and is computed once.  The env
@@ -964,11 +1093,34 @@ void dt_launch_flow_mark(hipStream_t s, const SimArrays& A, FlowMark* marks, con
 void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env, const IpmCal* cal,
                     float* flow, uint8_t* valid, int oh, int ow, const uint8_t* mask) {
   if (R.N <= 0) return;
-  hipLaunchKernelGGL(k_flow_setup, dim3((unsigned)((R.N + 63) / 64)), dim3(64), 0, s, A, marks, recs, per_env ? 1 : 0, R.W, R.H, mask);
+  dt_launch_flow_setup(s, R, A, marks, recs, per_env, mask);
   const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
   auto k = obj && R.tribox ? k_flow<true> : k_flow<false>;
   hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut),
                      obj ? R.objbox : nullptr, obj ? R.stris : nullptr, obj ? R.tribox : nullptr, R.objs, recs, cal, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, flow, valid, mask);
+}
+
+void dt_launch_flow_setup(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env,
+                          const uint8_t* mask) {
+  if (R.N <= 0) return;
+  hipLaunchKernelGGL(k_flow_setup, dim3((unsigned)((R.N + 63) / 64)), dim3(64), 0, s, A, marks, recs, per_env ? 1 : 0, R.W, R.H, mask);
+}
+
+void dt_launch_camera_maps(hipStream_t s, const RenderParams& R, const CameraMapsOut& o, const uint8_t* texel_class, const uint8_t* mesh_class,
+                           int n_mesh_class, const FlowRec* recs, const IpmCal* cal, int oh, int ow, const uint8_t* mask, const int32_t* cal_src,
+                           const int32_t* env_cal, int n_cal) {
+  if (R.N <= 0 || (!o.depth && !o.labels && !o.inst && !o.flow)) return;
+  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
+  const bool tb = obj && R.tribox;                     // ... and left its box stream
+  const bool tab = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations (never with flow: the caller refused it)
+  auto k = o.flow ? (tb ? k_camera_maps<true, false, true> : k_camera_maps<true, false, false>)
+           : tab  ? (tb ? k_camera_maps<false, true, true> : k_camera_maps<false, true, false>)
+                  : (tb ? k_camera_maps<false, false, true> : k_camera_maps<false, false, false>);
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut),
+                     obj ? R.objbox : nullptr, obj ? R.stris : nullptr, tb ? R.tribox : nullptr, R.objs, texel_class, mesh_class, n_mesh_class,
+                     R.tex_w, R.tex_h, o.flow ? recs : nullptr, o.flow ? cal : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, o.depth,
+                     o.f16 ? 1 : 0, o.labels, o.inst, o.flow, o.flow ? o.valid : nullptr, mask, tab && !o.flow ? cal_src : nullptr,
+                     tab && !o.flow ? env_cal : nullptr, tab && !o.flow ? n_cal : 0);
 }
 
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,

@@ -33,7 +33,7 @@ TILE_OTHER = 10
  FIELD_WHEEL_DIST, FIELD_RENDER_POS, FIELD_RENDER_PIPE) = range(29)
 # DTSIM_FIELD_RENDER_PIPE values (dtsim.h DTSIM_PIPE_*)
 PIPE_GENERIC, PIPE_GENERIC_ENV, PIPE_Q, PIPE_V3, PIPE_V3DR, PIPE_ENV_LIGHT = 1, 2, 3, 4, 5, 16
-KERNEL_STEP, KERNEL_RENDER, KERNEL_RESET, KERNEL_QUERY, KERNEL_OBSERVE = range(5)
+KERNEL_STEP, KERNEL_RENDER, KERNEL_RESET, KERNEL_QUERY, KERNEL_OBSERVE, KERNEL_CAMERA_MAPS = range(6)
 OBS_HWC, OBS_CHW, OBS_F32 = 0, 1, 2
 OBS_GRAY, OBS_MAX_DEPTH = 4, 16                # dtsim_obs_push: grey stack slots / the deepest stack
 BLEND_MAX = 8                                 # dtsim_blend_frames: the most frame batches in one blend
@@ -53,7 +53,7 @@ EXPORTS = [
     "dtsim_abi_version", "dtsim_last_error", "dtsim_device_count", "dtsim_create", "dtsim_destroy",
     "dtsim_set_assets", "dtsim_set_maps", "dtsim_set_distortion_lut", "dtsim_reset",
     "dtsim_set_spawn_pool", "dtsim_step", "dtsim_step_ex", "dtsim_render", "dtsim_render_ex", "dtsim_set_segment_assets", "dtsim_frames_devptr", "dtsim_frames_bytes",
-    "dtsim_bind_frames", "dtsim_draw_lines", "dtsim_draw_leds", "dtsim_allgather_frames", "dtsim_observe", "dtsim_observe_cubic", "dtsim_render_masked", "dtsim_observe_masked", "dtsim_observe_cubic_masked", "dtsim_copy_rows", "dtsim_obs_push", "dtsim_blend_frames", "dtsim_depth", "dtsim_depth_masked", "dtsim_set_label_assets", "dtsim_labels", "dtsim_labels_masked", "dtsim_instances", "dtsim_instances_masked", "dtsim_boxes", "dtsim_bev", "dtsim_set_ipm_calibrations", "dtsim_ipm", "dtsim_flow_mark", "dtsim_flow", "dtsim_flow_masked", "dtsim_set_reset_sampler", "dtsim_reset_done", "dtsim_query", "dtsim_read_agent", "dtsim_read", "dtsim_write", "dtsim_field_devptr",
+    "dtsim_bind_frames", "dtsim_draw_lines", "dtsim_draw_leds", "dtsim_allgather_frames", "dtsim_observe", "dtsim_observe_cubic", "dtsim_render_masked", "dtsim_observe_masked", "dtsim_observe_cubic_masked", "dtsim_copy_rows", "dtsim_obs_push", "dtsim_blend_frames", "dtsim_depth", "dtsim_depth_masked", "dtsim_set_label_assets", "dtsim_labels", "dtsim_labels_masked", "dtsim_instances", "dtsim_instances_masked", "dtsim_boxes", "dtsim_bev", "dtsim_set_ipm_calibrations", "dtsim_ipm", "dtsim_flow_mark", "dtsim_flow", "dtsim_flow_masked", "dtsim_camera_maps", "dtsim_camera_maps_masked", "dtsim_set_reset_sampler", "dtsim_reset_done", "dtsim_query", "dtsim_read_agent", "dtsim_read", "dtsim_write", "dtsim_field_devptr",
     "dtsim_field_bytes", "dtsim_state_bytes", "dtsim_sync", "dtsim_stream", "dtsim_profile_read",
     "dtsim_set_distortion_luts", "dtsim_build_remap_maps", "dtsim_fill_pack_remap",
 ]
@@ -142,6 +142,11 @@ class Probe(C.Structure):
     ]
 
 
+class CameraMapsOut(C.Structure):
+    """dtsim_camera_maps_out: the device pointers of the outputs that are on, NULL for the others."""
+    _fields_ = [("depth", C.c_void_p), ("labels", C.c_void_p), ("instances", C.c_void_p), ("flow", C.c_void_p), ("flow_valid", C.c_void_p)]
+
+
 class AgentInfo(C.Structure):
     """dtsim_agent_info: what Simulator.step returns about one env besides the observation."""
     _fields_ = [
@@ -226,6 +231,8 @@ def load(path: str | None = None):
         "dtsim_flow_mark": (ci, [vp, vp]),
         "dtsim_flow": (ci, [vp, vp, vp, ci, ci, C.c_uint32]),
         "dtsim_flow_masked": (ci, [vp, vp, vp, ci, ci, C.c_uint32, vp]),
+        "dtsim_camera_maps": (ci, [vp, C.POINTER(CameraMapsOut), ci, ci, C.c_uint32]),
+        "dtsim_camera_maps_masked": (ci, [vp, C.POINTER(CameraMapsOut), ci, ci, C.c_uint32, vp]),
         "dtsim_query": (ci, [vp, ci, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double, C.POINTER(Probe)]),
         "dtsim_read_agent": (ci, [vp, ci, C.POINTER(AgentInfo)]),
         "dtsim_read": (ci, [vp, ci, vp, sz]),

@@ -1007,6 +1007,52 @@ class BatchedSimulator:
         self._map_pass(self._lib.dtsim_flow, self._lib.dtsim_flow_masked, mp, ptr, vp, h, w, 0)
         return out
 
+    def camera_maps(self, height=None, width=None, *, depth=None, depth_dtype: str = "float32", labels=None, instances=None, flow=None,
+                    flow_valid=None, mask=None):
+        """depth(), labels(), instances() and flow() of ONE size from one launch (dtsim_camera_maps, include/dtsim.h): the pixel is classified
+        once -- what each single pass pays for -- and every output that is on is taken from that one nearest sample, so they agree with each
+        other pixel by pixel.  Each of `depth`, `labels`, `instances`, `flow`, `flow_valid` is None (off), True (the simulator's own persistent
+        tensor: the one the single method returns without `out`) or a tensor to write into, checked as the single method checks its `out`;
+        `flow_valid` needs `flow`.  Returns a dict of the outputs that are on.  `depth_dtype`, the size and `mask` as depth()'s; labels install
+        the default tables at first use, as labels() does; flow refuses what flow() refuses (per-env calibrations, undistort=True) and needs a
+        flow_mark() on this simulator first (an env without a mark of its episode gets zeros, as in flow()).  Needs a preceding render() of the
+        current state.  With mesh objects in view after a second render from another pose, depth, labels and instances follow flow()'s
+        triangle test (a triangle the pass culled is skipped), where the single passes can still see its stale record.  A bad argument raises
+        ValueError before anything is launched."""
+        if depth_dtype not in self._DEPTH_DTYPES:
+            raise ValueError(f"camera_maps: depth_dtype {depth_dtype!r}: 'float32' or 'float16'")
+        h, w = self._map_size("camera_maps", "the maps are", height, width)
+        asked = dict(depth=depth, labels=labels, instances=instances, flow=flow, flow_valid=flow_valid)
+        if all(v is None or v is False for v in asked.values()):
+            raise ValueError("camera_maps: no output asked for")
+        on = {k: v for k, v in asked.items() if v is not None and v is not False}
+        if "flow_valid" in on and "flow" not in on:
+            raise ValueError("camera_maps: flow_valid needs flow")
+        if "flow" in on:
+            if self.undistort:
+                raise ValueError("camera_maps: flow with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
+            if self._cal is not None:
+                raise ValueError("camera_maps: flow with per-env calibrations (camera_rand, set_camera_calibrations) is not supported")
+        mp = self._mask_arg(mask)
+        n = self.num_envs
+        kinds = {"depth": ((n, h, w), depth_dtype), "labels": ((n, h, w), "uint8"), "instances": ((n, h, w), "uint8"),
+                 "flow": ((n, 2, h, w), "float32"), "flow_valid": ((n, h, w), "uint8")}
+        res, arg, spans = {}, _ffi.CameraMapsOut(), []
+        for name, v in on.items():
+            shape, dtype = kinds[name]
+            res[name], ptr = self._result(name, None if v is True else v, shape, dtype)
+            setattr(arg, name, ptr.value)
+            spans.append((ptr.value, ptr.value + int(np.prod(shape)) * self._TYPESTR[dtype][1], name))
+        spans.sort()
+        for (a0, a1, an), (b0, b1, bn) in zip(spans, spans[1:]):
+            if b0 < a1:
+                raise ValueError(f"camera_maps: {an} and {bn} overlap")
+        if "labels" in on:
+            self._need_label_assets()
+        flags = (_ffi.DEPTH_F16 if "depth" in on and depth_dtype == "float16" else 0) | self._env_tables_flag()
+        self._map_pass(self._lib.dtsim_camera_maps, self._lib.dtsim_camera_maps_masked, mp, C.byref(arg), h, w, flags)
+        return res
+
     @staticmethod
     def _state_array_offset(name: str, n: int) -> int:
         """Byte offset of array `name` in the state blob of n envs (csrc/state_fields.h DT_STATE_ARRAYS: [planes][n] float64 arrays in slab

@@ -102,6 +102,14 @@ there is 0, 0).  A camera post-pass like depth, under the same rules, but the on
 `frame_skip` sub-updates; an env restarted in the step has no mark of its new episode: its rows are all 0 (flow and flags); with
 `final_obs=True` `info["final_flow"]` is the finished env's last flow.  After `reset()` the map is all 0 too.  `motion_blur`,
 `camera_rand` (even with `camera_rand_maps`) and `undistort=True` raise ValueError.
+
+One launch for the camera maps (`fused_maps=True`, opt-in): those of `depth_shape`, `label_shape`, `instance_shape` and `flow_shape` that are
+set must be equal, and at least one must be set (else ValueError, before a device is touched).  Every place above where the depth, label,
+instance and flow passes stand then holds ONE `BatchedSimulator.camera_maps` call (`dtsim_camera_maps`, include/dtsim.h), which classifies
+each pixel once and writes all of them; boxes, bev and ipm follow as before.  The outputs are the same quantities in the same tensors, and
+everything composes as without the option; with mesh objects in view the depth, label and instance bytes can differ from the single
+passes' on the few pixels where those still see a culled triangle's stale record (profiles/camera_maps_parity.txt).  With
+`fused_maps=False` (the default) the env makes the calls above, call for call.
 """
 from __future__ import annotations
 
@@ -132,7 +140,7 @@ class DuckietownVecEnv:
                  bev_shape: Optional[Tuple[int, int]] = None, bev_cell: float = 0.02, bev_rows_behind: int = 0,
                  bev_instances: bool = False, ipm_shape: Optional[Tuple[int, int]] = None, ipm_cell: float = 0.02,
                  ipm_rows_behind: int = 0, ipm_valid: bool = False, camera_rand_maps: bool = False,
-                 flow_shape: Optional[Tuple[int, int]] = None, flow_valid: bool = False, **sim_kwargs):
+                 flow_shape: Optional[Tuple[int, int]] = None, flow_valid: bool = False, fused_maps: bool = False, **sim_kwargs):
         # (the argument errors come before a device or the simulator is touched)
         if isinstance(frame_stack, bool) or not isinstance(frame_stack, (int, np.integer)) or not 1 <= frame_stack <= _ffi.OBS_MAX_DEPTH:
             raise ValueError(f"frame_stack must be an integer in 1 .. {_ffi.OBS_MAX_DEPTH}, got {frame_stack!r}")
@@ -160,6 +168,15 @@ class DuckietownVecEnv:
         if flow_shape is not None and sim_kwargs.get("undistort"):
             raise ValueError("flow_shape with undistort=True is not supported (the frames show UndistortWrapper's view, not the camera's)")
         self.flow_shape = self._camera_map_shape("flow_shape", flow_shape, cam)
+        self.fused_maps = bool(fused_maps)
+        if self.fused_maps:
+            named = {k: v for k, v in (("depth_shape", self.depth_shape), ("label_shape", self.label_shape),
+                                       ("instance_shape", self.instance_shape), ("flow_shape", self.flow_shape)) if v is not None}
+            if not named:
+                raise ValueError("fused_maps=True needs at least one of depth_shape, label_shape, instance_shape, flow_shape (it fuses their passes)")
+            if len(set(named.values())) != 1:
+                raise ValueError(f"fused_maps=True needs one size for all camera maps (one launch fills them), got {named}")
+            self._fused_shape = next(iter(named.values()))
         self.bev_shape, self.bev_cell, self.bev_rows_behind = None, bev_cell, bev_rows_behind
         if bev_shape is None:
             if bev_instances:
@@ -322,7 +339,24 @@ class DuckietownVecEnv:
         """The passes of the outputs that are on, in the table's order, each into the env's own tensor (`mask`: only those envs' rows): of the
         state the last render() showed the depth, then the labels, then the instances and their boxes -- labels and instances of one shape
         come from one launch --, then the flow since the envs' marks (and its flags); then, of the current state, the bird's-eye map (and its ids); last, of the frame batch as it stands, the
-        ground-projected image (and its flags)."""
+        ground-projected image (and its flags).  fused_maps: the camera maps -- depth, labels, instances, flow -- by one camera_maps call."""
+        if self.fused_maps:
+            # ONE launch in place of the depth / labels / instances / flow calls below; the rest as without the option
+            self.sim.camera_maps(self._fused_shape[0], self._fused_shape[1], depth=self.depth, depth_dtype=self.depth_dtype, labels=self.labels,
+                                 instances=self.instances, flow=self.flow, flow_valid=self.flow_valid, mask=mask)
+            if self.boxes is not None:
+                self.sim.boxes(self.instances, out=self.boxes, mask=mask)
+        else:
+            self._single_map_passes(mask)
+        if self.bev is not None:
+            self.sim.bev(self.bev_shape[0], self.bev_shape[1], cell=self.bev_cell, rows_behind=self.bev_rows_behind, out=self.bev, mask=mask,
+                         instances_out=self.bev_instances)
+        if self.ipm is not None:
+            self.sim.ipm(self.ipm_shape[0], self.ipm_shape[1], cell=self.ipm_cell, rows_behind=self.ipm_rows_behind, chw=self.chw, out=self.ipm,
+                         mask=mask, valid_out=self.ipm_valid)
+
+    def _single_map_passes(self, mask):
+        """The camera maps by their single passes (fused_maps=False): depth, labels, instances and boxes, flow."""
         if self.depth is not None:
             self.sim.depth(self.depth_shape[0], self.depth_shape[1], dtype=self.depth_dtype, out=self.depth, mask=mask)
         fused = self.labels is not None and self.label_shape == self.instance_shape
@@ -335,12 +369,6 @@ class DuckietownVecEnv:
                 self.sim.boxes(self.instances, out=self.boxes, mask=mask)
         if self.flow is not None:
             self.sim.flow(self.flow_shape[0], self.flow_shape[1], out=self.flow, mask=mask, valid_out=self.flow_valid)
-        if self.bev is not None:
-            self.sim.bev(self.bev_shape[0], self.bev_shape[1], cell=self.bev_cell, rows_behind=self.bev_rows_behind, out=self.bev, mask=mask,
-                         instances_out=self.bev_instances)
-        if self.ipm is not None:
-            self.sim.ipm(self.ipm_shape[0], self.ipm_shape[1], cell=self.ipm_cell, rows_behind=self.ipm_rows_behind, chw=self.chw, out=self.ipm,
-                         mask=mask, valid_out=self.ipm_valid)
 
     def _keep_final(self, obs, done, info):
         """final_obs: the finished envs' rows of `obs` (stacked: of the whole history) and of every output that is on, before the reset
@@ -366,6 +394,10 @@ class DuckietownVecEnv:
         with self.torch.cuda.stream(self.stream):
             self.sim.reset()                                        # device sampler (dtsim_reset(states = NULL))
             obs = self._show(first=self._all)
+            if self.fused_maps and self.flow is not None:
+                # camera_maps refuses a flow before the first flow_mark where flow() answers with zeros: a mark of no env gives the handle its
+                # (empty) marks, and the reset's map is flow()'s -- all 0
+                self.sim.flow_mark(mask=self.torch.zeros(self.num_envs, dtype=self.torch.uint8, device=self.device))
             self._map_passes()
             self._mark()
             if self._blur:

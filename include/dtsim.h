@@ -269,7 +269,8 @@ enum {
 #define DTSIM_PIPE_ENV_LIGHT 16   /* flag: each env lit by its own light on the shared camera */
 
 /* kernels for dtsim_profile_read */
-enum { DTSIM_KERNEL_STEP = 0, DTSIM_KERNEL_RENDER = 1, DTSIM_KERNEL_RESET = 2, DTSIM_KERNEL_QUERY = 3, DTSIM_KERNEL_OBSERVE = 4, DTSIM_KERNEL__COUNT = 5 };
+enum { DTSIM_KERNEL_STEP = 0, DTSIM_KERNEL_RENDER = 1, DTSIM_KERNEL_RESET = 2, DTSIM_KERNEL_QUERY = 3, DTSIM_KERNEL_OBSERVE = 4,
+       DTSIM_KERNEL_CAMERA_MAPS = 5 /* dtsim_camera_maps' kernel (without its flow set-up launch) */, DTSIM_KERNEL__COUNT = 6 };
 
 int dtsim_abi_version(void);
 const char* dtsim_last_error(void);
@@ -748,6 +749,32 @@ int dtsim_ipm(dtsim_t* h, uint8_t* img, uint8_t* valid, int32_t* src, int oh, in
 int dtsim_flow_mark(dtsim_t* h, const uint8_t* mask);
 int dtsim_flow(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags);
 int dtsim_flow_masked(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, uint32_t flags, const uint8_t* mask);
+
+/* Depth, labels, instances and flow of ONE size from one launch: the learner that turns several of them on pays the classification of a pixel
+ * -- four samples against the planes and the z-buffer of the env's projected triangles, which is the cost of each single pass -- once.
+ * THE QUANTITY, by reference.  Every non-null output is the quantity of its own entry point -- depth: dtsim_depth's (half with
+ * DTSIM_DEPTH_F16), labels: dtsim_labels', instances: dtsim_instances', flow / flow_valid: dtsim_flow's -- and all come from ONE classification
+ * of the pixel: the sample with the smallest eye depth, ties to the lowest index, sky counting as +inf.  So where instances is o + 1, labels is
+ * the class of object o's mesh; depth is the depth of the sample that owns labels and instances; flow is the motion of that sample's surface
+ * point.  The triangles are tested as dtsim_flow tests them (the boxes of the pass itself: a triangle the pass culled is skipped).
+ * SIZE.  dtsim_depth's, one (oh, ow) for all outputs; the shapes are those of the single entry points.  flags: DTSIM_DEPTH_F16 and
+ * DTSIM_MAP_ENV_TABLES (dtsim_depth's PER-ENV TABLES), nothing else.
+ * STATE.  dtsim_depth's rules; labels needs dtsim_set_label_assets; with flow also dtsim_flow's rules: a fisheye handle needs
+ * dtsim_set_ipm_calibrations, installed per-env distortion tables are refused with or without DTSIM_MAP_ENV_TABLES, and -- where dtsim_flow
+ * answers with an all-zero map -- a handle on which dtsim_flow_mark has never been called is refused (an env without a mark of its episode
+ * still gets flow 0, valid 0).  All DTSIM_E_STATE.  DTSIM_E_INVALID: a null handle, struct or mask, all five pointers null, flow_valid without
+ * flow, outputs that overlap, a bad size, an unknown flag.  A failed call launches nothing and writes nothing.  With flow the call first
+ * brings the envs' flow records up to date, as dtsim_flow does.  Asynchronous, stream-ordered.  One state (and one mark) gives the same bytes
+ * on every call and for every env index.  The masked form: as dtsim_depth_masked, for every output. */
+typedef struct dtsim_camera_maps_out {
+  void* depth;            /* [N][oh][ow] float32, or half with DTSIM_DEPTH_F16; or NULL */
+  uint8_t* labels;        /* [N][oh][ow]; or NULL (needs the label tables, else DTSIM_E_STATE) */
+  uint8_t* instances;     /* [N][oh][ow]; or NULL */
+  float* flow;            /* [N][2][oh][ow]; or NULL (needs marks as dtsim_flow does) */
+  uint8_t* flow_valid;    /* [N][oh][ow]; or NULL; needs flow */
+} dtsim_camera_maps_out;
+int dtsim_camera_maps(dtsim_t* h, const dtsim_camera_maps_out* out, int oh, int ow, uint32_t flags);
+int dtsim_camera_maps_masked(dtsim_t* h, const dtsim_camera_maps_out* out, int oh, int ow, uint32_t flags, const uint8_t* mask);
 
 /* Geometry queries of the reference at arbitrary poses, evaluated on the device against
  * env env_idx[q]'s world (its map, dynamic objects and visibility): _valid_pose,

@@ -24,7 +24,10 @@ small: (64, 64) at 0.04) against the plain step in the SAME run -- VARIANTS=plai
 variants ipm | ipm_small | ipm_only (no flags) | bev_ipm (the bird's-eye maps and the ground projection, input and target) can be listed.
 FLOW=1 (or full): the whole step with info["flow"] + info["flow_valid"] (DuckietownVecEnv(flow_shape=(120, 160), flow_valid=True); full:
 480 x 640) against the plain step in the SAME run -- VARIANTS=plain,flow (or plain,flow_full) with ROUNDS=5 unless given; the variants
-flow | flow_full | flow_only (no flags) can be listed."""
+flow | flow_full | flow_only (no flags) can be listed.
+FUSED=1: the whole step with depth, labels, instances + boxes and flow + flags at 120 x 160, by the single passes (`all_maps`) and by ONE
+dtsim_camera_maps launch (`all_maps_fused`: DuckietownVecEnv(fused_maps=True)), against the plain step in the SAME run --
+VARIANTS=plain,all_maps,all_maps_fused with ROUNDS=5 unless given; the two variants can be listed like any other."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-duckietown_amd"))
@@ -44,6 +47,7 @@ INSTANCES = os.environ.get("INSTANCES", "0")
 BEV = os.environ.get("BEV", "0")
 IPM = os.environ.get("IPM", "0")
 FLOW = os.environ.get("FLOW", "0")
+FUSED = os.environ.get("FUSED", "0")
 MAP = os.environ.get("MAP", "small_loop")
 MAP_TAG = "" if MAP == "small_loop" else " " + MAP          # (the default map's lines read as they always did)
 VARIANTS = [v for v in os.environ.get("VARIANTS", "").split(",") if v]
@@ -57,12 +61,14 @@ if IPM != "0" and not VARIANTS:
     VARIANTS, ROUNDS = ["plain", "ipm_small" if IPM == "small" else "ipm"], int(os.environ.get("ROUNDS", "5"))
 if FLOW != "0" and not VARIANTS:
     VARIANTS, ROUNDS = ["plain", "flow_full" if FLOW == "full" else "flow"], int(os.environ.get("ROUNDS", "5"))
+if FUSED != "0" and not VARIANTS:
+    VARIANTS, ROUNDS = ["plain", "all_maps", "all_maps_fused"], int(os.environ.get("ROUNDS", "5"))
 a = torch.rand((N, 2), device="cuda") * 2 - 1
 
 
 class Variant:
     def __init__(self, name, stack=1, gray=False, normalize=True, emulate=False, blur="0", wheels=False, depth="0", depth_dtype="float32", labels="0", instances="0",
-                 boxes=True, bev="0", bev_instances=True, ipm="0", ipm_valid=True, flow="0", flow_valid=True):
+                 boxes=True, bev="0", bev_instances=True, ipm="0", ipm_valid=True, flow="0", flow_valid=True, fused=False):
         self.name, self.emulate, self.depth, self.rerender = name, emulate, stack, blur == "rerender"
         kw = {} if emulate or (stack == 1 and not gray) else dict(frame_stack=stack, grayscale=gray)
         if blur != "0":
@@ -81,6 +87,8 @@ class Variant:
             kw.update(ipm_shape=(64, 64) if ipm == "small" else (128, 128), ipm_cell=0.04 if ipm == "small" else 0.02, ipm_valid=ipm_valid)
         if flow != "0":
             kw.update(flow_shape=(480, 640) if flow == "full" else (120, 160), flow_valid=flow_valid)
+        if fused:
+            kw.update(fused_maps=True)
         self.env = DuckietownVecEnv(MAP, N, obs_shape=(120, 160), seed=0, domain_rand=False, distortion=True, final_obs=FINAL,
                                     normalize=normalize, **kw)
         obs = self.env.reset()
@@ -133,6 +141,8 @@ def make(name):
             "bev_ipm": lambda: Variant("bev + ids + ipm + valid 128 x 128 at 0.02 m", bev="1", ipm="1"),
             "flow": lambda: Variant("flow + valid 120 x 160", flow="1"), "flow_full": lambda: Variant("flow + valid 480 x 640", flow="full"),
             "flow_only": lambda: Variant("flow 120 x 160, no flags", flow="1", flow_valid=False),
+            "all_maps": lambda: Variant("depth + labels + instances + boxes + flow + valid 120 x 160", depth="1", labels="1", instances="1", flow="1"),
+            "all_maps_fused": lambda: Variant("the same, fused_maps=True", depth="1", labels="1", instances="1", flow="1", fused=True),
             "wheels": lambda: Variant("plain, wheels"), "blur": lambda: Variant("motion blur", blur="1"),
             "blur_rerender": lambda: Variant("motion blur, first frame rendered again", blur="rerender")}[name]()
 
