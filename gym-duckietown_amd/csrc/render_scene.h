@@ -113,7 +113,6 @@ struct MsaaPos { float x[4], y[4]; };
 constexpr MsaaPos MSAA_POS = {{-0.125f, 0.375f, -0.375f, 0.125f}, {0.375f, 0.125f, -0.125f, -0.375f}};
 
 // The centre (sx, sy), in pixels of the W x H rectilinear source image (+y down), of the NDC point (nx, ny): of a LUT entry l, (l.x, l.y).
-// One site keeps a written-out copy: k_labels (render_views.hip), whose instructions move when it calls this; the reason stands there.
 __device__ inline void src_px(const float nx, const float ny, const int W, const int H, float& sx, float& sy) {
   sx = (nx + 1.f) * 0.5f * (float)W; sy = (1.f - ny) * 0.5f * (float)H;
 }

@@ -2,7 +2,9 @@
 // its projected mesh triangles (ScreenTri / ObjBox) and the camera table (lut).  None of them uses the raster's machinery (queues, work
 // lists, quad records, workgroup map, per-pixel tables); what they share with the pass is render_scene.h, and the unit is compiled with
 // render.hip's flags (build.py), so that classify() and test_tri are the frame's own code here.  In order: k_overlay_lines, scene_samples4
-// (the opaque scene at the four samples of a pixel), k_overlay_leds, k_depth, k_labels, k_flow*, k_camera_maps, k_bev, k_ipm_*, then their dt_launch_* (dtsim_dev.h).
+// (the opaque scene at the four samples of a pixel), k_overlay_leds, the rules the camera-map kernels share (out_camera_pixel, EnvEntry, EnvScene,
+// Winner / take_nearer, instance_id, tile_texel_class, sample_class, flow_image and the flow's four rules, store_depth), k_depth, k_labels, k_flow*, k_camera_maps, k_bev, k_ipm_*, then
+// view_scene and their dt_launch_* (dtsim_dev.h).
 #include "dtsim_dev.h"
 #include "render_scene.h"
 #include "flow_transform.h"
@@ -293,13 +295,166 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
   }
 }
 
+// ---- the rules that the camera-map kernels (k_depth, k_labels, k_flow, k_camera_maps) share, each stated once -------------------------------
+// Output pixel `pix` = (i, j) of the [oh][ow] map is camera pixel (i sy + sy / 2, j sx + sx / 2), sy = H / oh, sx = W / ow: point-sampled, only
+// those pixels are traced.
+__device__ __forceinline__ size_t out_camera_pixel(const int pix, const int W, const int H, const int oh, const int ow) {
+  const int sx = W / ow, sy = H / oh;
+  const int i = pix / ow, j = pix - i * ow;
+  return (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
+}
+// ... and (e, pix) of an [N][oh * ow] map, or of plane k (0: x, 1: y) of an [N][2][oh * ow] flow map, is element:
+__device__ __forceinline__ size_t map_at(const int e, const int n_out, const int pix) { return (size_t)e * (size_t)n_out + (size_t)pix; }
+__device__ __forceinline__ size_t flow_at(const int e, const int n_out, const int pix, const int k) { return (2 * (size_t)e + k) * (size_t)n_out + (size_t)pix; }
+
+// The table entry of a thread's camera pixel `at` (in: the thread owns one) for each env of its chunk.  Without CAL it is the shared table's,
+// loaded once.  CAL: the entry depends on the env -- env_cal[e], then the calibration's source index, then the identity table's entry there:
+// three dependent loads (cal_entry).  pixel(e, e1) is called at the top of the loop body, behind nothing: it hands out env e's entry and
+// issues the chain of env e + 1, which is waited for at the top of the next iteration, behind this env's scene.
+template <bool CAL>
+struct EnvEntry {
+  const float4* lut; const int32_t* cal_src; const int32_t* env_cal;
+  int n_cal; bool in; size_t at; int W, H;
+  ViewPix p;
+  float4 l_nxt;
+  __device__ __forceinline__ EnvEntry(const float4* lut, const int32_t* cal_src, const int32_t* env_cal, const int n_cal, const bool in, const size_t at,
+                             const int W, const int H, const int e0)
+      : lut(lut), cal_src(cal_src), env_cal(env_cal), n_cal(n_cal), in(in), at(at), W(W), H(H), p(NO_PIX), l_nxt(make_float4(0.f, 0.f, 0.f, 0.f)) {
+    if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
+    else if (in) p = view_pixel(lut, at, W, H);
+  }
+  __device__ __forceinline__ ViewPix pixel(const int e, const int e1) {
+    if constexpr (CAL) {
+      const float4 l = l_nxt;
+      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
+      p.live = l.z != 0.f; p.nx = l.x; p.ny = l.y;
+      src_px(l.x, l.y, W, H, p.sxp, p.syp);
+    }
+    return p;
+  }
+};
+
+// What a pixel reads of env e, all at a wave-uniform index (read-only __restrict__ pointers: scalar loads): its camera record, its map and the
+// rows of the pass's ObjBox / ScreenTri / (TBOX) box streams; objbox null: the pass projected no mesh triangles.  The map id is clamped:
+// calling a masked form with another mask than the pass's is the caller's error (include/dtsim.h) and its result is undefined -- the record of
+// a skipped env is an older state's, or the zeros the scratch starts with -- and the clamp only keeps that error from indexing outside the map
+// table on a device others share.
+// (The env's rows are member functions, evaluated at scene_samples4's call inside `if (p.live)`: as fields filled before it, +3 instructions, +2 SGPRs.)
+struct EnvScene {
+  EnvCam c; const RenderMapDev* rm; MapU m;
+  int e, max_tris; const ObjBox* objbox; const ScreenTri* stris; const float4* tribox;
+  __device__ const ObjBox* boxes() const { return objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr; }
+  __device__ const ScreenTri* tris() const { return objbox ? stris + (size_t)e * max_tris : nullptr; }
+  __device__ const float4* tri_boxes() const { return objbox ? tribox + (size_t)e * max_tris : nullptr; }
+  __device__ int n_obj() const { return objbox ? rm->n_obj : 0; }
+};
+__device__ __forceinline__ EnvScene env_scene(const int e, const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const int n_maps,
+                                     const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris, const float4* __restrict__ tribox,
+                                     const int max_tris) {
+  EnvScene s;
+  s.c = cams[e];
+  s.rm = &maps[min((unsigned)s.c.map_id, (unsigned)(n_maps - 1))];
+  s.m = map_u(*s.rm);
+  s.e = e; s.max_tris = max_tris; s.objbox = objbox; s.stris = stris; s.tribox = tribox;
+  return s;
+}
+// scene_samples4 of that env at that pixel; sky = +inf.
+template <bool WHO, bool TBOX = false>
+__device__ __forceinline__ void scene_samples4(const EnvScene& s, const TileLds* tiles, const ViewPix& p, const float sxn, const float syn, float depth[4],
+                                      Hit* hits, int* obj) {
+  scene_samples4<WHO, TBOX>(s.c, s.m, tiles, s.boxes(), s.tris(), s.n_obj(), p.nx, p.ny, p.sxp, p.syp, sxn, syn, __builtin_inff(), depth, hits, obj,
+                            TBOX ? s.tri_boxes() : nullptr);
+}
+
+// The WINNER of a pixel: the sample with the smallest depth, ties to the lowest index; sky = +inf, so it wins only when all four are sky.  d: its
+// depth, o: its object or -1, ox / oy: its sample offsets, h: its plane hit; unread members fold away.  A kernel folds samples 1..3 into sample 0
+// in its own unrolled loop: a function handed the arrays keeps them in scratch or changes instruction counts (profiles/render_views_isa.txt).
+struct Winner { float d; int o; float ox, oy; Hit h; };
+__device__ __forceinline__ Winner first_sample(const float d, const int o, const Hit& h) { return {d, o, MSAA_POS.x[0], MSAA_POS.y[0], h}; }
+__device__ __forceinline__ void take_nearer(Winner& w, const float d, const int o, const int q, const Hit& h) {
+  if (d < w.d) { w.d = d; w.o = o; w.ox = MSAA_POS.x[q]; w.oy = MSAA_POS.y[q]; w.h = h; }
+}
+// Its instance id: o + 1 of its object (the o of scene_samples4<true>: the env's map's object list), else DTSIM_INSTANCE_NONE.
+__device__ __forceinline__ uint32_t instance_id(const int ob) { return ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE; }
+
+// The class of the nearest texel of a textured tile at tile fraction (fx, fz): the texel coordinates are tile_texel_xy's, the ones tile_color
+// filters at, with the half-texel shift taken back: floor(x + 0.5), wrapped.  tex_w, tex_h: the one (power-of-two) size of all tile textures;
+// texel_class: dt_pack_label_tables' pool, addressed like R.texels.  A camera pixel (sample_class) and a BEV cell (k_bev) that hit one world
+// point name one class because both call this.
+__device__ __forceinline__ uint32_t tile_texel_class(const TileLds& tr, const float fx, const float fz, const int tex_w, const int tex_h,
+                                            const uint8_t* __restrict__ texel_class) {
+  float x, y;
+  tile_texel_xy(tr, fx, fz, x, y);
+  const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
+  return texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
+}
+// Owner -> class, of the winner's object ob (or -1) and plane hit h: the mesh table through the map's object-instance table, the two fixed plane
+// classes, or for a tile the class of its texel.
+__device__ __forceinline__ uint32_t sample_class(const int ob, const Hit& h, const EnvScene& s, const TileLds* __restrict__ tiles,
+                                                 const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
+                                                 const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h) {
+  if (ob >= 0) return mesh_class[min((unsigned)objs[s.rm->obj_off + ob].mesh_id, (unsigned)(n_mesh_class - 1))];
+  if (h.cls == CLS_SKY) return DTSIM_LABEL_SKY;
+  if (h.cls == CLS_GROUND) return DTSIM_LABEL_GROUND;
+  const TileLds tr = tiles[s.m.tile_off + h.tj * s.m.gw + h.ti];
+  if (!(tr.flags & 2u)) return DTSIM_LABEL_GROUND;     // a present tile without a texture has no texel table
+  // the tile fraction, as shade_msaa hands it to tile_color
+  return tile_texel_class(tr, h.wx * s.m.its - (float)h.ti, h.wz * s.m.its - (float)h.tj, tex_w, tex_h, texel_class);
+}
+
+// An eye-space point on the image: w, the rectilinear (u, v) of dtsim_ipm's step 1 and A(u, v) -- the identity, or with a calibration the
+// forward model at (u - 0.5, v - 0.5) (ipm_project.h dt_ipm_forward, in float64: in float32 its 25 operations would take the count of
+// roundings R of tests/test_flow_model_host.py past 32).  Both terms of a flow go through this one function, so one point gives one value.
+struct FlowPt { double ax, ay; float w, u, v; };
+__device__ inline FlowPt flow_image(const float x, const float y, const float z, const float tx, const float ty, const float Wf, const float Hf,
+                                    const IpmCal* __restrict__ cal) {
+  FlowPt p;
+  p.w = -z;
+  p.u = (x / p.w / tx + 1.f) * 0.5f * Wf;             // R: 4 roundings (two divisions, the sum, the product by W; x 0.5 is exact)
+  p.v = (1.f - y / p.w / ty) * 0.5f * Hf;             //    (the same 4, of the other coordinate)
+  p.ax = (double)p.u; p.ay = (double)p.v;
+  if (cal) dt_ipm_forward(*cal, p.ax - 0.5, p.ay - 0.5, 0.0, p.ax, p.ay);   // (wave-uniform) R: none, float64
+  return p;
+}
+
+// The flow of the winner, rule by rule (as ONE function they change k_flow's instruction count: profiles/render_views_isa.txt).
+// Its eye-space hit X = d (xe, ye, -1), rebuilt from the sample's own ray (scene_samples4's statement of it) at the sample's depth:
+struct Eye3 { float x, y, z; };
+__device__ __forceinline__ Eye3 winner_eye_point(const Winner& w, const ViewPix& p, const EnvCam& c, const float sxn, const float syn) {
+  const float xe = fmaf(w.ox, sxn, p.nx) * c.tx, ye = fmaf(-w.oy, syn, p.ny) * c.ty;
+  return {w.d * xe, w.d * ye, -w.d};
+}
+// ... the ONE pair (M, t) it moves by: the static one, or the winning object's dynamic slot's (a per-lane read, only on lanes such an object owns):
+__device__ __forceinline__ const FlowXf* flow_xf(const FlowRec& rec, const int ob, const RenderMapDev& rm, const ObjInstDev* objs) {
+  const FlowXf* xf = &rec.fix;
+  if (ob >= 0) {
+    const int slot = objs[rm.obj_off + ob].dyn_slot;
+    if (slot >= 0) xf = &rec.dyn[min(slot, DTSIM_MAX_DYNAMIC - 1)];
+  }
+  return xf;
+}
+// ... M X + t.  R: 3 roundings per coordinate (three fused multiply-adds), x and w both enter u: 6
+__device__ __forceinline__ Eye3 flow_apply(const FlowXf* xf, const Eye3& X) {
+  return {fmaf(xf->M[0], X.x, fmaf(xf->M[1], X.y, fmaf(xf->M[2], X.z, xf->t[0]))), fmaf(xf->M[3], X.x, fmaf(xf->M[4], X.y, fmaf(xf->M[5], X.z, xf->t[1]))),
+          fmaf(xf->M[6], X.x, fmaf(xf->M[7], X.y, fmaf(xf->M[8], X.z, xf->t[2])))};
+}
+// ... and whether the previous point lies in front of the camera and on the image (a NaN fails every comparison; w, u, v by value: by FlowPt&, k_flow moves).
+__device__ __forceinline__ bool flow_valid(const float w, const float u, const float v, const float Wf, const float Hf) {
+  return w >= NEAR_Z && u >= 0.f && u < Wf && v >= 0.f && v < Hf;
+}
+
+// The depth store of one pixel (to: map_at): float32, or half.
+__device__ __forceinline__ void store_depth(void* __restrict__ out, const bool f16, const size_t to, const float d) {
+  if (f16) static_cast<__half*>(out)[to] = __float2half_rn(d);
+  else static_cast<float*>(out)[to] = d;
+}
+
 // ---- k_depth: the depth map of every env's camera frame (dtsim_depth; the quantity: include/dtsim.h) -------------------------------------
-// Output pixel (i, j) of the [oh][ow] map is camera pixel (i sy + sy / 2, j sx + sx / 2), sy = H / oh, sx = W / ow: point-sampled, only those
-// pixels are traced.  A thread owns one output pixel -- its table entry (source-pixel NDC, live flag) is loaded once -- and loops over the
-// DEPTH_ENVS envs of its chunk (grid: pixel blocks x env chunks); the env's camera record, map and object boxes are wave-uniform (read-only
-// __restrict__ pointers at a uniform index: scalar loads), and every store is one coalesced row segment of one env's map.  Per env the depth
-// is scene_depth4 -- the code under the LED spheres, i.e. classify() per sample and the z-buffer of the triangles the pass projected -- and
-// the minimum of the four.
+// A thread owns one output pixel (out_camera_pixel) -- its table entry (source-pixel NDC, live flag) is loaded once -- and loops over the
+// DEPTH_ENVS envs of its chunk (grid: pixel blocks x env chunks); the env's camera record, map and object boxes are wave-uniform (EnvScene),
+// and every store is one coalesced row segment of one env's map.  Per env the depth is scene_samples4 without WHO -- the code under the LED
+// spheres, i.e. classify() per sample and the z-buffer of the triangles the pass projected -- and the minimum of the four (the winner's
+// depth, taken by an fminf tree since nothing else of the winner is wanted).
 // One state, one result: the env loop is kept as ONE copy of its body (no unrolling, no peeled iteration), so every env of every chunk, the
 // tail chunk included, runs the same instructions on its record, whatever the compiler fuses inside classify() (which is the frame's own
 // code and stays as it is, so its products are not restated as explicit fused multiply-adds here); the pixel's part (table entry, sample
@@ -307,8 +462,8 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
 // tests/test_gpu_depth.py::test_env_positions_and_the_tail_chunk_give_the_same_bytes (envs e, e + 64, e + 128 of one state, a second call, a
 // second render: byte-identical), which fails if a peeled or versioned copy ever rounds differently.
 // CAL (dtsim_set_distortion_luts' tables installed and DTSIM_MAP_ENV_TABLES given; cal_src / env_cal / n_cal are read only then): the same grid,
-// thread and loop, but the pixel's entry is the ENV's -- cal_entry() above -- and is taken inside the loop body, still one copy of it
-// (tests/test_gpu_camera_rand_maps.py holds envs e, e + 64, e + 70 of one state and table to the same bytes).  scene_depth4 is called as
+// thread and loop, but the pixel's entry is the ENV's -- EnvEntry<true> -- and is taken inside the loop body, still one copy of it
+// (tests/test_gpu_camera_rand_maps.py holds envs e, e + 64, e + 70 of one state and table to the same bytes).  The scene is sampled as
 // without CAL.  CAL = false keeps the instructions it had before the parameter (tools/isa_compare.py; profiles/render_views_isa.txt).
 template <bool F16, bool CAL = false>
 __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
@@ -319,68 +474,37 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
-  const int sy = H / oh, sx = W / ow;
-  ViewPix p = NO_PIX;
-  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
-    if constexpr (!CAL) p = view_pixel(lut, at, W, H);
-  }
-  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-  // CAL: the entry depends on the env -- env_cal[e], then the calibration's source index, then the identity table's entry there: three
-  // dependent loads.  The NEXT env's chain is issued at the top of the body and waited for at the top of the next one, behind this env's scene.
-  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
+  EnvEntry<CAL> entry(lut, cal_src, env_cal, n_cal, in, in ? out_camera_pixel(pix, W, H, oh, ow) : 0, W, H, e0);
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
-    if constexpr (CAL) {
-      const float4 l = l_nxt;
-      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
-      p.live = l.z != 0.f; p.nx = l.x; p.ny = l.y;
-      src_px(l.x, l.y, W, H, p.sxp, p.syp);
-    }
+    const ViewPix p = entry.pixel(e, e1);
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvCam c = cams[e];
-    // (calling the masked form with another mask than the pass's is the caller's error -- include/dtsim.h -- and its result is undefined: the
-    // record of a skipped env is an older state's, or the zeros the scratch starts with.  The clamp only keeps that error from indexing
-    // outside the map table on a device others share.)
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];
-    const MapU m = map_u(rm);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, nullptr, max_tris);
     float d = 0.f;
     if (p.live) {
       float ds[4];
-      scene_depth4(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
-                   objbox ? rm.n_obj : 0, p.nx, p.ny, p.sxp, p.syp, sxn, syn, __builtin_inff(), ds);
+      scene_samples4<false>(s, tiles, p, sxn, syn, ds, nullptr, nullptr);
       d = fminf(fminf(ds[0], ds[1]), fminf(ds[2], ds[3]));
     }
-    if (in) {
-      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
-      if (F16) static_cast<__half*>(out)[to] = __float2half_rn(d);
-      else static_cast<float*>(out)[to] = d;
-    }
+    if (in) store_depth(out, F16, map_at(e, n_out, pix), d);
   }
 }
 
 // ---- k_labels: the semantic label map of every env's camera frame (dtsim_labels; the quantity: include/dtsim.h) ---------------------------
 // The sibling of k_depth: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once, the env's camera
 // record, map and object boxes at a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_labels.py holds envs e, e + 64,
-// e + 128 to the same bytes).  Per env it runs scene_samples4<true> -- scene_depth4's statements plus who owns each sample --, takes the sample
-// with the smallest depth (ties: the lowest index; sky = +inf, so it wins only when all four are sky) and maps its owner to a class: the mesh
-// table through the map's object-instance table, the two fixed plane classes, or for a tile the class of the nearest texel -- the texel
-// coordinates are tile_texel_xy's, the ones tile_color filters at, with the half-texel shift taken back: floor(x + 0.5), wrapped.
+// e + 128 to the same bytes).  Per env it runs scene_samples4<true> -- k_depth's statements plus who owns each sample --, takes the
+// winner and maps its owner to a class (sample_class).
 // A thread owns ONE pixel, not four adjacent ones: the pass is bound by the four classify() calls and the triangle loop per pixel and env, not
 // by its stores (k_depth takes the same time for half maps as for float32 ones, profiles/depth_timing.txt; k_labels, with a quarter of the
 // bytes, takes 1.4 x k_depth's time on planes and the same time under meshes, profiles/labels_timing.txt); four pixels per lane would serialise
 // four of those per lane for the sake of one wider store, and a wavefront's 64 byte stores are still one contiguous 64-byte row segment.
-// tex_w, tex_h: the one (power-of-two) size of all tile textures; texel_class: dt_pack_label_tables' pool, addressed like R.texels.
 // LAB / INST (dtsim_labels: <true, false>; dtsim_instances: <false, true>, or <true, true> when it is given a label map too): which of the two
-// maps the launch writes, from the ONE classification of the pixel -- `inst` takes o + 1 of the winning sample's object (the o of
-// scene_samples4<true>: the env's map's object list), DTSIM_INSTANCE_NONE for every other owner and for a pixel without a source; a second
-// byte store at the same offset, as coalesced as the first.  Without LAB the class mapping -- mesh table, tile record, texel gather -- is not
-// compiled, and the plane hits it alone reads are dead.
-// CAL: k_depth's, word for word -- the env's own table entry, taken inside the one loop body; scene_samples4<true> is called as without it.
+// maps the launch writes, from the ONE classification of the pixel -- `inst` takes the winner's instance_id, DTSIM_INSTANCE_NONE also for a
+// pixel without a source; a second byte store at the same offset, as coalesced as the first.  Without LAB the class mapping -- mesh table,
+// tile record, texel gather -- is not compiled, and the plane hits it alone reads are dead.  CAL: as k_depth's.
 static_assert(DTSIM_MAX_OBJECTS <= 255, "an instance id o + 1 must fit the map's byte");
 template <bool LAB, bool INST, bool CAL = false>
 __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
@@ -393,74 +517,28 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
-  // k_depth's prologue with view_pixel and src_px written out: taken from the helpers, k_labels<true, *> come out with register copies in
-  // another order (tools/isa_compare.py; profiles/render_views_isa.txt), and a moved kernel keeps its instructions.  The one such copy.
-  const int sy = H / oh, sx = W / ow;
-  float nx = 0.f, ny = 0.f, sxp = 0.f, syp = 0.f;
-  bool live = false;
-  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
-    if constexpr (!CAL) {
-      const float4 l = lut[at];
-      live = l.z != 0.f;
-      nx = l.x; ny = l.y;
-      sxp = (l.x + 1.f) * 0.5f * (float)W; syp = (1.f - l.y) * 0.5f * (float)H;     // centre of the source pixel
-    }
-  }
-  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);      // CAL: the env's own entry, the next env's chain of loads in flight (as k_depth's)
-  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
+  EnvEntry<CAL> entry(lut, cal_src, env_cal, n_cal, in, in ? out_camera_pixel(pix, W, H, oh, ow) : 0, W, H, e0);
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
-    if constexpr (CAL) {
-      const float4 l = l_nxt;
-      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
-      live = l.z != 0.f;
-      nx = l.x; ny = l.y;
-      src_px(l.x, l.y, W, H, sxp, syp);
-    }
+    const ViewPix p = entry.pixel(e, e1);
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvCam c = cams[e];
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
-    const MapU m = map_u(rm);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, nullptr, max_tris);
     uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
-    if (live) {
+    if (p.live) {
       float ds[4];
       Hit hs[4];
       int os[4];
-      scene_samples4<true>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr, objbox ? stris + (size_t)e * max_tris : nullptr,
-                           objbox ? rm.n_obj : 0, nx, ny, sxp, syp, sxn, syn, __builtin_inff(), ds, hs, os);
-      float db = ds[0];
-      Hit hb = hs[0];
-      int ob = os[0];
+      scene_samples4<true>(s, tiles, p, sxn, syn, ds, hs, os);
+      Winner w = first_sample(ds[0], os[0], hs[0]);
 #pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; }
-      if constexpr (INST) who = ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE;
-      if constexpr (LAB) {
-        if (ob >= 0) {
-          const int mid = objs[rm.obj_off + ob].mesh_id;
-          cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
-        } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
-        else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
-        else {
-          const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
-          cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
-          if (tr.flags & 2u) {
-            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade_msaa hands it to tile_color
-            float x, y;
-            tile_texel_xy(tr, fx, fz, x, y);
-            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
-          }
-        }
-      }
+      for (int q = 1; q < 4; ++q) take_nearer(w, ds[q], os[q], q, hs[q]);
+      if constexpr (INST) who = instance_id(w.o);
+      if constexpr (LAB) cls = sample_class(w.o, w.h, s, tiles, objs, texel_class, mesh_class, n_mesh_class, tex_w, tex_h);
     }
     if (in) {
-      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
+      const size_t to = map_at(e, n_out, pix);
       if constexpr (LAB) out[to] = (uint8_t)cls;
       if constexpr (INST) inst[to] = (uint8_t)who;
     }
@@ -503,27 +581,12 @@ __global__ __launch_bounds__(64) void k_flow_setup(const SimArrays A, const Flow
   dt_flow_record(marks[e], cur, A.episode[e], A.map_id[e], per_env != 0, W, H, r);
   recs[e] = r;
 }
-// An eye-space point on the image: w, the rectilinear (u, v) of dtsim_ipm's step 1 and A(u, v) -- the identity, or with a calibration the
-// forward model at (u - 0.5, v - 0.5) (ipm_project.h dt_ipm_forward, in float64: in float32 its 25 operations would take the count of
-// roundings R of tests/test_flow_model_host.py past 32).  Both terms of a flow go through this one function, so one point gives one value.
-struct FlowPt { double ax, ay; float w, u, v; };
-__device__ inline FlowPt flow_image(const float x, const float y, const float z, const float tx, const float ty, const float Wf, const float Hf,
-                                    const IpmCal* __restrict__ cal) {
-  FlowPt p;
-  p.w = -z;
-  p.u = (x / p.w / tx + 1.f) * 0.5f * Wf;             // R: 4 roundings (two divisions, the sum, the product by W; x 0.5 is exact)
-  p.v = (1.f - y / p.w / ty) * 0.5f * Hf;             //    (the same 4, of the other coordinate)
-  p.ax = (double)p.u; p.ay = (double)p.v;
-  if (cal) dt_ipm_forward(*cal, p.ax - 0.5, p.ay - 0.5, 0.0, p.ax, p.ay);   // (wave-uniform) R: none, float64
-  return p;
-}
 // k_flow: the sibling of k_labels -- the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once, the
 // env's camera record, map, object boxes and FlowRec at a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_flow.py holds
-// envs e, e + 64, e + 128 to the same bytes).  Per env it runs scene_samples4<true>, takes the sample k_labels takes (smallest depth, ties to
-// the lowest index, sky = +inf), rebuilds its eye-space hit X = d (xe, ye, -1) from the sample's own ray, applies ONE pair (M, t) -- the
-// static one, or the winning object's dynamic slot's, a per-lane read of the env's record only on lanes a dynamic object owns -- and puts X
-// and M X + t on the image through flow_image.  flow = A(prev) - A(cur), rounded to float32 once.  The two stores of a pixel go to the two
-// planes of its env's map: each a coalesced row segment, as is the byte of `valid`.
+// envs e, e + 64, e + 128 to the same bytes).  Per env it runs scene_samples4<true>, takes the winner, rebuilds its eye-space hit
+// X = d (xe, ye, -1) from the sample's own ray, applies ONE pair (M, t) -- the static one, or the winning object's dynamic slot's, a per-lane
+// read of the env's record only on lanes a dynamic object owns -- and puts X and M X + t on the image through flow_image.
+// flow = A(prev) - A(cur), rounded to float32 once.
 // TBOX: the pass left a box stream (RenderParams.tribox; scene_samples4 says why the flow reads it).
 template <bool TBOX>
 __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
@@ -534,21 +597,13 @@ __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, c
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
-  const int sy = H / oh, sx = W / ow;
-  ViewPix p = NO_PIX;
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    p = view_pixel(lut, (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2), W, H);
-  }
-  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
+  const ViewPix p = in ? view_pixel(lut, out_camera_pixel(pix, W, H, oh, ow), W, H) : NO_PIX;
   const float sxn = 2.f / (float)W, syn = 2.f / (float)H, Wf = (float)W, Hf = (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's rows keep their bytes
-    const EnvCam c = cams[e];
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
-    const MapU m = map_u(rm);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, tribox, max_tris);
     const FlowRec& rec = recs[e];
     float fu = 0.f, fv = 0.f;
     bool ok = false;
@@ -556,52 +611,35 @@ __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, c
       float ds[4];
       Hit hs[4];
       int os[4];
-      scene_samples4<true, TBOX>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr,
-                                 objbox ? stris + (size_t)e * max_tris : nullptr, objbox ? rm.n_obj : 0, p.nx, p.ny, p.sxp, p.syp, sxn, syn,
-                                 __builtin_inff(), ds, hs, os, TBOX && objbox ? tribox + (size_t)e * max_tris : nullptr);
-      float db = ds[0], oxq = ox[0], oyq = oy[0];
-      int ob = os[0];
+      scene_samples4<true, TBOX>(s, tiles, p, sxn, syn, ds, hs, os);
+      Winner w = first_sample(ds[0], os[0], hs[0]);
 #pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (ds[q] < db) { db = ds[q]; ob = os[q]; oxq = ox[q]; oyq = oy[q]; }
-      if (db < __builtin_inff() && rec.valid) {        // not sky (sky = +inf wins only when all four are), and a mark of this episode
-        // the eye-space hit of the sample's ray (scene_samples4's statement of it) at the sample's depth
-        const float xe = fmaf(oxq, sxn, p.nx) * c.tx, ye = fmaf(-oyq, syn, p.ny) * c.ty;
-        const float X = db * xe, Y = db * ye, Z = -db;
-        const FlowXf* xf = &rec.fix;
-        if (ob >= 0) {
-          const int slot = objs[rm.obj_off + ob].dyn_slot;
-          if (slot >= 0) xf = &rec.dyn[min(slot, DTSIM_MAX_DYNAMIC - 1)];
-        }
-        // R: 3 roundings per coordinate (three fused multiply-adds), x and w both enter u: 6
-        const float xp = fmaf(xf->M[0], X, fmaf(xf->M[1], Y, fmaf(xf->M[2], Z, xf->t[0])));
-        const float yp = fmaf(xf->M[3], X, fmaf(xf->M[4], Y, fmaf(xf->M[5], Z, xf->t[1])));
-        const float zp = fmaf(xf->M[6], X, fmaf(xf->M[7], Y, fmaf(xf->M[8], Z, xf->t[2])));
-        const FlowPt a = flow_image(X, Y, Z, rec.txc, rec.tyc, Wf, Hf, cal);
-        const FlowPt b = flow_image(xp, yp, zp, rec.txp, rec.typ, Wf, Hf, cal);
-        ok = b.w >= NEAR_Z && b.u >= 0.f && b.u < Wf && b.v >= 0.f && b.v < Hf;      // (a NaN fails every comparison)
+      for (int q = 1; q < 4; ++q) take_nearer(w, ds[q], os[q], q, hs[q]);
+      if (w.d < __builtin_inff() && rec.valid) {       // not sky (sky = +inf wins only when all four are), and a mark of this episode
+        const Eye3 X = winner_eye_point(w, p, s.c, sxn, syn), Xp = flow_apply(flow_xf(rec, w.o, *s.rm, objs), X);
+        const FlowPt a = flow_image(X.x, X.y, X.z, rec.txc, rec.tyc, Wf, Hf, cal);
+        const FlowPt b = flow_image(Xp.x, Xp.y, Xp.z, rec.txp, rec.typ, Wf, Hf, cal);
+        ok = flow_valid(b.w, b.u, b.v, Wf, Hf);
         if (ok) { fu = (float)(b.ax - a.ax); fv = (float)(b.ay - a.ay); }              // R: 1 (the one rounding of the difference)
       }
     }
-    if (in) {
-      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
-      flow[2 * (size_t)e * (size_t)n_out + (size_t)pix] = fu;
-      flow[(2 * (size_t)e + 1) * (size_t)n_out + (size_t)pix] = fv;
-      if (valid) valid[to] = ok ? 1 : 0;
+    if (in) {                                          // the two planes of the env's map: each store a coalesced row segment, as is the byte of `valid`
+      flow[flow_at(e, n_out, pix, 0)] = fu;
+      flow[flow_at(e, n_out, pix, 1)] = fv;
+      if (valid) valid[map_at(e, n_out, pix)] = ok ? 1 : 0;
     }
   }
 }
 
 // ---- k_camera_maps: depth, labels, instances and flow of one size from ONE classification of the pixel (dtsim_camera_maps) -------------------
 // The sibling of k_labels and k_flow: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once -- with
-// CAL the env's own, cal_entry() with the next env's chain in flight, as k_depth's --, the env's camera record, map, object boxes and FlowRec at
-// a wave-uniform index, the env loop ONE copy of its body (tests/test_gpu_camera_maps.py holds envs e, e + 64, e + 128 to the same bytes), the
-// wave-uniform mask skip.  Per env it runs scene_samples4<true, TBOX> ONCE and takes the sample k_labels takes (smallest depth, ties to the
-// lowest index, sky = +inf); every output is that one winner's:
+// CAL the env's own, as k_depth's --, the env's camera record, map, object boxes and FlowRec at a wave-uniform index, the env loop ONE copy of
+// its body (tests/test_gpu_camera_maps.py holds envs e, e + 64, e + 128 to the same bytes), the wave-uniform mask skip.  Per env it runs
+// scene_samples4<true, TBOX> ONCE, and every output is its one winner's:
 //   depth      its depth -- the minimum of the four, k_depth's value --, 0 for a pixel without a source; float32, or half (f16, wave-uniform);
-//   labels     k_labels' class mapping, statement for statement;
-//   inst       o + 1 of its object, else DTSIM_INSTANCE_NONE;
-//   flow/valid k_flow's body, statement for statement (FLOW: only then are the float64 forward model and the FlowRec compiled in).
+//   labels     its sample_class;
+//   inst       its instance_id;
+//   flow/valid k_flow's body, written out (the one such site: the comment in the body) (FLOW: only then are the float64 forward model and the FlowRec compiled in).
 // depth, labels and inst are branched on at run time (kernel arguments: wave-uniform); with FLOW, flow is written and valid if given.  The
 // four passes it stands for pay the four classify() calls and the triangle loop once each; this one pays them once (the stores are not the
 // cost: k_labels' comment).  TBOX: the pass's box stream whenever it exists, for every output -- scene_samples4 says what that changes for
@@ -622,31 +660,14 @@ __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ 
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
-  const int sy = H / oh, sx = W / ow;
-  ViewPix p = NO_PIX;
-  size_t at = 0;                                       // CAL: the camera pixel of this output pixel
-  if (in) {
-    const int i = pix / ow, j = pix - i * ow;
-    at = (size_t)(i * sy + sy / 2) * W + (j * sx + sx / 2);
-    if constexpr (!CAL) p = view_pixel(lut, at, W, H);
-  }
-  const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
-  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
   const int e0 = blockIdx.y * DEPTH_ENVS, e1 = min(N, e0 + DEPTH_ENVS);
-  float4 l_nxt = make_float4(0.f, 0.f, 0.f, 0.f);      // CAL: the env's own entry, the next env's chain of loads in flight (as k_depth's)
-  if constexpr (CAL) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e0, in, at, W, H);
+  EnvEntry<CAL> entry(lut, cal_src, env_cal, n_cal, in, in ? out_camera_pixel(pix, W, H, oh, ow) : 0, W, H, e0);
+  const float sxn = 2.f / (float)W, syn = 2.f / (float)H;
 #pragma clang loop unroll(disable)
   for (int e = e0; e < e1; ++e) {
-    if constexpr (CAL) {
-      const float4 l = l_nxt;
-      if (e + 1 < e1) l_nxt = cal_entry(lut, cal_src, env_cal, n_cal, e + 1, in, at, W, H);
-      p.live = l.z != 0.f; p.nx = l.x; p.ny = l.y;
-      src_px(l.x, l.y, W, H, p.sxp, p.syp);
-    }
+    const ViewPix p = entry.pixel(e, e1);
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's rows keep their bytes
-    const EnvCam c = cams[e];
-    const RenderMapDev& rm = maps[min((unsigned)c.map_id, (unsigned)(n_maps - 1))];   // (the clamp: as k_depth's)
-    const MapU m = map_u(rm);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, tribox, max_tris);
     float d = 0.f, fu = 0.f, fv = 0.f;
     uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
     bool ok = false;
@@ -654,44 +675,27 @@ __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ 
       float ds[4];
       Hit hs[4];
       int os[4];
-      scene_samples4<true, TBOX>(c, m, tiles, objbox ? objbox + (size_t)e * DTSIM_MAX_OBJECTS : nullptr,
-                                 objbox ? stris + (size_t)e * max_tris : nullptr, objbox ? rm.n_obj : 0, p.nx, p.ny, p.sxp, p.syp, sxn, syn,
-                                 __builtin_inff(), ds, hs, os, TBOX && objbox ? tribox + (size_t)e * max_tris : nullptr);
-      float db = ds[0], oxq = ox[0], oyq = oy[0];
-      Hit hb = hs[0];
-      int ob = os[0];
+      scene_samples4<true, TBOX>(s, tiles, p, sxn, syn, ds, hs, os);
+      Winner w = first_sample(ds[0], os[0], hs[0]);
 #pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (ds[q] < db) { db = ds[q]; hb = hs[q]; ob = os[q]; oxq = ox[q]; oyq = oy[q]; }
+      for (int q = 1; q < 4; ++q) take_nearer(w, ds[q], os[q], q, hs[q]);
+      // THE ONE WRITTEN-OUT SITE of the unit: to the end of the block the winner is read through copies of its members, and instance_id,
+      // winner_eye_point, flow_xf, flow_apply and flow_valid are written out.  The copy guards no behaviour: with them called, or w read in place,
+      // k_camera_maps<true, *, *> only encode two compares e32 instead of e64, which tools/isa_compare.py counts as other opcodes
+      // (profiles/render_views_isa.txt); it can go when tool or compiler stop telling them apart.  Until then a rule's change is made here too.
+      const float db = w.d, oxq = w.ox, oyq = w.oy; const int ob = w.o; const Hit& hb = w.h;
       d = db;
       who = ob >= 0 ? (uint32_t)ob + 1u : (uint32_t)DTSIM_INSTANCE_NONE;
-      if (labels) {                                    // (wave-uniform) k_labels' mapping
-        if (ob >= 0) {
-          const int mid = objs[rm.obj_off + ob].mesh_id;
-          cls = mesh_class[min((unsigned)mid, (unsigned)(n_mesh_class - 1))];
-        } else if (hb.cls == CLS_SKY) cls = DTSIM_LABEL_SKY;
-        else if (hb.cls == CLS_GROUND) cls = DTSIM_LABEL_GROUND;
-        else {
-          const TileLds tr = tiles[m.tile_off + hb.tj * m.gw + hb.ti];
-          cls = DTSIM_LABEL_GROUND;                    // a present tile without a texture has no texel table
-          if (tr.flags & 2u) {
-            const float fx = hb.wx * m.its - (float)hb.ti, fz = hb.wz * m.its - (float)hb.tj;   // the tile fraction, as shade_msaa hands it to tile_color
-            float x, y;
-            tile_texel_xy(tr, fx, fz, x, y);
-            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
-          }
-        }
-      }
-      if constexpr (FLOW) {                            // k_flow's body
+      if (labels) cls = sample_class(ob, hb, s, tiles, objs, texel_class, mesh_class, n_mesh_class, tex_w, tex_h);   // (wave-uniform)
+      if constexpr (FLOW) {
         const FlowRec& rec = recs[e];
         const float Wf = (float)W, Hf = (float)H;
-        if (db < __builtin_inff() && rec.valid) {      // not sky, and a mark of this episode
-          const float xe = fmaf(oxq, sxn, p.nx) * c.tx, ye = fmaf(-oyq, syn, p.ny) * c.ty;
+        if (db < __builtin_inff() && rec.valid) {     // not sky, and a mark of this episode
+          const float xe = fmaf(oxq, sxn, p.nx) * s.c.tx, ye = fmaf(-oyq, syn, p.ny) * s.c.ty;
           const float X = db * xe, Y = db * ye, Z = -db;
           const FlowXf* xf = &rec.fix;
           if (ob >= 0) {
-            const int slot = objs[rm.obj_off + ob].dyn_slot;
+            const int slot = objs[s.rm->obj_off + ob].dyn_slot;
             if (slot >= 0) xf = &rec.dyn[min(slot, DTSIM_MAX_DYNAMIC - 1)];
           }
           const float xp = fmaf(xf->M[0], X, fmaf(xf->M[1], Y, fmaf(xf->M[2], Z, xf->t[0])));
@@ -699,22 +703,19 @@ __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ 
           const float zp = fmaf(xf->M[6], X, fmaf(xf->M[7], Y, fmaf(xf->M[8], Z, xf->t[2])));
           const FlowPt a = flow_image(X, Y, Z, rec.txc, rec.tyc, Wf, Hf, cal);
           const FlowPt b = flow_image(xp, yp, zp, rec.txp, rec.typ, Wf, Hf, cal);
-          ok = b.w >= NEAR_Z && b.u >= 0.f && b.u < Wf && b.v >= 0.f && b.v < Hf;      // (a NaN fails every comparison)
-          if (ok) { fu = (float)(b.ax - a.ax); fv = (float)(b.ay - a.ay); }              // the one rounding of the difference
+          ok = b.w >= NEAR_Z && b.u >= 0.f && b.u < Wf && b.v >= 0.f && b.v < Hf;
+          if (ok) { fu = (float)(b.ax - a.ax); fv = (float)(b.ay - a.ay); }              // R: 1 (the one rounding of the difference)
         }
       }
     }
     if (in) {
-      const size_t to = (size_t)e * (size_t)n_out + (size_t)pix;
-      if (depth) {
-        if (f16) static_cast<__half*>(depth)[to] = __float2half_rn(d);
-        else static_cast<float*>(depth)[to] = d;
-      }
+      const size_t to = map_at(e, n_out, pix);
+      if (depth) store_depth(depth, f16, to, d);
       if (labels) labels[to] = (uint8_t)cls;
       if (inst) inst[to] = (uint8_t)who;
       if constexpr (FLOW) {
-        flow[2 * (size_t)e * (size_t)n_out + (size_t)pix] = fu;
-        flow[(2 * (size_t)e + 1) * (size_t)n_out + (size_t)pix] = fv;
+        flow[flow_at(e, n_out, pix, 0)] = fu;
+        flow[flow_at(e, n_out, pix, 1)] = fv;
         if (valid) valid[to] = ok ? 1 : 0;
       }
     }
@@ -741,9 +742,9 @@ __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ 
 // wavefront fills slot (it + 1) & 1 while the others may still read slot it & 1, which is not written again before the next barrier.  An
 // env on a map without objects (workgroup-uniform) meets no barrier and no work of the first wavefront at all.
 // Per cell: the first rectangle of the list that holds the cell gives the class and the id; else the tile under P = (x, z) + f d + s r
-// (float32 from the rounded pose: five roundings, < 1e-5 m below 32 m), found and sampled by k_labels' statements -- floorf(w * its), the tile
-// fraction w * its - tile, tile_texel_xy, floor(x + 0.5) wrapped, the texel_class pool -- so a camera label pixel and a cell that hit one
-// world point name one class.  No camera record, no distortion table, nothing a render pass leaves behind is read.
+// (float32 from the rounded pose: five roundings, < 1e-5 m below 32 m), found by floorf(w * its) and sampled at the tile fraction
+// w * its - tile by tile_texel_class, as sample_class samples it, so a camera label pixel and a cell that hit one world point name one class.
+// No camera record, no distortion table, nothing a render pass leaves behind is read.
 struct alignas(16) BevRect { float cf, cs, af, as, bf, bs; uint32_t cls, id; };
 struct alignas(16) BevEnv {                                        // what a cell needs of its env, in LDS:
   float x, z, dc, ds;                                              // the pose; cell * cos, cell * sin of the angle
@@ -864,13 +865,8 @@ __global__ __launch_bounds__(256) void k_bev(const double* __restrict__ pos_x, c
         if (fi >= 0.f && fj >= 0.f && fi < (float)ev.gw && fj < (float)ev.gh) {
           const int ti = (int)fi, tj = (int)fj;
           const TileLds tr = s_tiles[ev.tile_off + tj * ev.gw + ti];
-          if ((tr.flags & 3u) == 3u) {                 // present and textured (else: the ground's class)
-            const float fx = wx * its - (float)ti, fz = wz * its - (float)tj;     // the tile fraction, as k_labels takes it
-            float x, y;
-            tile_texel_xy(tr, fx, fz, x, y);
-            const int x0 = (int)floorf(x + 0.5f) & (tex_w - 1), y0 = (int)floorf(y + 0.5f) & (tex_h - 1);
-            cls = texel_class[tr.tex_off + (uint32_t)(y0 * (tex_w + 1) + x0)];
-          }
+          // present and textured (else: the ground's class); the tile fraction, as sample_class takes it
+          if ((tr.flags & 3u) == 3u) cls = tile_texel_class(tr, wx * its - (float)ti, wz * its - (float)tj, tex_w, tex_h, texel_class);
         }
       }
     }
@@ -1052,6 +1048,16 @@ __global__ __launch_bounds__(256) void k_ipm_env(const uint8_t* __restrict__ fra
 
 static inline dim3 dt_ipm_grid(const IpmArgs& a) { return view_grid((a.oh * a.ow + IPM_CPT - 1) / IPM_CPT, a.N); }   // a thread per IPM_CPT cells
 
+// What every camera-map launch hands its kernel of the pass, decided here once: the rows of the projected mesh triangles (objbox / stris: null
+// unless the pass projected some; tribox: the pass moreover left its box stream -- the TBOX instantiations) and the per-env tables (null / 0
+// unless all three are given -- the CAL instantiations).
+struct ViewScene { const float4* lut; const ObjBox* objbox; const ScreenTri* stris; const float4* tribox; const int32_t* cal_src; const int32_t* env_cal; int n_cal; };
+static inline ViewScene view_scene(const RenderParams& R, const int32_t* cal_src = nullptr, const int32_t* env_cal = nullptr, const int n_cal = 0) {
+  const bool obj = R.stris && R.objbox, cal = cal_src && env_cal && n_cal > 0;
+  return {reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, obj ? R.tribox : nullptr,
+          cal ? cal_src : nullptr, cal ? env_cal : nullptr, cal ? n_cal : 0};
+}
+
 }  // namespace
 
 void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d_spheres, int first, int count, int env) {
@@ -1062,27 +1068,21 @@ void dt_launch_overlay_leds(hipStream_t s, const RenderParams& R, const float* d
 void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, int ow, bool f16, const uint8_t* mask, const int32_t* cal_src,
                      const int32_t* env_cal, int n_cal) {
   if (R.N <= 0) return;
-  const dim3 grid = view_grid(oh * ow, R.N);
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  const bool cal = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations
-  auto k = cal ? (f16 ? k_depth<true, true> : k_depth<false, true>) : (f16 ? k_depth<true> : k_depth<false>);
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr,
-                     obj ? R.stris : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, mask, cal ? cal_src : nullptr, cal ? env_cal : nullptr,
-                     cal ? n_cal : 0);
+  const ViewScene v = view_scene(R, cal_src, env_cal, n_cal);
+  auto k = v.cal_src ? (f16 ? k_depth<true, true> : k_depth<false, true>) : (f16 ? k_depth<true> : k_depth<false>);
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, R.max_tris, R.n_maps, R.N,
+                     R.W, R.H, oh, ow, out, mask, v.cal_src, v.env_cal, v.n_cal);
 }
 
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
                       uint8_t* inst, int oh, int ow, const uint8_t* mask, const int32_t* cal_src, const int32_t* env_cal, int n_cal) {
   if (R.N <= 0 || (!out && !inst)) return;
-  const dim3 grid = view_grid(oh * ow, R.N);
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  const bool cal = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations
-  auto k = cal ? (out && inst ? k_labels<true, true, true> : out ? k_labels<true, false, true> : k_labels<false, true, true>)
-               : (out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>);
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, R.envcam, R.maps, R.tile_recs,
-                     reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, R.objs, texel_class, mesh_class,
-                     n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask, cal ? cal_src : nullptr,
-                     cal ? env_cal : nullptr, cal ? n_cal : 0);
+  const ViewScene v = view_scene(R, cal_src, env_cal, n_cal);
+  auto k = v.cal_src ? (out && inst ? k_labels<true, true, true> : out ? k_labels<true, false, true> : k_labels<false, true, true>)
+                     : (out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>);
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, R.objs, texel_class,
+                     mesh_class, n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask, v.cal_src, v.env_cal,
+                     v.n_cal);
 }
 
 void dt_launch_flow_mark(hipStream_t s, const SimArrays& A, FlowMark* marks, const uint8_t* mask) {
@@ -1094,10 +1094,10 @@ void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, co
                     float* flow, uint8_t* valid, int oh, int ow, const uint8_t* mask) {
   if (R.N <= 0) return;
   dt_launch_flow_setup(s, R, A, marks, recs, per_env, mask);
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  auto k = obj && R.tribox ? k_flow<true> : k_flow<false>;
-  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut),
-                     obj ? R.objbox : nullptr, obj ? R.stris : nullptr, obj ? R.tribox : nullptr, R.objs, recs, cal, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, flow, valid, mask);
+  const ViewScene v = view_scene(R);
+  auto k = v.tribox ? k_flow<true> : k_flow<false>;
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, recs, cal,
+                     R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, flow, valid, mask);
 }
 
 void dt_launch_flow_setup(hipStream_t s, const RenderParams& R, const SimArrays& A, const FlowMark* marks, FlowRec* recs, bool per_env,
@@ -1110,17 +1110,14 @@ void dt_launch_camera_maps(hipStream_t s, const RenderParams& R, const CameraMap
                            int n_mesh_class, const FlowRec* recs, const IpmCal* cal, int oh, int ow, const uint8_t* mask, const int32_t* cal_src,
                            const int32_t* env_cal, int n_cal) {
   if (R.N <= 0 || (!o.depth && !o.labels && !o.inst && !o.flow)) return;
-  const bool obj = R.stris && R.objbox;                // the pass projected mesh triangles
-  const bool tb = obj && R.tribox;                     // ... and left its box stream
-  const bool tab = cal_src && env_cal && n_cal > 0;    // per-env tables: the CAL instantiations (never with flow: the caller refused it)
-  auto k = o.flow ? (tb ? k_camera_maps<true, false, true> : k_camera_maps<true, false, false>)
-           : tab  ? (tb ? k_camera_maps<false, true, true> : k_camera_maps<false, true, false>)
-                  : (tb ? k_camera_maps<false, false, true> : k_camera_maps<false, false, false>);
-  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, reinterpret_cast<const float4*>(R.lut),
-                     obj ? R.objbox : nullptr, obj ? R.stris : nullptr, tb ? R.tribox : nullptr, R.objs, texel_class, mesh_class, n_mesh_class,
-                     R.tex_w, R.tex_h, o.flow ? recs : nullptr, o.flow ? cal : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, o.depth,
-                     o.f16 ? 1 : 0, o.labels, o.inst, o.flow, o.flow ? o.valid : nullptr, mask, tab && !o.flow ? cal_src : nullptr,
-                     tab && !o.flow ? env_cal : nullptr, tab && !o.flow ? n_cal : 0);
+  const ViewScene v = view_scene(R, o.flow ? nullptr : cal_src, env_cal, n_cal);   // (no tables with flow: the caller refused that)
+  const bool tb = v.tribox != nullptr;
+  auto k = o.flow    ? (tb ? k_camera_maps<true, false, true> : k_camera_maps<true, false, false>)
+           : v.cal_src ? (tb ? k_camera_maps<false, true, true> : k_camera_maps<false, true, false>)
+                     : (tb ? k_camera_maps<false, false, true> : k_camera_maps<false, false, false>);
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, texel_class,
+                     mesh_class, n_mesh_class, R.tex_w, R.tex_h, o.flow ? recs : nullptr, o.flow ? cal : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh,
+                     ow, o.depth, o.f16 ? 1 : 0, o.labels, o.inst, o.flow, o.flow ? o.valid : nullptr, mask, v.cal_src, v.env_cal, v.n_cal);
 }
 
 void dt_launch_bev(hipStream_t s, const RenderParams& R, const SimArrays& A, const double* ocorners, const uint8_t* texel_class,
