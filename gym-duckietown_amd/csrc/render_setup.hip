@@ -453,7 +453,9 @@ __global__ __launch_bounds__(DT_OBJSETUP_T) void k_obj_setup(SimArrays A, Render
     if (!ok) { st.bx0 = 1e30f; st.bx1 = -1e30f; st.by0 = 1e30f; st.by1 = -1e30f; }
     st.index = t;
     // culled triangles (outside the view, degenerate, beyond near / far) leave only their inverted box: k_resolve_obj culls on
-    // the boxes and reads the 128-byte record of survivors only
+    // the boxes and reads the 128-byte record of survivors only.  (dt_render_layout sets R.tribox whenever it sets R.stris, so the `!R.tribox` arm
+    // below and the test after it are never taken the other way: no pass runs without the stream, and every reader of the records -- k_resolve_obj,
+    // render_views.hip's scene_samples4 -- tests a triangle by the stream's box, never by the one a culled triangle's record still holds.)
     if (ok || !R.tribox) out[t] = st;
     if (R.tribox) R.tribox[(size_t)e * R.max_tris + t] = make_float4(st.bx0, st.bx1, st.by0, st.by1);   // the cull stream of k_resolve_obj: 16 B per triangle, contiguous
     if (ok) {

@@ -158,15 +158,16 @@ struct LedS { float ex, ey, ez, r, cr, cg, cb, a, bx0, bx1, by0, by1; };     // 
 // WHO (k_labels): also who owns each sample -- hits[q] = classify()'s plane hit (class, tile, world hit), obj[q] = the object (the o of the
 // ObjBox loop) whose triangle won the sample's z-buffer AND lies strictly nearer than the plane (the colour pass's depth test, shade_msaa),
 // else -1.  Without WHO (hits, obj unused, may be null) nothing of that is compiled: the depth arithmetic is the same statements in both.
-// tbox (k_flow): the env's rows of RenderParams.tribox, the screen boxes k_obj_setup writes for EVERY triangle of a live object in every pass.
-// With that stream the pass rewrites the ScreenTri record of a surviving triangle only, so a triangle culled in this pass (outside the view,
-// behind the near plane) keeps the record -- and the box inside it -- of the last pass it survived: tested by its record's box, as the
-// callers without tbox test it, it is z-buffered where it stood in that older frame.  The flow is asked for after a second render from
-// another pose, which is when that shows; with tbox the box is the stream's and a culled triangle is skipped, as the colour pass skips it.
-template <bool WHO, bool TBOX = false>
-__device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
-                                      const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
-                                      const float sky, float depth[4], Hit* hits, int* obj, const float4* tbox = nullptr) {
+// tbox: the env's rows of RenderParams.tribox, the screen boxes k_obj_setup writes for EVERY triangle of a live object in every pass (the pass
+// allocates the stream whenever it allocates the records: dt_render_layout).  A triangle is tested by ITS BOX IN THAT STREAM, never by the box
+// inside its record: the pass rewrites the ScreenTri record of a surviving triangle only, so a triangle it culled (a vertex behind the near
+// plane, no area, off the frame) keeps the record of the last pass it survived -- or, on a fresh handle, whatever the allocation held -- and
+// its inverted box in the stream is what skips it here, as the colour pass skips it.  Every reader of the records goes through this function,
+// so every map of a re-rendered handle is that of a fresh handle in the same state (tests/test_gpu_rerender_maps.py).
+template <bool WHO>
+__device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const float4* tbox,
+                                      const int n_obj, const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
+                                      const float sky, float depth[4], Hit* hits, int* obj) {
   const auto &ox = MSAA_POS.x, &oy = MSAA_POS.y;
   float wbest[4] = {0.f, 0.f, 0.f, 0.f};
   int tbest[4] = {-1, -1, -1, -1};
@@ -175,13 +176,10 @@ __device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const Tile
     for (int o = 0; o < n_obj; ++o) {
       const ObjBox ob = boxes[o];
       if (ob.count <= 0 || sxp < ob.bx0 - 1.f || sxp > ob.bx1 + 1.f || syp < ob.by0 - 1.f || syp > ob.by1 + 1.f) continue;
-      if constexpr (TBOX) {                           // (k_flow) the pass's own cull stream: see the comment above
-        for (int t = ob.first; t < ob.first + ob.count; ++t) {
-          const float4 b = tbox[t];
-          if (!(sxp < b.x || sxp > b.y || syp < b.z || syp > b.w)) test_tri_inside(tb[t], sxp, syp, wbest, tbest);
-        }
-      } else
-      for (int t = ob.first; t < ob.first + ob.count; ++t) test_tri(tb[t], sxp, syp, wbest, tbest);
+      for (int t = ob.first; t < ob.first + ob.count; ++t) {   // the pass's own cull stream: see the comment above
+        const float4 b = tbox[t];
+        if (!(sxp < b.x || sxp > b.y || syp < b.z || syp > b.w)) test_tri_inside(tb[t], sxp, syp, wbest, tbest);
+      }
       if constexpr (WHO) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)                   // the sample's winner so far is one of this object's triangles
@@ -205,10 +203,10 @@ __device__ inline void scene_samples4(const EnvCam& c, const MapU& m, const Tile
     depth[q] = d;
   }
 }
-__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const int n_obj,
-                                    const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
+__device__ inline void scene_depth4(const EnvCam& c, const MapU& m, const TileLds* tiles, const ObjBox* boxes, const ScreenTri* tb, const float4* tbox,
+                                    const int n_obj, const float nx, const float ny, const float sxp, const float syp, const float sxn, const float syn,
                                     const float sky, float depth[4]) {
-  scene_samples4<false>(c, m, tiles, boxes, tb, n_obj, nx, ny, sxp, syp, sxn, syn, sky, depth, nullptr, nullptr);
+  scene_samples4<false>(c, m, tiles, boxes, tb, tbox, n_obj, nx, ny, sxp, syp, sxn, syn, sky, depth, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvCam* __restrict__ cams, const float* __restrict__ spheres,
@@ -256,9 +254,9 @@ __global__ __launch_bounds__(256) void k_overlay_leds(RenderParams R, const EnvC
       if (!(sp.r > 0.f) || sxp < sp.bx0 || sxp > sp.bx1 || syp < sp.by0 || syp > sp.by1) continue;
       if (!have_depth) {                               // the opaque scene's depth at the four samples, once per pixel that any sphere may touch
         have_depth = true;
-        const bool obj = R.stris && R.objbox;
+        const bool obj = R.stris && R.objbox && R.tribox;
         scene_depth4(c, m, tiles, obj ? R.objbox + (size_t)env * DTSIM_MAX_OBJECTS : nullptr, obj ? R.stris + (size_t)env * R.max_tris : nullptr,
-                     obj ? R.maps[c.map_id].n_obj : 0, nx, ny, sxp, syp, sxn, syn, 3.0e38f, depth);
+                     obj ? R.tribox + (size_t)env * R.max_tris : nullptr, obj ? R.maps[c.map_id].n_obj : 0, nx, ny, sxp, syp, sxn, syn, 3.0e38f, depth);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -335,7 +333,7 @@ struct EnvEntry {
 };
 
 // What a pixel reads of env e, all at a wave-uniform index (read-only __restrict__ pointers: scalar loads): its camera record, its map and the
-// rows of the pass's ObjBox / ScreenTri / (TBOX) box streams; objbox null: the pass projected no mesh triangles.  The map id is clamped:
+// rows of the pass's ObjBox / ScreenTri / box streams; objbox null: the pass projected no mesh triangles.  The map id is clamped:
 // calling a masked form with another mask than the pass's is the caller's error (include/dtsim.h) and its result is undefined -- the record of
 // a skipped env is an older state's, or the zeros the scratch starts with -- and the clamp only keeps that error from indexing outside the map
 // table on a device others share.
@@ -359,11 +357,11 @@ __device__ __forceinline__ EnvScene env_scene(const int e, const EnvCam* __restr
   return s;
 }
 // scene_samples4 of that env at that pixel; sky = +inf.
-template <bool WHO, bool TBOX = false>
+template <bool WHO>
 __device__ __forceinline__ void scene_samples4(const EnvScene& s, const TileLds* tiles, const ViewPix& p, const float sxn, const float syn, float depth[4],
                                       Hit* hits, int* obj) {
-  scene_samples4<WHO, TBOX>(s.c, s.m, tiles, s.boxes(), s.tris(), s.n_obj(), p.nx, p.ny, p.sxp, p.syp, sxn, syn, __builtin_inff(), depth, hits, obj,
-                            TBOX ? s.tri_boxes() : nullptr);
+  scene_samples4<WHO>(s.c, s.m, tiles, s.boxes(), s.tris(), s.tri_boxes(), s.n_obj(), p.nx, p.ny, p.sxp, p.syp, sxn, syn, __builtin_inff(), depth, hits,
+                      obj);
 }
 
 // The WINNER of a pixel: the sample with the smallest depth, ties to the lowest index; sky = +inf, so it wins only when all four are sky.  d: its
@@ -468,9 +466,9 @@ __device__ __forceinline__ void store_depth(void* __restrict__ out, const bool f
 template <bool F16, bool CAL = false>
 __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
-                                               const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
-                                               void* __restrict__ out, const uint8_t* __restrict__ mask, const int32_t* __restrict__ cal_src,
-                                               const int32_t* __restrict__ env_cal, const int n_cal) {
+                                               const float4* __restrict__ tribox, const int max_tris, const int n_maps, const int N, const int W, const int H,
+                                               const int oh, const int ow, void* __restrict__ out, const uint8_t* __restrict__ mask,
+                                               const int32_t* __restrict__ cal_src, const int32_t* __restrict__ env_cal, const int n_cal) {
   const int n_out = oh * ow;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool in = pix < n_out;
@@ -481,7 +479,7 @@ __global__ __launch_bounds__(256) void k_depth(const EnvCam* __restrict__ cams, 
   for (int e = e0; e < e1; ++e) {
     const ViewPix p = entry.pixel(e, e1);
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, nullptr, max_tris);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, tribox, max_tris);
     float d = 0.f;
     if (p.live) {
       float ds[4];
@@ -509,7 +507,7 @@ static_assert(DTSIM_MAX_OBJECTS <= 255, "an instance id o + 1 must fit the map's
 template <bool LAB, bool INST, bool CAL = false>
 __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                 const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
-                                                const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
+                                                const float4* __restrict__ tribox, const ObjInstDev* __restrict__ objs, const uint8_t* __restrict__ texel_class,
                                                 const uint8_t* __restrict__ mesh_class, const int n_mesh_class, const int tex_w, const int tex_h,
                                                 const int max_tris, const int n_maps, const int N, const int W, const int H, const int oh, const int ow,
                                                 uint8_t* __restrict__ out, uint8_t* __restrict__ inst, const uint8_t* __restrict__ mask,
@@ -524,7 +522,7 @@ __global__ __launch_bounds__(256) void k_labels(const EnvCam* __restrict__ cams,
   for (int e = e0; e < e1; ++e) {
     const ViewPix p = entry.pixel(e, e1);
     if (mask && !mask[e]) continue;                    // (wave-uniform) the masked call: this env's row keeps its bytes
-    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, nullptr, max_tris);
+    const EnvScene s = env_scene(e, cams, maps, n_maps, objbox, stris, tribox, max_tris);
     uint32_t cls = DTSIM_LABEL_NONE, who = DTSIM_INSTANCE_NONE;
     if (p.live) {
       float ds[4];
@@ -587,8 +585,6 @@ __global__ __launch_bounds__(64) void k_flow_setup(const SimArrays A, const Flow
 // X = d (xe, ye, -1) from the sample's own ray, applies ONE pair (M, t) -- the static one, or the winning object's dynamic slot's, a per-lane
 // read of the env's record only on lanes a dynamic object owns -- and puts X and M X + t on the image through flow_image.
 // flow = A(prev) - A(cur), rounded to float32 once.
-// TBOX: the pass left a box stream (RenderParams.tribox; scene_samples4 says why the flow reads it).
-template <bool TBOX>
 __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                               const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
                                               const float4* __restrict__ tribox, const ObjInstDev* __restrict__ objs, const FlowRec* __restrict__ recs,
@@ -611,7 +607,7 @@ __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, c
       float ds[4];
       Hit hs[4];
       int os[4];
-      scene_samples4<true, TBOX>(s, tiles, p, sxn, syn, ds, hs, os);
+      scene_samples4<true>(s, tiles, p, sxn, syn, ds, hs, os);
       Winner w = first_sample(ds[0], os[0], hs[0]);
 #pragma unroll
       for (int q = 1; q < 4; ++q) take_nearer(w, ds[q], os[q], q, hs[q]);
@@ -635,17 +631,16 @@ __global__ __launch_bounds__(256) void k_flow(const EnvCam* __restrict__ cams, c
 // The sibling of k_labels and k_flow: the same grid (output-pixel blocks x env chunks of DEPTH_ENVS), the pixel's table entry loaded once -- with
 // CAL the env's own, as k_depth's --, the env's camera record, map, object boxes and FlowRec at a wave-uniform index, the env loop ONE copy of
 // its body (tests/test_gpu_camera_maps.py holds envs e, e + 64, e + 128 to the same bytes), the wave-uniform mask skip.  Per env it runs
-// scene_samples4<true, TBOX> ONCE, and every output is its one winner's:
+// scene_samples4<true> ONCE, and every output is its one winner's:
 //   depth      its depth -- the minimum of the four, k_depth's value --, 0 for a pixel without a source; float32, or half (f16, wave-uniform);
 //   labels     its sample_class;
 //   inst       its instance_id;
 //   flow/valid k_flow's body, written out (the one such site: the comment in the body) (FLOW: only then are the float64 forward model and the FlowRec compiled in).
 // depth, labels and inst are branched on at run time (kernel arguments: wave-uniform); with FLOW, flow is written and valid if given.  The
 // four passes it stands for pay the four classify() calls and the triangle loop once each; this one pays them once (the stores are not the
-// cost: k_labels' comment).  TBOX: the pass's box stream whenever it exists, for every output -- scene_samples4 says what that changes for
-// depth, labels and instances against their single passes: a triangle culled in this pass is skipped, as the colour pass skips it.
+// cost: k_labels' comment).
 // FLOW && CAL does not exist: the flow under per-env tables is refused (dtsim_flow).
-template <bool FLOW, bool CAL, bool TBOX>
+template <bool FLOW, bool CAL>
 __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ cams, const RenderMapDev* __restrict__ maps, const TileLds* __restrict__ tiles,
                                                      const float4* __restrict__ lut, const ObjBox* __restrict__ objbox, const ScreenTri* __restrict__ stris,
                                                      const float4* __restrict__ tribox, const ObjInstDev* __restrict__ objs,
@@ -675,7 +670,7 @@ __global__ __launch_bounds__(256) void k_camera_maps(const EnvCam* __restrict__ 
       float ds[4];
       Hit hs[4];
       int os[4];
-      scene_samples4<true, TBOX>(s, tiles, p, sxn, syn, ds, hs, os);
+      scene_samples4<true>(s, tiles, p, sxn, syn, ds, hs, os);
       Winner w = first_sample(ds[0], os[0], hs[0]);
 #pragma unroll
       for (int q = 1; q < 4; ++q) take_nearer(w, ds[q], os[q], q, hs[q]);
@@ -1049,11 +1044,11 @@ __global__ __launch_bounds__(256) void k_ipm_env(const uint8_t* __restrict__ fra
 static inline dim3 dt_ipm_grid(const IpmArgs& a) { return view_grid((a.oh * a.ow + IPM_CPT - 1) / IPM_CPT, a.N); }   // a thread per IPM_CPT cells
 
 // What every camera-map launch hands its kernel of the pass, decided here once: the rows of the projected mesh triangles (objbox / stris: null
-// unless the pass projected some; tribox: the pass moreover left its box stream -- the TBOX instantiations) and the per-env tables (null / 0
+// unless the pass projected some; tribox: its box stream, which it leaves whenever it leaves the records) and the per-env tables (null / 0
 // unless all three are given -- the CAL instantiations).
 struct ViewScene { const float4* lut; const ObjBox* objbox; const ScreenTri* stris; const float4* tribox; const int32_t* cal_src; const int32_t* env_cal; int n_cal; };
 static inline ViewScene view_scene(const RenderParams& R, const int32_t* cal_src = nullptr, const int32_t* env_cal = nullptr, const int n_cal = 0) {
-  const bool obj = R.stris && R.objbox, cal = cal_src && env_cal && n_cal > 0;
+  const bool obj = R.stris && R.objbox && R.tribox, cal = cal_src && env_cal && n_cal > 0;
   return {reinterpret_cast<const float4*>(R.lut), obj ? R.objbox : nullptr, obj ? R.stris : nullptr, obj ? R.tribox : nullptr,
           cal ? cal_src : nullptr, cal ? env_cal : nullptr, cal ? n_cal : 0};
 }
@@ -1070,8 +1065,8 @@ void dt_launch_depth(hipStream_t s, const RenderParams& R, void* out, int oh, in
   if (R.N <= 0) return;
   const ViewScene v = view_scene(R, cal_src, env_cal, n_cal);
   auto k = v.cal_src ? (f16 ? k_depth<true, true> : k_depth<false, true>) : (f16 ? k_depth<true> : k_depth<false>);
-  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, R.max_tris, R.n_maps, R.N,
-                     R.W, R.H, oh, ow, out, mask, v.cal_src, v.env_cal, v.n_cal);
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.max_tris, R.n_maps,
+                     R.N, R.W, R.H, oh, ow, out, mask, v.cal_src, v.env_cal, v.n_cal);
 }
 
 void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel_class, const uint8_t* mesh_class, int n_mesh_class, uint8_t* out,
@@ -1080,7 +1075,7 @@ void dt_launch_labels(hipStream_t s, const RenderParams& R, const uint8_t* texel
   const ViewScene v = view_scene(R, cal_src, env_cal, n_cal);
   auto k = v.cal_src ? (out && inst ? k_labels<true, true, true> : out ? k_labels<true, false, true> : k_labels<false, true, true>)
                      : (out && inst ? k_labels<true, true> : out ? k_labels<true, false> : k_labels<false, true>);
-  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, R.objs, texel_class,
+  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, texel_class,
                      mesh_class, n_mesh_class, R.tex_w, R.tex_h, R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, out, inst, mask, v.cal_src, v.env_cal,
                      v.n_cal);
 }
@@ -1095,8 +1090,7 @@ void dt_launch_flow(hipStream_t s, const RenderParams& R, const SimArrays& A, co
   if (R.N <= 0) return;
   dt_launch_flow_setup(s, R, A, marks, recs, per_env, mask);
   const ViewScene v = view_scene(R);
-  auto k = v.tribox ? k_flow<true> : k_flow<false>;
-  hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, recs, cal,
+  hipLaunchKernelGGL(k_flow, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, recs, cal,
                      R.max_tris, R.n_maps, R.N, R.W, R.H, oh, ow, flow, valid, mask);
 }
 
@@ -1111,10 +1105,7 @@ void dt_launch_camera_maps(hipStream_t s, const RenderParams& R, const CameraMap
                            const int32_t* env_cal, int n_cal) {
   if (R.N <= 0 || (!o.depth && !o.labels && !o.inst && !o.flow)) return;
   const ViewScene v = view_scene(R, o.flow ? nullptr : cal_src, env_cal, n_cal);   // (no tables with flow: the caller refused that)
-  const bool tb = v.tribox != nullptr;
-  auto k = o.flow    ? (tb ? k_camera_maps<true, false, true> : k_camera_maps<true, false, false>)
-           : v.cal_src ? (tb ? k_camera_maps<false, true, true> : k_camera_maps<false, true, false>)
-                     : (tb ? k_camera_maps<false, false, true> : k_camera_maps<false, false, false>);
+  auto k = o.flow ? k_camera_maps<true, false> : v.cal_src ? k_camera_maps<false, true> : k_camera_maps<false, false>;
   hipLaunchKernelGGL(k, view_grid(oh * ow, R.N), dim3(256), 0, s, R.envcam, R.maps, R.tile_recs, v.lut, v.objbox, v.stris, v.tribox, R.objs, texel_class,
                      mesh_class, n_mesh_class, R.tex_w, R.tex_h, o.flow ? recs : nullptr, o.flow ? cal : nullptr, R.max_tris, R.n_maps, R.N, R.W, R.H, oh,
                      ow, o.depth, o.f16 ? 1 : 0, o.labels, o.inst, o.flow, o.flow ? o.valid : nullptr, mask, v.cal_src, v.env_cal, v.n_cal);

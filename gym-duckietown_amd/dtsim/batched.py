@@ -1016,9 +1016,7 @@ class BatchedSimulator:
         `flow_valid` needs `flow`.  Returns a dict of the outputs that are on.  `depth_dtype`, the size and `mask` as depth()'s; labels install
         the default tables at first use, as labels() does; flow refuses what flow() refuses (per-env calibrations, undistort=True) and needs a
         flow_mark() on this simulator first (an env without a mark of its episode gets zeros, as in flow()).  Needs a preceding render() of the
-        current state.  With mesh objects in view after a second render from another pose, depth, labels and instances follow flow()'s
-        triangle test (a triangle the pass culled is skipped), where the single passes can still see its stale record.  A bad argument raises
-        ValueError before anything is launched."""
+        current state.  Every output is its single method's, byte for byte.  A bad argument raises ValueError before anything is launched."""
         if depth_dtype not in self._DEPTH_DTYPES:
             raise ValueError(f"camera_maps: depth_dtype {depth_dtype!r}: 'float32' or 'float16'")
         h, w = self._map_size("camera_maps", "the maps are", height, width)

@@ -107,8 +107,7 @@ One launch for the camera maps (`fused_maps=True`, opt-in): those of `depth_shap
 set must be equal, and at least one must be set (else ValueError, before a device is touched).  Every place above where the depth, label,
 instance and flow passes stand then holds ONE `BatchedSimulator.camera_maps` call (`dtsim_camera_maps`, include/dtsim.h), which classifies
 each pixel once and writes all of them; boxes, bev and ipm follow as before.  The outputs are the same quantities in the same tensors, and
-everything composes as without the option; with mesh objects in view the depth, label and instance bytes can differ from the single
-passes' on the few pixels where those still see a culled triangle's stale record (profiles/camera_maps_parity.txt).  With
+everything composes as without the option, byte for byte (tests/test_gpu_rerender_maps.py drives both past mesh objects).  With
 `fused_maps=False` (the default) the env makes the calls above, call for call.
 """
 from __future__ import annotations

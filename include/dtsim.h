@@ -756,7 +756,7 @@ int dtsim_flow_masked(dtsim_t* h, float* flow, uint8_t* valid, int oh, int ow, u
  * DTSIM_DEPTH_F16), labels: dtsim_labels', instances: dtsim_instances', flow / flow_valid: dtsim_flow's -- and all come from ONE classification
  * of the pixel: the sample with the smallest eye depth, ties to the lowest index, sky counting as +inf.  So where instances is o + 1, labels is
  * the class of object o's mesh; depth is the depth of the sample that owns labels and instances; flow is the motion of that sample's surface
- * point.  The triangles are tested as dtsim_flow tests them (the boxes of the pass itself: a triangle the pass culled is skipped).
+ * point.  The triangles are tested as every single pass tests them (the boxes of the render pass itself: a triangle it culled is skipped).
  * SIZE.  dtsim_depth's, one (oh, ow) for all outputs; the shapes are those of the single entry points.  flags: DTSIM_DEPTH_F16 and
  * DTSIM_MAP_ENV_TABLES (dtsim_depth's PER-ENV TABLES), nothing else.
  * STATE.  dtsim_depth's rules; labels needs dtsim_set_label_assets; with flow also dtsim_flow's rules: a fisheye handle needs

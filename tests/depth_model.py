@@ -172,8 +172,14 @@ def _scene(map_name, asset_tree):
     return _town()[0] if asset_tree else fp.scene(map_name)
 
 
+def case_of(ref):
+    """The Case a model function is asked about: a name of CASES, or a Case of the caller's own (tests/rerender_model.py keeps its cases out
+    of CASES, whose members test_depth_model_host.py derives the tolerance over).  A Case is hashable, so the caches below take either."""
+    return ref if isinstance(ref, Case) else CASES[ref]
+
+
 def scene_of(case_name):
-    return _scene(CASES[case_name].map_name, CASES[case_name].asset_tree)
+    return _scene(case_of(case_name).map_name, case_of(case_name).asset_tree)
 
 
 def _cases():
@@ -231,7 +237,7 @@ def host_objects(case_name):
     """Per env the oracle's object states (frame_parity.obj_states' form) after the case's steps, from the oracle's own physics: every env
     starts from the map's object poses, the walking duckies' wait shortened to case.wait, and stands still (zero actions)."""
     import copy
-    case, sc = CASES[case_name], scene_of(case_name)
+    case, sc = case_of(case_name), scene_of(case_name)
     if not sc.m.objects:
         return tuple(None for _ in case.states)
     if case.steps == 0:                              # nothing has moved: the map's own poses
@@ -268,7 +274,7 @@ def host_camera(case, e, nudge=False):
 @functools.lru_cache(maxsize=None)
 def host_buffers(case_name, e, nudge=False):
     """(depths [4, H, W], surfaces [4, H, W]) of env e of the case on the oracle alone; cached and read-only."""
-    case = CASES[case_name]
+    case = case_of(case_name)
     cam = host_camera(case, e, nudge)
     depths, ids = oracle_buffers(cam, scene_of(case_name), host_objects(case_name)[e])
     srf = surfaces(cam, depths, ids)

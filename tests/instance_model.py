@@ -67,10 +67,17 @@ MODEL_CASES = tuple(n for n in CASES if not n.startswith("two_"))          # the
 CROWD_CASES = tuple("crowd_" + v for v in CROWD_VIEWS)
 
 
+def case_of(name):
+    """A name of CASES, or a dm.Case of the caller's own (dm.case_of), in this module's form."""
+    if isinstance(name, dm.Case):
+        return Case(name.W, name.H, len(name.states), name.cap, dm_case=name, dm_name=name)
+    return CASES[name]
+
+
 @functools.lru_cache(maxsize=None)
 def host_buffers(name, e, nudge=False):
     """(depths [4, H, W], surfaces [4, H, W]) of env e of the case, on the oracle alone; cached, read-only."""
-    c = CASES[name]
+    c = case_of(name)
     if c.dm_name is not None:
         return dm.host_buffers(c.dm_name, e, nudge)
     if c.view is not None:
@@ -95,7 +102,7 @@ def instances_of(depths, srf):
 def expected(name, e, kind=None, nudge=False):
     """(instances [H, W] uint8, sure [H, W] bool) of env e of the case: full size, through the source map `kind` (None / "fisheye" /
     "undistort") by nearest source pixel with id 0 -- and sure -- where a pixel has no source.  Cached, read-only."""
-    c = CASES[name]
+    c = case_of(name)
     d0, s0 = host_buffers(name, e, False)
     d1, s1 = host_buffers(name, e, True)
     inst = instances_of(d1, s1) if nudge else instances_of(d0, s0)

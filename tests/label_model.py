@@ -42,14 +42,19 @@ CASES["marks_town"] = dm.Case("test_town", dm.W, dm.H, True, tuple(p + LOW_CAM f
 OWN = tuple(n for n in CASES if n not in dm.CASES)
 
 
+def case_of(name):
+    """A name of CASES, or a dm.Case of the caller's own (dm.case_of)."""
+    return name if isinstance(name, dm.Case) else CASES[name]
+
+
 def scene_of(name):
-    return dm._scene(CASES[name].map_name, CASES[name].asset_tree)
+    return dm._scene(case_of(name).map_name, case_of(name).asset_tree)
 
 
 @functools.lru_cache(maxsize=None)
 def host_buffers(name, e, nudge=False):
     """dm.host_buffers for every case of CASES: (depths [4, H, W], surfaces [4, H, W]) of env e on the oracle alone; read-only."""
-    if name in dm.CASES:
+    if isinstance(name, dm.Case) or name in dm.CASES:
         return dm.host_buffers(name, e, nudge)
     case, sc = CASES[name], scene_of(name)
     assert case.steps == 0
@@ -67,7 +72,7 @@ def host_buffers(name, e, nudge=False):
 def host_tables(name):
     """(tile kind -> [h, w] uint8 classes of its texture, [n_objects] class of every map object) of the case's scene: dtsim/labels.py's
     defaults, built as BatchedSimulator.label_assets() builds them."""
-    case, sc = CASES[name], scene_of(name)
+    case, sc = case_of(name), scene_of(name)
     lib = assets.AssetLibrary(fp.ASSETS) if case.asset_tree else assets.AssetLibrary(None)
     tiles = {}
     for kd, tex in sc.textures.items():
@@ -129,10 +134,15 @@ def world_hit(cam, depth, tile, q):
 def sample_classes(name, e, nudge=False, tables=None):
     """(cls [4, H, W] the class of every sample's surface, same [4, H, W] bool: the 3 x 3 texel neighbourhood of a tile sample holds one
     class; True for the other surfaces).  tables: (tile kind -> classes, object -> class) in place of host_tables(name)."""
-    case, sc = CASES[name], scene_of(name)
-    tiles, obj_cls = host_tables(name) if tables is None else tables
-    cam = dm.host_camera(case, e, nudge)
+    case, sc = case_of(name), scene_of(name)
     depths, srf = host_buffers(name, e, nudge)
+    return sample_classes_of(dm.host_camera(case, e, nudge), sc, host_tables(name) if tables is None else tables, depths, srf)
+
+
+def sample_classes_of(cam, sc, tables, depths, srf):
+    """sample_classes' rule on any camera, scene, tables (tile kind -> classes, object -> class) and per-sample (depths, surfaces): a state read
+    back from a device has no case."""
+    tiles, obj_cls = tables
     cls = np.empty(srf.shape, np.int64)
     same = np.ones(srf.shape, bool)
     texel = sc.m.tile_size / max(t.shape[0] for t in tiles.values())
@@ -165,7 +175,7 @@ def expected(name, e, kind=None, nudge=False):
 
 def expected_with(name, e, kind=None, nudge=False, tables=None):
     """expected() under a user's tables (sample_classes' `tables`); not cached."""
-    case = CASES[name]
+    case = case_of(name)
     d0, s0 = host_buffers(name, e, False)
     d1, s1 = host_buffers(name, e, True)
     c0, same0 = sample_classes(name, e, False, tables)

@@ -1,6 +1,6 @@
-"""Time of the fused camera-map launch WITHOUT flow (dtsim_camera_maps with depth, labels and instances: k_camera_maps<false, CAL, TBOX>) on one
-rendered batch, under the single fisheye table (CAL = false) and under camera_rand's per-env tables (CAMERA_RAND=1: CAL = true); TBOX is
-whether the map has mesh objects.  tools/time_camera_maps.py times the launch with flow.  Device events around REPS back-to-back calls on
+"""Time of the fused camera-map launch WITHOUT flow (dtsim_camera_maps with depth, labels and instances: k_camera_maps<false, CAL>) on one
+rendered batch, under the single fisheye table (CAL = false) and under camera_rand's per-env tables (CAMERA_RAND=1: CAL = true).
+tools/time_camera_maps.py times the launch with flow.  Device events around REPS back-to-back calls on
 the handle's stream, after a warm-up, over ROUNDS rounds; the median round and the spread (min .. max).
 N=4096 MAP=small_loop W=640 H=480, maps at H / 4 x W / 4; MAP=loop_pedestrians for the triangle loop (STEPS zero-action steps first)."""
 import os, sys
